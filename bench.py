@@ -1,14 +1,19 @@
 #!/usr/bin/env python3
 """Headline benchmark: MS/s of CF32 input through the 256-channel PFB + FM chain on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 One step = one pass of the hot path over one batch of synthetic CF32 that is already
 resident in HBM: dcBlocker -> NCO pre-mix -> firpfbch(256, m=7, 80 dB) -> per-channel
 freqdem(kf) -> channel-major F32 [256][nf]  (BASELINE.json configs[2] with `-a 0`, the
-reference's own "no AGC" setting, apps/SoapySDR.hs:195-198; the AGC-enabled variant is
-measured beside it and reported under "agc_variant" -- see DESIGN.md section 6).
+reference's own "no AGC" setting, apps/SoapySDR.hs:195-198).
+
+A plain run does what the headline needs: set up, pre-heat, W warm-up steps, the K timed
+steps, the outputs of the last timed step (--dump-outputs), the JSON line.  --full adds the
+side measurements (cold window, sustained runs with board power, the roofline's own launch
+passes, the AGC-enabled variant "agc_variant", the other BASELINE shapes, the CPU baseline,
+the N > 1 channel-shard / hybrid partitions) -- see DESIGN.md section 6.
 
 Multi-GPU (--gpus N): one process per GPU; every rank runs the chain on its own time
 stripe of the stream (no data-path collective: FM/DeNo outputs of a stripe depend only
@@ -60,8 +65,36 @@ def parse():
                          "reported as `sustained_long` (with the board's sclk / socket power sampled from rocm-smi meanwhile) and at the same "
                          "time what brings the board into the power state a long stream sees (the cap's averaging window is hundreds of ms: "
                          "profiles/r03_short_run_preheat.txt), so that the K timed steps behind it measure THAT state; 0 = off "
-                         "(the K-step figure from an idle board is always reported as `cold_window`)")
+                         "(the K-step figure from an idle board is reported as `cold_window` under --full)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the side measurements (cold window, sustained runs, roofline launch passes, agc_variant, other_configs, "
+                         "cpu_baseline, the N > 1 channel_shard / hybrid partitions); the --no-* options above apply to them")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/output.npy (float32; [..., 2] = re, im for CF32): the whole "
+                         "output up to 64 MB, else a fixed seeded sample of it (sorted flat positions).  The timed steps start from a "
+                         "fresh stream state, so equal arguments give equal outputs from run to run")
     return ap.parse_args()
+
+
+DUMP_MAX_BYTES = 64_000_000
+DUMP_SAMPLE = 1 << 22          # elements of a sampled output (16 MB of F32, 32 MB of CF32)
+DUMP_SEED = 20260101
+
+
+def output_sample(out, shape, comp):
+    """Host copy of the chain's output in `out` (device F32 buffer; `shape` elements of `comp` floats each, comp = 2 for CF32):
+    all of it when it fits DUMP_MAX_BYTES, else the elements at DUMP_SAMPLE seeded random flat positions, in ascending order."""
+    import numpy as np
+    import torch
+    n = int(np.prod(shape))
+    flat = out[: n * comp].view(n, comp)
+    if n * comp * 4 <= DUMP_MAX_BYTES:
+        a = flat.cpu().numpy().reshape(tuple(shape) + ((comp,) if comp > 1 else ()))
+    else:
+        idx = np.unique(np.random.default_rng(DUMP_SEED).integers(0, n, DUMP_SAMPLE))
+        a = flat.index_select(0, torch.from_numpy(idx).to(out.device)).cpu().numpy()
+        a = a if comp > 1 else a.reshape(-1)
+    return np.ascontiguousarray(a, dtype=np.float32)
 
 
 def physical_cores():
@@ -270,10 +303,12 @@ def main():
         chain.seek_frames(rank * a.steps * nf)      # rank r's stripe of one long stream
     stream = torch.cuda.current_stream().cuda_stream
     xv = [x.view(-1) for x in xs]
-    # second handle for the per-launch kernel timing pass behind the timed region (created now: allocations between the two
+    # --full: second handle for the per-launch kernel timing pass behind the timed region (created now: allocations between the two
     # would be an idle gap)
-    kch = cs.Chain(channels=M, demod=a.demod, kf=a.kf, agc=a.agc, mix=a.mix, max_frames=nf, device=local, flags=_lib.FLAG_QUIET | _lib.FLAG_TIME_KERNELS,
-                   chan_first=(rank if chan and world > 1 else (a.chan_first if per_rank else 0)), chan_stride=(world if chan and world > 1 else per_rank))
+    kch = None
+    if a.full:
+        kch = cs.Chain(channels=M, demod=a.demod, kf=a.kf, agc=a.agc, mix=a.mix, max_frames=nf, device=local, flags=_lib.FLAG_QUIET | _lib.FLAG_TIME_KERNELS,
+                       chan_first=(rank if chan and world > 1 else (a.chan_first if per_rank else 0)), chan_stride=(world if chan and world > 1 else per_rank))
 
     def step(i):
         if chan and a.mix:
@@ -303,9 +338,9 @@ def main():
         return d, chain.kernel_time()
 
     # channel shards work on ONE stream: the chunk has to reach every rank (8 B per input sample over xGMI).  The bench synthesises
-    # the identical chunk on every rank, so the broadcast is timed here once, on its own (csdr_comm_broadcast = ncclBroadcast)
+    # the identical chunk on every rank, so the broadcast is timed here once, on its own (csdr_comm_broadcast = ncclBroadcast; --full)
     bcast = None
-    if chan and comm is not None:
+    if a.full and chan and comm is not None:
         barrier()
         for r in range(3):
             if r == 1:
@@ -316,18 +351,23 @@ def main():
         bcast = {"ms": round(tbc * 1e3, 4), "bytes": nx * 8, "gb_per_s": round(nx * 8 / tbc / 1e9, 1), "ranks": world,
                  "note": "csdr_comm_broadcast (ncclBroadcast) of one step's input from rank 0, timed alone; not inside `value` "
                          "(every rank synthesises the same chunk)"}
-    # (0) the contract's W + K steps on an idle board: reported as `cold_window`, never `value`
+    # (0) --full: the contract's W + K steps on an idle board, reported as `cold_window`, never `value`; a plain run only times a few
+    # untimed steps for the pre-heat's first estimate of a step
     barrier()
-    dt_cold, _ = timed(a.steps, a.warmup)
+    if a.full:
+        dt_cold, _ = timed(a.steps, a.warmup)
+        est = dt_cold / a.steps
+    elif a.preheat_ms > 0:
+        est = timed(3, 1)[0] / 3
     # (1) >= preheat_ms of back-to-back steps, one synchronisation at the end: `sustained_long`, and the state `value` is measured in
     preheat_steps, sus_long, smi = 0, None, None
     kms_l, klaunches_l = 0.0, 0
     if a.preheat_ms > 0:
-        est = max(dt_cold / a.steps, 1e-5)
+        est = max(est, 1e-5)
         preheat_steps = max(10, int(a.preheat_ms * 1e-3 / est) + 1)
         # (under rocprofv3 the preloaded tool has initialised the GPU in this process: the pool refuses a child that execs, which rocm-smi does)
-        smi = SmiSampler(local) if rank == 0 and "rocprof" not in os.environ.get("LD_PRELOAD", "") else None
-        for attempt in range(4):                # the estimate comes from a K-step window: re-run longer until the run lasts preheat_ms
+        smi = SmiSampler(local) if a.full and rank == 0 and "rocprof" not in os.environ.get("LD_PRELOAD", "") else None
+        for attempt in range(4):                # the estimate comes from a short window: re-run longer until the run lasts preheat_ms
             if use_dist:                        # every rank the SAME number of steps (a step may contain a collective)
                 t = torch.tensor([preheat_steps], dtype=torch.int64, device=dev)
                 dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -355,11 +395,21 @@ def main():
         sus_long = {"steps": preheat_steps, "seconds": round(t_b - t_a, 3), "ms_per_step": round(d_l * 1e3, 4),
                     "value": round(nx * (1 if chan else world) / d_l / 1e6, 1), "unit": "MS/s",
                     "launch_ms_events": round(kms_l / klaunches_l, 4) if klaunches_l else None, "launches": klaunches_l}
-    # (2) the contract: W warm-up steps, then EXACTLY K timed steps between barrier + synchronize
+    # (2) the contract: W warm-up steps, then EXACTLY K timed steps between barrier + synchronize.  The handle starts them from the
+    # state it was created in (the pre-heat's step count varies from run to run), so that the last timed step computes the same
+    # output in every run with the same arguments (--dump-outputs)
+    if chan:
+        chain.reset()
+    else:
+        chain.seek_frames(rank * a.steps * nf)
     dt, (kname_r, kms_r, klaunches_r) = timed(a.steps, a.warmup)
-    # (3) the same step over 400 further launches (`sustained`), still back to back
+    dump = None
+    if a.dump_outputs and rank == 0:
+        comp = out_elem // 4                    # F32 (FM) or CF32
+        dump = {"output": output_sample(out, chain.out_shape(nx), comp)}
+    # (3) --full: the same step over 400 further launches (`sustained`), still back to back
     d_s = None
-    if world == 1:
+    if a.full and world == 1:
         n_sus = 400
         t_s = time.perf_counter()
         for i in range(n_sus):
@@ -367,24 +417,26 @@ def main():
         torch.cuda.synchronize()
         d_s = (time.perf_counter() - t_s) / n_sus
 
-    # the dominant kernel's own launch duration: a separate pass of K launches with a hipEvent pair around every launch, on the
+    # --full: the dominant kernel's own launch duration: a separate pass of K launches with a hipEvent pair around every launch, on the
     # launch stream, right behind the timed region (same board state); what rocprofv3's average for the kernel must agree with.
-    # Every rank runs it (no collective inside), rank 0 reports its own.
-    for i in range(max(a.warmup, 2)):
-        kch.process_device(xs[i & 1].data_ptr(), nx, out.data_ptr(), stream)
-    torch.cuda.synchronize()
-    kch.kernel_time()
-    for i in range(a.steps):
-        kch.process_device(xs[i & 1].data_ptr(), nx, out.data_ptr(), stream)
-    torch.cuda.synchronize()
-    kname, kms, klaunches = kch.kernel_time()
-    kch.close()
+    # Every rank runs it (no collective inside), rank 0 reports its own.  A plain run names the kernel its timed region launched.
+    kname, kms, klaunches = kname_r, 0.0, 0
+    if a.full:
+        for i in range(max(a.warmup, 2)):
+            kch.process_device(xs[i & 1].data_ptr(), nx, out.data_ptr(), stream)
+        torch.cuda.synchronize()
+        kch.kernel_time()
+        for i in range(a.steps):
+            kch.process_device(xs[i & 1].data_ptr(), nx, out.data_ptr(), stream)
+        torch.cuda.synchronize()
+        kname, kms, klaunches = kch.kernel_time()
+        kch.close()
     if sus_long is not None and smi is not None:
         # samples from 0.5 s into the long run (the power state has settled) to its end
         sus_long["board"] = smi.finish(t_a - smi.t0 + min(0.5, 0.25 * (t_b - t_a)), t_b - smi.t0)
 
-    # ---- side measurements of the N > 1 run (north_star's channel partition, the hybrid partition): behind the contract's numbers,
-    # under a watchdog.  They are the only part of a default run that issues data-path collectives (csdr_comm / RCCL), and no N > 1
+    # ---- --full: side measurements of the N > 1 run (north_star's channel partition, the hybrid partition): behind the contract's numbers,
+    # under a watchdog.  They are the only part of a --full run that issues data-path collectives (csdr_comm / RCCL), and no N > 1
     # hardware was available to try them on: if one of them raises or does not come back within CSDR_BENCH_SIDE_TIMEOUT seconds, the
     # line is printed without them ("side_error") and every rank leaves with status 0.
     chan2, hyb = None, None
@@ -525,38 +577,6 @@ def main():
         if per_rank:
             # one rank of a channel-shard run: the whole stream in, its 1 / G of the rows out (--mix: its partial mix, what the all-reduce sums)
             alg_bytes_per_sample = 8 + (out_elem / M if a.mix else out_elem / per_rank)
-        kavg_ms = kms / max(klaunches, 1)
-        achieved_pairs = (nx * alg_bytes_per_sample) / (kavg_ms * 1e-3) / 1e9 if klaunches else None
-        kreg_ms = kms_r / max(klaunches_r, 1)
-        # `roofline.achieved` / `frac` are what a STREAM sees: the launch cadence of the dominant kernel (+ its correction kernel) over the long
-        # back-to-back run (`sustained_long`: >= preheat_ms at the board's power cap), from one hipEvent in front of that run's first launch
-        # and one behind its last on the launch stream.  The K-step window behind a barrier (`frac_k_step_window`) and the K event-paired
-        # launches (`frac_event_pairs`) run 2-3 % faster -- the board has just idled for the barrier -- and are reported beside it.
-        ksus_ms = kms_l / klaunches_l if klaunches_l else None
-        roof_ms = ksus_ms if ksus_ms else kavg_ms
-        achieved = (nx * alg_bytes_per_sample) / (roof_ms * 1e-3) / 1e9 if (ksus_ms or klaunches) else None
-        # HBM bytes per launch from the committed PMC passes of this very configuration (tools/profile_all.sh +
-        # tools/collect_all.sh: FETCH_SIZE x 2 + WRITE_SIZE, separate --pmc runs); null when it has not been profiled
-        tj = {}
-        tfile = os.path.join(ROOT, "profiles", "traffic.json")
-        if os.path.exists(tfile):
-            try:
-                tj = json.load(open(tfile))
-            except Exception:
-                tj = {}
-
-        # a traffic.json entry is only as good as the kernels it was counted on: every entry carries the hash of the kernel sources
-        # (csrc/*.hip, *.h) it was collected with (tools/collect_profile.py); a different hash today -> traffic is reported as null
-        src_sha = kernel_sources_sha16()
-        stale = []
-
-        def traffic_of(kernel):
-            e = tj.get(f"{kernel}|M={M}|nf={nf}", {})
-            if e and e.get("src_sha16") != src_sha:
-                stale.append(kernel)
-                return None
-            return e.get("hbm_bytes_per_launch")
-        traffic = traffic_of(kname)
         cfg_name = {(64, "none", False): "cfg2", (256, "fm", False): "cfg3", (1024, "fm", False): "cfg4 shape (one GPU)" if world == 1 else "cfg4",
                     (4096, "none", True): "cfg5 shape (one GPU)" if world == 1 else "cfg5"}.get((M, a.demod, bool(a.mix)), "custom")
         if per_rank:
@@ -587,25 +607,58 @@ def main():
                                           if (chan and a.mix) else None),
                        "rccl_ranks": (comm.world if comm is not None else (dist.get_world_size() if use_dist else 1))},
             "hbm_roofline_frac_whole_step": round(value * 1e6 * alg_bytes_per_sample / 1e9 / (HBM_PEAK_GBS * (1 if chan else world)), 4),
-            "roofline": {"bound": "hbm", "kernel": kname, "achieved": round(achieved, 1) if achieved else None,
-                         "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4) if achieved else None,
-                         "frac_of_measured_copy_ceiling": round(achieved / HBM_COPY_GBS, 4) if achieved else None,
-                         "traffic": traffic, "launch_ms": round(roof_ms, 4), "launches": klaunches_l if ksus_ms else klaunches,
-                         "launch_ms_source": ("hipEvents around the sustained_long run's launches on the launch stream (region / launches): the steady state at the power cap"
-                                              if ksus_ms else "hipEvent pairs around K launches (no sustained run: --preheat-ms 0)"),
-                         "launch_ms_event_pairs": round(kavg_ms, 4), "launches_event_pairs": klaunches,
-                         "frac_event_pairs": round(achieved_pairs / HBM_PEAK_GBS, 4) if achieved_pairs else None,
-                         "traffic_source": ("profiles/traffic.json: rocprofv3 --pmc passes of this configuration (FETCH_SIZE x 2 + WRITE_SIZE per launch, "
-                                            "tools/profile_all.sh + tools/collect_all.sh), not re-measured in this run; kernel sources unchanged since "
-                                            f"(src_sha16 {src_sha})") if not stale else
-                                           f"null: profiles/traffic.json was collected on other kernel sources than today's (src_sha16 {src_sha}); re-run tools/profile_all.sh",
-                         "launch_ms_k_step_window": round(kreg_ms, 4) if klaunches_r else None,
-                         "frac_k_step_window": round(nx * alg_bytes_per_sample / (kreg_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4) if klaunches_r else None,
-                         "alg_bytes_per_sample": alg_bytes_per_sample, "samples_per_launch": nx},
-            "cold_window": {"steps": a.steps, "warmup": a.warmup, "ms_per_step": round(dt_cold / a.steps * 1e3, 4),
-                            "value": round(total_samples / dt_cold / 1e6, 1), "unit": "MS/s",
-                            "note": "the same W + K steps started on an idle board (no pre-heat): inside the board's power transient"},
         }
+        if a.full:
+            kavg_ms = kms / max(klaunches, 1)
+            achieved_pairs = (nx * alg_bytes_per_sample) / (kavg_ms * 1e-3) / 1e9 if klaunches else None
+            kreg_ms = kms_r / max(klaunches_r, 1)
+            # `roofline.achieved` / `frac` are what a STREAM sees: the launch cadence of the dominant kernel (+ its correction kernel) over the long
+            # back-to-back run (`sustained_long`: >= preheat_ms at the board's power cap), from one hipEvent in front of that run's first launch
+            # and one behind its last on the launch stream.  The K-step window behind a barrier (`frac_k_step_window`) and the K event-paired
+            # launches (`frac_event_pairs`) run 2-3 % faster -- the board has just idled for the barrier -- and are reported beside it.
+            ksus_ms = kms_l / klaunches_l if klaunches_l else None
+            roof_ms = ksus_ms if ksus_ms else kavg_ms
+            achieved = (nx * alg_bytes_per_sample) / (roof_ms * 1e-3) / 1e9 if (ksus_ms or klaunches) else None
+            # HBM bytes per launch from the committed PMC passes of this very configuration (tools/profile_all.sh +
+            # tools/collect_all.sh: FETCH_SIZE x 2 + WRITE_SIZE, separate --pmc runs); null when it has not been profiled
+            tj = {}
+            tfile = os.path.join(ROOT, "profiles", "traffic.json")
+            if os.path.exists(tfile):
+                try:
+                    tj = json.load(open(tfile))
+                except Exception:
+                    tj = {}
+
+            # a traffic.json entry is only as good as the kernels it was counted on: every entry carries the hash of the kernel sources
+            # (csrc/*.hip, *.h) it was collected with (tools/collect_profile.py); a different hash today -> traffic is reported as null
+            src_sha = kernel_sources_sha16()
+            stale = []
+
+            def traffic_of(kernel):
+                e = tj.get(f"{kernel}|M={M}|nf={nf}", {})
+                if e and e.get("src_sha16") != src_sha:
+                    stale.append(kernel)
+                    return None
+                return e.get("hbm_bytes_per_launch")
+            traffic = traffic_of(kname)
+            res["roofline"] = {"bound": "hbm", "kernel": kname, "achieved": round(achieved, 1) if achieved else None,
+                               "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4) if achieved else None,
+                               "frac_of_measured_copy_ceiling": round(achieved / HBM_COPY_GBS, 4) if achieved else None,
+                               "traffic": traffic, "launch_ms": round(roof_ms, 4), "launches": klaunches_l if ksus_ms else klaunches,
+                               "launch_ms_source": ("hipEvents around the sustained_long run's launches on the launch stream (region / launches): the steady state at the power cap"
+                                                    if ksus_ms else "hipEvent pairs around K launches (no sustained run: --preheat-ms 0)"),
+                               "launch_ms_event_pairs": round(kavg_ms, 4), "launches_event_pairs": klaunches,
+                               "frac_event_pairs": round(achieved_pairs / HBM_PEAK_GBS, 4) if achieved_pairs else None,
+                               "traffic_source": ("profiles/traffic.json: rocprofv3 --pmc passes of this configuration (FETCH_SIZE x 2 + WRITE_SIZE per launch, "
+                                                  "tools/profile_all.sh + tools/collect_all.sh), not re-measured in this run; kernel sources unchanged since "
+                                                  f"(src_sha16 {src_sha})") if not stale else
+                                                 f"null: profiles/traffic.json was collected on other kernel sources than today's (src_sha16 {src_sha}); re-run tools/profile_all.sh",
+                               "launch_ms_k_step_window": round(kreg_ms, 4) if klaunches_r else None,
+                               "frac_k_step_window": round(nx * alg_bytes_per_sample / (kreg_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4) if klaunches_r else None,
+                               "alg_bytes_per_sample": alg_bytes_per_sample, "samples_per_launch": nx}
+            res["cold_window"] = {"steps": a.steps, "warmup": a.warmup, "ms_per_step": round(dt_cold / a.steps * 1e3, 4),
+                                  "value": round(total_samples / dt_cold / 1e6, 1), "unit": "MS/s",
+                                  "note": "the same W + K steps started on an idle board (no pre-heat): inside the board's power transient"}
         if sus_long:
             res["value_sustained"] = sus_long["value"]      # the same metric over the long run: what a stream sees (`value` is the contract's K-step window)
             sus_long["hbm_roofline_frac_whole_step"] = round(sus_long["value"] * 1e6 * alg_bytes_per_sample / 1e9 / (HBM_PEAK_GBS * (1 if chan else world)), 4)
@@ -623,7 +676,7 @@ def main():
         if hyb:
             res["hybrid"] = hyb
             res["value_hybrid"] = hyb["value"]               # SURVEY 8e(B) with the AGC on (weak scaling)
-        if world == 1 and not per_rank and not a.no_agc_variant and a.agc == 0.0 and M == 256 and not a.mix:
+        if a.full and world == 1 and not per_rank and not a.no_agc_variant and a.agc == 0.0 and M == 256 and not a.mix:
             # cfg3 with the AGC on (squelch threshold -a 10 between the tone and the noise channels): the PFB kernel
             # writes channel-major CF32, the time-parallel verified AGC tail (bit-identical to the sequential
             # recurrence) adds squelch + freqdem
@@ -661,7 +714,7 @@ def main():
                                               "traffic": (ta + tb) if (ta and tb) else None}
             ch2.close()
 
-        if world == 1 and not per_rank and not a.no_other_configs and not a.no_agc_variant and a.agc == 0.0 and M == 256 and a.demod == "fm" and not a.mix and nf == 262144:
+        if a.full and world == 1 and not per_rank and not a.no_other_configs and not a.no_agc_variant and a.agc == 0.0 and M == 256 and a.demod == "fm" and not a.mix and nf == 262144:
             # The other BASELINE shapes, each for ~0.5 s on the same (hot) board and the same 67.1 M input samples per step, so that a driver-run line
             # carries them too (verdict r04: "none of cfg2/cfg4/cfg5 figures is driver-run").  Whole-step figures (host clock around a back-to-back
             # loop); the kernels behind them are profiled under profiles/rNN_*.  Not the headline: `value` above is.
@@ -724,17 +777,21 @@ def main():
             res["other_configs"] = others
             del out2
 
-        if world == 1 and not per_rank and not a.no_cpu_baseline:
+        if a.full and world == 1 and not per_rank and not a.no_cpu_baseline:
             x_host = xs[0][: 4096 * M * 4].cpu().numpy().view(np.complex64).reshape(-1)
             res["cpu_baseline"] = cpu_baseline(M, a.demod, a.kf, a.agc, x_host, a.cpu_seconds, a.mix)
         if side_state["error"]:
             res["side_error"] = side_state["error"]
+        if dump is not None:
+            os.makedirs(a.dump_outputs, exist_ok=True)
+            for name, arr in dump.items():
+                np.save(os.path.join(a.dump_outputs, f"{name}.npy"), arr)
         print(json.dumps(res), flush=True)
         if use_dist and not (no_collectives or side_state["error"]):
             dist.barrier()
             dist.destroy_process_group()
 
-    if world > 1:
+    if a.full and world > 1:
         limit = float(os.environ.get("CSDR_BENCH_SIDE_TIMEOUT", "300"))
         threading.Thread(target=watchdog, args=(limit,), daemon=True).start()
         try:

@@ -820,7 +820,7 @@ def test_bench_channel_shard_two_ranks_one_gpu(shard, mix):
     env = dict(os.environ, CSDR_BENCH_ONE_GPU="1", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", "29571", os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--frames", "8192",
-           "--shard", shard, "--demod", "none", "--no-cpu-baseline", "--no-agc-variant", "--preheat-ms", "300"] + (["--mix"] if mix else [])
+           "--shard", shard, "--demod", "none", "--no-cpu-baseline", "--no-agc-variant", "--preheat-ms", "300", "--full"] + (["--mix"] if mix else [])
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=root)
     lines = [l for l in p.stdout.splitlines() if l.startswith('{"metric"')]
     assert p.returncode == 0 and len(lines) == 1, p.stderr[-2000:]
@@ -867,7 +867,7 @@ def test_bench_side_measurements_cannot_cost_the_line():
     env = dict(os.environ, CSDR_BENCH_ONE_GPU="1", MASTER_ADDR="127.0.0.1", CSDR_BENCH_SIDE_TIMEOUT="0.001")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", "29573", os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--frames", "8192",
-           "--demod", "none", "--no-cpu-baseline", "--no-agc-variant", "--preheat-ms", "300"]
+           "--demod", "none", "--no-cpu-baseline", "--no-agc-variant", "--preheat-ms", "300", "--full"]
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=root)
     lines = [l for l in p.stdout.splitlines() if l.startswith('{"metric"')]
     assert p.returncode == 0 and len(lines) == 1, p.stderr[-2000:]
@@ -879,6 +879,47 @@ def test_bench_side_measurements_cannot_cost_the_line():
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=dict(env, CSDR_BENCH_SIDE_STRICT="1"), cwd=root)
     lines = [l for l in p.stdout.splitlines() if l.startswith('{"metric"')]
     assert p.returncode != 0 and len(lines) == 1 and "side_error" in json.loads(lines[0]), p.stderr[-2000:]
+
+
+def test_bench_plain_run_dumps_the_last_timed_step(tmp_path):
+    """A plain bench.py run (no --full) prints the headline fields of exactly K timed steps and none of the side measurements;
+    --dump-outputs writes what the last timed step computed: the same array in two runs, equal to the output of a fresh handle
+    taken through the same W + K steps on the same inputs."""
+    import json
+    import subprocess
+    import sys
+    import torch
+    from synth import synth_cf32_torch
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    M, nf, K, W = 256, 8192, 5, 2
+    runs = []
+    for d in ("a", "b"):
+        cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", str(K), "--warmup", str(W), "--frames", str(nf),
+               "--preheat-ms", "200", "--dump-outputs", str(tmp_path / d)]
+        p = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=root)
+        lines = [l for l in p.stdout.splitlines() if l.startswith('{"metric"')]
+        assert p.returncode == 0 and len(lines) == 1, p.stderr[-2000:]
+        runs.append(json.loads(lines[0]))
+    r = runs[0]
+    assert r["steps"] == K and r["warmup"] == W and r["value"] > 0 and r["ms_per_step"] > 0
+    assert r["unit"] == "MS/s" and r["higher_is_better"] is True and r["dtype"] == "f32" and r["metric"].startswith("MS/s")
+    assert abs(r["value"] - M * nf / r["ms_per_step"] / 1e3) <= 0.02 * r["value"]
+    for k in ("roofline", "cold_window", "sustained", "agc_variant", "other_configs", "cpu_baseline"):
+        assert k not in r, k
+    a, b = (np.load(tmp_path / d / "output.npy") for d in ("a", "b"))
+    assert a.dtype == np.float32 and a.shape == (M, nf)
+    assert np.array_equal(a.view(np.uint32), b.view(np.uint32))
+    dev = torch.device("cuda", 0)
+    xs = [synth_cf32_torch(M * nf, M, dev, seed=20260101 + 7919 * i) for i in range(2)]
+    out = torch.empty(M * nf, dtype=torch.float32, device=dev)
+    from composable_sdr_amd import _lib
+    ch = cs.Chain(channels=M, demod="fm", kf=0.3, max_frames=nf, device=0, flags=_lib.FLAG_QUIET | _lib.FLAG_TIME_KERNELS | _lib.FLAG_TIME_REGION)
+    stream = torch.cuda.current_stream().cuda_stream
+    for i in list(range(W)) + list(range(K)):
+        ch.process_device(xs[i & 1].data_ptr(), M * nf, out.data_ptr(), stream)
+    torch.cuda.synchronize()
+    ch.close()
+    assert np.array_equal(out.cpu().numpy().reshape(M, nf).view(np.uint32), a.view(np.uint32))
 
 
 def test_seek_frames_sets_premix_phase():

@@ -5,7 +5,7 @@ TAG=${1:-sq}; shift || true
 export TMPDIR=/tmp
 OUT=gpurun_out/prof_$TAG
 mkdir -p $OUT
-ARGS="--steps 5 --warmup 1 --no-cpu-baseline --no-agc-variant $*"
+ARGS="--full --steps 5 --warmup 1 --no-cpu-baseline --no-agc-variant $*"
 KRE='k_run256|k_run64'
 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CU_CYCLES SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_SCA SQ_ACTIVE_INST_MISC SQ_ACTIVE_INST_VMEM SQ_ACTIVE_INST_FLAT SQ_THREAD_CYCLES_VALU \
    --kernel-include-regex "$KRE" -f csv -d $OUT/pmc5 -o p -- python3 bench.py $ARGS > $OUT/pmc5.log 2>&1
