@@ -8,11 +8,13 @@ with the DSP behind `compact` done by the fused C-ABI chain.  Sinks are the refe
 `fileSink`s (Sink.hs:29-34): `<out>.cf32` / `<out>_ch<k>.cf32` for DeNo (SoapySDR.hs:240); demodulated audio goes to
 raw `.f32` by default or, with `audio="AU" | "WAV"`, through `audioFileSink` (Sink.hs:41-74: libsndfile float,
 big-endian; written here by hand, see the class).  `--offset` and `-b` are the reference's mixDown/mixUp and
-resampler in front of `takeNArr`."""
+resampler in front of `takeNArr`.  DeFMS (`demod="fms"`, SoapySDR.hs:261-264) skips the DC blocker, `compact` and the
+channelizer: agc -> fmDemodulator 0.8 -> stereoFMDecoder per source chunk into one 2-channel sink."""
 import struct
 import numpy as np
 
-from .pipes import Chain, ChainConfig, compose, idPipe, mixDown, mixUp, resampler, unPipe
+from .pipes import (Chain, ChainConfig, automaticGainControl, compose, fmDemodulator, idPipe, mixDown, mixUp, resampler,
+                    stereoFMDecoder, unPipe)
 from .trans import Fold, compact, takeNArr
 
 
@@ -119,6 +121,8 @@ def sdr_process(filename, channels=1, demod="none", kf=0.3, agc=0.0, mix=False, 
                 outname="output", chunksize=1024, m=4, offset=0.0, samplerate=2.56e6, bandwidth=0.0, decim=4, audio=None):
     """soapy-sdr --filename F -s samplerate -b bandwidth --offset f -c channels --demod ... -a agc [-m]
     -n numsamples -o outname.  Returns the list of files written."""
+    if demod == "fms":
+        return _sdr_process_fms(filename, channels, agc, numsamples, outname, chunksize, offset, samplerate, bandwidth, decim, audio)
     nch = channels
     mixed = bool(mix) and nch > 1
     ext = ".cf32" if demod == "none" else ".f32"
@@ -136,17 +140,8 @@ def sdr_process(filename, channels=1, demod="none", kf=0.3, agc=0.0, mix=False, 
     chain = Chain(ChainConfig(channels=nch, demod=demod, kf=kf, agc=agc, mix=mixed, max_frames=m * 1024, decim=decim,
                               deemph_fc=float(np.float32(5000.0 / out_bw))))
     fold = compact(m * nch * 1024, _FusedFold(chain, sinks, mixed))
-    # prep = takeNArr ns . (resampler . offset)   (SoapySDR.hs:206-207): per source chunk, the --offset mixer first
-    # (f = 2*pi*offset/fs; mixDown f if f > 0, mixUp (-f) if f < 0, :200-205), then the resampler
-    # (rate = bandwidth / samplerate, 60 dB, identity when -b 0, :190-194)
-    f = np.float32(2 * np.pi * offset / samplerate)
-    offset_p = idPipe
-    if f != 0:
-        offset_p = mixDown(float(f), max_samples=chunksize) if f > 0 else mixUp(float(-f), max_samples=chunksize)
-    resamp_p = idPipe
-    if bandwidth != 0:
-        resamp_p = resampler(float(np.float32(bandwidth / samplerate)), 60.0, max_samples=chunksize)
-    process, cleanup = unPipe(compose(resamp_p, offset_p))       # (process, cleanup) <- unPipe (resampler . offset)
+    # prep = takeNArr ns . (resampler . offset)   (SoapySDR.hs:206-207)
+    process, cleanup = unPipe(_prep(offset, samplerate, bandwidth, chunksize))       # (process, cleanup) <- unPipe (resampler . offset)
     try:
         for a in takeNArr(numsamples, process(readFromFile(chunksize, filename))):
             fold.step(a)
@@ -154,3 +149,42 @@ def sdr_process(filename, channels=1, demod="none", kf=0.3, agc=0.0, mix=False, 
         fold.done()
         cleanup()
     return names
+
+
+def _prep(offset, samplerate, bandwidth, chunksize):
+    """resampler . offset (SoapySDR.hs:190-205): per source chunk, the --offset mixer first (f = 2*pi*offset/fs; mixDown f if
+    f > 0, mixUp (-f) if f < 0), then the resampler (rate = bandwidth / samplerate, 60 dB, identity when -b 0)"""
+    f = np.float32(2 * np.pi * offset / samplerate)
+    offset_p = idPipe
+    if f != 0:
+        offset_p = mixDown(float(f), max_samples=chunksize) if f > 0 else mixUp(float(-f), max_samples=chunksize)
+    resamp_p = idPipe
+    if bandwidth != 0:
+        resamp_p = resampler(float(np.float32(bandwidth / samplerate)), 60.0, max_samples=chunksize)
+    return compose(resamp_p, offset_p)
+
+
+def _sdr_process_fms(filename, channels, agc, numsamples, outname, chunksize, offset, samplerate, bandwidth, decim, audio):
+    """DeFMS decim fmt (SoapySDR.hs:261-264): prep src -> agc -> fmDemodulator 0.8 -> stereoFMDecoder outBW decim sink, one call
+    per source chunk: no DC blocker, no compact, no channelizer; -c only divides the sink's rate.  The sink is one 2-channel
+    audioFileSink at round(outBW) div decim div nch Hz (getAudioSink decim fmt 2), or raw interleaved L, R float32 <out>.f32."""
+    out_bw = bandwidth if bandwidth != 0 else samplerate
+    if audio:
+        sink = audioFileSink(audio, int(round(out_bw)) // decim // channels, numsamples, 2, outname)
+        name = sink.path
+    else:
+        name = outname + ".f32"
+        sink = fileSink(name)
+    cap = 4 * chunksize + 16                                      # the resampler's largest output (rate <= 2: 2 ceil(r n))
+    agc_p = automaticGainControl(agc, max_samples=cap) if agc != 0.0 else idPipe
+    dem = compose(stereoFMDecoder(out_bw, decim, max_samples=cap), compose(fmDemodulator(0.8, max_samples=cap), agc_p))
+    process, cleanup = unPipe(_prep(offset, samplerate, bandwidth, chunksize))
+    r = dem._start()
+    try:
+        for a in takeNArr(numsamples, process(readFromFile(chunksize, filename))):
+            sink.step(dem._process(r, a))
+    finally:
+        dem._done(r)
+        sink.done()
+        cleanup()
+    return [name]

@@ -609,6 +609,137 @@ int csdr_ampdem_destroy(csdr_ampdem *h)
 }
 
 // ---------------------------------------------------------------------------
+// stereoFMDecoder quadRate decim (Liquid.chs:959-1078), nchan independent streams
+// ---------------------------------------------------------------------------
+}  // extern "C"
+struct csdr_fmstereo {
+    int device; uint32_t C, max_n, M; FmsDesign f; uint32_t theta = 0; int cur = 0;
+    float *d_hp = nullptr, *d_ha = nullptr, *d_hdec = nullptr, *d_xh[2] = {nullptr, nullptr}, *d_ub[2] = {nullptr, nullptr};
+    float2 *d_p = nullptr, *d_bq = nullptr; float *d_lpr = nullptr, *d_lr = nullptr, *d_dh[2] = {nullptr, nullptr}; uint2 *d_pll = nullptr;
+    float *d_in = nullptr, *d_out = nullptr;
+    hipEvent_t ev[6] = {}; bool timed = false;
+    uint32_t Hx() const { return f.N - 1 + f.d; }
+    uint32_t ustride() const { return f.N - 1 + max_n; }
+};
+static int fms_init_state(csdr_fmstereo *h)
+{
+    const uint32_t C = h->C, Hd = (uint32_t)h->f.h_dec.size() - 1;
+    for (int i = 0; i < 2; i++) {
+        CSDR_HIP(hipMemset(h->d_xh[i], 0, sizeof(float) * (size_t)C * h->Hx()));
+        CSDR_HIP(hipMemset(h->d_ub[i], 0, sizeof(float) * (size_t)C * h->ustride()));
+        CSDR_HIP(hipMemset(h->d_dh[i], 0, sizeof(float) * (size_t)2 * C * Hd));
+    }
+    CSDR_HIP(hipMemset(h->d_bq, 0, sizeof(float2) * 2 * (size_t)C));
+    std::vector<uint2> pll(C, make_uint2(0u, h->f.d_nco));           // ncoPE: theta 0, d_theta = constrain(ncoF)
+    CSDR_HIP(hipMemcpy(h->d_pll, pll.data(), sizeof(uint2) * C, hipMemcpyHostToDevice));
+    h->theta = 0; h->cur = 0;
+    return 0;
+}
+extern "C" {
+int csdr_fmstereo_destroy(csdr_fmstereo *h)
+{
+    if (!h) return CSDR_OK;
+    DevGuard guard(h->device);
+    (void)hipDeviceSynchronize();
+    void *ptrs[] = {h->d_hp, h->d_ha, h->d_hdec, h->d_xh[0], h->d_xh[1], h->d_ub[0], h->d_ub[1], h->d_p, h->d_bq, h->d_lpr, h->d_lr,
+                    h->d_dh[0], h->d_dh[1], h->d_pll, h->d_in, h->d_out};
+    for (void *p : ptrs) if (p) (void)hipFree(p);
+    for (hipEvent_t e : h->ev) if (e) (void)hipEventDestroy(e);
+    delete h;
+    return CSDR_OK;
+}
+int csdr_fmstereo_create(float quad_rate, uint32_t decim, uint32_t nchan, uint32_t max_samples, csdr_fmstereo **out)
+{
+    if (!out || !nchan || decim < 1 || decim > 4096 || !(quad_rate >= 40000.f && quad_rate <= 2.7e6f)) {
+        set_error("fmstereo: bad arguments (quad_rate in [40e3, 2.7e6]: the 19 kHz pilot below Nyquist, FIRs of <= 2000 taps; decim in [1, 4096])");
+        return CSDR_ERR_INVALID;
+    }
+    int dev; int r = check_device(-1, &dev); if (r) return r;
+    csdr_fmstereo *h = new (std::nothrow) csdr_fmstereo();
+    if (!h) return CSDR_ERR_NOMEM;
+    h->device = dev; h->C = nchan; h->max_n = max_samples ? max_samples : 4096; h->M = decim;
+    h->f = design_fmstereo((double)quad_rate, decim);
+    h->timed = diag_env("CSDR_FMS_TIME") != nullptr;           // hipEvents around the five kernels (tools/fms_time.py)
+    const size_t C = nchan, N = h->f.N, Hd = h->f.h_dec.size() - 1, n = h->max_n;
+    auto fail = [&](int rc) { csdr_fmstereo_destroy(h); return rc; };
+    if ((r = dev_alloc(&h->d_hp, N)) || (r = dev_alloc(&h->d_ha, N)) || (r = dev_alloc(&h->d_hdec, h->f.h_dec.size())) ||
+        (r = dev_alloc(&h->d_xh[0], C * h->Hx())) || (r = dev_alloc(&h->d_xh[1], C * h->Hx())) ||
+        (r = dev_alloc(&h->d_ub[0], C * h->ustride())) || (r = dev_alloc(&h->d_ub[1], C * h->ustride())) ||
+        (r = dev_alloc(&h->d_p, C * n)) || (r = dev_alloc(&h->d_lpr, C * n)) || (r = dev_alloc(&h->d_lr, 2 * C * n)) ||
+        (r = dev_alloc(&h->d_bq, 2 * C)) || (r = dev_alloc(&h->d_dh[0], 2 * C * Hd)) || (r = dev_alloc(&h->d_dh[1], 2 * C * Hd)) ||
+        (r = dev_alloc(&h->d_pll, C)) || (r = dev_alloc(&h->d_in, C * n)) || (r = dev_alloc(&h->d_out, 2 * C * (n / decim))))
+        return fail(r);
+    CSDR_HIP_CLEAN(hipMemcpy(h->d_hp, h->f.h_pilot.data(), sizeof(float) * N, hipMemcpyHostToDevice), csdr_fmstereo_destroy(h));
+    CSDR_HIP_CLEAN(hipMemcpy(h->d_ha, h->f.h_audio.data(), sizeof(float) * N, hipMemcpyHostToDevice), csdr_fmstereo_destroy(h));
+    CSDR_HIP_CLEAN(hipMemcpy(h->d_hdec, h->f.h_dec.data(), sizeof(float) * h->f.h_dec.size(), hipMemcpyHostToDevice), csdr_fmstereo_destroy(h));
+    if ((r = fms_init_state(h))) return fail(r);
+    *out = h;
+    return CSDR_OK;
+}
+int csdr_fmstereo_process_device(csdr_fmstereo *h, const void *d_mpx, uint32_t n, void *d_lr, uint32_t *n_out, void *stream)
+{
+    if (!h || !n_out) { set_error("fmstereo: null argument"); return CSDR_ERR_INVALID; }
+    if (n > h->max_n) { set_error("fmstereo: %u samples > max %u", n, h->max_n); return CSDR_ERR_SIZE; }
+    *n_out = h->C * 2 * (n / h->M);
+    if (!n) return CSDR_OK;
+    if (!d_mpx || !d_lr) { set_error("fmstereo: null buffer"); return CSDR_ERR_INVALID; }
+    FmsBufs b{h->d_hp, h->d_ha, h->d_hdec, {h->d_xh[0], h->d_xh[1]}, {h->d_ub[0], h->d_ub[1]}, h->d_p, h->d_lpr, h->d_lr, h->d_pll, h->d_bq,
+              {h->d_dh[0], h->d_dh[1]}};
+    FmsLaunch l{h->C, n, h->f.N, h->f.d, h->M, (uint32_t)h->f.h_dec.size(), h->ustride(), h->theta, h->f.d_nco, h->cur,
+                h->f.scale_pilot, h->f.scale_audio, h->f.alpha, h->f.beta, h->f.bq.b0, h->f.bq.b1, h->f.bq.b2, h->f.bq.a1, h->f.bq.a2};
+    const bool timed = h->timed;
+    if (timed && !h->ev[0])
+        for (hipEvent_t &e : h->ev) CSDR_HIP(hipEventCreate(&e));
+    int r = launch_fmstereo((const float *)d_mpx, (float *)d_lr, b, l, (hipStream_t)stream, timed ? h->ev : nullptr);
+    if (r) return r;
+    h->theta += n * h->f.d_nco;
+    h->cur ^= 1;
+    return CSDR_OK;
+}
+int csdr_fmstereo_process(csdr_fmstereo *h, const float *mpx, uint32_t n, float *lr, uint32_t *n_out)
+{
+    if (!h || !n_out || (n && (!mpx || !lr))) { set_error("fmstereo: null argument"); return CSDR_ERR_INVALID; }
+    if (n > h->max_n) { set_error("fmstereo: %u samples > max %u", n, h->max_n); return CSDR_ERR_SIZE; }
+    *n_out = h->C * 2 * (n / h->M);
+    if (!n) return CSDR_OK;
+    DevGuard guard(h->device);
+    if (!guard.ok) { set_error("fmstereo: cannot select device %d", h->device); return CSDR_ERR_HIP; }
+    CSDR_HIP(hipMemcpy(h->d_in, mpx, sizeof(float) * (size_t)h->C * n, hipMemcpyHostToDevice));
+    int r = csdr_fmstereo_process_device(h, h->d_in, n, h->d_out, n_out, nullptr);
+    if (r) return r;
+    CSDR_HIP(hipMemcpy(lr, h->d_out, sizeof(float) * (size_t)*n_out, hipMemcpyDeviceToHost));
+    return CSDR_OK;
+}
+int csdr_fmstereo_reset(csdr_fmstereo *h)
+{
+    if (!h) return CSDR_ERR_INVALID;
+    DevGuard guard(h->device);
+    CSDR_HIP(hipDeviceSynchronize());
+    return fms_init_state(h);
+}
+uint32_t csdr_fmstereo_get_delay(const csdr_fmstereo *h) { return h ? h->f.d : 0; }
+uint32_t csdr_fmstereo_get_taps_len(const csdr_fmstereo *h) { return h ? h->f.N : 0; }
+int csdr_fmstereo_get_pll(csdr_fmstereo *h, uint32_t chan, uint32_t *theta, uint32_t *d_theta)
+{
+    if (!h || chan >= h->C) { set_error("fmstereo: bad channel"); return CSDR_ERR_INVALID; }
+    DevGuard guard(h->device);
+    uint2 w;
+    CSDR_HIP(hipMemcpy(&w, h->d_pll + chan, sizeof(uint2), hipMemcpyDeviceToHost));
+    if (theta) *theta = w.x;
+    if (d_theta) *d_theta = w.y;
+    return CSDR_OK;
+}
+int csdr_fmstereo_kernel_times(csdr_fmstereo *h, float *us5)
+{
+    if (!h || !us5) return CSDR_ERR_INVALID;
+    if (!h->ev[0]) { set_error("fmstereo: kernel timing needs CSDR_DIAG=1 CSDR_FMS_TIME=1 at create"); return CSDR_ERR_INVALID; }
+    DevGuard guard(h->device);
+    CSDR_HIP(hipEventSynchronize(h->ev[5]));
+    for (int i = 0; i < 5; i++) { float ms = 0.f; CSDR_HIP(hipEventElapsedTime(&ms, h->ev[i], h->ev[i + 1])); us5[i] = 1000.f * ms; }
+    return CSDR_OK;
+}
+
+// ---------------------------------------------------------------------------
 // fused chain
 // ---------------------------------------------------------------------------
 }  // extern "C"

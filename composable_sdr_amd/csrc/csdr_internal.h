@@ -162,6 +162,37 @@ int launch_biquad(const float *X, float *Y, uint32_t C, uint32_t nf, const Biqua
 int launch_firdecim(const float *X, float *out, uint32_t C, uint32_t nf, uint32_t M, const float *h, uint32_t h_len,
                     const float *hist_in, float *hist_out, hipStream_t s);
 
+// ---- stereo FM decoder (kernels_fmstereo.hip; design in design.cpp) ----
+float fir_group_delay(const std::vector<float> &h, float fc);
+struct FmsDesign {
+    uint32_t N = 0, d = 0;                          // taps of every FIR (round(q / 1350)); wire delay round(groupdelay(pilot FIR, 100 / q))
+    std::vector<float> h_pilot, h_audio;            // kaiser(N, 800 / q, 60, 0), kaiser(N, 15000 / q, 60, 0)
+    float scale_pilot = 0.f, scale_audio = 0.f;     // 2 fc of each
+    uint32_t d_nco = 0;                             // constrain(19000 2 pi / q): the mixers' and the PLL's start step
+    float alpha = 0.f, beta = 0.f;                  // PLL gains: 9 / q and sqrtf of it
+    BiquadParams bq;                                // iirFilter 2 (5000 / q) 0 10 10
+    std::vector<float> h_dec;                       // firdecim_rrrf_create_kaiser(decim, 10, 60)
+};
+FmsDesign design_fmstereo(double quad_rate, uint32_t decim);
+struct FmsBufs {
+    const float *hp, *ha, *hdec;                    // taps (device)
+    float *xh[2];                                   // [C][Hx] input history (Hx = N - 1 + d), ping-pong
+    float *ub[2];                                   // [C][ustride] u with N - 1 history samples in front, ping-pong
+    float2 *p;                                      // [C][max_n] pilot branch
+    float *lpr, *lr;                                // [C][max_n] L+R; [2C][max_n] L / R planes
+    uint2 *pll;                                     // [C] (theta, d_theta)
+    float2 *bq;                                     // [2C] de-emphasis state (v1, v2)
+    float *dh[2];                                   // [2C][h_dec - 1] decimator history, ping-pong
+};
+struct FmsLaunch {
+    uint32_t C, n, N, d, M, h_dec_len, ustride, theta0, d_nco; int cur;
+    float scale_pilot, scale_audio, alpha, beta;
+    float b0, b1, b2, a1, a2;
+};
+// mpx [C][n] -> out [C][2 (n / M)] (L, R interleaved); the kernels' hipEvents bracket when ev != nullptr (6 events)
+int launch_fmstereo(const float *mpx, float *out, const FmsBufs &b, const FmsLaunch &l, hipStream_t s, hipEvent_t *ev);
+size_t fms_front_lds(uint32_t N, uint32_t d);
+
 // ---- time-parallel exact AGC [+ freqdem] tail (kernels_agc_tail.hip) ----
 struct AgcTailPlan;
 int agc_tail_create(uint32_t C, uint32_t max_nf, AgcTailPlan **out);

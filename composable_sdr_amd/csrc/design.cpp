@@ -151,6 +151,42 @@ std::vector<float> design_firdecim_kaiser(uint32_t M, uint32_t m, float As)
     return h;
 }
 
+// ---- stereoFMDecoder' quadRate decim (Liquid.chs:985-1078), DESIGN.md 4.9 ----
+// fir_group_delay(h, n, fc) = Re(sum i h[i] e^{j 2 pi fc i} / sum h[i] e^{j 2 pi fc i}), accumulated in f32 (liquid-dsp 1.3.2 as
+// recalled; the complex quotient's real part is taken as (t0 conj(t1)).re / |t1|^2 in f32)
+float fir_group_delay(const std::vector<float> &h, float fc)
+{
+    float t0r = 0.f, t0i = 0.f, t1r = 0.f, t1i = 0.f;
+    for (size_t i = 0; i < h.size(); i++) {
+        const float a = (float)(2.0 * 3.14159265358979323846 * (double)fc * (double)i);
+        const float c = cosf(a), s = sinf(a), hc = h[i] * c, hs = h[i] * s, fi = (float)i;
+        t0r = t0r + hc * fi; t0i = t0i + hs * fi;
+        t1r = t1r + hc; t1i = t1i + hs;
+    }
+    const float num = t0r * t1r + t0i * t1i, den = t1r * t1r + t1i * t1i;
+    return num / den;
+}
+
+FmsDesign design_fmstereo(double quad_rate, uint32_t decim)
+{
+    FmsDesign f;
+    const double pi = 3.14159265358979323846;
+    f.N = (uint32_t)std::nearbyint(quad_rate / 1350.0);                  // Haskell `round` (half-even) of quadRate / 1350
+    const float fc_pilot = (float)(800.0 / quad_rate), fc_audio = (float)(15000.0 / quad_rate);
+    std::vector<double> hp = firdes_kaiser(f.N, (double)fc_pilot, 60.0), ha = firdes_kaiser(f.N, (double)fc_audio, 60.0);
+    f.h_pilot.resize(f.N); f.h_audio.resize(f.N);
+    for (uint32_t i = 0; i < f.N; i++) { f.h_pilot[i] = (float)hp[i]; f.h_audio[i] = (float)ha[i]; }
+    f.scale_pilot = 2.0f * fc_pilot; f.scale_audio = 2.0f * fc_audio;   // firfiltCreateCKaiser: set_scale (2 fc)
+    f.d = (uint32_t)std::nearbyint(fir_group_delay(f.h_pilot, (float)(100.0 / quad_rate)));
+    const float ncoF = (float)(19000.0 * 2.0 * pi / quad_rate);
+    f.d_nco = nco_freq_word(ncoF);
+    f.alpha = (float)(9.0 / quad_rate);                                   // nco_crcf_pll_set_bandwidth: alpha = bw, beta = sqrtf(alpha)
+    f.beta = sqrtf(f.alpha);
+    f.bq = design_butter2_lowpass((float)(5000.0 / quad_rate));
+    f.h_dec = design_firdecim_kaiser(decim, 10, 60.0f);
+    return f;
+}
+
 uint32_t nco_freq_word(float freq)
 {
     float p = (float)((double)freq * 0.159154943091895);   // freq / 2pi, rounded to f32

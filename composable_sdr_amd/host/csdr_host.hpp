@@ -237,6 +237,61 @@ inline Pipe<Array<cf32>, Array<cf32>> ncoMixer(float f, bool up, uint32_t max_in
 inline Pipe<Array<cf32>, Array<cf32>> mixDown(float f, uint32_t max_in) { return ncoMixer(f, false, max_in); }
 inline Pipe<Array<cf32>, Array<cf32>> mixUp(float f, uint32_t max_in) { return ncoMixer(f, true, max_in); }
 
+// ---- DeFMS's per-chunk Pipes (SoapySDR.hs:261-264): automaticGainControl tres (Liquid.chs:727-728), fmDemodulator kf
+// (Liquid.chs:333-334), stereoFMDecoder quadRate decim (Liquid.chs:1069-1078; interleaved L, R out) ----
+inline Pipe<Array<cf32>, Array<cf32>> agcPipe(float tres, uint32_t max_in)
+{
+    Pipe<Array<cf32>, Array<cf32>> p;
+    p.start = [=]() {
+        csdr_agc *h = nullptr;
+        check(csdr_agc_create(tres, 1, max_in, &h));
+        return std::shared_ptr<void>(h, [](void *q) { csdr_agc_destroy(static_cast<csdr_agc *>(q)); });
+    };
+    p.process = [](void *rr, const Array<cf32> &a) {
+        Array<cf32> y(a.size());
+        if (!a.empty())
+            check(csdr_agc_process(static_cast<csdr_agc *>(rr), reinterpret_cast<const float *>(a.data()), (uint32_t)a.size(), reinterpret_cast<float *>(y.data())));
+        return y;
+    };
+    p.done = [](void *) {};
+    return p;
+}
+inline Pipe<Array<cf32>, Array<float>> freqdemPipe(float kf, uint32_t max_in)
+{
+    Pipe<Array<cf32>, Array<float>> p;
+    p.start = [=]() {
+        csdr_freqdem *h = nullptr;
+        check(csdr_freqdem_create(kf, 1, max_in, &h));
+        return std::shared_ptr<void>(h, [](void *q) { csdr_freqdem_destroy(static_cast<csdr_freqdem *>(q)); });
+    };
+    p.process = [](void *rr, const Array<cf32> &a) {
+        Array<float> m(a.size());
+        if (!a.empty())
+            check(csdr_freqdem_process(static_cast<csdr_freqdem *>(rr), reinterpret_cast<const float *>(a.data()), (uint32_t)a.size(), m.data()));
+        return m;
+    };
+    p.done = [](void *) {};
+    return p;
+}
+inline Pipe<Array<float>, Array<float>> fmStereoPipe(float quad_rate, uint32_t decim, uint32_t max_in)
+{
+    Pipe<Array<float>, Array<float>> p;
+    p.start = [=]() {
+        csdr_fmstereo *h = nullptr;
+        check(csdr_fmstereo_create(quad_rate, decim, 1, max_in, &h));
+        return std::shared_ptr<void>(h, [](void *q) { csdr_fmstereo_destroy(static_cast<csdr_fmstereo *>(q)); });
+    };
+    p.process = [decim](void *rr, const Array<float> &a) {
+        Array<float> y(2 * (a.size() / decim));
+        uint32_t n = 0;
+        if (!a.empty()) check(csdr_fmstereo_process(static_cast<csdr_fmstereo *>(rr), a.data(), (uint32_t)a.size(), y.data(), &n));
+        y.resize(n);
+        return y;
+    };
+    p.done = [](void *) {};
+    return p;
+}
+
 // ---- the fused chain as a Pipe (replaces mix . mux (replicate nch demod) . firpfbchChannelizer nc) ----
 struct ChainOpts {
     uint32_t channels = 1; bool dc_block = true; float agc = 0.f; bool fm = false; bool am = false; bool wbfm = false; uint32_t decim = 4; float deemph_fc = 0.025f; float kf = 0.3f; bool mix = false;

@@ -1,5 +1,5 @@
 // soapy-sdr's file-input mode (apps/SoapySDR.hs:181-283) on the C-ABI chain:
-//   soapy_sdr_file --filename in.cf32 -n N -c M [--demod DeNo|DeNBFM kf|DeWBFM decim|DeAM] [-a dB] [-m] [-o output] [--chunksize 1024]
+//   soapy_sdr_file --filename in.cf32 -n N -c M [--demod DeNo|DeNBFM kf|DeWBFM decim|DeFMS decim|DeAM] [-a dB] [-m] [-o output] [--chunksize 1024]
 //                  [-s samplerate] [-b bandwidth] [--offset Hz] [--audio AU|WAV]
 //                  [--world W --rank R --id-file PATH [--id-nonce N] [--device D]]
 // --world W: one process per GPU, each reading the same file; process R owns the channels R, R + W, ... (interleaved channel shard,
@@ -72,12 +72,50 @@ template <class Out> static int run(const std::string &in, const ChainOpts &o, s
     return 0;
 }
 
+// DeFMS decim fmt (SoapySDR.hs:261-264): prep src -> agc -> fmDemodulator 0.8 -> stereoFMDecoder outBW decim sink, one call per
+// source chunk (no DC blocker, no compact, no channelizer; -c only divides the sink's rate); sink: one 2-channel audio file at
+// round(outBW) div decim div nch Hz, or raw interleaved L, R float32 <out>.f32
+static int run_fms(const std::string &in, const ChainOpts &o, size_t n, const std::string &out, size_t chunk)
+{
+    const double bw = g_front.bandwidth != 0.0 ? g_front.bandwidth : g_front.samplerate;
+    std::shared_ptr<Fold<Array<float>>> sink;
+    if (!g_front.audio.empty())
+        sink = std::make_shared<AudioFileSink>(g_front.audio, (uint32_t)std::llround(bw) / o.decim / o.channels, 2u, out);
+    else sink = std::make_shared<FileSink<float>>(out + ".f32");
+    const uint32_t cap = (uint32_t)(4 * chunk + 16);                  // the resampler's largest output (rate <= 2)
+    Pipe<Array<cf32>, Array<cf32>> agc = o.agc != 0.f ? agcPipe(o.agc, cap) : idPipe<Array<cf32>>();
+    auto dem = addPipe(compose(fmStereoPipe((float)bw, o.decim, cap), compose(freqdemPipe(0.8f, cap), agc)), sink);
+    FILE *f = std::fopen(in.c_str(), "rb");
+    if (!f) { std::cerr << "Unable to open source: " << in << "\n"; return 1; }
+    using CPipe = Pipe<Array<cf32>, Array<cf32>>;
+    const float fo = (float)(2.0 * 3.14159265358979323846 * g_front.offset / g_front.samplerate);
+    CPipe offset = fo > 0 ? mixDown(fo, (uint32_t)chunk) : (fo < 0 ? mixUp(-fo, (uint32_t)chunk) : idPipe<Array<cf32>>());
+    CPipe resamp = g_front.bandwidth != 0.0 ? resampler((float)(g_front.bandwidth / g_front.samplerate), 60.0f, (uint32_t)chunk)
+                                            : idPipe<Array<cf32>>();
+    auto prep = unPipe(compose(resamp, offset));
+    TakeN take(n);
+    Array<cf32> a(chunk);
+    while (true) {
+        a.resize(chunk);
+        const size_t got = std::fread(a.data(), sizeof(cf32), chunk, f);
+        if (!got) break;
+        a.resize(got);
+        Array<cf32> b = prep.process(a);
+        if (!take.feed(b)) break;
+        dem->step(b);
+    }
+    std::fclose(f);
+    dem->done();
+    prep.cleanup();
+    return 0;
+}
+
 int main(int argc, char **argv)
 {
     std::string in, out = "output", demod = "DeNo";
     ChainOpts o; o.flags = 0;
     size_t n = 1024, chunk = 1024;
-    std::string id_file; int device = -1; uint64_t id_nonce = 0;
+    std::string id_file; int device = -1; uint64_t id_nonce = 0; bool fms = false;
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
         auto next = [&]() -> const char * { if (i + 1 >= argc) { std::cerr << "missing value for " << a << "\n"; std::exit(2); } return argv[++i]; };
@@ -97,15 +135,18 @@ int main(int argc, char **argv)
         else if (a == "--id-file") id_file = next();
         else if (a == "--id-nonce") id_nonce = std::strtoull(next(), nullptr, 10);
         else if (a == "--device") device = std::atoi(next());
-        else if (a == "--demod") { demod = next(); if (demod == "DeNBFM") { o.fm = true; o.kf = (float)std::atof(next()); } else if (demod == "DeAM") o.am = true; else if (demod == "DeWBFM") { o.wbfm = true; o.decim = (uint32_t)std::atoi(next()); } }
+        else if (a == "--demod") { demod = next(); if (demod == "DeNBFM") { o.fm = true; o.kf = (float)std::atof(next()); } else if (demod == "DeAM") o.am = true; else if (demod == "DeWBFM") { o.wbfm = true; o.decim = (uint32_t)std::atoi(next()); }
+                                     else if (demod == "DeFMS") { fms = true; o.decim = (uint32_t)std::atoi(next()); } }
         else { std::cerr << "unknown option " << a << "\n"; return 2; }
     }
     if (in.empty()) { std::cerr << "--filename is required (SoapySDR live sources are out of scope)\n"; return 2; }
     if (o.world < 1 || o.rank >= o.world) { std::cerr << "--rank must be below --world\n"; return 2; }
     if (o.world > 1 && o.channels % o.world) { std::cerr << "--world must divide -c\n"; return 2; }
     if (o.world > 1 && o.mix && id_file.empty()) { std::cerr << "--world with --mix needs --id-file (the communicator's bootstrap)\n"; return 2; }
+    if (fms && (o.decim < 1 || o.world > 1 || o.mix)) { std::cerr << "DeFMS takes a decimation >= 1 and runs one stream (no --world, no --mix)\n"; return 2; }
     try {
         o.device = device;
+        if (fms) return run_fms(in, o, n, out, chunk);
         // the communicator exists only where the path has an exchange step: --mix over channel shards (also a world of one, which
         // then runs the same C entry points)
         if (o.mix && o.channels > 1 && !id_file.empty()) o.comm = commFromIdFile(id_file, (int)o.rank, (int)o.world, device, id_nonce);

@@ -196,6 +196,70 @@ def wbFMDemodulator(quadRate, decim, max_samples=4096):
                            fmDemodulator(0.6, max_samples=max_samples)))
 
 
+class FmStereo:
+    """The `csdr_fmstereo_*` object: stereoFMDecoder quadRate decim on `nchan` independent F32 MPX streams (include/csdr.h)."""
+
+    def __init__(self, quadRate, decim, nchan=1, max_samples=1 << 16):
+        h = C.c_void_p()
+        check(lib().csdr_fmstereo_create(float(quadRate), int(decim), int(nchan), int(max_samples), C.byref(h)))
+        self._h = _Handle(h, lib().csdr_fmstereo_destroy)
+        self.decim, self.nchan = int(decim), int(nchan)
+
+    @property
+    def h(self):
+        if not self._h.h:
+            raise CsdrError(_lib.ERR_INVALID, "fmstereo already destroyed")
+        return self._h.h
+
+    @property
+    def delay(self):
+        return int(lib().csdr_fmstereo_get_delay(self.h))
+
+    @property
+    def taps_len(self):
+        return int(lib().csdr_fmstereo_get_taps_len(self.h))
+
+    def pll(self, chan=0):
+        th, d = C.c_uint32(), C.c_uint32()
+        check(lib().csdr_fmstereo_get_pll(self.h, chan, C.byref(th), C.byref(d)))
+        return th.value, d.value
+
+    def process(self, mpx):
+        """[nchan][n] (or [n] for one stream) F32 -> [nchan][2 (n // decim)] (or [2 (n // decim)]) interleaved L, R."""
+        x = np.ascontiguousarray(mpx, dtype=np.float32)
+        n = x.size // self.nchan
+        y = np.empty(x.shape[:-1] + (2 * (n // self.decim),), dtype=np.float32)
+        n_out = C.c_uint32()
+        check(lib().csdr_fmstereo_process(self.h, _ptr(x), n, _ptr(y), C.byref(n_out)))
+        assert n_out.value == y.size, (n_out.value, y.size)
+        return y
+
+    def process_device(self, d_mpx_ptr, n, d_lr_ptr, stream=0):
+        """Device-resident variant: raw device pointers (ints), enqueues on `stream`; returns the element count."""
+        n_out = C.c_uint32()
+        check(lib().csdr_fmstereo_process_device(self.h, C.c_void_p(d_mpx_ptr), n, C.c_void_p(d_lr_ptr), C.byref(n_out),
+                                                 C.c_void_p(stream)))
+        return n_out.value
+
+    def kernel_times(self):
+        """us of the last call's front, pll, back, deemph, decim kernels (needs CSDR_DIAG=1 CSDR_FMS_TIME=1 at create)"""
+        t = (C.c_float * 5)()
+        check(lib().csdr_fmstereo_kernel_times(self.h, t))
+        return list(t)
+
+    def reset(self):
+        check(lib().csdr_fmstereo_reset(self.h))
+
+    def close(self):
+        self._h.close()
+
+
+def stereoFMDecoder(quadRate, decim, nchan=1, max_samples=1 << 16):
+    """stereoFMDecoder quadRate decim (Liquid.chs:1069-1078) as a Pipe from F32 MPX arrays ([nchan][n], or [n]) to interleaved
+    stereo L, R, L, R ... ([nchan][2 (n div decim)]).  The wire delay is a constant d samples (deviation)."""
+    return Pipe(lambda: FmStereo(quadRate, decim, nchan, max_samples), lambda r, a: r.process(a), lambda r: r.close())
+
+
 def resampler(r, as_db=60.0, max_samples=1 << 20):
     """resampler r as (Liquid.chs:115-117): Pipe IO (Array CF32) (Array CF32) with a variable-length output
     (`shrinkToFit` to the count msresamp_crcf_execute reports, :79-98).  r == 0 is the identity."""

@@ -204,6 +204,39 @@ int csdr_ampdem_process(csdr_ampdem *h, const float *x_cf32, uint32_t n, float *
 int csdr_ampdem_destroy(csdr_ampdem *h);
 
 /* ------------------------------------------------------------------------ *
+ * stereoFMDecoder quadRate decim  (Liquid.chs:959-1078; DeFMS decim fmt, SoapySDR.hs:261-264),
+ * `nchan` independent streams.  replaces the reference's pilot-branch NCOs + firfilt_crcf
+ * (mixUp ncoF . firPilot . mixDown ncoF), the pilot PLL (two nco_crcf + pll_step / step,
+ * Liquid.chs:959-989), the L+R / L-R firfilt_crcf, the L/R matrix, and per channel
+ * iirFilter 2 (5000/q) 0 10 10 + firDecimator decim (Liquid.chs:1005-1046).
+ *   quad_rate q: the MPX sample rate (the app's outBW); every FIR has round(q/1350) taps;
+ *   q in [40e3, 2.7e6].  mpx is [nchan][n] F32 (freqdem output), lr is [nchan][2*floor(n/decim)]
+ *   F32 interleaved L, R, L, R ...; *n_out = nchan * 2 * floor(n/decim) elements.
+ *   Any n <= max_samples is accepted.  Everything up to the de-emphasis is stream-continuous;
+ *   the decimator consumes floor(n/decim)*decim samples per call and drops the rest, as the
+ *   reference's firDecim `div` does (Liquid.chs:495-497).
+ * DEVIATION: the reference's `delay d` (Trans.hs:86-104) lags the wire by d more
+ * samples per chunk and pairs its buffered tail with a zero wire at the end; this object applies
+ * the evident intent instead: the wire is x[t - d] (0 before the stream start), every input
+ * sample yields one output pair, no end-of-stream flush (the last d wire samples are not emitted).
+ * d = round(fir_group_delay(pilot FIR, 100/q)) (csdr_fmstereo_get_delay).  liquid-dsp's Kaiser
+ * design, group delay and PLL arithmetic are recalled from 1.3.2: unpinned.
+ * ------------------------------------------------------------------------ */
+typedef struct csdr_fmstereo csdr_fmstereo;
+int csdr_fmstereo_create(float quad_rate, uint32_t decim, uint32_t nchan, uint32_t max_samples, csdr_fmstereo **out);
+int csdr_fmstereo_process(csdr_fmstereo *h, const float *mpx, uint32_t n, float *lr, uint32_t *n_out);
+int csdr_fmstereo_process_device(csdr_fmstereo *h, const void *d_mpx, uint32_t n, void *d_lr, uint32_t *n_out, void *stream);
+int csdr_fmstereo_reset(csdr_fmstereo *h);                       /* back to the state right after create            */
+uint32_t csdr_fmstereo_get_delay(const csdr_fmstereo *h);        /* d, the wire delay in samples                    */
+uint32_t csdr_fmstereo_get_taps_len(const csdr_fmstereo *h);     /* N, the taps of every FIR                        */
+/* the PLL's uint32 words (ncoPE theta, d_theta) of stream `chan` after the last call (synchronises) */
+int csdr_fmstereo_get_pll(csdr_fmstereo *h, uint32_t chan, uint32_t *theta, uint32_t *d_theta);
+/* with CSDR_DIAG=1 CSDR_FMS_TIME=1 at create: hipEvent times of the last call's five kernels in us
+ * (front, pll, back, deemph, decim); synchronises.  CSDR_ERR_INVALID when timing is off. */
+int csdr_fmstereo_kernel_times(csdr_fmstereo *h, float *us5);
+int csdr_fmstereo_destroy(csdr_fmstereo *h);
+
+/* ------------------------------------------------------------------------ *
  * The fused chain: everything assembleFold (apps/SoapySDR.hs:208-226) puts
  * behind `compact`:
  *     dcBlocker                                   (SoapySDR.hs:213-214)
