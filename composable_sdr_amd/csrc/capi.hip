@@ -783,13 +783,18 @@ const RouteRow ROUTES[] = {
      "(the shard's channel sum is M / G x the phasor sum of the G surviving branches)",
      "the same kernels (any call size)", "... -> k_transpose -> k_agc_spec -> k_agc_fix [-> k_fm] [-> k_mix]"},
 };
-const RouteRow *route_select(uint32_t M, uint32_t p, uint32_t G, uint32_t flags)
+// dc: the handle's DC blocker, null without one.  Every fused plan truncates the DC state somewhere (warm-up windows, look-back tiles,
+// dcfix); a handle whose alpha does not fit the plan's shortest window (dc_window_ok) takes the generic row.
+const RouteRow *route_select(uint32_t M, uint32_t p, uint32_t G, uint32_t flags, const DcParams *dc)
 {
     const RouteRow *generic = &ROUTES[sizeof(ROUTES) / sizeof(ROUTES[0]) - 1];
     if (M <= 1 || (flags & CSDR_FLAG_FORCE_GENERIC)) return generic;
     if (G > 1 && diag_env("CSDR_SHARD_GENERIC")) return generic;
     for (const RouteRow &r : ROUTES) {
         if (r.M != M || !(G < 32 && (r.strides >> G) & 1u)) continue;
+        // shortest window of the plan: WU = 6 read-only warm-up tiles of 4096 samples (k_run256v2, k_run64v2, k_run1024v3, k_run1024v2),
+        // H_WU = 7 frames of 4096 samples in front of a k_front4096 run
+        if (dc && r.plan != PLAN_GENERIC && !dc_window_ok(*dc, (r.plan == PLAN_HUGE4096 ? 7 : 6) * 4096.0)) continue;
         const bool ok = r.plan == PLAN_FUSED256 ? fused_supported(M, p) : r.plan == PLAN_SMALL64 ? small_supported(M, p)
                       : r.plan == PLAN_BIG1024 ? (big_supported(M, p) && !diag_env("CSDR_NO_RUN1024"))
                       : r.plan == PLAN_HUGE4096 ? (huge_supported(M, p) && !diag_env("CSDR_NO_RUN4096")) : true;
@@ -926,6 +931,7 @@ int csdr_chain_create(const csdr_chain_cfg *cfg_in, csdr_chain **out)
     }
     if (cfg->demod == CSDR_DEMOD_FM && !(cfg->kf > 0.f)) { set_error("chain: FM needs kf > 0"); return CSDR_ERR_INVALID; }
     if (cfg->dc_block && !(cfg->dc_alpha > 0.f && cfg->dc_alpha < 1.f)) { set_error("chain: dc_alpha out of (0,1)"); return CSDR_ERR_INVALID; }
+    if (cfg->pfb_m > 32u) { set_error("chain: pfb_m %u out of 1..32 (0 = 7)", cfg->pfb_m); return CSDR_ERR_INVALID; }
     const uint32_t M = cfg->channels;
     uint32_t c0 = cfg->chan_first, C = cfg->chan_count ? cfg->chan_count : M - c0;
     const uint32_t G = cfg->chan_stride > 1 ? cfg->chan_stride : 1;
@@ -987,9 +993,10 @@ int csdr_chain_create(const csdr_chain_cfg *cfg_in, csdr_chain **out)
     // With the AGC on, the fused kernel stops at the channel-major CF32 samples and the
     // exactly-sequential per-channel AGC tail (one lane per channel) + freqdem + mix follow.
     // interleaved shards: the fused M = 256 chain takes strides 2, 4, 8 (k_run256v2<.., G>); every other shape the any-M route with a pruned DFT
-    const RouteRow *route = route_select(M, h->p, G, cfg->flags);          // the one place a configuration is mapped to a plan (table above)
+    const DcParams *dcp = cfg->dc_block ? &h->dc : nullptr;
+    const RouteRow *route = route_select(M, h->p, G, cfg->flags, dcp);     // the one place a configuration is mapped to a plan (table above)
     if (route->plan == PLAN_HUGE4096 && (C != M || (cfg->mix && cfg->demod == CSDR_DEMOD_NONE && cfg->agc_threshold_db == 0.0f && !am)))
-        route = route_select(M, h->p, G, cfg->flags | CSDR_FLAG_FORCE_GENERIC);   // contiguous shards; DeNo --mix over all channels (= M x branch 0: nothing beats not computing
+        route = route_select(M, h->p, G, cfg->flags | CSDR_FLAG_FORCE_GENERIC, dcp);   // contiguous shards; DeNo --mix over all channels (= M x branch 0: nothing beats not computing
                                                                                    // the bank; CSDR_FLAG_NO_MIX_IDENTITY's full bank + DFT + sum stays on the any-M kernels too)
     h->use_fused = route->plan != PLAN_GENERIC;
     if (h->use_fused) {
@@ -1049,8 +1056,10 @@ int csdr_chain_create(const csdr_chain_cfg *cfg_in, csdr_chain **out)
             h->path = "generic+mix-identity"; h->timed_kernel = (M % 4096u == 0) ? "k_dc_fold" : "k_dc_tile";   // refined per call
         }
         // interleaved shard, DeNo --mix, no AGC: only the G branches (M / G) n2 survive the shard's channel sum (kernels_dc_tile.hip, k_dc_fold8)
+        // (the conditions of dctile_mix_identity_shard_supported that do not depend on the call: every call of whole frames then takes it)
         h->mix_identity_shard = M > 1 && (G == 2 || G == 4 || G == 8) && (uint64_t)C * G == M && cfg->mix && cfg->demod == CSDR_DEMOD_NONE && cfg->agc_threshold_db == 0.0f &&
-                                h->dctile && !(cfg->flags & CSDR_FLAG_NO_MIX_IDENTITY) && !am && M % 4096u == 0 && (M / G) % 512u == 0;
+                                h->dctile && !(cfg->flags & CSDR_FLAG_NO_MIX_IDENTITY) && !am && M % 4096u == 0 && (M / G) % 512u == 0 &&
+                                h->p <= 33u && h->dc.beta > 0.f;
         if (h->mix_identity_shard) {
             if ((r = dev_alloc(&h->d_u0hist, 2 * (size_t)(h->p - 1) * G))) return fail(r);
         }
@@ -1067,6 +1076,7 @@ int csdr_chain_create(const csdr_chain_cfg *cfg_in, csdr_chain **out)
             h->path = h->mix_identity_shard ? "generic+pruned-dft+shard-mix-identity" : "generic+pruned-dft";
             if (h->mix_identity_shard) h->timed_kernel = "k_dc_fold8";
         }
+        if (M > 1 && cfg->dc_block && !h->dctile) h->path += "+dc-scan";     // alpha outside the DC shortcuts (dc_window_ok): launch_dc_mix
     }
     if ((cfg_in->flags & CSDR_FLAG_DFT_BACKWARD) && M > 1 && !(cfg_in->mix != 0)) {
         if (C != M || G > 1) { set_error("chain: CSDR_FLAG_DFT_BACKWARD is built for whole-band handles (no channel shard)"); return fail(CSDR_ERR_INVALID); }
@@ -1146,9 +1156,11 @@ static int chain_generic(csdr_chain *h, const float2 *d_in, uint32_t nx, void *d
     if (M > 1) {
         const size_t hist = (size_t)(h->p - 1) * M;
         nco.theta0 = h->theta; nco.d_theta = h->d_theta; nco.tab_len = h->tab_len; nco.tab_pos = h->tab_pos; nco.up = 0;
-        if (h->mix_identity_shard && dctile_mix_identity_shard_supported(h->dctile, M, nx, h->p, h->G)) {
-            // the shard's channel sum = (M / G) x sum of the G surviving branches' FIRs (whole frames of M % 4096 == 0 samples; other calls
-            // fall through to the pruned-DFT route below, which shares no state with this one but the DC blocker's: see the create-time note)
+        if (h->mix_identity_shard) {
+            // the shard's channel sum = (M / G) x sum of the G surviving branches' FIRs.  The create-time predicate holds every condition
+            // that does not depend on the call, and calls are whole frames: a call it refuses is a bug, not a reason to switch routes (the
+            // pruned-DFT route keeps no branch histories of its own)
+            if (!dctile_mix_identity_shard_supported(h->dctile, M, nx, h->p, h->G)) { set_error("chain: shard mix identity refused a call of %u samples", nx); return CSDR_ERR_INVALID; }
             const size_t hs = (size_t)(h->p - 1) * h->G;
             float2 *hin = h->d_u0hist + (size_t)h->u0_cur * hs, *hout = h->d_u0hist + (size_t)(h->u0_cur ^ 1) * hs;
             h->timed_kernel = "k_dc_fold8";

@@ -78,6 +78,17 @@ struct DcParams {
     float log2_beta;
 };
 
+// DC shortcuts: a route that cuts the DC blocker's state after a window of N samples (read-only warm-up tiles, look-back
+// tiles, the dcfix corrections behind cold starts) was sized for the default alpha = 0.0005.  It may serve a handle whose beta^N is no
+// larger than what the same window leaves at that alpha (for every N this amounts to alpha >= 0.0005), and whose warm-up folds can
+// form their weight ratio beta^-512 in f32 (alpha below ~0.15; above it the fold's 0 * inf is NaN).  A handle that fails takes the
+// any-M route with the exact block scan (launch_dc_mix).
+inline bool dc_window_ok(const DcParams &dc, double N)
+{
+    const double b = dc.beta, b0 = (double)(1.0f - 0.0005f);
+    return b > 0.0 && __builtin_pow(b, N) <= __builtin_pow(b0, N) && -512.0 * __builtin_log2(b) < 120.0;
+}
+
 struct NcoParams {
     uint32_t theta0;       // phase of the first sample of this call
     uint32_t d_theta;

@@ -496,6 +496,10 @@ void dctile_destroy(DcTilePlan *p)
 
 int dctile_create(const DcParams &dc, uint64_t max_samples, DcTilePlan **out)
 {
+    // k_dc_tile looks back LOOKBACK tiles; k_dc_fold / k_dc_fold8 fold with beta^-512 ratios: *out stays null when the handle's alpha
+    // does not fit them (dc_window_ok), and the caller keeps the exact block scan
+    *out = nullptr;
+    if (!dc_window_ok(dc, LOOKBACK * 4096.0)) return 0;
     DcTilePlan *p = new DcTilePlan();
     p->max_nb = (uint32_t)((max_samples + 4095) / 4096);
     auto fail = [&](int r) { dctile_destroy(p); return r; };

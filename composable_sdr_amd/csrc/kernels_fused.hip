@@ -459,7 +459,8 @@ int fused_create(const FusedConfig &cfg, FusedPlan **out)
     if (const char *e = diag_env("CSDR_RUN_MIN_TILES")) p->run_min_tiles = (uint32_t)atol(e);
     if (cfg.mix) ALLOC(p->d_premix, (size_t)cfg.C * cfg.max_nf * (cfg.fm ? 4 : 8));
     if (diag_env("CSDR_TRACE")) { ALLOC(p->d_trace, sizeof(u64) * 16 * p->max_nb); CSDR_HIP(hipMemset(p->d_trace, 0, sizeof(u64) * 16 * p->max_nb)); }
-    p->nowu = cfg.G == 1 && cfg.c0 == 0 && cfg.C == cfg.M && cfg.dc_block && !(diag_env("CSDR_NOWU") && atoi(diag_env("CSDR_NOWU")) == 0);
+    p->nowu = cfg.G == 1 && cfg.c0 == 0 && cfg.C == cfg.M && cfg.dc_block && dc_window_ok(cfg.dc, (DCFIX_F - 1) * 256.0) &&     // k_run256_dcfix: 112 frames
+              !(diag_env("CSDR_NOWU") && atoi(diag_env("CSDR_NOWU")) == 0);
     if (p->nowu) {
         ALLOC(p->d_cpre, sizeof(float2) * 2050);
         ALLOC(p->d_side, sizeof(float2) * 2048 * 4 * DCFIX_F);

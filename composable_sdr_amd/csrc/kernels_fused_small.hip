@@ -415,7 +415,7 @@ int small_create(const FusedConfig &cfg, SmallPlan **out)
         p->cus = (uint32_t)cus;
         p->v2_ok = !cfg.fm && cfg.c0 == 0 && cfg.C == (uint32_t)MS && !diag_env("CSDR_RUN64_V1");
     }
-    if (p->v2_ok && cfg.dc_block && !(diag_env("CSDR_NOWU") && atoi(diag_env("CSDR_NOWU")) == 0)) {
+    if (p->v2_ok && cfg.dc_block && dc_window_ok(cfg.dc, RUN64_DCFIX_F * 64.0) && !(diag_env("CSDR_NOWU") && atoi(diag_env("CSDR_NOWU")) == 0)) {
         // k_run64v2 without warm-up windows: the state hand-over array and the chain's response to a unit DC state at the channels 30..33,
         // frames 64 .. 64 + RUN64_DCFIX_F - 1 behind a halo tile's start (= the run's first output frames)
         hipError_t e1 = hipMalloc((void **)&p->d_cpre, sizeof(float2) * 1026), e2 = hipMalloc((void **)&p->d_rt, sizeof(float2) * 2 * RUN64_DCFIX_F * 4);

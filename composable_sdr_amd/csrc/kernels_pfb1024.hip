@@ -571,7 +571,7 @@ int big_create(const FusedConfig &cfg, BigPlan **out)
         hipError_t e1 = hipMalloc((void **)&p->d_cpre, sizeof(float2) * (p->cus + 2)), e2 = hipMalloc((void **)&p->d_side, sizeof(float2) * (size_t)(p->cus + 1) * RUN1024_DCFIX_F);
         if (e1 != hipSuccess || e2 != hipSuccess) return fail(hip_fail(e1 != hipSuccess ? e1 : e2, "hipMalloc", __FILE__, __LINE__));
         CSDR_HIP(hipMemset(p->d_cpre, 0, sizeof(float2) * (p->cus + 2)));
-        if (cfg.dc_block && !(diag_env("CSDR_NOWU") && atoi(diag_env("CSDR_NOWU")) == 0)) {
+        if (cfg.dc_block && dc_window_ok(cfg.dc, 12 * 4096.0) && !(diag_env("CSDR_NOWU") && atoi(diag_env("CSDR_NOWU")) == 0)) {   // error beta^(12 x 4096)
             hipError_t e3 = hipMalloc((void **)&p->d_rt, sizeof(float2) * 2 * RUN1024_DCFIX_F * 4);
             if (e3 != hipSuccess) return fail(hip_fail(e3, "hipMalloc", __FILE__, __LINE__));
             std::vector<float2> rt((size_t)2 * RUN1024_DCFIX_F * 4, make_float2(0.f, 0.f));
@@ -587,7 +587,7 @@ int big_create(const FusedConfig &cfg, BigPlan **out)
         if (e1 != hipSuccess || e2 != hipSuccess) return fail(hip_fail(e1 != hipSuccess ? e1 : e2, "hipMalloc", __FILE__, __LINE__));
         CSDR_HIP(hipMemset(p->d_cpre, 0, sizeof(float2) * (p->cus + 2)));
     }
-    if (p->v3_ok && cfg.dc_block && !(diag_env("CSDR_NOWU") && atoi(diag_env("CSDR_NOWU")) == 0)) {
+    if (p->v3_ok && cfg.dc_block && dc_window_ok(cfg.dc, 35 * 1024.0) && !(diag_env("CSDR_NOWU") && atoi(diag_env("CSDR_NOWU")) == 0)) {   // halo + 32-frame dcfix
         hipError_t e3 = hipMalloc((void **)&p->d_rt, sizeof(float2) * 2 * RUN1024_DCFIX_F * 4);
         if (e3 != hipSuccess) return fail(hip_fail(e3, "hipMalloc", __FILE__, __LINE__));
         std::vector<float2> rt((size_t)2 * RUN1024_DCFIX_F * 4);

@@ -263,7 +263,10 @@ typedef struct csdr_chain_cfg {
     uint32_t struct_size;       /* = sizeof(csdr_chain_cfg)                              */
     uint32_t channels;          /* -c M, >= 1                                            */
     uint32_t dc_block;          /* 1: include dcBlocker (assembleFold always does)       */
-    float    dc_alpha;          /* 0.0005 (Liquid.chs:577)                               */
+    float    dc_alpha;          /* 0.0005 (Liquid.chs:577); in (0, 1) with dc_block, else CSDR_ERR_INVALID.
+                                 * The fused kernels and k_dc_tile cut the DC state after fixed windows sized for 0.0005:
+                                 * alpha < 0.0005 or > ~0.15 (whose fold weights beta^-512 overflow f32) runs the any-M
+                                 * route with the exact block scan instead (path "...+dc-scan")         */
     float    agc_threshold_db;  /* -a tres; 0 = no AGC (SoapySDR.hs:195-198)             */
     uint32_t demod;             /* CSDR_DEMOD_*                                          */
     float    kf;                /* DeNBFM kf                                             */
@@ -273,7 +276,9 @@ typedef struct csdr_chain_cfg {
     int32_t  device;            /* HIP device ordinal, -1 = current device               */
     uint32_t max_frames;        /* largest n_in/channels per call; 0 = 4096              */
     uint32_t flags;             /* CSDR_FLAG_*                                           */
-    uint32_t pfb_m;             /* filter semi-length m, 0 = 7  (Liquid.chs:813)         */
+    uint32_t pfb_m;             /* filter semi-length m, 0 = 7  (Liquid.chs:813); 1..32, else CSDR_ERR_INVALID.
+                                 * Fused kernels exist for m = 7 only (other m: the any-M route); the DeNo --mix
+                                 * identity folds need 2m <= 33                                                   */
     float    pfb_as;            /* stop-band attenuation, 0 = 80 dB (Liquid.chs:813)     */
     uint32_t wbfm_decim;        /* DeWBFM decim (SoapySDR.hs:252-259); 0 = 4             */
     float    deemph_fc;         /* DeWBFM de-emphasis corner 5000/quadRate (Liquid.chs:655); 0 = 0.025 */

@@ -326,14 +326,16 @@ void orc_pfb_analyzer_execute(orc_pfb *q, const cf32 *x, cf32 *y)
 /* ------------------------------------------------------------------ */
 typedef struct { orc_pfb *fb; orc_nco *nco; unsigned M; } orc_chan;
 
-orc_chan *orc_chan_create(unsigned M)
+/* m, As: the prototype's semi-length and stop-band attenuation (csdr_chain_cfg::pfb_m, pfb_as) */
+orc_chan *orc_chan_create_ex(unsigned M, unsigned m, float As)
 {
     orc_chan *q = (orc_chan *)calloc(1, sizeof(*q));
     q->M = M;
-    q->fb = orc_pfb_create(M, 7, 80.0f);                /* Liquid.chs:813 */
+    q->fb = orc_pfb_create(M, m, As);
     q->nco = orc_nco_create(orc_pfb_offset(M));         /* Liquid.chs:816-818 */
     return q;
 }
+orc_chan *orc_chan_create(unsigned M) { return orc_chan_create_ex(M, 7, 80.0f); }   /* Liquid.chs:813 */
 void orc_chan_destroy(orc_chan *q) { if (q) { orc_pfb_destroy(q->fb); orc_nco_destroy(q->nco); free(q); } }
 void orc_chan_set_dft_backward(orc_chan *q, int backward) { orc_pfb_set_dft_backward(q->fb, backward); }
 uint32_t orc_chan_dtheta(const orc_chan *q) { return q->nco->d_theta; }
@@ -758,13 +760,14 @@ typedef struct {
 } orc_chain;
 
 orc_chain *orc_chain_create_wbfm(unsigned M, int dc_block, int agc_enable, float agc_thr_db, float deemph_fc, unsigned decim, int mix);
-orc_chain *orc_chain_create(unsigned M, int dc_block, int agc_enable, float agc_thr_db,
-                            int demod, float kf, int mix)
+/* dc_alpha, m, As: csdr_chain_cfg::dc_alpha, pfb_m, pfb_as */
+orc_chain *orc_chain_create_ex(unsigned M, int dc_block, int agc_enable, float agc_thr_db,
+                               int demod, float kf, int mix, float dc_alpha, unsigned m, float As)
 {
     orc_chain *q = (orc_chain *)calloc(1, sizeof(*q));
     q->M = M; q->dc_block = dc_block; q->agc_enable = agc_enable; q->demod = demod; q->mix = mix;
-    if (dc_block) q->dc = orc_dcblock_create(0.0005f);   /* Liquid.chs:577 */
-    if (M > 1) q->chan = orc_chan_create(M);
+    if (dc_block) q->dc = orc_dcblock_create(dc_alpha);
+    if (M > 1) q->chan = orc_chan_create_ex(M, m, As);
     if (agc_enable) {
         q->agc = (orc_agc **)calloc(M, sizeof(orc_agc *));
         for (unsigned k = 0; k < M; k++) q->agc[k] = orc_agc_create_ref(agc_thr_db);
@@ -779,6 +782,13 @@ orc_chain *orc_chain_create(unsigned M, int dc_block, int agc_enable, float agc_
     }
     return q;
 }
+orc_chain *orc_chain_create(unsigned M, int dc_block, int agc_enable, float agc_thr_db,
+                            int demod, float kf, int mix)
+{
+    return orc_chain_create_ex(M, dc_block, agc_enable, agc_thr_db, demod, kf, mix, 0.0005f, 7, 80.0f);   /* Liquid.chs:577, 813 */
+}
+/* the channelizer's prototype taps (M * 2m), NULL for M = 1 */
+const float *orc_chain_pfb_taps(const orc_chain *q) { return q->chan ? orc_pfb_taps(q->chan->fb) : NULL; }
 /* DeWBFM decim: wbFMDemodulator outBW decim . agc (SoapySDR.hs:252-259); deemph_fc = 5000 / outBW */
 orc_chain *orc_chain_create_wbfm(unsigned M, int dc_block, int agc_enable, float agc_thr_db, float deemph_fc, unsigned decim, int mix)
 {

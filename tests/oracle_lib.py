@@ -55,6 +55,7 @@ def lib():
             "orc_chan_set_dft_backward": (None, [vp, i32]),
             "orc_chain_set_dft_backward": (None, [vp, i32]),
             "orc_chan_create": (vp, [u32]),
+            "orc_chan_create_ex": (vp, [u32, u32, f32]),
             "orc_chan_destroy": (None, [vp]),
             "orc_chan_dtheta": (u32, [vp]),
             "orc_chan_theta": (u32, [vp]),
@@ -90,6 +91,8 @@ def lib():
             "orc_ampdem_demodulate_block": (None, [vp, vp, u32, vp]),
             "orc_mix_f32": (None, [vp, u32, u32, vp]),
             "orc_chain_create": (vp, [u32, i32, i32, f32, i32, f32, i32]),
+            "orc_chain_create_ex": (vp, [u32, i32, i32, f32, i32, f32, i32, f32, u32, f32]),
+            "orc_chain_pfb_taps": (vp, [vp]),
             "orc_chain_destroy": (None, [vp]),
             "orc_chain_process": (None, [vp, vp, u32, vp]),
         }
@@ -216,9 +219,9 @@ class Chan(_Obj):
     """firpfbchChan: premix + analyzer per frame + transpose -> [M][nf]."""
     _destroy = "orc_chan_destroy"
 
-    def __init__(self, M):
-        self.M = M
-        self.h = lib().orc_chan_create(M)
+    def __init__(self, M, m=7, As=80.0):
+        self.M, self.p = M, 2 * m
+        self.h = lib().orc_chan_create_ex(M, m, np.float32(As))
 
     @property
     def dtheta(self):
@@ -365,19 +368,29 @@ class Chain(_Obj):
     """assembleFold's DSP (SoapySDR.hs:208-226) on compacted chunks."""
     _destroy = "orc_chain_destroy"
 
-    def __init__(self, M, dc_block=True, agc_db=0.0, demod="none", kf=0.3, mix=False, decim=4, deemph_fc=0.025, dft_backward=False):
-        self.M = M
+    def __init__(self, M, dc_block=True, agc_db=0.0, demod="none", kf=0.3, mix=False, decim=4, deemph_fc=0.025, dft_backward=False,
+                 dc_alpha=0.0005, pfb_m=7, pfb_as=80.0):
+        self.M, self.p = M, 2 * pfb_m
         self.demod = {"none": 0, "fm": 1, "am": 2, "wbfm": 3}[demod]
         self.mix = bool(mix) and M > 1
         self.decim = decim if self.demod == 3 else 1
         if self.demod == 3:
+            assert (dc_alpha, pfb_m, pfb_as) == (0.0005, 7, 80.0), "the WBFM chain is built with the default DC blocker and prototype"
             self.h = lib().orc_chain_create_wbfm(M, int(dc_block), int(agc_db != 0.0), np.float32(agc_db),
                                                  np.float32(deemph_fc), decim, int(self.mix))
         else:
-            self.h = lib().orc_chain_create(M, int(dc_block), int(agc_db != 0.0), np.float32(agc_db),
-                                            self.demod, np.float32(kf), int(self.mix))
+            self.h = lib().orc_chain_create_ex(M, int(dc_block), int(agc_db != 0.0), np.float32(agc_db),
+                                               self.demod, np.float32(kf), int(self.mix), np.float32(dc_alpha), pfb_m, np.float32(pfb_as))
         if dft_backward:                      # the other possible convention of the analyzer's transform (unpinned: SURVEY 7.1)
             lib().orc_chain_set_dft_backward(self.h, 1)
+
+    @property
+    def taps(self):
+        """the channelizer's prototype (M * 2m taps); empty for M = 1"""
+        ptr = lib().orc_chain_pfb_taps(self.h)
+        if not ptr:
+            return np.zeros(0, dtype=np.float32)
+        return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(C.c_float)), shape=(self.M * self.p,)).copy()
 
     def process(self, x):
         x = _c64(x)
