@@ -80,6 +80,15 @@ SIGNATURES = {
     "csdr_fmstereo_get_pll": (_i32, [_vp, _u32, _pu32, _pu32]),
     "csdr_fmstereo_kernel_times": (_i32, [_vp, C.POINTER(C.c_float)]),
     "csdr_fmstereo_destroy": (_i32, [_vp]),
+    "csdr_symsync_create": (_i32, [_u32, _u32, _f32, _u32, _f32, _u32, _u32, _u32, _pp]),
+    "csdr_symsync_process": (_i32, [_vp, _vp, _u32, _vp, _pu32]),
+    "csdr_symsync_process_device": (_i32, [_vp, _vp, _u32, _vp, _vp, _vp]),
+    "csdr_symsync_reset": (_i32, [_vp]),
+    "csdr_symsync_get_state": (_i32, [_vp, _u32, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                       C.POINTER(C.c_float)]),
+    "csdr_symsync_get_taps_len": (_u32, [_vp]),
+    "csdr_symsync_get_taps": (_i32, [_vp, _vp, _vp]),
+    "csdr_symsync_destroy": (_i32, [_vp]),
     "csdr_chain_cfg_default": (None, [C.POINTER(ChainCfg), _u32]),
     "csdr_chain_create": (_i32, [C.POINTER(ChainCfg), _pp]),
     "csdr_chain_process": (_i32, [_vp, _vp, _u32, _vp, _pu32]),

@@ -9,13 +9,15 @@ with the DSP behind `compact` done by the fused C-ABI chain.  Sinks are the refe
 raw `.f32` by default or, with `audio="AU" | "WAV"`, through `audioFileSink` (Sink.hs:41-74: libsndfile float,
 big-endian; written here by hand, see the class).  `--offset` and `-b` are the reference's mixDown/mixUp and
 resampler in front of `takeNArr`.  DeFMS (`demod="fms"`, SoapySDR.hs:261-264) skips the DC blocker, `compact` and the
-channelizer: agc -> fmDemodulator 0.8 -> stereoFMDecoder per source chunk into one 2-channel sink."""
+channelizer: agc -> fmDemodulator 0.8 -> stereoFMDecoder per source chunk into one 2-channel sink.  DeNBFMSync k
+(`demod="nbfmsync"`, SoapySDR.hs:273-280) runs the FM chain behind `compact (4*k*nch*1024)` and then symSyncR k 4 0 64 per
+channel into raw `.f32` sinks."""
 import struct
 import numpy as np
 
-from .pipes import (Chain, ChainConfig, automaticGainControl, compose, fmDemodulator, idPipe, mixDown, mixUp, resampler,
+from .pipes import (Chain, ChainConfig, SymSync, automaticGainControl, compose, fmDemodulator, idPipe, mixDown, mixUp, resampler,
                     stereoFMDecoder, unPipe)
-from .trans import Fold, compact, takeNArr
+from .trans import Fold, compact, mix as mix_pipe, takeNArr
 
 
 def readFromFile(n, fp):
@@ -76,6 +78,36 @@ class _FusedFold(Fold):
             s.done()
 
 
+class _SyncFold(Fold):
+    """DeNBFMSync's fold behind `compact`: one chain call per compacted chunk (FM rows, no mix), then one symsync call over
+    all rows (one stream per channel for the whole run); row k goes to sink k, or with -m the truncating left fold of the rows
+    (Trans.hs:119-122) to the one sink."""
+
+    def __init__(self, chain, sync, sinks, mixed):
+        self.chain, self.sync, self.sinks, self.mixed = chain, sync, sinks, mixed
+
+    def step(self, a):
+        M = self.chain.M
+        usable = len(a) // M * M
+        if usable == 0:
+            self.sinks[0].step(np.empty(0, dtype=np.float32))          # nx = 0 -> [empty]: only sink 1 sees it
+            return self
+        y = self.chain.process(a[:usable]).reshape(M, -1)
+        rows = self.sync.process(y)
+        if self.mixed:
+            self.sinks[0].step(mix_pipe._process(None, rows))
+        else:
+            for s, r in zip(self.sinks, rows):
+                s.step(r)
+        return self
+
+    def done(self):
+        self.chain.close()
+        self.sync.close()
+        for s in self.sinks:
+            s.done()
+
+
 class audioFileSink(Fold):
     """audioFileSink fmt sr sn nch fp (Sink.hs:41-74): libsndfile, SampleFormatFloat, EndianBig, file fp + ".au" / ".wav".
 
@@ -118,11 +150,13 @@ class audioFileSink(Fold):
 
 
 def sdr_process(filename, channels=1, demod="none", kf=0.3, agc=0.0, mix=False, numsamples=1024,
-                outname="output", chunksize=1024, m=4, offset=0.0, samplerate=2.56e6, bandwidth=0.0, decim=4, audio=None):
+                outname="output", chunksize=1024, m=4, offset=0.0, samplerate=2.56e6, bandwidth=0.0, decim=4, audio=None, k=4):
     """soapy-sdr --filename F -s samplerate -b bandwidth --offset f -c channels --demod ... -a agc [-m]
-    -n numsamples -o outname.  Returns the list of files written."""
+    -n numsamples -o outname.  demod="nbfmsync" is DeNBFMSync k.  Returns the list of files written."""
     if demod == "fms":
         return _sdr_process_fms(filename, channels, agc, numsamples, outname, chunksize, offset, samplerate, bandwidth, decim, audio)
+    if demod == "nbfmsync":
+        return _sdr_process_sync(filename, channels, agc, mix, numsamples, outname, chunksize, offset, samplerate, bandwidth, k)
     nch = channels
     mixed = bool(mix) and nch > 1
     ext = ".cf32" if demod == "none" else ".f32"
@@ -188,3 +222,26 @@ def _sdr_process_fms(filename, channels, agc, numsamples, outname, chunksize, of
         sink.done()
         cleanup()
     return [name]
+
+
+def _sdr_process_sync(filename, channels, agc, mix, numsamples, outname, chunksize, offset, samplerate, bandwidth, k):
+    """DeNBFMSync k (SoapySDR.hs:273-280): assembleFold (fileSink (n ++ ".f32")) (fmDemWithSync k . agc) outname nch (4*k):
+    prep -> dcBlocker -> compact (4*k*nch*1024) -> channelizer -> per channel agc -> fmDemodulator (0.02 k) -> symSyncR k 4 0 64
+    -> raw .f32 sinks, or with -m the channels' truncating left fold into one sink"""
+    nch = channels
+    mixed = bool(mix) and nch > 1
+    stems = [outname] if (mixed or nch == 1) else [f"{outname}_ch{j}" for j in range(1, nch + 1)]
+    names = [st + ".f32" for st in stems]
+    sinks = [fileSink(nm) for nm in names]
+    kf = float(np.float32(0.02) * np.float32(k))                   # 0.02 * fromIntegral k as a Haskell Float
+    chain = Chain(ChainConfig(channels=nch, demod="fm", kf=kf, agc=agc, mix=False, max_frames=4 * k * 1024))
+    sync = SymSync(k, 4, 0.0, 64, nchan=nch, max_samples=4 * k * 1024)
+    fold = compact(4 * k * nch * 1024, _SyncFold(chain, sync, sinks, mixed))
+    process, cleanup = unPipe(_prep(offset, samplerate, bandwidth, chunksize))
+    try:
+        for a in takeNArr(numsamples, process(readFromFile(chunksize, filename))):
+            fold.step(a)
+    finally:
+        fold.done()
+        cleanup()
+    return names

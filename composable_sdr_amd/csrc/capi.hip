@@ -740,6 +740,116 @@ int csdr_fmstereo_kernel_times(csdr_fmstereo *h, float *us5)
 }
 
 // ---------------------------------------------------------------------------
+// symSyncR k m beta M (Liquid.chs:244-282): symsync_rrrf on nchan independent streams
+// ---------------------------------------------------------------------------
+}  // extern "C"
+struct csdr_symsync {
+    int device; uint32_t C, max_n; SymsyncDesign d;
+    float *d_mf = nullptr, *d_dmf = nullptr, *d_hist = nullptr, *d_x = nullptr, *d_y = nullptr;
+    SymsyncState *d_st = nullptr; uint32_t *d_ny = nullptr, *d_fault = nullptr;
+};
+static int symsync_init_state(csdr_symsync *h)
+{
+    CSDR_HIP(hipMemset(h->d_hist, 0, sizeof(float) * (size_t)h->C * (h->d.L - 1)));
+    std::vector<SymsyncState> st(h->C, h->d.init);
+    CSDR_HIP(hipMemcpy(h->d_st, st.data(), sizeof(SymsyncState) * h->C, hipMemcpyHostToDevice));
+    CSDR_HIP(hipMemset(h->d_fault, 0, sizeof(uint32_t)));
+    return 0;
+}
+extern "C" {
+int csdr_symsync_destroy(csdr_symsync *h)
+{
+    if (!h) return CSDR_OK;
+    DevGuard guard(h->device);
+    (void)hipDeviceSynchronize();
+    void *ptrs[] = {h->d_mf, h->d_dmf, h->d_hist, h->d_x, h->d_y, h->d_st, h->d_ny, h->d_fault};
+    for (void *p : ptrs) if (p) (void)hipFree(p);
+    delete h;
+    return CSDR_OK;
+}
+int csdr_symsync_create(uint32_t k, uint32_t m, float beta, uint32_t npfb, float lf_bw, uint32_t k_out, uint32_t nchan,
+                        uint32_t max_samples, csdr_symsync **out)
+{
+    const uint64_t L = 2ull * k * m;
+    if (!out || !nchan || k_out < 1 || k < k_out || m < 1 || L > SYMSYNC_MAX_SUB || npfb < 1 || npfb > SYMSYNC_MAX_PFB ||
+        L * npfb > SYMSYNC_MAX_BANK || !(lf_bw >= 0.f && lf_bw <= 1.f)) {
+        set_error("symsync: bad arguments (k >= k_out >= 1, m >= 1, 2 k m <= %u, npfb in [1, %u], 2 k m npfb <= %u, lf_bw in [0, 1])",
+                  SYMSYNC_MAX_SUB, SYMSYNC_MAX_PFB, SYMSYNC_MAX_BANK);
+        return CSDR_ERR_INVALID;
+    }
+    int dev; int r = check_device(-1, &dev); if (r) return r;
+    csdr_symsync *h = new (std::nothrow) csdr_symsync();
+    if (!h) return CSDR_ERR_NOMEM;
+    h->device = dev; h->C = nchan; h->max_n = max_samples ? max_samples : 4096;
+    h->d = design_symsync_kaiser(k, m, beta, npfb, lf_bw, k_out);
+    const size_t C = nchan, n = h->max_n, LM = h->d.mf.size();
+    auto fail = [&](int rc) { csdr_symsync_destroy(h); return rc; };
+    if ((r = dev_alloc(&h->d_mf, LM)) || (r = dev_alloc(&h->d_dmf, LM)) || (r = dev_alloc(&h->d_hist, C * (h->d.L - 1))) ||
+        (r = dev_alloc(&h->d_st, C)) || (r = dev_alloc(&h->d_ny, C)) || (r = dev_alloc(&h->d_fault, 1)) ||
+        (r = dev_alloc(&h->d_x, C * n)) || (r = dev_alloc(&h->d_y, C * n)))
+        return fail(r);
+    CSDR_HIP_CLEAN(hipMemcpy(h->d_mf, h->d.mf.data(), sizeof(float) * LM, hipMemcpyHostToDevice), csdr_symsync_destroy(h));
+    CSDR_HIP_CLEAN(hipMemcpy(h->d_dmf, h->d.dmf.data(), sizeof(float) * LM, hipMemcpyHostToDevice), csdr_symsync_destroy(h));
+    if ((r = symsync_init_state(h))) return fail(r);
+    *out = h;
+    return CSDR_OK;
+}
+int csdr_symsync_process_device(csdr_symsync *h, const void *d_x, uint32_t n, void *d_y, void *d_ny, void *stream)
+{
+    if (!h || !d_ny) { set_error("symsync: null argument"); return CSDR_ERR_INVALID; }
+    if (n > h->max_n) { set_error("symsync: %u samples > max %u", n, h->max_n); return CSDR_ERR_SIZE; }
+    if (n && (!d_x || !d_y)) { set_error("symsync: null buffer"); return CSDR_ERR_INVALID; }
+    const SymsyncDesign &d = h->d;
+    SymsyncLaunch l{h->C, n, n, d.L, d.M, d.k_out, (float)d.k, d.b0, d.b1, d.b2, d.a1, d.a2, d.rate_adj};
+    return launch_symsync((const float *)d_x, (float *)d_y, (uint32_t *)d_ny, h->d_mf, h->d_dmf, h->d_hist, h->d_st, h->d_fault, l,
+                          (hipStream_t)stream);
+}
+int csdr_symsync_process(csdr_symsync *h, const float *x, uint32_t n, float *y, uint32_t *ny)
+{
+    if (!h || !ny || (n && (!x || !y))) { set_error("symsync: null argument"); return CSDR_ERR_INVALID; }
+    if (n > h->max_n) { set_error("symsync: %u samples > max %u", n, h->max_n); return CSDR_ERR_SIZE; }
+    DevGuard guard(h->device);
+    if (!guard.ok) { set_error("symsync: cannot select device %d", h->device); return CSDR_ERR_HIP; }
+    if (n) CSDR_HIP(hipMemcpy(h->d_x, x, sizeof(float) * (size_t)h->C * n, hipMemcpyHostToDevice));
+    int r = csdr_symsync_process_device(h, h->d_x, n, h->d_y, h->d_ny, nullptr);
+    if (r) return r;
+    uint32_t fault = 0;
+    CSDR_HIP(hipMemcpy(ny, h->d_ny, sizeof(uint32_t) * h->C, hipMemcpyDeviceToHost));
+    CSDR_HIP(hipMemcpy(&fault, h->d_fault, sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (n) CSDR_HIP(hipMemcpy(y, h->d_y, sizeof(float) * (size_t)h->C * n, hipMemcpyDeviceToHost));
+    if (fault) { set_error("symsync: a stream is faulted (del <= 0 or more than n outputs in a call); reset clears it"); return CSDR_ERR_SIZE; }
+    return CSDR_OK;
+}
+int csdr_symsync_reset(csdr_symsync *h)
+{
+    if (!h) return CSDR_ERR_INVALID;
+    DevGuard guard(h->device);
+    CSDR_HIP(hipDeviceSynchronize());
+    return symsync_init_state(h);
+}
+int csdr_symsync_get_state(csdr_symsync *h, uint32_t chan, float *tau, float *rate, float *del, float *q_hat)
+{
+    if (!h || chan >= h->C) { set_error("symsync: bad channel"); return CSDR_ERR_INVALID; }
+    DevGuard guard(h->device);
+    SymsyncState s;
+    CSDR_HIP(hipMemcpy(&s, h->d_st + chan, sizeof(SymsyncState), hipMemcpyDeviceToHost));
+    if (tau) *tau = s.tau;
+    if (rate) *rate = s.rate;
+    if (del) *del = s.del;
+    if (q_hat) *q_hat = s.q_hat;
+    if (s.fault) { set_error("symsync: stream %u is faulted", chan); return CSDR_ERR_SIZE; }
+    return CSDR_OK;
+}
+uint32_t csdr_symsync_get_taps_len(const csdr_symsync *h) { return h ? h->d.L : 0; }
+int csdr_symsync_get_taps(const csdr_symsync *h, float *mf, float *dmf)
+{
+    if (!h) return CSDR_ERR_INVALID;
+    if (mf) std::memcpy(mf, h->d.mf.data(), sizeof(float) * h->d.mf.size());
+    if (dmf) std::memcpy(dmf, h->d.dmf.data(), sizeof(float) * h->d.dmf.size());
+    return CSDR_OK;
+}
+
+// ---------------------------------------------------------------------------
 // fused chain
 // ---------------------------------------------------------------------------
 }  // extern "C"

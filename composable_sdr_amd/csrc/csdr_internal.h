@@ -204,6 +204,31 @@ struct FmsLaunch {
 int launch_fmstereo(const float *mpx, float *out, const FmsBufs &b, const FmsLaunch &l, hipStream_t s, hipEvent_t *ev);
 size_t fms_front_lds(uint32_t N, uint32_t d);
 
+// ---- symbol synchroniser (kernels_symsync.hip; design in design.cpp) ----
+constexpr uint32_t SYMSYNC_MAX_SUB = 64;             // h_sub_len = 2 k m: the taps of one sub-filter
+constexpr uint32_t SYMSYNC_MAX_PFB = 256;            // npfb
+constexpr uint32_t SYMSYNC_MAX_BANK = 4096;          // h_sub_len npfb: both banks and the windows stay below 64 KiB of LDS
+struct SymsyncState {                                // one stream, kept in HBM between calls
+    float tau, bf, rate, del, q_hat, v0, v1;         // v0, v1: the loop filter's direct form II state (v[0], v[1])
+    int32_t b;                                       // filterbank index
+    uint32_t decim, fault;                           // decim_counter; sticky fault mark
+};
+struct SymsyncDesign {
+    uint32_t k = 0, m = 0, M = 0, k_out = 0, H_len = 0, L = 0;   // L = h_sub_len = H_len / M = 2 k m
+    std::vector<float> H, dH;                        // the prototype (f32) and its scaled derivative, H_len each
+    std::vector<float> mf, dmf;                      // the banks, tap-major [L][M]: mf[j M + p] = H[p + (L - 1 - j) M]
+    float b0 = 0.f, b1 = 0.f, b2 = 0.f, a1 = 0.f, a2 = 0.f, rate_adj = 0.f;   // set_lf_bw, divided by A[0]
+    SymsyncState init{};
+};
+SymsyncDesign design_symsync_kaiser(uint32_t k, uint32_t m, float beta, uint32_t M, float lf_bw, uint32_t k_out);
+struct SymsyncLaunch {
+    uint32_t C, n, cap, L, M, k_out;
+    float kf, b0, b1, b2, a1, a2, rate_adj;
+};
+// x [C][n] -> y [C][cap] (row stride cap), ny [C]; hist [C][L - 1] and st [C] in place; *fault_any = 1 when a stream is faulted
+int launch_symsync(const float *x, float *y, uint32_t *ny, const float *mf, const float *dmf, float *hist, SymsyncState *st,
+                   uint32_t *fault_any, const SymsyncLaunch &l, hipStream_t s);
+
 // ---- time-parallel exact AGC [+ freqdem] tail (kernels_agc_tail.hip) ----
 struct AgcTailPlan;
 int agc_tail_create(uint32_t C, uint32_t max_nf, AgcTailPlan **out);

@@ -187,6 +187,46 @@ FmsDesign design_fmstereo(double quad_rate, uint32_t decim)
     return f;
 }
 
+// ---- symsync_rrrf_create_kaiser(k, m, beta, M) + set_lf_bw + set_output_rate (Liquid.chs:244-282), DESIGN.md 4.10 ----
+// liquid-dsp 1.3.2 as recalled (unpinned): H_len = 2 M k m + 1, Hf = liquid_firdes_kaiser(H_len, 0.75f / (k M), 40, 0) in f64,
+// H = Hf 2 0.75 rounded once to f32 (beta is ignored); the derivative, its scale and the loop filter in f32 as liquid does.
+SymsyncDesign design_symsync_kaiser(uint32_t k, uint32_t m, float beta, uint32_t M, float lf_bw, uint32_t k_out)
+{
+    (void)beta;
+    SymsyncDesign d;
+    d.k = k; d.m = m; d.M = M; d.k_out = k_out;
+    d.H_len = 2 * M * k * m + 1;
+    d.L = d.H_len / M;                                                   // firpfb: integer division drops the last tap
+    const float fc = 0.75f / (float)(k * M);
+    std::vector<double> hd = firdes_kaiser(d.H_len, (double)fc, 40.0);
+    const uint32_t N = d.H_len;
+    d.H.resize(N); d.dH.resize(N);
+    for (uint32_t i = 0; i < N; i++) d.H[i] = (float)(hd[i] * 1.5);
+    float hdh_max = 0.f;
+    for (uint32_t i = 0; i < N; i++) {
+        d.dH[i] = i == 0 ? d.H[1] - d.H[N - 1] : (i == N - 1 ? d.H[0] - d.H[i - 1] : d.H[i + 1] - d.H[i - 1]);
+        const float p = d.H[i] * d.dH[i];
+        if (std::fabs(p) > hdh_max || i == 0) hdh_max = std::fabs(p);
+    }
+    const float s = 0.06f / hdh_max;
+    for (uint32_t i = 0; i < N; i++) d.dH[i] = d.dH[i] * s;
+    d.mf.resize((size_t)d.L * M); d.dmf.resize((size_t)d.L * M);
+    for (uint32_t j = 0; j < d.L; j++)
+        for (uint32_t p = 0; p < M; p++) {
+            d.mf[(size_t)j * M + p] = d.H[p + (d.L - 1 - j) * M];          // loaded reversed: the newest sample meets H[p]
+            d.dmf[(size_t)j * M + p] = d.dH[p + (d.L - 1 - j) * M];
+        }
+    // set_lf_bw(bt): B = {0.22 bt, 0, 0}, A = {1 - 0.5 (1 - bt), -0.495 (1 - bt), 0}; iirfiltsos divides both by A[0]
+    const float alpha = 1.0f - lf_bw, lb = 0.22f * lf_bw, ha = 0.5f * alpha, hb = 0.495f * alpha;
+    const float A0 = 1.0f - ha, A1 = -hb, A2 = 0.0f;
+    d.b0 = lb / A0; d.b1 = 0.0f / A0; d.b2 = 0.0f / A0; d.a1 = A1 / A0; d.a2 = A2 / A0;
+    d.rate_adj = (float)(0.5 * (double)lf_bw);
+    d.init = SymsyncState{};
+    d.init.rate = (float)k / (float)k_out;                               // set_output_rate: rate = del = k / k_out
+    d.init.del = d.init.rate;
+    return d;
+}
+
 uint32_t nco_freq_word(float freq)
 {
     float p = (float)((double)freq * 0.159154943091895);   // freq / 2pi, rounded to f32

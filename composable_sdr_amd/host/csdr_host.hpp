@@ -292,6 +292,32 @@ inline Pipe<Array<float>, Array<float>> fmStereoPipe(float quad_rate, uint32_t d
     return p;
 }
 
+// ---- symSyncR k m beta M (Liquid.chs:244-282; set_lf_bw 0.05, set_output_rate 2) on the channel rows of one chunk: one
+// csdr_symsync handle with one stream per row for the whole run; row c of the output holds that stream's ny[c] samples ----
+inline Pipe<std::vector<Array<float>>, std::vector<Array<float>>> symSyncR(uint32_t k, uint32_t m, float beta, uint32_t M, uint32_t nchan,
+                                                                          uint32_t max_in)
+{
+    Pipe<std::vector<Array<float>>, std::vector<Array<float>>> p;
+    p.start = [=]() {
+        csdr_symsync *h = nullptr;
+        check(csdr_symsync_create(k, m, beta, M, 0.05f, 2, nchan, max_in, &h));
+        return std::shared_ptr<void>(h, [](void *q) { csdr_symsync_destroy(static_cast<csdr_symsync *>(q)); });
+    };
+    p.process = [nchan](void *rr, const std::vector<Array<float>> &rows) {
+        if (rows.size() != nchan || rows[0].empty()) return std::vector<Array<float>>(rows.size());   // nx = 0 -> [empty]
+        const size_t n = rows[0].size();
+        Array<float> x(nchan * n), y(nchan * n);
+        for (uint32_t c = 0; c < nchan; c++) std::copy(rows[c].begin(), rows[c].end(), x.begin() + c * n);
+        std::vector<uint32_t> ny(nchan);
+        check(csdr_symsync_process(static_cast<csdr_symsync *>(rr), x.data(), (uint32_t)n, y.data(), ny.data()));
+        std::vector<Array<float>> out;
+        for (uint32_t c = 0; c < nchan; c++) out.emplace_back(y.begin() + c * n, y.begin() + c * n + ny[c]);
+        return out;
+    };
+    p.done = [](void *) {};
+    return p;
+}
+
 // ---- the fused chain as a Pipe (replaces mix . mux (replicate nch demod) . firpfbchChannelizer nc) ----
 struct ChainOpts {
     uint32_t channels = 1; bool dc_block = true; float agc = 0.f; bool fm = false; bool am = false; bool wbfm = false; uint32_t decim = 4; float deemph_fc = 0.025f; float kf = 0.3f; bool mix = false;

@@ -1,5 +1,5 @@
 // soapy-sdr's file-input mode (apps/SoapySDR.hs:181-283) on the C-ABI chain:
-//   soapy_sdr_file --filename in.cf32 -n N -c M [--demod DeNo|DeNBFM kf|DeWBFM decim|DeFMS decim|DeAM] [-a dB] [-m] [-o output] [--chunksize 1024]
+//   soapy_sdr_file --filename in.cf32 -n N -c M [--demod DeNo|DeNBFM kf|DeWBFM decim|DeFMS decim|DeAM|DeNBFMSync k] [-a dB] [-m] [-o output] [--chunksize 1024]
 //                  [-s samplerate] [-b bandwidth] [--offset Hz] [--audio AU|WAV]
 //                  [--world W --rank R --id-file PATH [--id-nonce N] [--device D]]
 // --world W: one process per GPU, each reading the same file; process R owns the channels R, R + W, ... (interleaved channel shard,
@@ -110,12 +110,58 @@ static int run_fms(const std::string &in, const ChainOpts &o, size_t n, const st
     return 0;
 }
 
+// DeNBFMSync k (SoapySDR.hs:273-280): assembleFold with compact (4 k nch 1024) and, per channel, fmDemWithSync k . agc
+// (Liquid.chs:431-437): the chain's FM rows (kf = 0.02 k in f32, no mix) -> symSyncR k 4 0 64 with one stream per channel for the
+// whole run -> raw <out>.f32 / <out>_ch<j>.f32, or with -m the truncating left fold of the channels (Trans.hs:119-122) into one
+static int run_sync(const std::string &in, ChainOpts o, uint32_t k, size_t n, const std::string &out, size_t chunk)
+{
+    const uint32_t M = o.channels;
+    const bool mixed = o.mix && M > 1;
+    o.fm = true; o.kf = 0.02f * (float)k; o.mix = false; o.max_frames = 4 * k * 1024;
+    using Rows = std::vector<Array<float>>;
+    std::vector<std::shared_ptr<Fold<Array<float>>>> sinks;
+    if (mixed || M == 1) sinks.push_back(std::make_shared<FileSink<float>>(out + ".f32"));
+    else for (uint32_t c = 0; c < M; c++) sinks.push_back(std::make_shared<FileSink<float>>(out + "_ch" + std::to_string(c + 1) + ".f32"));
+    std::shared_ptr<Fold<Rows>> tail = std::make_shared<Distribute<float>>(sinks);
+    if (mixed) {
+        Pipe<Rows, Rows> mixp;
+        mixp.start = []() { return std::shared_ptr<void>(); };
+        mixp.process = [](void *, const Rows &rows) { return Rows{mix(rows)}; };
+        mixp.done = [](void *) {};
+        tail = addPipe(mixp, tail);
+    }
+    auto fold = compact<cf32>((size_t)4 * k * M * 1024, addPipe(fusedChain<float>(o), addPipe(symSyncR(k, 4, 0.f, 64, M, 4 * k * 1024), tail)));
+    FILE *f = std::fopen(in.c_str(), "rb");
+    if (!f) { std::cerr << "Unable to open source: " << in << "\n"; return 1; }
+    using CPipe = Pipe<Array<cf32>, Array<cf32>>;
+    const float fo = (float)(2.0 * 3.14159265358979323846 * g_front.offset / g_front.samplerate);
+    CPipe offset = fo > 0 ? mixDown(fo, (uint32_t)chunk) : (fo < 0 ? mixUp(-fo, (uint32_t)chunk) : idPipe<Array<cf32>>());
+    CPipe resamp = g_front.bandwidth != 0.0 ? resampler((float)(g_front.bandwidth / g_front.samplerate), 60.0f, (uint32_t)chunk)
+                                            : idPipe<Array<cf32>>();
+    auto prep = unPipe(compose(resamp, offset));
+    TakeN take(n);
+    Array<cf32> a(chunk);
+    while (true) {
+        a.resize(chunk);
+        const size_t got = std::fread(a.data(), sizeof(cf32), chunk, f);
+        if (!got) break;
+        a.resize(got);
+        Array<cf32> b = prep.process(a);
+        if (!take.feed(b)) break;
+        fold->step(b);
+    }
+    std::fclose(f);
+    fold->done();
+    prep.cleanup();
+    return 0;
+}
+
 int main(int argc, char **argv)
 {
     std::string in, out = "output", demod = "DeNo";
     ChainOpts o; o.flags = 0;
     size_t n = 1024, chunk = 1024;
-    std::string id_file; int device = -1; uint64_t id_nonce = 0; bool fms = false;
+    std::string id_file; int device = -1; uint64_t id_nonce = 0; bool fms = false; uint32_t sync_k = 0;
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
         auto next = [&]() -> const char * { if (i + 1 >= argc) { std::cerr << "missing value for " << a << "\n"; std::exit(2); } return argv[++i]; };
@@ -136,7 +182,8 @@ int main(int argc, char **argv)
         else if (a == "--id-nonce") id_nonce = std::strtoull(next(), nullptr, 10);
         else if (a == "--device") device = std::atoi(next());
         else if (a == "--demod") { demod = next(); if (demod == "DeNBFM") { o.fm = true; o.kf = (float)std::atof(next()); } else if (demod == "DeAM") o.am = true; else if (demod == "DeWBFM") { o.wbfm = true; o.decim = (uint32_t)std::atoi(next()); }
-                                     else if (demod == "DeFMS") { fms = true; o.decim = (uint32_t)std::atoi(next()); } }
+                                     else if (demod == "DeFMS") { fms = true; o.decim = (uint32_t)std::atoi(next()); }
+                                     else if (demod == "DeNBFMSync") { const int kk = std::atoi(next()); sync_k = kk > 0 ? (uint32_t)kk : 0xffffffffu; } }
         else { std::cerr << "unknown option " << a << "\n"; return 2; }
     }
     if (in.empty()) { std::cerr << "--filename is required (SoapySDR live sources are out of scope)\n"; return 2; }
@@ -144,9 +191,14 @@ int main(int argc, char **argv)
     if (o.world > 1 && o.channels % o.world) { std::cerr << "--world must divide -c\n"; return 2; }
     if (o.world > 1 && o.mix && id_file.empty()) { std::cerr << "--world with --mix needs --id-file (the communicator's bootstrap)\n"; return 2; }
     if (fms && (o.decim < 1 || o.world > 1 || o.mix)) { std::cerr << "DeFMS takes a decimation >= 1 and runs one stream (no --world, no --mix)\n"; return 2; }
+    if (sync_k && (sync_k > 8 || o.world > 1 || !g_front.audio.empty())) {
+        std::cerr << "DeNBFMSync takes k in [1, 8] (symSyncR k 4 0 64), writes raw .f32 and runs on one GPU (no --world, no --audio)\n";
+        return 2;
+    }
     try {
         o.device = device;
         if (fms) return run_fms(in, o, n, out, chunk);
+        if (sync_k) return run_sync(in, o, sync_k, n, out, chunk);
         // the communicator exists only where the path has an exchange step: --mix over channel shards (also a world of one, which
         // then runs the same C entry points)
         if (o.mix && o.channels > 1 && !id_file.empty()) o.comm = commFromIdFile(id_file, (int)o.rank, (int)o.world, device, id_nonce);

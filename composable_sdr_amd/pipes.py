@@ -260,6 +260,80 @@ def stereoFMDecoder(quadRate, decim, nchan=1, max_samples=1 << 16):
     return Pipe(lambda: FmStereo(quadRate, decim, nchan, max_samples), lambda r, a: r.process(a), lambda r: r.close())
 
 
+class SymSync:
+    """The `csdr_symsync_*` object: symSyncR k m beta npfb (set_lf_bw lf_bw, set_output_rate k_out) on `nchan` independent F32
+    streams (include/csdr.h)."""
+
+    def __init__(self, k, m=4, beta=0.0, npfb=64, nchan=1, max_samples=1 << 16, lf_bw=0.05, k_out=2):
+        h = C.c_void_p()
+        check(lib().csdr_symsync_create(int(k), int(m), float(beta), int(npfb), float(lf_bw), int(k_out), int(nchan),
+                                        int(max_samples), C.byref(h)))
+        self._h = _Handle(h, lib().csdr_symsync_destroy)
+        self.k, self.npfb, self.nchan = int(k), int(npfb), int(nchan)
+
+    @property
+    def h(self):
+        if not self._h.h:
+            raise CsdrError(_lib.ERR_INVALID, "symsync already destroyed")
+        return self._h.h
+
+    @property
+    def taps_len(self):
+        return int(lib().csdr_symsync_get_taps_len(self.h))
+
+    def taps(self):
+        """(mf, dmf), each [h_sub_len][npfb] as the kernel holds them"""
+        L = self.taps_len
+        mf, dmf = np.empty((L, self.npfb), np.float32), np.empty((L, self.npfb), np.float32)
+        check(lib().csdr_symsync_get_taps(self.h, _ptr(mf), _ptr(dmf)))
+        return mf, dmf
+
+    def state(self, chan=0):
+        """(tau, rate, del, q_hat) of stream `chan`; raises CsdrError (ERR_SIZE) when the stream is faulted"""
+        v = [C.c_float() for _ in range(4)]
+        check(lib().csdr_symsync_get_state(self.h, chan, *[C.byref(a) for a in v]))
+        return tuple(np.float32(a.value) for a in v)
+
+    def process_rows(self, x):
+        """[nchan][n] (or [n]) F32 -> (y [nchan][n], counts [nchan]): row c holds counts[c] outputs"""
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        n = x.size // self.nchan
+        y = np.empty((self.nchan, n), dtype=np.float32)
+        ny = np.zeros(self.nchan, dtype=np.uint32)
+        check(lib().csdr_symsync_process(self.h, _ptr(x), n, _ptr(y), ny.ctypes.data_as(C.POINTER(C.c_uint32))))
+        return y, ny
+
+    def process(self, x):
+        """[nchan][n] -> a list of nchan arrays (their lengths vary); [n] -> one array"""
+        y, ny = self.process_rows(x)
+        out = [y[c, :ny[c]] for c in range(self.nchan)]
+        return out[0] if np.ndim(x) == 1 else out
+
+    def process_device(self, d_x_ptr, n, d_y_ptr, d_ny_ptr, stream=0):
+        """Device-resident variant: raw device pointers (ints) for x [nchan][n], y [nchan][n], counts [nchan]; enqueues on
+        `stream`"""
+        check(lib().csdr_symsync_process_device(self.h, C.c_void_p(d_x_ptr), n, C.c_void_p(d_y_ptr), C.c_void_p(d_ny_ptr),
+                                                C.c_void_p(stream)))
+
+    def reset(self):
+        check(lib().csdr_symsync_reset(self.h))
+
+    def close(self):
+        self._h.close()
+
+
+def symSyncR(k, m=4, beta=0.0, M=64, nchan=1, max_samples=1 << 16):
+    """symSyncR k m beta M (Liquid.chs:244-282: set_lf_bw 0.05, set_output_rate 2) as a Pipe from F32 arrays ([nchan][n], or
+    [n]) to the synchronised samples: a list of per-stream arrays, or one array for [n]"""
+    return Pipe(lambda: SymSync(k, m, beta, M, nchan, max_samples), lambda r, a: r.process(a), lambda r: r.close())
+
+
+def fmDemWithSync(k, nchan=1, max_samples=1 << 16):
+    """fmDemWithSync k = symSyncR k 4 0 64 . fmDemodulator (0.02 * k) (Liquid.chs:431-437), the product taken in f32"""
+    kf = float(np.float32(0.02) * np.float32(k))
+    return compose(symSyncR(k, 4, 0.0, 64, nchan, max_samples), fmDemodulator(kf, nchan, max_samples))
+
+
 def resampler(r, as_db=60.0, max_samples=1 << 20):
     """resampler r as (Liquid.chs:115-117): Pipe IO (Array CF32) (Array CF32) with a variable-length output
     (`shrinkToFit` to the count msresamp_crcf_execute reports, :79-98).  r == 0 is the identity."""

@@ -237,6 +237,46 @@ int csdr_fmstereo_kernel_times(csdr_fmstereo *h, float *us5);
 int csdr_fmstereo_destroy(csdr_fmstereo *h);
 
 /* ------------------------------------------------------------------------ *
+ * symSyncR k m beta npfb  (Liquid.chs:244-282; fmDemWithSync k = symSyncR k 4 0 64 . fmDemodulator (0.02 k),
+ * Liquid.chs:431-437; DeNBFMSync k, SoapySDR.hs:273-280), `nchan` independent F32 streams.  Replaces
+ * symsync_rrrf_create_kaiser(k, m, beta, npfb) + set_lf_bw(lf_bw) + set_output_rate(k_out) + symsync_rrrf_execute
+ * through syncSym (Liquid.chs:196-221; the reference passes lf_bw 0.05 and k_out 2).  liquid-dsp 1.3.2 as recalled:
+ * unpinned.
+ *   design: H_len = 2 npfb k m + 1; H = liquid_firdes_kaiser(H_len, 0.75 / (k npfb), 40, 0) 2 0.75 (f64, rounded once;
+ *     beta ignored); dH[i] = H[i+1] - H[i-1] wrapping at both ends, scaled by 0.06 / max |H[i] dH[i]|; two firpfb banks of
+ *     npfb sub-filters of h_sub_len = H_len / npfb = 2 k m taps, sub-filter p = H[p + j npfb] reversed (newest sample
+ *     meets H[p]).  Loop filter (set_lf_bw bt): B = {0.22 bt, 0, 0}, A = {1 - 0.5 (1 - bt), -0.495 (1 - bt), 0} / A[0]
+ *     in direct form II; rate_adjustment 0.5 bt.  Initial rate = del = k / k_out, tau = bf = b = 0, decim_counter 0.
+ *   per input sample: push x; while b < npfb { y = MF_b / k; if decim_counter == k_out { decim_counter = 0;
+ *     q = clip(MF_b dMF_b, -1, 1); q_hat = iir(q); rate += rate_adjustment q_hat; del = rate + q_hat }
+ *     decim_counter++; tau += del; bf = tau npfb; b = roundf(bf) }; then tau -= 1, bf -= npfb, b -= npfb.
+ *   Arithmetic: plain f32 without contraction; each dot product summed oldest sample first, starting from the first
+ *     product; roundf; a correctly rounded / k.  The output does not depend on the chunking, bit for bit.
+ *   Limits (create, else CSDR_ERR_INVALID): k >= k_out >= 1, m >= 1, 2 k m <= 64, npfb in [1, 256], 2 k m npfb <= 4096,
+ *     lf_bw in [0, 1].
+ *   x is [nchan][n]; y is [nchan][n] (row stride n: the reference's ny = nx buffer), row c holding ny[c] outputs
+ *     (about n k_out / k).
+ * DEVIATION: a stream that would take del <= 0, index a bank outside [0, npfb) or write more than n
+ * outputs in one call (the reference loops for ever or overruns its buffer there) stops producing for the call and is
+ * marked faulted; the mark is sticky until reset, a faulted stream yields 0 outputs, and csdr_symsync_process returns
+ * CSDR_ERR_SIZE (csdr_symsync_get_state reports it per stream).
+ * ------------------------------------------------------------------------ */
+typedef struct csdr_symsync csdr_symsync;
+int csdr_symsync_create(uint32_t k, uint32_t m, float beta, uint32_t npfb, float lf_bw, uint32_t k_out, uint32_t nchan,
+                        uint32_t max_samples, csdr_symsync **out);
+int csdr_symsync_process(csdr_symsync *h, const float *x, uint32_t n, float *y, uint32_t *ny);
+/* device buffers: d_x [nchan][n] F32, d_y [nchan][n] F32, d_ny [nchan] uint32; enqueued on `stream`, no synchronisation
+ * (a fault shows in csdr_symsync_get_state or the next csdr_symsync_process) */
+int csdr_symsync_process_device(csdr_symsync *h, const void *d_x, uint32_t n, void *d_y, void *d_ny, void *stream);
+int csdr_symsync_reset(csdr_symsync *h);                         /* back to the state right after create            */
+/* tau, rate, del, q_hat of stream `chan` after the last call (synchronises); CSDR_ERR_SIZE when the stream is faulted */
+int csdr_symsync_get_state(csdr_symsync *h, uint32_t chan, float *tau, float *rate, float *del, float *q_hat);
+uint32_t csdr_symsync_get_taps_len(const csdr_symsync *h);       /* h_sub_len = 2 k m                                */
+/* both banks as the kernel holds them, tap-major [h_sub_len][npfb]: mf[j npfb + p] = H[p + (h_sub_len - 1 - j) npfb] */
+int csdr_symsync_get_taps(const csdr_symsync *h, float *mf, float *dmf);
+int csdr_symsync_destroy(csdr_symsync *h);
+
+/* ------------------------------------------------------------------------ *
  * The fused chain: everything assembleFold (apps/SoapySDR.hs:208-226) puts
  * behind `compact`:
  *     dcBlocker                                   (SoapySDR.hs:213-214)

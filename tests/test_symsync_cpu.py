@@ -1,0 +1,158 @@
+"""Symbol timing recovery (symSyncR / DeNBFMSync) without a GPU: the CPU restatement's design and behaviour,
+and the new C ABI / Python / C++ surface being present (creating the object must fail loudly with no device)."""
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import symsync_restatement as S
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+f32 = np.float32
+
+
+def test_design_of_the_reference_settings():
+    P = S.design(4, 4, 64, 0.05, 2)
+    assert (P["H_len"], P["L"]) == (2049, 32)
+    assert P["mf"].shape == P["dmf"].shape == (32, 64)
+    # every matched sub-filter passes DC with a gain of about k
+    assert np.all(np.abs(P["mf"].sum(axis=0) - 4.0) < 0.03)
+    assert np.abs(P["H"] * P["dH"]).max() == pytest.approx(0.06, rel=1e-6)
+    # the banks are H / dH reversed per phase: the newest sample meets H[p]
+    assert np.array_equal(P["mf"][-1], P["H"][:64]) and np.array_equal(P["mf"][0], P["H"][31 * 64:32 * 64])
+    alpha = f32(1) - f32(0.05)
+    A0 = f32(1) - f32(0.5) * alpha
+    assert P["b0"] == (f32(0.22) * f32(0.05)) / A0 and P["a1"] == -(f32(0.495) * alpha) / A0
+    assert P["b1"] == P["b2"] == P["a2"] == 0 and P["rate_adj"] == f32(0.025)
+    s = S.SymSync(1)
+    assert s.dl[0] == s.rate[0] == f32(2.0)
+
+
+def _fsk(nsym=3000, offset=0.37, ppm=200.0, seed=1):
+    x, bits = S.nrz_fsk_iq(nsym, k=4, offset=offset, ppm=ppm, seed=seed)
+    return S.freqdem(x, f32(0.08)), bits
+
+
+@pytest.mark.parametrize("offset,ppm", [(0.37, 200.0), (2.9, -200.0)])
+def test_timing_recovery_locks_on_fsk(offset, ppm):
+    """k = 4 NRZ FSK with a fractional timing offset and a 200 ppm clock error: after 500 symbols every decision at the loop's
+    sampling instants is right and the eye there is open by more than 0.8 of the amplitude (deviation / kf = 1.25)"""
+    m, bits = _fsk(offset=offset, ppm=ppm)
+    outs, _, marks, s = S.run_calls(m, [m.size])
+    y, mk = outs[0], marks[0]
+    assert abs(y.size - m.size / 2) < 4                        # k_out / k = 1/2 output per input sample
+    e, n, lag, _ = S.decide(y, mk, bits, 500)
+    eye = np.abs(y[mk][500:500 + n]).min() / 1.25
+    print(f"offset {offset} ppm {ppm}: {e} errors in {n} symbols (lag {lag}), eye {eye:.3f}, rate {s.rate[0]:.6f}")
+    assert e == 0 and n > 2000 and eye > 0.8
+
+
+def test_chunking_is_bit_identical():
+    m, _ = _fsk(nsym=1500)
+    one = S.run_calls(m, [m.size])[0][0]
+    for c in (1, 7, 4096):
+        calls = [c] * (m.size // c) + ([m.size % c] if m.size % c else [])
+        got = S.run_calls(m, calls)[0][0]
+        assert np.array_equal(got.view(np.uint32), one.view(np.uint32)), c
+
+
+def test_streams_are_independent():
+    m, _ = _fsk(nsym=600)
+    X = np.stack([m, -m, np.roll(m, 3)])
+    outs, counts, _, _ = S.run_calls(X, [1000, 1397])
+    for r in range(3):
+        single = S.run_calls(X[r], [1000, 1397])[0][0]
+        assert np.array_equal(outs[r].view(np.uint32), single.view(np.uint32))
+
+
+def test_fault_rule_stops_and_sticks_until_reset():
+    """a steep, huge decaying exponential keeps q at -1 and drives del to <= 0: the stream stops producing within the call's
+    capacity, is flagged and stays silent in later calls; the other stream is untouched; reset clears the flag"""
+    n = 8192
+    r = (1e36 * np.exp(-np.arange(n) / 100.0)).astype(f32)
+    m, _ = _fsk(nsym=n // 4 + 2)
+    X = np.stack([r, m[:n]])
+    s = S.SymSync(2)
+    y, ny = s.process(X)
+    assert s.fault.tolist() == [True, False]
+    assert 0 < ny[0] <= n and not (s.dl[0] > 0)
+    y2, ny2 = s.process(X)
+    assert ny2[0] == 0 and ny2[1] > 0
+    got = np.concatenate([y[1, :ny[1]], y2[1, :ny2[1]]])
+    assert np.array_equal(got.view(np.uint32), S.run_calls(np.concatenate([m[:n], m[:n]]), [n, n])[0][0].view(np.uint32))
+    s.reset()
+    assert not s.fault.any() and s.dl[0] == f32(2.0)
+
+
+def test_header_library_and_signatures_carry_symsync():
+    import ctypes as C
+    import composable_sdr_amd as cs
+    from composable_sdr_amd import _lib
+    hdr = open(os.path.join(ROOT, "include", "csdr.h")).read()
+    names = ["csdr_symsync_create", "csdr_symsync_process", "csdr_symsync_process_device", "csdr_symsync_reset",
+             "csdr_symsync_get_state", "csdr_symsync_get_taps_len", "csdr_symsync_get_taps", "csdr_symsync_destroy"]
+    if not os.path.exists(cs.lib_path()):
+        cs.build_library()
+    lib = C.CDLL(cs.lib_path())
+    for n in names:
+        assert n + "(" in hdr and n in _lib.SIGNATURES and hasattr(lib, n), n
+    assert cs.SymSync and cs.symSyncR and cs.fmDemWithSync
+
+
+@pytest.mark.parametrize("args", [(2, 4, 0.0, 64, 0.05, 3), (4, 4, 0.0, 64, 0.05, 0), (9, 4, 0.0, 64, 0.05, 2),
+                                  (4, 4, 0.0, 257, 0.05, 2), (4, 4, 0.0, 0, 0.05, 2), (4, 4, 0.0, 129, 0.05, 2),
+                                  (4, 4, 0.0, 64, 1.5, 2), (4, 0, 0.0, 64, 0.05, 2)])
+def test_create_rejects_out_of_range_settings(args):
+    """k >= k_out >= 1, m >= 1, 2 k m <= 64, npfb in [1, 256], 2 k m npfb <= 4096, lf_bw in [0, 1]: checked before the device"""
+    import ctypes as C
+    import composable_sdr_amd as cs
+    h = C.c_void_p()
+    k, m, beta, npfb, bw, k_out = args
+    assert cs.lib().csdr_symsync_create(k, m, beta, npfb, bw, k_out, 1, 1024, C.byref(h)) == -1
+
+
+def test_symsync_without_gpu_is_nodev():
+    import torch
+    if torch.cuda.is_available():
+        pytest.skip("GPU present")
+    import composable_sdr_amd as cs
+    with pytest.raises(cs.CsdrError) as e:
+        cs.symSyncR(4, 4, 0.0, 64)._start()
+    assert e.value.code == -3
+
+
+def test_cpp_host_parses_denbfmsync(tmp_path):
+    """`--demod DeNBFMSync 4` is an option of the C++ host (it used to stop with "unknown option 4")"""
+    exe = os.path.join(ROOT, "composable_sdr_amd", "host", "soapy_sdr_file")
+    if not os.path.exists(exe):
+        subprocess.check_call(["make", "-C", os.path.dirname(exe), "-s"])
+    r = subprocess.run([exe, "--filename", "/nonexistent.cf32", "-n", "16", "--demod", "DeNBFMSync", "4", "-o",
+                        str(tmp_path / "sync")], capture_output=True, text=True, timeout=120, env=dict(os.environ, CSDR_QUIET="1"))
+    assert "unknown option" not in r.stderr, r.stderr
+    assert r.returncode != 2, r.stderr
+
+
+def test_symsync_kernel_has_no_scratch_and_no_contraction(tmp_path):
+    """k_symsync keeps its state and the staged block in registers / LDS; its only fused multiply-adds are the correctly rounded
+    division's v_div_scale / v_div_fmas / v_div_fixup sequence"""
+    import re
+    import shutil
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    if not os.path.exists(hipcc):
+        pytest.skip("hipcc not available")
+    src = os.path.join(ROOT, "composable_sdr_amd", "csrc", "kernels_symsync.hip")
+    out = subprocess.run([hipcc, "-O3", "-std=c++17", "--offload-arch=gfx950", "-c", src, "-o", str(tmp_path / "ss.o"),
+                          "-Rpass-analysis=kernel-resource-usage"], capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-2000:]
+    blocks = {b.splitlines()[0]: b for b in re.split(r"remark: Function Name: ", out.stderr)[1:]}
+    names = [n for n in blocks if "k_symsync" in n]
+    assert len(names) == 1
+    b = blocks[names[0]]
+    assert int(re.search(r"ScratchSize \[bytes/lane\]: (\d+)", b).group(1)) == 0
+    assert int(re.search(r"VGPRs Spill: (\d+)", b).group(1)) == 0
+    asm = subprocess.run([hipcc, "-O3", "-std=c++17", "--offload-arch=gfx950", "--cuda-device-only", "-S", src, "-o", "-"],
+                         capture_output=True, text=True, timeout=600).stdout
+    assert "v_div_scale_f32" in asm and "v_div_fmas_f32" in asm and "v_div_fixup_f32" in asm
+    fmas = re.findall(r"^\s+(v_fma\w*|v_fmac\w*|v_mad\w*f32|v_pk_fma\w*)", asm, re.M)
+    assert len(fmas) <= 5, fmas                                 # the division's Newton-Raphson steps only
