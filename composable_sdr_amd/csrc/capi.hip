@@ -22,7 +22,9 @@ namespace {
 
 struct DevGuard {
     int prev = -1; bool ok = true;
-    explicit DevGuard(int dev) {
+    DevGuard() = default;
+    explicit DevGuard(int dev) { select(dev); }
+    void select(int dev) {
         if (hipGetDevice(&prev) != hipSuccess) { ok = false; return; }
         if (dev >= 0 && dev != prev && hipSetDevice(dev) != hipSuccess) ok = false;
     }
@@ -108,13 +110,13 @@ struct csdr_chain {
     csdr_chain_cfg cfg;
     int device;
     uint32_t M, p, C, c0, max_nf; uint64_t max_nx;
-    bool use_fused = false;
     std::string path;
     // design
     std::vector<float> taps;
     uint32_t theta = 0, d_theta = 0, tab_len = 0, tab_pos = 0;
     DcParams dc; AgcParams agc; float fm_ref = 0.f;
-    // device memory
+    // device memory (mem frees every buffer below with the handle)
+    DeviceBuffers mem;
     float *d_taps = nullptr;
     float2 *d_tw = nullptr, *d_nco_tab = nullptr, *d_dcstate = nullptr, *d_scratch = nullptr;
     uint32_t G = 1;                  // chan_stride: interleaved shard g = c0 of G (generic route, pruned DFT)
@@ -138,12 +140,9 @@ struct csdr_chain {
     HostSlot slot[CSDR_CHAIN_INFLIGHT];
     hipStream_t s_in = nullptr, s_k = nullptr, s_out = nullptr;
     uint32_t q_head = 0, q_count = 0;      // oldest pending slot, number of pending chunks
-    FusedPlan *fused = nullptr;
-    SmallPlan *small = nullptr;
-    BigPlan *big = nullptr;          // M = 1024 run kernel
-    HugePlan *huge = nullptr;        // M = 4096: branch-tiled front kernel + 1024-point back kernel (kernels_pfb4096.hip)
+    ChainPlan *plan = nullptr;       // the fused route's plan (fused.h); null: the any-M route (chain_generic)
     DcTilePlan *dctile = nullptr;   // generic path with the DC blocker: single-pass scan kernel
-    uint32_t n_cus = 256;            // compute units of the device (run count of the fused M = 1024 kernel)
+    uint32_t n_cus = 256;            // compute units of the device (run counts of k_pfb1024 and of the plans: FusedConfig::cus)
     AgcTailPlan *agc_tail = nullptr; // AGC on: time-parallel verified tail (unless CSDR_FLAG_AGC_SEQUENTIAL)
     // DeAM: the chain runs as DeNo into d_amz, then the ampmodem peak detector (kernels_am.hip) [+ mix]
     bool tail_only = false;          // CSDR_FLAG_TAIL_ONLY: AGC [+ freqdem] [+ mix] on a channel-major CF32 plane
@@ -160,13 +159,16 @@ struct csdr_chain {
     hipEvent_t e_pd_done[2] = {nullptr, nullptr}, e_pd_tail[3] = {nullptr, nullptr, nullptr}, e_serial = nullptr;
     bool pd_used[2] = {false, false}, pd_tail_rec = false, serial_pending = false, in_submit = false;
     uint32_t pd_count = 0, pd_indep_calls = 0;
-    bool call_indep = false; hipEvent_t call_ev_tail = nullptr;     // handed to the fused plan by the call in progress
+    bool call_indep = false; hipEvent_t call_ev_tail = nullptr;     // handed to the plan by the call in progress
     // entry points share the handle's state: a call on a caller's stream is remembered so that the host-buffer entry point
     // (own stream s_k) can order itself behind it, and the other way round
     // (a handle-owned event recorded on the caller's stream behind the call's work: the caller may destroy the stream afterwards)
     hipEvent_t e_user = nullptr; bool user_stream_dirty = false;
     bool pd_last_indep = false;      // the previous csdr_chain_submit_device call ran as an independent launch
 };
+
+// a device buffer of the chain: n elements of T (at least one), freed with the handle
+template <class T> static int chain_alloc(csdr_chain *h, T **p, size_t n) { return h->mem.alloc(p, sizeof(T) * (n ? n : 1)); }
 
 extern "C" {
 
@@ -860,33 +862,37 @@ int csdr_symsync_get_taps(const csdr_symsync *h, float *mf, float *dmf)
 // between its run-sized and its chunk-sized kernel by the call's frame count (the thresholds are part of the row's text).
 // ---------------------------------------------------------------------------
 namespace {
-enum RoutePlan { PLAN_FUSED256, PLAN_SMALL64, PLAN_BIG1024, PLAN_HUGE4096, PLAN_GENERIC };
 constexpr uint32_t ST1 = 1u << 1, ST2 = 1u << 2, ST4 = 1u << 4, ST8 = 1u << 8, ST_ANY = ~0u;
 struct RouteRow {
     uint32_t M;                 // channels the row is for; 0: any count
     uint32_t strides;           // bit g: chan_stride g accepted (bit 1: whole band or a contiguous shard)
-    RoutePlan plan;
+    bool (*supported)(uint32_t M, uint32_t p);              // the plan takes M channels of p taps per branch
+    int (*create)(const FusedConfig &cfg, ChainPlan **out); // null: the any-M route (chain_generic)
+    const char *path_prefix;    // csdr_chain_path: prefix + the plan's kernel name [+interleaved-shard] [+agc]
+    // shortest window of the plan: WU = 6 read-only warm-up tiles of 4096 samples (k_run256v2, k_run64v2, k_run1024v3, k_run1024v2),
+    // H_WU = 7 frames of 4096 samples in front of a k_front4096 run
+    double dc_window;
     const char *name, *run_sized, *other, *agc_tail;
 };
 const RouteRow ROUTES[] = {
-    {256, ST1 | ST2 | ST4 | ST8, PLAN_FUSED256, "fused-256",
+    {256, ST1 | ST2 | ST4 | ST8, plan256_supported, plan256_create, "fused-256|", 6 * 4096.0, "fused-256",
      "k_run256v2<FM | CF32[, G]> (whole band: calls of >= 1024 whole tiles of 16 frames; interleaved shards G = 2, 4, 8: every whole tile)",
      "k_tile256<FM | CF32> (look-back tile kernel: chunk-sized calls, ragged ends, and contiguous channel shards at every size) [+ k_shard_gather]",
      "channelizer -> CF32 plane (tile-major for run-sized calls of whole tiles) -> k_agc_spec_tm | k_agc_spec -> k_agc_fix [-> k_mix]"},
-    {64, ST1, PLAN_SMALL64, "fused-k_run64",
+    {64, ST1, plan64_supported, plan64_create, "fused-", 6 * 4096.0, "fused-k_run64",
      "k_run64v2 (CF32 output, whole band, nf % 64 == 0, >= 8 tiles of 64 frames per run)", "k_run64<FM | CF32> (FM output, shards, ragged calls)",
      "k_run64v2 -> CF32 plane (tile-major, run-sized calls) -> k_agc_spec_tm | k_run64<CF32> -> k_agc_spec; -> k_agc_fix [-> k_mix]"},
-    {1024, ST1 | ST2 | ST4 | ST8, PLAN_BIG1024, "fused-k_run1024",
+    {1024, ST1 | ST2 | ST4 | ST8, plan1024_supported, plan1024_create, "fused-", 6 * 4096.0, "fused-k_run1024",
      "k_run1024v3<FM | CF32> (whole band, calls of whole 4-frame tiles; a call that ends inside a 128-byte line stores the front part of it); "
      "k_shard1024<FM | CF32, G> (interleaved shards G = 4, 8: fold of the aliasing branches behind the FIR + a (1024 / G)-point DFT across the lanes; run-sized calls of whole tiles); "
      "k_run1024v2<FM, 2> (interleaved shards G = 2, FM output)",
      "k_run1024<FM | CF32> (ragged calls, contiguous shards, the other calls of interleaved shards) [+ k_pfb1024_fixup, k_shard_gather1024]", "k_run1024v3<CF32> -> CF32 plane (tile-major) -> k_agc_spec_tm | k_run1024<CF32> -> k_agc_spec; -> k_agc_fix [-> k_mix]"},
-    {4096, ST1, PLAN_HUGE4096, "fused-4096",
+    {4096, ST1, plan4096_supported, plan4096_create, "fused-4096|", 7 * 4096.0, "fused-4096",
      "k_front4096 (DC blocker + pre-mix + FIR, branch-tiled: four sibling workgroups per frame, radix-4 split of the DFT on the registers) -> z (8 B / sample) "
      "-> k_back4096<CF32 | FM | FM,mix> (four 1024-point DFTs per frame, 16-frame blocks, whole 128-byte lines per row) [-> k_mix4096_finish]; whole band; "
      "DeNo --mix without the AGC keeps the any-M route's mix identity",
      "the same kernels (any call size; short calls use fewer runs)", "k_front4096 -> k_back4096<CF32> -> CF32 plane (tile-major: calls of whole 16-frame blocks, >= 4096 frames) -> k_agc_spec_tm | k_agc_spec -> k_agc_fix [-> k_mix]"},
-    {0, ST_ANY, PLAN_GENERIC, "generic",
+    {0, ST_ANY, nullptr, nullptr, nullptr, 0.0, "generic",
      "k_dc_tile -> k_pfb_fir (M = 1024, forced generic: k_pfb1024) -> k_fft_r16 | k_fft_pow2 | k_dft_direct [interleaved shard: k_fold + (M / G)-point DFT] "
      "-> k_transpose_fm | k_mix_frames | k_transpose;  DeNo --mix over all channels: k_dc_fold + k_mixid_finish (M % 4096 == 0) | k_dc_tile + k_branch0_fir "
      "(the sum of all bins of a frame is M x branch 0);  DeNo --mix of an interleaved shard (M % 4096 == 0, G = 2, 4, 8): k_dc_fold8 + k_mixid_shard_finish "
@@ -901,14 +907,9 @@ const RouteRow *route_select(uint32_t M, uint32_t p, uint32_t G, uint32_t flags,
     if (M <= 1 || (flags & CSDR_FLAG_FORCE_GENERIC)) return generic;
     if (G > 1 && diag_env("CSDR_SHARD_GENERIC")) return generic;
     for (const RouteRow &r : ROUTES) {
-        if (r.M != M || !(G < 32 && (r.strides >> G) & 1u)) continue;
-        // shortest window of the plan: WU = 6 read-only warm-up tiles of 4096 samples (k_run256v2, k_run64v2, k_run1024v3, k_run1024v2),
-        // H_WU = 7 frames of 4096 samples in front of a k_front4096 run
-        if (dc && r.plan != PLAN_GENERIC && !dc_window_ok(*dc, (r.plan == PLAN_HUGE4096 ? 7 : 6) * 4096.0)) continue;
-        const bool ok = r.plan == PLAN_FUSED256 ? fused_supported(M, p) : r.plan == PLAN_SMALL64 ? small_supported(M, p)
-                      : r.plan == PLAN_BIG1024 ? (big_supported(M, p) && !diag_env("CSDR_NO_RUN1024"))
-                      : r.plan == PLAN_HUGE4096 ? (huge_supported(M, p) && !diag_env("CSDR_NO_RUN4096")) : true;
-        if (ok) return &r;
+        if (r.M != M || !(G < 32 && (r.strides >> G) & 1u)) continue;     // (the any-M row has M = 0)
+        if (dc && !dc_window_ok(*dc, r.dc_window)) continue;
+        if (r.supported(M, p)) return &r;
     }
     return generic;
 }
@@ -980,10 +981,7 @@ static int chain_init_state(csdr_chain *h, hipStream_t s)
         CSDR_HIP(hipMemsetAsync(h->d_amq[0], 0, sizeof(float) * h->C, s));     // ampmodem_reset: q_hat = 0
         CSDR_HIP(hipMemsetAsync(h->d_amq[1], 0, sizeof(float) * h->C, s));
     }
-    if (h->fused) { int r = fused_reset(h->fused, s); if (r) return r; }
-    if (h->small) { int r = small_reset(h->small, s); if (r) return r; }
-    if (h->big) { int r = big_reset(h->big, s); if (r) return r; }
-    if (h->huge) { int r = huge_reset(h->huge, s); if (r) return r; }
+    if (h->plan) { int r = h->plan->reset(s); if (r) return r; }
     if (h->dctile) { int r = dctile_reset(h->dctile, s); if (r) return r; }
     return 0;
 }
@@ -1021,12 +1019,12 @@ int csdr_chain_create(const csdr_chain_cfg *cfg_in, csdr_chain **out)
         h->agc = make_agc(cfg->agc_threshold_db);
         if (cfg->demod == CSDR_DEMOD_FM) h->fm_ref = fm_ref_of(cfg->kf);
         auto failt = [&](int code) { csdr_chain_destroy(h); return code; };
-        if ((r = dev_alloc(&h->d_dcstate, 1))) return failt(r);
-        if ((r = dev_alloc(&h->d_agc, h->C))) return failt(r);
-        if (cfg->demod == CSDR_DEMOD_FM && ((r = dev_alloc(&h->d_rp[0], h->C)) || (r = dev_alloc(&h->d_rp[1], h->C)))) return failt(r);
-        if (cfg->mix && h->C > 1 && (r = dev_alloc(&h->d_B, (size_t)h->C * h->max_nf))) return failt(r);
+        if ((r = chain_alloc(h, &h->d_dcstate, 1))) return failt(r);
+        if ((r = chain_alloc(h, &h->d_agc, h->C))) return failt(r);
+        if (cfg->demod == CSDR_DEMOD_FM && ((r = chain_alloc(h, &h->d_rp[0], h->C)) || (r = chain_alloc(h, &h->d_rp[1], h->C)))) return failt(r);
+        if (cfg->mix && h->C > 1 && (r = chain_alloc(h, &h->d_B, (size_t)h->C * h->max_nf))) return failt(r);
         if (!(cfg->flags & CSDR_FLAG_AGC_SEQUENTIAL)) { if ((r = agc_tail_create(h->C, h->max_nf, &h->agc_tail))) return failt(r); }
-        else if ((r = dev_alloc(&h->d_A, (size_t)h->C * h->max_nf))) return failt(r);        // the one-lane-per-channel kernel works in place
+        else if ((r = chain_alloc(h, &h->d_A, (size_t)h->C * h->max_nf))) return failt(r);        // the one-lane-per-channel kernel works in place
         h->path = std::string("tail-only+agc") + (h->agc_tail ? "-spec" : "");
         h->timed_kernel = "k_agc_spec";
         if ((r = chain_init_state(h, nullptr))) return failt(r);
@@ -1073,19 +1071,19 @@ int csdr_chain_create(const csdr_chain_cfg *cfg_in, csdr_chain **out)
     if (cfg->demod == CSDR_DEMOD_FM) h->fm_ref = fm_ref_of(cfg->kf);
 
     auto fail = [&](int code) { csdr_chain_destroy(h); return code; };
-    if ((r = dev_alloc(&h->d_dcstate, 1))) return fail(r);
-    if ((r = dev_alloc(&h->d_scratch, 2 * (size_t)(h->max_nx / DC_BLOCK + 2)))) return fail(r);
+    if ((r = chain_alloc(h, &h->d_dcstate, 1))) return fail(r);
+    if ((r = chain_alloc(h, &h->d_scratch, 2 * (size_t)(h->max_nx / DC_BLOCK + 2)))) return fail(r);
 
     if (M > 1) {
         h->taps = design_pfb_taps(M, m, As);
         h->d_theta = nco_freq_word(pfb_premix_freq(M));
         h->tab_len = nco_period(h->d_theta, 1u << 17);
-        if ((r = dev_alloc(&h->d_taps, h->taps.size()))) return fail(r);
+        if ((r = chain_alloc(h, &h->d_taps, h->taps.size()))) return fail(r);
         CSDR_HIP_CLEAN(hipMemcpy(h->d_taps, h->taps.data(), sizeof(float) * h->taps.size(), hipMemcpyHostToDevice), csdr_chain_destroy(h));
         if (h->tab_len) {
             std::vector<float2> tab(h->tab_len);
             for (uint32_t i = 0; i < h->tab_len; i++) { float c, s; nco_phasor(i * h->d_theta, &c, &s); tab[i] = make_float2(c, s); }
-            if ((r = dev_alloc(&h->d_nco_tab, h->tab_len))) return fail(r);
+            if ((r = chain_alloc(h, &h->d_nco_tab, h->tab_len))) return fail(r);
             CSDR_HIP_CLEAN(hipMemcpy(h->d_nco_tab, tab.data(), sizeof(float2) * h->tab_len, hipMemcpyHostToDevice), csdr_chain_destroy(h));
         }
         std::vector<float2> tw(M);
@@ -1093,11 +1091,11 @@ int csdr_chain_create(const csdr_chain_cfg *cfg_in, csdr_chain **out)
             double a = -2.0 * 3.14159265358979323846 * (double)i / (double)M;
             tw[i] = make_float2((float)std::cos(a), (float)std::sin(a));
         }
-        if ((r = dev_alloc(&h->d_tw, M))) return fail(r);
+        if ((r = chain_alloc(h, &h->d_tw, M))) return fail(r);
         CSDR_HIP_CLEAN(hipMemcpy(h->d_tw, tw.data(), sizeof(float2) * M, hipMemcpyHostToDevice), csdr_chain_destroy(h));
     }
-    if (cfg->agc_threshold_db != 0.0f && (r = dev_alloc(&h->d_agc, C))) return fail(r);
-    if (cfg->demod == CSDR_DEMOD_FM && ((r = dev_alloc(&h->d_rp[0], C)) || (r = dev_alloc(&h->d_rp[1], C)))) return fail(r);
+    if (cfg->agc_threshold_db != 0.0f && (r = chain_alloc(h, &h->d_agc, C))) return fail(r);
+    if (cfg->demod == CSDR_DEMOD_FM && ((r = chain_alloc(h, &h->d_rp[0], C)) || (r = chain_alloc(h, &h->d_rp[1], C)))) return fail(r);
 
     // Path selection: the fused kernels cover M = 256 (DC blocker + pre-mix + PFB [+ freqdem]).
     // With the AGC on, the fused kernel stops at the channel-major CF32 samples and the
@@ -1105,49 +1103,34 @@ int csdr_chain_create(const csdr_chain_cfg *cfg_in, csdr_chain **out)
     // interleaved shards: the fused M = 256 chain takes strides 2, 4, 8 (k_run256v2<.., G>); every other shape the any-M route with a pruned DFT
     const DcParams *dcp = cfg->dc_block ? &h->dc : nullptr;
     const RouteRow *route = route_select(M, h->p, G, cfg->flags, dcp);     // the one place a configuration is mapped to a plan (table above)
-    if (route->plan == PLAN_HUGE4096 && (C != M || (cfg->mix && cfg->demod == CSDR_DEMOD_NONE && cfg->agc_threshold_db == 0.0f && !am)))
+    if (route->M == 4096 && (C != M || (cfg->mix && cfg->demod == CSDR_DEMOD_NONE && cfg->agc_threshold_db == 0.0f && !am)))
         route = route_select(M, h->p, G, cfg->flags | CSDR_FLAG_FORCE_GENERIC, dcp);   // contiguous shards; DeNo --mix over all channels (= M x branch 0: nothing beats not computing
                                                                                    // the bank; CSDR_FLAG_NO_MIX_IDENTITY's full bank + DFT + sum stays on the any-M kernels too)
-    h->use_fused = route->plan != PLAN_GENERIC;
-    if (h->use_fused) {
+    if (route->create) {
         const bool agc_on = cfg->agc_threshold_db != 0.0f;
         FusedConfig fc{};
         fc.M = M; fc.p = h->p; fc.C = C; fc.c0 = c0; fc.max_nf = h->max_nf; fc.G = G;
         fc.dc_block = cfg->dc_block != 0; fc.dc = h->dc;
         fc.fm = cfg->demod == CSDR_DEMOD_FM && !agc_on; fc.fm_ref = h->fm_ref;
-        fc.mix = cfg->mix != 0 && !agc_on; fc.taps = h->taps.data(); fc.d_theta = h->d_theta;
-        if (route->plan == PLAN_SMALL64) {
-            if ((r = small_create(fc, &h->small))) return fail(r);
-            h->path = std::string("fused-") + small_name(h->small) + (agc_on ? "+agc" : "");
-            h->timed_kernel = small_name(h->small);
-        } else if (route->plan == PLAN_HUGE4096) {
-            if ((r = huge_create(fc, &h->huge))) return fail(r);
-            h->path = std::string("fused-4096|") + huge_name(h->huge) + (agc_on ? "+agc" : "");
-            h->timed_kernel = huge_name(h->huge);
-        } else if (route->plan == PLAN_BIG1024) {
-            if ((r = big_create(fc, &h->big))) return fail(r);
-            h->path = std::string("fused-") + big_name(h->big) + (G > 1 ? "+interleaved-shard" : "") + (agc_on ? "+agc" : "");
-            h->timed_kernel = big_name(h->big);
-        } else {
-            if ((r = fused_create(fc, &h->fused))) return fail(r);
-            h->path = std::string("fused-256|") + fused_name(h->fused) + (G > 1 ? "+interleaved-shard" : "") + (agc_on ? "+agc" : "");
-            h->timed_kernel = fused_name(h->fused);
-        }
+        fc.mix = cfg->mix != 0 && !agc_on; fc.taps = h->taps.data(); fc.d_theta = h->d_theta; fc.cus = h->n_cus;
+        if ((r = route->create(fc, &h->plan))) return fail(r);
+        h->path = std::string(route->path_prefix) + h->plan->name() + (G > 1 ? "+interleaved-shard" : "") + (agc_on ? "+agc" : "");
+        h->timed_kernel = h->plan->name();
         if (agc_on) {
             // d_A: channel-major CF32 from the channelizer; d_B: per-channel tail output in front of --mix
             // (the fused M = 256 plans may write it tile-major for k_agc_spec_tm, which reads up to a segment in front of / behind the plane)
             // The guards (2 x 64 KiB per channel: 128 MiB at 1024 channels) exist only where a call can take that route: a time-parallel
             // tail (not CSDR_FLAG_AGC_SEQUENTIAL), a channel count k_agc_spec_tm takes, calls of >= 4 W = 4096 frames
-            const bool tm_possible = (h->fused || h->big || h->small || h->huge) && !(cfg->flags & CSDR_FLAG_AGC_SEQUENTIAL) && h->max_nf >= 4096u &&
+            const bool tm_possible = !(cfg->flags & CSDR_FLAG_AGC_SEQUENTIAL) && h->max_nf >= 4096u &&
                                      (C % 64u == 0 || (C < 64u && 64u % C == 0));
             h->a_guard = tm_possible ? agc_tail_tm_guard(C) : 0;
-            if ((r = dev_alloc(&h->d_A, (size_t)C * h->max_nf + 2 * h->a_guard))) return fail(r);
+            if ((r = chain_alloc(h, &h->d_A, (size_t)C * h->max_nf + 2 * h->a_guard))) return fail(r);
             if (h->a_guard) {
                 // only the guards need defined contents (the warm-ups of the first and last segments read them, masked by position)
                 CSDR_HIP_CLEAN(hipMemset(h->d_A, 0, sizeof(float2) * h->a_guard), csdr_chain_destroy(h));
                 CSDR_HIP_CLEAN(hipMemset(h->d_A + h->a_guard + (size_t)C * h->max_nf, 0, sizeof(float2) * h->a_guard), csdr_chain_destroy(h));
             }
-            if (cfg->mix && (r = dev_alloc(&h->d_B, (size_t)C * h->max_nf))) return fail(r);
+            if (cfg->mix && (r = chain_alloc(h, &h->d_B, (size_t)C * h->max_nf))) return fail(r);
         }
     } else {
         h->path = "generic";
@@ -1155,14 +1138,14 @@ int csdr_chain_create(const csdr_chain_cfg *cfg_in, csdr_chain **out)
         h->timed_kernel = M > 1 ? (use1024 ? "k_pfb1024" : "k_pfb_fir") : "k_dc_apply";
         if (use1024) h->path = "generic+pfb1024";
         if (M > 1) {
-            if ((r = dev_alloc(&h->d_u, (size_t)(h->p - 1) * M + h->max_nx)) || (r = dev_alloc(&h->d_hist_tmp, (size_t)(h->p - 1) * M))) return fail(r);
+            if ((r = chain_alloc(h, &h->d_u, (size_t)(h->p - 1) * M + h->max_nx)) || (r = chain_alloc(h, &h->d_hist_tmp, (size_t)(h->p - 1) * M))) return fail(r);
         }
-        if ((r = dev_alloc(&h->d_A, h->max_nx)) || (r = dev_alloc(&h->d_B, use1024 && h->max_nx < 2048 ? 2048 : h->max_nx))) return fail(r);   // k_pfb1024 keeps yfirst|ylast (2 x nruns x 1024) in d_B
+        if ((r = chain_alloc(h, &h->d_A, h->max_nx)) || (r = chain_alloc(h, &h->d_B, use1024 && h->max_nx < 2048 ? 2048 : h->max_nx))) return fail(r);   // k_pfb1024 keeps yfirst|ylast (2 x nruns x 1024) in d_B
         if (M > 1 && cfg->dc_block && (r = dctile_create(h->dc, h->max_nx, &h->dctile))) return fail(r);
         h->mix_identity = M > 1 && G == 1 && C == M && cfg->mix && cfg->demod == CSDR_DEMOD_NONE && cfg->agc_threshold_db == 0.0f &&
                           h->dctile && !(cfg->flags & CSDR_FLAG_NO_MIX_IDENTITY) && !am;
         if (h->mix_identity) {
-            if ((r = dev_alloc(&h->d_u0, (size_t)(h->p - 1) + h->max_nf)) || (r = dev_alloc(&h->d_u0hist, 2 * (h->p - 1)))) return fail(r);
+            if ((r = chain_alloc(h, &h->d_u0, (size_t)(h->p - 1) + h->max_nf)) || (r = chain_alloc(h, &h->d_u0hist, 2 * (h->p - 1)))) return fail(r);
             h->path = "generic+mix-identity"; h->timed_kernel = (M % 4096u == 0) ? "k_dc_fold" : "k_dc_tile";   // refined per call
         }
         // interleaved shard, DeNo --mix, no AGC: only the G branches (M / G) n2 survive the shard's channel sum (kernels_dc_tile.hip, k_dc_fold8)
@@ -1171,7 +1154,7 @@ int csdr_chain_create(const csdr_chain_cfg *cfg_in, csdr_chain **out)
                                 h->dctile && !(cfg->flags & CSDR_FLAG_NO_MIX_IDENTITY) && !am && M % 4096u == 0 && (M / G) % 512u == 0 &&
                                 h->p <= 33u && h->dc.beta > 0.f;
         if (h->mix_identity_shard) {
-            if ((r = dev_alloc(&h->d_u0hist, 2 * (size_t)(h->p - 1) * G))) return fail(r);
+            if ((r = chain_alloc(h, &h->d_u0hist, 2 * (size_t)(h->p - 1) * G))) return fail(r);
         }
         if (G > 1) {
             const uint32_t Mg = M / G;
@@ -1180,7 +1163,7 @@ int csdr_chain_create(const csdr_chain_cfg *cfg_in, csdr_chain **out)
             for (uint32_t i = 0; i < Mg; i++) twg[i] = make_float2((float)std::cos(tp * i / Mg), (float)std::sin(tp * i / Mg));
             for (uint32_t j2 = 0; j2 < G; j2++) ph[j2] = make_float2((float)std::cos(tp * ((uint64_t)j2 * c0 % G) / G), (float)std::sin(tp * ((uint64_t)j2 * c0 % G) / G));
             for (uint32_t j1 = 0; j1 < Mg; j1++) ph[G + j1] = make_float2((float)std::cos(tp * ((uint64_t)j1 * c0 % M) / M), (float)std::sin(tp * ((uint64_t)j1 * c0 % M) / M));
-            if ((r = dev_alloc(&h->d_tw_g, Mg)) || (r = dev_alloc(&h->d_fold_ph, G + Mg)) || (r = dev_alloc(&h->d_fold, (size_t)Mg * h->max_nf))) return fail(r);
+            if ((r = chain_alloc(h, &h->d_tw_g, Mg)) || (r = chain_alloc(h, &h->d_fold_ph, G + Mg)) || (r = chain_alloc(h, &h->d_fold, (size_t)Mg * h->max_nf))) return fail(r);
             if (hipMemcpy(h->d_tw_g, twg.data(), sizeof(float2) * Mg, hipMemcpyHostToDevice) != hipSuccess ||
                 hipMemcpy(h->d_fold_ph, ph.data(), sizeof(float2) * (G + Mg), hipMemcpyHostToDevice) != hipSuccess) { set_error("chain: fold table upload failed"); return fail(CSDR_ERR_HIP); }
             h->path = h->mix_identity_shard ? "generic+pruned-dft+shard-mix-identity" : "generic+pruned-dft";
@@ -1191,14 +1174,14 @@ int csdr_chain_create(const csdr_chain_cfg *cfg_in, csdr_chain **out)
     if ((cfg_in->flags & CSDR_FLAG_DFT_BACKWARD) && M > 1 && !(cfg_in->mix != 0)) {
         if (C != M || G > 1) { set_error("chain: CSDR_FLAG_DFT_BACKWARD is built for whole-band handles (no channel shard)"); return fail(CSDR_ERR_INVALID); }
         h->dft_backward = true;
-        CSDR_HIP_CLEAN(hipMalloc(&h->d_perm, (size_t)C * h->max_nf * ((cfg_in->demod == CSDR_DEMOD_NONE) ? 8u : 4u)), csdr_chain_destroy(h));
+        if ((r = h->mem.alloc(&h->d_perm, (size_t)C * h->max_nf * ((cfg_in->demod == CSDR_DEMOD_NONE) ? 8u : 4u)))) return fail(r);
         h->path += "+dft-backward";
     }
     if (am) {
         h->am = true; h->am_mix = am_mix;
-        if ((r = dev_alloc(&h->d_amz, (size_t)C * h->max_nf))) return fail(r);
-        if (am_mix) { CSDR_HIP_CLEAN(hipMalloc(&h->d_amf, sizeof(float) * (size_t)C * h->max_nf), csdr_chain_destroy(h)); }
-        CSDR_HIP_CLEAN(hipMalloc(&h->d_amq[0], sizeof(float) * C), csdr_chain_destroy(h)); CSDR_HIP_CLEAN(hipMalloc(&h->d_amq[1], sizeof(float) * C), csdr_chain_destroy(h));
+        if ((r = chain_alloc(h, &h->d_amz, (size_t)C * h->max_nf))) return fail(r);
+        if (am_mix && (r = chain_alloc(h, &h->d_amf, (size_t)C * h->max_nf))) return fail(r);
+        if ((r = chain_alloc(h, &h->d_amq[0], C)) || (r = chain_alloc(h, &h->d_amq[1], C))) return fail(r);
         h->path += "+am";
     }
     if (wbfm) {
@@ -1210,16 +1193,16 @@ int csdr_chain_create(const csdr_chain_cfg *cfg_in, csdr_chain **out)
         const std::vector<float> taps = design_firdecim_kaiser(h->wb_decim, 10, 60.0f);
         h->wb_hlen = (uint32_t)taps.size();
         const size_t rows = (size_t)C * h->max_nf, hist = (size_t)C * (h->wb_hlen - 1);
-        if (hipMalloc(&h->d_wbf, sizeof(float) * rows) != hipSuccess || hipMalloc(&h->d_wbh, sizeof(float) * taps.size()) != hipSuccess ||
-            hipMalloc(&h->d_wbhist[0], sizeof(float) * hist) != hipSuccess || hipMalloc(&h->d_wbhist[1], sizeof(float) * hist) != hipSuccess ||
-            hipMalloc(&h->d_wbst[0], sizeof(float2) * C) != hipSuccess || hipMalloc(&h->d_wbst[1], sizeof(float2) * C) != hipSuccess ||
-            (wbfm_mix && hipMalloc(&h->d_wbo, sizeof(float) * rows) != hipSuccess)) { set_error("chain: WBFM tail allocation failed"); return fail(CSDR_ERR_HIP); }
+        if (chain_alloc(h, &h->d_wbf, rows) || chain_alloc(h, &h->d_wbh, taps.size()) || chain_alloc(h, &h->d_wbhist[0], hist) || chain_alloc(h, &h->d_wbhist[1], hist) ||
+            chain_alloc(h, &h->d_wbst[0], C) || chain_alloc(h, &h->d_wbst[1], C) || (wbfm_mix && chain_alloc(h, &h->d_wbo, rows))) {
+            set_error("chain: WBFM tail allocation failed"); return fail(CSDR_ERR_HIP);
+        }
         CSDR_HIP_CLEAN(hipMemcpy(h->d_wbh, taps.data(), sizeof(float) * taps.size(), hipMemcpyHostToDevice), csdr_chain_destroy(h));
         h->path += "+wbfm";
     }
     if (h->d_agc && !(cfg->flags & CSDR_FLAG_AGC_SEQUENTIAL)) {
         if ((r = agc_tail_create(C, h->max_nf, &h->agc_tail))) return fail(r);
-        h->path += h->use_fused ? "-spec" : "+agc-spec";
+        h->path += h->plan ? "-spec" : "+agc-spec";
     }
     if ((r = chain_init_state(h, nullptr))) return fail(r);
     CSDR_HIP_CLEAN(hipDeviceSynchronize(), csdr_chain_destroy(h));
@@ -1231,7 +1214,7 @@ int csdr_chain_create(const csdr_chain_cfg *cfg_in, csdr_chain **out)
                h->path.c_str(), dev, M, c0, c0 + C - 1, M > 1 ? M * h->p : 0, m, As, h->d_theta, cfg->dc_block,
                cfg->dc_alpha, cfg->agc_threshold_db, am ? "AM" : (wbfm ? "WBFM" : (cfg->demod == CSDR_DEMOD_FM ? "FM" : "none")), cfg->kf, cfg_in->mix);
         // per-channel outputs / AGC / demod tails beyond the fused kernels' channel counts run stage by stage through HBM
-        if (!h->use_fused && !h->mix_identity && M > 1024)
+        if (!h->plan && !h->mix_identity && M > 1024)
             printf("csdr chain: note: %u channels with per-channel output run on the any-M route (DC blocker, FIR, DFT and tail as separate kernels, "
                    "~0.09 of the HBM roofline on MI355X); fused kernels exist for 64, 256 and 1024 channels, and for DeNo --mix over all channels of any count\n", M);
         fflush(stdout);
@@ -1242,17 +1225,46 @@ int csdr_chain_create(const csdr_chain_cfg *cfg_in, csdr_chain **out)
 
 uint32_t csdr_chain_out_elem_size(const csdr_chain *h) { return h && (h->cfg.demod == CSDR_DEMOD_FM || h->am || h->wbfm) ? 4u : 8u; }
 
-// AGC on: Z[C][nf] (channel-major CF32 in d_A) -> AGC + squelch [+ freqdem] [+ mix] -> d_out
-static int chain_agc_tail(csdr_chain *h, const float2 *Z, uint32_t nf, void *d_out, hipStream_t s, bool tm = false)
+// Z[C][nf] (channel-major CF32) -> AGC + squelch [+ freqdem] [+ mix] -> d_out: the time-parallel tail (tm: Z tile-major), or with
+// CSDR_FLAG_AGC_SEQUENTIAL one lane per channel in place on Z; without the AGC (the any-M route) only freqdem / mix
+static int chain_tail(csdr_chain *h, float2 *Z, uint32_t nf, void *d_out, hipStream_t s, bool tm = false)
 {
     const bool fm = h->cfg.demod == CSDR_DEMOD_FM, mixo = h->cfg.mix && h->M > 1;
-    void *T = mixo ? (void *)h->d_B : d_out;
-    int r = agc_tail_process(h->agc_tail, Z, T, fm, nf, h->d_agc, h->agc, h->fm_ref,
-                             fm ? h->d_rp[h->rp_cur] : nullptr, fm ? h->d_rp[h->rp_cur ^ 1] : nullptr, s, tm);
-    if (r) return r;
-    if (fm) h->rp_cur ^= 1;
-    if (mixo) return launch_mix((const float *)T, (float *)d_out, h->C, fm ? nf : 2 * nf, s);
+    int r;
+    if (h->agc_tail) {
+        void *T = mixo ? (void *)h->d_B : d_out;
+        if ((r = agc_tail_process(h->agc_tail, Z, T, fm, nf, h->d_agc, h->agc, h->fm_ref,
+                                  fm ? h->d_rp[h->rp_cur] : nullptr, fm ? h->d_rp[h->rp_cur ^ 1] : nullptr, s, tm))) return r;
+        if (fm) h->rp_cur ^= 1;
+        if (mixo) return launch_mix((const float *)T, (float *)d_out, h->C, fm ? nf : 2 * nf, s);
+        return 0;
+    }
+    if (h->d_agc && (r = launch_agc(Z, h->C, nf, h->d_agc, h->agc, s))) return r;
+    if (fm) {
+        float *F = mixo ? (float *)h->d_B : (float *)d_out;
+        if ((r = launch_fm(Z, F, h->C, nf, h->fm_ref, h->d_rp[h->rp_cur], h->d_rp[h->rp_cur ^ 1], s))) return r;
+        h->rp_cur ^= 1;
+        if (mixo) return launch_mix(F, (float *)d_out, h->C, nf, s);
+    } else if (mixo) return launch_mix((const float *)Z, (float *)d_out, h->C, 2 * nf, s);
     return 0;
+}
+
+// the NCO phase behind a call of nx input samples (and the position in the pre-mix table)
+static void chain_advance_nco(csdr_chain *h, uint32_t nx)
+{
+    h->theta += nx * h->d_theta;
+    if (h->tab_len) h->tab_pos = (uint32_t)(((uint64_t)h->tab_pos + nx) % h->tab_len);
+}
+
+// The argument checks of every entry point that takes a chunk (texts and codes are part of the C ABI), then the handle's device
+static int chain_check_chunk(const csdr_chain *h, const void *in, uint32_t n_in, const void *out, DevGuard &guard)
+{
+    if (n_in && (!in || !out)) { set_error("chain: null buffer"); return CSDR_ERR_INVALID; }
+    if (n_in % h->M) { set_error("chain: n_in=%u is not a multiple of channels=%u (the reference misbehaves here; Liquid.chs:832-862)", n_in, h->M); return CSDR_ERR_SIZE; }
+    if (n_in > h->max_nx) { set_error("chain: n_in=%u exceeds max_frames*channels=%llu", n_in, (unsigned long long)h->max_nx); return CSDR_ERR_SIZE; }
+    guard.select(h->device);
+    if (!guard.ok) { set_error("chain: cannot select device %d", h->device); return CSDR_ERR_HIP; }
+    return CSDR_OK;
 }
 
 static int chain_generic(csdr_chain *h, const float2 *d_in, uint32_t nx, void *d_out, hipStream_t s)
@@ -1278,8 +1290,7 @@ static int chain_generic(csdr_chain *h, const float2 *d_in, uint32_t nx, void *d
             if ((r = dctile_mix_identity_shard(h->dctile, d_in, nx, nco, h->d_nco_tab, h->d_taps, M, h->p, h->G, h->c0, hin, hout, (float2 *)d_out, s))) return r;
             if ((r = h->timer.end(s))) return r;
             h->u0_cur ^= 1;
-            h->theta += nx * h->d_theta;
-            if (h->tab_len) h->tab_pos = (uint32_t)(((uint64_t)h->tab_pos + nx) % h->tab_len);
+            chain_advance_nco(h, nx);
             return 0;
         }
         if (h->mix_identity) {
@@ -1301,8 +1312,7 @@ static int chain_generic(csdr_chain *h, const float2 *d_in, uint32_t nx, void *d
                 if ((r = launch_branch0_fir(h->d_u0, h->d_taps, (float2 *)d_out, hout, M, h->p, nf, s))) return r;
             }
             h->u0_cur ^= 1;
-            h->theta += nx * h->d_theta;
-            if (h->tab_len) h->tab_pos = (uint32_t)(((uint64_t)h->tab_pos + nx) % h->tab_len);
+            chain_advance_nco(h, nx);
             return 0;
         }
         float2 *u_new = h->d_u + hist;
@@ -1326,20 +1336,8 @@ static int chain_generic(csdr_chain *h, const float2 *d_in, uint32_t nx, void *d
         CSDR_HIP(hipMemcpyAsync(h->d_hist_tmp, h->d_u + nx, sizeof(float2) * hist, hipMemcpyDeviceToDevice, s));
         CSDR_HIP(hipMemcpyAsync(h->d_u, h->d_hist_tmp, sizeof(float2) * hist, hipMemcpyDeviceToDevice, s));
         if (fused1024) {
-            h->theta += nx * h->d_theta;
-            if (h->tab_len) h->tab_pos = (uint32_t)(((uint64_t)h->tab_pos + nx) % h->tab_len);
-            if (fm && !agc) return 0;
-            if (agc && h->agc_tail) return chain_agc_tail(h, Z, nf, d_out, s);
-            if (agc) {
-                if ((r = launch_agc(Z, C, nf, h->d_agc, h->agc, s))) return r;
-                if (fm) {
-                    float *F = mixo ? (float *)h->d_B : (float *)d_out;
-                    if ((r = launch_fm(Z, F, C, nf, h->fm_ref, h->d_rp[h->rp_cur], h->d_rp[h->rp_cur ^ 1], s))) return r;
-                    h->rp_cur ^= 1;
-                    if (mixo && (r = launch_mix(F, (float *)d_out, C, nf, s))) return r;
-                } else if (mixo && (r = launch_mix((const float *)Z, (float *)d_out, C, 2 * nf, s))) return r;
-            }
-            return 0;
+            chain_advance_nco(h, nx);
+            return agc ? chain_tail(h, Z, nf, d_out, s) : 0;      // (without the AGC: freqdem done in the kernel, no mix on this route)
         }
         // DeNo --mix over all channels: the frame sum happens inside the DFT kernel, Y never goes to HBM
         const bool fused_mix = !agc && !fm && mixo && C == M && dft_mix_supported(M);
@@ -1350,8 +1348,7 @@ static int chain_generic(csdr_chain *h, const float2 *d_in, uint32_t nx, void *d
         } else if (fused_mix) r = launch_dft_mix(h->d_A, (float2 *)d_out, h->d_tw, M, nf, s);
         else r = launch_dft(h->d_A, h->d_B, h->d_tw, M, nf, s);
         if (r) return r;
-        h->theta += nx * h->d_theta;
-        if (h->tab_len) h->tab_pos = (uint32_t)(((uint64_t)h->tab_pos + nx) % h->tab_len);
+        chain_advance_nco(h, nx);
         if (fused_mix) return 0;
         const uint32_t Mw = M / h->G, cw = h->G > 1 ? 0u : h->c0;     // width of a DFT output frame, first owned bin in it
         if (!agc && (fm || mixo)) {
@@ -1368,17 +1365,7 @@ static int chain_generic(csdr_chain *h, const float2 *d_in, uint32_t nx, void *d
         if ((r = launch_dc_mix(d_in, Z, nx, h->cfg.dc_block != 0, h->dc, h->d_dcstate, h->d_scratch, false, nco, nullptr, s))) return r;
         if ((r = h->timer.end(s))) return r;
     }
-    if (agc && h->agc_tail) return chain_agc_tail(h, Z, nf, d_out, s);
-    if (agc && (r = launch_agc(Z, C, nf, h->d_agc, h->agc, s))) return r;
-    if (fm) {
-        float *F = mixo ? (float *)h->d_B : (float *)d_out;
-        if ((r = launch_fm(Z, F, C, nf, h->fm_ref, h->d_rp[h->rp_cur], h->d_rp[h->rp_cur ^ 1], s))) return r;
-        h->rp_cur ^= 1;
-        if (mixo && (r = launch_mix(F, (float *)d_out, C, nf, s))) return r;
-    } else if (mixo) {
-        if ((r = launch_mix((const float *)Z, (float *)d_out, C, 2 * nf, s))) return r;
-    }
-    return 0;
+    return chain_tail(h, Z, nf, d_out, s);
 }
 
 static int chain_process_device_inner(csdr_chain *h, const void *d_in, uint32_t n_in, void *d_out, uint32_t *n_out, void *stream);
@@ -1475,60 +1462,32 @@ static int chain_process_device_inner(csdr_chain *h, const void *d_in, uint32_t 
     if (!h) { set_error("chain: null handle"); return CSDR_ERR_INVALID; }
     if (n_out) *n_out = 0;
     if (n_in == 0) return CSDR_OK;
-    if (!d_in || !d_out) { set_error("chain: null buffer"); return CSDR_ERR_INVALID; }
-    if (n_in % h->M) { set_error("chain: n_in=%u is not a multiple of channels=%u (the reference misbehaves here; Liquid.chs:832-862)", n_in, h->M); return CSDR_ERR_SIZE; }
-    if (n_in > h->max_nx) { set_error("chain: n_in=%u exceeds max_frames*channels=%llu", n_in, (unsigned long long)h->max_nx); return CSDR_ERR_SIZE; }
-    DevGuard guard(h->device);
-    if (!guard.ok) { set_error("chain: cannot select device %d", h->device); return CSDR_ERR_HIP; }
+    DevGuard guard;
+    int r;
+    if ((r = chain_check_chunk(h, d_in, n_in, d_out, guard))) return r;
     hipStream_t s = (hipStream_t)stream;
     const uint32_t nf = n_in / h->M;
-    int r;
     if (h->tail_only) {
+        // the time-parallel tail reads the rows where they are; the sequential AGC works in place on a copy
         const bool fm = h->cfg.demod == CSDR_DEMOD_FM, mixo = h->cfg.mix && h->M > 1;
-        if (h->agc_tail) {
-            if ((r = chain_agc_tail(h, (const float2 *)d_in, nf, d_out, s))) return r;
-        } else {
-            CSDR_HIP(hipMemcpyAsync(h->d_A, d_in, sizeof(float2) * (size_t)n_in, hipMemcpyDeviceToDevice, s));
-            if ((r = launch_agc(h->d_A, h->C, nf, h->d_agc, h->agc, s))) return r;
-            if (fm) {
-                float *F = mixo ? (float *)h->d_B : (float *)d_out;
-                if ((r = launch_fm(h->d_A, F, h->C, nf, h->fm_ref, h->d_rp[h->rp_cur], h->d_rp[h->rp_cur ^ 1], s))) return r;
-                h->rp_cur ^= 1;
-                if (mixo && (r = launch_mix(F, (float *)d_out, h->C, nf, s))) return r;
-            } else if (mixo) { if ((r = launch_mix((const float *)h->d_A, (float *)d_out, h->C, 2 * nf, s))) return r; }
-            else CSDR_HIP(hipMemcpyAsync(d_out, h->d_A, sizeof(float2) * (size_t)n_in, hipMemcpyDeviceToDevice, s));
-        }
+        if (!h->agc_tail) CSDR_HIP(hipMemcpyAsync(h->d_A, d_in, sizeof(float2) * (size_t)n_in, hipMemcpyDeviceToDevice, s));
+        if ((r = chain_tail(h, h->agc_tail ? (float2 *)d_in : h->d_A, nf, d_out, s))) return r;
+        if (!h->agc_tail && !fm && !mixo) CSDR_HIP(hipMemcpyAsync(d_out, h->d_A, sizeof(float2) * (size_t)n_in, hipMemcpyDeviceToDevice, s));
         if (n_out) *n_out = mixo ? nf : h->C * nf;
         return CSDR_OK;
     }
-    if (h->use_fused) {
+    if (h->plan) {
         const bool agc_on = h->d_agc != nullptr, fm = h->cfg.demod == CSDR_DEMOD_FM, mixo = h->cfg.mix != 0;
         float2 *Z = (agc_on && (fm || mixo || h->agc_tail)) ? h->d_A + h->a_guard : (float2 *)d_out;
         FusedCall fcall{};
-        // AGC tail behind the fused M = 256 / M = 1024 chains, run-sized calls of whole tiles: the plane between the two kernels is tile-major
-        const bool tm = agc_on && h->agc_tail && h->a_guard && Z != (float2 *)d_out && agc_tail_tm_supported(h->agc_tail, nf) &&
-                        (h->fused ? fused_tile_major_ok(h->fused, nf) : h->big ? big_tile_major_ok(h->big, nf) : h->small ? small_tile_major_ok(h->small, nf) : (h->huge && huge_tile_major_ok(h->huge, nf)));
+        // AGC tail behind a fused chain, run-sized calls of whole tiles: the plane between the two kernels is tile-major
+        const bool tm = agc_on && h->agc_tail && h->a_guard && Z != (float2 *)d_out && agc_tail_tm_supported(h->agc_tail, nf) && h->plan->tile_major_ok(nf);
         fcall.tile_major = tm;
         fcall.d_in = (const float2 *)d_in; fcall.d_out = agc_on ? (void *)Z : d_out; fcall.nf = nf; fcall.theta0 = h->theta;
         fcall.indep = h->call_indep; fcall.ev_tail = h->call_ev_tail;
-        if (h->small) { if ((r = small_process(h->small, fcall, s, &h->timer))) return r; h->timed_kernel = small_name(h->small); }   // k_run64v2 or k_run64, by call
-        else if (h->big) { if ((r = big_process(h->big, fcall, s, &h->timer))) return r; h->timed_kernel = big_name(h->big); }   // k_run1024v2 or k_run1024, by call
-        else if (h->huge) { if ((r = huge_process(h->huge, fcall, s, &h->timer))) return r; }
-        else if ((r = fused_process(h->fused, fcall, s, &h->timer))) return r;
-        h->theta += n_in * h->d_theta;
-        if (agc_on && h->agc_tail) {
-            if ((r = chain_agc_tail(h, Z, nf, d_out, s, tm))) return r;
-        } else if (agc_on) {
-            if ((r = launch_agc(Z, h->C, nf, h->d_agc, h->agc, s))) return r;
-            if (fm) {
-                float *F = mixo ? (float *)h->d_B : (float *)d_out;
-                if ((r = launch_fm(Z, F, h->C, nf, h->fm_ref, h->d_rp[h->rp_cur], h->d_rp[h->rp_cur ^ 1], s))) return r;
-                h->rp_cur ^= 1;
-                if (mixo && (r = launch_mix(F, (float *)d_out, h->C, nf, s))) return r;
-            } else if (mixo) {
-                if ((r = launch_mix((const float *)Z, (float *)d_out, h->C, 2 * nf, s))) return r;
-            }
-        }
+        if ((r = h->plan->process(fcall, s, &h->timer))) return r;
+        chain_advance_nco(h, n_in);
+        if (agc_on && (r = chain_tail(h, Z, nf, d_out, s, tm))) return r;
     } else {
         if ((r = chain_generic(h, (const float2 *)d_in, n_in, d_out, s))) return r;
     }
@@ -1542,7 +1501,7 @@ static int chain_device_status(csdr_chain *h)
 {
     unsigned st = 0, st2 = 0;
     int r;
-    if (h->fused && (r = fused_status(h->fused, &st))) return r;
+    if (h->plan && (r = h->plan->status(&st))) return r;
     if (h->dctile && (r = dctile_status(h->dctile, &st2))) return r;
     if (st || st2) {
         set_error("chain: an inter-workgroup wait timed out on the device (fused status 0x%x, dc-tile status 0x%x): the output of the affected calls is invalid", st, st2);
@@ -1563,11 +1522,8 @@ int csdr_chain_submit_device(csdr_chain *h, const void *d_in, uint32_t n_in, voi
     if (!h) { set_error("chain: null handle"); return CSDR_ERR_INVALID; }
     if (n_out) *n_out = 0;
     if (n_in == 0) return CSDR_OK;
-    if (!d_in || !d_out) { set_error("chain: null buffer"); return CSDR_ERR_INVALID; }
-    if (n_in % h->M) { set_error("chain: n_in=%u is not a multiple of channels=%u (the reference misbehaves here; Liquid.chs:832-862)", n_in, h->M); return CSDR_ERR_SIZE; }
-    if (n_in > h->max_nx) { set_error("chain: n_in=%u exceeds max_frames*channels=%llu", n_in, (unsigned long long)h->max_nx); return CSDR_ERR_SIZE; }
-    DevGuard guard(h->device);
-    if (!guard.ok) { set_error("chain: cannot select device %d", h->device); return CSDR_ERR_HIP; }
+    DevGuard guard;
+    if (int r = chain_check_chunk(h, d_in, n_in, d_out, guard)) return r;
     if (!h->s_pd[0]) {
         CSDR_HIP(hipDeviceSynchronize());               // whatever the handle has queued on caller streams so far
         // created into locals and published together: a partial failure leaves the handle as it was
@@ -1585,7 +1541,7 @@ int csdr_chain_submit_device(csdr_chain *h, const void *d_in, uint32_t n_in, voi
         for (int i = 0; i < 2; i++) { h->s_pd[i] = st[i]; h->e_pd_done[i] = ev[i]; }
         for (int i = 0; i < 3; i++) h->e_pd_tail[i] = ev[2 + i];
         h->e_serial = ev[5];
-        if (h->fused) fused_keep_tail(h->fused);
+        if (h->plan) h->plan->keep_tail();
     }
     if (h->s_k && h->q_count) CSDR_HIP(hipStreamSynchronize(h->s_k));       // host-buffer chunks still in flight come first
     const uint32_t nf = n_in / h->M, k = h->pd_count;
@@ -1594,7 +1550,7 @@ int csdr_chain_submit_device(csdr_chain *h, const void *d_in, uint32_t n_in, voi
     // An independent launch (fused M = 256 chain without AGC / AM / WBFM tails, run-kernel-sized whole-tile chunk, previous
     // chunk's tail on file) reads nothing an earlier launch writes: it only waits for the input and for the copy of the
     // previous chunk's tail.  Every other call is ordered behind everything the handle has in flight.
-    const bool overlap = h->use_fused && h->fused && !h->d_agc && !h->am && !h->wbfm && fused_can_overlap(h->fused, nf);
+    const bool overlap = h->plan && !h->d_agc && !h->am && !h->wbfm && h->plan->can_overlap(nf);
     if (ready_event) CSDR_HIP(hipStreamWaitEvent(s, (hipEvent_t)ready_event, 0));
     if (h->serial_pending) { CSDR_HIP(hipStreamWaitEvent(s, h->e_serial, 0)); h->serial_pending = false; }
     if (overlap) {
@@ -1607,7 +1563,7 @@ int csdr_chain_submit_device(csdr_chain *h, const void *d_in, uint32_t n_in, voi
     const int r = csdr_chain_process_device(h, d_in, n_in, d_out, n_out, s);
     h->call_indep = false; h->call_ev_tail = nullptr; h->in_submit = false;
     if (r) return r;
-    h->pd_tail_rec = h->fused && fused_tail_recorded(h->fused);
+    h->pd_tail_rec = h->plan && h->plan->tail_recorded();
     if (overlap) h->pd_indep_calls++;
     h->pd_last_indep = overlap;
     CSDR_HIP(hipEventRecord(h->e_pd_done[si], s));
@@ -1662,13 +1618,10 @@ static int chain_host_init(csdr_chain *h)
 int csdr_chain_submit(csdr_chain *h, const float *in, uint32_t n_in, void *out)
 {
     if (!h) { set_error("chain: null handle"); return CSDR_ERR_INVALID; }
-    if (n_in && (!in || !out)) { set_error("chain: null buffer"); return CSDR_ERR_INVALID; }
-    if (n_in % h->M) { set_error("chain: n_in=%u is not a multiple of channels=%u (the reference misbehaves here; Liquid.chs:832-862)", n_in, h->M); return CSDR_ERR_SIZE; }
-    if (n_in > h->max_nx) { set_error("chain: n_in=%u exceeds max_frames*channels=%llu", n_in, (unsigned long long)h->max_nx); return CSDR_ERR_SIZE; }
-    if (h->q_count == CSDR_CHAIN_INFLIGHT) { set_error("chain: %d chunks already in flight (collect first)", CSDR_CHAIN_INFLIGHT); return CSDR_ERR_BUSY; }
-    DevGuard guard(h->device);
-    if (!guard.ok) { set_error("chain: cannot select device %d", h->device); return CSDR_ERR_HIP; }
+    DevGuard guard;
     int r;
+    if ((r = chain_check_chunk(h, in, n_in, out, guard))) return r;
+    if (h->q_count == CSDR_CHAIN_INFLIGHT) { set_error("chain: %d chunks already in flight (collect first)", CSDR_CHAIN_INFLIGHT); return CSDR_ERR_BUSY; }
     if ((r = chain_host_init(h))) return r;
     if (h->user_stream_dirty) {                         // csdr_chain_process_device calls on caller streams precede this chunk
         CSDR_HIP(hipEventSynchronize(h->e_user));
@@ -1736,11 +1689,8 @@ int csdr_chain_process(csdr_chain *h, const float *in, uint32_t n_in, void *out,
         if ((r = csdr_chain_collect(h, n_out))) return r;
     } else {
         // pageable caller memory: the runtime's own staged hipMemcpy beats a hand-made copy into page-locked memory
-        if (!in || !out) { set_error("chain: null buffer"); return CSDR_ERR_INVALID; }
-        if (n_in % h->M) { set_error("chain: n_in=%u is not a multiple of channels=%u (the reference misbehaves here; Liquid.chs:832-862)", n_in, h->M); return CSDR_ERR_SIZE; }
-        if (n_in > h->max_nx) { set_error("chain: n_in=%u exceeds max_frames*channels=%llu", n_in, (unsigned long long)h->max_nx); return CSDR_ERR_SIZE; }
-        DevGuard guard(h->device);
-        if (!guard.ok) { set_error("chain: cannot select device %d", h->device); return CSDR_ERR_HIP; }
+        DevGuard guard;
+        if ((r = chain_check_chunk(h, in, n_in, out, guard))) return r;
         if ((r = chain_host_init(h))) return r;
         if (h->user_stream_dirty) { CSDR_HIP(hipEventSynchronize(h->e_user)); h->user_stream_dirty = false; }
         csdr_chain::HostSlot &sl = h->slot[0];
@@ -1778,10 +1728,7 @@ int csdr_chain_seek_frames(csdr_chain *h, uint64_t frames)
     const uint64_t n = frames * (uint64_t)h->M;
     h->theta = (uint32_t)(n * (uint64_t)h->d_theta);
     if (h->tab_len) h->tab_pos = (uint32_t)(n % h->tab_len);
-    if (h->fused) fused_seek(h->fused, frames);
-    if (h->small) small_seek(h->small, frames);
-    if (h->big) big_seek(h->big, frames);
-    if (h->huge) huge_seek(h->huge, frames);
+    if (h->plan) h->plan->seek(frames);
     return CSDR_OK;
 }
 
@@ -1802,9 +1749,7 @@ int csdr_chain_get_nco(const csdr_chain *h, uint32_t *theta, uint32_t *d_theta)
 int csdr_chain_debug_trace(csdr_chain *h, unsigned long long *out, uint32_t ntiles)
 {
     if (!h || !out) return CSDR_ERR_INVALID;
-    if (!h->fused) return 0;
-    (void)hipDeviceSynchronize();
-    return fused_trace(h->fused, out, ntiles);
+    return h->plan ? h->plan->trace(out, ntiles) : 0;
 }
 int csdr_chain_debug_agc(csdr_chain *h, uint32_t *checked, uint32_t *redone)
 {
@@ -1836,7 +1781,7 @@ const char *csdr_chain_kernel_time(csdr_chain *h, double *total_ms, uint32_t *la
     if (total_ms) *total_ms = h->timer.acc_ms;
     if (launches) *launches = h->timer.launches;
     h->timer.acc_ms = 0.0; h->timer.launches = 0;
-    if (h->fused) h->timed_kernel = fused_name(h->fused);      // the kernel the last call launched
+    if (h->plan) h->timed_kernel = h->plan->name();      // the kernel the last call launched
     return h->timed_kernel.c_str();
 }
 
@@ -1845,17 +1790,10 @@ int csdr_chain_destroy(csdr_chain *h)
     if (!h) return CSDR_OK;
     DevGuard guard(h->device);
     (void)hipDeviceSynchronize();
-    if (h->fused) fused_destroy(h->fused);
-    if (h->small) small_destroy(h->small);
-    if (h->big) big_destroy(h->big);
-    if (h->huge) huge_destroy(h->huge);
+    delete h->plan;
     if (h->dctile) dctile_destroy(h->dctile);
     if (h->agc_tail) agc_tail_destroy(h->agc_tail);
     h->timer.destroy();
-    void *ptrs[] = {h->d_taps, h->d_tw, h->d_nco_tab, h->d_dcstate, h->d_scratch, h->d_u, h->d_hist_tmp, h->d_A, h->d_B,
-                    h->d_agc, h->d_rp[0], h->d_rp[1], h->d_amz, h->d_amf, h->d_amq[0], h->d_amq[1], h->d_tw_g, h->d_fold_ph, h->d_fold, h->d_u0, h->d_u0hist,
-                    h->d_wbf, h->d_wbo, h->d_wbh, h->d_wbhist[0], h->d_wbhist[1], h->d_wbst[0], h->d_wbst[1], h->d_perm};
-    for (void *p : ptrs) if (p) (void)hipFree(p);
     for (auto &sl : h->slot) {
         if (sl.d_in) (void)hipFree(sl.d_in);
         if (sl.d_out) (void)hipFree(sl.d_out);

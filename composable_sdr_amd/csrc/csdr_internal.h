@@ -29,6 +29,25 @@ int  hip_fail(hipError_t e, const char *what, const char *file, int line);
         }                                                                       \
     } while (0)
 
+// ---- device buffers released together (fused plans, chain handles) ---------
+// alloc() records every buffer it makes; the destructor frees them all
+struct DeviceBuffers {
+    DeviceBuffers() = default;
+    DeviceBuffers(const DeviceBuffers &) = delete;
+    DeviceBuffers &operator=(const DeviceBuffers &) = delete;
+    ~DeviceBuffers() { for (void *q : owned) (void)hipFree(q); }
+    template <class T> int alloc(T **p, size_t bytes) {      // hipMalloc of `bytes` (at least one) into *p
+        void *q = nullptr;
+        const hipError_t e = hipMalloc(&q, bytes ? bytes : 1);
+        if (e != hipSuccess) return hip_fail(e, "hipMalloc", __FILE__, __LINE__);
+        owned.push_back(q);
+        *p = static_cast<T *>(q);
+        return 0;
+    }
+private:
+    std::vector<void *> owned;
+};
+
 // ---- diagnostics knobs ------------------------------------------------------
 // The CSDR_* variables that change a launch plan (CSDR_RUN_MIN_TILES, CSDR_RUN_WEIGHTS, CSDR_AGC_L / _W, CSDR_WU, CSDR_RUN1024_V3, ...:
 // DESIGN.md section 6.1; several of them change RESULTS) exist for A/B measurements and for the tests that force a kernel onto a small
@@ -302,9 +321,5 @@ struct KernelTimer {
     }
     void destroy() { for (auto e : ev) (void)hipEventDestroy(e); ev.clear(); used = 0; if (r0) { (void)hipEventDestroy(r0); (void)hipEventDestroy(r1); r0 = r1 = nullptr; } open = false; }
 };
-
-// ---- fused kernels (kernels_fused.hip) --------------------------------------
-struct FusedPlan;   // opaque per-handle plan
-bool fused_supported(uint32_t M, uint32_t p);
 
 }  // namespace csdr

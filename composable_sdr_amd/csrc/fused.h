@@ -13,6 +13,7 @@ struct FusedConfig {
     bool mix;
     const float *taps;       // host, M*p
     uint32_t d_theta;
+    uint32_t cus = 256;      // compute units of the device (the run counts of the launches)
 };
 
 struct FusedCall {
@@ -21,30 +22,77 @@ struct FusedCall {
     uint32_t nf;
     uint32_t theta0;         // NCO phase of the first sample
     // pipelined entry point (csdr_chain_submit_device): run the launch without reading anything an earlier launch wrote, if the
-    // plan can (fused_can_overlap); ev_tail is recorded on s once the chunk's last tiles are saved for the next call's run 0
+    // plan can (ChainPlan::can_overlap); ev_tail is recorded on s once the chunk's last tiles are saved for the next call's run 0
     bool indep = false;
     hipEvent_t ev_tail = nullptr;
     // CF32 plans: write the output TILE-MAJOR -- block t / 16 holds the 128-byte lines of all C rows back to back (a tile's whole
     // output is one contiguous C x 128 bytes) -- instead of row-major [C][nf]: what the time-parallel AGC tail reads (k_agc_spec_tm).
-    // Only for calls fused_tile_major_ok() accepts.
+    // Only for calls ChainPlan::tile_major_ok() accepts.
     bool tile_major = false;
 };
-bool fused_tile_major_ok(const FusedPlan *plan, uint32_t nf);
-void fused_keep_tail(FusedPlan *plan);                  // from now on every run-kernel call saves its last WU + 1 raw tiles
-bool fused_can_overlap(const FusedPlan *plan, uint32_t nf);
-bool fused_tail_recorded(const FusedPlan *plan);       // the last call saved its tail (and recorded FusedCall::ev_tail)   // the next call of nf frames can run with FusedCall::indep
 
-bool fused_supported(uint32_t M, uint32_t p);
-int  fused_create(const FusedConfig &cfg, FusedPlan **out);
-int  fused_reset(FusedPlan *plan, hipStream_t s);
-int  fused_process(FusedPlan *plan, const FusedCall &call, hipStream_t s, KernelTimer *timer);
-const char *fused_name(const FusedPlan *plan);
-void fused_seek(FusedPlan *plan, uint64_t frames);   // after fused_reset: global frame index of the next frame
-// sticky device-side error word (bit0/bit1: an inter-workgroup wait hit its spin limit); reads, then clears it; synchronises
-int  fused_status(FusedPlan *plan, unsigned *status);
-// CSDR_TRACE=1: per-tile s_memtime stamps (16 per tile) of the last launches; returns tiles copied
-int  fused_trace(FusedPlan *plan, unsigned long long *out, uint32_t ntiles);
-void fused_destroy(FusedPlan *plan);
+// The plan of one fused route (a RouteRow of capi.hip): M = 64 (kernels_fused_small.hip), 256 (kernels_fused.hip), 1024 (kernels_pfb1024.hip)
+// and 4096 (kernels_pfb4096.hip) derive from it.  The base owns what they share: the configuration, the CU count, the global frame counter,
+// the ping-pong index of the state buffers, the device buffers (mem: freed with the plan) and the mix ending of the 64, 256 and 1024 plans
+// (run() writes d_premix, process() sums its rows into the call's output).
+struct ChainPlan {
+    FusedConfig cfg;
+    uint32_t cus;                // compute units the launches are sized for (cfg.cus; the M = 256 plan takes CSDR_CUS)
+    uint64_t frames_done = 0;    // global frame index of the next frame (its parity selects the pre-mix phasor row)
+    int cur = 0;                 // the next call reads the state buffers [cur] and writes [cur ^ 1]
+    void *d_premix = nullptr;    // per-channel output in front of launch_mix (cfg.mix; the M = 4096 plan mixes in its back kernel)
+    DeviceBuffers mem;
+
+    explicit ChainPlan(const FusedConfig &c) : cfg(c), cus(c.cus) {}
+    virtual ~ChainPlan() = default;
+
+    // One call.  A tile-major or independent request the plan cannot run (tile_major_ok, can_overlap) is refused before anything is queued.
+    int process(const FusedCall &call, hipStream_t s, KernelTimer *timer);
+    int reset(hipStream_t s) { cur = 0; frames_done = 0; return reset_state(s); }
+    void seek(uint64_t frames) { frames_done = frames; }     // after reset: global frame index of the next frame
+    // the kernel the last call launched (before the first call: the one a call of max_nf frames takes)
+    virtual const char *name() const = 0;
+    virtual bool tile_major_ok(uint32_t nf) const = 0;     // FusedCall::tile_major for a call of nf frames
+
+    // M = 256 only
+    virtual void keep_tail() {}                                 // from now on every run-kernel call saves its last WU + 1 raw tiles
+    virtual bool can_overlap(uint32_t nf) const { (void)nf; return false; }    // the next call of nf frames can run with FusedCall::indep
+    virtual bool tail_recorded() const { return false; }        // the last call saved its tail (and recorded FusedCall::ev_tail)
+    // sticky device-side error word (bit0/bit1: an inter-workgroup wait hit its spin limit); reads, then clears it; synchronises
+    virtual int status(unsigned *st) { *st = 0; return 0; }
+    // CSDR_TRACE=1: per-tile s_memtime stamps (16 per tile) of the last launches; returns tiles copied
+    virtual int trace(unsigned long long *out, uint32_t ntiles) { (void)out; (void)ntiles; return 0; }
+
+protected:
+    // nco_crcf_mix_block_down's phasor conj(cos + j sin) of theta = n d_theta, n < 2M: the phase sequence has period 2M for a power-of-two M
+    // (row 0: even frames, n = j; row 1: odd frames, n = M + j)
+    std::vector<float2> premix_table() const;
+    virtual int reset_state(hipStream_t s) = 0;      // zero the stream state the plan carries between calls
+    // the call's launches into out (d_premix when mixing); a launch sequence with two steps may flip cur between them, process() flips it behind the call
+    virtual int run(const FusedCall &call, void *out, hipStream_t s, KernelTimer *timer) = 0;
+};
+
+// the factories' common part: a plan of type Plan, set up by its init()
+template <class Plan> int make_plan(const FusedConfig &cfg, ChainPlan **out)
+{
+    Plan *p = new Plan(cfg);
+    if (int r = p->init()) { delete p; return r; }
+    *out = p;
+    return 0;
+}
+
+// One route per channel count (RouteRow, capi.hip): whether the plan takes M channels of p taps per branch, and the factory
+bool plan256_supported(uint32_t M, uint32_t p);
+int  plan256_create(const FusedConfig &cfg, ChainPlan **out);
+bool plan64_supported(uint32_t M, uint32_t p);
+int  plan64_create(const FusedConfig &cfg, ChainPlan **out);
+bool plan1024_supported(uint32_t M, uint32_t p);      // (CSDR_NO_RUN1024: no)
+int  plan1024_create(const FusedConfig &cfg, ChainPlan **out);
+// M = 4096: branch-tiled front kernel (DC blocker + pre-mix + FIR + first radix-4 stage) -> z -> back kernel (four 1024-point DFTs per
+// frame + tails); whole band
+bool plan4096_supported(uint32_t M, uint32_t p);      // (CSDR_NO_RUN4096: no)
+int  plan4096_create(const FusedConfig &cfg, ChainPlan **out);
+
 // second-generation run kernel of the M = 256 chain (kernels_fused_v2.hip): whole-band calls of >= run_min_tiles tiles.
 // run_args points at a RunArgs (fused_common.h) the plan fills.
 int  run256_v2_launch(const void *run_args, bool fm, unsigned G, unsigned nruns, hipStream_t s);
@@ -56,41 +104,6 @@ int  run256_dcfix_launch(const void *run_args, bool fm, unsigned nruns, const fl
 // one 512-thread workgroup per CU, front / back wave roles; linked only by tools/variants/build_run256_v3.sh (-DCSDR_WITH_RUN256_V3)
 int  run256_v3_launch(const void *run_args, bool fm, unsigned nruns, hipStream_t s);
 
-
-// M = 64 run kernel (kernels_fused_small.hip): same call interface
-struct SmallPlan;
-bool small_supported(uint32_t M, uint32_t p);
-int  small_create(const FusedConfig &cfg, SmallPlan **out);
-int  small_reset(SmallPlan *plan, hipStream_t s);
-int  small_process(SmallPlan *plan, const FusedCall &call, hipStream_t s, KernelTimer *timer);
-void small_seek(SmallPlan *plan, uint64_t frames);
-const char *small_name(const SmallPlan *plan);
-bool small_tile_major_ok(const SmallPlan *plan, uint32_t nf);     // the call goes to k_run64v2 as whole 64-frame tiles, no mix inside the plan
-void small_destroy(SmallPlan *plan);
-
-
-// M = 1024 run kernel (kernels_pfb1024.hip, DC = true): same call interface
-struct BigPlan;
-bool big_supported(uint32_t M, uint32_t p);
-int  big_create(const FusedConfig &cfg, BigPlan **out);
-int  big_reset(BigPlan *plan, hipStream_t s);
-int  big_process(BigPlan *plan, const FusedCall &call, hipStream_t s, KernelTimer *timer);
-void big_seek(BigPlan *plan, uint64_t frames);
-const char *big_name(const BigPlan *plan);
-bool big_tile_major_ok(const BigPlan *plan, uint32_t nf);     // FusedCall::tile_major for this call (CF32 output through k_run1024v3<CF32>)
-void big_destroy(BigPlan *plan);
-
-// M = 4096 (kernels_pfb4096.hip): branch-tiled front kernel (DC blocker + pre-mix + FIR + first radix-4 stage) -> z -> back kernel (four
-// 1024-point DFTs per frame + tails); whole band; same call interface
-struct HugePlan;
-bool huge_supported(uint32_t M, uint32_t p);
-int  huge_create(const FusedConfig &cfg, HugePlan **out);
-int  huge_reset(HugePlan *plan, hipStream_t s);
-int  huge_process(HugePlan *plan, const FusedCall &call, hipStream_t s, KernelTimer *timer);
-void huge_seek(HugePlan *plan, uint64_t frames);
-const char *huge_name(const HugePlan *plan);
-bool huge_tile_major_ok(const HugePlan *plan, uint32_t nf);      // CF32 output, whole 16-frame blocks, no mix inside the plan
-void huge_destroy(HugePlan *plan);
 
 // k_run64v2 (kernels_run64_v2.hip): whole-band M = 64 calls with CF32 output and nf % 64 == 0; same state buffers as k_run64
 struct Run64v2Host {

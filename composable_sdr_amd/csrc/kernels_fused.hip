@@ -362,25 +362,21 @@ __global__ __launch_bounds__(64) void k_shard_gather(const float *__restrict__ s
     for (uint32_t i = threadIdx.x; i < rem * w; i += 64) dst[((size_t)m * nf + t0) * w + i] = src[(size_t)(c0 + G * m) * rem * w + i];
 }
 
-struct FusedPlan {
-    FusedConfig cfg;
-    std::string name;
+struct FusedPlan : ChainPlan {
+    using ChainPlan::ChainPlan;
+    std::string kernel;
     uint32_t max_nb = 0, epoch = 0;
-    uint64_t frames_done = 0;    // global frame counter (parity selects the premix phasor row)
     float *d_taps = nullptr;
     float2 *d_tw = nullptr, *d_wpre = nullptr;
     float2 *d_yhist[2] = {nullptr, nullptr}, *d_vend[2] = {nullptr, nullptr}, *d_rp[2] = {nullptr, nullptr};
-    int cur = 0;
     unsigned *d_ticket = nullptr, *d_yflag = nullptr, *d_status = nullptr;
     u64 *d_agg = nullptr, *d_ylast = nullptr;
-    void *d_premix = nullptr;    // per-channel output before mixing
     // whole-band run-kernel launches without warm-up windows (RunArgs::nowu, round 5): DC state in front of every run's halo tile, the
     // uncorrected near-DC channels of every run's first tiles, the chain's response to a unit DC state (k_run256_dcfix)
     float2 *d_cpre = nullptr, *d_side = nullptr, *d_rt = nullptr;
     bool nowu = false;
     u64 *d_trace = nullptr;
     uint32_t run_min_tiles = 1024;   // chunks with at least this many tiles use the run kernel (measured crossover: FM ~900 tiles, CF32 ~700; profiles/r04_call_size_sweeps.txt)
-    uint32_t cus = 256;
     float slot_weight[8] = {1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f};   // tile share of the k-th co-resident run of a CU
     uint32_t resident_wgs_v2 = 512;  // workgroups of k_run256v2 the device holds at once
     bool use_v3 = false;             // variant builds only (CSDR_WITH_RUN256_V3 + CSDR_RUN_V3=1): k_run256v3, round 4's one-workgroup-per-CU experiment (tools/variants/)
@@ -389,11 +385,50 @@ struct FusedPlan {
     float *d_shard_tail = nullptr;   // interleaved shard: whole-band result of a call's ragged end, [256][< 16] CF32 at most
     float4 *d_tail[3] = {nullptr, nullptr, nullptr};
     int tail_w = 0;                  // slot that holds the tail of the most recent chunk
-    bool tail_valid = false, keep_tail = false;
+    bool tail_valid = false, save_tails = false;
     TileArgs proto;
+
+    int init();
+    const char *name() const override { return kernel.c_str(); }
+    bool tile_major_ok(uint32_t nf) const override;
+    void keep_tail() override { save_tails = cfg.G == 1; }     // interleaved shards never run as independent launches
+    bool can_overlap(uint32_t nf) const override;
+    bool tail_recorded() const override { return save_tails && tail_valid; }
+    int status(unsigned *st) override;
+    int trace(unsigned long long *out, uint32_t ntiles) override;
+    int reset_state(hipStream_t s) override;
+    int run(const FusedCall &call, void *out, hipStream_t s, KernelTimer *timer) override;
+    bool v2_call(uint32_t nf) const { return cfg.G == 1 && cfg.c0 == 0 && cfg.C == cfg.M && nf / NB >= run_min_tiles; }
 };
 
-bool fused_supported(uint32_t M, uint32_t p) { return M == 256 && p == P; }
+int ChainPlan::process(const FusedCall &call, hipStream_t s, KernelTimer *timer)
+{
+    if (!call.nf) return 0;
+    if ((call.tile_major && !tile_major_ok(call.nf)) || (call.indep && !can_overlap(call.nf))) {
+        set_error("fused: internal: tile-major output or an independent launch requested from a call that cannot run as one");
+        return -1;
+    }
+    int r = run(call, d_premix ? d_premix : call.d_out, s, timer);
+    if (r) return r;
+    cur ^= 1;
+    frames_done += call.nf;
+    if (d_premix) return launch_mix((const float *)d_premix, (float *)call.d_out, cfg.C, cfg.fm ? call.nf : 2 * call.nf, s);
+    return 0;
+}
+
+std::vector<float2> ChainPlan::premix_table() const
+{
+    std::vector<float2> wpre(2 * cfg.M);
+    for (uint32_t i = 0; i < 2 * cfg.M; i++) {
+        float c, s;
+        nco_phasor(i * cfg.d_theta, &c, &s);
+        wpre[i] = make_float2(c, -s);
+    }
+    return wpre;
+}
+
+bool plan256_supported(uint32_t M, uint32_t p) { return M == 256 && p == P; }
+int plan256_create(const FusedConfig &cfg, ChainPlan **out) { return make_plan<FusedPlan>(cfg, out); }
 
 void dc_state_response(const FusedConfig &cfg, const float2 *wpre, uint32_t f0, uint32_t nfr, uint32_t k0, float2 *rt)
 {
@@ -432,59 +467,55 @@ void dc_state_response(const FusedConfig &cfg, const float2 *wpre, uint32_t f0, 
     }
 }
 
-int fused_create(const FusedConfig &cfg, FusedPlan **out)
+int FusedPlan::init()
 {
-    FusedPlan *p = new FusedPlan();
-    p->cfg = cfg;
-    p->name = cfg.fm ? "k_tile256<FM>" : "k_tile256<CF32>";
-    p->max_nb = (cfg.max_nf + NB - 1) / NB;
-    auto fail = [&](int r) { fused_destroy(p); return r; };
-#define ALLOC(ptr, bytes) do { hipError_t e = hipMalloc((void **)&(ptr), (bytes) ? (bytes) : 1); if (e != hipSuccess) return fail(hip_fail(e, "hipMalloc", __FILE__, __LINE__)); } while (0)
-    ALLOC(p->d_taps, sizeof(float) * cfg.M * cfg.p);
-    ALLOC(p->d_tw, sizeof(float2) * cfg.M);
-    ALLOC(p->d_wpre, sizeof(float2) * 2 * cfg.M);
+    int r;
+    kernel = cfg.fm ? "k_tile256<FM>" : "k_tile256<CF32>";
+    max_nb = (cfg.max_nf + NB - 1) / NB;
+    if ((r = mem.alloc(&d_taps, sizeof(float) * cfg.M * cfg.p))) return r;
+    if ((r = mem.alloc(&d_tw, sizeof(float2) * cfg.M))) return r;
+    if ((r = mem.alloc(&d_wpre, sizeof(float2) * 2 * cfg.M))) return r;
     for (int i = 0; i < 2; i++) {
-        ALLOC(p->d_yhist[i], sizeof(float2) * 13 * cfg.M);
-        ALLOC(p->d_vend[i], sizeof(float2));
-        ALLOC(p->d_rp[i], sizeof(float2) * (cfg.G > 1 ? cfg.M : cfg.C));     // interleaved shard: full-band indices (fused_v2: rp_in / rp_out)
+        if ((r = mem.alloc(&d_yhist[i], sizeof(float2) * 13 * cfg.M))) return r;
+        if ((r = mem.alloc(&d_vend[i], sizeof(float2)))) return r;
+        if ((r = mem.alloc(&d_rp[i], sizeof(float2) * (cfg.G > 1 ? cfg.M : cfg.C)))) return r;     // interleaved shard: full-band indices (fused_v2: rp_in / rp_out)
     }
-    if (cfg.G > 1) ALLOC(p->d_shard_tail, sizeof(float2) * cfg.M * NB);
-    for (int i = 0; i < 3; i++) { ALLOC(p->d_tail[i], sizeof(float4) * 2048 * (WU + 1)); CSDR_HIP(hipMemset(p->d_tail[i], 0, sizeof(float4) * 2048 * (WU + 1))); }
-    p->tail_valid = true;            // a fresh stream: zero history IS the exact history
-    ALLOC(p->d_ticket, sizeof(unsigned));
-    ALLOC(p->d_status, sizeof(unsigned));
-    ALLOC(p->d_yflag, sizeof(unsigned) * p->max_nb);
-    ALLOC(p->d_agg, sizeof(u64) * 2 * p->max_nb);
-    ALLOC(p->d_ylast, sizeof(u64) * (size_t)cfg.M * p->max_nb);
-    if (const char *e = diag_env("CSDR_RUN_MIN_TILES")) p->run_min_tiles = (uint32_t)atol(e);
-    if (cfg.mix) ALLOC(p->d_premix, (size_t)cfg.C * cfg.max_nf * (cfg.fm ? 4 : 8));
-    if (diag_env("CSDR_TRACE")) { ALLOC(p->d_trace, sizeof(u64) * 16 * p->max_nb); CSDR_HIP(hipMemset(p->d_trace, 0, sizeof(u64) * 16 * p->max_nb)); }
-    p->nowu = cfg.G == 1 && cfg.c0 == 0 && cfg.C == cfg.M && cfg.dc_block && dc_window_ok(cfg.dc, (DCFIX_F - 1) * 256.0) &&     // k_run256_dcfix: 112 frames
-              !(diag_env("CSDR_NOWU") && atoi(diag_env("CSDR_NOWU")) == 0);
-    if (p->nowu) {
-        ALLOC(p->d_cpre, sizeof(float2) * 2050);
-        ALLOC(p->d_side, sizeof(float2) * 2048 * 4 * DCFIX_F);
-        ALLOC(p->d_rt, sizeof(float2) * 2 * DCFIX_F * 4);
-        CSDR_HIP(hipMemset(p->d_cpre, 0, sizeof(float2) * 2050));
+    if (cfg.G > 1 && (r = mem.alloc(&d_shard_tail, sizeof(float2) * cfg.M * NB))) return r;
+    for (int i = 0; i < 3; i++) {
+        if ((r = mem.alloc(&d_tail[i], sizeof(float4) * 2048 * (WU + 1)))) return r;
+        CSDR_HIP(hipMemset(d_tail[i], 0, sizeof(float4) * 2048 * (WU + 1)));
     }
-#undef ALLOC
-    CSDR_HIP(hipMemcpy(p->d_taps, cfg.taps, sizeof(float) * cfg.M * cfg.p, hipMemcpyHostToDevice));
-    std::vector<float2> tw(cfg.M), wpre(2 * cfg.M);
+    tail_valid = true;               // a fresh stream: zero history IS the exact history
+    if ((r = mem.alloc(&d_ticket, sizeof(unsigned)))) return r;
+    if ((r = mem.alloc(&d_status, sizeof(unsigned)))) return r;
+    if ((r = mem.alloc(&d_yflag, sizeof(unsigned) * max_nb))) return r;
+    if ((r = mem.alloc(&d_agg, sizeof(u64) * 2 * max_nb))) return r;
+    if ((r = mem.alloc(&d_ylast, sizeof(u64) * (size_t)cfg.M * max_nb))) return r;
+    if (const char *e = diag_env("CSDR_RUN_MIN_TILES")) run_min_tiles = (uint32_t)atol(e);
+    if (cfg.mix && (r = mem.alloc(&d_premix, (size_t)cfg.C * cfg.max_nf * (cfg.fm ? 4 : 8)))) return r;
+    if (diag_env("CSDR_TRACE")) {
+        if ((r = mem.alloc(&d_trace, sizeof(u64) * 16 * max_nb))) return r;
+        CSDR_HIP(hipMemset(d_trace, 0, sizeof(u64) * 16 * max_nb));
+    }
+    nowu = cfg.G == 1 && cfg.c0 == 0 && cfg.C == cfg.M && cfg.dc_block && dc_window_ok(cfg.dc, (DCFIX_F - 1) * 256.0) &&     // k_run256_dcfix: 112 frames
+           !(diag_env("CSDR_NOWU") && atoi(diag_env("CSDR_NOWU")) == 0);
+    if (nowu) {
+        if ((r = mem.alloc(&d_cpre, sizeof(float2) * 2050))) return r;
+        if ((r = mem.alloc(&d_side, sizeof(float2) * 2048 * 4 * DCFIX_F))) return r;
+        if ((r = mem.alloc(&d_rt, sizeof(float2) * 2 * DCFIX_F * 4))) return r;
+        CSDR_HIP(hipMemset(d_cpre, 0, sizeof(float2) * 2050));
+    }
+    CSDR_HIP(hipMemcpy(d_taps, cfg.taps, sizeof(float) * cfg.M * cfg.p, hipMemcpyHostToDevice));
+    std::vector<float2> tw(cfg.M);
     for (uint32_t k1 = 0; k1 < 16; k1++)
         for (uint32_t b1 = 0; b1 < 16; b1++) {
             const double a = -2.0 * 3.14159265358979323846 * (double)(b1 * k1) / (double)cfg.M;
             tw[16 * k1 + b1] = make_float2((float)std::cos(a), (float)std::sin(a));
         }
-    // nco_crcf_mix_block_down multiplies by conj(cos + j sin) of theta = n*d_theta; for M = 256
-    // the phase sequence has period 2M: row 0 = even frames (n = j), row 1 = odd (n = M + j)
-    for (uint32_t i = 0; i < 2 * cfg.M; i++) {
-        float c, s;
-        nco_phasor(i * cfg.d_theta, &c, &s);
-        wpre[i] = make_float2(c, -s);
-    }
-    CSDR_HIP(hipMemcpy(p->d_tw, tw.data(), sizeof(float2) * cfg.M, hipMemcpyHostToDevice));
-    CSDR_HIP(hipMemcpy(p->d_wpre, wpre.data(), sizeof(float2) * 2 * cfg.M, hipMemcpyHostToDevice));
-    if (p->nowu) {
+    const std::vector<float2> wpre = premix_table();
+    CSDR_HIP(hipMemcpy(d_tw, tw.data(), sizeof(float2) * cfg.M, hipMemcpyHostToDevice));
+    CSDR_HIP(hipMemcpy(d_wpre, wpre.data(), sizeof(float2) * 2 * cfg.M, hipMemcpyHostToDevice));
+    if (nowu) {
         // Response of the chain, at the channels 126..129, to a DC-blocker state of 1 in front of a tile: the blocker's output carries
         // -alpha beta^n of it at sample n, which goes through the pre-mix (the table above), the polyphase FIR and the DFT like any
         // input.  Frames 15 .. 127 behind the tile's start = frame -1 .. 111 of the run that started its halo tile without its state;
@@ -492,17 +523,17 @@ int fused_create(const FusedConfig &cfg, FusedPlan **out)
         // the tile's first frame; f64 throughout.
         std::vector<float2> rt((size_t)2 * DCFIX_F * 4);
         dc_state_response(cfg, wpre.data(), 15u, (uint32_t)DCFIX_F, 126u, rt.data());
-        CSDR_HIP(hipMemcpy(p->d_rt, rt.data(), sizeof(float2) * rt.size(), hipMemcpyHostToDevice));
+        CSDR_HIP(hipMemcpy(d_rt, rt.data(), sizeof(float2) * rt.size(), hipMemcpyHostToDevice));
     }
-    CSDR_HIP(hipMemset(p->d_status, 0, sizeof(unsigned)));
-    CSDR_HIP(hipMemset(p->d_yflag, 0, sizeof(unsigned) * p->max_nb));
-    CSDR_HIP(hipMemset(p->d_agg, 0, sizeof(u64) * 2 * p->max_nb));
+    CSDR_HIP(hipMemset(d_status, 0, sizeof(unsigned)));
+    CSDR_HIP(hipMemset(d_yflag, 0, sizeof(unsigned) * max_nb));
+    CSDR_HIP(hipMemset(d_agg, 0, sizeof(u64) * 2 * max_nb));
 
-    TileArgs &A = p->proto;
+    TileArgs &A = proto;
     A = TileArgs{};
-    A.taps = p->d_taps; A.tw = p->d_tw; A.wpre = p->d_wpre;
-    A.ticket = p->d_ticket; A.agg = p->d_agg; A.ylast = p->d_ylast; A.yflag = p->d_yflag; A.status = p->d_status;
-    A.c0 = cfg.c0; A.C = cfg.C; A.fm_ref = cfg.fm_ref; A.trace = p->d_trace;
+    A.taps = d_taps; A.tw = d_tw; A.wpre = d_wpre;
+    A.ticket = d_ticket; A.agg = d_agg; A.ylast = d_ylast; A.yflag = d_yflag; A.status = d_status;
+    A.c0 = cfg.c0; A.C = cfg.C; A.fm_ref = cfg.fm_ref; A.trace = d_trace;
     const double beta = cfg.dc_block ? (double)cfg.dc.beta : 0.0;
     A.alpha = cfg.dc_block ? (float)(1.0 - beta) : 0.0f;    // alpha = 1 - beta with beta = f32(1 - 0.0005)
     A.beta = (float)beta;
@@ -510,100 +541,77 @@ int fused_create(const FusedConfig &cfg, FusedPlan **out)
     for (int k = 0; k < 16; k++) A.b16[k] = (float)std::pow(beta, 16.0 * k);
     for (int k = 0; k < 17; k++) A.b256[k] = (float)std::pow(beta, 256.0 * k);
     for (int k = 0; k < 16; k++) A.bj[k] = (float)std::pow(beta, (double)k);
-    {
-        int dev = 0, cus = 256;
-        (void)hipGetDevice(&dev);
-        (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-        if (const char *e = diag_env("CSDR_CUS")) { if (atoi(e) > 0 && atoi(e) < cus) cus = atoi(e); }      // experiments: a plan sized for a CU-masked stream
-        p->cus = (uint32_t)cus;
-        p->resident_wgs_v2 = (uint32_t)(cus * run256_v2_blocks_per_cu(cfg.fm));
-        if (const char *e = diag_env("CSDR_RESIDENT_WGS")) p->resident_wgs_v2 = (uint32_t)atol(e);
+    if (const char *e = diag_env("CSDR_CUS")) { if (atoi(e) > 0 && (uint32_t)atoi(e) < cus) cus = (uint32_t)atoi(e); }     // experiments: a plan sized for a CU-masked stream
+    resident_wgs_v2 = (uint32_t)(cus * run256_v2_blocks_per_cu(cfg.fm));
+    if (const char *e = diag_env("CSDR_RESIDENT_WGS")) resident_wgs_v2 = (uint32_t)atol(e);
 #ifdef CSDR_WITH_RUN256_V3          // variant build only (tools/variants/build_run256_v3.sh): round 4's one-workgroup-per-CU experiment
-        if (const char *e = diag_env("CSDR_RUN_V3")) p->use_v3 = atoi(e) != 0;
+    if (const char *e = diag_env("CSDR_RUN_V3")) use_v3 = atoi(e) != 0;
 #endif
-        if (const char *e = diag_env("CSDR_RUN_WEIGHTS")) {
-            int k = 0;
-            for (const char *q = e; *q && k < 8; k++) { p->slot_weight[k] = (float)atof(q); q = strchr(q, ','); if (!q) break; q++; }
-        }
+    if (const char *e = diag_env("CSDR_RUN_WEIGHTS")) {
+        int k = 0;
+        for (const char *q = e; *q && k < 8; k++) { slot_weight[k] = (float)atof(q); q = strchr(q, ','); if (!q) break; q++; }
     }
-    *out = p;
     return 0;
 }
 
-int fused_reset(FusedPlan *p, hipStream_t s)
+int FusedPlan::reset_state(hipStream_t s)
 {
-    p->cur = 0; p->frames_done = 0;
     for (int i = 0; i < 2; i++) {
-        CSDR_HIP(hipMemsetAsync(p->d_yhist[i], 0, sizeof(float2) * 13 * p->cfg.M, s));
-        CSDR_HIP(hipMemsetAsync(p->d_vend[i], 0, sizeof(float2), s));
-        CSDR_HIP(hipMemsetAsync(p->d_rp[i], 0, sizeof(float2) * (p->cfg.G > 1 ? p->cfg.M : p->cfg.C), s));
+        CSDR_HIP(hipMemsetAsync(d_yhist[i], 0, sizeof(float2) * 13 * cfg.M, s));
+        CSDR_HIP(hipMemsetAsync(d_vend[i], 0, sizeof(float2), s));
+        CSDR_HIP(hipMemsetAsync(d_rp[i], 0, sizeof(float2) * (cfg.G > 1 ? cfg.M : cfg.C), s));
     }
-    CSDR_HIP(hipMemsetAsync(p->d_tail[0], 0, sizeof(float4) * 2048 * (WU + 1), s));
-    p->tail_w = 0; p->tail_valid = true;
+    CSDR_HIP(hipMemsetAsync(d_tail[0], 0, sizeof(float4) * 2048 * (WU + 1), s));
+    tail_w = 0; tail_valid = true;
     return 0;
 }
 
-void fused_keep_tail(FusedPlan *p) { p->keep_tail = p->cfg.G == 1; }     // interleaved shards never run as independent launches
-bool fused_tail_recorded(const FusedPlan *p) { return p->keep_tail && p->tail_valid; }
-
-static bool fused_v2_call(const FusedPlan *p, uint32_t nf)
-{
-    const FusedConfig &c = p->cfg;
-    return c.G == 1 && c.c0 == 0 && c.C == c.M && nf / NB >= p->run_min_tiles;
-}
-
-bool fused_tile_major_ok(const FusedPlan *p, uint32_t nf)
+bool FusedPlan::tile_major_ok(uint32_t nf) const
 {
     // the calls that go to k_run256v2 / v3 as whole tiles: CF32 output below 4 GiB, no mix inside the plan
-    const FusedConfig &c = p->cfg;
-    const bool shard = c.G > 1;
-    if (c.fm || c.mix || nf % NB || !nf) return false;
-    if (shard) return (uint64_t)c.C * nf * 8u < (1ull << 32);
-    return c.c0 == 0 && c.C == c.M && nf / NB >= p->run_min_tiles;
+    if (cfg.fm || cfg.mix || nf % NB || !nf) return false;
+    if (cfg.G > 1) return (uint64_t)cfg.C * nf * 8u < (1ull << 32);
+    return cfg.c0 == 0 && cfg.C == cfg.M && nf / NB >= run_min_tiles;
 }
 
-bool fused_can_overlap(const FusedPlan *p, uint32_t nf)
+bool FusedPlan::can_overlap(uint32_t nf) const
 {
-    return p->keep_tail && p->tail_valid && fused_v2_call(p, nf) && nf % NB == 0 && !p->cfg.mix;
+    return save_tails && tail_valid && v2_call(nf) && nf % NB == 0 && !cfg.mix;
 }
 
-int fused_process(FusedPlan *p, const FusedCall &call, hipStream_t s, KernelTimer *timer)
+int FusedPlan::run(const FusedCall &call, void *out, hipStream_t s, KernelTimer *timer)
 {
-    const FusedConfig &c = p->cfg;
+    const FusedConfig &c = cfg;
     const uint32_t nf = call.nf;
-    if (!nf) return 0;
     int r;
-    TileArgs A = p->proto;
+    TileArgs A = proto;
     A.x = call.d_in;
-    A.out = c.mix ? p->d_premix : call.d_out;
-    A.yhist_in = p->d_yhist[p->cur]; A.yhist_out = p->d_yhist[p->cur ^ 1];
-    A.vend_in = p->d_vend[p->cur];   A.vend_out = p->d_vend[p->cur ^ 1];
-    A.rp_in = p->d_rp[p->cur];       A.rp_out = p->d_rp[p->cur ^ 1];
+    A.out = out;
+    A.yhist_in = d_yhist[cur]; A.yhist_out = d_yhist[cur ^ 1];
+    A.vend_in = d_vend[cur];   A.vend_out = d_vend[cur ^ 1];
+    A.rp_in = d_rp[cur];       A.rp_out = d_rp[cur ^ 1];
     A.out_stride = nf; A.out_t0 = 0;
-    if (call.tile_major) {
-        if (!fused_tile_major_ok(p, nf)) { set_error("fused: internal: tile-major output requested from a call that cannot write it"); return -1; }
-        A.out_stride = NB;                   // a row's 16 frames of a tile are one 128-byte line; rows follow each other inside the tile's block
-    }
-    A.parity0 = (uint32_t)(p->frames_done & 1);
+    if (call.tile_major) A.out_stride = NB;      // a row's 16 frames of a tile are one 128-byte line; rows follow each other inside the tile's block
+    A.parity0 = (uint32_t)(frames_done & 1);
     const uint32_t nb_full = nf / NB;
     const bool shard = c.G > 1;      // interleaved shard: every whole tile goes through k_run256v2<.., G> (the tile kernel only knows whole bands)
     if (shard && (uint64_t)c.C * nf * (c.fm ? 4u : 8u) >= (1ull << 32)) { set_error("fused: interleaved shard output of %u frames exceeds 4 GiB", nf); return -1; }
     const bool whole_band = c.G == 1 && c.c0 == 0 && c.C == c.M;      // (a contiguous channel shard takes the tile kernel, which masks its stores, at every size)
-    if ((nb_full >= p->run_min_tiles && whole_band) || shard) {
+    if ((nb_full >= run_min_tiles && whole_band) || shard) {
         // large chunk: dependency-free runs of full tiles (k_run256v2; its lane offsets are 32-bit over 16 rows and the row groups
         // go through a 64-bit base, so the output may exceed 4 GiB); a ragged tail (< 16 frames) follows as a second launch of the
         // tile kernel on the state the run kernel leaves behind
         const bool v2 = true;
         // third generation: one 512-thread workgroup per CU (half the cold starts), whole band
-        const bool v3 = !shard && p->use_v3;
-        p->name = v3 ? (c.fm ? "k_run256v3<FM>" : "k_run256v3<CF32>") : (c.fm ? "k_run256v2<FM>" : "k_run256v2<CF32>");
-        if (shard) p->name += "/G" + std::to_string(c.G);
+        const bool v3 = !shard && use_v3;
+        kernel = v3 ? (c.fm ? "k_run256v3<FM>" : "k_run256v3<CF32>") : (c.fm ? "k_run256v2<FM>" : "k_run256v2<CF32>");
+        if (shard) kernel += "/G" + std::to_string(c.G);
         RunArgs RA{};
         A.nf = nb_full * NB; A.nb = nb_full;
         RA.t = A; RA.pk = phase_consts(c.fm_ref);
         // one run per resident workgroup slot (a single round), runs balanced to within one tile,
         // at least 8 tiles per run so that the warm-up reads stay below 7/8 of a run
-        uint32_t nruns = v3 ? p->cus : p->resident_wgs_v2;
+        uint32_t nruns = v3 ? cus : resident_wgs_v2;
         if (v3) { if (const char *e = diag_env("CSDR_V3_RUNS")) nruns = (uint32_t)atol(e); }
         if (nruns > A.nb / 8) nruns = A.nb / 8;
         if (nruns < 1) nruns = 1;
@@ -616,8 +624,8 @@ int fused_process(FusedPlan *p, const FusedCall &call, hipStream_t s, KernelTime
         const float *v2_weight = c.fm ? v2_weight_fm : v2_weight_cf;
         static const float equal_weight[8] = {1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f};
         static const bool pd_equal = diag_env("CSDR_PD_EQUAL") != nullptr;
-        RA.split = make_split(A.nb, nruns, p->cus, (call.indep && pd_equal) ? equal_weight : ((v2 && !diag_env("CSDR_RUN_WEIGHTS")) ? v2_weight : p->slot_weight));
-        { const char *e = diag_env("CSDR_PRIO_ROT"); RA.prio_div = e ? (atoi(e) ? p->cus : 0u) : (v2 ? 0u : p->cus); }
+        RA.split = make_split(A.nb, nruns, cus, (call.indep && pd_equal) ? equal_weight : ((v2 && !diag_env("CSDR_RUN_WEIGHTS")) ? v2_weight : slot_weight));
+        { const char *e = diag_env("CSDR_PRIO_ROT"); RA.prio_div = e ? (atoi(e) ? cus : 0u) : (v2 ? 0u : cus); }
         { const char *e = diag_env("CSDR_TRACE"); RA.trace_light = (e && atoi(e) == 2) ? 1u : 0u; }
         { const char *e = diag_env("CSDR_WU"); RA.wu = e ? (uint32_t)atoi(e) : (uint32_t)WU; }       // experiments: fewer tiles = wrong DC state at run starts
         { const char *e = diag_env("CSDR_WU_ROT"); RA.wu_rot = e ? (uint32_t)atoi(e) : 0u; }      // measured: no effect on the run-start burst
@@ -626,95 +634,77 @@ int fused_process(FusedPlan *p, const FusedCall &call, hipStream_t s, KernelTime
         RA.l2beta = c.dc_block ? (float)std::log2((double)c.dc.beta) : -1000.0f;
         RA.tile_step = call.tile_major ? c.C * 128u : (uint32_t)NB * (c.fm ? 4u : 8u);
         const bool whole = nf == nb_full * NB;
-        RA.indep = (call.indep && v2 && whole && !c.mix && p->keep_tail && p->tail_valid) ? 1u : 0u;
+        RA.indep = call.indep ? 1u : 0u;     // (process() has checked can_overlap)
         // whole band, dependent launches: no warm-up windows (the DC state a run misses at its start is put back, where it still matters 16 frames
         // later -- the four channels around DC -- by k_run256_dcfix behind the launch); runs of >= 8 tiles, <= 2048 of them
-        RA.nowu = (p->nowu && !shard && !v3 && !RA.indep && nruns >= 2 && nruns <= 2048) ? 1u : 0u;
-        RA.cpre = p->d_cpre; RA.side = p->d_side;
-        RA.prev_tail = p->d_tail[p->tail_w];
-        if (call.indep && !RA.indep) { set_error("fused: internal: independent launch requested from a call that cannot run as one"); return -1; }
-        if (p->keep_tail && !shard && v2 && whole && nb_full >= WU + 1) {
+        RA.nowu = (nowu && !shard && !v3 && !RA.indep && nruns >= 2 && nruns <= 2048) ? 1u : 0u;
+        RA.cpre = d_cpre; RA.side = d_side;
+        RA.prev_tail = d_tail[tail_w];
+        if (save_tails && !shard && v2 && whole && nb_full >= WU + 1) {
             // this chunk's last WU + 1 tiles, for run 0 of the next call (queued in front of the launch: the copy only reads the input)
-            const int nxt = (p->tail_w + 1) % 3;
+            const int nxt = (tail_w + 1) % 3;
             static const bool nocopy = diag_env("CSDR_PD_NOCOPY") != nullptr;      // scheduling experiments only (wrong run-0 starts)
             if (!nocopy) hipLaunchKernelGGL(k_save_tail, dim3(2048 * (WU + 1) / 256), dim3(256), 0, s,
-                                            reinterpret_cast<const float4 *>(call.d_in + (size_t)(nb_full - (WU + 1)) * 4096), p->d_tail[nxt]);
+                                            reinterpret_cast<const float4 *>(call.d_in + (size_t)(nb_full - (WU + 1)) * 4096), d_tail[nxt]);
             if (call.ev_tail) CSDR_HIP(hipEventRecord(call.ev_tail, s));
-            p->tail_w = nxt; p->tail_valid = true;
-        } else p->tail_valid = false;
+            tail_w = nxt; tail_valid = true;
+        } else tail_valid = false;
         if (timer && (r = timer->begin(s))) return r;
         if (nb_full == 0) { /* shard, fewer than 16 frames: the tile kernel below does the whole call */ }
 #ifdef CSDR_WITH_RUN256_V3
         else if (v3) { if ((r = run256_v3_launch(&RA, c.fm, nruns, s))) return r; }
 #endif
         else if ((r = run256_v2_launch(&RA, c.fm, c.G, nruns, s))) return r;
-        if (RA.nowu && nb_full && (r = run256_dcfix_launch(&RA, c.fm, nruns, p->d_rt, s))) return r;
+        if (RA.nowu && nb_full && (r = run256_dcfix_launch(&RA, c.fm, nruns, d_rt, s))) return r;
         if (timer && (r = timer->end(s))) return r;             // the bracket covers k_run256_dcfix: it is part of every no-warm-up step
         const uint32_t rem = nf - nb_full * NB;
         if (rem) {
-            if (nb_full) p->cur ^= 1;                            // the tail starts from the run kernel's state
-            TileArgs T = p->proto;
+            if (nb_full) cur ^= 1;                            // the tail starts from the run kernel's state
+            TileArgs T = proto;
             T.x = call.d_in + (size_t)nb_full * NB * c.M; T.out = A.out;
-            if (shard) { T.c0 = 0; T.C = c.M; T.out = p->d_shard_tail; }   // whole band into [256][rem], the owned rows are gathered below
-            T.yhist_in = p->d_yhist[p->cur]; T.yhist_out = p->d_yhist[p->cur ^ 1];
-            T.vend_in = p->d_vend[p->cur];   T.vend_out = p->d_vend[p->cur ^ 1];
-            T.rp_in = p->d_rp[p->cur];       T.rp_out = p->d_rp[p->cur ^ 1];
-            if (++p->epoch == 0) p->epoch = 1;
-            T.epoch = p->epoch; T.nf = rem; T.nb = 1; T.out_stride = nf; T.out_t0 = nb_full * NB;
+            if (shard) { T.c0 = 0; T.C = c.M; T.out = d_shard_tail; }   // whole band into [256][rem], the owned rows are gathered below
+            T.yhist_in = d_yhist[cur]; T.yhist_out = d_yhist[cur ^ 1];
+            T.vend_in = d_vend[cur];   T.vend_out = d_vend[cur ^ 1];
+            T.rp_in = d_rp[cur];       T.rp_out = d_rp[cur ^ 1];
+            if (++epoch == 0) epoch = 1;
+            T.epoch = epoch; T.nf = rem; T.nb = 1; T.out_stride = nf; T.out_t0 = nb_full * NB;
             if (shard) { T.out_stride = rem; T.out_t0 = 0; }
-            T.parity0 = (uint32_t)((p->frames_done + nb_full * NB) & 1);
-            CSDR_HIP(hipMemsetAsync(p->d_ticket, 0, sizeof(unsigned), s));
+            T.parity0 = (uint32_t)((frames_done + nb_full * NB) & 1);
+            CSDR_HIP(hipMemsetAsync(d_ticket, 0, sizeof(unsigned), s));
             if (c.fm) hipLaunchKernelGGL(k_tile256<true>, dim3(1), dim3(256), 0, s, T);
             else hipLaunchKernelGGL(k_tile256<false>, dim3(1), dim3(256), 0, s, T);
-            if (shard) hipLaunchKernelGGL(k_shard_gather, dim3(c.C), dim3(64), 0, s, (const float *)p->d_shard_tail, (float *)A.out, c.c0, c.G, rem,
+            if (shard) hipLaunchKernelGGL(k_shard_gather, dim3(c.C), dim3(64), 0, s, (const float *)d_shard_tail, (float *)A.out, c.c0, c.G, rem,
                                           nf, nb_full * NB, c.fm ? 1u : 2u);
         }
     } else {
-        p->name = c.fm ? "k_tile256<FM>" : "k_tile256<CF32>";
-        p->tail_valid = false;
-        if (call.indep) { set_error("fused: internal: independent launch requested from a tile-kernel call"); return -1; }
-        if (++p->epoch == 0) p->epoch = 1;
-        A.epoch = p->epoch; A.nf = nf; A.nb = (nf + NB - 1) / NB;
-        CSDR_HIP(hipMemsetAsync(p->d_ticket, 0, sizeof(unsigned), s));
+        kernel = c.fm ? "k_tile256<FM>" : "k_tile256<CF32>";
+        tail_valid = false;
+        if (++epoch == 0) epoch = 1;
+        A.epoch = epoch; A.nf = nf; A.nb = (nf + NB - 1) / NB;
+        CSDR_HIP(hipMemsetAsync(d_ticket, 0, sizeof(unsigned), s));
         if (timer && (r = timer->begin(s))) return r;
         if (c.fm) hipLaunchKernelGGL(k_tile256<true>, dim3(A.nb), dim3(256), 0, s, A);
         else hipLaunchKernelGGL(k_tile256<false>, dim3(A.nb), dim3(256), 0, s, A);
         if (timer && (r = timer->end(s))) return r;
     }
     CSDR_HIP(hipGetLastError());
-    p->cur ^= 1;
-    p->frames_done += nf;
-    if (c.mix) {
-        if ((r = launch_mix((const float *)p->d_premix, (float *)call.d_out, c.C, c.fm ? nf : 2 * nf, s))) return r;
-    }
     return 0;
 }
 
-const char *fused_name(const FusedPlan *p) { return p->name.c_str(); }
-void fused_seek(FusedPlan *p, uint64_t frames) { p->frames_done = frames; }
-
-int fused_trace(FusedPlan *p, unsigned long long *out, uint32_t ntiles)
+int FusedPlan::trace(unsigned long long *out, uint32_t ntiles)
 {
-    if (!p->d_trace) return 0;
-    if (ntiles > p->max_nb) ntiles = p->max_nb;
-    CSDR_HIP(hipMemcpy(out, p->d_trace, sizeof(u64) * 16 * ntiles, hipMemcpyDeviceToHost));
+    (void)hipDeviceSynchronize();
+    if (!d_trace) return 0;
+    if (ntiles > max_nb) ntiles = max_nb;
+    CSDR_HIP(hipMemcpy(out, d_trace, sizeof(u64) * 16 * ntiles, hipMemcpyDeviceToHost));
     return (int)ntiles;
 }
 
-int fused_status(FusedPlan *p, unsigned *status)
+int FusedPlan::status(unsigned *st)
 {
-    CSDR_HIP(hipMemcpy(status, p->d_status, sizeof(unsigned), hipMemcpyDeviceToHost));
-    if (*status) CSDR_HIP(hipMemset(p->d_status, 0, sizeof(unsigned)));     // sticky until reported once
+    CSDR_HIP(hipMemcpy(st, d_status, sizeof(unsigned), hipMemcpyDeviceToHost));
+    if (*st) CSDR_HIP(hipMemset(d_status, 0, sizeof(unsigned)));     // sticky until reported once
     return 0;
-}
-
-void fused_destroy(FusedPlan *p)
-{
-    if (!p) return;
-    void *ptrs[] = {p->d_shard_tail, p->d_tail[0], p->d_tail[1], p->d_tail[2], p->d_taps, p->d_tw, p->d_wpre, p->d_yhist[0], p->d_yhist[1], p->d_vend[0], p->d_vend[1], p->d_rp[0],
-                    p->d_rp[1], p->d_ticket, p->d_yflag, p->d_status, p->d_agg, p->d_ylast, p->d_premix, p->d_trace, p->d_cpre, p->d_side, p->d_rt};
-    for (void *q : ptrs) if (q) (void)hipFree(q);
-    delete p;
 }
 
 }  // namespace csdr

@@ -335,68 +335,59 @@ __global__ __launch_bounds__(64) void k_run64_fixup(const float2 *__restrict__ y
 // ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
-struct SmallPlan {
-    FusedConfig cfg;
-    uint32_t max_nb = 0, resident_wgs = 768, cus = 256;
+struct SmallPlan : ChainPlan {
+    using ChainPlan::ChainPlan;
+    uint32_t max_nb = 0, resident_wgs = 768;
     bool v2_ok = false, v2_last = false;     // k_run64v2 usable (CF32, whole band); used by the last call
-    uint64_t frames_done = 0;
     float *d_taps = nullptr;
     float2 *d_tw = nullptr, *d_wpre = nullptr;
     float2 *d_yhist[2] = {nullptr, nullptr}, *d_vend[2] = {nullptr, nullptr}, *d_rp[2] = {nullptr, nullptr};
     float2 *d_yfirst = nullptr, *d_ylast = nullptr;
     float2 *d_cpre = nullptr, *d_rt = nullptr;      // k_run64v2 without warm-up windows (Run64v2Host::cpre / rt)
-    void *d_premix = nullptr;
-    int cur = 0;
     TileArgs proto;
+
+    int init();
+    const char *name() const override { return cfg.fm ? "k_run64<FM>" : (v2_last ? "k_run64v2" : "k_run64<CF32>"); }
+    // the call goes to k_run64v2 as whole 64-frame tiles, no mix inside the plan
+    bool tile_major_ok(uint32_t nf) const override
+    {
+        return v2_ok && !cfg.mix && !cfg.fm && (uint64_t)cfg.C * nf * 8u < (1ull << 32) && run64_v2_runs(nf, cus) != 0;
+    }
+    int reset_state(hipStream_t s) override;
+    int run(const FusedCall &call, void *out, hipStream_t s, KernelTimer *timer) override;
 };
 
-bool small_supported(uint32_t M, uint32_t p) { return M == (uint32_t)MS && p == (uint32_t)P; }
+bool plan64_supported(uint32_t M, uint32_t p) { return M == (uint32_t)MS && p == (uint32_t)P; }
+int plan64_create(const FusedConfig &cfg, ChainPlan **out) { return make_plan<SmallPlan>(cfg, out); }
 
-void small_destroy(SmallPlan *p)
+int SmallPlan::init()
 {
-    if (!p) return;
-    void *ptrs[] = {p->d_taps, p->d_tw, p->d_wpre, p->d_yhist[0], p->d_yhist[1], p->d_vend[0], p->d_vend[1], p->d_rp[0],
-                    p->d_rp[1], p->d_yfirst, p->d_ylast, p->d_premix, p->d_cpre, p->d_rt};
-    for (void *q : ptrs) if (q) (void)hipFree(q);
-    delete p;
-}
-
-int small_create(const FusedConfig &cfg, SmallPlan **out)
-{
-    SmallPlan *p = new SmallPlan();
-    p->cfg = cfg;
-    p->max_nb = (cfg.max_nf + TS - 1) / TS;
-    auto fail = [&](int r) { small_destroy(p); return r; };
-#define ALLOC(ptr, bytes) do { hipError_t e = hipMalloc((void **)&(ptr), (bytes) ? (bytes) : 1); if (e != hipSuccess) return fail(hip_fail(e, "hipMalloc", __FILE__, __LINE__)); } while (0)
-    ALLOC(p->d_taps, sizeof(float) * cfg.M * cfg.p);
-    ALLOC(p->d_tw, sizeof(float2) * 16 * R2);
-    ALLOC(p->d_wpre, sizeof(float2) * 2 * cfg.M);
+    int r;
+    max_nb = (cfg.max_nf + TS - 1) / TS;
+    if ((r = mem.alloc(&d_taps, sizeof(float) * cfg.M * cfg.p))) return r;
+    if ((r = mem.alloc(&d_tw, sizeof(float2) * 16 * R2))) return r;
+    if ((r = mem.alloc(&d_wpre, sizeof(float2) * 2 * cfg.M))) return r;
     for (int i = 0; i < 2; i++) {
-        ALLOC(p->d_yhist[i], sizeof(float2) * 13 * cfg.M);
-        ALLOC(p->d_vend[i], sizeof(float2));
-        ALLOC(p->d_rp[i], sizeof(float2) * cfg.C);
+        if ((r = mem.alloc(&d_yhist[i], sizeof(float2) * 13 * cfg.M))) return r;
+        if ((r = mem.alloc(&d_vend[i], sizeof(float2)))) return r;
+        if ((r = mem.alloc(&d_rp[i], sizeof(float2) * cfg.C))) return r;
     }
-    ALLOC(p->d_yfirst, sizeof(float2) * (size_t)cfg.M * (p->max_nb + 2));
-    ALLOC(p->d_ylast, sizeof(float2) * (size_t)cfg.M * (p->max_nb + 2));
-    if (cfg.mix) ALLOC(p->d_premix, (size_t)cfg.C * cfg.max_nf * (cfg.fm ? 4 : 8));
-#undef ALLOC
-    CSDR_HIP(hipMemcpy(p->d_taps, cfg.taps, sizeof(float) * cfg.M * cfg.p, hipMemcpyHostToDevice));
-    std::vector<float2> tw(16 * R2), wpre(2 * cfg.M);
+    if ((r = mem.alloc(&d_yfirst, sizeof(float2) * (size_t)cfg.M * (max_nb + 2)))) return r;
+    if ((r = mem.alloc(&d_ylast, sizeof(float2) * (size_t)cfg.M * (max_nb + 2)))) return r;
+    if (cfg.mix && (r = mem.alloc(&d_premix, (size_t)cfg.C * cfg.max_nf * (cfg.fm ? 4 : 8)))) return r;
+    CSDR_HIP(hipMemcpy(d_taps, cfg.taps, sizeof(float) * cfg.M * cfg.p, hipMemcpyHostToDevice));
+    std::vector<float2> tw(16 * R2);
     for (int k1 = 0; k1 < 16; k1++)
         for (int b2 = 0; b2 < R2; b2++) {
             const double a = -2.0 * 3.14159265358979323846 * (double)(b2 * k1) / (double)cfg.M;
             tw[R2 * k1 + b2] = make_float2((float)std::cos(a), (float)std::sin(a));
         }
-    for (uint32_t i = 0; i < 2 * cfg.M; i++) {       // nco phase sequence has period 2M for a power-of-two M
-        float c, s;
-        nco_phasor(i * cfg.d_theta, &c, &s);
-        wpre[i] = make_float2(c, -s);
-    }
-    CSDR_HIP(hipMemcpy(p->d_tw, tw.data(), sizeof(float2) * tw.size(), hipMemcpyHostToDevice));
-    CSDR_HIP(hipMemcpy(p->d_wpre, wpre.data(), sizeof(float2) * wpre.size(), hipMemcpyHostToDevice));
-    TileArgs &A = p->proto;
+    const std::vector<float2> wpre = premix_table();
+    CSDR_HIP(hipMemcpy(d_tw, tw.data(), sizeof(float2) * tw.size(), hipMemcpyHostToDevice));
+    CSDR_HIP(hipMemcpy(d_wpre, wpre.data(), sizeof(float2) * wpre.size(), hipMemcpyHostToDevice));
+    TileArgs &A = proto;
     A = TileArgs{};
-    A.taps = p->d_taps; A.tw = p->d_tw; A.wpre = p->d_wpre;
+    A.taps = d_taps; A.tw = d_tw; A.wpre = d_wpre;
     A.c0 = cfg.c0; A.C = cfg.C; A.fm_ref = cfg.fm_ref;
     const double beta = cfg.dc_block ? (double)cfg.dc.beta : 0.0;
     A.alpha = cfg.dc_block ? (float)(1.0 - beta) : 0.0f;
@@ -404,89 +395,66 @@ int small_create(const FusedConfig &cfg, SmallPlan **out)
     for (int k = 0; k < 16; k++) A.b16[k] = (float)std::pow(beta, 16.0 * k);
     for (int k = 0; k < 17; k++) A.b256[k] = (float)std::pow(beta, 256.0 * k);
     for (int k = 0; k < 16; k++) A.bj[k] = (float)std::pow(beta, (double)k);
-    {
-        int dev = 0, cus = 256, occ = 3;
-        (void)hipGetDevice(&dev);
-        (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-        if (cfg.fm) (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_run64<true>, 256, 0);
-        else (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_run64<false>, 256, 0);
-        if (occ < 1) occ = 1;
-        p->resident_wgs = (uint32_t)(cus * occ);
-        p->cus = (uint32_t)cus;
-        p->v2_ok = !cfg.fm && cfg.c0 == 0 && cfg.C == (uint32_t)MS && !diag_env("CSDR_RUN64_V1");
-    }
-    if (p->v2_ok && cfg.dc_block && dc_window_ok(cfg.dc, RUN64_DCFIX_F * 64.0) && !(diag_env("CSDR_NOWU") && atoi(diag_env("CSDR_NOWU")) == 0)) {
+    int occ = 3;
+    if (cfg.fm) (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_run64<true>, 256, 0);
+    else (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_run64<false>, 256, 0);
+    if (occ < 1) occ = 1;
+    resident_wgs = cus * (uint32_t)occ;
+    v2_ok = !cfg.fm && cfg.c0 == 0 && cfg.C == (uint32_t)MS && !diag_env("CSDR_RUN64_V1");
+    if (v2_ok && cfg.dc_block && dc_window_ok(cfg.dc, RUN64_DCFIX_F * 64.0) && !(diag_env("CSDR_NOWU") && atoi(diag_env("CSDR_NOWU")) == 0)) {
         // k_run64v2 without warm-up windows: the state hand-over array and the chain's response to a unit DC state at the channels 30..33,
         // frames 64 .. 64 + RUN64_DCFIX_F - 1 behind a halo tile's start (= the run's first output frames)
-        hipError_t e1 = hipMalloc((void **)&p->d_cpre, sizeof(float2) * 1026), e2 = hipMalloc((void **)&p->d_rt, sizeof(float2) * 2 * RUN64_DCFIX_F * 4);
-        if (e1 != hipSuccess || e2 != hipSuccess) return fail(hip_fail(e1 != hipSuccess ? e1 : e2, "hipMalloc", __FILE__, __LINE__));
-        CSDR_HIP(hipMemset(p->d_cpre, 0, sizeof(float2) * 1026));
+        if ((r = mem.alloc(&d_cpre, sizeof(float2) * 1026)) || (r = mem.alloc(&d_rt, sizeof(float2) * 2 * RUN64_DCFIX_F * 4))) return r;
+        CSDR_HIP(hipMemset(d_cpre, 0, sizeof(float2) * 1026));
         std::vector<float2> rt((size_t)2 * RUN64_DCFIX_F * 4);
         dc_state_response(cfg, wpre.data(), 64u, (uint32_t)RUN64_DCFIX_F, 30u, rt.data());
-        CSDR_HIP(hipMemcpy(p->d_rt, rt.data(), sizeof(float2) * rt.size(), hipMemcpyHostToDevice));
+        CSDR_HIP(hipMemcpy(d_rt, rt.data(), sizeof(float2) * rt.size(), hipMemcpyHostToDevice));
     }
-    *out = p;
     return 0;
 }
 
-int small_reset(SmallPlan *p, hipStream_t s)
+int SmallPlan::reset_state(hipStream_t s)
 {
-    p->cur = 0; p->frames_done = 0;
     for (int i = 0; i < 2; i++) {
-        CSDR_HIP(hipMemsetAsync(p->d_yhist[i], 0, sizeof(float2) * 13 * p->cfg.M, s));
-        CSDR_HIP(hipMemsetAsync(p->d_vend[i], 0, sizeof(float2), s));
-        CSDR_HIP(hipMemsetAsync(p->d_rp[i], 0, sizeof(float2) * p->cfg.C, s));
+        CSDR_HIP(hipMemsetAsync(d_yhist[i], 0, sizeof(float2) * 13 * cfg.M, s));
+        CSDR_HIP(hipMemsetAsync(d_vend[i], 0, sizeof(float2), s));
+        CSDR_HIP(hipMemsetAsync(d_rp[i], 0, sizeof(float2) * cfg.C, s));
     }
     return 0;
 }
 
-void small_seek(SmallPlan *p, uint64_t frames) { p->frames_done = frames; }
-
-bool small_tile_major_ok(const SmallPlan *p, uint32_t nf)
+int SmallPlan::run(const FusedCall &call, void *out, hipStream_t s, KernelTimer *timer)
 {
-    return p && p->v2_ok && !p->cfg.mix && !p->cfg.fm && (uint64_t)p->cfg.C * nf * 8u < (1ull << 32) && run64_v2_runs(nf, p->cus) != 0;
-}
-
-int small_process(SmallPlan *p, const FusedCall &call, hipStream_t s, KernelTimer *timer)
-{
-    const FusedConfig &c = p->cfg;
+    const FusedConfig &c = cfg;
     const uint32_t nf = call.nf;
-    if (!nf) return 0;
     int r;
-    const uint32_t v2runs = (p->v2_ok && (uint64_t)c.C * nf * 8u < (1ull << 32)) ? run64_v2_runs(nf, p->cus) : 0;
-    p->v2_last = v2runs != 0;
-    if (call.tile_major && !v2runs) { set_error("small_process: tile-major output asked for a call k_run64v2 does not take"); return -1; }
+    const uint32_t v2runs = (v2_ok && (uint64_t)c.C * nf * 8u < (1ull << 32)) ? run64_v2_runs(nf, cus) : 0;
+    v2_last = v2runs != 0;
     if (v2runs) {
         Run64v2Host H{};
-        H.x = call.d_in; H.out = (float2 *)(c.mix ? p->d_premix : call.d_out);
-        H.taps = p->d_taps; H.tw = p->d_tw; H.wpre = p->d_wpre;
-        H.uhist_in = p->d_yhist[p->cur]; H.uhist_out = p->d_yhist[p->cur ^ 1];
-        H.vend_in = p->d_vend[p->cur]; H.vend_out = p->d_vend[p->cur ^ 1];
-        H.nf = nf; H.nruns = v2runs; H.parity0 = (uint32_t)(p->frames_done & 1);
+        H.x = call.d_in; H.out = (float2 *)out;
+        H.taps = d_taps; H.tw = d_tw; H.wpre = d_wpre;
+        H.uhist_in = d_yhist[cur]; H.uhist_out = d_yhist[cur ^ 1];
+        H.vend_in = d_vend[cur]; H.vend_out = d_vend[cur ^ 1];
+        H.nf = nf; H.nruns = v2runs; H.parity0 = (uint32_t)(frames_done & 1);
         H.tile_major = call.tile_major;
-        H.cpre = v2runs <= 1024u ? p->d_cpre : nullptr; H.rt = p->d_rt;
+        H.cpre = v2runs <= 1024u ? d_cpre : nullptr; H.rt = d_rt;
         H.dc_block = c.dc_block; H.beta = c.dc_block ? (double)c.dc.beta : 0.0;
-        if ((r = run64_v2_launch(H, s, timer))) return r;
-        p->cur ^= 1;
-        p->frames_done += nf;
-        if (c.mix) {
-            if ((r = launch_mix((const float *)p->d_premix, (float *)call.d_out, c.C, 2 * nf, s))) return r;
-        }
-        return 0;
+        return run64_v2_launch(H, s, timer);
     }
     SmallArgs SA{};
     TileArgs &A = SA.t;
-    A = p->proto;
+    A = proto;
     A.x = call.d_in;
-    A.out = c.mix ? p->d_premix : call.d_out;
-    A.yhist_in = p->d_yhist[p->cur]; A.yhist_out = p->d_yhist[p->cur ^ 1];
-    A.vend_in = p->d_vend[p->cur];   A.vend_out = p->d_vend[p->cur ^ 1];
-    A.rp_in = p->d_rp[p->cur];       A.rp_out = p->d_rp[p->cur ^ 1];
+    A.out = out;
+    A.yhist_in = d_yhist[cur]; A.yhist_out = d_yhist[cur ^ 1];
+    A.vend_in = d_vend[cur];   A.vend_out = d_vend[cur ^ 1];
+    A.rp_in = d_rp[cur];       A.rp_out = d_rp[cur ^ 1];
     A.nf = nf; A.nb = (nf + TS - 1) / TS; A.out_stride = nf; A.out_t0 = 0;
-    A.parity0 = (uint32_t)(p->frames_done & 1);
-    SA.yfirst = p->d_yfirst; SA.ylast_run = p->d_ylast;
+    A.parity0 = (uint32_t)(frames_done & 1);
+    SA.yfirst = d_yfirst; SA.ylast_run = d_ylast;
     // one run per resident workgroup slot, at least 8 tiles per run once the chunk is large enough
-    SA.S = (A.nb + p->resident_wgs - 1) / p->resident_wgs;
+    SA.S = (A.nb + resident_wgs - 1) / resident_wgs;
     if (SA.S < 8) SA.S = A.nb >= 8 * 64 ? 8 : (A.nb + 63) / 64;
     if (SA.S < 1) SA.S = 1;
     SA.l2beta = c.dc_block ? (float)std::log2((double)c.dc.beta) : -1000.0f;
@@ -496,17 +464,10 @@ int small_process(SmallPlan *p, const FusedCall &call, hipStream_t s, KernelTime
     else hipLaunchKernelGGL(k_run64<false>, dim3(nruns), dim3(256), 0, s, SA);
     if (timer && (r = timer->end(s))) return r;
     if (c.fm && nruns > 1)
-        hipLaunchKernelGGL(k_run64_fixup, dim3(nruns - 1), dim3(64), 0, s, p->d_yfirst, p->d_ylast, (float *)A.out, nf,
+        hipLaunchKernelGGL(k_run64_fixup, dim3(nruns - 1), dim3(64), 0, s, d_yfirst, d_ylast, (float *)A.out, nf,
                            SA.S * TS, c.c0, c.C, c.fm_ref);
     CSDR_HIP(hipGetLastError());
-    p->cur ^= 1;
-    p->frames_done += nf;
-    if (c.mix) {
-        if ((r = launch_mix((const float *)p->d_premix, (float *)call.d_out, c.C, c.fm ? nf : 2 * nf, s))) return r;
-    }
     return 0;
 }
-
-const char *small_name(const SmallPlan *p) { return p->cfg.fm ? "k_run64<FM>" : (p->v2_last ? "k_run64v2" : "k_run64<CF32>"); }
 
 }  // namespace csdr

@@ -453,10 +453,8 @@ __global__ __launch_bounds__(256) void k_shard_gather1024(const float *__restric
     for (size_t i = threadIdx.x; i < (size_t)nf * w; i += 256) dst[dn + i] = src[so + i];
 }
 
-struct BigPlan {
-    FusedConfig cfg;
-    uint32_t cus = 256;
-    uint64_t frames_done = 0;
+struct BigPlan : ChainPlan {
+    using ChainPlan::ChainPlan;
     float *d_taps = nullptr;
     float4 *d_taps_t = nullptr, *d_taps_q = nullptr;
     bool v3_ok = false, v3_last = false;      // k_run1024v3 (FM, whole band) selected; used by the last call
@@ -467,74 +465,68 @@ struct BigPlan {
     float2 *d_uhist[2] = {nullptr, nullptr}, *d_vend[2] = {nullptr, nullptr}, *d_rp[2] = {nullptr, nullptr};
     float2 *d_scratch = nullptr;     // yfirst | ylast
     void *d_full = nullptr;          // interleaved shard, calls k_run1024v2 does not take: whole-band result [1024][max_nf] (allocated on first use)
-    void *d_premix = nullptr;
     float2 *d_cpre = nullptr, *d_side = nullptr, *d_rt = nullptr;       // k_run1024v3 without warm-up windows (Run1024v2Host::cpre / side / rt)
-    int cur = 0;
+
+    int init();
+    const char *name() const override
+    {
+        if (v3_last) return cfg.fm ? "k_run1024v3<FM>" : "k_run1024v3<CF32>";
+        if (s1_last) return cfg.fm ? (cfg.G == 8 ? "k_shard1024<FM>/G8" : "k_shard1024<FM>/G4") : (cfg.G == 8 ? "k_shard1024<CF32>/G8" : "k_shard1024<CF32>/G4");
+        if (v2_last) return cfg.G == 8 ? "k_run1024v2<FM>/G8" : cfg.G == 4 ? "k_run1024v2<FM>/G4" : cfg.G == 2 ? "k_run1024v2<FM>/G2" : "k_run1024v2<FM>";
+        return cfg.fm ? "k_run1024<FM>" : "k_run1024<CF32>";
+    }
+    // CF32 output through k_run1024v3<CF32> (whole band) or k_shard1024<CF32, G> (interleaved shard)
+    bool tile_major_ok(uint32_t nf) const override
+    {
+        if (s1_ok) return !cfg.fm && !cfg.mix && nf % 16u == 0 && shard1024_runs(nf, false, cfg.G, cus) != 0;
+        return v3_ok && !cfg.fm && !cfg.mix && nf % 16u == 0 && (uint64_t)nf * 8192u < (1ull << 31) && run1024_v3_runs(nf, false, cus) != 0;
+    }
+    int reset_state(hipStream_t s) override;
+    int run(const FusedCall &call, void *out, hipStream_t s, KernelTimer *timer) override;
 };
 
-bool big_supported(uint32_t M, uint32_t p) { return M == (uint32_t)PM && p == (uint32_t)PP; }
+bool plan1024_supported(uint32_t M, uint32_t p) { return M == (uint32_t)PM && p == (uint32_t)PP && !diag_env("CSDR_NO_RUN1024"); }
+int plan1024_create(const FusedConfig &cfg, ChainPlan **out) { return make_plan<BigPlan>(cfg, out); }
 
-void big_destroy(BigPlan *p)
+int BigPlan::init()
 {
-    if (!p) return;
-    void *ptrs[] = {p->d_taps, p->d_taps_t, p->d_taps_q, p->d_tw, p->d_wpre, p->d_uhist[0], p->d_uhist[1], p->d_vend[0], p->d_vend[1], p->d_rp[0], p->d_rp[1],
-                    p->d_scratch, p->d_premix, p->d_full, p->d_cpre, p->d_side, p->d_rt};
-    for (void *q : ptrs) if (q) (void)hipFree(q);
-    delete p;
-}
-
-int big_create(const FusedConfig &cfg, BigPlan **out)
-{
-    BigPlan *p = new BigPlan();
-    p->cfg = cfg;
-    auto fail = [&](int r) { big_destroy(p); return r; };
-    {
-        int dev = 0, cus = 256;
-        (void)hipGetDevice(&dev);
-        (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-        p->cus = (uint32_t)cus;
-    }
-#define ALLOC(ptr, bytes) do { hipError_t e = hipMalloc((void **)&(ptr), (bytes) ? (bytes) : 1); if (e != hipSuccess) return fail(hip_fail(e, "hipMalloc", __FILE__, __LINE__)); } while (0)
-    ALLOC(p->d_taps, sizeof(float) * PM * PP);
-    ALLOC(p->d_taps_t, sizeof(float) * PM * 16);
-    ALLOC(p->d_taps_q, sizeof(float) * PM * 18);
-    ALLOC(p->d_tw, sizeof(float2) * PM);
-    ALLOC(p->d_wpre, sizeof(float2) * 2 * PM);
+    int rc;     // (r: a branch below)
+    if ((rc = mem.alloc(&d_taps, sizeof(float) * PM * PP))) return rc;
+    if ((rc = mem.alloc(&d_taps_t, sizeof(float) * PM * 16))) return rc;
+    if ((rc = mem.alloc(&d_taps_q, sizeof(float) * PM * 18))) return rc;
+    if ((rc = mem.alloc(&d_tw, sizeof(float2) * PM))) return rc;
+    if ((rc = mem.alloc(&d_wpre, sizeof(float2) * 2 * PM))) return rc;
     for (int i = 0; i < 2; i++) {
-        ALLOC(p->d_uhist[i], sizeof(float2) * 13 * PM);
-        ALLOC(p->d_vend[i], sizeof(float2));
-        ALLOC(p->d_rp[i], sizeof(float2) * (cfg.G > 1 ? (uint32_t)PM : cfg.C));     // interleaved shard: indexed by the primed channel k'
+        if ((rc = mem.alloc(&d_uhist[i], sizeof(float2) * 13 * PM))) return rc;
+        if ((rc = mem.alloc(&d_vend[i], sizeof(float2)))) return rc;
+        if ((rc = mem.alloc(&d_rp[i], sizeof(float2) * (cfg.G > 1 ? (uint32_t)PM : cfg.C)))) return rc;     // interleaved shard: indexed by the primed channel k'
     }
-    ALLOC(p->d_scratch, sizeof(float2) * 2 * (size_t)p->cus * PM);
-    if (cfg.mix) ALLOC(p->d_premix, (size_t)cfg.C * cfg.max_nf * (cfg.fm ? 4 : 8));
-#undef ALLOC
-    CSDR_HIP(hipMemcpy(p->d_taps, cfg.taps, sizeof(float) * PM * PP, hipMemcpyHostToDevice));
+    if ((rc = mem.alloc(&d_scratch, sizeof(float2) * 2 * (size_t)cus * PM))) return rc;
+    if (cfg.mix && (rc = mem.alloc(&d_premix, (size_t)cfg.C * cfg.max_nf * (cfg.fm ? 4 : 8)))) return rc;
+    CSDR_HIP(hipMemcpy(d_taps, cfg.taps, sizeof(float) * PM * PP, hipMemcpyHostToDevice));
     {
         std::vector<float> tt((size_t)PM * 16, 0.f);
         for (int j = 0; j < PM; j++) for (int n = 0; n < PP; n++) tt[(size_t)j * 16 + n] = cfg.taps[(PM - 1 - j) + n * PM];
-        CSDR_HIP(hipMemcpy(p->d_taps_t, tt.data(), sizeof(float) * tt.size(), hipMemcpyHostToDevice));
+        CSDR_HIP(hipMemcpy(d_taps_t, tt.data(), sizeof(float) * tt.size(), hipMemcpyHostToDevice));
     }
-    std::vector<float2> tw(PM), wpre(2 * PM);
+    std::vector<float2> tw(PM), wpre = premix_table();
     for (int i = 0; i < PM; i++) {
         const double a = -2.0 * 3.14159265358979323846 * (double)i / (double)PM;
         tw[i] = make_float2((float)std::cos(a), (float)std::sin(a));
     }
-    for (uint32_t i = 0; i < 2 * (uint32_t)PM; i++) {           // the NCO phase sequence has period 2M for a power-of-two M
-        float c, sn;
-        nco_phasor(i * cfg.d_theta, &c, &sn);
-        wpre[i] = make_float2(c, -sn);
-        if (cfg.G > 1) {
-            // interleaved shard g = c0 of G: a shift of the whole spectrum by g channels, W1024^(r g) on branch r, rides on the branch's
-            // pre-mix phasor for free (the FIR is linear): every kernel of the plan then sees the PRIMED spectrum Y'[k'] = Y[k' + g],
-            // of which the shard owns the rows k' = 0 mod G
+    if (cfg.G > 1) {
+        // interleaved shard g = c0 of G: a shift of the whole spectrum by g channels, W1024^(r g) on branch r, rides on the branch's
+        // pre-mix phasor for free (the FIR is linear): every kernel of the plan then sees the PRIMED spectrum Y'[k'] = Y[k' + g],
+        // of which the shard owns the rows k' = 0 mod G
+        for (uint32_t i = 0; i < 2 * (uint32_t)PM; i++) {
             const int n = (int)(((i & (uint32_t)(PM - 1)) * cfg.c0) & (uint32_t)(PM - 1));
             const double a = -2.0 * 3.14159265358979323846 * (double)n / (double)PM;
             const double wr = std::cos(a), wi = std::sin(a), xr = wpre[i].x, xi = wpre[i].y;
             wpre[i] = make_float2((float)(xr * wr - xi * wi), (float)(xr * wi + xi * wr));
         }
     }
-    CSDR_HIP(hipMemcpy(p->d_tw, tw.data(), sizeof(float2) * tw.size(), hipMemcpyHostToDevice));
-    CSDR_HIP(hipMemcpy(p->d_wpre, wpre.data(), sizeof(float2) * wpre.size(), hipMemcpyHostToDevice));
+    CSDR_HIP(hipMemcpy(d_tw, tw.data(), sizeof(float2) * tw.size(), hipMemcpyHostToDevice));
+    CSDR_HIP(hipMemcpy(d_wpre, wpre.data(), sizeof(float2) * wpre.size(), hipMemcpyHostToDevice));
     {
         // k_run1024v2's table: [q][piece][j] float4 = floats 4 piece .. 4 piece + 3 of the row (14 taps, even-frame phasor) of
         // branch 256 q + j; behind it [q][j] float2: the odd-frame phasor (the f32 phases of the two are not exact negatives)
@@ -547,134 +539,105 @@ int big_create(const FusedConfig &cfg, BigPlan **out)
             for (int e = 0; e < 16; e++) tq[((size_t)(q * 4 + (e >> 2)) * 256 + j) * 4 + (e & 3)] = row[e];
             tq[(size_t)PM * 16 + 2 * (size_t)r] = wpre[PM + r].x; tq[(size_t)PM * 16 + 2 * (size_t)r + 1] = wpre[PM + r].y;
         }
-        CSDR_HIP(hipMemcpy(p->d_taps_q, tq.data(), sizeof(float) * tq.size(), hipMemcpyHostToDevice));
+        CSDR_HIP(hipMemcpy(d_taps_q, tq.data(), sizeof(float) * tq.size(), hipMemcpyHostToDevice));
         // k_run1024v2: the interleaved shards only (FM output); its whole-band instantiations are no longer built -- k_run1024v3 takes every
         // whole-band call of whole 4-frame tiles (a call that ends inside a 128-byte line stores the front part of it)
-        p->v2_ok = false;
+        v2_ok = false;
         // whole band, calls of whole 4-frame tiles: k_run1024v3 (CSDR_RUN1024_V3=0: k_run1024 for the comparison)
-        p->v3_ok = cfg.c0 == 0 && cfg.C == (uint32_t)PM && cfg.G == 1 && !diag_env("CSDR_RUN1024_V1") && !(diag_env("CSDR_RUN1024_V3") && atoi(diag_env("CSDR_RUN1024_V3")) == 0);
-        if (cfg.G > 1) p->v2_ok = cfg.fm && !diag_env("CSDR_RUN1024_V1");       // k_run1024v2<FM, G>; CF32 shards: whole band + row gather (below)
+        v3_ok = cfg.c0 == 0 && cfg.C == (uint32_t)PM && cfg.G == 1 && !diag_env("CSDR_RUN1024_V1") && !(diag_env("CSDR_RUN1024_V3") && atoi(diag_env("CSDR_RUN1024_V3")) == 0);
+        if (cfg.G > 1) v2_ok = cfg.fm && !diag_env("CSDR_RUN1024_V1");       // k_run1024v2<FM, G>; CF32 shards: whole band + row gather (below)
         // until the first call: the kernel a call of max_nf frames would take (csdr_chain_path names it)
-        p->s1_ok = (cfg.G == 4 || cfg.G == 8) && !diag_env("CSDR_RUN1024_V1");      // k_shard1024<FM | CF32, G>: every run-sized call of whole tiles
-        p->s1_last = p->s1_ok && shard1024_runs(cfg.max_nf, cfg.fm, cfg.G, p->cus) != 0;
-        p->v2_last = !p->s1_last && p->v2_ok && (cfg.max_nf & 3u) == 0 && run1024_v2_runs(cfg.max_nf, p->cus) != 0;
-        p->v3_last = p->v3_ok && run1024_v3_runs(cfg.max_nf, cfg.fm, p->cus) != 0;
-        if (p->v3_last) p->v2_last = false;
+        s1_ok = (cfg.G == 4 || cfg.G == 8) && !diag_env("CSDR_RUN1024_V1");      // k_shard1024<FM | CF32, G>: every run-sized call of whole tiles
+        s1_last = s1_ok && shard1024_runs(cfg.max_nf, cfg.fm, cfg.G, cus) != 0;
+        v2_last = !s1_last && v2_ok && (cfg.max_nf & 3u) == 0 && run1024_v2_runs(cfg.max_nf, cus) != 0;
+        v3_last = v3_ok && run1024_v3_runs(cfg.max_nf, cfg.fm, cus) != 0;
+        if (v3_last) v2_last = false;
     }
-    if (p->s1_ok) {
+    if (s1_ok) {
         // k_shard1024 without warm-up windows (as k_run1024v3 below): the state hand-over between the runs, the side copies of the ONE owned channel
         // among the four around DC (510 .. 513; primed k' = k - g, row k' / G -- none for the shards 2 .. 5 of 8), and the chain's response to a
         // unit DC state there (computed on the plan's phasor table, which carries the shard's shift: the primed spectrum)
-        p->s1_mfix = -1;
+        s1_mfix = -1;
         uint32_t kp = 0;
-        for (uint32_t k = 510; k <= 513; k++) if ((k + (uint32_t)PM - cfg.c0) % cfg.G == 0) { kp = (k + (uint32_t)PM - cfg.c0) % (uint32_t)PM; p->s1_mfix = (int)(kp / cfg.G); }
-        hipError_t e1 = hipMalloc((void **)&p->d_cpre, sizeof(float2) * (p->cus + 2)), e2 = hipMalloc((void **)&p->d_side, sizeof(float2) * (size_t)(p->cus + 1) * RUN1024_DCFIX_F);
-        if (e1 != hipSuccess || e2 != hipSuccess) return fail(hip_fail(e1 != hipSuccess ? e1 : e2, "hipMalloc", __FILE__, __LINE__));
-        CSDR_HIP(hipMemset(p->d_cpre, 0, sizeof(float2) * (p->cus + 2)));
+        for (uint32_t k = 510; k <= 513; k++) if ((k + (uint32_t)PM - cfg.c0) % cfg.G == 0) { kp = (k + (uint32_t)PM - cfg.c0) % (uint32_t)PM; s1_mfix = (int)(kp / cfg.G); }
+        if ((rc = mem.alloc(&d_cpre, sizeof(float2) * (cus + 2))) || (rc = mem.alloc(&d_side, sizeof(float2) * (size_t)(cus + 1) * RUN1024_DCFIX_F))) return rc;
+        CSDR_HIP(hipMemset(d_cpre, 0, sizeof(float2) * (cus + 2)));
         if (cfg.dc_block && dc_window_ok(cfg.dc, 12 * 4096.0) && !(diag_env("CSDR_NOWU") && atoi(diag_env("CSDR_NOWU")) == 0)) {   // error beta^(12 x 4096)
-            hipError_t e3 = hipMalloc((void **)&p->d_rt, sizeof(float2) * 2 * RUN1024_DCFIX_F * 4);
-            if (e3 != hipSuccess) return fail(hip_fail(e3, "hipMalloc", __FILE__, __LINE__));
+            if ((rc = mem.alloc(&d_rt, sizeof(float2) * 2 * RUN1024_DCFIX_F * 4))) return rc;
             std::vector<float2> rt((size_t)2 * RUN1024_DCFIX_F * 4, make_float2(0.f, 0.f));
-            if (p->s1_mfix >= 0) dc_state_response(cfg, wpre.data(), 15u, (uint32_t)RUN1024_DCFIX_F, kp, rt.data());      // (channel 0 of the four is the owned one)
-            CSDR_HIP(hipMemcpy(p->d_rt, rt.data(), sizeof(float2) * rt.size(), hipMemcpyHostToDevice));
+            if (s1_mfix >= 0) dc_state_response(cfg, wpre.data(), 15u, (uint32_t)RUN1024_DCFIX_F, kp, rt.data());      // (channel 0 of the four is the owned one)
+            CSDR_HIP(hipMemcpy(d_rt, rt.data(), sizeof(float2) * rt.size(), hipMemcpyHostToDevice));
         }
     }
-    if (p->v3_ok) {
+    if (v3_ok) {
         // k_run1024v3's state hand-over and the side copies of the four channels around DC (510..513): the kernel always writes them (a few
         // hundred bytes per run); launches without warm-up windows (dc_block, not CSDR_NOWU=0) also get the chain's response to a unit DC state
         // at those channels, frames 15 .. 47 behind a cold start (= frame -1 .. 31 of the run)
-        hipError_t e1 = hipMalloc((void **)&p->d_cpre, sizeof(float2) * (p->cus + 2)), e2 = hipMalloc((void **)&p->d_side, sizeof(float2) * (size_t)(p->cus + 1) * 4 * RUN1024_DCFIX_F);
-        if (e1 != hipSuccess || e2 != hipSuccess) return fail(hip_fail(e1 != hipSuccess ? e1 : e2, "hipMalloc", __FILE__, __LINE__));
-        CSDR_HIP(hipMemset(p->d_cpre, 0, sizeof(float2) * (p->cus + 2)));
+        if ((rc = mem.alloc(&d_cpre, sizeof(float2) * (cus + 2))) || (rc = mem.alloc(&d_side, sizeof(float2) * (size_t)(cus + 1) * 4 * RUN1024_DCFIX_F))) return rc;
+        CSDR_HIP(hipMemset(d_cpre, 0, sizeof(float2) * (cus + 2)));
     }
-    if (p->v3_ok && cfg.dc_block && dc_window_ok(cfg.dc, 35 * 1024.0) && !(diag_env("CSDR_NOWU") && atoi(diag_env("CSDR_NOWU")) == 0)) {   // halo + 32-frame dcfix
-        hipError_t e3 = hipMalloc((void **)&p->d_rt, sizeof(float2) * 2 * RUN1024_DCFIX_F * 4);
-        if (e3 != hipSuccess) return fail(hip_fail(e3, "hipMalloc", __FILE__, __LINE__));
+    if (v3_ok && cfg.dc_block && dc_window_ok(cfg.dc, 35 * 1024.0) && !(diag_env("CSDR_NOWU") && atoi(diag_env("CSDR_NOWU")) == 0)) {   // halo + 32-frame dcfix
+        if ((rc = mem.alloc(&d_rt, sizeof(float2) * 2 * RUN1024_DCFIX_F * 4))) return rc;
         std::vector<float2> rt((size_t)2 * RUN1024_DCFIX_F * 4);
         dc_state_response(cfg, wpre.data(), 15u, (uint32_t)RUN1024_DCFIX_F, 510u, rt.data());
-        CSDR_HIP(hipMemcpy(p->d_rt, rt.data(), sizeof(float2) * rt.size(), hipMemcpyHostToDevice));
+        CSDR_HIP(hipMemcpy(d_rt, rt.data(), sizeof(float2) * rt.size(), hipMemcpyHostToDevice));
     }
-    *out = p;
     return 0;
 }
 
-int big_reset(BigPlan *p, hipStream_t s)
+int BigPlan::reset_state(hipStream_t s)
 {
-    p->cur = 0; p->frames_done = 0;
     for (int i = 0; i < 2; i++) {
-        CSDR_HIP(hipMemsetAsync(p->d_uhist[i], 0, sizeof(float2) * 13 * PM, s));
-        CSDR_HIP(hipMemsetAsync(p->d_vend[i], 0, sizeof(float2), s));
-        CSDR_HIP(hipMemsetAsync(p->d_rp[i], 0, sizeof(float2) * (p->cfg.G > 1 ? (uint32_t)PM : p->cfg.C), s));
+        CSDR_HIP(hipMemsetAsync(d_uhist[i], 0, sizeof(float2) * 13 * PM, s));
+        CSDR_HIP(hipMemsetAsync(d_vend[i], 0, sizeof(float2), s));
+        CSDR_HIP(hipMemsetAsync(d_rp[i], 0, sizeof(float2) * (cfg.G > 1 ? (uint32_t)PM : cfg.C), s));
     }
     return 0;
 }
 
-void big_seek(BigPlan *p, uint64_t frames) { p->frames_done = frames; }
-const char *big_name(const BigPlan *p)
+int BigPlan::run(const FusedCall &call, void *out, hipStream_t s, KernelTimer *timer)
 {
-    if (p->v3_last) return p->cfg.fm ? "k_run1024v3<FM>" : "k_run1024v3<CF32>";
-    if (p->s1_last) return p->cfg.fm ? (p->cfg.G == 8 ? "k_shard1024<FM>/G8" : "k_shard1024<FM>/G4") : (p->cfg.G == 8 ? "k_shard1024<CF32>/G8" : "k_shard1024<CF32>/G4");
-    if (p->v2_last) return p->cfg.G == 8 ? "k_run1024v2<FM>/G8" : p->cfg.G == 4 ? "k_run1024v2<FM>/G4" : p->cfg.G == 2 ? "k_run1024v2<FM>/G2" : "k_run1024v2<FM>";
-    return p->cfg.fm ? "k_run1024<FM>" : "k_run1024<CF32>";
-}
-
-bool big_tile_major_ok(const BigPlan *p, uint32_t nf)
-{
-    if (p && p->s1_ok) return !p->cfg.fm && !p->cfg.mix && nf % 16u == 0 && shard1024_runs(nf, false, p->cfg.G, p->cus) != 0;      // interleaved shard: k_shard1024<CF32, G>
-    return p && p->v3_ok && !p->cfg.fm && !p->cfg.mix && nf % 16u == 0 && (uint64_t)nf * 8192u < (1ull << 31) && run1024_v3_runs(nf, false, p->cus) != 0;
-}
-
-int big_process(BigPlan *p, const FusedCall &call, hipStream_t s, KernelTimer *timer)
-{
-    const FusedConfig &c = p->cfg;
+    const FusedConfig &c = cfg;
     const uint32_t nf = call.nf;
-    if (!nf) return 0;
     int r;
-    const uint32_t s1runs = p->s1_ok ? shard1024_runs(nf, c.fm, c.G, p->cus) : 0;
-    p->s1_last = s1runs != 0;
-    const uint32_t v2runs = (!s1runs && p->v2_ok && (nf & 3u) == 0 && (uint64_t)nf * 8192u < (1ull << 31)) ? run1024_v2_runs(nf, p->cus) : 0;
-    p->v2_last = v2runs != 0;
-    if (call.tile_major && !big_tile_major_ok(p, nf)) { set_error("big_process: tile-major output asked for a call k_run1024v3<CF32> does not take"); return CSDR_ERR_INVALID; }
-    const uint32_t v3runs = (p->v3_ok && (uint64_t)nf * 8192u < (1ull << 31)) ? run1024_v3_runs(nf, c.fm, p->cus) : 0;
-    p->v3_last = v3runs != 0;
-    if (v3runs) p->v2_last = false;
+    const uint32_t s1runs = s1_ok ? shard1024_runs(nf, c.fm, c.G, cus) : 0;
+    s1_last = s1runs != 0;
+    const uint32_t v2runs = (!s1runs && v2_ok && (nf & 3u) == 0 && (uint64_t)nf * 8192u < (1ull << 31)) ? run1024_v2_runs(nf, cus) : 0;
+    v2_last = v2runs != 0;
+    const uint32_t v3runs = (v3_ok && (uint64_t)nf * 8192u < (1ull << 31)) ? run1024_v3_runs(nf, c.fm, cus) : 0;
+    v3_last = v3runs != 0;
+    if (v3runs) v2_last = false;
     if (v2runs || v3runs || s1runs) {
         Run1024v2Host H{};
-        H.x = call.d_in; H.out = c.mix ? p->d_premix : call.d_out; H.taps_q = p->d_taps_q; H.tw = p->d_tw;
-        H.uhist_in = p->d_uhist[p->cur]; H.uhist_out = p->d_uhist[p->cur ^ 1];
-        H.vend_in = p->d_vend[p->cur]; H.vend_out = p->d_vend[p->cur ^ 1];
-        H.rp_in = p->d_rp[p->cur]; H.rp_out = p->d_rp[p->cur ^ 1];
-        H.nf = nf; H.nruns = v2runs; H.parity0 = (uint32_t)(p->frames_done & 1);
+        H.x = call.d_in; H.out = out; H.taps_q = d_taps_q; H.tw = d_tw;
+        H.uhist_in = d_uhist[cur]; H.uhist_out = d_uhist[cur ^ 1];
+        H.vend_in = d_vend[cur]; H.vend_out = d_vend[cur ^ 1];
+        H.rp_in = d_rp[cur]; H.rp_out = d_rp[cur ^ 1];
+        H.nf = nf; H.nruns = v2runs; H.parity0 = (uint32_t)(frames_done & 1);
         H.G = c.G; H.g = c.G > 1 ? c.c0 : 0u;
         H.tile_major = call.tile_major && (v3runs || s1runs) && !c.fm;
         H.dc_block = c.dc_block; H.beta = c.dc_block ? (double)c.dc.beta : 0.0; H.fm_ref = c.fm_ref;
-        if (v3runs) { H.cpre = p->d_cpre; H.side = p->d_side; H.rt = v3runs <= p->cus ? p->d_rt : nullptr; }
-        if (s1runs) { H.cpre = p->d_cpre; H.side = p->d_side; H.rt = p->d_rt; H.mfix = p->s1_mfix; }
-        if (s1runs) { if ((r = shard1024_launch(H, c.fm, s1runs, s, timer))) return r; }
-        else if (v3runs) { if ((r = run1024_v3_launch(H, c.fm, v3runs, s, timer))) return r; }
-        else if ((r = run1024_v2_launch(H, c.fm, s, timer))) return r;
-        p->cur ^= 1;
-        p->frames_done += nf;
-        if (c.mix) {
-            if ((r = launch_mix((const float *)p->d_premix, (float *)call.d_out, c.C, c.fm ? nf : 2 * nf, s))) return r;
-        }
-        return 0;
+        if (v3runs) { H.cpre = d_cpre; H.side = d_side; H.rt = v3runs <= cus ? d_rt : nullptr; }
+        if (s1runs) { H.cpre = d_cpre; H.side = d_side; H.rt = d_rt; H.mfix = s1_mfix; }
+        if (s1runs) return shard1024_launch(H, c.fm, s1runs, s, timer);
+        if (v3runs) return run1024_v3_launch(H, c.fm, v3runs, s, timer);
+        return run1024_v2_launch(H, c.fm, s, timer);
     }
     Pfb1024Args A{};
-    A.u = call.d_in; A.taps = p->d_taps; A.taps_t = p->d_taps_t; A.tw = p->d_tw; A.wpre = p->d_wpre;
-    A.out = c.mix ? p->d_premix : call.d_out;
+    A.u = call.d_in; A.taps = d_taps; A.taps_t = d_taps_t; A.tw = d_tw; A.wpre = d_wpre;
+    A.out = out;
     const bool shard = c.G > 1;
     if (shard) {
         // an interleaved shard's call that k_run1024v2<FM, G> does not take (CF32 output, ragged or short call): the whole primed
         // band through k_run1024 into scratch, then the owned rows k1' = 0 mod G are gathered into the shard's plane
-        if (!p->d_full) { hipError_t e = hipMalloc(&p->d_full, (size_t)PM * c.max_nf * (c.fm ? 4 : 8)); if (e != hipSuccess) return hip_fail(e, "hipMalloc", __FILE__, __LINE__); }
-        A.out = p->d_full;
+        if (!d_full && (r = mem.alloc(&d_full, (size_t)PM * c.max_nf * (c.fm ? 4 : 8)))) return r;
+        A.out = d_full;
     }
-    A.rp_in = p->d_rp[p->cur]; A.rp_out = p->d_rp[p->cur ^ 1];
-    A.vend_in = p->d_vend[p->cur]; A.vend_out = p->d_vend[p->cur ^ 1];
-    A.uhist_in = p->d_uhist[p->cur]; A.uhist_out = p->d_uhist[p->cur ^ 1];
+    A.rp_in = d_rp[cur]; A.rp_out = d_rp[cur ^ 1];
+    A.vend_in = d_vend[cur]; A.vend_out = d_vend[cur ^ 1];
+    A.uhist_in = d_uhist[cur]; A.uhist_out = d_uhist[cur ^ 1];
     A.nf = nf; A.nb = (nf + PT - 1) / PT; A.c0 = shard ? 0u : c.c0; A.C = shard ? (uint32_t)PM : c.C; A.ref = c.fm_ref;
-    A.parity0 = (uint32_t)(p->frames_done & 1);
+    A.parity0 = (uint32_t)(frames_done & 1);
     const double beta = c.dc_block ? (double)c.dc.beta : 0.0;
     A.alpha = c.dc_block ? (float)(1.0 - beta) : 0.0f;
     A.l2beta = c.dc_block ? (float)std::log2(beta) : -1000.0f;
@@ -682,22 +645,17 @@ int big_process(BigPlan *p, const FusedCall &call, hipStream_t s, KernelTimer *t
     A.dm = (float)std::pow(beta, 1024.0);
     A.pk = phase_consts(c.fm_ref);
     // one run per CU, at least 8 tiles per run (a run >= 1 spends 3 read-only + 2 halo tiles on its start state)
-    uint32_t nruns = p->cus;
+    uint32_t nruns = cus;
     if (nruns > A.nb / 8) nruns = A.nb / 8;
     if (nruns < 1) nruns = 1;
-    A.nruns = nruns; A.yfirst = p->d_scratch; A.ylast = p->d_scratch + (size_t)nruns * PM;
+    A.nruns = nruns; A.yfirst = d_scratch; A.ylast = d_scratch + (size_t)nruns * PM;
     if (timer && (r = timer->begin(s))) return r;
     if (c.fm) hipLaunchKernelGGL((k_pfb1024<true, true>), dim3(nruns), dim3(1024), 0, s, A);
     else hipLaunchKernelGGL((k_pfb1024<false, true>), dim3(nruns), dim3(1024), 0, s, A);
     if (timer && (r = timer->end(s))) return r;
     if (c.fm && nruns > 1) hipLaunchKernelGGL(k_pfb1024_fixup, dim3(nruns - 1), dim3(1024), 0, s, A);
-    if (shard) hipLaunchKernelGGL(k_shard_gather1024, dim3(c.C), dim3(256), 0, s, (const float *)p->d_full, (float *)(c.mix ? p->d_premix : call.d_out), c.G, nf, c.fm ? 1u : 2u);
+    if (shard) hipLaunchKernelGGL(k_shard_gather1024, dim3(c.C), dim3(256), 0, s, (const float *)d_full, (float *)out, c.G, nf, c.fm ? 1u : 2u);
     CSDR_HIP(hipGetLastError());
-    p->cur ^= 1;
-    p->frames_done += nf;
-    if (c.mix) {
-        if ((r = launch_mix((const float *)p->d_premix, (float *)call.d_out, c.C, c.fm ? nf : 2 * nf, s))) return r;
-    }
     return 0;
 }
 

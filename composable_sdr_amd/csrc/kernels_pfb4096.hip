@@ -409,75 +409,52 @@ __global__ __launch_bounds__(256) void k_mix4096_finish(const float *__restrict_
 }  // namespace
 
 // ---------------------------------------------------------------------------------------------------------------------------------
-struct HugePlan {
-    FusedConfig cfg;
-    uint32_t cus = 256;
-    uint64_t frames_done = 0;
+struct HugePlan : ChainPlan {
+    using ChainPlan::ChainPlan;
     float *d_taps = nullptr;
     float2 *d_wpre = nullptr, *d_tw4 = nullptr, *d_tw = nullptr, *d_z = nullptr;
     float4 *d_tail[2] = {nullptr, nullptr};
     float *d_part = nullptr;
-    int cur = 0;
-    std::string name;
+    std::string kernel;
+
+    int init();
+    const char *name() const override { return kernel.c_str(); }
+    // CF32 output, whole 16-frame blocks, no mix inside the plan
+    bool tile_major_ok(uint32_t nf) const override { return !cfg.fm && !cfg.mix && nf && (nf & 15u) == 0; }
+    int reset_state(hipStream_t s) override
+    {
+        CSDR_HIP(hipMemsetAsync(d_tail[0], 0, sizeof(float4) * 2048 * H_COLD, s));
+        return 0;
+    }
+    int run(const FusedCall &call, void *out, hipStream_t s, KernelTimer *timer) override;
 };
 
-bool huge_supported(uint32_t M, uint32_t p) { return M == (uint32_t)H_M && p == (uint32_t)P; }
+bool plan4096_supported(uint32_t M, uint32_t p) { return M == (uint32_t)H_M && p == (uint32_t)P && !diag_env("CSDR_NO_RUN4096"); }
+int plan4096_create(const FusedConfig &cfg, ChainPlan **out) { return make_plan<HugePlan>(cfg, out); }
 
-void huge_destroy(HugePlan *p)
+int HugePlan::init()
 {
-    if (!p) return;
-    void *ptrs[] = {p->d_taps, p->d_wpre, p->d_tw4, p->d_tw, p->d_z, p->d_tail[0], p->d_tail[1], p->d_part};
-    for (void *q : ptrs) if (q) (void)hipFree(q);
-    delete p;
-}
-
-int huge_reset(HugePlan *p, hipStream_t s)
-{
-    p->frames_done = 0; p->cur = 0;
-    CSDR_HIP(hipMemsetAsync(p->d_tail[0], 0, sizeof(float4) * 2048 * H_COLD, s));
-    return 0;
-}
-void huge_seek(HugePlan *p, uint64_t frames) { p->frames_done = frames; }
-const char *huge_name(const HugePlan *p) { return p->name.c_str(); }
-
-int huge_create(const FusedConfig &cfg, HugePlan **out)
-{
-    HugePlan *p = new HugePlan();
-    p->cfg = cfg;
-    auto fail = [&](int r) { huge_destroy(p); return r; };
-    {
-        int dev = 0, cus = 256;
-        (void)hipGetDevice(&dev);
-        (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-        p->cus = (uint32_t)cus;
-    }
-#define ALLOC(ptr, bytes) do { hipError_t e = hipMalloc((void **)&(ptr), (bytes) ? (bytes) : 1); if (e != hipSuccess) return fail(hip_fail(e, "hipMalloc", __FILE__, __LINE__)); } while (0)
-    ALLOC(p->d_taps, sizeof(float) * H_M * P);
-    ALLOC(p->d_wpre, sizeof(float2) * 2 * H_M);
-    ALLOC(p->d_tw4, sizeof(float2) * 3 * 1024);
-    ALLOC(p->d_tw, sizeof(float2) * 1024);
-    ALLOC(p->d_z, sizeof(float2) * ((size_t)cfg.max_nf + 1) * H_M);
-    ALLOC(p->d_tail[0], sizeof(float4) * 2048 * H_COLD);
-    ALLOC(p->d_tail[1], sizeof(float4) * 2048 * H_COLD);
-    if (cfg.mix) ALLOC(p->d_part, sizeof(float) * 64 * ((size_t)(cfg.max_nf + 15) / 16));
-#undef ALLOC
-    CSDR_HIP(hipMemcpy(p->d_taps, cfg.taps, sizeof(float) * H_M * P, hipMemcpyHostToDevice));
-    std::vector<float2> wpre(2 * H_M), tw4(3 * 1024), tw(1024);
-    for (uint32_t i = 0; i < 2u * H_M; i++) {           // the NCO phase sequence has period 2M for a power-of-two M (as every fused plan)
-        float c, sn;
-        nco_phasor(i * cfg.d_theta, &c, &sn);
-        wpre[i] = make_float2(c, -sn);
-    }
+    int rc;     // (r: a radix-4 branch below)
+    if ((rc = mem.alloc(&d_taps, sizeof(float) * H_M * P))) return rc;
+    if ((rc = mem.alloc(&d_wpre, sizeof(float2) * 2 * H_M))) return rc;
+    if ((rc = mem.alloc(&d_tw4, sizeof(float2) * 3 * 1024))) return rc;
+    if ((rc = mem.alloc(&d_tw, sizeof(float2) * 1024))) return rc;
+    if ((rc = mem.alloc(&d_z, sizeof(float2) * ((size_t)cfg.max_nf + 1) * H_M))) return rc;
+    if ((rc = mem.alloc(&d_tail[0], sizeof(float4) * 2048 * H_COLD))) return rc;
+    if ((rc = mem.alloc(&d_tail[1], sizeof(float4) * 2048 * H_COLD))) return rc;
+    if (cfg.mix && (rc = mem.alloc(&d_part, sizeof(float) * 64 * ((size_t)(cfg.max_nf + 15) / 16)))) return rc;
+    CSDR_HIP(hipMemcpy(d_taps, cfg.taps, sizeof(float) * H_M * P, hipMemcpyHostToDevice));
+    const std::vector<float2> wpre = premix_table();
+    std::vector<float2> tw4(3 * 1024), tw(1024);
     const double tp = -2.0 * 3.14159265358979323846;
     for (int r = 1; r < 4; r++)
         for (int j1 = 0; j1 < 1024; j1++) tw4[(r - 1) * 1024 + j1] = make_float2((float)std::cos(tp * (double)(j1 * r) / 4096.0), (float)std::sin(tp * (double)(j1 * r) / 4096.0));
     for (int i = 0; i < 1024; i++) tw[i] = make_float2((float)std::cos(tp * (double)i / 1024.0), (float)std::sin(tp * (double)i / 1024.0));
-    CSDR_HIP(hipMemcpy(p->d_wpre, wpre.data(), sizeof(float2) * wpre.size(), hipMemcpyHostToDevice));
-    CSDR_HIP(hipMemcpy(p->d_tw4, tw4.data(), sizeof(float2) * tw4.size(), hipMemcpyHostToDevice));
-    CSDR_HIP(hipMemcpy(p->d_tw, tw.data(), sizeof(float2) * tw.size(), hipMemcpyHostToDevice));
-    CSDR_HIP(hipMemset(p->d_tail[0], 0, sizeof(float4) * 2048 * H_COLD));
-    p->name = cfg.mix ? "k_front4096+k_back4096<FM,mix>" : (cfg.fm ? "k_front4096+k_back4096<FM>" : "k_front4096+k_back4096<CF32>");
-    *out = p;
+    CSDR_HIP(hipMemcpy(d_wpre, wpre.data(), sizeof(float2) * wpre.size(), hipMemcpyHostToDevice));
+    CSDR_HIP(hipMemcpy(d_tw4, tw4.data(), sizeof(float2) * tw4.size(), hipMemcpyHostToDevice));
+    CSDR_HIP(hipMemcpy(d_tw, tw.data(), sizeof(float2) * tw.size(), hipMemcpyHostToDevice));
+    CSDR_HIP(hipMemset(d_tail[0], 0, sizeof(float4) * 2048 * H_COLD));
+    kernel = cfg.mix ? "k_front4096+k_back4096<FM,mix>" : (cfg.fm ? "k_front4096+k_back4096<FM>" : "k_front4096+k_back4096<CF32>");
     return 0;
 }
 
@@ -491,15 +468,15 @@ static uint32_t huge_runs(uint32_t nf, uint32_t cus)
     return nruns ? nruns : 1;
 }
 
-int huge_process(HugePlan *p, const FusedCall &call, hipStream_t s, KernelTimer *timer)
+int HugePlan::run(const FusedCall &call, void *out, hipStream_t s, KernelTimer *timer)
 {
-    const FusedConfig &c = p->cfg;
+    const FusedConfig &c = cfg;
     const uint32_t nf = call.nf;
-    if (!nf) return 0;
+    if (c.mix && !c.fm) { set_error("k_back4096: --mix without freqdem goes through the mix identity (capi route)"); return -1; }
     Front4096Args A{};
-    A.x = reinterpret_cast<const float4 *>(call.d_in); A.tail = p->d_tail[p->cur]; A.z = p->d_z;
-    A.taps = p->d_taps; A.wpre = p->d_wpre; A.tw4 = p->d_tw4;
-    A.nf = nf; A.nruns = huge_runs(nf, p->cus); A.parity0 = (uint32_t)(p->frames_done & 1u);
+    A.x = reinterpret_cast<const float4 *>(call.d_in); A.tail = d_tail[cur]; A.z = d_z;
+    A.taps = d_taps; A.wpre = d_wpre; A.tw4 = d_tw4;
+    A.nf = nf; A.nruns = huge_runs(nf, cus); A.parity0 = (uint32_t)(frames_done & 1u);
     const double beta = c.dc_block ? (double)c.dc.beta : 0.0;
     A.alpha = c.dc_block ? (float)(1.0 - beta) : 0.0f; A.beta = (float)beta; A.l2beta = c.dc_block ? (float)std::log2(beta) : -1000.0f;
     for (int i = 0; i < 16; i++) A.b16[i] = (float)std::pow(beta, 16.0 * i);
@@ -508,38 +485,32 @@ int huge_process(HugePlan *p, const FusedCall &call, hipStream_t s, KernelTimer 
     if (timer && (r = timer->begin(s))) return r;
     hipLaunchKernelGGL(k_front4096, dim3(4 * A.nruns), dim3(512), 0, s, A);
     Back4096Args Bk{};
-    Bk.z = p->d_z; Bk.tw = p->d_tw; Bk.nf = nf; Bk.out_stride = nf;
-    Bk.tile_major = (call.tile_major && !c.fm && !c.mix) ? 1u : 0u;
-    if (call.tile_major && (!Bk.tile_major || (nf & 15u))) { set_error("huge_process: tile-major output asked for a call k_back4096<CF32> does not take"); return -1; }
+    Bk.z = d_z; Bk.tw = d_tw; Bk.nf = nf; Bk.out_stride = nf;
+    Bk.tile_major = call.tile_major ? 1u : 0u;
     Bk.pk = phase_consts(1.0f); Bk.pk.hp *= c.fm_ref; Bk.pk.pi *= c.fm_ref; Bk.pk.ref = c.fm_ref;
     Bk.fm_ref = c.fm_ref; Bk.tiny = 1e-37f;
     const uint32_t nblk = (nf + 15) / 16;
     if (c.mix) {
-        if (!c.fm) { set_error("k_back4096: --mix without freqdem goes through the mix identity (capi route)"); return -1; }
-        Bk.out = p->d_part;
+        Bk.out = d_part;
         hipLaunchKernelGGL((k_back4096<2>), dim3(4 * nblk), dim3(1024), 0, s, Bk);
-        hipLaunchKernelGGL(k_mix4096_finish, dim3((nf + 255) / 256), dim3(256), 0, s, (const float *)p->d_part, (float *)call.d_out, nf);
+        hipLaunchKernelGGL(k_mix4096_finish, dim3((nf + 255) / 256), dim3(256), 0, s, (const float *)d_part, (float *)out, nf);
     } else {
-        Bk.out = call.d_out;
+        Bk.out = out;
         if (c.fm) hipLaunchKernelGGL((k_back4096<1>), dim3(4 * nblk), dim3(1024), 0, s, Bk);
         else hipLaunchKernelGGL((k_back4096<0>), dim3(4 * nblk), dim3(1024), 0, s, Bk);
     }
     if (timer && (r = timer->end(s))) return r;
     CSDR_HIP(hipGetLastError());
     // the call's last 19 raw frames for the next call's run 0 (older ones move up when the call is shorter than that)
-    float4 *nt = p->d_tail[p->cur ^ 1];
+    float4 *nt = d_tail[cur ^ 1];
     const size_t fb = sizeof(float4) * 2048;
     if (nf >= (uint32_t)H_COLD) {
         CSDR_HIP(hipMemcpyAsync(nt, reinterpret_cast<const char *>(call.d_in) + (size_t)(nf - H_COLD) * fb, fb * H_COLD, hipMemcpyDeviceToDevice, s));
     } else {
-        CSDR_HIP(hipMemcpyAsync(nt, reinterpret_cast<const char *>(p->d_tail[p->cur]) + (size_t)nf * fb, fb * (H_COLD - nf), hipMemcpyDeviceToDevice, s));
+        CSDR_HIP(hipMemcpyAsync(nt, reinterpret_cast<const char *>(d_tail[cur]) + (size_t)nf * fb, fb * (H_COLD - nf), hipMemcpyDeviceToDevice, s));
         CSDR_HIP(hipMemcpyAsync(reinterpret_cast<char *>(nt) + (size_t)(H_COLD - nf) * fb, call.d_in, fb * nf, hipMemcpyDeviceToDevice, s));
     }
-    p->cur ^= 1;
-    p->frames_done += nf;
     return 0;
 }
-
-bool huge_tile_major_ok(const HugePlan *p, uint32_t nf) { return p && !p->cfg.fm && !p->cfg.mix && nf && (nf & 15u) == 0; }
 
 }  // namespace csdr
