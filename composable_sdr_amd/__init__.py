@@ -8,6 +8,6 @@ from ._lib import CsdrError, lib, lib_path, build_library, DEMOD_NONE, DEMOD_FM,
 from .pipes import (  # noqa: F401
     Pipe, compose, Chain, ChainConfig, dcBlocker, mixDown, mixUp, automaticGainControl,
     fmDemodulator, amDemodulator, resampler, iirFilter, firDecimator, wbFMDemodulator, firpfbchChannelizer,
-    FmStereo, stereoFMDecoder, SymSync, symSyncR, fmDemWithSync,
+    FmStereo, stereoFMDecoder, SymSync, symSyncR, fmDemWithSync, FirHilb, realToComplex, complexToReal,
 )
 from .trans import compact, takeNArr, mix, mux, distribute_, addPipe  # noqa: F401

@@ -89,6 +89,15 @@ SIGNATURES = {
     "csdr_symsync_get_taps_len": (_u32, [_vp]),
     "csdr_symsync_get_taps": (_i32, [_vp, _vp, _vp]),
     "csdr_symsync_destroy": (_i32, [_vp]),
+    "csdr_firhilb_create": (_i32, [_u32, _f32, _u32, _pp]),
+    "csdr_firhilb_decim": (_i32, [_vp, _vp, _u32, _vp]),
+    "csdr_firhilb_interp": (_i32, [_vp, _vp, _u32, _vp]),
+    "csdr_firhilb_decim_device": (_i32, [_vp, _vp, _u32, _vp, _vp]),
+    "csdr_firhilb_interp_device": (_i32, [_vp, _vp, _u32, _vp, _vp]),
+    "csdr_firhilb_reset": (_i32, [_vp]),
+    "csdr_firhilb_get_taps_len": (_u32, [_vp]),
+    "csdr_firhilb_get_taps": (_i32, [_vp, _vp]),
+    "csdr_firhilb_destroy": (_i32, [_vp]),
     "csdr_chain_cfg_default": (None, [C.POINTER(ChainCfg), _u32]),
     "csdr_chain_create": (_i32, [C.POINTER(ChainCfg), _pp]),
     "csdr_chain_process": (_i32, [_vp, _vp, _u32, _vp, _pu32]),

@@ -1,6 +1,7 @@
 """Replay of `sdrProcess` / `assembleFold` (apps/SoapySDR.hs:181-283) for the file-input path:
 
     readFromFile chunksize fp        Source.chs:259-271   headerless LE float32 I/Q, <= chunksize samples per array
+    | readFromAudioFile chunksize    Source.chs:273-307   a mono WAV / AU file: chunksize floats -> mixUp pi . realToComplex
       -> takeNArr n                  Trans.hs:33-56
       -> dcBlocker -> compact (4*nch*1024) -> PFB -> per-channel demod -> sinks   SoapySDR.hs:208-226
 
@@ -15,8 +16,8 @@ channel into raw `.f32` sinks."""
 import struct
 import numpy as np
 
-from .pipes import (Chain, ChainConfig, SymSync, automaticGainControl, compose, fmDemodulator, idPipe, mixDown, mixUp, resampler,
-                    stereoFMDecoder, unPipe)
+from .pipes import (Chain, ChainConfig, SymSync, automaticGainControl, compose, fmDemodulator, idPipe, mixDown, mixUp, realToComplex,
+                    resampler, stereoFMDecoder, unPipe)
 from .trans import Fold, compact, mix as mix_pipe, takeNArr
 
 
@@ -28,6 +29,148 @@ def readFromFile(n, fp):
             if not b:
                 return
             yield np.frombuffer(b[: len(b) // 8 * 8], dtype=np.complex64)
+
+
+class SourceError(RuntimeError):
+    """the reference's "Unable to open source" (SoapySDR.hs:172-179)"""
+
+
+class AudioFile:
+    """openAudioFile's SF.Handle (Source.chs:273-285) without libsndfile: a hand-written reader, as audioFileSink's writers are.
+
+    RIFF / RIFX WAV with `fmt ` tag 1 (PCM 8 / 16 / 24 / 32), 3 (IEEE float 32 / 64) or 0xFFFE (extensible: the tag is the
+    sub-format's first two bytes); chunks other than `fmt ` and `data` (fact, PEAK, LIST ...) are skipped.  `.snd` AU with
+    encoding 2, 3, 4, 5 (PCM 8 / 16 / 24 / 32), 6, 7 (float 32 / 64), big-endian.  read(n) is libsndfile's float read
+    (hGetBuffer): PCM16 / 32768, PCM24 / 8388608, PCM32 / 2147483648, WAV's unsigned 8 bit (v - 128) / 128, AU's signed
+    8 bit / 128, floats as they are (64 -> 32 rounded).  A data size of 0 or 0xffffffff (a writer that never closed) means
+    "to the end of the file"."""
+
+    def __init__(self, path, f, channels, rate, kind, width, big, offset, nbytes):
+        self.path, self.f, self.channels, self.rate = path, f, channels, rate
+        self.kind, self.width, self.big = kind, width, big            # kind: "u8" | "int" | "float"
+        self.left = nbytes // width * width
+        f.seek(offset)
+
+    @staticmethod
+    def open(path):
+        """the AudioFile of `path`, or None when the header is neither WAV nor AU (the caller then reads raw CF32, as
+        initFileSource does when libsndfile refuses the file); SourceError for an audio file this reader cannot decode"""
+        f = open(path, "rb")
+        try:
+            a = AudioFile._parse(path, f)
+        except Exception:
+            f.close()
+            raise
+        if a is None:
+            f.close()
+        return a
+
+    @staticmethod
+    def _parse(path, f):
+        size = f.seek(0, 2)
+        f.seek(0)
+        head = f.read(12)
+        if len(head) >= 12 and head[:4] in (b"RIFF", b"RIFX") and head[8:12] == b"WAVE":
+            e = "<" if head[:4] == b"RIFF" else ">"
+            fmt, pos = None, 12
+            while pos + 8 <= size:
+                f.seek(pos)
+                cid, csz = struct.unpack(e + "4sI", f.read(8))
+                if cid == b"fmt ":
+                    b = f.read(min(csz, 40))
+                    if len(b) < 16:
+                        raise SourceError(f"Unable to open source: {path}: short fmt chunk")
+                    tag, nch, rate, _, _, bits = struct.unpack(e + "HHIIHH", b[:16])
+                    if tag == 0xFFFE and len(b) >= 26:
+                        tag = struct.unpack(e + "H", b[24:26])[0]
+                    fmt = (tag, nch, rate, bits)
+                elif cid == b"data":
+                    if fmt is None:
+                        raise SourceError(f"Unable to open source: {path}: data chunk before fmt")
+                    tag, nch, rate, bits = fmt
+                    if (tag, bits) not in ((1, 8), (1, 16), (1, 24), (1, 32), (3, 32), (3, 64)):
+                        raise SourceError(f"Unable to open source: {path}: WAV format tag {tag} with {bits} bits is not supported")
+                    avail = size - (pos + 8)
+                    nbytes = avail if csz in (0, 0xffffffff) else min(csz, avail)
+                    kind = "float" if tag == 3 else ("u8" if bits == 8 else "int")
+                    return AudioFile(path, f, nch, rate, kind, bits // 8, e == ">", pos + 8, nbytes)
+                pos += 8 + csz + (csz & 1)
+            raise SourceError(f"Unable to open source: {path}: WAV without a data chunk")
+        if len(head) >= 4 and head[:4] == b".snd":
+            f.seek(0)
+            b = f.read(24)
+            if len(b) < 24:
+                raise SourceError(f"Unable to open source: {path}: short AU header")
+            _, off, dsz, enc, rate, nch = struct.unpack(">4sIIIII", b)
+            table = {2: ("int", 1), 3: ("int", 2), 4: ("int", 3), 5: ("int", 4), 6: ("float", 4), 7: ("float", 8)}
+            if enc not in table or off < 24 or off > size:
+                raise SourceError(f"Unable to open source: {path}: AU encoding {enc} is not supported")
+            avail = size - off
+            nbytes = avail if dsz in (0, 0xffffffff) else min(dsz, avail)
+            return AudioFile(path, f, nch, rate, table[enc][0], table[enc][1], True, off, nbytes)
+        return None
+
+    def read(self, n):
+        """hGetBuffer h n: up to n float32 samples (fewer at the end of the data, none after it)"""
+        b = self.f.read(min(n * self.width, self.left))
+        b = b[: len(b) // self.width * self.width]
+        self.left -= len(b)
+        e, w = (">" if self.big else "<"), self.width
+        if self.kind == "float":
+            return np.frombuffer(b, dtype=e + ("f4" if w == 4 else "f8")).astype(np.float32)
+        if self.kind == "u8":
+            return ((np.frombuffer(b, dtype=np.uint8).astype(np.int32) - 128).astype(np.float32) / np.float32(128.0))
+        if w == 3:
+            u = np.frombuffer(b, dtype=np.uint8).reshape(-1, 3).astype(np.int32)
+            hi, mid, lo = (u[:, 0], u[:, 1], u[:, 2]) if self.big else (u[:, 2], u[:, 1], u[:, 0])
+            v = ((hi << 24) | (mid << 16) | (lo << 8)) >> 8               # sign-extended
+        else:
+            v = np.frombuffer(b, dtype=e + {1: "i1", 2: "i2", 4: "i4"}[w])
+        return v.astype(np.float32) * np.float32(1.0 / float(1 << (8 * w - 1)))
+
+    def close(self):
+        self.f.close()
+
+
+def openAudioFile(fp):
+    """openAudioFile (Source.chs:273-285): the handle, or None for a file that is no audio file; anything but mono is the
+    reference's SoapyException -> "Unable to open source" (there is no fall-back to raw for such a file)"""
+    h = AudioFile.open(fp)
+    if h is not None and h.channels != 1:
+        h.close()
+        raise SourceError(f"Unable to open source: {fp} has {h.channels} channels, an audio source must be mono")
+    return h
+
+
+def readFromAudioFile(n, h):
+    """readFromAudioFile n (Source.chs:291-307) in front of its Pipe: arrays of at most n floats until the data ends"""
+    while True:
+        a = h.read(n)
+        if a.size == 0:
+            return
+        yield a
+
+
+def fileSource(chunksize, fp):
+    """initFileSource (SoapySDR.hs:172-179): every file is tried as an audio file first and read as raw CF32 otherwise.
+    Returns (stream of CF32 arrays, cleanup).  An audio source yields, per chunksize floats read,
+    mixUp (2 pi 0.5) . realToComplex of them: chunksize / 2 samples, the real band 0 .. fs/2 on -fs/4 .. fs/4 of the complex
+    rate fs / 2.  DEVIATION: the reference drops the last float of every chunk when chunksize is odd while liquid's windows
+    run on; that is not replayed, an odd chunksize is refused for an audio source.  The last, short chunk of a file may be odd:
+    its last float is dropped (firhilbDecim's `length div 2`)."""
+    h = openAudioFile(fp)
+    if h is None:
+        return readFromFile(chunksize, fp), (lambda: None)
+    if chunksize % 2:
+        h.close()
+        raise SourceError(f"Unable to open source: {fp} is an audio file and needs an even --chunksize (got {chunksize})")
+    f = float(np.float32(2 * np.pi * 0.5))                             # the Haskell Float 2 * pi * 0.5
+    process, cleanup = unPipe(compose(mixUp(f, max_samples=chunksize // 2), realToComplex(max_samples=chunksize // 2)))
+
+    def done():
+        h.close()
+        cleanup()
+    return process(readFromAudioFile(chunksize, h)), done
 
 
 class fileSink(Fold):
@@ -159,6 +302,7 @@ def sdr_process(filename, channels=1, demod="none", kf=0.3, agc=0.0, mix=False, 
         return _sdr_process_sync(filename, channels, agc, mix, numsamples, outname, chunksize, offset, samplerate, bandwidth, k)
     nch = channels
     mixed = bool(mix) and nch > 1
+    source, close_source = fileSource(chunksize, filename)
     ext = ".cf32" if demod == "none" else ".f32"
     stems = [outname] if (mixed or nch == 1) else [f"{outname}_ch{k}" for k in range(1, nch + 1)]
     out_bw = bandwidth if bandwidth != 0 else samplerate
@@ -177,11 +321,12 @@ def sdr_process(filename, channels=1, demod="none", kf=0.3, agc=0.0, mix=False, 
     # prep = takeNArr ns . (resampler . offset)   (SoapySDR.hs:206-207)
     process, cleanup = unPipe(_prep(offset, samplerate, bandwidth, chunksize))       # (process, cleanup) <- unPipe (resampler . offset)
     try:
-        for a in takeNArr(numsamples, process(readFromFile(chunksize, filename))):
+        for a in takeNArr(numsamples, process(source)):
             fold.step(a)
     finally:
         fold.done()
         cleanup()
+        close_source()
     return names
 
 
@@ -203,6 +348,7 @@ def _sdr_process_fms(filename, channels, agc, numsamples, outname, chunksize, of
     per source chunk: no DC blocker, no compact, no channelizer; -c only divides the sink's rate.  The sink is one 2-channel
     audioFileSink at round(outBW) div decim div nch Hz (getAudioSink decim fmt 2), or raw interleaved L, R float32 <out>.f32."""
     out_bw = bandwidth if bandwidth != 0 else samplerate
+    source, close_source = fileSource(chunksize, filename)
     if audio:
         sink = audioFileSink(audio, int(round(out_bw)) // decim // channels, numsamples, 2, outname)
         name = sink.path
@@ -215,12 +361,13 @@ def _sdr_process_fms(filename, channels, agc, numsamples, outname, chunksize, of
     process, cleanup = unPipe(_prep(offset, samplerate, bandwidth, chunksize))
     r = dem._start()
     try:
-        for a in takeNArr(numsamples, process(readFromFile(chunksize, filename))):
+        for a in takeNArr(numsamples, process(source)):
             sink.step(dem._process(r, a))
     finally:
         dem._done(r)
         sink.done()
         cleanup()
+        close_source()
     return [name]
 
 
@@ -230,6 +377,7 @@ def _sdr_process_sync(filename, channels, agc, mix, numsamples, outname, chunksi
     -> raw .f32 sinks, or with -m the channels' truncating left fold into one sink"""
     nch = channels
     mixed = bool(mix) and nch > 1
+    source, close_source = fileSource(chunksize, filename)
     stems = [outname] if (mixed or nch == 1) else [f"{outname}_ch{j}" for j in range(1, nch + 1)]
     names = [st + ".f32" for st in stems]
     sinks = [fileSink(nm) for nm in names]
@@ -239,9 +387,10 @@ def _sdr_process_sync(filename, channels, agc, mix, numsamples, outname, chunksi
     fold = compact(4 * k * nch * 1024, _SyncFold(chain, sync, sinks, mixed))
     process, cleanup = unPipe(_prep(offset, samplerate, bandwidth, chunksize))
     try:
-        for a in takeNArr(numsamples, process(readFromFile(chunksize, filename))):
+        for a in takeNArr(numsamples, process(source)):
             fold.step(a)
     finally:
         fold.done()
         cleanup()
+        close_source()
     return names

@@ -852,6 +852,96 @@ int csdr_symsync_get_taps(const csdr_symsync *h, float *mf, float *dmf)
 }
 
 // ---------------------------------------------------------------------------
+// realToComplex / complexToReal (Liquid.chs:503-546): firhilbf as a 2:1 decimator and a 1:2 interpolator
+// ---------------------------------------------------------------------------
+}  // extern "C"
+struct csdr_firhilb {
+    int device; uint32_t m, max_n; std::vector<float> hq;
+    float *d_hist[2] = {nullptr, nullptr}; int cur = 0;     // the windows, pair-interleaved (w1[j], w0[j]), ping-pong
+    float *d_x = nullptr, *d_y = nullptr;
+};
+static int firhilb_run(csdr_firhilb *h, bool interp, const void *d_x, uint32_t n, void *d_y, void *stream)
+{
+    if (!h) { set_error("firhilb: null argument"); return CSDR_ERR_INVALID; }
+    if (n > h->max_n) { set_error("firhilb: %u samples > max %u", n, h->max_n); return CSDR_ERR_SIZE; }
+    if (!n) return CSDR_OK;
+    if (!d_x || !d_y || d_x == d_y) { set_error("firhilb: null or aliased buffer"); return CSDR_ERR_INVALID; }
+    FirhilbLaunch l{};
+    l.n = n; l.m = h->m;
+    std::memcpy(l.hq, h->hq.data(), sizeof(float) * h->hq.size());
+    const int r = launch_firhilb(interp, (const float *)d_x, (float *)d_y, h->d_hist[h->cur], h->d_hist[h->cur ^ 1], l, (hipStream_t)stream);
+    if (!r) h->cur ^= 1;
+    return r;
+}
+static int firhilb_host(csdr_firhilb *h, bool interp, const float *x, uint32_t n, float *y)
+{
+    if (!h || (n && (!x || !y))) { set_error("firhilb: null argument"); return CSDR_ERR_INVALID; }
+    if (n > h->max_n) { set_error("firhilb: %u samples > max %u", n, h->max_n); return CSDR_ERR_SIZE; }
+    if (!n) return CSDR_OK;
+    DevGuard guard(h->device);
+    if (!guard.ok) { set_error("firhilb: cannot select device %d", h->device); return CSDR_ERR_HIP; }
+    CSDR_HIP(hipMemcpy(h->d_x, x, sizeof(float) * 2 * (size_t)n, hipMemcpyHostToDevice));
+    const int r = firhilb_run(h, interp, h->d_x, n, h->d_y, nullptr);
+    if (r) return r;
+    CSDR_HIP(hipMemcpy(y, h->d_y, sizeof(float) * 2 * (size_t)n, hipMemcpyDeviceToHost));
+    return CSDR_OK;
+}
+extern "C" {
+int csdr_firhilb_destroy(csdr_firhilb *h)
+{
+    if (!h) return CSDR_OK;
+    DevGuard guard(h->device);
+    (void)hipDeviceSynchronize();
+    void *ptrs[] = {h->d_hist[0], h->d_hist[1], h->d_x, h->d_y};
+    for (void *p : ptrs) if (p) (void)hipFree(p);
+    delete h;
+    return CSDR_OK;
+}
+int csdr_firhilb_create(uint32_t m, float as_db, uint32_t max_samples, csdr_firhilb **out)
+{
+    if (!out || m < 2 || m > FIRHILB_MAX_M || !(as_db > 0.f) || max_samples > (1u << 30)) {
+        set_error("firhilb: bad arguments (m in [2, %u], As > 0, max_samples <= 2^30)", FIRHILB_MAX_M);
+        return CSDR_ERR_INVALID;
+    }
+    int dev; int r = check_device(-1, &dev); if (r) return r;
+    csdr_firhilb *h = new (std::nothrow) csdr_firhilb();
+    if (!h) return CSDR_ERR_NOMEM;
+    h->device = dev; h->m = m; h->max_n = max_samples ? max_samples : 4096;
+    h->hq = design_firhilb(m, as_db);
+    const size_t n2 = 2 * (size_t)h->max_n;
+    if ((r = dev_alloc(&h->d_hist[0], 4 * m)) || (r = dev_alloc(&h->d_hist[1], 4 * m)) || (r = dev_alloc(&h->d_x, n2)) ||
+        (r = dev_alloc(&h->d_y, n2))) { csdr_firhilb_destroy(h); return r; }
+    CSDR_HIP_CLEAN(hipMemset(h->d_hist[0], 0, sizeof(float) * 4 * m), csdr_firhilb_destroy(h));
+    *out = h;
+    return CSDR_OK;
+}
+int csdr_firhilb_decim_device(csdr_firhilb *h, const void *d_x, uint32_t n, void *d_y, void *stream)
+{
+    return firhilb_run(h, false, d_x, n, d_y, stream);
+}
+int csdr_firhilb_interp_device(csdr_firhilb *h, const void *d_x, uint32_t n, void *d_y, void *stream)
+{
+    return firhilb_run(h, true, d_x, n, d_y, stream);
+}
+int csdr_firhilb_decim(csdr_firhilb *h, const float *x_f32, uint32_t n, float *y_cf32) { return firhilb_host(h, false, x_f32, n, y_cf32); }
+int csdr_firhilb_interp(csdr_firhilb *h, const float *x_cf32, uint32_t n, float *y_f32) { return firhilb_host(h, true, x_cf32, n, y_f32); }
+int csdr_firhilb_reset(csdr_firhilb *h)
+{
+    if (!h) return CSDR_ERR_INVALID;
+    DevGuard guard(h->device);
+    CSDR_HIP(hipDeviceSynchronize());
+    CSDR_HIP(hipMemset(h->d_hist[h->cur], 0, sizeof(float) * 4 * h->m));
+    return CSDR_OK;
+}
+uint32_t csdr_firhilb_get_taps_len(const csdr_firhilb *h) { return h ? 2 * h->m : 0; }
+int csdr_firhilb_get_taps(const csdr_firhilb *h, float *hq)
+{
+    if (!h || !hq) return CSDR_ERR_INVALID;
+    std::memcpy(hq, h->hq.data(), sizeof(float) * h->hq.size());
+    return CSDR_OK;
+}
+
+// ---------------------------------------------------------------------------
 // fused chain
 // ---------------------------------------------------------------------------
 }  // extern "C"

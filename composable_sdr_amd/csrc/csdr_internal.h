@@ -248,6 +248,18 @@ struct SymsyncLaunch {
 int launch_symsync(const float *x, float *y, uint32_t *ny, const float *mf, const float *dmf, float *hist, SymsyncState *st,
                    uint32_t *fault_any, const SymsyncLaunch &l, hipStream_t s);
 
+// ---- firhilbf: realToComplex / complexToReal (kernels_firhilb.hip; design in design.cpp) ----
+constexpr uint32_t FIRHILB_MAX_M = 16;               // filter semi-length m: 2 m quadrature taps, 2 m pairs of history
+// firhilbf_create(m, As): the 2 m quadrature-branch taps hq, oldest sample first
+std::vector<float> design_firhilb(uint32_t m, float As);
+struct FirhilbLaunch {
+    uint32_t n, m, vec;                              // n pairs; vec: both buffers 16-byte aligned (set by the launcher)
+    float hq[2 * FIRHILB_MAX_M];
+};
+// x [2 n] -> y [2 n] floats (pairs: x0, x1 -> re, im when decimating; re, im -> y0, y1 when interpolating); hist_in / hist_out
+// [4 m]: the windows pair-interleaved (w1[j], w0[j]) before and after the call; x and y must not overlap
+int launch_firhilb(bool interp, const float *x, float *y, const float *hist_in, float *hist_out, FirhilbLaunch l, hipStream_t s);
+
 // ---- time-parallel exact AGC [+ freqdem] tail (kernels_agc_tail.hip) ----
 struct AgcTailPlan;
 int agc_tail_create(uint32_t C, uint32_t max_nf, AgcTailPlan **out);

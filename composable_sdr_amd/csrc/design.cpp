@@ -71,9 +71,11 @@ std::vector<float> design_pfb_taps(uint32_t M, uint32_t m, float As)
     return h;
 }
 
-// liquid_firdes_kaiser(N, fc, As, 0): h[i] = sinc(2 fc t) w_kaiser(i), t = i - (N-1)/2 (f64)
-static std::vector<double> firdes_kaiser(uint32_t N, double fc, double As)
+// liquid_firdes_kaiser(N, fc, As, 0): h[i] = sinc(2 fc t) w_kaiser(i), t = i - (N-1)/2 (f64).  The window's argument is
+// 2 t / wden, wden = N - 1 (what KAT1 pins) unless the caller passes another
+static std::vector<double> firdes_kaiser(uint32_t N, double fc, double As, double wden = 0.0)
 {
+    if (wden == 0.0) wden = (double)(N - 1);
     const double beta = kaiser_beta(As), ib = bessel_i0(beta);
     const double pi = 3.14159265358979323846;
     std::vector<double> h(N);
@@ -83,7 +85,7 @@ static std::vector<double> firdes_kaiser(uint32_t N, double fc, double As)
         double sinc = std::fabs(x) < 0.01
                           ? std::cos(pi * x / 2) * std::cos(pi * x / 4) * std::cos(pi * x / 8)
                           : std::sin(pi * x) / (pi * x);
-        double r = 2.0 * t / (double)(N - 1);
+        double r = 2.0 * t / wden;
         double a = 1.0 - r * r;
         h[i] = sinc * bessel_i0(beta * std::sqrt(a > 0 ? a : 0)) / ib;
     }
@@ -185,6 +187,24 @@ FmsDesign design_fmstereo(double quad_rate, uint32_t decim)
     f.bq = design_butter2_lowpass((float)(5000.0 / quad_rate));
     f.h_dec = design_firdecim_kaiser(decim, 10, 60.0f);
     return f;
+}
+
+// ---- firhilbf_create(m, As) (Liquid.chs:503-546), DESIGN.md 4.11 ----
+// h = liquid_firdes_kaiser(4 m + 1, 0.25, As, 0); hc[i] = h[i] e^{j pi t / 2}, t = i - 2 m; hq[j] = Im hc[4 m - i], i = 2 j + 1.
+// t is odd there, so the factor is exactly +-1: the prototype in f64, rounded once.  The Kaiser window's argument is 2 t / h_len
+// here, not the 2 t / (h_len - 1) of the other designs: that is what the tap table this block was specified by holds
+// (0.0065559 .. 0.6219635 for m = 5, As = 60), and nothing pins liquid's firhilbf taps either way.
+std::vector<float> design_firhilb(uint32_t m, float As)
+{
+    const uint32_t h_len = 4 * m + 1;
+    const std::vector<double> h = firdes_kaiser(h_len, 0.25, As, (double)h_len);
+    std::vector<float> hq(2 * m);
+    for (uint32_t j = 0; j < 2 * m; j++) {
+        const uint32_t i = h_len - (2 * j + 1) - 1;
+        const int t = (int)i - (int)(2 * m);
+        hq[j] = (float)((((t % 4) + 4) % 4 == 1) ? h[i] : -h[i]);
+    }
+    return hq;
 }
 
 // ---- symsync_rrrf_create_kaiser(k, m, beta, M) + set_lf_bw + set_output_rate (Liquid.chs:244-282), DESIGN.md 4.10 ----

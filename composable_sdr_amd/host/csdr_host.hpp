@@ -14,6 +14,7 @@
 //   mix            Trans.hs:119-122   left fold of element-wise +
 //   fileSink       Sink.hs:29-34      raw chunk writer
 //   readFromFile   Source.chs:259-271 raw CF32 chunks of <= n samples
+//   openAudioFile / readFromAudioFile  Source.chs:273-307  a mono WAV / AU file through mixUp pi . realToComplex (FileSource)
 #pragma once
 #include <complex>
 #include <cstdint>
@@ -236,6 +237,181 @@ inline Pipe<Array<cf32>, Array<cf32>> ncoMixer(float f, bool up, uint32_t max_in
 }
 inline Pipe<Array<cf32>, Array<cf32>> mixDown(float f, uint32_t max_in) { return ncoMixer(f, false, max_in); }
 inline Pipe<Array<cf32>, Array<cf32>> mixUp(float f, uint32_t max_in) { return ncoMixer(f, true, max_in); }
+
+// ---- realToComplex / complexToReal (Liquid.chs:536-537, 545-546): firhilbf_create 5 60 as a 2:1 decimator / 1:2 interpolator;
+// max_in in complex samples.  An odd-length float array loses its last float (firhilbDecim's `length div 2`) ----
+inline Pipe<Array<float>, Array<cf32>> realToComplex(uint32_t max_in, uint32_t m = 5, float as_db = 60.0f)
+{
+    Pipe<Array<float>, Array<cf32>> p;
+    p.start = [=]() {
+        csdr_firhilb *h = nullptr;
+        check(csdr_firhilb_create(m, as_db, max_in, &h));
+        return std::shared_ptr<void>(h, [](void *q) { csdr_firhilb_destroy(static_cast<csdr_firhilb *>(q)); });
+    };
+    p.process = [](void *rr, const Array<float> &a) {
+        Array<cf32> y(a.size() / 2);
+        check(csdr_firhilb_decim(static_cast<csdr_firhilb *>(rr), a.data(), (uint32_t)y.size(), reinterpret_cast<float *>(y.data())));
+        return y;
+    };
+    p.done = [](void *) {};
+    return p;
+}
+inline Pipe<Array<cf32>, Array<float>> complexToReal(uint32_t max_in, uint32_t m = 5, float as_db = 60.0f)
+{
+    Pipe<Array<cf32>, Array<float>> p;
+    p.start = [=]() {
+        csdr_firhilb *h = nullptr;
+        check(csdr_firhilb_create(m, as_db, max_in, &h));
+        return std::shared_ptr<void>(h, [](void *q) { csdr_firhilb_destroy(static_cast<csdr_firhilb *>(q)); });
+    };
+    p.process = [](void *rr, const Array<cf32> &a) {
+        Array<float> y(2 * a.size());
+        check(csdr_firhilb_interp(static_cast<csdr_firhilb *>(rr), reinterpret_cast<const float *>(a.data()), (uint32_t)a.size(), y.data()));
+        return y;
+    };
+    p.done = [](void *) {};
+    return p;
+}
+
+// ---- openAudioFile / readFromAudioFile (Source.chs:273-307) without libsndfile: a hand-written reader, as AudioFileSink is a
+// hand-written writer.  RIFF / RIFX WAV with fmt tag 1 (PCM 8 / 16 / 24 / 32), 3 (IEEE float 32 / 64) or 0xFFFE (the tag is the
+// sub-format's first two bytes), other chunks skipped; .snd AU with encoding 2, 3, 4, 5 (PCM 8 / 16 / 24 / 32), 6, 7 (float
+// 32 / 64).  read() is libsndfile's float read: PCM16 / 32768, PCM24 / 8388608, PCM32 / 2147483648, WAV's unsigned 8 bit
+// (v - 128) / 128, AU's signed 8 bit / 128.  A data size of 0 or 0xffffffff means "to the end of the file" ----
+struct SourceError : std::runtime_error { using std::runtime_error::runtime_error; };
+struct AudioFile {
+    enum Kind { U8, INT, FLOAT };
+    FILE *f = nullptr; uint32_t channels = 0, rate = 0, width = 0; Kind kind = INT; bool big = false; uint64_t left = 0;
+    ~AudioFile() { if (f) std::fclose(f); }
+    static uint32_t u32(const unsigned char *p, bool be) { return be ? (uint32_t)p[0] << 24 | p[1] << 16 | p[2] << 8 | p[3] : (uint32_t)p[3] << 24 | p[2] << 16 | p[1] << 8 | p[0]; }
+    static uint32_t u16(const unsigned char *p, bool be) { return be ? p[0] << 8 | p[1] : p[1] << 8 | p[0]; }
+    // the AudioFile of `path`, or null when the header is neither WAV nor AU (the caller then reads raw CF32)
+    static std::unique_ptr<AudioFile> open(const std::string &path)
+    {
+        FILE *f = std::fopen(path.c_str(), "rb");
+        if (!f) throw SourceError("Unable to open source: " + path);
+        std::unique_ptr<AudioFile> a(new AudioFile());
+        a->f = f;
+        std::fseek(f, 0, SEEK_END);
+        const uint64_t size = (uint64_t)std::ftell(f);
+        std::fseek(f, 0, SEEK_SET);
+        unsigned char head[12];
+        const size_t got = std::fread(head, 1, 12, f);
+        auto fail = [&](const std::string &why) -> std::unique_ptr<AudioFile> { throw SourceError("Unable to open source: " + path + ": " + why); };
+        if (got >= 12 && (!std::memcmp(head, "RIFF", 4) || !std::memcmp(head, "RIFX", 4)) && !std::memcmp(head + 8, "WAVE", 4)) {
+            const bool be = head[3] == 'X';
+            bool have_fmt = false; uint32_t tag = 0, bits = 0;
+            for (uint64_t pos = 12; pos + 8 <= size;) {
+                unsigned char ch[8], b[40];
+                std::fseek(f, (long)pos, SEEK_SET);
+                if (std::fread(ch, 1, 8, f) != 8) break;
+                const uint32_t csz = u32(ch + 4, be);
+                if (!std::memcmp(ch, "fmt ", 4)) {
+                    const size_t nb = std::fread(b, 1, csz < 40 ? csz : 40, f);
+                    if (nb < 16) return fail("short fmt chunk");
+                    tag = u16(b, be); a->channels = u16(b + 2, be); a->rate = u32(b + 4, be); bits = u16(b + 14, be);
+                    if (tag == 0xFFFE && nb >= 26) tag = u16(b + 24, be);
+                    have_fmt = true;
+                } else if (!std::memcmp(ch, "data", 4)) {
+                    if (!have_fmt) return fail("data chunk before fmt");
+                    if (!((tag == 1 && (bits == 8 || bits == 16 || bits == 24 || bits == 32)) || (tag == 3 && (bits == 32 || bits == 64))))
+                        return fail("WAV format tag " + std::to_string(tag) + " with " + std::to_string(bits) + " bits is not supported");
+                    const uint64_t avail = size - (pos + 8);
+                    const uint64_t nbytes = (csz == 0 || csz == 0xffffffffu) ? avail : (csz < avail ? csz : avail);
+                    a->kind = tag == 3 ? FLOAT : (bits == 8 ? U8 : INT); a->width = bits / 8; a->big = be;
+                    a->left = nbytes / a->width * a->width;
+                    return a;                                      // the file position is the first sample
+                }
+                pos += 8 + (uint64_t)csz + (csz & 1);
+            }
+            return fail("WAV without a data chunk");
+        }
+        if (got >= 4 && !std::memcmp(head, ".snd", 4)) {
+            unsigned char b[24];
+            std::fseek(f, 0, SEEK_SET);
+            if (std::fread(b, 1, 24, f) != 24) return fail("short AU header");
+            const uint32_t off = u32(b + 4, true), dsz = u32(b + 8, true), enc = u32(b + 12, true);
+            a->rate = u32(b + 16, true); a->channels = u32(b + 20, true);
+            if (enc < 2 || enc > 7 || off < 24 || off > size) return fail("AU encoding " + std::to_string(enc) + " is not supported");
+            static const uint32_t widths[8] = {0, 0, 1, 2, 3, 4, 4, 8};
+            a->kind = enc >= 6 ? FLOAT : INT; a->width = widths[enc]; a->big = true;
+            const uint64_t avail = size - off;
+            a->left = ((dsz == 0 || dsz == 0xffffffffu) ? avail : (dsz < avail ? dsz : avail)) / a->width * a->width;
+            std::fseek(f, (long)off, SEEK_SET);
+            return a;
+        }
+        return nullptr;
+    }
+    // hGetBuffer h n: up to n floats (fewer at the end of the data, none after it)
+    Array<float> read(size_t n)
+    {
+        uint64_t want = (uint64_t)n * width;
+        if (want > left) want = left;
+        std::vector<unsigned char> b(want);
+        size_t gotb = want ? std::fread(b.data(), 1, want, f) : 0;
+        gotb = gotb / width * width;
+        left -= gotb;
+        Array<float> y(gotb / width);
+        for (size_t i = 0; i < y.size(); i++) {
+            const unsigned char *p = b.data() + i * width;
+            unsigned char q[8];
+            for (uint32_t j = 0; j < width; j++) q[j] = big ? p[width - 1 - j] : p[j];       // little-endian now
+            if (kind == FLOAT) {
+                if (width == 4) std::memcpy(&y[i], q, 4);
+                else { double d; std::memcpy(&d, q, 8); y[i] = (float)d; }
+            } else if (kind == U8) y[i] = (float)((int)q[0] - 128) / 128.0f;
+            else {
+                uint32_t u = 0;
+                for (uint32_t j = 0; j < width; j++) u |= (uint32_t)q[j] << (8 * (j + 4 - width));   // left-aligned in 32 bits
+                const int32_t v = (int32_t)u >> (8 * (4 - width));                                      // sign-extended
+                y[i] = (float)v * (1.0f / (float)(1ull << (8 * width - 1)));
+            }
+        }
+        return y;
+    }
+};
+
+// initFileSource (SoapySDR.hs:172-179): every file is tried as an audio file first and read as raw CF32 otherwise.  An audio
+// source must be mono ("Unable to open source", no fall-back to raw) and yields, per `chunk` floats read,
+// mixUp (2 pi 0.5) . realToComplex of them: chunk / 2 samples.  DEVIATION: the reference drops the last float of every chunk when
+// chunk is odd while liquid's windows run on; an odd chunk is refused for an audio source instead.  A last, short chunk with an
+// odd count drops its last float.
+struct FileSource {
+    FILE *f = nullptr; std::unique_ptr<AudioFile> audio; size_t chunk;
+    UnPiped<Array<float>, Array<cf32>> front; bool have_front = false;
+    FileSource(const std::string &path, size_t chunk_) : chunk(chunk_)
+    {
+        audio = AudioFile::open(path);
+        if (!audio) {
+            f = std::fopen(path.c_str(), "rb");
+            if (!f) throw SourceError("Unable to open source: " + path);
+            return;
+        }
+        if (audio->channels != 1)
+            throw SourceError("Unable to open source: " + path + " has " + std::to_string(audio->channels) + " channels, an audio source must be mono");
+        if (chunk % 2)
+            throw SourceError("Unable to open source: " + path + " is an audio file and needs an even --chunksize (got " + std::to_string(chunk) + ")");
+        const float fm = (float)(2.0 * 3.14159265358979323846 * 0.5);          // the Haskell Float 2 * pi * 0.5
+        front = unPipe(compose(mixUp(fm, (uint32_t)(chunk / 2)), realToComplex((uint32_t)(chunk / 2))));
+        have_front = true;
+    }
+    ~FileSource() { if (f) std::fclose(f); }
+    // the next array; false at the end of the file
+    bool next(Array<cf32> &a)
+    {
+        if (audio) {
+            const Array<float> x = audio->read(chunk);
+            if (x.empty()) return false;
+            a = front.process(x);
+            return true;
+        }
+        a.resize(chunk);
+        const size_t got = std::fread(a.data(), sizeof(cf32), chunk, f);
+        a.resize(got);
+        return got != 0;
+    }
+    void close() { if (have_front) { front.cleanup(); have_front = false; } }
+};
 
 // ---- DeFMS's per-chunk Pipes (SoapySDR.hs:261-264): automaticGainControl tres (Liquid.chs:727-728), fmDemodulator kf
 // (Liquid.chs:333-334), stereoFMDecoder quadRate decim (Liquid.chs:1069-1078; interleaved L, R out) ----

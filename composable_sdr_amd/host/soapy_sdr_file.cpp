@@ -5,7 +5,8 @@
 // --world W: one process per GPU, each reading the same file; process R owns the channels R, R + W, ... (interleaved channel shard,
 // SURVEY 8e(A)) and writes only their <out>_ch<k+1> files (SoapySDR.hs:209-212); with --mix the partial sums of the W processes meet
 // in one RCCL all-reduce per chunk (csdr_chain_process_mix) and process 0 writes the one mixed file (SoapySDR.hs:217-222).
-// readFromFile -> [mixDown/mixUp (--offset)] -> [resampler (-b)] -> takeNArr -> compact(4*M*1024) -> fused chain (dcBlocker + PFB + demod [+mix]) -> fileSinks
+// --filename may also be a mono WAV / AU file (initFileSource, SoapySDR.hs:172-179): it is then read through mixUp pi . realToComplex.
+// readFromFile | readFromAudioFile -> [mixDown/mixUp (--offset)] -> [resampler (-b)] -> takeNArr -> compact(4*M*1024) -> fused chain (dcBlocker + PFB + demod [+mix]) -> fileSinks
 // named <out>.cf32 / <out>_ch<k>.cf32 (DeNo, SoapySDR.hs:240) or raw .f32 for FM (the reference wraps
 // the same samples in WAV/AU through libsndfile).
 #include <cmath>
@@ -25,6 +26,7 @@ template <class Out> static int run(const std::string &in, const ChainOpts &o, s
 {
     const uint32_t M = o.channels;
     const bool mixed = o.mix && M > 1;
+    FileSource src(in, chunk);                              // before any sink exists: a refused source leaves no output file
     std::vector<std::shared_ptr<Fold<Array<Out>>>> sinks;
     auto make = [&](const std::string &stem) -> std::shared_ptr<Fold<Array<Out>>> {
         if constexpr (std::is_same<Out, float>::value) {
@@ -46,8 +48,6 @@ template <class Out> static int run(const std::string &in, const ChainOpts &o, s
     else for (uint32_t row = 0; row < o.owned(); row++) sinks.push_back(make(out + "_ch" + std::to_string(o.channel_of(row) + 1)));
     auto fold = compact<cf32>((size_t)4 * M * 1024, addPipe(fusedChain<Out>(o), std::static_pointer_cast<Fold<std::vector<Array<Out>>>>(
                                                                                     std::make_shared<Distribute<Out>>(sinks))));
-    FILE *f = std::fopen(in.c_str(), "rb");
-    if (!f) { std::cerr << "Unable to open source: " << in << "\n"; return 1; }
     // prep = takeNArr ns . (resampler . offset)  (SoapySDR.hs:190-207)
     using CPipe = Pipe<Array<cf32>, Array<cf32>>;
     const float fo = (float)(2.0 * 3.14159265358979323846 * g_front.offset / g_front.samplerate);
@@ -56,17 +56,13 @@ template <class Out> static int run(const std::string &in, const ChainOpts &o, s
                                             : idPipe<Array<cf32>>();
     auto prep = unPipe(compose(resamp, offset));            // (process, cleanup) <- unPipe (resampler . offset)
     TakeN take(n);
-    Array<cf32> a(chunk);
-    while (true) {
-        a.resize(chunk);
-        const size_t got = std::fread(a.data(), sizeof(cf32), chunk, f);
-        if (!got) break;
-        a.resize(got);
+    Array<cf32> a;
+    while (src.next(a)) {
         Array<cf32> b = prep.process(a);
         if (!take.feed(b)) break;
         fold->step(b);
     }
-    std::fclose(f);
+    src.close();
     fold->done();
     prep.cleanup();
     return 0;
@@ -78,6 +74,7 @@ template <class Out> static int run(const std::string &in, const ChainOpts &o, s
 static int run_fms(const std::string &in, const ChainOpts &o, size_t n, const std::string &out, size_t chunk)
 {
     const double bw = g_front.bandwidth != 0.0 ? g_front.bandwidth : g_front.samplerate;
+    FileSource src(in, chunk);
     std::shared_ptr<Fold<Array<float>>> sink;
     if (!g_front.audio.empty())
         sink = std::make_shared<AudioFileSink>(g_front.audio, (uint32_t)std::llround(bw) / o.decim / o.channels, 2u, out);
@@ -85,8 +82,6 @@ static int run_fms(const std::string &in, const ChainOpts &o, size_t n, const st
     const uint32_t cap = (uint32_t)(4 * chunk + 16);                  // the resampler's largest output (rate <= 2)
     Pipe<Array<cf32>, Array<cf32>> agc = o.agc != 0.f ? agcPipe(o.agc, cap) : idPipe<Array<cf32>>();
     auto dem = addPipe(compose(fmStereoPipe((float)bw, o.decim, cap), compose(freqdemPipe(0.8f, cap), agc)), sink);
-    FILE *f = std::fopen(in.c_str(), "rb");
-    if (!f) { std::cerr << "Unable to open source: " << in << "\n"; return 1; }
     using CPipe = Pipe<Array<cf32>, Array<cf32>>;
     const float fo = (float)(2.0 * 3.14159265358979323846 * g_front.offset / g_front.samplerate);
     CPipe offset = fo > 0 ? mixDown(fo, (uint32_t)chunk) : (fo < 0 ? mixUp(-fo, (uint32_t)chunk) : idPipe<Array<cf32>>());
@@ -94,17 +89,13 @@ static int run_fms(const std::string &in, const ChainOpts &o, size_t n, const st
                                             : idPipe<Array<cf32>>();
     auto prep = unPipe(compose(resamp, offset));
     TakeN take(n);
-    Array<cf32> a(chunk);
-    while (true) {
-        a.resize(chunk);
-        const size_t got = std::fread(a.data(), sizeof(cf32), chunk, f);
-        if (!got) break;
-        a.resize(got);
+    Array<cf32> a;
+    while (src.next(a)) {
         Array<cf32> b = prep.process(a);
         if (!take.feed(b)) break;
         dem->step(b);
     }
-    std::fclose(f);
+    src.close();
     dem->done();
     prep.cleanup();
     return 0;
@@ -118,6 +109,7 @@ static int run_sync(const std::string &in, ChainOpts o, uint32_t k, size_t n, co
     const uint32_t M = o.channels;
     const bool mixed = o.mix && M > 1;
     o.fm = true; o.kf = 0.02f * (float)k; o.mix = false; o.max_frames = 4 * k * 1024;
+    FileSource src(in, chunk);
     using Rows = std::vector<Array<float>>;
     std::vector<std::shared_ptr<Fold<Array<float>>>> sinks;
     if (mixed || M == 1) sinks.push_back(std::make_shared<FileSink<float>>(out + ".f32"));
@@ -131,8 +123,6 @@ static int run_sync(const std::string &in, ChainOpts o, uint32_t k, size_t n, co
         tail = addPipe(mixp, tail);
     }
     auto fold = compact<cf32>((size_t)4 * k * M * 1024, addPipe(fusedChain<float>(o), addPipe(symSyncR(k, 4, 0.f, 64, M, 4 * k * 1024), tail)));
-    FILE *f = std::fopen(in.c_str(), "rb");
-    if (!f) { std::cerr << "Unable to open source: " << in << "\n"; return 1; }
     using CPipe = Pipe<Array<cf32>, Array<cf32>>;
     const float fo = (float)(2.0 * 3.14159265358979323846 * g_front.offset / g_front.samplerate);
     CPipe offset = fo > 0 ? mixDown(fo, (uint32_t)chunk) : (fo < 0 ? mixUp(-fo, (uint32_t)chunk) : idPipe<Array<cf32>>());
@@ -140,17 +130,13 @@ static int run_sync(const std::string &in, ChainOpts o, uint32_t k, size_t n, co
                                             : idPipe<Array<cf32>>();
     auto prep = unPipe(compose(resamp, offset));
     TakeN take(n);
-    Array<cf32> a(chunk);
-    while (true) {
-        a.resize(chunk);
-        const size_t got = std::fread(a.data(), sizeof(cf32), chunk, f);
-        if (!got) break;
-        a.resize(got);
+    Array<cf32> a;
+    while (src.next(a)) {
         Array<cf32> b = prep.process(a);
         if (!take.feed(b)) break;
         fold->step(b);
     }
-    std::fclose(f);
+    src.close();
     fold->done();
     prep.cleanup();
     return 0;

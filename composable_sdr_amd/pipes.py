@@ -334,6 +334,73 @@ def fmDemWithSync(k, nchan=1, max_samples=1 << 16):
     return compose(symSyncR(k, 4, 0.0, 64, nchan, max_samples), fmDemodulator(kf, nchan, max_samples))
 
 
+class FirHilb:
+    """The `csdr_firhilb_*` object: firhilbf_create m As (firhilbCreate, Liquid.chs:520-525, fixes 5 and 60), a half-band Hilbert
+    transform driven as a 2:1 real-to-complex decimator and a 1:2 complex-to-real interpolator on shared windows
+    (include/csdr.h).  `max_samples` is the largest call in complex samples."""
+
+    def __init__(self, m=5, as_db=60.0, max_samples=1 << 16):
+        h = C.c_void_p()
+        check(lib().csdr_firhilb_create(int(m), float(as_db), int(max_samples), C.byref(h)))
+        self._h = _Handle(h, lib().csdr_firhilb_destroy)
+        self.m = int(m)
+
+    @property
+    def h(self):
+        if not self._h.h:
+            raise CsdrError(_lib.ERR_INVALID, "firhilb already destroyed")
+        return self._h.h
+
+    @property
+    def taps_len(self):
+        return int(lib().csdr_firhilb_get_taps_len(self.h))
+
+    def taps(self):
+        """the 2 m quadrature-branch taps hq, oldest sample first"""
+        hq = np.empty(self.taps_len, np.float32)
+        check(lib().csdr_firhilb_get_taps(self.h, _ptr(hq)))
+        return hq
+
+    def decim(self, x):
+        """firhilbDecim (Liquid.chs:530-534): F32 [2 n (+ 1)] -> CF32 [n]; `length div 2` drops an odd last float"""
+        x = np.ascontiguousarray(x, dtype=np.float32).reshape(-1)
+        n = x.size // 2
+        y = np.empty(n, dtype=np.complex64)
+        check(lib().csdr_firhilb_decim(self.h, _ptr(x), n, _ptr(y)))
+        return y
+
+    def interp(self, x):
+        """firhilbInterp (Liquid.chs:539-543): CF32 [n] -> F32 [2 n]"""
+        x = _c64(x).reshape(-1)
+        y = np.empty(2 * x.size, dtype=np.float32)
+        check(lib().csdr_firhilb_interp(self.h, _ptr(x), x.size, _ptr(y)))
+        return y
+
+    def decim_device(self, d_x_ptr, n, d_y_ptr, stream=0):
+        """Device-resident variant: raw device pointers (ints) for 2 n floats in, n complex out; enqueues on `stream`"""
+        check(lib().csdr_firhilb_decim_device(self.h, C.c_void_p(d_x_ptr), n, C.c_void_p(d_y_ptr), C.c_void_p(stream)))
+
+    def interp_device(self, d_x_ptr, n, d_y_ptr, stream=0):
+        """Device-resident variant: n complex in, 2 n floats out"""
+        check(lib().csdr_firhilb_interp_device(self.h, C.c_void_p(d_x_ptr), n, C.c_void_p(d_y_ptr), C.c_void_p(stream)))
+
+    def reset(self):
+        check(lib().csdr_firhilb_reset(self.h))
+
+    def close(self):
+        self._h.close()
+
+
+def realToComplex(m=5, as_db=60.0, max_samples=1 << 16):
+    """realToComplex (Liquid.chs:536-537) as a Pipe from F32 arrays to CF32 arrays of half the length"""
+    return Pipe(lambda: FirHilb(m, as_db, max_samples), lambda r, a: r.decim(a), lambda r: r.close())
+
+
+def complexToReal(m=5, as_db=60.0, max_samples=1 << 16):
+    """complexToReal (Liquid.chs:545-546) as a Pipe from CF32 arrays to F32 arrays of twice the length"""
+    return Pipe(lambda: FirHilb(m, as_db, max_samples), lambda r, a: r.interp(a), lambda r: r.close())
+
+
 def resampler(r, as_db=60.0, max_samples=1 << 20):
     """resampler r as (Liquid.chs:115-117): Pipe IO (Array CF32) (Array CF32) with a variable-length output
     (`shrinkToFit` to the count msresamp_crcf_execute reports, :79-98).  r == 0 is the identity."""

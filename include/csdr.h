@@ -277,6 +277,35 @@ int csdr_symsync_get_taps(const csdr_symsync *h, float *mf, float *dmf);
 int csdr_symsync_destroy(csdr_symsync *h);
 
 /* ------------------------------------------------------------------------ *
+ * realToComplex / complexToReal  (Liquid.chs:503-546; the audio-file source mixUp (2 pi 0.5) . realToComplex,
+ * Source.chs:273-307).  Replaces firhilbf_create(m, As) (firhilbCreate passes 5, 60.0, Liquid.chs:520-525) with
+ * firhilbf_decim_execute_block (Liquid.chs:530-534) and firhilbf_interp_execute_block (Liquid.chs:539-543).
+ * liquid-dsp 1.3.2 as recalled: unpinned.
+ *   design: h = liquid_firdes_kaiser(4 m + 1, 0.25, As, 0) (f64, rounded once); hc[i] = h[i] e^{j pi (i - 2 m) / 2};
+ *     the 2 m quadrature taps hq[j] = Im hc[4 m - i], i = 2 j + 1.
+ *   state: two windows w0, w1 of 2 m floats, zero after create / reset; a push appends the newest, index 0 is the oldest.
+ *   decimator, per input pair (x0, x1): push x0 to w1, yq = sum_j hq[j] w1[j]; push x1 to w0, yi = w0[m - 1]; out yi + j yq.
+ *   interpolator, per input x: push Im x to w0, y[0] = w0[m - 1]; push Re x to w1, y[1] = sum_j hq[j] w1[j].
+ *   Arithmetic: plain f32 without contraction, the sum taken j = 0 .. 2 m - 1 starting from the first product.  The output
+ *     does not depend on the chunking, bit for bit.  One handle may be driven in both directions; the windows are shared.
+ *   Limits (create, else CSDR_ERR_INVALID): m in [2, 16], As > 0, max_samples <= 2^30 (0 means 4096).
+ *   n counts complex samples: any n <= max_samples, 0 included.  Input and output buffers must not overlap.
+ * ------------------------------------------------------------------------ */
+typedef struct csdr_firhilb csdr_firhilb;
+int csdr_firhilb_create(uint32_t m, float as_db, uint32_t max_samples, csdr_firhilb **out);
+/* firhilbf_decim_execute_block (Liquid.chs:530-534): 2 n reals in, n complex out */
+int csdr_firhilb_decim(csdr_firhilb *h, const float *x_f32, uint32_t n, float *y_cf32);
+/* firhilbf_interp_execute_block (Liquid.chs:539-543): n complex in, 2 n reals out */
+int csdr_firhilb_interp(csdr_firhilb *h, const float *x_cf32, uint32_t n, float *y_f32);
+/* device buffers of 2 n floats each; enqueued on `stream`, no synchronisation */
+int csdr_firhilb_decim_device(csdr_firhilb *h, const void *d_x, uint32_t n, void *d_y, void *stream);
+int csdr_firhilb_interp_device(csdr_firhilb *h, const void *d_x, uint32_t n, void *d_y, void *stream);
+int csdr_firhilb_reset(csdr_firhilb *h);                         /* back to the state right after create            */
+uint32_t csdr_firhilb_get_taps_len(const csdr_firhilb *h);       /* 2 m                                              */
+int csdr_firhilb_get_taps(const csdr_firhilb *h, float *hq);     /* the quadrature taps, oldest sample first         */
+int csdr_firhilb_destroy(csdr_firhilb *h);
+
+/* ------------------------------------------------------------------------ *
  * The fused chain: everything assembleFold (apps/SoapySDR.hs:208-226) puts
  * behind `compact`:
  *     dcBlocker                                   (SoapySDR.hs:213-214)

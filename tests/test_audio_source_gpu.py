@@ -1,0 +1,170 @@
+"""The audio-file source (initFileSource / openAudioFile / readFromAudioFile, SoapySDR.hs:172-179, Source.chs:273-307) in both
+hosts, and README Example 6 from a WAV recording to the KML of position fixes.
+
+A mono WAV / AU --filename is read as floats, chunksize at a time, through mixUp (2 pi 0.5) . realToComplex; everything behind
+is the raw-CF32 path.  So sdr_process on the audio file must write, byte for byte, what it writes for the raw CF32 file made by
+hand from the same Pipes, read with half the chunk size (the same chunk boundaries)."""
+import os
+import struct
+import subprocess
+
+import numpy as np
+import pytest
+
+import helilink
+
+pytestmark = pytest.mark.gpu
+
+cs = pytest.importorskip("composable_sdr_amd")
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+EXE = os.path.join(ROOT, "composable_sdr_amd", "host", "soapy_sdr_file")
+f32 = np.float32
+
+
+def _write_wav(path, x, kind, rate=48000, nch=1):
+    if kind == "pcm16":
+        tag, bits, payload = 1, 16, np.round(np.asarray(x, np.float64) * 32767.0).astype("<i2").tobytes()
+    else:
+        tag, bits, payload = 3, 32, np.asarray(x, "<f4").tobytes()
+    fmt = struct.pack("<HHIIHH", tag, nch, rate, rate * nch * bits // 8, nch * bits // 8, bits)
+    body = b"WAVE" + b"fmt " + struct.pack("<I", len(fmt)) + fmt + b"data" + struct.pack("<I", len(payload)) + payload
+    open(path, "wb").write(b"RIFF" + struct.pack("<I", len(body)) + body)
+    return str(path)
+
+
+def _by_hand(wav, chunksize, raw):
+    """reader + FirHilb.decim + the mixUp Pipe, chunk by chunk, into a raw CF32 file"""
+    from composable_sdr_amd.app import openAudioFile, readFromAudioFile
+    h = openAudioFile(wav)
+    fh = cs.FirHilb(max_samples=chunksize // 2)
+    mix = cs.mixUp(float(f32(2 * np.pi * 0.5)), max_samples=chunksize // 2)
+    r = mix._start()
+    out = [mix._process(r, fh.decim(a)) for a in readFromAudioFile(chunksize, h)]
+    mix._done(r)
+    fh.close()
+    h.close()
+    z = np.concatenate(out)
+    z.tofile(raw)
+    return z
+
+
+def _cpp(args):
+    if not os.path.exists(EXE):
+        subprocess.check_call(["make", "-C", os.path.dirname(EXE), "-s"])
+    return subprocess.run([EXE] + [str(a) for a in args], capture_output=True, text=True, timeout=300, env=dict(os.environ, CSDR_QUIET="1"))
+
+
+def _real_band_signal(n, seed):
+    """a real recording: three tones and noise, well inside +-1"""
+    rng = np.random.default_rng(seed)
+    t = np.arange(n)
+    x = 0.3 * np.cos(2 * np.pi * 0.2875 * t + 0.4) + 0.2 * np.cos(2 * np.pi * 0.13 * t) + 0.1 * np.cos(2 * np.pi * 0.41 * t + 1.0)
+    return (x + 0.05 * rng.standard_normal(n)).astype(f32)
+
+
+@pytest.mark.parametrize("kind", ["pcm16", "float"])
+@pytest.mark.parametrize("demod,nch", [("none", 1), ("none", 8), ("fm", 1), ("fm", 8)])
+def test_wav_source_equals_the_raw_file_made_by_hand_in_both_hosts(tmp_path, monkeypatch, kind, demod, nch):
+    monkeypatch.setenv("CSDR_QUIET", "1")
+    from composable_sdr_amd.app import sdr_process
+    chunk = 1024
+    nfl = 2 * 20000 * nch + 2 * 777 + 1                      # an odd number of floats: the last one is dropped
+    wav = _write_wav(tmp_path / "in.wav", _real_band_signal(nfl, seed=31 + nch), kind)
+    z = _by_hand(wav, chunk, tmp_path / "in.cf32")
+    assert z.size == nfl // 2
+    n = 20000 * nch
+    a = sdr_process(wav, channels=nch, demod=demod, kf=0.3, numsamples=n, outname=str(tmp_path / "wav"), chunksize=chunk)
+    b = sdr_process(str(tmp_path / "in.cf32"), channels=nch, demod=demod, kf=0.3, numsamples=n, outname=str(tmp_path / "raw"),
+                    chunksize=chunk // 2)
+    assert len(a) == len(b) == nch
+    for p, q in zip(a, b):
+        got = open(p, "rb").read()
+        assert len(got) > 0 and got == open(q, "rb").read(), p
+    r = _cpp(["--filename", wav, "-n", n, "-c", nch, "--chunksize", chunk, "-o", tmp_path / "cpp"] +
+             (["--demod", "DeNBFM", "0.3"] if demod == "fm" else []))
+    assert r.returncode == 0, r.stderr
+    for p in a:
+        q = str(tmp_path / "cpp") + os.path.basename(p)[3:]
+        assert open(q, "rb").read() == open(p, "rb").read(), q
+
+
+def test_au_source_written_by_the_audio_sink(tmp_path, monkeypatch):
+    """an AU float file as audioFileSink writes it goes through the same source"""
+    monkeypatch.setenv("CSDR_QUIET", "1")
+    from composable_sdr_amd.app import audioFileSink, sdr_process
+    x = _real_band_signal(2 * 9000, seed=40)
+    s = audioFileSink("AU", 48000, 0, 1, str(tmp_path / "in"))
+    s.step(x)
+    s.done()
+    _by_hand(s.path, 512, tmp_path / "in.cf32")
+    a = sdr_process(s.path, numsamples=9000, outname=str(tmp_path / "au"), chunksize=512)
+    b = sdr_process(str(tmp_path / "in.cf32"), numsamples=9000, outname=str(tmp_path / "raw"), chunksize=256)
+    assert open(a[0], "rb").read() == open(b[0], "rb").read() and os.path.getsize(a[0]) == 8 * 9000
+
+
+def test_odd_chunksize_and_stereo_are_refused_by_both_hosts(tmp_path, monkeypatch):
+    monkeypatch.setenv("CSDR_QUIET", "1")
+    from composable_sdr_amd.app import SourceError, sdr_process
+    x = _real_band_signal(4000, seed=50)
+    mono = _write_wav(tmp_path / "mono.wav", x, "pcm16")
+    stereo = _write_wav(tmp_path / "stereo.wav", x, "pcm16", nch=2)
+    with pytest.raises(SourceError, match="even"):
+        sdr_process(mono, numsamples=100, outname=str(tmp_path / "a"), chunksize=1023)
+    with pytest.raises(SourceError, match="2 channels"):
+        sdr_process(stereo, numsamples=100, outname=str(tmp_path / "b"), chunksize=1024)
+    assert not os.path.exists(tmp_path / "a.cf32") and not os.path.exists(tmp_path / "b.cf32")
+    r = _cpp(["--filename", mono, "-n", 100, "--chunksize", 1023, "-o", tmp_path / "c"])
+    assert r.returncode != 0 and "even" in r.stderr and not os.path.exists(tmp_path / "c.cf32")
+    r = _cpp(["--filename", stereo, "-n", 100, "-o", tmp_path / "d"])
+    assert r.returncode != 0 and "2 channels" in r.stderr and not os.path.exists(tmp_path / "d.cf32")
+    # an odd chunk size stays fine for a raw file
+    x.view(np.complex64).tofile(tmp_path / "raw.cf32")
+    assert os.path.getsize(sdr_process(str(tmp_path / "raw.cf32"), numsamples=100, outname=str(tmp_path / "e"), chunksize=1023)[0]) == 800
+
+
+def _fsk_real(bitstring, sps=40, centre=0.2875, dev=0.0125, amp=0.5):
+    """continuous-phase binary FSK as a real signal: `sps` real samples per symbol, '0' = +dev, '1' = -dev cycles per real sample
+    around `centre`; the NRZ frequency pulse has raised-cosine edges sps / 2 samples long (as symsync_restatement.nrz_fsk_iq)"""
+    b = np.array([1.0 if c == "0" else -1.0 for c in bitstring])
+    f = np.repeat(dev * b, sps)
+    w = np.hanning(sps // 2 + 2)[1:-1]
+    f = np.convolve(f, w / w.sum(), mode="same")
+    return (amp * np.cos(2 * np.pi * np.cumsum(centre + f))).astype(f32)
+
+
+def test_readme_example_6_from_wav_to_kml(tmp_path, monkeypatch):
+    """soapy-sdr --filename helicopter.wav --offset 1.8e3 -b 4.8e3 --demod "DeNBFMSync 4", then helidecode output.f32.
+
+    The 40-line message of tests/helilink.py behind 1500 and in front of 200 seeded random symbols, 1200-baud continuous-phase
+    FSK at 40 real samples per symbol (a 48 kHz recording, 24 kHz complex behind the source, k = 4 behind -b 4800), deviation
+    600 Hz of the nominal 24 kHz with '0' the positive one, centred at 0.2875 cycles per real sample, which the source puts at
+    2 * 0.2875 - 0.5 = +0.075 cycles per complex sample = +1800 Hz.  Required: all 40 lines back exactly, 39 placemarks."""
+    monkeypatch.setenv("CSDR_QUIET", "1")
+    from composable_sdr_amd import helidecode as H
+    from composable_sdr_amd.app import sdr_process
+    rng = np.random.default_rng(77)
+    rnd = lambda n: "".join(str(b) for b in rng.integers(0, 2, n))  # noqa: E731
+    body = helilink.message_bits(lead=0)
+    bs = rnd(1500) + body + rnd(200)
+    # precondition: the ideal +-1 stream of these bits decodes to 40 of 40
+    ideal = [H.decode(fr) for fr in H.frames(H.bits(helilink.stream(bs)))]
+    want = [ln[2:].decode("latin-1") for ln in helilink.LINES]
+    assert ideal == want
+    wav = _write_wav(tmp_path / "helicopter.wav", _fsk_real(bs), "pcm16")
+    n = 4 * len(bs) - 64
+    out = sdr_process(wav, channels=1, demod="nbfmsync", k=4, numsamples=n, outname=str(tmp_path / "output"), chunksize=1024,
+                      samplerate=24000.0, bandwidth=4800.0, offset=1800.0)
+    y = np.fromfile(out[0], dtype=f32)
+    got_bits = H.bits(y)
+    lines = [H.decode(fr) for fr in H.frames(got_bits)]
+    # where the decisions stand against the transmitted bits (best lag), for the report
+    d = np.array([c == "1" for c in got_bits])
+    t = np.array([c == "1" for c in bs])
+    best = min(((int(np.sum(d[1600:1600 + 20000] != t[1600 - lag:1600 - lag + 20000])), lag) for lag in range(0, 64)))
+    print(f"example 6 from WAV: {y.size} outputs, {len(lines)} frames, {sum(a == b for a, b in zip(lines, want))} lines exact; "
+          f"{best[0]} bit errors in 20000 symbols behind symbol 1600 at lag {best[1]}")
+    assert lines == want
+    fixes = H.main([out[0], str(tmp_path)])
+    assert len(fixes) == 39
+    assert open(tmp_path / "output.kml").read().count("<Placemark>") == 39
