@@ -98,6 +98,11 @@ SIGNATURES = {
     "csdr_firhilb_get_taps_len": (_u32, [_vp]),
     "csdr_firhilb_get_taps": (_i32, [_vp, _vp]),
     "csdr_firhilb_destroy": (_i32, [_vp]),
+    "csdr_fskdem_create": (_i32, [_u32, _u32, _f32, _u32, _u32, _pp]),
+    "csdr_fskdem_process": (_i32, [_vp, _vp, _u32, _vp, _vp, _pu32]),
+    "csdr_fskdem_process_device": (_i32, [_vp, _vp, _u32, _vp, _vp, _vp]),
+    "csdr_fskdem_get_design": (_i32, [_vp, _pu32, _vp]),
+    "csdr_fskdem_destroy": (_i32, [_vp]),
     "csdr_chain_cfg_default": (None, [C.POINTER(ChainCfg), _u32]),
     "csdr_chain_create": (_i32, [C.POINTER(ChainCfg), _pp]),
     "csdr_chain_process": (_i32, [_vp, _vp, _u32, _vp, _pu32]),

@@ -942,6 +942,83 @@ int csdr_firhilb_get_taps(const csdr_firhilb *h, float *hq)
 }
 
 // ---------------------------------------------------------------------------
+// fskDemodulator m k bw (Liquid.chs:336-382): fskdem on nchan independent CF32 streams
+// ---------------------------------------------------------------------------
+}  // extern "C"
+struct csdr_fskdem {
+    int device; uint32_t C, max_n; FskdemDesign d;
+    float2 *d_W = nullptr, *d_x = nullptr; uint32_t *d_map = nullptr, *d_sym = nullptr;
+    float *d_e = nullptr;                                   // host-path energies: allocated by the first call that asks for them
+};
+extern "C" {
+int csdr_fskdem_destroy(csdr_fskdem *h)
+{
+    if (!h) return CSDR_OK;
+    DevGuard guard(h->device);
+    (void)hipDeviceSynchronize();
+    void *ptrs[] = {h->d_W, h->d_x, h->d_map, h->d_sym, h->d_e};
+    for (void *p : ptrs) if (p) (void)hipFree(p);
+    delete h;
+    return CSDR_OK;
+}
+int csdr_fskdem_create(uint32_t m, uint32_t k, float bandwidth, uint32_t nchan, uint32_t max_samples, csdr_fskdem **out)
+{
+    if (!out || !nchan || m < 1 || m > FSKDEM_MAX_M || k < 2 || k > FSKDEM_MAX_K || !(bandwidth > 0.f && bandwidth < 0.5f)) {
+        set_error("fskdem: bad arguments (m in [1, %u], k in [2, %u], bandwidth in (0, 0.5), nchan >= 1)", FSKDEM_MAX_M, FSKDEM_MAX_K);
+        return CSDR_ERR_INVALID;
+    }
+    int dev; int r = check_device(-1, &dev); if (r) return r;
+    csdr_fskdem *h = new (std::nothrow) csdr_fskdem();
+    if (!h) return CSDR_ERR_NOMEM;
+    h->device = dev; h->C = nchan; h->max_n = max_samples ? max_samples : 4096;
+    h->d = design_fskdem(m, k, bandwidth);
+    if (h->d.repeated && !getenv("CSDR_QUIET"))
+        fprintf(stderr, "csdr_fskdem_create(%u, %u, %g): warning, the demodulation map is not unique (K = %u); consider a larger bandwidth or k\n",
+                m, k, (double)bandwidth, h->d.K);
+    const size_t C = nchan, n = h->max_n;
+    if ((r = dev_alloc(&h->d_W, h->d.K)) || (r = dev_alloc(&h->d_map, h->d.M)) || (r = dev_alloc(&h->d_x, C * n)) ||
+        (r = dev_alloc(&h->d_sym, C * (n / k)))) { csdr_fskdem_destroy(h); return r; }
+    CSDR_HIP_CLEAN(hipMemcpy(h->d_W, h->d.W.data(), sizeof(float2) * h->d.K, hipMemcpyHostToDevice), csdr_fskdem_destroy(h));
+    CSDR_HIP_CLEAN(hipMemcpy(h->d_map, h->d.map.data(), sizeof(uint32_t) * h->d.M, hipMemcpyHostToDevice), csdr_fskdem_destroy(h));
+    *out = h;
+    return CSDR_OK;
+}
+int csdr_fskdem_process_device(csdr_fskdem *h, const void *d_x, uint32_t n, void *d_sym, void *d_energy, void *stream)
+{
+    if (!h) { set_error("fskdem: null argument"); return CSDR_ERR_INVALID; }
+    if (n > h->max_n) { set_error("fskdem: %u samples > max %u", n, h->max_n); return CSDR_ERR_SIZE; }
+    if (n / h->d.k == 0) return CSDR_OK;
+    if (!d_x || !d_sym) { set_error("fskdem: null buffer"); return CSDR_ERR_INVALID; }
+    const FskdemLaunch l{h->C, n, h->d.k, h->d.K, h->d.M};
+    return launch_fskdem((const float2 *)d_x, (uint32_t *)d_sym, (float *)d_energy, h->d_W, h->d_map, l, (hipStream_t)stream);
+}
+int csdr_fskdem_process(csdr_fskdem *h, const float *x, uint32_t n, uint32_t *sym, float *energy, uint32_t *n_out)
+{
+    if (!h || !n_out) { set_error("fskdem: null argument"); return CSDR_ERR_INVALID; }
+    if (n > h->max_n) { set_error("fskdem: %u samples > max %u", n, h->max_n); return CSDR_ERR_SIZE; }
+    const size_t ns = n / h->d.k, C = h->C;
+    *n_out = (uint32_t)(C * ns);
+    if (!ns) return CSDR_OK;
+    if (!x || !sym) { set_error("fskdem: null buffer"); return CSDR_ERR_INVALID; }
+    DevGuard guard(h->device);
+    if (!guard.ok) { set_error("fskdem: cannot select device %d", h->device); return CSDR_ERR_HIP; }
+    int r;
+    if (energy && !h->d_e && (r = dev_alloc(&h->d_e, C * (h->max_n / h->d.k) * h->d.M))) return r;
+    CSDR_HIP(hipMemcpy(h->d_x, x, sizeof(float2) * C * n, hipMemcpyHostToDevice));
+    if ((r = csdr_fskdem_process_device(h, h->d_x, n, h->d_sym, energy ? h->d_e : nullptr, nullptr))) return r;
+    CSDR_HIP(hipMemcpy(sym, h->d_sym, sizeof(uint32_t) * C * ns, hipMemcpyDeviceToHost));
+    if (energy) CSDR_HIP(hipMemcpy(energy, h->d_e, sizeof(float) * C * ns * h->d.M, hipMemcpyDeviceToHost));
+    return CSDR_OK;
+}
+int csdr_fskdem_get_design(const csdr_fskdem *h, uint32_t *K, uint32_t *demod_map)
+{
+    if (!h) { set_error("fskdem: null argument"); return CSDR_ERR_INVALID; }
+    if (K) *K = h->d.K;
+    if (demod_map) std::memcpy(demod_map, h->d.map.data(), sizeof(uint32_t) * h->d.M);
+    return CSDR_OK;
+}
+
+// ---------------------------------------------------------------------------
 // fused chain
 // ---------------------------------------------------------------------------
 }  // extern "C"

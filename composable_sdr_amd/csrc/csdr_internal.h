@@ -260,6 +260,22 @@ struct FirhilbLaunch {
 // [4 m]: the windows pair-interleaved (w1[j], w0[j]) before and after the call; x and y must not overlap
 int launch_firhilb(bool interp, const float *x, float *y, const float *hist_in, float *hist_out, FirhilbLaunch l, hipStream_t s);
 
+// ---- M-FSK demodulator (kernels_fskdem.hip; design in design.cpp) ----
+constexpr uint32_t FSKDEM_MAX_M = 8;                 // bits per symbol: 2^m tones (this library's limit, not liquid's)
+constexpr uint32_t FSKDEM_MAX_K = 2048;              // samples per symbol (liquid's limit)
+struct FskdemDesign {
+    uint32_t m = 0, k = 0, M = 0, K = 0;             // M = 2^m tones; K: the transform size, k <= K <= max(16, 4 k)
+    std::vector<uint32_t> map;                       // demod_map: the bin of tone i, M entries below K
+    std::vector<float> W;                            // e^{-2 pi i t / K}, t < K, interleaved (re, im)
+    bool repeated = false;                           // two tones share a bin (liquid warns and goes on)
+};
+FskdemDesign design_fskdem(uint32_t m, uint32_t k, float bandwidth);
+struct FskdemLaunch { uint32_t C, n, k, K, M; };
+// x [C][n] CF32 -> sym [C][n / k] uint32 and, when energy != nullptr, energy [C][n / k][M] F32; the n mod k samples at the end
+// of every row are not read.  W [K] and map [M] are the design's arrays on the device
+int launch_fskdem(const float2 *x, uint32_t *sym, float *energy, const float2 *W, const uint32_t *map, const FskdemLaunch &l,
+                  hipStream_t s);
+
 // ---- time-parallel exact AGC [+ freqdem] tail (kernels_agc_tail.hip) ----
 struct AgcTailPlan;
 int agc_tail_create(uint32_t C, uint32_t max_nf, AgcTailPlan **out);

@@ -247,6 +247,44 @@ SymsyncDesign design_symsync_kaiser(uint32_t k, uint32_t m, float beta, uint32_t
     return d;
 }
 
+// ---- fskdem_create(m, k, bandwidth) (Liquid.chs:336-382), DESIGN.md 4.12 ----
+// liquid-dsp 1.3.2 as recalled (unpinned), all of it in f32 as liquid does it: the transform size K is the K_hat in
+// [k, max(16, 4 k)] whose tone spacing 0.5 df K_hat lies nearest an integer (the first of equals; the search stops at the
+// first error below 1e-6), and tone i sits in bin roundf(freq K), a negative one wrapped by + K.  A wrapped index that rounds
+// to K itself (a tone less than half a bin below 0) names bin 0; liquid would read one past its buffer there.
+FskdemDesign design_fskdem(uint32_t m, uint32_t k, float bandwidth)
+{
+    FskdemDesign d;
+    d.m = m; d.k = k; d.M = 1u << m;
+    const float M2 = 0.5f * (float)(d.M - 1);
+    const float df = bandwidth / M2;
+    const uint32_t K_min = k, K_max = 4 * k > 16 ? 4 * k : 16;
+    float err_min = 0.f;
+    d.K = K_min;
+    for (uint32_t K_hat = K_min; K_hat <= K_max; K_hat++) {
+        const float v = 0.5f * df * (float)K_hat;
+        const float err = std::fabs(roundf(v) - v);
+        if (K_hat == K_min || err < err_min) { d.K = K_hat; err_min = err; }
+        if (err < 1e-6f) break;
+    }
+    d.map.resize(d.M);
+    for (uint32_t i = 0; i < d.M; i++) {
+        const float freq = ((float)i - M2) * bandwidth / M2;
+        const float idx = freq * (float)d.K;
+        d.map[i] = (uint32_t)roundf(idx < 0.f ? idx + (float)d.K : idx) % d.K;
+    }
+    for (uint32_t i = 0; i < d.M && !d.repeated; i++)
+        for (uint32_t j = 0; j < i; j++) if (d.map[i] == d.map[j]) { d.repeated = true; break; }
+    // W[t] = e^{-2 pi i t / K}: evaluated in f64, rounded once
+    d.W.resize(2 * (size_t)d.K);
+    for (uint32_t t = 0; t < d.K; t++) {
+        const double a = 2.0 * 3.14159265358979323846 * (double)t / (double)d.K;
+        d.W[2 * t] = (float)std::cos(a);
+        d.W[2 * t + 1] = (float)-std::sin(a);
+    }
+    return d;
+}
+
 uint32_t nco_freq_word(float freq)
 {
     float p = (float)((double)freq * 0.159154943091895);   // freq / 2pi, rounded to f32

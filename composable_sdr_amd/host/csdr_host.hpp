@@ -494,6 +494,33 @@ inline Pipe<std::vector<Array<float>>, std::vector<Array<float>>> symSyncR(uint3
     return p;
 }
 
+// ---- fskDemodulator m k bw (Liquid.chs:336-382) on the channel rows of one chunk: one csdr_fskdem handle with one stream
+// per row; row c of the output holds the n div k symbols of row c, the n mod k samples left over are dropped (:367-376) ----
+inline Pipe<std::vector<Array<cf32>>, std::vector<Array<uint32_t>>> FskDemodulator(uint32_t m, uint32_t k, float bw, uint32_t nchan,
+                                                                                 uint32_t max_in)
+{
+    Pipe<std::vector<Array<cf32>>, std::vector<Array<uint32_t>>> p;
+    p.start = [=]() {
+        csdr_fskdem *h = nullptr;
+        check(csdr_fskdem_create(m, k, bw, nchan, max_in, &h));
+        return std::shared_ptr<void>(h, [](void *q) { csdr_fskdem_destroy(static_cast<csdr_fskdem *>(q)); });
+    };
+    p.process = [nchan, k](void *rr, const std::vector<Array<cf32>> &rows) {
+        if (rows.size() != nchan || rows[0].empty()) return std::vector<Array<uint32_t>>(rows.size());
+        const size_t n = rows[0].size(), ns = n / k;
+        Array<cf32> x(nchan * n);
+        for (uint32_t c = 0; c < nchan; c++) std::copy(rows[c].begin(), rows[c].end(), x.begin() + c * n);
+        Array<uint32_t> sym(nchan * ns);
+        uint32_t n_out = 0;
+        check(csdr_fskdem_process(static_cast<csdr_fskdem *>(rr), reinterpret_cast<const float *>(x.data()), (uint32_t)n, sym.data(), nullptr, &n_out));
+        std::vector<Array<uint32_t>> out;
+        for (uint32_t c = 0; c < nchan; c++) out.emplace_back(sym.begin() + c * ns, sym.begin() + (c + 1) * ns);
+        return out;
+    };
+    p.done = [](void *) {};
+    return p;
+}
+
 // ---- the fused chain as a Pipe (replaces mix . mux (replicate nch demod) . firpfbchChannelizer nc) ----
 struct ChainOpts {
     uint32_t channels = 1; bool dc_block = true; float agc = 0.f; bool fm = false; bool am = false; bool wbfm = false; uint32_t decim = 4; float deemph_fc = 0.025f; float kf = 0.3f; bool mix = false;

@@ -401,6 +401,63 @@ def complexToReal(m=5, as_db=60.0, max_samples=1 << 16):
     return Pipe(lambda: FirHilb(m, as_db, max_samples), lambda r, a: r.interp(a), lambda r: r.close())
 
 
+class FskDem:
+    """The `csdr_fskdem_*` object: fskDemodulator m k bw (Liquid.chs:336-382) on `nchan` independent CF32 streams: M = 2^m
+    tones, k samples per symbol (include/csdr.h, DESIGN.md 4.12).  A call of n samples per row yields n // k symbols per row
+    and drops the last n % k samples; nothing is carried between calls."""
+
+    def __init__(self, m, k, bw, nchan=1, max_samples=1 << 16):
+        h = C.c_void_p()
+        check(lib().csdr_fskdem_create(int(m), int(k), float(bw), int(nchan), int(max_samples), C.byref(h)))
+        self._h = _Handle(h, lib().csdr_fskdem_destroy)
+        self.m, self.k, self.M, self.nchan = int(m), int(k), 1 << int(m), int(nchan)
+
+    @property
+    def h(self):
+        if not self._h.h:
+            raise CsdrError(_lib.ERR_INVALID, "fskdem already destroyed")
+        return self._h.h
+
+    def design(self):
+        """(K, demod_map): the transform size and the bin of each of the M tones"""
+        K = C.c_uint32()
+        dmap = np.empty(self.M, dtype=np.uint32)
+        check(lib().csdr_fskdem_get_design(self.h, C.byref(K), _ptr(dmap)))
+        return K.value, dmap
+
+    def process_rows(self, x, energy=False):
+        """[nchan][n] (or [n]) CF32 -> symbols [nchan][n // k] uint32, or with energy=True (symbols, E [nchan][n // k][M])"""
+        x = _c64(x)
+        n = x.size // self.nchan
+        ns = n // self.k
+        sym = np.empty((self.nchan, ns), dtype=np.uint32)
+        e = np.empty((self.nchan, ns, self.M), dtype=np.float32) if energy else None
+        n_out = C.c_uint32()
+        check(lib().csdr_fskdem_process(self.h, _ptr(x), n, _ptr(sym), _ptr(e) if energy else None, C.byref(n_out)))
+        assert n_out.value == sym.size, (n_out.value, sym.size)
+        return (sym, e) if energy else sym
+
+    def process(self, x):
+        """[nchan][n] -> symbols [nchan][n // k]; [n] -> [n // k]"""
+        sym = self.process_rows(x)
+        return sym[0] if np.ndim(x) == 1 else sym
+
+    def process_device(self, d_x_ptr, n, d_sym_ptr, d_energy_ptr=0, stream=0):
+        """Device-resident variant: raw device pointers (ints) for x [nchan][n] CF32, symbols [nchan][n // k] uint32 and,
+        unless 0, energies [nchan][n // k][M] F32; enqueues on `stream`"""
+        check(lib().csdr_fskdem_process_device(self.h, C.c_void_p(d_x_ptr), n, C.c_void_p(d_sym_ptr),
+                                               C.c_void_p(d_energy_ptr) if d_energy_ptr else None, C.c_void_p(stream)))
+
+    def close(self):
+        self._h.close()
+
+
+def fskDemodulator(m, k, bw, nchan=1, max_samples=1 << 16):
+    """fskDemodulator m k bw (Liquid.chs:378-382) as a Pipe from CF32 arrays ([nchan][n], or [n]) to uint32 symbols
+    ([nchan][n div k], or [n div k]); the n mod k samples left over in a chunk are dropped, as there (Liquid.chs:367-376)"""
+    return Pipe(lambda: FskDem(m, k, bw, nchan, max_samples), lambda r, a: r.process(a), lambda r: r.close())
+
+
 def resampler(r, as_db=60.0, max_samples=1 << 20):
     """resampler r as (Liquid.chs:115-117): Pipe IO (Array CF32) (Array CF32) with a variable-length output
     (`shrinkToFit` to the count msresamp_crcf_execute reports, :79-98).  r == 0 is the identity."""

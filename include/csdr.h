@@ -306,6 +306,38 @@ int csdr_firhilb_get_taps(const csdr_firhilb *h, float *hq);     /* the quadratu
 int csdr_firhilb_destroy(csdr_firhilb *h);
 
 /* ------------------------------------------------------------------------ *
+ * fskDemodulator m k bw  (Liquid.chs:336-382), `nchan` independent CF32 streams: non-coherent M-FSK, M = 2^m tones,
+ * k samples per symbol, tones spread over +- bw.  Replaces fskdem_create(m, k, bw) / fskdem_demodulate per symbol /
+ * fskdem_destroy (imports :338-348) and the energies of fskdem_get_symbol_energy.  liquid-dsp 1.3.2 as recalled:
+ * unpinned.
+ *   design (all f32): M2 = 0.5 (M - 1), df = bw / M2; K = the K_hat in [k, max(16, 4 k)] with the smallest
+ *     |roundf(v) - v|, v = 0.5 df K_hat (the first of equals; the search stops at the first error below 1e-6);
+ *     demod_map[i] = roundf(idx < 0 ? idx + K : idx) mod K, idx = ((i - M2) bw / M2) K.  Two tones may share a bin: as in
+ *     liquid that is a warning on stderr (silenced by CSDR_QUIET in the environment), not an error.
+ *   per symbol of k samples: X[b] = sum_{j < k} x[j] e^{-2 pi i b j / K} (the K-point forward DFT of the zero-padded
+ *     symbol) at the M mapped bins; E[s] = |X[demod_map[s]]|; the symbol is the first s with the largest E
+ *     (s == 0 || E[s] > max so far), so an all-zero symbol gives 0.
+ *   Arithmetic: plain f32 without contraction.  The phasors come from a table W[t] = e^{-2 pi i t / K}, t < K, evaluated
+ *     in f64 and rounded once, indexed by (b j) mod K; a product is four multiplies, one subtraction and one addition;
+ *     each sum starts at +0 and takes j = 0 .. k - 1 in that order; E = sqrtf(re re + im im), correctly rounded.
+ *   Chunk rule (Liquid.chs:367-376: `n div k` symbols, the throw commented out): a call of n samples per row yields
+ *     n / k symbols per row and drops the last n mod k samples of every row.  The handle carries nothing from call to
+ *     call, so a stream cut at symbol boundaries gives the same bits as one call, and any other cut loses the tails.
+ *   Limits (create, else CSDR_ERR_INVALID): m >= 1, k in [2, 2048], 0 < bw < 0.5 (where liquid exits) and m <= 8 (this
+ *     library's).  n > max_samples: CSDR_ERR_SIZE (max_samples 0 means 4096).
+ *   x is [nchan][n] CF32 (what a DeNo chain writes); sym is [nchan][n / k] uint32; energy, when not NULL, is
+ *     [nchan][n / k][M] F32; *n_out = nchan * (n / k).
+ * ------------------------------------------------------------------------ */
+typedef struct csdr_fskdem csdr_fskdem;
+int csdr_fskdem_create(uint32_t m, uint32_t k, float bandwidth, uint32_t nchan, uint32_t max_samples, csdr_fskdem **out);
+int csdr_fskdem_process(csdr_fskdem *h, const float *x_cf32, uint32_t n, uint32_t *sym, float *energy, uint32_t *n_out);
+/* device buffers as above; d_energy may be NULL; enqueued on `stream`, no synchronisation */
+int csdr_fskdem_process_device(csdr_fskdem *h, const void *d_x, uint32_t n, void *d_sym, void *d_energy, void *stream);
+/* K and the M entries of demod_map (either pointer may be NULL) */
+int csdr_fskdem_get_design(const csdr_fskdem *h, uint32_t *K, uint32_t *demod_map);
+int csdr_fskdem_destroy(csdr_fskdem *h);
+
+/* ------------------------------------------------------------------------ *
  * The fused chain: everything assembleFold (apps/SoapySDR.hs:208-226) puts
  * behind `compact`:
  *     dcBlocker                                   (SoapySDR.hs:213-214)
