@@ -103,6 +103,16 @@ SIGNATURES = {
     "csdr_fskdem_process_device": (_i32, [_vp, _vp, _u32, _vp, _vp, _vp]),
     "csdr_fskdem_get_design": (_i32, [_vp, _pu32, _vp]),
     "csdr_fskdem_destroy": (_i32, [_vp]),
+    "csdr_firdes_kaiser": (_i32, [_u32, _f32, _f32, _f32, _vp]),
+    "csdr_fir_groupdelay": (_i32, [_vp, _u32, _f32, _vp]),
+    "csdr_firfilt_create_kaiser": (_i32, [_u32, _f32, _f32, _f32, _i32, _u32, _u32, _pp]),
+    "csdr_firfilt_create_taps": (_i32, [_vp, _u32, _f32, _i32, _u32, _u32, _pp]),
+    "csdr_firfilt_process": (_i32, [_vp, _vp, _u32, _vp]),
+    "csdr_firfilt_process_device": (_i32, [_vp, _vp, _u32, _vp, _vp]),
+    "csdr_firfilt_reset": (_i32, [_vp]),
+    "csdr_firfilt_get_taps_len": (_u32, [_vp]),
+    "csdr_firfilt_get_taps": (_i32, [_vp, _vp, _vp]),
+    "csdr_firfilt_destroy": (_i32, [_vp]),
     "csdr_chain_cfg_default": (None, [C.POINTER(ChainCfg), _u32]),
     "csdr_chain_create": (_i32, [C.POINTER(ChainCfg), _pp]),
     "csdr_chain_process": (_i32, [_vp, _vp, _u32, _vp, _pu32]),

@@ -1019,6 +1019,121 @@ int csdr_fskdem_get_design(const csdr_fskdem *h, uint32_t *K, uint32_t *demod_ma
 }
 
 // ---------------------------------------------------------------------------
+// firFilterCKaiser / firFilterC / firFilterR (Liquid.chs:868-916, 955-957): firfilt_crcf / firfilt_rrrf on nchan independent
+// rows; the two design functions need no GPU
+// ---------------------------------------------------------------------------
+static bool firdes_kaiser_args_ok(uint32_t n, float fc, float as_db, float mu)
+{
+    return n >= 2 && n <= FIRFILT_MAX_LEN && fc > 0.f && fc <= 0.5f && as_db > 0.f && mu == 0.f;
+}
+int csdr_firdes_kaiser(uint32_t n, float fc, float as_db, float mu, float *h)
+{
+    if (!h || !firdes_kaiser_args_ok(n, fc, as_db, mu)) {
+        set_error("firdes_kaiser: bad arguments (n in [2, %u], fc in (0, 0.5], As > 0, mu == 0)", FIRFILT_MAX_LEN);
+        return CSDR_ERR_INVALID;
+    }
+    const std::vector<float> t = design_firfilt_kaiser(n, fc, as_db);
+    std::memcpy(h, t.data(), sizeof(float) * n);
+    return CSDR_OK;
+}
+int csdr_fir_groupdelay(const float *h, uint32_t n, float fc, float *gd)
+{
+    if (!h || !gd || !n || !(fc >= -0.5f && fc <= 0.5f)) { set_error("fir_groupdelay: bad arguments (n >= 1, |fc| <= 0.5)"); return CSDR_ERR_INVALID; }
+    *gd = fir_group_delay(std::vector<float>(h, h + n), fc);
+    return CSDR_OK;
+}
+}  // extern "C"
+struct csdr_firfilt {
+    int device; uint32_t C, max_n, el; bool cplx; std::vector<float> taps; float scale;   // el: bytes per sample
+    float *d_h = nullptr; char *d_hist[2] = {nullptr, nullptr}; int cur = 0;               // [C][L - 1] samples, ping-pong
+    char *d_x = nullptr, *d_y = nullptr;
+    size_t hist_bytes() const { return (size_t)C * (taps.size() - 1) * el; }
+};
+extern "C" {
+int csdr_firfilt_destroy(csdr_firfilt *h)
+{
+    if (!h) return CSDR_OK;
+    DevGuard guard(h->device);
+    (void)hipDeviceSynchronize();
+    void *ptrs[] = {h->d_h, h->d_hist[0], h->d_hist[1], h->d_x, h->d_y};
+    for (void *p : ptrs) if (p) (void)hipFree(p);
+    delete h;
+    return CSDR_OK;
+}
+int csdr_firfilt_create_taps(const float *taps, uint32_t n, float scale, int32_t is_complex, uint32_t nchan, uint32_t max_samples,
+                             csdr_firfilt **out)
+{
+    if (!out || !taps || !nchan || n < 1 || n > FIRFILT_MAX_LEN || max_samples > (1u << 30)) {
+        set_error("firfilt: bad arguments (taps, 1 <= n <= %u, nchan >= 1, max_samples <= 2^30)", FIRFILT_MAX_LEN);
+        return CSDR_ERR_INVALID;
+    }
+    int dev; int r = check_device(-1, &dev); if (r) return r;
+    csdr_firfilt *h = new (std::nothrow) csdr_firfilt();
+    if (!h) return CSDR_ERR_NOMEM;
+    h->device = dev; h->C = nchan; h->max_n = max_samples ? max_samples : 4096; h->cplx = is_complex != 0;
+    h->el = h->cplx ? sizeof(float2) : sizeof(float);
+    h->taps.assign(taps, taps + n); h->scale = scale;
+    const size_t plane = (size_t)nchan * h->max_n * h->el;
+    if ((r = dev_alloc(&h->d_h, n)) || (r = dev_alloc(&h->d_hist[0], h->hist_bytes())) || (r = dev_alloc(&h->d_hist[1], h->hist_bytes())) ||
+        (r = dev_alloc(&h->d_x, plane)) || (r = dev_alloc(&h->d_y, plane))) { csdr_firfilt_destroy(h); return r; }
+    CSDR_HIP_CLEAN(hipMemcpy(h->d_h, taps, sizeof(float) * n, hipMemcpyHostToDevice), csdr_firfilt_destroy(h));
+    if (h->hist_bytes()) CSDR_HIP_CLEAN(hipMemset(h->d_hist[0], 0, h->hist_bytes()), csdr_firfilt_destroy(h));
+    *out = h;
+    return CSDR_OK;
+}
+int csdr_firfilt_create_kaiser(uint32_t n, float fc, float as_db, float mu, int32_t is_complex, uint32_t nchan, uint32_t max_samples,
+                               csdr_firfilt **out)
+{
+    if (!firdes_kaiser_args_ok(n, fc, as_db, mu)) {
+        set_error("firfilt: bad design (n in [2, %u], fc in (0, 0.5], As > 0, mu == 0)", FIRFILT_MAX_LEN);
+        return CSDR_ERR_INVALID;
+    }
+    const std::vector<float> t = design_firfilt_kaiser(n, fc, as_db);
+    return csdr_firfilt_create_taps(t.data(), n, 2.0f * fc, is_complex, nchan, max_samples, out);   // firfilt_crcf_set_scale (2 fc), :893
+}
+int csdr_firfilt_process_device(csdr_firfilt *h, const void *d_x, uint32_t n, void *d_y, void *stream)
+{
+    if (!h) { set_error("firfilt: null argument"); return CSDR_ERR_INVALID; }
+    if (n > h->max_n) { set_error("firfilt: %u samples > max %u", n, h->max_n); return CSDR_ERR_SIZE; }
+    if (!n) return CSDR_OK;
+    if (!d_x || !d_y || d_x == d_y) { set_error("firfilt: null or aliased buffer"); return CSDR_ERR_INVALID; }
+    const FirfiltLaunch l{h->C, n, (uint32_t)h->taps.size(), h->scale};
+    const int r = launch_firfilt(h->cplx, d_x, d_y, h->d_h, h->d_hist[h->cur], h->d_hist[h->cur ^ 1], l, (hipStream_t)stream);
+    if (!r) h->cur ^= 1;
+    return r;
+}
+int csdr_firfilt_process(csdr_firfilt *h, const float *x, uint32_t n, float *y)
+{
+    if (!h || (n && (!x || !y))) { set_error("firfilt: null argument"); return CSDR_ERR_INVALID; }
+    if (n > h->max_n) { set_error("firfilt: %u samples > max %u", n, h->max_n); return CSDR_ERR_SIZE; }
+    if (!n) return CSDR_OK;
+    DevGuard guard(h->device);
+    if (!guard.ok) { set_error("firfilt: cannot select device %d", h->device); return CSDR_ERR_HIP; }
+    const size_t bytes = (size_t)h->C * n * h->el;
+    CSDR_HIP(hipMemcpy(h->d_x, x, bytes, hipMemcpyHostToDevice));
+    const int r = csdr_firfilt_process_device(h, h->d_x, n, h->d_y, nullptr);
+    if (r) return r;
+    CSDR_HIP(hipMemcpy(y, h->d_y, bytes, hipMemcpyDeviceToHost));
+    return CSDR_OK;
+}
+int csdr_firfilt_reset(csdr_firfilt *h)
+{
+    if (!h) return CSDR_ERR_INVALID;
+    DevGuard guard(h->device);
+    CSDR_HIP(hipDeviceSynchronize());
+    if (h->hist_bytes()) CSDR_HIP(hipMemset(h->d_hist[h->cur], 0, h->hist_bytes()));
+    return CSDR_OK;
+}
+uint32_t csdr_firfilt_get_taps_len(const csdr_firfilt *h) { return h ? (uint32_t)h->taps.size() : 0; }
+int csdr_firfilt_get_taps(const csdr_firfilt *h, float *taps, float *scale)
+{
+    if (!h) return CSDR_ERR_INVALID;
+    if (taps) std::memcpy(taps, h->taps.data(), sizeof(float) * h->taps.size());
+    if (scale) *scale = h->scale;
+    return CSDR_OK;
+}
+
+// ---------------------------------------------------------------------------
 // fused chain
 // ---------------------------------------------------------------------------
 }  // extern "C"

@@ -276,6 +276,16 @@ struct FskdemLaunch { uint32_t C, n, k, K, M; };
 int launch_fskdem(const float2 *x, uint32_t *sym, float *energy, const float2 *W, const uint32_t *map, const FskdemLaunch &l,
                   hipStream_t s);
 
+// ---- FIR filter (kernels_firfilt.hip; design in design.cpp) ----
+constexpr uint32_t FIRFILT_MAX_LEN = 2048;           // taps (this library's limit): tile + halo stay below 64 KiB of LDS
+// liquid_firdes_kaiser(n, fc, As, 0): f64, rounded once, window argument 2 t / (n - 1) (the form KAT1 pins); n >= 2
+std::vector<float> design_firfilt_kaiser(uint32_t n, float fc, float As);
+struct FirfiltLaunch { uint32_t C, n, L; float scale; };
+// x [C][n] -> y [C][n] of F32 or (cplx) CF32, y[t] = scale sum_i h[i] x[t - i]; h [L] on the device; hist_in / hist_out
+// [C][L - 1]: the samples in front of the call and behind it (different arrays); x and y must not overlap
+int launch_firfilt(bool cplx, const void *x, void *y, const float *h, const void *hist_in, void *hist_out, const FirfiltLaunch &l,
+                   hipStream_t s);
+
 // ---- time-parallel exact AGC [+ freqdem] tail (kernels_agc_tail.hip) ----
 struct AgcTailPlan;
 int agc_tail_create(uint32_t C, uint32_t max_nf, AgcTailPlan **out);

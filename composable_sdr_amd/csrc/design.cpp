@@ -285,6 +285,15 @@ FskdemDesign design_fskdem(uint32_t m, uint32_t k, float bandwidth)
     return d;
 }
 
+// ---- firfiltCreateCKaiser n fc as mu (Liquid.chs:889-895), csdr_firdes_kaiser; DESIGN.md 4.13 ----
+std::vector<float> design_firfilt_kaiser(uint32_t n, float fc, float As)
+{
+    const std::vector<double> hd = firdes_kaiser(n, (double)fc, (double)As);
+    std::vector<float> h(n);
+    for (uint32_t i = 0; i < n; i++) h[i] = (float)hd[i];
+    return h;
+}
+
 uint32_t nco_freq_word(float freq)
 {
     float p = (float)((double)freq * 0.159154943091895);   // freq / 2pi, rounded to f32

@@ -16,6 +16,7 @@
 //   readFromFile   Source.chs:259-271 raw CF32 chunks of <= n samples
 //   openAudioFile / readFromAudioFile  Source.chs:273-307  a mono WAV / AU file through mixUp pi . realToComplex (FileSource)
 #pragma once
+#include <algorithm>
 #include <complex>
 #include <cstdint>
 #include <cstdio>
@@ -26,6 +27,7 @@
 #include <time.h>
 #include <unistd.h>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/csdr.h"
@@ -519,6 +521,56 @@ inline Pipe<std::vector<Array<cf32>>, std::vector<Array<uint32_t>>> FskDemodulat
     };
     p.done = [](void *) {};
     return p;
+}
+
+// ---- firFilterCKaiser n fc as mu / firFilterC f / firFilterR f (Liquid.chs:868-916, 955-957) on the channel rows of one chunk:
+// one csdr_firfilt handle with one filter state per row; the liquid object f is its taps and scale here.  Rows of one chunk
+// have one length; an empty chunk passes through ----
+namespace detail {
+template <class T> Pipe<std::vector<Array<T>>, std::vector<Array<T>>> firFilterRows(std::function<csdr_firfilt *()> create, uint32_t nchan)
+{
+    Pipe<std::vector<Array<T>>, std::vector<Array<T>>> p;
+    p.start = [=]() { return std::shared_ptr<void>(create(), [](void *q) { csdr_firfilt_destroy(static_cast<csdr_firfilt *>(q)); }); };
+    p.process = [nchan](void *rr, const std::vector<Array<T>> &rows) {
+        if (rows.size() != nchan || rows[0].empty()) return std::vector<Array<T>>(rows.size());
+        const size_t n = rows[0].size();
+        Array<T> x(nchan * n), y(nchan * n);
+        for (uint32_t c = 0; c < nchan; c++) std::copy(rows[c].begin(), rows[c].end(), x.begin() + c * n);
+        check(csdr_firfilt_process(static_cast<csdr_firfilt *>(rr), reinterpret_cast<const float *>(x.data()), (uint32_t)n,
+                                   reinterpret_cast<float *>(y.data())));
+        std::vector<Array<T>> out;
+        for (uint32_t c = 0; c < nchan; c++) out.emplace_back(y.begin() + c * n, y.begin() + (c + 1) * n);
+        return out;
+    };
+    p.done = [](void *) {};
+    return p;
+}
+template <class T> Pipe<std::vector<Array<T>>, std::vector<Array<T>>> firFilterTaps(const Array<float> &taps, float scale, uint32_t nchan,
+                                                                                    uint32_t max_in)
+{
+    return firFilterRows<T>([=]() {
+        csdr_firfilt *h = nullptr;
+        check(csdr_firfilt_create_taps(taps.data(), (uint32_t)taps.size(), scale, std::is_same<T, cf32>::value, nchan, max_in, &h));
+        return h;
+    }, nchan);
+}
+}  // namespace detail
+inline Pipe<std::vector<Array<cf32>>, std::vector<Array<cf32>>> FirFilterC(const Array<float> &taps, float scale, uint32_t nchan, uint32_t max_in)
+{
+    return detail::firFilterTaps<cf32>(taps, scale, nchan, max_in);
+}
+inline Pipe<std::vector<Array<float>>, std::vector<Array<float>>> FirFilterR(const Array<float> &taps, float scale, uint32_t nchan, uint32_t max_in)
+{
+    return detail::firFilterTaps<float>(taps, scale, nchan, max_in);
+}
+inline Pipe<std::vector<Array<cf32>>, std::vector<Array<cf32>>> FirFilterCKaiser(uint32_t n, float fc, float as_db, float mu, uint32_t nchan,
+                                                                                uint32_t max_in)
+{
+    return detail::firFilterRows<cf32>([=]() {
+        csdr_firfilt *h = nullptr;
+        check(csdr_firfilt_create_kaiser(n, fc, as_db, mu, 1, nchan, max_in, &h));
+        return h;
+    }, nchan);
 }
 
 // ---- the fused chain as a Pipe (replaces mix . mux (replicate nch demod) . firpfbchChannelizer nc) ----

@@ -458,6 +458,96 @@ def fskDemodulator(m, k, bw, nchan=1, max_samples=1 << 16):
     return Pipe(lambda: FskDem(m, k, bw, nchan, max_samples), lambda r, a: r.process(a), lambda r: r.close())
 
 
+def firdes_kaiser(n, fc, as_db=60.0):
+    """liquid_firdes_kaiser(n, fc, as_db, 0) (`csdr_firdes_kaiser`): n taps as F32, evaluated in f64 and rounded once.  No GPU needed"""
+    h = np.empty(max(int(n), 0), dtype=np.float32)
+    check(lib().csdr_firdes_kaiser(int(n), float(fc), float(as_db), 0.0, _ptr(h)))
+    return h
+
+
+def fir_groupdelay(h, fc):
+    """firfilt_crcf_groupdelay (Liquid.chs:879) of the taps h at the normalised frequency fc (`csdr_fir_groupdelay`).  No GPU needed"""
+    h = np.ascontiguousarray(h, dtype=np.float32).reshape(-1)
+    gd = C.c_float()
+    check(lib().csdr_fir_groupdelay(_ptr(h), h.size, float(fc), C.byref(gd)))
+    return gd.value
+
+
+class FirFilt:
+    """The `csdr_firfilt_*` object: firfilt_crcf (`is_complex`, CF32 rows) or firfilt_rrrf (F32 rows) with real taps on `nchan`
+    independent rows: y[t] = scale * sum_i taps[i] x[t - i], the last len(taps) - 1 samples of a row carried from call to call
+    (include/csdr.h).  `FirFilt.kaiser` is firfiltCreateCKaiser (Liquid.chs:889-895)."""
+
+    def __init__(self, taps, scale=1.0, is_complex=True, nchan=1, max_samples=1 << 16, _kaiser=None):
+        h = C.c_void_p()
+        if _kaiser is not None:
+            n, fc, as_db, mu = _kaiser
+            check(lib().csdr_firfilt_create_kaiser(int(n), float(fc), float(as_db), float(mu), int(bool(is_complex)), int(nchan),
+                                                   int(max_samples), C.byref(h)))
+        else:
+            t = np.ascontiguousarray(taps, dtype=np.float32).reshape(-1)
+            check(lib().csdr_firfilt_create_taps(_ptr(t), t.size, float(scale), int(bool(is_complex)), int(nchan), int(max_samples),
+                                                 C.byref(h)))
+        self._h = _Handle(h, lib().csdr_firfilt_destroy)
+        self.is_complex, self.nchan = bool(is_complex), int(nchan)
+        self.dtype = np.complex64 if self.is_complex else np.float32
+
+    @classmethod
+    def kaiser(cls, n, fc, as_db=60.0, mu=0.0, is_complex=True, nchan=1, max_samples=1 << 16):
+        """the taps of firdes_kaiser(n, fc, as_db) and the scale 2 fc"""
+        return cls(None, is_complex=is_complex, nchan=nchan, max_samples=max_samples, _kaiser=(n, fc, as_db, mu))
+
+    @property
+    def h(self):
+        if not self._h.h:
+            raise CsdrError(_lib.ERR_INVALID, "firfilt already destroyed")
+        return self._h.h
+
+    @property
+    def taps_len(self):
+        return int(lib().csdr_firfilt_get_taps_len(self.h))
+
+    def taps(self):
+        """(taps F32 [L], scale)"""
+        t = np.empty(self.taps_len, np.float32)
+        s = C.c_float()
+        check(lib().csdr_firfilt_get_taps(self.h, _ptr(t), C.byref(s)))
+        return t, np.float32(s.value)
+
+    def process(self, x):
+        """[nchan][n] -> [nchan][n]; [n] -> [n]"""
+        x = np.ascontiguousarray(x, dtype=self.dtype)
+        y = np.empty_like(x)
+        check(lib().csdr_firfilt_process(self.h, _ptr(x), x.size // self.nchan, _ptr(y)))
+        return y
+
+    def process_device(self, d_x_ptr, n, d_y_ptr, stream=0):
+        """Device-resident variant: raw device pointers (ints) for x and y, [nchan][n] each; enqueues on `stream`"""
+        check(lib().csdr_firfilt_process_device(self.h, C.c_void_p(d_x_ptr), n, C.c_void_p(d_y_ptr), C.c_void_p(stream)))
+
+    def reset(self):
+        check(lib().csdr_firfilt_reset(self.h))
+
+    def close(self):
+        self._h.close()
+
+
+def firFilterCKaiser(n, fc, as_db=60.0, mu=0.0, nchan=1, max_samples=1 << 16):
+    """firFilterCKaiser n fc as mu (Liquid.chs:897-916 over firfiltCreateCKaiser, :889-895) as a Pipe of CF32 arrays
+    ([nchan][n], or [n])"""
+    return Pipe(lambda: FirFilt.kaiser(n, fc, as_db, mu, True, nchan, max_samples), lambda r, a: r.process(a), lambda r: r.close())
+
+
+def firFilterC(taps, scale=1.0, nchan=1, max_samples=1 << 16):
+    """firFilterC f (Liquid.chs:868-887): firfilt_crcf as a Pipe of CF32 arrays; the liquid object f is its taps and scale here"""
+    return Pipe(lambda: FirFilt(taps, scale, True, nchan, max_samples), lambda r, a: r.process(a), lambda r: r.close())
+
+
+def firFilterR(taps, scale=1.0, nchan=1, max_samples=1 << 16):
+    """firFilterR f (Liquid.chs:955-957): firfilt_rrrf as a Pipe of F32 arrays; the liquid object f is its taps and scale here"""
+    return Pipe(lambda: FirFilt(taps, scale, False, nchan, max_samples), lambda r, a: r.process(a), lambda r: r.close())
+
+
 def resampler(r, as_db=60.0, max_samples=1 << 20):
     """resampler r as (Liquid.chs:115-117): Pipe IO (Array CF32) (Array CF32) with a variable-length output
     (`shrinkToFit` to the count msresamp_crcf_execute reports, :79-98).  r == 0 is the identity."""

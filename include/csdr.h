@@ -338,6 +338,43 @@ int csdr_fskdem_get_design(const csdr_fskdem *h, uint32_t *K, uint32_t *demod_ma
 int csdr_fskdem_destroy(csdr_fskdem *h);
 
 /* ------------------------------------------------------------------------ *
+ * firFilterCKaiser n fc as mu / firFilterC f / firFilterR f  (Liquid.chs:868-916, 955-957), `nchan` independent rows of
+ * F32 (firfilt_rrrf) or CF32 (firfilt_crcf) samples, real taps.  Replaces firfilt_crcf_create_kaiser + set_scale (2 fc)
+ * (firfiltCreateCKaiser, :889-895), firfilt_*_execute_block, firfilt_crcf_groupdelay (:879) and liquid_firdes_kaiser.
+ *   filter: L taps h[0 .. L-1], a scale s: y[t] = s * sum_{i < L} h[i] x[t - i].  x[t < 0] is the row's history: the last
+ *     L - 1 samples of earlier calls, zeros after create and after reset.  The scale multiplies the finished dot product, as
+ *     firfilt_*_set_scale has it.
+ *   Arithmetic: plain f32 without contraction, f32 subnormals kept.  Per output acc = +0; for i = 0, 1 .. L - 1 in that
+ *     order acc = acc + h[i] * x[t - i], the product rounded, then the sum; y = s * acc, always multiplied, no tap skipped;
+ *     complex samples: the same on re and im separately.  The result does not depend on the call size, on where a stream
+ *     is cut, on nchan or on host versus device entry, bit for bit.
+ *   csdr_firdes_kaiser (no GPU needed): liquid_firdes_kaiser(n, fc, As, 0): h[i] = sinc(2 fc t) w(i), t = i - (n - 1) / 2,
+ *     w the Kaiser window of beta(As) with the argument 2 t / (n - 1); evaluated in f64 and rounded once (the form the
+ *     known answers of images/ex1_5.gif pin).  CSDR_ERR_INVALID: n < 2, n > 2048, fc outside (0, 0.5], as_db <= 0,
+ *     mu != 0 (every call in the reference passes 0), h NULL.
+ *   csdr_fir_groupdelay (no GPU needed): Re(sum i h[i] e^{j 2 pi fc i} / sum h[i] e^{j 2 pi fc i}), accumulated in f32
+ *     (liquid's fir_group_delay as recalled); CSDR_ERR_INVALID: NULL, n = 0, |fc| > 0.5.
+ *   create_kaiser: the taps of csdr_firdes_kaiser and s = 2 fc, evaluated in f32.  create_taps: the caller's taps
+ *     (copied) and scale; 1 <= n <= 2048 (this library's limit).  is_complex: 0 F32 rows, otherwise CF32 rows.
+ *   process: x and y are [nchan][n]; any n <= max_samples (max_samples 0 means 4096), n = 0 is a no-op; x and y must not
+ *     overlap.  n > max_samples: CSDR_ERR_SIZE; NULL or bad arguments: CSDR_ERR_INVALID; no GPU: CSDR_ERR_NODEV.
+ * ------------------------------------------------------------------------ */
+typedef struct csdr_firfilt csdr_firfilt;
+int csdr_firdes_kaiser(uint32_t n, float fc, float as_db, float mu, float *h);
+int csdr_fir_groupdelay(const float *h, uint32_t n, float fc, float *gd);
+int csdr_firfilt_create_kaiser(uint32_t n, float fc, float as_db, float mu, int32_t is_complex, uint32_t nchan,
+                               uint32_t max_samples, csdr_firfilt **out);
+int csdr_firfilt_create_taps(const float *h, uint32_t n, float scale, int32_t is_complex, uint32_t nchan,
+                             uint32_t max_samples, csdr_firfilt **out);
+int csdr_firfilt_process(csdr_firfilt *h, const float *x, uint32_t n, float *y);
+/* device buffers as above; enqueued on `stream`, no synchronisation */
+int csdr_firfilt_process_device(csdr_firfilt *h, const void *d_x, uint32_t n, void *d_y, void *stream);
+int csdr_firfilt_reset(csdr_firfilt *h);                          /* the history back to zeros                       */
+uint32_t csdr_firfilt_get_taps_len(const csdr_firfilt *h);
+int csdr_firfilt_get_taps(const csdr_firfilt *h, float *taps, float *scale);   /* either pointer may be NULL        */
+int csdr_firfilt_destroy(csdr_firfilt *h);
+
+/* ------------------------------------------------------------------------ *
  * The fused chain: everything assembleFold (apps/SoapySDR.hs:208-226) puts
  * behind `compact`:
  *     dcBlocker                                   (SoapySDR.hs:213-214)
