@@ -10,5 +10,6 @@ from .pipes import (  # noqa: F401
     fmDemodulator, amDemodulator, resampler, iirFilter, firDecimator, wbFMDemodulator, firpfbchChannelizer,
     FmStereo, stereoFMDecoder, SymSync, symSyncR, fmDemWithSync, FirHilb, realToComplex, complexToReal,
     FskDem, fskDemodulator, FirFilt, firFilterCKaiser, firFilterC, firFilterR, firdes_kaiser, fir_groupdelay,
+    IirSos, iirCFilter, iirFilterN, iirFilterSOS, iirdes_butter_lowpass,
 )
 from .trans import compact, takeNArr, mix, mux, distribute_, addPipe  # noqa: F401

@@ -113,6 +113,15 @@ SIGNATURES = {
     "csdr_firfilt_get_taps_len": (_u32, [_vp]),
     "csdr_firfilt_get_taps": (_i32, [_vp, _vp, _vp]),
     "csdr_firfilt_destroy": (_i32, [_vp]),
+    "csdr_iirdes_butter_lowpass": (_i32, [_u32, _f32, _vp, _vp]),
+    "csdr_iirsos_create_prototype": (_i32, [_u32, _f32, _f32, _f32, _f32, _i32, _u32, _u32, _pp]),
+    "csdr_iirsos_create_sos": (_i32, [_vp, _vp, _u32, _i32, _u32, _u32, _pp]),
+    "csdr_iirsos_process": (_i32, [_vp, _vp, _u32, _vp]),
+    "csdr_iirsos_process_device": (_i32, [_vp, _vp, _u32, _vp, _vp]),
+    "csdr_iirsos_reset": (_i32, [_vp]),
+    "csdr_iirsos_get_nsec": (_u32, [_vp]),
+    "csdr_iirsos_get_sos": (_i32, [_vp, _vp, _vp]),
+    "csdr_iirsos_destroy": (_i32, [_vp]),
     "csdr_chain_cfg_default": (None, [C.POINTER(ChainCfg), _u32]),
     "csdr_chain_create": (_i32, [C.POINTER(ChainCfg), _pp]),
     "csdr_chain_process": (_i32, [_vp, _vp, _u32, _vp, _pu32]),

@@ -1134,6 +1134,127 @@ int csdr_firfilt_get_taps(const csdr_firfilt *h, float *taps, float *scale)
 }
 
 // ---------------------------------------------------------------------------
+// iirCFilter n fc f0 ap as (Liquid.chs:594-608) and its F32 and bring-your-own-sections forms: a cascade of second-order
+// sections on nchan independent rows; the design function needs no GPU
+// ---------------------------------------------------------------------------
+static bool iirdes_args_ok(uint32_t order, float fc) { return order >= 1 && order <= IIRSOS_MAX_ORDER && fc > 0.f && fc < 0.5f; }
+int csdr_iirdes_butter_lowpass(uint32_t order, float fc, float *b, float *a)
+{
+    if (!b || !a || !iirdes_args_ok(order, fc)) {
+        set_error("iirdes_butter_lowpass: bad arguments (order in [1, %u], fc in (0, 0.5))", IIRSOS_MAX_ORDER);
+        return CSDR_ERR_INVALID;
+    }
+    design_butter_lowpass_sos(order, fc, b, a);
+    return CSDR_OK;
+}
+}  // extern "C"
+struct csdr_iirsos {
+    int device; uint32_t C, max_n, el; bool cplx; std::vector<float> b, a;                // el: bytes per sample; b, a [3 S], a0 = 1
+    IirSosSection *d_sec = nullptr; char *d_st = nullptr, *d_x = nullptr, *d_y = nullptr;  // d_st [C][S] states of 2 samples
+    uint32_t nsec() const { return (uint32_t)(b.size() / 3); }
+    size_t st_bytes() const { return (size_t)C * nsec() * 2 * el; }
+};
+extern "C" {
+int csdr_iirsos_destroy(csdr_iirsos *h)
+{
+    if (!h) return CSDR_OK;
+    DevGuard guard(h->device);
+    (void)hipDeviceSynchronize();
+    void *ptrs[] = {h->d_sec, h->d_st, h->d_x, h->d_y};
+    for (void *p : ptrs) if (p) (void)hipFree(p);
+    delete h;
+    return CSDR_OK;
+}
+int csdr_iirsos_create_sos(const float *b, const float *a, uint32_t nsec, int32_t is_complex, uint32_t nchan, uint32_t max_samples,
+                           csdr_iirsos **out)
+{
+    if (!out || !b || !a || !nchan || nsec < 1 || nsec > IIRSOS_MAX_SEC || max_samples > (1u << 30)) {
+        set_error("iirsos: bad arguments (b, a, 1 <= nsec <= %u, nchan >= 1, max_samples <= 2^30)", IIRSOS_MAX_SEC);
+        return CSDR_ERR_INVALID;
+    }
+    // every section divided by its a0 (iirfiltsos), then strictly stable: the scan's matrix powers would overflow otherwise
+    std::vector<float> bn(3 * nsec), an(3 * nsec);
+    std::vector<IirSosSection> sec(nsec);
+    for (uint32_t s = 0; s < nsec; s++) {
+        const float a0 = a[3 * s];
+        if (!(a0 != 0.f) || !std::isfinite(a0)) { set_error("iirsos: section %u has a0 = %g", s, (double)a0); return CSDR_ERR_INVALID; }
+        for (int i = 0; i < 3; i++) { bn[3 * s + i] = b[3 * s + i] / a0; an[3 * s + i] = a[3 * s + i] / a0; }
+        an[3 * s] = 1.f;
+        const double a1 = an[3 * s + 1], a2 = an[3 * s + 2];
+        const bool finite = std::isfinite(bn[3 * s]) && std::isfinite(bn[3 * s + 1]) && std::isfinite(bn[3 * s + 2]);
+        if (!finite || !(std::fabs(a2) < 1.0) || !(std::fabs(a1) < 1.0 + a2)) {
+            set_error("iirsos: section %u is not strictly stable or not finite (needs |a2| < 1 and |a1| < 1 + a2; a1 = %g, a2 = %g)", s, a1, a2);
+            return CSDR_ERR_INVALID;
+        }
+        sec[s] = make_iirsos_section(&bn[3 * s], an[3 * s + 1], an[3 * s + 2]);
+    }
+    int dev; int r = check_device(-1, &dev); if (r) return r;
+    csdr_iirsos *h = new (std::nothrow) csdr_iirsos();
+    if (!h) return CSDR_ERR_NOMEM;
+    h->device = dev; h->C = nchan; h->max_n = max_samples ? max_samples : 4096; h->cplx = is_complex != 0;
+    h->el = h->cplx ? sizeof(float2) : sizeof(float);
+    h->b = bn; h->a = an;
+    const size_t plane = (size_t)nchan * h->max_n * h->el;
+    if ((r = dev_alloc(&h->d_sec, nsec)) || (r = dev_alloc(&h->d_st, h->st_bytes())) || (r = dev_alloc(&h->d_x, plane)) ||
+        (r = dev_alloc(&h->d_y, plane))) { csdr_iirsos_destroy(h); return r; }
+    CSDR_HIP_CLEAN(hipMemcpy(h->d_sec, sec.data(), sizeof(IirSosSection) * nsec, hipMemcpyHostToDevice), csdr_iirsos_destroy(h));
+    CSDR_HIP_CLEAN(hipMemset(h->d_st, 0, h->st_bytes()), csdr_iirsos_destroy(h));
+    *out = h;
+    return CSDR_OK;
+}
+int csdr_iirsos_create_prototype(uint32_t order, float fc, float f0, float ap, float as_db, int32_t is_complex, uint32_t nchan,
+                                 uint32_t max_samples, csdr_iirsos **out)
+{
+    (void)f0; (void)ap; (void)as_db;              // do not enter a Butterworth low-pass; ignored, as csdr_iirfilt_create does
+    if (!iirdes_args_ok(order, fc)) {
+        set_error("iirsos: bad design (order in [1, %u], fc in (0, 0.5))", IIRSOS_MAX_ORDER);
+        return CSDR_ERR_INVALID;
+    }
+    const uint32_t S = (order + 1) / 2;
+    float b[3 * IIRSOS_MAX_SEC], a[3 * IIRSOS_MAX_SEC];
+    design_butter_lowpass_sos(order, fc, b, a);
+    return csdr_iirsos_create_sos(b, a, S, is_complex, nchan, max_samples, out);
+}
+int csdr_iirsos_process_device(csdr_iirsos *h, const void *d_x, uint32_t n, void *d_y, void *stream)
+{
+    if (!h) { set_error("iirsos: null argument"); return CSDR_ERR_INVALID; }
+    if (n > h->max_n) { set_error("iirsos: %u samples > max %u", n, h->max_n); return CSDR_ERR_SIZE; }
+    if (!n) return CSDR_OK;
+    if (!d_x || !d_y) { set_error("iirsos: null buffer"); return CSDR_ERR_INVALID; }
+    return launch_iirsos(h->cplx, d_x, d_y, h->C, n, h->nsec(), h->d_sec, h->d_st, (hipStream_t)stream);
+}
+int csdr_iirsos_process(csdr_iirsos *h, const float *x, uint32_t n, float *y)
+{
+    if (!h || (n && (!x || !y))) { set_error("iirsos: null argument"); return CSDR_ERR_INVALID; }
+    if (n > h->max_n) { set_error("iirsos: %u samples > max %u", n, h->max_n); return CSDR_ERR_SIZE; }
+    if (!n) return CSDR_OK;
+    DevGuard guard(h->device);
+    if (!guard.ok) { set_error("iirsos: cannot select device %d", h->device); return CSDR_ERR_HIP; }
+    const size_t bytes = (size_t)h->C * n * h->el;
+    CSDR_HIP(hipMemcpy(h->d_x, x, bytes, hipMemcpyHostToDevice));
+    const int r = csdr_iirsos_process_device(h, h->d_x, n, h->d_y, nullptr);
+    if (r) return r;
+    CSDR_HIP(hipMemcpy(y, h->d_y, bytes, hipMemcpyDeviceToHost));
+    return CSDR_OK;
+}
+int csdr_iirsos_reset(csdr_iirsos *h)
+{
+    if (!h) return CSDR_ERR_INVALID;
+    DevGuard guard(h->device);
+    CSDR_HIP(hipDeviceSynchronize());
+    CSDR_HIP(hipMemset(h->d_st, 0, h->st_bytes()));
+    return CSDR_OK;
+}
+uint32_t csdr_iirsos_get_nsec(const csdr_iirsos *h) { return h ? h->nsec() : 0; }
+int csdr_iirsos_get_sos(const csdr_iirsos *h, float *b, float *a)
+{
+    if (!h) return CSDR_ERR_INVALID;
+    if (b) std::memcpy(b, h->b.data(), sizeof(float) * h->b.size());
+    if (a) std::memcpy(a, h->a.data(), sizeof(float) * h->a.size());
+    return CSDR_OK;
+}
+
+// ---------------------------------------------------------------------------
 // fused chain
 // ---------------------------------------------------------------------------
 }  // extern "C"

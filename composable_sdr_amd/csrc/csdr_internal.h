@@ -286,6 +286,21 @@ struct FirfiltLaunch { uint32_t C, n, L; float scale; };
 int launch_firfilt(bool cplx, const void *x, void *y, const float *h, const void *hist_in, void *hist_out, const FirfiltLaunch &l,
                    hipStream_t s);
 
+// ---- order-n IIR filter as a cascade of second-order sections (kernels_iirsos.hip; design in design.cpp) ----
+constexpr uint32_t IIRSOS_MAX_SEC = 8, IIRSOS_MAX_ORDER = 2 * IIRSOS_MAX_SEC;
+// Butterworth low-pass of order n (1 .. 16) at fc in (0, 0.5) by the bilinear transform with pre-warping: S = ceil(n / 2) sections
+// b[3 S], a[3 S] with a0 = 1, one per conjugate pole pair (highest Q first), for odd n a first-order section last; every section
+// has unit DC gain.  f64, rounded once
+void design_butter_lowpass_sos(uint32_t n, float fc, float *b, float *a);
+// one section as the kernel reads it: y = b0 x + k1 v1 + k2 v2 on the state before the sample (k1 = b1 - b0 a1, k2 = b2 - b0 a2,
+// from the f32 coefficients in f64, rounded once), pw[k] = A^(16 * 2^k), A = [[-a1, -a2], [1, 0]] row-major
+struct IirSosSection { float b0, k1, k2, a1, a2, pad[3]; double pw[8][4]; };
+IirSosSection make_iirsos_section(const float *b, float a1, float a2);      // b[3] and a1, a2 already divided by a0
+// rows x [C][n] -> y [C][n] of F32 or (cplx) CF32, the same array or disjoint ones; sec [S] and state [C][S] (float2 (v1, v2), for
+// cplx float4 (v1.re, v1.im, v2.re, v2.im)) on the device; the state is read and rewritten in place
+int launch_iirsos(bool cplx, const void *x, void *y, uint32_t C, uint32_t n, uint32_t S, const IirSosSection *sec, void *state,
+                  hipStream_t s);
+
 // ---- time-parallel exact AGC [+ freqdem] tail (kernels_agc_tail.hip) ----
 struct AgcTailPlan;
 int agc_tail_create(uint32_t C, uint32_t max_nf, AgcTailPlan **out);

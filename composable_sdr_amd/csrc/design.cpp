@@ -294,6 +294,51 @@ std::vector<float> design_firfilt_kaiser(uint32_t n, float fc, float As)
     return h;
 }
 
+// ---- iirCFilter n fc f0 ap as (Liquid.chs:594-608), csdr_iirdes_butter_lowpass; DESIGN.md 4.14 ----
+// Analog prototype poles exp(+-j theta_i), theta_i = (2 (i + 1) + n - 1) pi / (2 n), and -1 for odd n; p_d = (1 + m p) / (1 - m p)
+// with m = tan(pi fc); all zeros at -1.  A pair gives A = [1, -2 Re p_d, |p_d|^2], B = g [1, 2, 1]; the real pole A = [1, -p_d, 0],
+// B = g [1, 1, 0].  g makes the section's DC gain one: (1 + a1 + a2) / 4 = |1 - p_d|^2 / 4 = m^2 / |1 - m p|^2 for a pair and
+// (1 - p_d) / 2 = m / (1 + m) for the real pole, taken in the forms that do not cancel
+void design_butter_lowpass_sos(uint32_t n, float fc, float *b, float *a)
+{
+    const double pi = 3.14159265358979323846, m = std::tan(pi * (double)fc);
+    const uint32_t L = n / 2;
+    for (uint32_t i = 0; i < L; i++) {
+        const double theta = (double)(2 * (i + 1) + n - 1) * pi / (double)(2 * n);
+        const double pr = std::cos(theta), pim = std::sin(theta);
+        const double dr = 1.0 - m * pr, di = -m * pim, den = dr * dr + di * di;                 // |1 - m p|^2
+        const double nr = 1.0 + m * pr, ni = m * pim;
+        const double re = (nr * dr + ni * di) / den, mag2 = (nr * nr + ni * ni) / den, g = m * m / den;
+        a[3 * i] = 1.f; a[3 * i + 1] = (float)(-2.0 * re); a[3 * i + 2] = (float)mag2;
+        b[3 * i] = (float)g; b[3 * i + 1] = (float)(2.0 * g); b[3 * i + 2] = (float)g;
+    }
+    if (n & 1) {
+        const double pd = (1.0 - m) / (1.0 + m), g = m / (1.0 + m);
+        a[3 * L] = 1.f; a[3 * L + 1] = (float)(-pd); a[3 * L + 2] = 0.f;
+        b[3 * L] = (float)g; b[3 * L + 1] = (float)g; b[3 * L + 2] = 0.f;
+    }
+}
+
+IirSosSection make_iirsos_section(const float *b, float a1, float a2)
+{
+    IirSosSection q{};
+    q.b0 = b[0]; q.a1 = a1; q.a2 = a2;
+    q.k1 = (float)((double)b[1] - (double)b[0] * (double)a1);
+    q.k2 = (float)((double)b[2] - (double)b[0] * (double)a2);
+    // powers of the state matrix of the f32 coefficients: A^(16), A^(32), ... A^(2048), as design_butter2_lowpass has them
+    auto mul = [](const double *x, const double *y, double *z) {
+        double t[4] = {x[0] * y[0] + x[1] * y[2], x[0] * y[1] + x[1] * y[3], x[2] * y[0] + x[3] * y[2], x[2] * y[1] + x[3] * y[3]};
+        for (int i = 0; i < 4; i++) z[i] = t[i];
+    };
+    double P[4] = {-(double)a1, -(double)a2, 1.0, 0.0};
+    for (int i = 0; i < 4; i++) mul(P, P, P);
+    for (int k = 0; k < 8; k++) {
+        for (int i = 0; i < 4; i++) q.pw[k][i] = P[i];
+        mul(P, P, P);
+    }
+    return q;
+}
+
 uint32_t nco_freq_word(float freq)
 {
     float p = (float)((double)freq * 0.159154943091895);   // freq / 2pi, rounded to f32

@@ -573,6 +573,49 @@ inline Pipe<std::vector<Array<cf32>>, std::vector<Array<cf32>>> FirFilterCKaiser
     }, nchan);
 }
 
+// ---- iirCFilter n fc f0 ap as (Liquid.chs:594-608) and the caller's own second-order sections on the channel rows of one chunk:
+// one csdr_iirsos handle with one state per row and section; a liquid iirfilt object is its sections here (b, a: [S][3] each,
+// row-major).  Rows of one chunk have one length; an empty chunk passes through ----
+namespace detail {
+template <class T> Pipe<std::vector<Array<T>>, std::vector<Array<T>>> iirSosRows(std::function<csdr_iirsos *()> create, uint32_t nchan)
+{
+    Pipe<std::vector<Array<T>>, std::vector<Array<T>>> p;
+    p.start = [=]() { return std::shared_ptr<void>(create(), [](void *q) { csdr_iirsos_destroy(static_cast<csdr_iirsos *>(q)); }); };
+    p.process = [nchan](void *rr, const std::vector<Array<T>> &rows) {
+        if (rows.size() != nchan || rows[0].empty()) return std::vector<Array<T>>(rows.size());
+        const size_t n = rows[0].size();
+        Array<T> x(nchan * n), y(nchan * n);
+        for (uint32_t c = 0; c < nchan; c++) std::copy(rows[c].begin(), rows[c].end(), x.begin() + c * n);
+        check(csdr_iirsos_process(static_cast<csdr_iirsos *>(rr), reinterpret_cast<const float *>(x.data()), (uint32_t)n,
+                                  reinterpret_cast<float *>(y.data())));
+        std::vector<Array<T>> out;
+        for (uint32_t c = 0; c < nchan; c++) out.emplace_back(y.begin() + c * n, y.begin() + (c + 1) * n);
+        return out;
+    };
+    p.done = [](void *) {};
+    return p;
+}
+}  // namespace detail
+inline Pipe<std::vector<Array<cf32>>, std::vector<Array<cf32>>> IirCFilter(uint32_t n, float fc, float f0, float ap, float as_db, uint32_t nchan,
+                                                                          uint32_t max_in)
+{
+    return detail::iirSosRows<cf32>([=]() {
+        csdr_iirsos *h = nullptr;
+        check(csdr_iirsos_create_prototype(n, fc, f0, ap, as_db, 1, nchan, max_in, &h));
+        return h;
+    }, nchan);
+}
+template <class T> Pipe<std::vector<Array<T>>, std::vector<Array<T>>> IirFilterSOS(const Array<float> &b, const Array<float> &a, uint32_t nchan,
+                                                                                   uint32_t max_in)
+{
+    return detail::iirSosRows<T>([=]() {
+        csdr_iirsos *h = nullptr;
+        if (b.size() != a.size() || b.size() % 3) throw std::runtime_error("IirFilterSOS: b and a must hold 3 floats per section each");
+        check(csdr_iirsos_create_sos(b.data(), a.data(), (uint32_t)(b.size() / 3), std::is_same<T, cf32>::value, nchan, max_in, &h));
+        return h;
+    }, nchan);
+}
+
 // ---- the fused chain as a Pipe (replaces mix . mux (replicate nch demod) . firpfbchChannelizer nc) ----
 struct ChainOpts {
     uint32_t channels = 1; bool dc_block = true; float agc = 0.f; bool fm = false; bool am = false; bool wbfm = false; uint32_t decim = 4; float deemph_fc = 0.025f; float kf = 0.3f; bool mix = false;

@@ -548,6 +548,97 @@ def firFilterR(taps, scale=1.0, nchan=1, max_samples=1 << 16):
     return Pipe(lambda: FirFilt(taps, scale, False, nchan, max_samples), lambda r, a: r.process(a), lambda r: r.close())
 
 
+def iirdes_butter_lowpass(n, fc):
+    """Butterworth low-pass of order n (1 .. 16) at fc in (0, 0.5) as second-order sections (`csdr_iirdes_butter_lowpass`):
+    (b, a), F32 [ceil(n / 2)][3] each with a0 = 1, every section of unit DC gain, evaluated in f64 and rounded once.  No GPU
+    needed"""
+    S = (max(int(n), 0) + 1) // 2
+    b, a = np.zeros((S, 3), np.float32), np.zeros((S, 3), np.float32)
+    check(lib().csdr_iirdes_butter_lowpass(int(n), float(fc), _ptr(b), _ptr(a)))
+    return b, a
+
+
+class IirSos:
+    """The `csdr_iirsos_*` object: a cascade of 1 .. 8 second-order sections with real coefficients on `nchan` independent rows
+    of CF32 (`is_complex`, iirfilt_crcf: re and im filtered alike) or F32 samples, every section's state carried from call to
+    call (include/csdr.h, DESIGN.md 4.14).  `IirSos(b, a)` takes the caller's sections ([S][3] each, divided by their a0);
+    `IirSos.prototype` is iirfilt_*_create_prototype(BUTTER, LOWPASS, SOS, n, fc, ..) (Liquid.chs:594-608)."""
+
+    def __init__(self, b, a, is_complex=True, nchan=1, max_samples=1 << 16, _prototype=None):
+        h = C.c_void_p()
+        if _prototype is not None:
+            n, fc, f0, ap, as_db = _prototype
+            check(lib().csdr_iirsos_create_prototype(int(n), float(fc), float(f0), float(ap), float(as_db), int(bool(is_complex)),
+                                                     int(nchan), int(max_samples), C.byref(h)))
+        else:
+            b = np.ascontiguousarray(b, dtype=np.float32).reshape(-1)
+            a = np.ascontiguousarray(a, dtype=np.float32).reshape(-1)
+            if b.size != a.size or b.size % 3:
+                raise CsdrError(_lib.ERR_INVALID, "iirsos: b and a must be [S][3] each")
+            check(lib().csdr_iirsos_create_sos(_ptr(b), _ptr(a), b.size // 3, int(bool(is_complex)), int(nchan), int(max_samples),
+                                               C.byref(h)))
+        self._h = _Handle(h, lib().csdr_iirsos_destroy)
+        self.is_complex, self.nchan = bool(is_complex), int(nchan)
+        self.dtype = np.complex64 if self.is_complex else np.float32
+
+    @classmethod
+    def prototype(cls, n, fc, f0=0.0, ap=10.0, as_db=10.0, is_complex=True, nchan=1, max_samples=1 << 16):
+        """the sections of iirdes_butter_lowpass(n, fc); f0, ap and as_db are accepted and ignored"""
+        return cls(None, None, is_complex=is_complex, nchan=nchan, max_samples=max_samples, _prototype=(n, fc, f0, ap, as_db))
+
+    @property
+    def h(self):
+        if not self._h.h:
+            raise CsdrError(_lib.ERR_INVALID, "iirsos already destroyed")
+        return self._h.h
+
+    @property
+    def nsec(self):
+        return int(lib().csdr_iirsos_get_nsec(self.h))
+
+    def sos(self):
+        """(b, a): F32 [S][3] each, as the handle runs them (a0 = 1)"""
+        S = self.nsec
+        b, a = np.empty((S, 3), np.float32), np.empty((S, 3), np.float32)
+        check(lib().csdr_iirsos_get_sos(self.h, _ptr(b), _ptr(a)))
+        return b, a
+
+    def process(self, x):
+        """[nchan][n] -> [nchan][n]; [n] -> [n]"""
+        x = np.ascontiguousarray(x, dtype=self.dtype)
+        y = np.empty_like(x)
+        check(lib().csdr_iirsos_process(self.h, _ptr(x), x.size // self.nchan, _ptr(y)))
+        return y
+
+    def process_device(self, d_x_ptr, n, d_y_ptr, stream=0):
+        """Device-resident variant: raw device pointers (ints) for x and y, [nchan][n] each (the same buffer or disjoint ones);
+        enqueues on `stream`"""
+        check(lib().csdr_iirsos_process_device(self.h, C.c_void_p(d_x_ptr), n, C.c_void_p(d_y_ptr), C.c_void_p(stream)))
+
+    def reset(self):
+        check(lib().csdr_iirsos_reset(self.h))
+
+    def close(self):
+        self._h.close()
+
+
+def iirCFilter(n, fc, f0=0.0, ap=10.0, as_db=10.0, nchan=1, max_samples=1 << 16):
+    """iirCFilter n fc f0 ap as (Liquid.chs:600-608): order-n Butterworth low-pass (iirfilt_crcf) as a Pipe of CF32 arrays
+    ([nchan][n], or [n])"""
+    return Pipe(lambda: IirSos.prototype(n, fc, f0, ap, as_db, True, nchan, max_samples), lambda r, a: r.process(a), lambda r: r.close())
+
+
+def iirFilterN(n, fc, f0=0.0, ap=10.0, as_db=10.0, nchan=1, max_samples=1 << 16):
+    """iirCFilter's design on F32 arrays for any order 1 .. 16 (`iirFilter` itself stays the order-2 `csdr_iirfilt` object)"""
+    return Pipe(lambda: IirSos.prototype(n, fc, f0, ap, as_db, False, nchan, max_samples), lambda r, a: r.process(a), lambda r: r.close())
+
+
+def iirFilterSOS(b, a, complex=False, nchan=1, max_samples=1 << 16):
+    """The caller's own second-order sections b, a ([S][3] each, S <= 8: a Chebyshev, elliptic or notch design brought from
+    elsewhere) as a Pipe of F32 or (complex) CF32 arrays; a liquid iirfilt object is its sections here"""
+    return Pipe(lambda: IirSos(b, a, complex, nchan, max_samples), lambda r, a_: r.process(a_), lambda r: r.close())
+
+
 def resampler(r, as_db=60.0, max_samples=1 << 20):
     """resampler r as (Liquid.chs:115-117): Pipe IO (Array CF32) (Array CF32) with a variable-length output
     (`shrinkToFit` to the count msresamp_crcf_execute reports, :79-98).  r == 0 is the identity."""

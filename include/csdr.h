@@ -375,6 +375,49 @@ int csdr_firfilt_get_taps(const csdr_firfilt *h, float *taps, float *scale);   /
 int csdr_firfilt_destroy(csdr_firfilt *h);
 
 /* ------------------------------------------------------------------------ *
+ * iirCFilter n fc f0 ap as  (Liquid.chs:594-608) = iirfilt_crcf_create_prototype(BUTTER, LOWPASS, SOS, n, fc, f0, ap, as),
+ * its real-valued form for any order, and the same object made from the caller's own sections: a cascade of S second-order
+ * sections (1 <= S <= 8) with real coefficients on `nchan` independent rows of F32 or CF32 samples.  csdr_iirfilt_* above
+ * (one order-2 section, F32) is unchanged.
+ *   section s: b[3 s .. 3 s + 2], a[3 s .. 3 s + 2] with a0 = 1.  Per sample, direct form II as in csdr_iirfilt:
+ *       v0 = x - a1 v1 - a2 v2;  y = b0 v0 + b1 v1 + b2 v2;  (v1, v2) <- (v0, v1)
+ *     The sections run in order s = 0 .. S - 1, each on the output of the one before.  On CF32 rows the real and the imaginary
+ *     part are filtered alike (iirfilt_crcf).  (v1, v2) of every section and row is zero after create and after reset and is
+ *     carried from call to call.  The result follows the sequential f32 loop up to summation order: the row is evaluated as a
+ *     blocked scan (4096 samples per block, block states combined in f64), so it is not bit-identical to that loop, nor between
+ *     two ways of cutting one stream into calls.  A row is one workgroup's work: nchan = 1 runs on one compute unit.
+ *   csdr_iirdes_butter_lowpass (no GPU needed): Butterworth low-pass of order n, 1 <= n <= 16, cut-off fc in (0, 0.5) cycles per
+ *     sample, S = ceil(n / 2) sections into b[3 S], a[3 S].  Analog poles exp(+-j theta_i), theta_i = (2 (i + 1) + n - 1) pi /
+ *     (2 n) for i < floor(n / 2), and -1 for odd n; bilinear transform with pre-warping m = tan(pi fc): p_d = (1 + m p) /
+ *     (1 - m p), all zeros at -1.  One section per conjugate pair in the order i = 0, 1, .. (highest Q first): a = [1, -2 Re p_d,
+ *     |p_d|^2], b = g [1, 2, 1]; for odd n a first-order section last: a = [1, -p_d, 0], b = g [1, 1, 0].  g gives every
+ *     section unit DC gain (liquid spreads the overall gain over the sections in equal parts: the product is the same).
+ *     Evaluated in f64 and rounded once.  For n = 2 these are csdr_iirfilt's coefficients.
+ *   create_prototype: that design; f0, ap and as_db do not enter a Butterworth low-pass and are ignored, as in
+ *     csdr_iirfilt_create.  create_sos: the caller's nsec sections (copied), each divided by its a0 (iirfiltsos).
+ *     is_complex: 0 F32 rows, otherwise CF32 rows.
+ *   process: x and y are [nchan][n]; any n <= max_samples (max_samples 0 means 4096), n = 0 is a no-op.  process_device: x and y
+ *     may be the same buffer, but must not overlap otherwise.
+ *   CSDR_ERR_INVALID: order 0 or > 16, fc <= 0 or >= 0.5, nsec 0 or > 8, a section with a0 = 0 or one that is not strictly
+ *     stable (needs |a2| < 1 and |a1| < 1 + a2 after the division), nchan 0, NULL arguments; n > max_samples: CSDR_ERR_SIZE;
+ *     no GPU: CSDR_ERR_NODEV.
+ * ------------------------------------------------------------------------ */
+typedef struct csdr_iirsos csdr_iirsos;
+int csdr_iirdes_butter_lowpass(uint32_t order, float fc, float *b, float *a);
+int csdr_iirsos_create_prototype(uint32_t order, float fc, float f0, float ap, float as_db, int32_t is_complex, uint32_t nchan,
+                                 uint32_t max_samples, csdr_iirsos **out);
+int csdr_iirsos_create_sos(const float *b, const float *a, uint32_t nsec, int32_t is_complex, uint32_t nchan,
+                           uint32_t max_samples, csdr_iirsos **out);
+int csdr_iirsos_process(csdr_iirsos *h, const float *x, uint32_t n, float *y);
+/* device buffers as above; enqueued on `stream`, no synchronisation.  d_y may be d_x itself (in place) or must not overlap
+ * it.  The launch goes to the calling thread's current device, which has to be the one the handle was created on */
+int csdr_iirsos_process_device(csdr_iirsos *h, const void *d_x, uint32_t n, void *d_y, void *stream);
+int csdr_iirsos_reset(csdr_iirsos *h);                            /* every section's state back to zero              */
+uint32_t csdr_iirsos_get_nsec(const csdr_iirsos *h);
+int csdr_iirsos_get_sos(const csdr_iirsos *h, float *b, float *a);   /* [3 nsec] each, a0 = 1; either may be NULL      */
+int csdr_iirsos_destroy(csdr_iirsos *h);
+
+/* ------------------------------------------------------------------------ *
  * The fused chain: everything assembleFold (apps/SoapySDR.hs:208-226) puts
  * behind `compact`:
  *     dcBlocker                                   (SoapySDR.hs:213-214)
