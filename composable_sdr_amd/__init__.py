@@ -11,5 +11,6 @@ from .pipes import (  # noqa: F401
     FmStereo, stereoFMDecoder, SymSync, symSyncR, fmDemWithSync, FirHilb, realToComplex, complexToReal,
     FskDem, fskDemodulator, FirFilt, firFilterCKaiser, firFilterC, firFilterR, firdes_kaiser, fir_groupdelay,
     IirSos, iirCFilter, iirFilterN, iirFilterSOS, iirdes_butter_lowpass,
+    GmskDem, gmskDemodulator, firdes_gmsktx, firdes_gmskrx, firFilterRNyquist,
 )
 from .trans import compact, takeNArr, mix, mux, distribute_, addPipe  # noqa: F401

@@ -113,6 +113,14 @@ SIGNATURES = {
     "csdr_firfilt_get_taps_len": (_u32, [_vp]),
     "csdr_firfilt_get_taps": (_i32, [_vp, _vp, _vp]),
     "csdr_firfilt_destroy": (_i32, [_vp]),
+    "csdr_firdes_gmsktx": (_i32, [_u32, _u32, _f32, _vp]),
+    "csdr_firdes_gmskrx": (_i32, [_u32, _u32, _f32, _vp]),
+    "csdr_gmskdem_create": (_i32, [_u32, _u32, _f32, _u32, _u32, _pp]),
+    "csdr_gmskdem_process": (_i32, [_vp, _vp, _u32, _vp, _vp, _pu32]),
+    "csdr_gmskdem_process_device": (_i32, [_vp, _vp, _u32, _vp, _vp, _vp]),
+    "csdr_gmskdem_reset": (_i32, [_vp]),
+    "csdr_gmskdem_get_design": (_i32, [_vp, _pu32, _vp]),
+    "csdr_gmskdem_destroy": (_i32, [_vp]),
     "csdr_iirdes_butter_lowpass": (_i32, [_u32, _f32, _vp, _vp]),
     "csdr_iirsos_create_prototype": (_i32, [_u32, _f32, _f32, _f32, _f32, _i32, _u32, _u32, _pp]),
     "csdr_iirsos_create_sos": (_i32, [_vp, _vp, _u32, _i32, _u32, _u32, _pp]),

@@ -1134,6 +1134,113 @@ int csdr_firfilt_get_taps(const csdr_firfilt *h, float *taps, float *scale)
 }
 
 // ---------------------------------------------------------------------------
+// gmskDemodulator m k bw (Liquid.chs:384-429): gmskdem on nchan independent CF32 streams; the two design
+// functions need no GPU
+// ---------------------------------------------------------------------------
+static int firdes_gmsk(const char *name, bool rx, uint32_t k, uint32_t m, float bt, float *h)
+{
+    if (!h || !gmsk_args_ok(k, m, bt)) {
+        set_error("%s: bad arguments (k in [%u, %u], m in [1, %u], BT in [0.2, 1], h)", name, GMSK_MIN_K, GMSK_MAX_K, GMSK_MAX_M);
+        return CSDR_ERR_INVALID;
+    }
+    const std::vector<float> t = rx ? design_gmskrx(k, m, bt) : design_gmsktx(k, m, bt);
+    std::memcpy(h, t.data(), sizeof(float) * t.size());
+    return CSDR_OK;
+}
+int csdr_firdes_gmsktx(uint32_t k, uint32_t m, float bt, float *h) { return firdes_gmsk("firdes_gmsktx", false, k, m, bt, h); }
+int csdr_firdes_gmskrx(uint32_t k, uint32_t m, float bt, float *h) { return firdes_gmsk("firdes_gmskrx", true, k, m, bt, h); }
+}  // extern "C"
+struct csdr_gmskdem {
+    int device; uint32_t C, max_n, k, m; std::vector<float> taps;
+    float *d_h = nullptr; float2 *d_hist[2] = {nullptr, nullptr}; int cur = 0;             // [C][L] samples, ping-pong
+    float2 *d_x = nullptr; uint32_t *d_sym = nullptr;
+    float *d_soft = nullptr;                                // host-path soft values: allocated by the first call that asks for them
+    size_t hist_bytes() const { return sizeof(float2) * C * taps.size(); }
+};
+extern "C" {
+int csdr_gmskdem_destroy(csdr_gmskdem *h)
+{
+    if (!h) return CSDR_OK;
+    DevGuard guard(h->device);
+    (void)hipDeviceSynchronize();
+    void *ptrs[] = {h->d_h, h->d_hist[0], h->d_hist[1], h->d_x, h->d_sym, h->d_soft};
+    for (void *p : ptrs) if (p) (void)hipFree(p);
+    delete h;
+    return CSDR_OK;
+}
+int csdr_gmskdem_create(uint32_t k, uint32_t m, float bt, uint32_t nchan, uint32_t max_samples, csdr_gmskdem **out)
+{
+    if (!out || !nchan || !gmsk_args_ok(k, m, bt) || max_samples > (1u << 30)) {
+        set_error("gmskdem: bad arguments (k in [%u, %u], m in [1, %u], BT in [0.2, 1], nchan >= 1, max_samples <= 2^30)", GMSK_MIN_K,
+                  GMSK_MAX_K, GMSK_MAX_M);
+        return CSDR_ERR_INVALID;
+    }
+    int dev; int r = check_device(-1, &dev); if (r) return r;
+    csdr_gmskdem *h = new (std::nothrow) csdr_gmskdem();
+    if (!h) return CSDR_ERR_NOMEM;
+    h->device = dev; h->C = nchan; h->max_n = max_samples ? max_samples : 4096; h->k = k; h->m = m;
+    h->taps = design_gmskrx(k, m, bt);
+    const size_t C = nchan, n = h->max_n, L = h->taps.size();
+    if ((r = dev_alloc(&h->d_h, L)) || (r = dev_alloc(&h->d_hist[0], C * L)) || (r = dev_alloc(&h->d_hist[1], C * L)) ||
+        (r = dev_alloc(&h->d_x, C * n)) || (r = dev_alloc(&h->d_sym, C * (n / k) + 1))) { csdr_gmskdem_destroy(h); return r; }
+    CSDR_HIP_CLEAN(hipMemcpy(h->d_h, h->taps.data(), sizeof(float) * L, hipMemcpyHostToDevice), csdr_gmskdem_destroy(h));
+    CSDR_HIP_CLEAN(hipMemset(h->d_hist[0], 0, h->hist_bytes()), csdr_gmskdem_destroy(h));
+    *out = h;
+    return CSDR_OK;
+}
+// n has to be a multiple of k (the reference throws, Liquid.chs:421) and at most max_samples; nothing is touched otherwise
+static int gmskdem_check_n(const csdr_gmskdem *h, uint32_t n)
+{
+    if (n % h->k) { set_error("gmskdem: %u samples are not a multiple of k = %u", n, h->k); return CSDR_ERR_SIZE; }
+    if (n > h->max_n) { set_error("gmskdem: %u samples > max %u", n, h->max_n); return CSDR_ERR_SIZE; }
+    return CSDR_OK;
+}
+int csdr_gmskdem_process_device(csdr_gmskdem *h, const void *d_x, uint32_t n, void *d_sym, void *d_soft, void *stream)
+{
+    if (!h) { set_error("gmskdem: null argument"); return CSDR_ERR_INVALID; }
+    int r = gmskdem_check_n(h, n); if (r) return r;
+    if (!n) return CSDR_OK;
+    if (!d_x || !d_sym) { set_error("gmskdem: null buffer"); return CSDR_ERR_INVALID; }
+    const GmskdemLaunch l{h->C, n, h->k, h->m, (uint32_t)h->taps.size(), (uint32_t)(0x100000000ull / h->k) + 1u};
+    r = launch_gmskdem((const float2 *)d_x, (uint32_t *)d_sym, (float *)d_soft, h->d_h, h->d_hist[h->cur], h->d_hist[h->cur ^ 1], l,
+                       (hipStream_t)stream);
+    if (!r) h->cur ^= 1;
+    return r;
+}
+int csdr_gmskdem_process(csdr_gmskdem *h, const float *x, uint32_t n, uint32_t *sym, float *soft, uint32_t *n_out)
+{
+    if (!h || !n_out) { set_error("gmskdem: null argument"); return CSDR_ERR_INVALID; }
+    int r = gmskdem_check_n(h, n); if (r) return r;
+    const size_t ns = n / h->k, C = h->C;
+    *n_out = (uint32_t)(C * ns);
+    if (!n) return CSDR_OK;
+    if (!x || !sym) { set_error("gmskdem: null buffer"); return CSDR_ERR_INVALID; }
+    DevGuard guard(h->device);
+    if (!guard.ok) { set_error("gmskdem: cannot select device %d", h->device); return CSDR_ERR_HIP; }
+    if (soft && !h->d_soft && (r = dev_alloc(&h->d_soft, C * (h->max_n / h->k) + 1))) return r;
+    CSDR_HIP(hipMemcpy(h->d_x, x, sizeof(float2) * C * n, hipMemcpyHostToDevice));
+    if ((r = csdr_gmskdem_process_device(h, h->d_x, n, h->d_sym, soft ? h->d_soft : nullptr, nullptr))) return r;
+    CSDR_HIP(hipMemcpy(sym, h->d_sym, sizeof(uint32_t) * C * ns, hipMemcpyDeviceToHost));
+    if (soft) CSDR_HIP(hipMemcpy(soft, h->d_soft, sizeof(float) * C * ns, hipMemcpyDeviceToHost));
+    return CSDR_OK;
+}
+int csdr_gmskdem_reset(csdr_gmskdem *h)
+{
+    if (!h) return CSDR_ERR_INVALID;
+    DevGuard guard(h->device);
+    CSDR_HIP(hipDeviceSynchronize());
+    CSDR_HIP(hipMemset(h->d_hist[h->cur], 0, h->hist_bytes()));
+    return CSDR_OK;
+}
+int csdr_gmskdem_get_design(const csdr_gmskdem *h, uint32_t *taps_len, float *taps)
+{
+    if (!h) { set_error("gmskdem: null argument"); return CSDR_ERR_INVALID; }
+    if (taps_len) *taps_len = (uint32_t)h->taps.size();
+    if (taps) std::memcpy(taps, h->taps.data(), sizeof(float) * h->taps.size());
+    return CSDR_OK;
+}
+
+// ---------------------------------------------------------------------------
 // iirCFilter n fc f0 ap as (Liquid.chs:594-608) and its F32 and bring-your-own-sections forms: a cascade of second-order
 // sections on nchan independent rows; the design function needs no GPU
 // ---------------------------------------------------------------------------

@@ -301,6 +301,23 @@ IirSosSection make_iirsos_section(const float *b, float a1, float a2);      // b
 int launch_iirsos(bool cplx, const void *x, void *y, uint32_t C, uint32_t n, uint32_t S, const IirSosSection *sec, void *state,
                   hipStream_t s);
 
+// ---- GMSK demodulator (kernels_gmskdem.hip; designs in design.cpp) ----
+constexpr uint32_t GMSK_MIN_K = 2, GMSK_MAX_K = 64, GMSK_MAX_M = 8;      // this library's limits: L = 2 k m + 1 <= 1025
+inline bool gmsk_args_ok(uint32_t k, uint32_t m, float bt)
+{
+    return k >= GMSK_MIN_K && k <= GMSK_MAX_K && m >= 1 && m <= GMSK_MAX_M && bt >= 0.2f && bt <= 1.0f;
+}
+// the Gaussian-filtered rectangular frequency pulse, L = 2 k m + 1 taps that sum to one; f64, rounded once
+std::vector<float> design_gmsktx(uint32_t k, uint32_t m, float bt);
+// this library's receive filter: the r of least sum r^2 whose cascade with the pulse is 1 at the centre and 0 at the 2 m other
+// symbol instants of its span; f64, made symmetric, rounded once
+std::vector<float> design_gmskrx(uint32_t k, uint32_t m, float bt);
+struct GmskdemLaunch { uint32_t C, n, k, m, L, kinv; };                  // n a multiple of k; kinv = 2^32 / k + 1
+// x [C][n] CF32 -> sym [C][n / k] uint32 and, when soft != nullptr, soft [C][n / k] F32; h [L] on the device; hist_in / hist_out
+// [C][L]: the samples in front of the call and behind it (different arrays)
+int launch_gmskdem(const float2 *x, uint32_t *sym, float *soft, const float *h, const float2 *hist_in, float2 *hist_out,
+                   const GmskdemLaunch &l, hipStream_t s);
+
 // ---- time-parallel exact AGC [+ freqdem] tail (kernels_agc_tail.hip) ----
 struct AgcTailPlan;
 int agc_tail_create(uint32_t C, uint32_t max_nf, AgcTailPlan **out);

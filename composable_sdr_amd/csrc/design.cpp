@@ -9,6 +9,7 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
+#include <utility>
 
 namespace csdr {
 
@@ -291,6 +292,82 @@ std::vector<float> design_firfilt_kaiser(uint32_t n, float fc, float As)
     const std::vector<double> hd = firdes_kaiser(n, (double)fc, (double)As);
     std::vector<float> h(n);
     for (uint32_t i = 0; i < n; i++) h[i] = (float)hd[i];
+    return h;
+}
+
+// ---- gmskdem_create(k, m, BT) (Liquid.chs:384-429) and firfilt_rrrf_create_rnyquist(GMSKRX, ..) (:935-953), csdr_firdes_gmsktx /
+// csdr_firdes_gmskrx; DESIGN.md 4.15 ----
+// The transmit pulse is the textbook one: a rectangle of one symbol through a Gaussian of bandwidth-time product BT, sampled at
+// t_i = i / k - m: g~_i = Q(c (t_i - 1/2)) - Q(c (t_i + 1/2)), c = 2 pi BT / sqrt(ln 2), Q(x) = erfc(x / sqrt 2) / 2, scaled to
+// sum one (liquid scales to pi / 2 k: that factor is the modulator's business here).
+static std::vector<double> design_gmsktx_f64(uint32_t k, uint32_t m, double bt)
+{
+    const uint32_t L = 2 * k * m + 1;
+    const double c = 2.0 * 3.14159265358979323846 * bt / std::sqrt(std::log(2.0));
+    auto Q = [](double x) { return 0.5 * std::erfc(x / std::sqrt(2.0)); };
+    std::vector<double> g(L);
+    double sum = 0.0;
+    for (uint32_t i = 0; i < L; i++) {
+        const double t = (double)i / (double)k - (double)m;
+        g[i] = Q(c * (t - 0.5)) - Q(c * (t + 0.5));
+        sum += g[i];
+    }
+    for (double &v : g) v /= sum;
+    return g;
+}
+
+std::vector<float> design_gmsktx(uint32_t k, uint32_t m, float bt)
+{
+    const std::vector<double> g = design_gmsktx_f64(k, m, (double)bt);
+    return std::vector<float>(g.begin(), g.end());
+}
+
+// The receive filter is this library's own, not liquid_firdes_gmskrx (whose construction is not pinned): with c = g * r (full
+// convolution, centre L - 1) it asks c[L - 1] = 1 and c[L - 1 + j k] = 0 for 0 < |j| <= m, which is A r = e_m with
+// A[j + m][i] = g[L - 1 + j k - i], and takes the solution of least sum r^2 (least noise gain): r = A^T lambda,
+// (A A^T) lambda = e_m.  The system has order 2 m + 1 <= 17 and a condition number of at most 61 (BT = 0.2): Gaussian
+// elimination with partial pivoting in f64.  r is made symmetric before it is rounded, so the f32 taps are exactly symmetric.
+std::vector<float> design_gmskrx(uint32_t k, uint32_t m, float bt)
+{
+    const std::vector<double> g = design_gmsktx_f64(k, m, (double)bt);
+    const int L = (int)g.size(), R = 2 * (int)m + 1;
+    std::vector<double> A((size_t)R * L, 0.0);
+    for (int j = 0; j < R; j++)
+        for (int i = 0; i < L; i++) {
+            const int idx = L - 1 + (j - (int)m) * (int)k - i;
+            if (idx >= 0 && idx < L) A[(size_t)j * L + i] = g[idx];
+        }
+    std::vector<double> N((size_t)R * R), lam(R, 0.0);
+    for (int a = 0; a < R; a++)
+        for (int b = 0; b < R; b++) {
+            double s = 0.0;
+            for (int i = 0; i < L; i++) s += A[(size_t)a * L + i] * A[(size_t)b * L + i];
+            N[(size_t)a * R + b] = s;
+        }
+    lam[m] = 1.0;
+    for (int p = 0; p < R; p++) {
+        int best = p;
+        for (int a = p + 1; a < R; a++) if (std::fabs(N[(size_t)a * R + p]) > std::fabs(N[(size_t)best * R + p])) best = a;
+        if (best != p) {
+            for (int b = 0; b < R; b++) std::swap(N[(size_t)p * R + b], N[(size_t)best * R + b]);
+            std::swap(lam[p], lam[best]);
+        }
+        for (int a = p + 1; a < R; a++) {
+            const double f = N[(size_t)a * R + p] / N[(size_t)p * R + p];
+            for (int b = p; b < R; b++) N[(size_t)a * R + b] -= f * N[(size_t)p * R + b];
+            lam[a] -= f * lam[p];
+        }
+    }
+    for (int p = R - 1; p >= 0; p--) {
+        double s = lam[p];
+        for (int b = p + 1; b < R; b++) s -= N[(size_t)p * R + b] * lam[b];
+        lam[p] = s / N[(size_t)p * R + p];
+    }
+    std::vector<double> r(L, 0.0);
+    for (int i = 0; i < L; i++)
+        for (int j = 0; j < R; j++) r[i] += A[(size_t)j * L + i] * lam[j];
+    std::vector<float> h(L);
+    for (int i = 0; i < L; i++) h[i] = (float)(0.5 * (r[i] + r[L - 1 - i]));
     return h;
 }
 

@@ -573,6 +573,45 @@ inline Pipe<std::vector<Array<cf32>>, std::vector<Array<cf32>>> FirFilterCKaiser
     }, nchan);
 }
 
+// ---- firFilterRNyquist k m beta mu (Liquid.chs:935-953: LIQUID_FIRFILT_GMSKRX and the scale 1 / k are hard-coded there):
+// FirFilterR on the taps of csdr_firdes_gmskrx(k, m, beta); mu != 0 is refused ----
+inline Pipe<std::vector<Array<float>>, std::vector<Array<float>>> FirFilterRNyquist(uint32_t k, uint32_t m, float beta, float mu, uint32_t nchan,
+                                                                                   uint32_t max_in)
+{
+    if (mu != 0.f) throw std::runtime_error("FirFilterRNyquist: mu != 0 is not supported");
+    Array<float> taps(2 * (size_t)k * m + 1);
+    check(csdr_firdes_gmskrx(k, m, beta, taps.data()));
+    return FirFilterR(taps, 1.0f / (float)k, nchan, max_in);
+}
+
+// ---- gmskDemodulator m k bw (Liquid.chs:384-429; the reference's argument order, gmskdem_create takes k m bw) on the channel
+// rows of one chunk: one csdr_gmskdem handle with one stream per row; row c of the output holds the n / k bits of row c; a row
+// length that is no multiple of k throws, as :421 does ----
+inline Pipe<std::vector<Array<cf32>>, std::vector<Array<uint32_t>>> GmskDemodulator(uint32_t m, uint32_t k, float bw, uint32_t nchan,
+                                                                                  uint32_t max_in)
+{
+    Pipe<std::vector<Array<cf32>>, std::vector<Array<uint32_t>>> p;
+    p.start = [=]() {
+        csdr_gmskdem *h = nullptr;
+        check(csdr_gmskdem_create(k, m, bw, nchan, max_in, &h));
+        return std::shared_ptr<void>(h, [](void *q) { csdr_gmskdem_destroy(static_cast<csdr_gmskdem *>(q)); });
+    };
+    p.process = [nchan, k](void *rr, const std::vector<Array<cf32>> &rows) {
+        if (rows.size() != nchan || rows[0].empty()) return std::vector<Array<uint32_t>>(rows.size());
+        const size_t n = rows[0].size(), ns = n / k;
+        Array<cf32> x(nchan * n);
+        for (uint32_t c = 0; c < nchan; c++) std::copy(rows[c].begin(), rows[c].end(), x.begin() + c * n);
+        Array<uint32_t> sym(nchan * ns);
+        uint32_t n_out = 0;
+        check(csdr_gmskdem_process(static_cast<csdr_gmskdem *>(rr), reinterpret_cast<const float *>(x.data()), (uint32_t)n, sym.data(), nullptr, &n_out));
+        std::vector<Array<uint32_t>> out;
+        for (uint32_t c = 0; c < nchan; c++) out.emplace_back(sym.begin() + c * ns, sym.begin() + (c + 1) * ns);
+        return out;
+    };
+    p.done = [](void *) {};
+    return p;
+}
+
 // ---- iirCFilter n fc f0 ap as (Liquid.chs:594-608) and the caller's own second-order sections on the channel rows of one chunk:
 // one csdr_iirsos handle with one state per row and section; a liquid iirfilt object is its sections here (b, a: [S][3] each,
 // row-major).  Rows of one chunk have one length; an empty chunk passes through ----

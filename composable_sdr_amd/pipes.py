@@ -548,6 +548,97 @@ def firFilterR(taps, scale=1.0, nchan=1, max_samples=1 << 16):
     return Pipe(lambda: FirFilt(taps, scale, False, nchan, max_samples), lambda r, a: r.process(a), lambda r: r.close())
 
 
+def _firdes_gmsk(fn, k, m, bt):
+    k, m = int(k), int(m)
+    h = np.empty(2 * k * m + 1 if 0 < k <= 64 and 0 < m <= 8 else 1, dtype=np.float32)
+    check(fn(k, m, float(bt), _ptr(h)))
+    return h
+
+
+def firdes_gmsktx(k, m, bt):
+    """The GMSK transmit pulse (`csdr_firdes_gmsktx`): a rectangle of one symbol through a Gaussian of bandwidth-time product
+    bt, 2 k m + 1 taps as F32 that sum to one, evaluated in f64 and rounded once.  No GPU needed"""
+    return _firdes_gmsk(lib().csdr_firdes_gmsktx, k, m, bt)
+
+
+def firdes_gmskrx(k, m, bt):
+    """This library's GMSK receive filter (`csdr_firdes_gmskrx`, not liquid_firdes_gmskrx): the 2 k m + 1 taps of least energy
+    whose cascade with firdes_gmsktx(k, m, bt) is 1 at the centre and 0 at the other symbol instants of its span; exactly
+    symmetric F32, evaluated in f64 and rounded once.  No GPU needed"""
+    return _firdes_gmsk(lib().csdr_firdes_gmskrx, k, m, bt)
+
+
+def firFilterRNyquist(k, m, beta, mu=0.0, nchan=1, max_samples=1 << 16):
+    """firFilterRNyquist k m beta mu (Liquid.chs:935-953, which hard-codes LIQUID_FIRFILT_GMSKRX and the scale 1 / k) as a Pipe
+    of F32 arrays: firFilterR(firdes_gmskrx(k, m, beta), 1 / k).  mu != 0 is refused, as in the other designs"""
+    if float(mu) != 0.0:
+        raise CsdrError(_lib.ERR_INVALID, "firFilterRNyquist: mu != 0 is not supported")
+    return firFilterR(firdes_gmskrx(k, m, beta), 1.0 / int(k), nchan, max_samples)
+
+
+class GmskDem:
+    """The `csdr_gmskdem_*` object: gmskdem_create(k, m, bt) (Liquid.chs:384-429; liquid's argument order) on `nchan`
+    independent CF32 streams: k samples per symbol, a receive filter of 2 k m + 1 taps (firdes_gmskrx), one bit per symbol
+    (include/csdr.h, DESIGN.md 4.15).  A call takes a multiple of k samples per row and yields n // k symbols per row; the last
+    2 k m + 1 samples of a row are carried from call to call."""
+
+    def __init__(self, k, m, bt, nchan=1, max_samples=1 << 16):
+        h = C.c_void_p()
+        check(lib().csdr_gmskdem_create(int(k), int(m), float(bt), int(nchan), int(max_samples), C.byref(h)))
+        self._h = _Handle(h, lib().csdr_gmskdem_destroy)
+        self.k, self.m, self.nchan = int(k), int(m), int(nchan)
+
+    @property
+    def h(self):
+        if not self._h.h:
+            raise CsdrError(_lib.ERR_INVALID, "gmskdem already destroyed")
+        return self._h.h
+
+    def design(self):
+        """the receive filter's taps, F32 [2 k m + 1]"""
+        L = C.c_uint32()
+        check(lib().csdr_gmskdem_get_design(self.h, C.byref(L), None))
+        t = np.empty(L.value, dtype=np.float32)
+        check(lib().csdr_gmskdem_get_design(self.h, None, _ptr(t)))
+        return t
+
+    def process_rows(self, x, soft=False):
+        """[nchan][n] (or [n]) CF32 -> symbols [nchan][n // k] uint32, or with soft=True (symbols, d [nchan][n // k] F32)"""
+        x = _c64(x)
+        n = x.size // self.nchan
+        ns = n // self.k
+        sym = np.empty((self.nchan, ns), dtype=np.uint32)
+        d = np.empty((self.nchan, ns), dtype=np.float32) if soft else None
+        n_out = C.c_uint32()
+        check(lib().csdr_gmskdem_process(self.h, _ptr(x), n, _ptr(sym), _ptr(d) if soft else None, C.byref(n_out)))
+        assert n_out.value == sym.size, (n_out.value, sym.size)
+        return (sym, d) if soft else sym
+
+    def process(self, x):
+        """[nchan][n] -> symbols [nchan][n // k]; [n] -> [n // k]"""
+        sym = self.process_rows(x)
+        return sym[0] if np.ndim(x) == 1 else sym
+
+    def process_device(self, d_x_ptr, n, d_sym_ptr, d_soft_ptr=0, stream=0):
+        """Device-resident variant: raw device pointers (ints) for x [nchan][n] CF32, symbols [nchan][n // k] uint32 and,
+        unless 0, soft values [nchan][n // k] F32; enqueues on `stream`"""
+        check(lib().csdr_gmskdem_process_device(self.h, C.c_void_p(d_x_ptr), n, C.c_void_p(d_sym_ptr),
+                                                C.c_void_p(d_soft_ptr) if d_soft_ptr else None, C.c_void_p(stream)))
+
+    def reset(self):
+        check(lib().csdr_gmskdem_reset(self.h))
+
+    def close(self):
+        self._h.close()
+
+
+def gmskDemodulator(m, k, bw, nchan=1, max_samples=1 << 16):
+    """gmskDemodulator m k bw (Liquid.chs:428-429; the reference's argument order, which hands `k m bw` on to gmskdem_create,
+    :409) as a Pipe from CF32 arrays ([nchan][n], or [n]) to uint32 bits ([nchan][n div k], or [n div k]); n not a multiple
+    of k is refused, as there (:421)"""
+    return Pipe(lambda: GmskDem(k, m, bw, nchan, max_samples), lambda r, a: r.process(a), lambda r: r.close())
+
+
 def iirdes_butter_lowpass(n, fc):
     """Butterworth low-pass of order n (1 .. 16) at fc in (0, 0.5) as second-order sections (`csdr_iirdes_butter_lowpass`):
     (b, a), F32 [ceil(n / 2)][3] each with a0 = 1, every section of unit DC gain, evaluated in f64 and rounded once.  No GPU

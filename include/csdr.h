@@ -375,6 +375,45 @@ int csdr_firfilt_get_taps(const csdr_firfilt *h, float *taps, float *scale);   /
 int csdr_firfilt_destroy(csdr_firfilt *h);
 
 /* ------------------------------------------------------------------------ *
+ * gmskDemodulator m k bw  (Liquid.chs:384-429), `nchan` independent CF32 streams: GMSK with k samples per symbol, a filter
+ * delay of m symbols and the bandwidth-time product BT.  Replaces gmskdem_create(k, m, BT) / gmskdem_demodulate per symbol /
+ * gmskdem_destroy (imports :386-396).  The argument order (k, m, bt) is liquid's; the Haskell gmskDemodulator m k bw hands
+ * `k m bw` on (:409).  liquid-dsp 1.3.2's gmskdem as recalled (unpinned) around a receive filter that is this library's own
+ * and pinned by its definition.
+ *   The two designs (no GPU needed), L = 2 k m + 1 taps each, evaluated in f64 and rounded once:
+ *     csdr_firdes_gmsktx: the Gaussian-filtered rectangular frequency pulse.  t_i = i / k - m, c = 2 pi BT / sqrt(ln 2),
+ *       g~_i = Q(c (t_i - 1/2)) - Q(c (t_i + 1/2)), Q(x) = erfc(x / sqrt 2) / 2, g = g~ / sum g~: the taps sum to one
+ *       (liquid scales them to pi / 2 k; that factor is the modulator's here).
+ *     csdr_firdes_gmskrx: NOT liquid_firdes_gmskrx.  The r of least sum r^2 whose cascade with g has no inter-symbol
+ *       interference over its own span: c = g * r (full convolution, centre L - 1), c[L - 1] = 1, c[L - 1 + j k] = 0 for
+ *       0 < |j| <= m.  With A[j + m][i] = g[L - 1 + j k - i] (0 outside [0, L)), g the f64 pulse: (A A^T) lambda = e_m by
+ *       Gaussian elimination with partial pivoting, r = A^T lambda, r_i <- (r_i + r_{L-1-i}) / 2, then rounded: the f32 taps
+ *       are exactly symmetric.
+ *     CSDR_ERR_INVALID: k outside [2, 64], m outside [1, 8], BT outside [0.2, 1] (this library's limits: below 0.2 the
+ *       system degenerates), h NULL.
+ *   demodulator: phi[t] = arg(conj(x[t - 1]) x[t]) as every freqdem of this library computes it (kf = 1 / 2 pi: radians);
+ *     x[t < 0] is the row's history: the last L samples of earlier calls, zeros after create and after reset.  Symbol s of a
+ *     call covers the samples s k .. s k + k - 1; its soft value is d[s] = sum_{i < L} r[i] phi[s k - i], the filter output
+ *     after the symbol's first sample has been pushed, as liquid has it; sym[s] = d[s] > 0 ? 1 : 0.
+ *   Arithmetic: plain f32 without contraction; acc = +0; for i = 0, 1 .. L - 1 in that order acc = acc + r[i] * phi[s k - i],
+ *     the product rounded, then the sum.  The result does not depend on the call size, on nchan, on whether soft is asked
+ *     for or on host versus device entry, bit for bit.
+ *   process: x is [nchan][n] CF32; sym is [nchan][n / k] uint32; soft, when not NULL, is [nchan][n / k] F32; *n_out =
+ *     nchan * (n / k).  n must be a multiple of k (the reference throws, :421): otherwise CSDR_ERR_SIZE with the state
+ *     untouched; n > max_samples: CSDR_ERR_SIZE (max_samples 0 means 4096); n = 0 is a no-op; NULL: CSDR_ERR_INVALID.
+ * ------------------------------------------------------------------------ */
+typedef struct csdr_gmskdem csdr_gmskdem;
+int csdr_firdes_gmsktx(uint32_t k, uint32_t m, float bt, float *h);
+int csdr_firdes_gmskrx(uint32_t k, uint32_t m, float bt, float *h);
+int csdr_gmskdem_create(uint32_t k, uint32_t m, float bt, uint32_t nchan, uint32_t max_samples, csdr_gmskdem **out);
+int csdr_gmskdem_process(csdr_gmskdem *h, const float *x_cf32, uint32_t n, uint32_t *sym, float *soft, uint32_t *n_out);
+/* device buffers as above; d_soft may be NULL; enqueued on `stream`, no synchronisation */
+int csdr_gmskdem_process_device(csdr_gmskdem *h, const void *d_x, uint32_t n, void *d_sym, void *d_soft, void *stream);
+int csdr_gmskdem_reset(csdr_gmskdem *h);                          /* the history back to zeros                       */
+int csdr_gmskdem_get_design(const csdr_gmskdem *h, uint32_t *taps_len, float *taps);   /* either may be NULL         */
+int csdr_gmskdem_destroy(csdr_gmskdem *h);
+
+/* ------------------------------------------------------------------------ *
  * iirCFilter n fc f0 ap as  (Liquid.chs:594-608) = iirfilt_crcf_create_prototype(BUTTER, LOWPASS, SOS, n, fc, f0, ap, as),
  * its real-valued form for any order, and the same object made from the caller's own sections: a cascade of S second-order
  * sections (1 <= S <= 8) with real coefficients on `nchan` independent rows of F32 or CF32 samples.  csdr_iirfilt_* above
