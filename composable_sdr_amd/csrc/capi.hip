@@ -1,8 +1,8 @@
-// C ABI of libcsdr_hip.so (see include/csdr.h).  Handle management, device buffers,
-// stream state, and the per-chunk launch sequences.  Product code: no CPU fallback,
+// C ABI of libcsdr_hip.so (see include/csdr.h): the route table and the chain handle (its device buffers, stream state and
+// per-chunk launch sequences).  The handles of the single blocks are in capi_blocks.hip.  Product code: no CPU fallback,
 // nothing from oracle/.
 #include "../../include/csdr.h"
-#include "csdr_internal.h"
+#include "capi_internal.h"
 #include "fused.h"
 
 #include <cmath>
@@ -14,97 +14,6 @@ namespace csdr {
 const char *last_error();
 }
 using namespace csdr;
-
-// ---------------------------------------------------------------------------
-// small helpers
-// ---------------------------------------------------------------------------
-namespace {
-
-struct DevGuard {
-    int prev = -1; bool ok = true;
-    DevGuard() = default;
-    explicit DevGuard(int dev) { select(dev); }
-    void select(int dev) {
-        if (hipGetDevice(&prev) != hipSuccess) { ok = false; return; }
-        if (dev >= 0 && dev != prev && hipSetDevice(dev) != hipSuccess) ok = false;
-    }
-    ~DevGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
-};
-
-int check_device(int32_t want, int *out_dev)
-{
-    int n = 0;
-    hipError_t e = hipGetDeviceCount(&n);
-    if (e != hipSuccess || n <= 0) {
-        set_error("no HIP device visible (hipGetDeviceCount: %s); libcsdr_hip has no CPU fallback",
-                  e == hipSuccess ? "0 devices" : hipGetErrorString(e));
-        return CSDR_ERR_NODEV;
-    }
-    int dev = want;
-    if (dev < 0) { CSDR_HIP(hipGetDevice(&dev)); }
-    if (dev >= n) { set_error("device %d out of range (%d visible)", dev, n); return CSDR_ERR_INVALID; }
-    *out_dev = dev;
-    return 0;
-}
-
-template <class T> int dev_alloc(T **p, size_t count)
-{
-    *p = nullptr;
-    if (!count) count = 1;
-    CSDR_HIP(hipMalloc((void **)p, count * sizeof(T)));
-    return 0;
-}
-
-DcParams make_dc(float alpha)
-{
-    DcParams d;
-    d.a1 = -1.0f + alpha;                 // iirfilt_crcf_create_dc_blocker
-    d.beta = -d.a1;
-    for (int i = 0; i < 9; i++) d.beta_pow_thr[i] = (float)std::pow((double)d.beta, (double)(DC_PER_THREAD << i));
-    d.beta_blk = std::pow((double)d.beta, (double)DC_BLOCK);
-    d.log2_beta = (float)std::log2((double)d.beta);
-    return d;
-}
-
-}  // namespace
-
-// ---------------------------------------------------------------------------
-// handles
-// ---------------------------------------------------------------------------
-struct csdr_dcblock {
-    int device; uint32_t max_n; DcParams dc;
-    float2 *d_state = nullptr, *d_scratch = nullptr, *d_x = nullptr, *d_y = nullptr;
-};
-struct csdr_nco {
-    int device; uint32_t max_n; uint32_t theta, d_theta;
-    float2 *d_x = nullptr, *d_y = nullptr;
-};
-struct csdr_agc {
-    int device; uint32_t C, max_n; AgcParams p; AgcState *d_st = nullptr; float2 *d_z = nullptr;
-};
-struct csdr_iirfilt {
-    int device; uint32_t C, max_n; BiquadParams p; float2 *d_st[2] = {nullptr, nullptr}; int cur = 0; float *d_x = nullptr;
-};
-struct csdr_firdecim {
-    int device; uint32_t C, max_n, M, h_len; float *d_h = nullptr, *d_hist[2] = {nullptr, nullptr}; int cur = 0;
-    float *d_x = nullptr, *d_y = nullptr;
-};
-struct csdr_resamp {
-    int device; uint32_t max_in; ResampDesign d;
-    // stage s (s < K: half-band decimators; s == K: the arbitrary stage): history-prefixed input buffer
-    std::vector<float2 *> d_buf; std::vector<float *> d_h; std::vector<uint32_t> H; std::vector<uint64_t> n_seen;
-    float *d_pfb = nullptr; float2 *d_out = nullptr;
-    uint64_t t_next = 0;         // Q32.32 absolute time (arbitrary-stage input samples) of the next output
-    bool passthrough = false;    // rate 0: the reference's "no resampler" (Liquid.chs:100-103)
-};
-struct csdr_ampdem {
-    int device; uint32_t C, max_n; float *d_q[2] = {nullptr, nullptr}; int cur = 0;
-    float2 *d_z = nullptr; float *d_f = nullptr;
-};
-struct csdr_freqdem {
-    int device; uint32_t C, max_n; float ref; float2 *d_rp[2] = {nullptr, nullptr}; int cur = 0;
-    float2 *d_z = nullptr; float *d_f = nullptr;
-};
 
 struct csdr_chain {
     csdr_chain_cfg cfg;
@@ -168,7 +77,7 @@ struct csdr_chain {
 };
 
 // a device buffer of the chain: n elements of T (at least one), freed with the handle
-template <class T> static int chain_alloc(csdr_chain *h, T **p, size_t n) { return h->mem.alloc(p, sizeof(T) * (n ? n : 1)); }
+template <class T> static int chain_alloc(csdr_chain *h, T **p, size_t n) { return h->mem.alloc_n(p, n); }
 
 extern "C" {
 
@@ -180,1185 +89,6 @@ int csdr_device_count(void)
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess) return 0;
     return n;
-}
-
-// ---------------------------------------------------------------------------
-// dcBlocker
-// ---------------------------------------------------------------------------
-int csdr_dcblock_create(float alpha, uint32_t max_samples, csdr_dcblock **out)
-{
-    if (!out || !(alpha > 0.f && alpha < 1.f)) { set_error("dcblock: bad arguments"); return CSDR_ERR_INVALID; }
-    int dev; int r = check_device(-1, &dev); if (r) return r;
-    csdr_dcblock *h = new (std::nothrow) csdr_dcblock();
-    if (!h) return CSDR_ERR_NOMEM;
-    h->device = dev; h->max_n = max_samples ? max_samples : 1u << 20; h->dc = make_dc(alpha);
-    if ((r = dev_alloc(&h->d_state, 1)) || (r = dev_alloc(&h->d_scratch, 2 * (size_t)(h->max_n / DC_BLOCK + 2))) ||
-        (r = dev_alloc(&h->d_x, h->max_n)) || (r = dev_alloc(&h->d_y, h->max_n))) { csdr_dcblock_destroy(h); return r; }
-    CSDR_HIP_CLEAN(hipMemset(h->d_state, 0, sizeof(float2)), csdr_dcblock_destroy(h));
-    *out = h;
-    return CSDR_OK;
-}
-
-int csdr_dcblock_process_device(csdr_dcblock *h, const void *d_x, uint32_t n, void *d_y, void *stream)
-{
-    if (!h) { set_error("dcblock: null handle"); return CSDR_ERR_INVALID; }
-    if (n > h->max_n) { set_error("dcblock: %u samples > max %u", n, h->max_n); return CSDR_ERR_SIZE; }
-    NcoParams nco{};
-    return launch_dc_mix((const float2 *)d_x, (float2 *)d_y, n, true, h->dc, h->d_state, h->d_scratch, false, nco,
-                         nullptr, (hipStream_t)stream);
-}
-
-int csdr_dcblock_process(csdr_dcblock *h, const float *x, uint32_t n, float *y)
-{
-    if (!h || (n && (!x || !y))) { set_error("dcblock: null argument"); return CSDR_ERR_INVALID; }
-    if (n > h->max_n) { set_error("dcblock: %u samples > max %u", n, h->max_n); return CSDR_ERR_SIZE; }
-    if (!n) return CSDR_OK;
-    DevGuard guard(h->device);
-    if (!guard.ok) { set_error("dcblock: cannot select device %d", h->device); return CSDR_ERR_HIP; }
-    CSDR_HIP(hipMemcpy(h->d_x, x, sizeof(float2) * n, hipMemcpyHostToDevice));
-    int r = csdr_dcblock_process_device(h, h->d_x, n, h->d_y, nullptr);
-    if (r) return r;
-    CSDR_HIP(hipMemcpy(y, h->d_y, sizeof(float2) * n, hipMemcpyDeviceToHost));
-    return CSDR_OK;
-}
-
-int csdr_dcblock_destroy(csdr_dcblock *h)
-{
-    if (!h) return CSDR_OK;
-    (void)hipFree(h->d_state); (void)hipFree(h->d_scratch); (void)hipFree(h->d_x); (void)hipFree(h->d_y);
-    delete h;
-    return CSDR_OK;
-}
-
-// ---------------------------------------------------------------------------
-// mixDown / mixUp
-// ---------------------------------------------------------------------------
-int csdr_nco_create(float freq, uint32_t max_samples, csdr_nco **out)
-{
-    if (!out || !std::isfinite(freq)) { set_error("nco: bad arguments"); return CSDR_ERR_INVALID; }
-    int dev; int r = check_device(-1, &dev); if (r) return r;
-    csdr_nco *h = new (std::nothrow) csdr_nco();
-    if (!h) return CSDR_ERR_NOMEM;
-    h->device = dev; h->max_n = max_samples ? max_samples : 1u << 20;
-    h->theta = 0; h->d_theta = nco_freq_word(freq);
-    if ((r = dev_alloc(&h->d_x, h->max_n)) || (r = dev_alloc(&h->d_y, h->max_n))) { csdr_nco_destroy(h); return r; }
-    *out = h;
-    return CSDR_OK;
-}
-
-static int nco_mix(csdr_nco *h, const float *x, uint32_t n, float *y, int up)
-{
-    if (!h || (n && (!x || !y))) { set_error("nco: null argument"); return CSDR_ERR_INVALID; }
-    if (n > h->max_n) { set_error("nco: %u samples > max %u", n, h->max_n); return CSDR_ERR_SIZE; }
-    if (!n) return CSDR_OK;
-    DevGuard guard(h->device);
-    if (!guard.ok) { set_error("nco: cannot select device %d", h->device); return CSDR_ERR_HIP; }
-    CSDR_HIP(hipMemcpy(h->d_x, x, sizeof(float2) * n, hipMemcpyHostToDevice));
-    NcoParams nco{}; nco.theta0 = h->theta; nco.d_theta = h->d_theta; nco.up = up;
-    DcParams dc{};
-    int r = launch_dc_mix(h->d_x, h->d_y, n, false, dc, nullptr, nullptr, true, nco, nullptr, nullptr);
-    if (r) return r;
-    CSDR_HIP(hipMemcpy(y, h->d_y, sizeof(float2) * n, hipMemcpyDeviceToHost));
-    h->theta += n * h->d_theta;
-    return CSDR_OK;
-}
-int csdr_nco_mix_down(csdr_nco *h, const float *x, uint32_t n, float *y) { return nco_mix(h, x, n, y, 0); }
-int csdr_nco_mix_up(csdr_nco *h, const float *x, uint32_t n, float *y) { return nco_mix(h, x, n, y, 1); }
-int csdr_nco_get_words(const csdr_nco *h, uint32_t *theta, uint32_t *d_theta)
-{
-    if (!h) return CSDR_ERR_INVALID;
-    if (theta) *theta = h->theta;
-    if (d_theta) *d_theta = h->d_theta;
-    return CSDR_OK;
-}
-int csdr_nco_destroy(csdr_nco *h)
-{
-    if (!h) return CSDR_OK;
-    (void)hipFree(h->d_x); (void)hipFree(h->d_y);
-    delete h;
-    return CSDR_OK;
-}
-
-// ---------------------------------------------------------------------------
-// automaticGainControl (nchan instances)
-// ---------------------------------------------------------------------------
-static AgcParams make_agc(float thr_db)
-{
-    AgcParams p; p.alpha = 0.1f; p.g_thr = agc_gain_threshold(thr_db); p.timeout = 1000u;
-    return p;
-}
-
-int csdr_agc_create(float threshold_db, uint32_t nchan, uint32_t max_samples, csdr_agc **out)
-{
-    if (!out || !nchan || !std::isfinite(threshold_db)) { set_error("agc: bad arguments"); return CSDR_ERR_INVALID; }
-    int dev; int r = check_device(-1, &dev); if (r) return r;
-    csdr_agc *h = new (std::nothrow) csdr_agc();
-    if (!h) return CSDR_ERR_NOMEM;
-    h->device = dev; h->C = nchan; h->max_n = max_samples ? max_samples : 4096; h->p = make_agc(threshold_db);
-    if ((r = dev_alloc(&h->d_st, nchan)) || (r = dev_alloc(&h->d_z, (size_t)nchan * h->max_n))) { csdr_agc_destroy(h); return r; }
-    if ((r = launch_agc_init(h->d_st, nchan, nullptr))) { csdr_agc_destroy(h); return r; }
-    CSDR_HIP(hipDeviceSynchronize());
-    *out = h;
-    return CSDR_OK;
-}
-int csdr_agc_process(csdr_agc *h, const float *x, uint32_t n, float *y)
-{
-    if (!h || (n && (!x || !y))) { set_error("agc: null argument"); return CSDR_ERR_INVALID; }
-    if (n > h->max_n) { set_error("agc: %u samples > max %u", n, h->max_n); return CSDR_ERR_SIZE; }
-    if (!n) return CSDR_OK;
-    DevGuard guard(h->device);
-    if (!guard.ok) { set_error("agc: cannot select device %d", h->device); return CSDR_ERR_HIP; }
-    const size_t bytes = sizeof(float2) * (size_t)h->C * n;
-    CSDR_HIP(hipMemcpy(h->d_z, x, bytes, hipMemcpyHostToDevice));
-    int r = launch_agc(h->d_z, h->C, n, h->d_st, h->p, nullptr);
-    if (r) return r;
-    CSDR_HIP(hipMemcpy(y, h->d_z, bytes, hipMemcpyDeviceToHost));
-    return CSDR_OK;
-}
-int csdr_agc_destroy(csdr_agc *h)
-{
-    if (!h) return CSDR_OK;
-    (void)hipFree(h->d_st); (void)hipFree(h->d_z);
-    delete h;
-    return CSDR_OK;
-}
-
-// ---------------------------------------------------------------------------
-// fmDemodulator (nchan instances)
-// ---------------------------------------------------------------------------
-static float fm_ref_of(float kf) { return (float)(1.0 / (2.0 * 3.14159265358979323846 * (double)kf)); }
-
-int csdr_freqdem_create(float kf, uint32_t nchan, uint32_t max_samples, csdr_freqdem **out)
-{
-    if (!out || !nchan || !(kf > 0.f)) { set_error("freqdem: bad arguments (kf must be > 0)"); return CSDR_ERR_INVALID; }
-    int dev; int r = check_device(-1, &dev); if (r) return r;
-    csdr_freqdem *h = new (std::nothrow) csdr_freqdem();
-    if (!h) return CSDR_ERR_NOMEM;
-    h->device = dev; h->C = nchan; h->max_n = max_samples ? max_samples : 4096; h->ref = fm_ref_of(kf);
-    if ((r = dev_alloc(&h->d_rp[0], nchan)) || (r = dev_alloc(&h->d_rp[1], nchan)) ||
-        (r = dev_alloc(&h->d_z, (size_t)nchan * h->max_n)) || (r = dev_alloc(&h->d_f, (size_t)nchan * h->max_n))) {
-        csdr_freqdem_destroy(h); return r;
-    }
-    CSDR_HIP_CLEAN(hipMemset(h->d_rp[0], 0, sizeof(float2) * nchan), csdr_freqdem_destroy(h));
-    CSDR_HIP_CLEAN(hipMemset(h->d_rp[1], 0, sizeof(float2) * nchan), csdr_freqdem_destroy(h));
-    *out = h;
-    return CSDR_OK;
-}
-int csdr_freqdem_process(csdr_freqdem *h, const float *x, uint32_t n, float *m)
-{
-    if (!h || (n && (!x || !m))) { set_error("freqdem: null argument"); return CSDR_ERR_INVALID; }
-    if (n > h->max_n) { set_error("freqdem: %u samples > max %u", n, h->max_n); return CSDR_ERR_SIZE; }
-    if (!n) return CSDR_OK;
-    DevGuard guard(h->device);
-    if (!guard.ok) { set_error("freqdem: cannot select device %d", h->device); return CSDR_ERR_HIP; }
-    CSDR_HIP(hipMemcpy(h->d_z, x, sizeof(float2) * (size_t)h->C * n, hipMemcpyHostToDevice));
-    int r = launch_fm(h->d_z, h->d_f, h->C, n, h->ref, h->d_rp[h->cur], h->d_rp[h->cur ^ 1], nullptr);
-    if (r) return r;
-    h->cur ^= 1;
-    CSDR_HIP(hipMemcpy(m, h->d_f, sizeof(float) * (size_t)h->C * n, hipMemcpyDeviceToHost));
-    return CSDR_OK;
-}
-int csdr_freqdem_destroy(csdr_freqdem *h)
-{
-    if (!h) return CSDR_OK;
-    (void)hipFree(h->d_rp[0]); (void)hipFree(h->d_rp[1]); (void)hipFree(h->d_z); (void)hipFree(h->d_f);
-    delete h;
-    return CSDR_OK;
-}
-
-// ---------------------------------------------------------------------------
-// iirFilter n fc f0 ap as (Liquid.chs:629-638), firDecimator m (Liquid.chs:485-501)
-// ---------------------------------------------------------------------------
-int csdr_iirfilt_create(uint32_t order, float fc, float f0, float ap, float as_db, uint32_t nchan, uint32_t max_samples, csdr_iirfilt **out)
-{
-    (void)f0; (void)ap; (void)as_db;
-    if (!out || !nchan || !(fc > 0.f && fc < 0.5f)) { set_error("iirfilt: bad arguments (fc in (0, 0.5))"); return CSDR_ERR_INVALID; }
-    if (order != 2) { set_error("iirfilt: only the reference's order-2 Butterworth low-pass is built (order %u)", order); return CSDR_ERR_INVALID; }
-    int dev; int r = check_device(-1, &dev); if (r) return r;
-    csdr_iirfilt *h = new (std::nothrow) csdr_iirfilt();
-    if (!h) return CSDR_ERR_NOMEM;
-    h->device = dev; h->C = nchan; h->max_n = max_samples ? max_samples : 4096; h->p = design_butter2_lowpass(fc);
-    if (hipMalloc(&h->d_x, sizeof(float) * (size_t)nchan * h->max_n) != hipSuccess || hipMalloc(&h->d_st[0], sizeof(float2) * nchan) != hipSuccess ||
-        hipMalloc(&h->d_st[1], sizeof(float2) * nchan) != hipSuccess) { set_error("iirfilt: device allocation failed"); csdr_iirfilt_destroy(h); return CSDR_ERR_HIP; }
-    CSDR_HIP_CLEAN(hipMemset(h->d_st[0], 0, sizeof(float2) * nchan), csdr_iirfilt_destroy(h)); CSDR_HIP_CLEAN(hipMemset(h->d_st[1], 0, sizeof(float2) * nchan), csdr_iirfilt_destroy(h));
-    *out = h;
-    return CSDR_OK;
-}
-int csdr_iirfilt_process(csdr_iirfilt *h, const float *x, uint32_t n, float *y)
-{
-    if (!h || (n && (!x || !y))) { set_error("iirfilt: null argument"); return CSDR_ERR_INVALID; }
-    if (n > h->max_n) { set_error("iirfilt: %u samples > max %u", n, h->max_n); return CSDR_ERR_SIZE; }
-    if (!n) return CSDR_OK;
-    DevGuard guard(h->device);
-    CSDR_HIP(hipMemcpy(h->d_x, x, sizeof(float) * (size_t)h->C * n, hipMemcpyHostToDevice));
-    int r = launch_biquad(h->d_x, h->d_x, h->C, n, h->p, h->d_st[h->cur], h->d_st[h->cur ^ 1], nullptr);
-    if (r) return r;
-    h->cur ^= 1;
-    CSDR_HIP(hipMemcpy(y, h->d_x, sizeof(float) * (size_t)h->C * n, hipMemcpyDeviceToHost));
-    return CSDR_OK;
-}
-int csdr_iirfilt_destroy(csdr_iirfilt *h)
-{
-    if (!h) return CSDR_OK;
-    (void)hipFree(h->d_x); (void)hipFree(h->d_st[0]); (void)hipFree(h->d_st[1]);
-    delete h;
-    return CSDR_OK;
-}
-int csdr_firdecim_create(uint32_t decim, uint32_t nchan, uint32_t max_samples, csdr_firdecim **out)
-{
-    if (!out || !nchan || decim < 1 || decim > 4096) { set_error("firdecim: bad arguments"); return CSDR_ERR_INVALID; }
-    int dev; int r = check_device(-1, &dev); if (r) return r;
-    csdr_firdecim *h = new (std::nothrow) csdr_firdecim();
-    if (!h) return CSDR_ERR_NOMEM;
-    const std::vector<float> taps = design_firdecim_kaiser(decim, 10, 60.0f);          // firdecimCreate, Liquid.chs:485-490
-    h->device = dev; h->C = nchan; h->max_n = max_samples ? max_samples : 4096; h->M = decim; h->h_len = (uint32_t)taps.size();
-    const size_t hist = (size_t)nchan * (h->h_len - 1);
-    if (hipMalloc(&h->d_x, sizeof(float) * (size_t)nchan * h->max_n) != hipSuccess || hipMalloc(&h->d_y, sizeof(float) * (size_t)nchan * (h->max_n / decim + 1)) != hipSuccess ||
-        hipMalloc(&h->d_h, sizeof(float) * taps.size()) != hipSuccess || hipMalloc(&h->d_hist[0], sizeof(float) * hist) != hipSuccess ||
-        hipMalloc(&h->d_hist[1], sizeof(float) * hist) != hipSuccess) { set_error("firdecim: device allocation failed"); csdr_firdecim_destroy(h); return CSDR_ERR_HIP; }
-    CSDR_HIP_CLEAN(hipMemcpy(h->d_h, taps.data(), sizeof(float) * taps.size(), hipMemcpyHostToDevice), csdr_firdecim_destroy(h));
-    CSDR_HIP_CLEAN(hipMemset(h->d_hist[0], 0, sizeof(float) * hist), csdr_firdecim_destroy(h)); CSDR_HIP_CLEAN(hipMemset(h->d_hist[1], 0, sizeof(float) * hist), csdr_firdecim_destroy(h));
-    *out = h;
-    return CSDR_OK;
-}
-int csdr_firdecim_process(csdr_firdecim *h, const float *x, uint32_t n, float *y)
-{
-    if (!h || (n && (!x || !y))) { set_error("firdecim: null argument"); return CSDR_ERR_INVALID; }
-    if (n > h->max_n) { set_error("firdecim: %u samples > max %u", n, h->max_n); return CSDR_ERR_SIZE; }
-    if (n % h->M) { set_error("firdecim: %u samples are not a multiple of the decimation %u (Liquid.chs:495-497)", n, h->M); return CSDR_ERR_SIZE; }
-    if (!n) return CSDR_OK;
-    DevGuard guard(h->device);
-    CSDR_HIP(hipMemcpy(h->d_x, x, sizeof(float) * (size_t)h->C * n, hipMemcpyHostToDevice));
-    int r = launch_firdecim(h->d_x, h->d_y, h->C, n, h->M, h->d_h, h->h_len, h->d_hist[h->cur], h->d_hist[h->cur ^ 1], nullptr);
-    if (r) return r;
-    h->cur ^= 1;
-    CSDR_HIP(hipMemcpy(y, h->d_y, sizeof(float) * (size_t)h->C * (n / h->M), hipMemcpyDeviceToHost));
-    return CSDR_OK;
-}
-int csdr_firdecim_destroy(csdr_firdecim *h)
-{
-    if (!h) return CSDR_OK;
-    (void)hipFree(h->d_x); (void)hipFree(h->d_y); (void)hipFree(h->d_h); (void)hipFree(h->d_hist[0]); (void)hipFree(h->d_hist[1]);
-    delete h;
-    return CSDR_OK;
-}
-
-// ---------------------------------------------------------------------------
-// resampler r as (Liquid.chs:56-117)
-// ---------------------------------------------------------------------------
-int csdr_resamp_create(float rate, float As, uint32_t max_in, csdr_resamp **out)
-{
-    if (!out || rate < 0.f || !(rate == rate)) { set_error("resamp: bad arguments"); return CSDR_ERR_INVALID; }
-    if (rate > 2.0f) { set_error("resamp: rate %g > 2 (interpolating half-band stages are not built)", rate); return CSDR_ERR_INVALID; }
-    int dev; int r = check_device(-1, &dev); if (r) return r;
-    csdr_resamp *h = new (std::nothrow) csdr_resamp();
-    if (!h) return CSDR_ERR_NOMEM;
-    h->device = dev; h->max_in = max_in ? max_in : 4096;
-    if (rate == 0.f) { h->passthrough = true; *out = h; return CSDR_OK; }
-    h->d = design_msresamp(rate, As);
-    const uint32_t K = h->d.K, P = 2 * h->d.m_arb;
-    h->d_buf.assign(K + 1, nullptr); h->d_h.assign(K, nullptr); h->H.assign(K + 1, 0); h->n_seen.assign(K + 1, 0);
-    auto fail = [&](int rc) { csdr_resamp_destroy(h); return rc; };
-    uint32_t cap = h->max_in;
-    for (uint32_t s = 0; s <= K; s++) {
-        h->H[s] = s < K ? 4 * h->d.m_hb[s] + 1 : P + 1;
-        if ((r = dev_alloc(&h->d_buf[s], (size_t)h->H[s] + cap + 2))) return fail(r);
-        CSDR_HIP_CLEAN(hipMemset(h->d_buf[s], 0, sizeof(float2) * ((size_t)h->H[s] + cap + 2)), csdr_resamp_destroy(h));
-        if (s < K) {
-            if (hipMalloc(&h->d_h[s], sizeof(float) * h->d.h_hb[s].size()) != hipSuccess) { set_error("resamp: allocation failed"); return fail(CSDR_ERR_HIP); }
-            CSDR_HIP_CLEAN(hipMemcpy(h->d_h[s], h->d.h_hb[s].data(), sizeof(float) * h->d.h_hb[s].size(), hipMemcpyHostToDevice), csdr_resamp_destroy(h));
-            cap = cap / 2 + 1;
-        }
-    }
-    if (hipMalloc(&h->d_pfb, sizeof(float) * h->d.pfb.size()) != hipSuccess) { set_error("resamp: allocation failed"); return fail(CSDR_ERR_HIP); }
-    CSDR_HIP_CLEAN(hipMemcpy(h->d_pfb, h->d.pfb.data(), sizeof(float) * h->d.pfb.size(), hipMemcpyHostToDevice), csdr_resamp_destroy(h));
-    if ((r = dev_alloc(&h->d_out, (size_t)csdr_resamp_max_out(h, h->max_in)))) return fail(r);
-    if (!getenv("CSDR_QUIET")) {
-        // what msresamp_crcf_print shows in the reference ("Using resampler:", Liquid.chs:105-106)
-        printf("csdr resampler: rate=%g = 2^-%u x %g, half-band taps:", rate, K, h->d.rho);
-        for (uint32_t s = 0; s < K; s++) printf(" %u", 4 * h->d.m_hb[s] + 1);
-        printf(", arbitrary stage: npfb=%u m=%u fc=%g As=%g\n", h->d.npfb, h->d.m_arb, h->d.fc, As);
-        fflush(stdout);
-    }
-    *out = h;
-    return CSDR_OK;
-}
-float csdr_resamp_get_rate(const csdr_resamp *h) { return h ? (h->passthrough ? 1.0f : h->d.rate) : 0.f; }
-uint32_t csdr_resamp_max_out(const csdr_resamp *h, uint32_t n_in)
-{
-    if (!h) return 0;
-    if (h->passthrough) return n_in;
-    return 2u * (uint32_t)std::ceil((double)h->d.rate * n_in) + 2u;      // the reference's 2*ceil(r*nx) (Liquid.chs:81)
-}
-int csdr_resamp_process_device(csdr_resamp *h, const void *d_x, uint32_t n_in, void *d_y, uint32_t *n_out, void *stream)
-{
-    if (!h || !n_out) { set_error("resamp: null argument"); return CSDR_ERR_INVALID; }
-    *n_out = 0;
-    if (!n_in) return CSDR_OK;
-    if (!d_x || !d_y) { set_error("resamp: null buffer"); return CSDR_ERR_INVALID; }
-    if (n_in > h->max_in) { set_error("resamp: %u samples > max %u", n_in, h->max_in); return CSDR_ERR_SIZE; }
-    DevGuard guard(h->device);
-    hipStream_t s = (hipStream_t)stream;
-    if (h->passthrough) {
-        CSDR_HIP(hipMemcpyAsync(d_y, d_x, sizeof(float2) * (size_t)n_in, hipMemcpyDeviceToDevice, s));
-        *n_out = n_in;
-        return CSDR_OK;
-    }
-    const uint32_t K = h->d.K, P = 2 * h->d.m_arb;
-    int r;
-    if ((const void *)(h->d_buf[0] + h->H[0]) != d_x)
-        CSDR_HIP(hipMemcpyAsync(h->d_buf[0] + h->H[0], d_x, sizeof(float2) * (size_t)n_in, hipMemcpyDeviceToDevice, s));
-    uint32_t n = n_in;
-    for (uint32_t st = 0; st < K; st++) {
-        // stage input: absolute samples [N0 - H, N0 + n) sit at buffer positions [0, H + n); output j = sum h[i] x[2j+1-i]
-        const uint64_t N0 = h->n_seen[st], N1 = N0 + n;
-        const uint32_t ny = (uint32_t)(N1 / 2 - N0 / 2);
-        const uint32_t base0 = (uint32_t)((2 * (N0 / 2) + 1) - N0 + h->H[st]);
-        float2 *dst = h->d_buf[st + 1] + h->H[st + 1];
-        if ((r = launch_hb_decim(h->d_buf[st], h->d_h[st], dst, ny, base0, h->d.m_hb[st], s))) return r;
-        if ((r = launch_keep_tail(h->d_buf[st], h->H[st], n, s))) return r;
-        h->n_seen[st] = N1;
-        n = ny;
-    }
-    {
-        const uint64_t N0 = h->n_seen[K], N1 = N0 + n;
-        uint32_t ny = 0;
-        if (N1 >= 2) {
-            // outputs while floor(t) + 1 <= N1 - 1, i.e. t < (N1 - 1) * 2^32
-            const uint64_t lim = (N1 - 1) << 32;
-            if (h->t_next < lim) ny = (uint32_t)((lim - h->t_next + h->d.delta - 1) / h->d.delta);
-        }
-        // buffer position of absolute sample a is a - (N0 - H)
-        const uint64_t t_first = h->t_next - (N0 << 32) + ((uint64_t)h->H[K] << 32);
-        if ((r = launch_resamp_arb(h->d_buf[K], h->d_pfb, (float2 *)d_y, ny, t_first, h->d.delta, h->d.npfb, P, s))) return r;
-        if ((r = launch_keep_tail(h->d_buf[K], h->H[K], n, s))) return r;
-        h->t_next += (uint64_t)ny * h->d.delta;
-        h->n_seen[K] = N1;
-        *n_out = ny;
-    }
-    return CSDR_OK;
-}
-int csdr_resamp_process(csdr_resamp *h, const float *x, uint32_t n_in, float *y, uint32_t *n_out)
-{
-    if (!h || !n_out) { set_error("resamp: null argument"); return CSDR_ERR_INVALID; }
-    *n_out = 0;
-    if (!n_in) return CSDR_OK;
-    if (!x || !y) { set_error("resamp: null buffer"); return CSDR_ERR_INVALID; }
-    if (n_in > h->max_in) { set_error("resamp: %u samples > max %u", n_in, h->max_in); return CSDR_ERR_SIZE; }
-    if (h->passthrough) { memcpy(y, x, sizeof(float2) * (size_t)n_in); *n_out = n_in; return CSDR_OK; }
-    DevGuard guard(h->device);
-    // the first stage's buffer doubles as the H2D landing area
-    float2 *stage0 = h->d_buf[0] + h->H[0];
-    CSDR_HIP(hipMemcpy(stage0, x, sizeof(float2) * (size_t)n_in, hipMemcpyHostToDevice));
-    // process_device copies d_x into the same place: skip that by handing it the landing area itself
-    uint32_t no = 0;
-    int r = csdr_resamp_process_device(h, stage0, n_in, h->d_out, &no, nullptr);
-    if (r) return r;
-    CSDR_HIP(hipMemcpy(y, h->d_out, sizeof(float2) * (size_t)no, hipMemcpyDeviceToHost));
-    *n_out = no;
-    return CSDR_OK;
-}
-int csdr_resamp_destroy(csdr_resamp *h)
-{
-    if (!h) return CSDR_OK;
-    for (float2 *p : h->d_buf) if (p) (void)hipFree(p);
-    for (float *p : h->d_h) if (p) (void)hipFree(p);
-    if (h->d_pfb) (void)hipFree(h->d_pfb);
-    if (h->d_out) (void)hipFree(h->d_out);
-    delete h;
-    return CSDR_OK;
-}
-
-// ---------------------------------------------------------------------------
-// amDemodulator (Liquid.chs:439-469)
-// ---------------------------------------------------------------------------
-int csdr_ampdem_create(float mod_index, uint32_t nchan, uint32_t max_samples, csdr_ampdem **out)
-{
-    if (!out || !nchan || !(mod_index > 0.f)) { set_error("ampdem: bad arguments (mod_index must be > 0)"); return CSDR_ERR_INVALID; }
-    int dev; int r = check_device(-1, &dev); if (r) return r;
-    csdr_ampdem *h = new (std::nothrow) csdr_ampdem();
-    if (!h) return CSDR_ERR_NOMEM;
-    h->device = dev; h->C = nchan; h->max_n = max_samples ? max_samples : 4096;
-    if ((r = dev_alloc(&h->d_z, (size_t)nchan * h->max_n)) || hipMalloc(&h->d_f, sizeof(float) * (size_t)nchan * h->max_n) != hipSuccess ||
-        hipMalloc(&h->d_q[0], sizeof(float) * nchan) != hipSuccess || hipMalloc(&h->d_q[1], sizeof(float) * nchan) != hipSuccess) {
-        set_error("ampdem: device allocation failed");
-        csdr_ampdem_destroy(h); return r ? r : CSDR_ERR_HIP;
-    }
-    CSDR_HIP_CLEAN(hipMemset(h->d_q[0], 0, sizeof(float) * nchan), csdr_ampdem_destroy(h));
-    CSDR_HIP_CLEAN(hipMemset(h->d_q[1], 0, sizeof(float) * nchan), csdr_ampdem_destroy(h));
-    *out = h;
-    return CSDR_OK;
-}
-int csdr_ampdem_process(csdr_ampdem *h, const float *x, uint32_t n, float *m)
-{
-    if (!h || (n && (!x || !m))) { set_error("ampdem: null argument"); return CSDR_ERR_INVALID; }
-    if (n > h->max_n) { set_error("ampdem: %u samples > max %u", n, h->max_n); return CSDR_ERR_SIZE; }
-    if (!n) return CSDR_OK;
-    DevGuard guard(h->device);
-    CSDR_HIP(hipMemcpy(h->d_z, x, sizeof(float2) * (size_t)h->C * n, hipMemcpyHostToDevice));
-    int r = launch_am(h->d_z, h->d_f, h->C, n, h->d_q[h->cur], h->d_q[h->cur ^ 1], 0.01f, nullptr);
-    if (r) return r;
-    h->cur ^= 1;
-    CSDR_HIP(hipMemcpy(m, h->d_f, sizeof(float) * (size_t)h->C * n, hipMemcpyDeviceToHost));
-    return CSDR_OK;
-}
-int csdr_ampdem_destroy(csdr_ampdem *h)
-{
-    if (!h) return CSDR_OK;
-    (void)hipFree(h->d_q[0]); (void)hipFree(h->d_q[1]); (void)hipFree(h->d_z); (void)hipFree(h->d_f);
-    delete h;
-    return CSDR_OK;
-}
-
-// ---------------------------------------------------------------------------
-// stereoFMDecoder quadRate decim (Liquid.chs:959-1078), nchan independent streams
-// ---------------------------------------------------------------------------
-}  // extern "C"
-struct csdr_fmstereo {
-    int device; uint32_t C, max_n, M; FmsDesign f; uint32_t theta = 0; int cur = 0;
-    float *d_hp = nullptr, *d_ha = nullptr, *d_hdec = nullptr, *d_xh[2] = {nullptr, nullptr}, *d_ub[2] = {nullptr, nullptr};
-    float2 *d_p = nullptr, *d_bq = nullptr; float *d_lpr = nullptr, *d_lr = nullptr, *d_dh[2] = {nullptr, nullptr}; uint2 *d_pll = nullptr;
-    float *d_in = nullptr, *d_out = nullptr;
-    hipEvent_t ev[6] = {}; bool timed = false;
-    uint32_t Hx() const { return f.N - 1 + f.d; }
-    uint32_t ustride() const { return f.N - 1 + max_n; }
-};
-static int fms_init_state(csdr_fmstereo *h)
-{
-    const uint32_t C = h->C, Hd = (uint32_t)h->f.h_dec.size() - 1;
-    for (int i = 0; i < 2; i++) {
-        CSDR_HIP(hipMemset(h->d_xh[i], 0, sizeof(float) * (size_t)C * h->Hx()));
-        CSDR_HIP(hipMemset(h->d_ub[i], 0, sizeof(float) * (size_t)C * h->ustride()));
-        CSDR_HIP(hipMemset(h->d_dh[i], 0, sizeof(float) * (size_t)2 * C * Hd));
-    }
-    CSDR_HIP(hipMemset(h->d_bq, 0, sizeof(float2) * 2 * (size_t)C));
-    std::vector<uint2> pll(C, make_uint2(0u, h->f.d_nco));           // ncoPE: theta 0, d_theta = constrain(ncoF)
-    CSDR_HIP(hipMemcpy(h->d_pll, pll.data(), sizeof(uint2) * C, hipMemcpyHostToDevice));
-    h->theta = 0; h->cur = 0;
-    return 0;
-}
-extern "C" {
-int csdr_fmstereo_destroy(csdr_fmstereo *h)
-{
-    if (!h) return CSDR_OK;
-    DevGuard guard(h->device);
-    (void)hipDeviceSynchronize();
-    void *ptrs[] = {h->d_hp, h->d_ha, h->d_hdec, h->d_xh[0], h->d_xh[1], h->d_ub[0], h->d_ub[1], h->d_p, h->d_bq, h->d_lpr, h->d_lr,
-                    h->d_dh[0], h->d_dh[1], h->d_pll, h->d_in, h->d_out};
-    for (void *p : ptrs) if (p) (void)hipFree(p);
-    for (hipEvent_t e : h->ev) if (e) (void)hipEventDestroy(e);
-    delete h;
-    return CSDR_OK;
-}
-int csdr_fmstereo_create(float quad_rate, uint32_t decim, uint32_t nchan, uint32_t max_samples, csdr_fmstereo **out)
-{
-    if (!out || !nchan || decim < 1 || decim > 4096 || !(quad_rate >= 40000.f && quad_rate <= 2.7e6f)) {
-        set_error("fmstereo: bad arguments (quad_rate in [40e3, 2.7e6]: the 19 kHz pilot below Nyquist, FIRs of <= 2000 taps; decim in [1, 4096])");
-        return CSDR_ERR_INVALID;
-    }
-    int dev; int r = check_device(-1, &dev); if (r) return r;
-    csdr_fmstereo *h = new (std::nothrow) csdr_fmstereo();
-    if (!h) return CSDR_ERR_NOMEM;
-    h->device = dev; h->C = nchan; h->max_n = max_samples ? max_samples : 4096; h->M = decim;
-    h->f = design_fmstereo((double)quad_rate, decim);
-    h->timed = diag_env("CSDR_FMS_TIME") != nullptr;           // hipEvents around the five kernels (tools/fms_time.py)
-    const size_t C = nchan, N = h->f.N, Hd = h->f.h_dec.size() - 1, n = h->max_n;
-    auto fail = [&](int rc) { csdr_fmstereo_destroy(h); return rc; };
-    if ((r = dev_alloc(&h->d_hp, N)) || (r = dev_alloc(&h->d_ha, N)) || (r = dev_alloc(&h->d_hdec, h->f.h_dec.size())) ||
-        (r = dev_alloc(&h->d_xh[0], C * h->Hx())) || (r = dev_alloc(&h->d_xh[1], C * h->Hx())) ||
-        (r = dev_alloc(&h->d_ub[0], C * h->ustride())) || (r = dev_alloc(&h->d_ub[1], C * h->ustride())) ||
-        (r = dev_alloc(&h->d_p, C * n)) || (r = dev_alloc(&h->d_lpr, C * n)) || (r = dev_alloc(&h->d_lr, 2 * C * n)) ||
-        (r = dev_alloc(&h->d_bq, 2 * C)) || (r = dev_alloc(&h->d_dh[0], 2 * C * Hd)) || (r = dev_alloc(&h->d_dh[1], 2 * C * Hd)) ||
-        (r = dev_alloc(&h->d_pll, C)) || (r = dev_alloc(&h->d_in, C * n)) || (r = dev_alloc(&h->d_out, 2 * C * (n / decim))))
-        return fail(r);
-    CSDR_HIP_CLEAN(hipMemcpy(h->d_hp, h->f.h_pilot.data(), sizeof(float) * N, hipMemcpyHostToDevice), csdr_fmstereo_destroy(h));
-    CSDR_HIP_CLEAN(hipMemcpy(h->d_ha, h->f.h_audio.data(), sizeof(float) * N, hipMemcpyHostToDevice), csdr_fmstereo_destroy(h));
-    CSDR_HIP_CLEAN(hipMemcpy(h->d_hdec, h->f.h_dec.data(), sizeof(float) * h->f.h_dec.size(), hipMemcpyHostToDevice), csdr_fmstereo_destroy(h));
-    if ((r = fms_init_state(h))) return fail(r);
-    *out = h;
-    return CSDR_OK;
-}
-int csdr_fmstereo_process_device(csdr_fmstereo *h, const void *d_mpx, uint32_t n, void *d_lr, uint32_t *n_out, void *stream)
-{
-    if (!h || !n_out) { set_error("fmstereo: null argument"); return CSDR_ERR_INVALID; }
-    if (n > h->max_n) { set_error("fmstereo: %u samples > max %u", n, h->max_n); return CSDR_ERR_SIZE; }
-    *n_out = h->C * 2 * (n / h->M);
-    if (!n) return CSDR_OK;
-    if (!d_mpx || !d_lr) { set_error("fmstereo: null buffer"); return CSDR_ERR_INVALID; }
-    FmsBufs b{h->d_hp, h->d_ha, h->d_hdec, {h->d_xh[0], h->d_xh[1]}, {h->d_ub[0], h->d_ub[1]}, h->d_p, h->d_lpr, h->d_lr, h->d_pll, h->d_bq,
-              {h->d_dh[0], h->d_dh[1]}};
-    FmsLaunch l{h->C, n, h->f.N, h->f.d, h->M, (uint32_t)h->f.h_dec.size(), h->ustride(), h->theta, h->f.d_nco, h->cur,
-                h->f.scale_pilot, h->f.scale_audio, h->f.alpha, h->f.beta, h->f.bq.b0, h->f.bq.b1, h->f.bq.b2, h->f.bq.a1, h->f.bq.a2};
-    const bool timed = h->timed;
-    if (timed && !h->ev[0])
-        for (hipEvent_t &e : h->ev) CSDR_HIP(hipEventCreate(&e));
-    int r = launch_fmstereo((const float *)d_mpx, (float *)d_lr, b, l, (hipStream_t)stream, timed ? h->ev : nullptr);
-    if (r) return r;
-    h->theta += n * h->f.d_nco;
-    h->cur ^= 1;
-    return CSDR_OK;
-}
-int csdr_fmstereo_process(csdr_fmstereo *h, const float *mpx, uint32_t n, float *lr, uint32_t *n_out)
-{
-    if (!h || !n_out || (n && (!mpx || !lr))) { set_error("fmstereo: null argument"); return CSDR_ERR_INVALID; }
-    if (n > h->max_n) { set_error("fmstereo: %u samples > max %u", n, h->max_n); return CSDR_ERR_SIZE; }
-    *n_out = h->C * 2 * (n / h->M);
-    if (!n) return CSDR_OK;
-    DevGuard guard(h->device);
-    if (!guard.ok) { set_error("fmstereo: cannot select device %d", h->device); return CSDR_ERR_HIP; }
-    CSDR_HIP(hipMemcpy(h->d_in, mpx, sizeof(float) * (size_t)h->C * n, hipMemcpyHostToDevice));
-    int r = csdr_fmstereo_process_device(h, h->d_in, n, h->d_out, n_out, nullptr);
-    if (r) return r;
-    CSDR_HIP(hipMemcpy(lr, h->d_out, sizeof(float) * (size_t)*n_out, hipMemcpyDeviceToHost));
-    return CSDR_OK;
-}
-int csdr_fmstereo_reset(csdr_fmstereo *h)
-{
-    if (!h) return CSDR_ERR_INVALID;
-    DevGuard guard(h->device);
-    CSDR_HIP(hipDeviceSynchronize());
-    return fms_init_state(h);
-}
-uint32_t csdr_fmstereo_get_delay(const csdr_fmstereo *h) { return h ? h->f.d : 0; }
-uint32_t csdr_fmstereo_get_taps_len(const csdr_fmstereo *h) { return h ? h->f.N : 0; }
-int csdr_fmstereo_get_pll(csdr_fmstereo *h, uint32_t chan, uint32_t *theta, uint32_t *d_theta)
-{
-    if (!h || chan >= h->C) { set_error("fmstereo: bad channel"); return CSDR_ERR_INVALID; }
-    DevGuard guard(h->device);
-    uint2 w;
-    CSDR_HIP(hipMemcpy(&w, h->d_pll + chan, sizeof(uint2), hipMemcpyDeviceToHost));
-    if (theta) *theta = w.x;
-    if (d_theta) *d_theta = w.y;
-    return CSDR_OK;
-}
-int csdr_fmstereo_kernel_times(csdr_fmstereo *h, float *us5)
-{
-    if (!h || !us5) return CSDR_ERR_INVALID;
-    if (!h->ev[0]) { set_error("fmstereo: kernel timing needs CSDR_DIAG=1 CSDR_FMS_TIME=1 at create"); return CSDR_ERR_INVALID; }
-    DevGuard guard(h->device);
-    CSDR_HIP(hipEventSynchronize(h->ev[5]));
-    for (int i = 0; i < 5; i++) { float ms = 0.f; CSDR_HIP(hipEventElapsedTime(&ms, h->ev[i], h->ev[i + 1])); us5[i] = 1000.f * ms; }
-    return CSDR_OK;
-}
-
-// ---------------------------------------------------------------------------
-// symSyncR k m beta M (Liquid.chs:244-282): symsync_rrrf on nchan independent streams
-// ---------------------------------------------------------------------------
-}  // extern "C"
-struct csdr_symsync {
-    int device; uint32_t C, max_n; SymsyncDesign d;
-    float *d_mf = nullptr, *d_dmf = nullptr, *d_hist = nullptr, *d_x = nullptr, *d_y = nullptr;
-    SymsyncState *d_st = nullptr; uint32_t *d_ny = nullptr, *d_fault = nullptr;
-};
-static int symsync_init_state(csdr_symsync *h)
-{
-    CSDR_HIP(hipMemset(h->d_hist, 0, sizeof(float) * (size_t)h->C * (h->d.L - 1)));
-    std::vector<SymsyncState> st(h->C, h->d.init);
-    CSDR_HIP(hipMemcpy(h->d_st, st.data(), sizeof(SymsyncState) * h->C, hipMemcpyHostToDevice));
-    CSDR_HIP(hipMemset(h->d_fault, 0, sizeof(uint32_t)));
-    return 0;
-}
-extern "C" {
-int csdr_symsync_destroy(csdr_symsync *h)
-{
-    if (!h) return CSDR_OK;
-    DevGuard guard(h->device);
-    (void)hipDeviceSynchronize();
-    void *ptrs[] = {h->d_mf, h->d_dmf, h->d_hist, h->d_x, h->d_y, h->d_st, h->d_ny, h->d_fault};
-    for (void *p : ptrs) if (p) (void)hipFree(p);
-    delete h;
-    return CSDR_OK;
-}
-int csdr_symsync_create(uint32_t k, uint32_t m, float beta, uint32_t npfb, float lf_bw, uint32_t k_out, uint32_t nchan,
-                        uint32_t max_samples, csdr_symsync **out)
-{
-    const uint64_t L = 2ull * k * m;
-    if (!out || !nchan || k_out < 1 || k < k_out || m < 1 || L > SYMSYNC_MAX_SUB || npfb < 1 || npfb > SYMSYNC_MAX_PFB ||
-        L * npfb > SYMSYNC_MAX_BANK || !(lf_bw >= 0.f && lf_bw <= 1.f)) {
-        set_error("symsync: bad arguments (k >= k_out >= 1, m >= 1, 2 k m <= %u, npfb in [1, %u], 2 k m npfb <= %u, lf_bw in [0, 1])",
-                  SYMSYNC_MAX_SUB, SYMSYNC_MAX_PFB, SYMSYNC_MAX_BANK);
-        return CSDR_ERR_INVALID;
-    }
-    int dev; int r = check_device(-1, &dev); if (r) return r;
-    csdr_symsync *h = new (std::nothrow) csdr_symsync();
-    if (!h) return CSDR_ERR_NOMEM;
-    h->device = dev; h->C = nchan; h->max_n = max_samples ? max_samples : 4096;
-    h->d = design_symsync_kaiser(k, m, beta, npfb, lf_bw, k_out);
-    const size_t C = nchan, n = h->max_n, LM = h->d.mf.size();
-    auto fail = [&](int rc) { csdr_symsync_destroy(h); return rc; };
-    if ((r = dev_alloc(&h->d_mf, LM)) || (r = dev_alloc(&h->d_dmf, LM)) || (r = dev_alloc(&h->d_hist, C * (h->d.L - 1))) ||
-        (r = dev_alloc(&h->d_st, C)) || (r = dev_alloc(&h->d_ny, C)) || (r = dev_alloc(&h->d_fault, 1)) ||
-        (r = dev_alloc(&h->d_x, C * n)) || (r = dev_alloc(&h->d_y, C * n)))
-        return fail(r);
-    CSDR_HIP_CLEAN(hipMemcpy(h->d_mf, h->d.mf.data(), sizeof(float) * LM, hipMemcpyHostToDevice), csdr_symsync_destroy(h));
-    CSDR_HIP_CLEAN(hipMemcpy(h->d_dmf, h->d.dmf.data(), sizeof(float) * LM, hipMemcpyHostToDevice), csdr_symsync_destroy(h));
-    if ((r = symsync_init_state(h))) return fail(r);
-    *out = h;
-    return CSDR_OK;
-}
-int csdr_symsync_process_device(csdr_symsync *h, const void *d_x, uint32_t n, void *d_y, void *d_ny, void *stream)
-{
-    if (!h || !d_ny) { set_error("symsync: null argument"); return CSDR_ERR_INVALID; }
-    if (n > h->max_n) { set_error("symsync: %u samples > max %u", n, h->max_n); return CSDR_ERR_SIZE; }
-    if (n && (!d_x || !d_y)) { set_error("symsync: null buffer"); return CSDR_ERR_INVALID; }
-    const SymsyncDesign &d = h->d;
-    SymsyncLaunch l{h->C, n, n, d.L, d.M, d.k_out, (float)d.k, d.b0, d.b1, d.b2, d.a1, d.a2, d.rate_adj};
-    return launch_symsync((const float *)d_x, (float *)d_y, (uint32_t *)d_ny, h->d_mf, h->d_dmf, h->d_hist, h->d_st, h->d_fault, l,
-                          (hipStream_t)stream);
-}
-int csdr_symsync_process(csdr_symsync *h, const float *x, uint32_t n, float *y, uint32_t *ny)
-{
-    if (!h || !ny || (n && (!x || !y))) { set_error("symsync: null argument"); return CSDR_ERR_INVALID; }
-    if (n > h->max_n) { set_error("symsync: %u samples > max %u", n, h->max_n); return CSDR_ERR_SIZE; }
-    DevGuard guard(h->device);
-    if (!guard.ok) { set_error("symsync: cannot select device %d", h->device); return CSDR_ERR_HIP; }
-    if (n) CSDR_HIP(hipMemcpy(h->d_x, x, sizeof(float) * (size_t)h->C * n, hipMemcpyHostToDevice));
-    int r = csdr_symsync_process_device(h, h->d_x, n, h->d_y, h->d_ny, nullptr);
-    if (r) return r;
-    uint32_t fault = 0;
-    CSDR_HIP(hipMemcpy(ny, h->d_ny, sizeof(uint32_t) * h->C, hipMemcpyDeviceToHost));
-    CSDR_HIP(hipMemcpy(&fault, h->d_fault, sizeof(uint32_t), hipMemcpyDeviceToHost));
-    if (n) CSDR_HIP(hipMemcpy(y, h->d_y, sizeof(float) * (size_t)h->C * n, hipMemcpyDeviceToHost));
-    if (fault) { set_error("symsync: a stream is faulted (del <= 0 or more than n outputs in a call); reset clears it"); return CSDR_ERR_SIZE; }
-    return CSDR_OK;
-}
-int csdr_symsync_reset(csdr_symsync *h)
-{
-    if (!h) return CSDR_ERR_INVALID;
-    DevGuard guard(h->device);
-    CSDR_HIP(hipDeviceSynchronize());
-    return symsync_init_state(h);
-}
-int csdr_symsync_get_state(csdr_symsync *h, uint32_t chan, float *tau, float *rate, float *del, float *q_hat)
-{
-    if (!h || chan >= h->C) { set_error("symsync: bad channel"); return CSDR_ERR_INVALID; }
-    DevGuard guard(h->device);
-    SymsyncState s;
-    CSDR_HIP(hipMemcpy(&s, h->d_st + chan, sizeof(SymsyncState), hipMemcpyDeviceToHost));
-    if (tau) *tau = s.tau;
-    if (rate) *rate = s.rate;
-    if (del) *del = s.del;
-    if (q_hat) *q_hat = s.q_hat;
-    if (s.fault) { set_error("symsync: stream %u is faulted", chan); return CSDR_ERR_SIZE; }
-    return CSDR_OK;
-}
-uint32_t csdr_symsync_get_taps_len(const csdr_symsync *h) { return h ? h->d.L : 0; }
-int csdr_symsync_get_taps(const csdr_symsync *h, float *mf, float *dmf)
-{
-    if (!h) return CSDR_ERR_INVALID;
-    if (mf) std::memcpy(mf, h->d.mf.data(), sizeof(float) * h->d.mf.size());
-    if (dmf) std::memcpy(dmf, h->d.dmf.data(), sizeof(float) * h->d.dmf.size());
-    return CSDR_OK;
-}
-
-// ---------------------------------------------------------------------------
-// realToComplex / complexToReal (Liquid.chs:503-546): firhilbf as a 2:1 decimator and a 1:2 interpolator
-// ---------------------------------------------------------------------------
-}  // extern "C"
-struct csdr_firhilb {
-    int device; uint32_t m, max_n; std::vector<float> hq;
-    float *d_hist[2] = {nullptr, nullptr}; int cur = 0;     // the windows, pair-interleaved (w1[j], w0[j]), ping-pong
-    float *d_x = nullptr, *d_y = nullptr;
-};
-static int firhilb_run(csdr_firhilb *h, bool interp, const void *d_x, uint32_t n, void *d_y, void *stream)
-{
-    if (!h) { set_error("firhilb: null argument"); return CSDR_ERR_INVALID; }
-    if (n > h->max_n) { set_error("firhilb: %u samples > max %u", n, h->max_n); return CSDR_ERR_SIZE; }
-    if (!n) return CSDR_OK;
-    if (!d_x || !d_y || d_x == d_y) { set_error("firhilb: null or aliased buffer"); return CSDR_ERR_INVALID; }
-    FirhilbLaunch l{};
-    l.n = n; l.m = h->m;
-    std::memcpy(l.hq, h->hq.data(), sizeof(float) * h->hq.size());
-    const int r = launch_firhilb(interp, (const float *)d_x, (float *)d_y, h->d_hist[h->cur], h->d_hist[h->cur ^ 1], l, (hipStream_t)stream);
-    if (!r) h->cur ^= 1;
-    return r;
-}
-static int firhilb_host(csdr_firhilb *h, bool interp, const float *x, uint32_t n, float *y)
-{
-    if (!h || (n && (!x || !y))) { set_error("firhilb: null argument"); return CSDR_ERR_INVALID; }
-    if (n > h->max_n) { set_error("firhilb: %u samples > max %u", n, h->max_n); return CSDR_ERR_SIZE; }
-    if (!n) return CSDR_OK;
-    DevGuard guard(h->device);
-    if (!guard.ok) { set_error("firhilb: cannot select device %d", h->device); return CSDR_ERR_HIP; }
-    CSDR_HIP(hipMemcpy(h->d_x, x, sizeof(float) * 2 * (size_t)n, hipMemcpyHostToDevice));
-    const int r = firhilb_run(h, interp, h->d_x, n, h->d_y, nullptr);
-    if (r) return r;
-    CSDR_HIP(hipMemcpy(y, h->d_y, sizeof(float) * 2 * (size_t)n, hipMemcpyDeviceToHost));
-    return CSDR_OK;
-}
-extern "C" {
-int csdr_firhilb_destroy(csdr_firhilb *h)
-{
-    if (!h) return CSDR_OK;
-    DevGuard guard(h->device);
-    (void)hipDeviceSynchronize();
-    void *ptrs[] = {h->d_hist[0], h->d_hist[1], h->d_x, h->d_y};
-    for (void *p : ptrs) if (p) (void)hipFree(p);
-    delete h;
-    return CSDR_OK;
-}
-int csdr_firhilb_create(uint32_t m, float as_db, uint32_t max_samples, csdr_firhilb **out)
-{
-    if (!out || m < 2 || m > FIRHILB_MAX_M || !(as_db > 0.f) || max_samples > (1u << 30)) {
-        set_error("firhilb: bad arguments (m in [2, %u], As > 0, max_samples <= 2^30)", FIRHILB_MAX_M);
-        return CSDR_ERR_INVALID;
-    }
-    int dev; int r = check_device(-1, &dev); if (r) return r;
-    csdr_firhilb *h = new (std::nothrow) csdr_firhilb();
-    if (!h) return CSDR_ERR_NOMEM;
-    h->device = dev; h->m = m; h->max_n = max_samples ? max_samples : 4096;
-    h->hq = design_firhilb(m, as_db);
-    const size_t n2 = 2 * (size_t)h->max_n;
-    if ((r = dev_alloc(&h->d_hist[0], 4 * m)) || (r = dev_alloc(&h->d_hist[1], 4 * m)) || (r = dev_alloc(&h->d_x, n2)) ||
-        (r = dev_alloc(&h->d_y, n2))) { csdr_firhilb_destroy(h); return r; }
-    CSDR_HIP_CLEAN(hipMemset(h->d_hist[0], 0, sizeof(float) * 4 * m), csdr_firhilb_destroy(h));
-    *out = h;
-    return CSDR_OK;
-}
-int csdr_firhilb_decim_device(csdr_firhilb *h, const void *d_x, uint32_t n, void *d_y, void *stream)
-{
-    return firhilb_run(h, false, d_x, n, d_y, stream);
-}
-int csdr_firhilb_interp_device(csdr_firhilb *h, const void *d_x, uint32_t n, void *d_y, void *stream)
-{
-    return firhilb_run(h, true, d_x, n, d_y, stream);
-}
-int csdr_firhilb_decim(csdr_firhilb *h, const float *x_f32, uint32_t n, float *y_cf32) { return firhilb_host(h, false, x_f32, n, y_cf32); }
-int csdr_firhilb_interp(csdr_firhilb *h, const float *x_cf32, uint32_t n, float *y_f32) { return firhilb_host(h, true, x_cf32, n, y_f32); }
-int csdr_firhilb_reset(csdr_firhilb *h)
-{
-    if (!h) return CSDR_ERR_INVALID;
-    DevGuard guard(h->device);
-    CSDR_HIP(hipDeviceSynchronize());
-    CSDR_HIP(hipMemset(h->d_hist[h->cur], 0, sizeof(float) * 4 * h->m));
-    return CSDR_OK;
-}
-uint32_t csdr_firhilb_get_taps_len(const csdr_firhilb *h) { return h ? 2 * h->m : 0; }
-int csdr_firhilb_get_taps(const csdr_firhilb *h, float *hq)
-{
-    if (!h || !hq) return CSDR_ERR_INVALID;
-    std::memcpy(hq, h->hq.data(), sizeof(float) * h->hq.size());
-    return CSDR_OK;
-}
-
-// ---------------------------------------------------------------------------
-// fskDemodulator m k bw (Liquid.chs:336-382): fskdem on nchan independent CF32 streams
-// ---------------------------------------------------------------------------
-}  // extern "C"
-struct csdr_fskdem {
-    int device; uint32_t C, max_n; FskdemDesign d;
-    float2 *d_W = nullptr, *d_x = nullptr; uint32_t *d_map = nullptr, *d_sym = nullptr;
-    float *d_e = nullptr;                                   // host-path energies: allocated by the first call that asks for them
-};
-extern "C" {
-int csdr_fskdem_destroy(csdr_fskdem *h)
-{
-    if (!h) return CSDR_OK;
-    DevGuard guard(h->device);
-    (void)hipDeviceSynchronize();
-    void *ptrs[] = {h->d_W, h->d_x, h->d_map, h->d_sym, h->d_e};
-    for (void *p : ptrs) if (p) (void)hipFree(p);
-    delete h;
-    return CSDR_OK;
-}
-int csdr_fskdem_create(uint32_t m, uint32_t k, float bandwidth, uint32_t nchan, uint32_t max_samples, csdr_fskdem **out)
-{
-    if (!out || !nchan || m < 1 || m > FSKDEM_MAX_M || k < 2 || k > FSKDEM_MAX_K || !(bandwidth > 0.f && bandwidth < 0.5f)) {
-        set_error("fskdem: bad arguments (m in [1, %u], k in [2, %u], bandwidth in (0, 0.5), nchan >= 1)", FSKDEM_MAX_M, FSKDEM_MAX_K);
-        return CSDR_ERR_INVALID;
-    }
-    int dev; int r = check_device(-1, &dev); if (r) return r;
-    csdr_fskdem *h = new (std::nothrow) csdr_fskdem();
-    if (!h) return CSDR_ERR_NOMEM;
-    h->device = dev; h->C = nchan; h->max_n = max_samples ? max_samples : 4096;
-    h->d = design_fskdem(m, k, bandwidth);
-    if (h->d.repeated && !getenv("CSDR_QUIET"))
-        fprintf(stderr, "csdr_fskdem_create(%u, %u, %g): warning, the demodulation map is not unique (K = %u); consider a larger bandwidth or k\n",
-                m, k, (double)bandwidth, h->d.K);
-    const size_t C = nchan, n = h->max_n;
-    if ((r = dev_alloc(&h->d_W, h->d.K)) || (r = dev_alloc(&h->d_map, h->d.M)) || (r = dev_alloc(&h->d_x, C * n)) ||
-        (r = dev_alloc(&h->d_sym, C * (n / k)))) { csdr_fskdem_destroy(h); return r; }
-    CSDR_HIP_CLEAN(hipMemcpy(h->d_W, h->d.W.data(), sizeof(float2) * h->d.K, hipMemcpyHostToDevice), csdr_fskdem_destroy(h));
-    CSDR_HIP_CLEAN(hipMemcpy(h->d_map, h->d.map.data(), sizeof(uint32_t) * h->d.M, hipMemcpyHostToDevice), csdr_fskdem_destroy(h));
-    *out = h;
-    return CSDR_OK;
-}
-int csdr_fskdem_process_device(csdr_fskdem *h, const void *d_x, uint32_t n, void *d_sym, void *d_energy, void *stream)
-{
-    if (!h) { set_error("fskdem: null argument"); return CSDR_ERR_INVALID; }
-    if (n > h->max_n) { set_error("fskdem: %u samples > max %u", n, h->max_n); return CSDR_ERR_SIZE; }
-    if (n / h->d.k == 0) return CSDR_OK;
-    if (!d_x || !d_sym) { set_error("fskdem: null buffer"); return CSDR_ERR_INVALID; }
-    const FskdemLaunch l{h->C, n, h->d.k, h->d.K, h->d.M};
-    return launch_fskdem((const float2 *)d_x, (uint32_t *)d_sym, (float *)d_energy, h->d_W, h->d_map, l, (hipStream_t)stream);
-}
-int csdr_fskdem_process(csdr_fskdem *h, const float *x, uint32_t n, uint32_t *sym, float *energy, uint32_t *n_out)
-{
-    if (!h || !n_out) { set_error("fskdem: null argument"); return CSDR_ERR_INVALID; }
-    if (n > h->max_n) { set_error("fskdem: %u samples > max %u", n, h->max_n); return CSDR_ERR_SIZE; }
-    const size_t ns = n / h->d.k, C = h->C;
-    *n_out = (uint32_t)(C * ns);
-    if (!ns) return CSDR_OK;
-    if (!x || !sym) { set_error("fskdem: null buffer"); return CSDR_ERR_INVALID; }
-    DevGuard guard(h->device);
-    if (!guard.ok) { set_error("fskdem: cannot select device %d", h->device); return CSDR_ERR_HIP; }
-    int r;
-    if (energy && !h->d_e && (r = dev_alloc(&h->d_e, C * (h->max_n / h->d.k) * h->d.M))) return r;
-    CSDR_HIP(hipMemcpy(h->d_x, x, sizeof(float2) * C * n, hipMemcpyHostToDevice));
-    if ((r = csdr_fskdem_process_device(h, h->d_x, n, h->d_sym, energy ? h->d_e : nullptr, nullptr))) return r;
-    CSDR_HIP(hipMemcpy(sym, h->d_sym, sizeof(uint32_t) * C * ns, hipMemcpyDeviceToHost));
-    if (energy) CSDR_HIP(hipMemcpy(energy, h->d_e, sizeof(float) * C * ns * h->d.M, hipMemcpyDeviceToHost));
-    return CSDR_OK;
-}
-int csdr_fskdem_get_design(const csdr_fskdem *h, uint32_t *K, uint32_t *demod_map)
-{
-    if (!h) { set_error("fskdem: null argument"); return CSDR_ERR_INVALID; }
-    if (K) *K = h->d.K;
-    if (demod_map) std::memcpy(demod_map, h->d.map.data(), sizeof(uint32_t) * h->d.M);
-    return CSDR_OK;
-}
-
-// ---------------------------------------------------------------------------
-// firFilterCKaiser / firFilterC / firFilterR (Liquid.chs:868-916, 955-957): firfilt_crcf / firfilt_rrrf on nchan independent
-// rows; the two design functions need no GPU
-// ---------------------------------------------------------------------------
-static bool firdes_kaiser_args_ok(uint32_t n, float fc, float as_db, float mu)
-{
-    return n >= 2 && n <= FIRFILT_MAX_LEN && fc > 0.f && fc <= 0.5f && as_db > 0.f && mu == 0.f;
-}
-int csdr_firdes_kaiser(uint32_t n, float fc, float as_db, float mu, float *h)
-{
-    if (!h || !firdes_kaiser_args_ok(n, fc, as_db, mu)) {
-        set_error("firdes_kaiser: bad arguments (n in [2, %u], fc in (0, 0.5], As > 0, mu == 0)", FIRFILT_MAX_LEN);
-        return CSDR_ERR_INVALID;
-    }
-    const std::vector<float> t = design_firfilt_kaiser(n, fc, as_db);
-    std::memcpy(h, t.data(), sizeof(float) * n);
-    return CSDR_OK;
-}
-int csdr_fir_groupdelay(const float *h, uint32_t n, float fc, float *gd)
-{
-    if (!h || !gd || !n || !(fc >= -0.5f && fc <= 0.5f)) { set_error("fir_groupdelay: bad arguments (n >= 1, |fc| <= 0.5)"); return CSDR_ERR_INVALID; }
-    *gd = fir_group_delay(std::vector<float>(h, h + n), fc);
-    return CSDR_OK;
-}
-}  // extern "C"
-struct csdr_firfilt {
-    int device; uint32_t C, max_n, el; bool cplx; std::vector<float> taps; float scale;   // el: bytes per sample
-    float *d_h = nullptr; char *d_hist[2] = {nullptr, nullptr}; int cur = 0;               // [C][L - 1] samples, ping-pong
-    char *d_x = nullptr, *d_y = nullptr;
-    size_t hist_bytes() const { return (size_t)C * (taps.size() - 1) * el; }
-};
-extern "C" {
-int csdr_firfilt_destroy(csdr_firfilt *h)
-{
-    if (!h) return CSDR_OK;
-    DevGuard guard(h->device);
-    (void)hipDeviceSynchronize();
-    void *ptrs[] = {h->d_h, h->d_hist[0], h->d_hist[1], h->d_x, h->d_y};
-    for (void *p : ptrs) if (p) (void)hipFree(p);
-    delete h;
-    return CSDR_OK;
-}
-int csdr_firfilt_create_taps(const float *taps, uint32_t n, float scale, int32_t is_complex, uint32_t nchan, uint32_t max_samples,
-                             csdr_firfilt **out)
-{
-    if (!out || !taps || !nchan || n < 1 || n > FIRFILT_MAX_LEN || max_samples > (1u << 30)) {
-        set_error("firfilt: bad arguments (taps, 1 <= n <= %u, nchan >= 1, max_samples <= 2^30)", FIRFILT_MAX_LEN);
-        return CSDR_ERR_INVALID;
-    }
-    int dev; int r = check_device(-1, &dev); if (r) return r;
-    csdr_firfilt *h = new (std::nothrow) csdr_firfilt();
-    if (!h) return CSDR_ERR_NOMEM;
-    h->device = dev; h->C = nchan; h->max_n = max_samples ? max_samples : 4096; h->cplx = is_complex != 0;
-    h->el = h->cplx ? sizeof(float2) : sizeof(float);
-    h->taps.assign(taps, taps + n); h->scale = scale;
-    const size_t plane = (size_t)nchan * h->max_n * h->el;
-    if ((r = dev_alloc(&h->d_h, n)) || (r = dev_alloc(&h->d_hist[0], h->hist_bytes())) || (r = dev_alloc(&h->d_hist[1], h->hist_bytes())) ||
-        (r = dev_alloc(&h->d_x, plane)) || (r = dev_alloc(&h->d_y, plane))) { csdr_firfilt_destroy(h); return r; }
-    CSDR_HIP_CLEAN(hipMemcpy(h->d_h, taps, sizeof(float) * n, hipMemcpyHostToDevice), csdr_firfilt_destroy(h));
-    if (h->hist_bytes()) CSDR_HIP_CLEAN(hipMemset(h->d_hist[0], 0, h->hist_bytes()), csdr_firfilt_destroy(h));
-    *out = h;
-    return CSDR_OK;
-}
-int csdr_firfilt_create_kaiser(uint32_t n, float fc, float as_db, float mu, int32_t is_complex, uint32_t nchan, uint32_t max_samples,
-                               csdr_firfilt **out)
-{
-    if (!firdes_kaiser_args_ok(n, fc, as_db, mu)) {
-        set_error("firfilt: bad design (n in [2, %u], fc in (0, 0.5], As > 0, mu == 0)", FIRFILT_MAX_LEN);
-        return CSDR_ERR_INVALID;
-    }
-    const std::vector<float> t = design_firfilt_kaiser(n, fc, as_db);
-    return csdr_firfilt_create_taps(t.data(), n, 2.0f * fc, is_complex, nchan, max_samples, out);   // firfilt_crcf_set_scale (2 fc), :893
-}
-int csdr_firfilt_process_device(csdr_firfilt *h, const void *d_x, uint32_t n, void *d_y, void *stream)
-{
-    if (!h) { set_error("firfilt: null argument"); return CSDR_ERR_INVALID; }
-    if (n > h->max_n) { set_error("firfilt: %u samples > max %u", n, h->max_n); return CSDR_ERR_SIZE; }
-    if (!n) return CSDR_OK;
-    if (!d_x || !d_y || d_x == d_y) { set_error("firfilt: null or aliased buffer"); return CSDR_ERR_INVALID; }
-    const FirfiltLaunch l{h->C, n, (uint32_t)h->taps.size(), h->scale};
-    const int r = launch_firfilt(h->cplx, d_x, d_y, h->d_h, h->d_hist[h->cur], h->d_hist[h->cur ^ 1], l, (hipStream_t)stream);
-    if (!r) h->cur ^= 1;
-    return r;
-}
-int csdr_firfilt_process(csdr_firfilt *h, const float *x, uint32_t n, float *y)
-{
-    if (!h || (n && (!x || !y))) { set_error("firfilt: null argument"); return CSDR_ERR_INVALID; }
-    if (n > h->max_n) { set_error("firfilt: %u samples > max %u", n, h->max_n); return CSDR_ERR_SIZE; }
-    if (!n) return CSDR_OK;
-    DevGuard guard(h->device);
-    if (!guard.ok) { set_error("firfilt: cannot select device %d", h->device); return CSDR_ERR_HIP; }
-    const size_t bytes = (size_t)h->C * n * h->el;
-    CSDR_HIP(hipMemcpy(h->d_x, x, bytes, hipMemcpyHostToDevice));
-    const int r = csdr_firfilt_process_device(h, h->d_x, n, h->d_y, nullptr);
-    if (r) return r;
-    CSDR_HIP(hipMemcpy(y, h->d_y, bytes, hipMemcpyDeviceToHost));
-    return CSDR_OK;
-}
-int csdr_firfilt_reset(csdr_firfilt *h)
-{
-    if (!h) return CSDR_ERR_INVALID;
-    DevGuard guard(h->device);
-    CSDR_HIP(hipDeviceSynchronize());
-    if (h->hist_bytes()) CSDR_HIP(hipMemset(h->d_hist[h->cur], 0, h->hist_bytes()));
-    return CSDR_OK;
-}
-uint32_t csdr_firfilt_get_taps_len(const csdr_firfilt *h) { return h ? (uint32_t)h->taps.size() : 0; }
-int csdr_firfilt_get_taps(const csdr_firfilt *h, float *taps, float *scale)
-{
-    if (!h) return CSDR_ERR_INVALID;
-    if (taps) std::memcpy(taps, h->taps.data(), sizeof(float) * h->taps.size());
-    if (scale) *scale = h->scale;
-    return CSDR_OK;
-}
-
-// ---------------------------------------------------------------------------
-// gmskDemodulator m k bw (Liquid.chs:384-429): gmskdem on nchan independent CF32 streams; the two design
-// functions need no GPU
-// ---------------------------------------------------------------------------
-static int firdes_gmsk(const char *name, bool rx, uint32_t k, uint32_t m, float bt, float *h)
-{
-    if (!h || !gmsk_args_ok(k, m, bt)) {
-        set_error("%s: bad arguments (k in [%u, %u], m in [1, %u], BT in [0.2, 1], h)", name, GMSK_MIN_K, GMSK_MAX_K, GMSK_MAX_M);
-        return CSDR_ERR_INVALID;
-    }
-    const std::vector<float> t = rx ? design_gmskrx(k, m, bt) : design_gmsktx(k, m, bt);
-    std::memcpy(h, t.data(), sizeof(float) * t.size());
-    return CSDR_OK;
-}
-int csdr_firdes_gmsktx(uint32_t k, uint32_t m, float bt, float *h) { return firdes_gmsk("firdes_gmsktx", false, k, m, bt, h); }
-int csdr_firdes_gmskrx(uint32_t k, uint32_t m, float bt, float *h) { return firdes_gmsk("firdes_gmskrx", true, k, m, bt, h); }
-}  // extern "C"
-struct csdr_gmskdem {
-    int device; uint32_t C, max_n, k, m; std::vector<float> taps;
-    float *d_h = nullptr; float2 *d_hist[2] = {nullptr, nullptr}; int cur = 0;             // [C][L] samples, ping-pong
-    float2 *d_x = nullptr; uint32_t *d_sym = nullptr;
-    float *d_soft = nullptr;                                // host-path soft values: allocated by the first call that asks for them
-    size_t hist_bytes() const { return sizeof(float2) * C * taps.size(); }
-};
-extern "C" {
-int csdr_gmskdem_destroy(csdr_gmskdem *h)
-{
-    if (!h) return CSDR_OK;
-    DevGuard guard(h->device);
-    (void)hipDeviceSynchronize();
-    void *ptrs[] = {h->d_h, h->d_hist[0], h->d_hist[1], h->d_x, h->d_sym, h->d_soft};
-    for (void *p : ptrs) if (p) (void)hipFree(p);
-    delete h;
-    return CSDR_OK;
-}
-int csdr_gmskdem_create(uint32_t k, uint32_t m, float bt, uint32_t nchan, uint32_t max_samples, csdr_gmskdem **out)
-{
-    if (!out || !nchan || !gmsk_args_ok(k, m, bt) || max_samples > (1u << 30)) {
-        set_error("gmskdem: bad arguments (k in [%u, %u], m in [1, %u], BT in [0.2, 1], nchan >= 1, max_samples <= 2^30)", GMSK_MIN_K,
-                  GMSK_MAX_K, GMSK_MAX_M);
-        return CSDR_ERR_INVALID;
-    }
-    int dev; int r = check_device(-1, &dev); if (r) return r;
-    csdr_gmskdem *h = new (std::nothrow) csdr_gmskdem();
-    if (!h) return CSDR_ERR_NOMEM;
-    h->device = dev; h->C = nchan; h->max_n = max_samples ? max_samples : 4096; h->k = k; h->m = m;
-    h->taps = design_gmskrx(k, m, bt);
-    const size_t C = nchan, n = h->max_n, L = h->taps.size();
-    if ((r = dev_alloc(&h->d_h, L)) || (r = dev_alloc(&h->d_hist[0], C * L)) || (r = dev_alloc(&h->d_hist[1], C * L)) ||
-        (r = dev_alloc(&h->d_x, C * n)) || (r = dev_alloc(&h->d_sym, C * (n / k) + 1))) { csdr_gmskdem_destroy(h); return r; }
-    CSDR_HIP_CLEAN(hipMemcpy(h->d_h, h->taps.data(), sizeof(float) * L, hipMemcpyHostToDevice), csdr_gmskdem_destroy(h));
-    CSDR_HIP_CLEAN(hipMemset(h->d_hist[0], 0, h->hist_bytes()), csdr_gmskdem_destroy(h));
-    *out = h;
-    return CSDR_OK;
-}
-// n has to be a multiple of k (the reference throws, Liquid.chs:421) and at most max_samples; nothing is touched otherwise
-static int gmskdem_check_n(const csdr_gmskdem *h, uint32_t n)
-{
-    if (n % h->k) { set_error("gmskdem: %u samples are not a multiple of k = %u", n, h->k); return CSDR_ERR_SIZE; }
-    if (n > h->max_n) { set_error("gmskdem: %u samples > max %u", n, h->max_n); return CSDR_ERR_SIZE; }
-    return CSDR_OK;
-}
-int csdr_gmskdem_process_device(csdr_gmskdem *h, const void *d_x, uint32_t n, void *d_sym, void *d_soft, void *stream)
-{
-    if (!h) { set_error("gmskdem: null argument"); return CSDR_ERR_INVALID; }
-    int r = gmskdem_check_n(h, n); if (r) return r;
-    if (!n) return CSDR_OK;
-    if (!d_x || !d_sym) { set_error("gmskdem: null buffer"); return CSDR_ERR_INVALID; }
-    const GmskdemLaunch l{h->C, n, h->k, h->m, (uint32_t)h->taps.size(), (uint32_t)(0x100000000ull / h->k) + 1u};
-    r = launch_gmskdem((const float2 *)d_x, (uint32_t *)d_sym, (float *)d_soft, h->d_h, h->d_hist[h->cur], h->d_hist[h->cur ^ 1], l,
-                       (hipStream_t)stream);
-    if (!r) h->cur ^= 1;
-    return r;
-}
-int csdr_gmskdem_process(csdr_gmskdem *h, const float *x, uint32_t n, uint32_t *sym, float *soft, uint32_t *n_out)
-{
-    if (!h || !n_out) { set_error("gmskdem: null argument"); return CSDR_ERR_INVALID; }
-    int r = gmskdem_check_n(h, n); if (r) return r;
-    const size_t ns = n / h->k, C = h->C;
-    *n_out = (uint32_t)(C * ns);
-    if (!n) return CSDR_OK;
-    if (!x || !sym) { set_error("gmskdem: null buffer"); return CSDR_ERR_INVALID; }
-    DevGuard guard(h->device);
-    if (!guard.ok) { set_error("gmskdem: cannot select device %d", h->device); return CSDR_ERR_HIP; }
-    if (soft && !h->d_soft && (r = dev_alloc(&h->d_soft, C * (h->max_n / h->k) + 1))) return r;
-    CSDR_HIP(hipMemcpy(h->d_x, x, sizeof(float2) * C * n, hipMemcpyHostToDevice));
-    if ((r = csdr_gmskdem_process_device(h, h->d_x, n, h->d_sym, soft ? h->d_soft : nullptr, nullptr))) return r;
-    CSDR_HIP(hipMemcpy(sym, h->d_sym, sizeof(uint32_t) * C * ns, hipMemcpyDeviceToHost));
-    if (soft) CSDR_HIP(hipMemcpy(soft, h->d_soft, sizeof(float) * C * ns, hipMemcpyDeviceToHost));
-    return CSDR_OK;
-}
-int csdr_gmskdem_reset(csdr_gmskdem *h)
-{
-    if (!h) return CSDR_ERR_INVALID;
-    DevGuard guard(h->device);
-    CSDR_HIP(hipDeviceSynchronize());
-    CSDR_HIP(hipMemset(h->d_hist[h->cur], 0, h->hist_bytes()));
-    return CSDR_OK;
-}
-int csdr_gmskdem_get_design(const csdr_gmskdem *h, uint32_t *taps_len, float *taps)
-{
-    if (!h) { set_error("gmskdem: null argument"); return CSDR_ERR_INVALID; }
-    if (taps_len) *taps_len = (uint32_t)h->taps.size();
-    if (taps) std::memcpy(taps, h->taps.data(), sizeof(float) * h->taps.size());
-    return CSDR_OK;
-}
-
-// ---------------------------------------------------------------------------
-// iirCFilter n fc f0 ap as (Liquid.chs:594-608) and its F32 and bring-your-own-sections forms: a cascade of second-order
-// sections on nchan independent rows; the design function needs no GPU
-// ---------------------------------------------------------------------------
-static bool iirdes_args_ok(uint32_t order, float fc) { return order >= 1 && order <= IIRSOS_MAX_ORDER && fc > 0.f && fc < 0.5f; }
-int csdr_iirdes_butter_lowpass(uint32_t order, float fc, float *b, float *a)
-{
-    if (!b || !a || !iirdes_args_ok(order, fc)) {
-        set_error("iirdes_butter_lowpass: bad arguments (order in [1, %u], fc in (0, 0.5))", IIRSOS_MAX_ORDER);
-        return CSDR_ERR_INVALID;
-    }
-    design_butter_lowpass_sos(order, fc, b, a);
-    return CSDR_OK;
-}
-}  // extern "C"
-struct csdr_iirsos {
-    int device; uint32_t C, max_n, el; bool cplx; std::vector<float> b, a;                // el: bytes per sample; b, a [3 S], a0 = 1
-    IirSosSection *d_sec = nullptr; char *d_st = nullptr, *d_x = nullptr, *d_y = nullptr;  // d_st [C][S] states of 2 samples
-    uint32_t nsec() const { return (uint32_t)(b.size() / 3); }
-    size_t st_bytes() const { return (size_t)C * nsec() * 2 * el; }
-};
-extern "C" {
-int csdr_iirsos_destroy(csdr_iirsos *h)
-{
-    if (!h) return CSDR_OK;
-    DevGuard guard(h->device);
-    (void)hipDeviceSynchronize();
-    void *ptrs[] = {h->d_sec, h->d_st, h->d_x, h->d_y};
-    for (void *p : ptrs) if (p) (void)hipFree(p);
-    delete h;
-    return CSDR_OK;
-}
-int csdr_iirsos_create_sos(const float *b, const float *a, uint32_t nsec, int32_t is_complex, uint32_t nchan, uint32_t max_samples,
-                           csdr_iirsos **out)
-{
-    if (!out || !b || !a || !nchan || nsec < 1 || nsec > IIRSOS_MAX_SEC || max_samples > (1u << 30)) {
-        set_error("iirsos: bad arguments (b, a, 1 <= nsec <= %u, nchan >= 1, max_samples <= 2^30)", IIRSOS_MAX_SEC);
-        return CSDR_ERR_INVALID;
-    }
-    // every section divided by its a0 (iirfiltsos), then strictly stable: the scan's matrix powers would overflow otherwise
-    std::vector<float> bn(3 * nsec), an(3 * nsec);
-    std::vector<IirSosSection> sec(nsec);
-    for (uint32_t s = 0; s < nsec; s++) {
-        const float a0 = a[3 * s];
-        if (!(a0 != 0.f) || !std::isfinite(a0)) { set_error("iirsos: section %u has a0 = %g", s, (double)a0); return CSDR_ERR_INVALID; }
-        for (int i = 0; i < 3; i++) { bn[3 * s + i] = b[3 * s + i] / a0; an[3 * s + i] = a[3 * s + i] / a0; }
-        an[3 * s] = 1.f;
-        const double a1 = an[3 * s + 1], a2 = an[3 * s + 2];
-        const bool finite = std::isfinite(bn[3 * s]) && std::isfinite(bn[3 * s + 1]) && std::isfinite(bn[3 * s + 2]);
-        if (!finite || !(std::fabs(a2) < 1.0) || !(std::fabs(a1) < 1.0 + a2)) {
-            set_error("iirsos: section %u is not strictly stable or not finite (needs |a2| < 1 and |a1| < 1 + a2; a1 = %g, a2 = %g)", s, a1, a2);
-            return CSDR_ERR_INVALID;
-        }
-        sec[s] = make_iirsos_section(&bn[3 * s], an[3 * s + 1], an[3 * s + 2]);
-    }
-    int dev; int r = check_device(-1, &dev); if (r) return r;
-    csdr_iirsos *h = new (std::nothrow) csdr_iirsos();
-    if (!h) return CSDR_ERR_NOMEM;
-    h->device = dev; h->C = nchan; h->max_n = max_samples ? max_samples : 4096; h->cplx = is_complex != 0;
-    h->el = h->cplx ? sizeof(float2) : sizeof(float);
-    h->b = bn; h->a = an;
-    const size_t plane = (size_t)nchan * h->max_n * h->el;
-    if ((r = dev_alloc(&h->d_sec, nsec)) || (r = dev_alloc(&h->d_st, h->st_bytes())) || (r = dev_alloc(&h->d_x, plane)) ||
-        (r = dev_alloc(&h->d_y, plane))) { csdr_iirsos_destroy(h); return r; }
-    CSDR_HIP_CLEAN(hipMemcpy(h->d_sec, sec.data(), sizeof(IirSosSection) * nsec, hipMemcpyHostToDevice), csdr_iirsos_destroy(h));
-    CSDR_HIP_CLEAN(hipMemset(h->d_st, 0, h->st_bytes()), csdr_iirsos_destroy(h));
-    *out = h;
-    return CSDR_OK;
-}
-int csdr_iirsos_create_prototype(uint32_t order, float fc, float f0, float ap, float as_db, int32_t is_complex, uint32_t nchan,
-                                 uint32_t max_samples, csdr_iirsos **out)
-{
-    (void)f0; (void)ap; (void)as_db;              // do not enter a Butterworth low-pass; ignored, as csdr_iirfilt_create does
-    if (!iirdes_args_ok(order, fc)) {
-        set_error("iirsos: bad design (order in [1, %u], fc in (0, 0.5))", IIRSOS_MAX_ORDER);
-        return CSDR_ERR_INVALID;
-    }
-    const uint32_t S = (order + 1) / 2;
-    float b[3 * IIRSOS_MAX_SEC], a[3 * IIRSOS_MAX_SEC];
-    design_butter_lowpass_sos(order, fc, b, a);
-    return csdr_iirsos_create_sos(b, a, S, is_complex, nchan, max_samples, out);
-}
-int csdr_iirsos_process_device(csdr_iirsos *h, const void *d_x, uint32_t n, void *d_y, void *stream)
-{
-    if (!h) { set_error("iirsos: null argument"); return CSDR_ERR_INVALID; }
-    if (n > h->max_n) { set_error("iirsos: %u samples > max %u", n, h->max_n); return CSDR_ERR_SIZE; }
-    if (!n) return CSDR_OK;
-    if (!d_x || !d_y) { set_error("iirsos: null buffer"); return CSDR_ERR_INVALID; }
-    return launch_iirsos(h->cplx, d_x, d_y, h->C, n, h->nsec(), h->d_sec, h->d_st, (hipStream_t)stream);
-}
-int csdr_iirsos_process(csdr_iirsos *h, const float *x, uint32_t n, float *y)
-{
-    if (!h || (n && (!x || !y))) { set_error("iirsos: null argument"); return CSDR_ERR_INVALID; }
-    if (n > h->max_n) { set_error("iirsos: %u samples > max %u", n, h->max_n); return CSDR_ERR_SIZE; }
-    if (!n) return CSDR_OK;
-    DevGuard guard(h->device);
-    if (!guard.ok) { set_error("iirsos: cannot select device %d", h->device); return CSDR_ERR_HIP; }
-    const size_t bytes = (size_t)h->C * n * h->el;
-    CSDR_HIP(hipMemcpy(h->d_x, x, bytes, hipMemcpyHostToDevice));
-    const int r = csdr_iirsos_process_device(h, h->d_x, n, h->d_y, nullptr);
-    if (r) return r;
-    CSDR_HIP(hipMemcpy(y, h->d_y, bytes, hipMemcpyDeviceToHost));
-    return CSDR_OK;
-}
-int csdr_iirsos_reset(csdr_iirsos *h)
-{
-    if (!h) return CSDR_ERR_INVALID;
-    DevGuard guard(h->device);
-    CSDR_HIP(hipDeviceSynchronize());
-    CSDR_HIP(hipMemset(h->d_st, 0, h->st_bytes()));
-    return CSDR_OK;
-}
-uint32_t csdr_iirsos_get_nsec(const csdr_iirsos *h) { return h ? h->nsec() : 0; }
-int csdr_iirsos_get_sos(const csdr_iirsos *h, float *b, float *a)
-{
-    if (!h) return CSDR_ERR_INVALID;
-    if (b) std::memcpy(b, h->b.data(), sizeof(float) * h->b.size());
-    if (a) std::memcpy(a, h->a.data(), sizeof(float) * h->a.size());
-    return CSDR_OK;
 }
 
 // ---------------------------------------------------------------------------
@@ -2141,7 +871,7 @@ int csdr_chain_submit(csdr_chain *h, const float *in, uint32_t n_in, void *out)
     sl.user_out = out; sl.n_out = 0; sl.out_bytes = 0; sl.staged_out = false;
     if (n_in) {
         const size_t in_bytes = sizeof(float2) * (size_t)n_in, out_max = (size_t)h->C * h->max_nf * 8;
-        if (!sl.d_in && ((r = dev_alloc(&sl.d_in, h->max_nx)))) return r;
+        if (!sl.d_in && ((r = chain_alloc(h, &sl.d_in, h->max_nx)))) return r;
         if (!sl.d_out) { CSDR_HIP(hipMalloc(&sl.d_out, out_max)); }
         // every resource of the slot exists before the chain's state moves on: a failure below this point cannot skip a chunk's state
         const bool stage_out = !is_pinned(out);
@@ -2204,7 +934,7 @@ int csdr_chain_process(csdr_chain *h, const float *in, uint32_t n_in, void *out,
         if ((r = chain_host_init(h))) return r;
         if (h->user_stream_dirty) { CSDR_HIP(hipEventSynchronize(h->e_user)); h->user_stream_dirty = false; }
         csdr_chain::HostSlot &sl = h->slot[0];
-        if (!sl.d_in && ((r = dev_alloc(&sl.d_in, h->max_nx)))) return r;
+        if (!sl.d_in && ((r = chain_alloc(h, &sl.d_in, h->max_nx)))) return r;
         if (!sl.d_out) { CSDR_HIP(hipMalloc(&sl.d_out, (size_t)h->C * h->max_nf * 8)); }
         CSDR_HIP(hipMemcpy(sl.d_in, in, sizeof(float2) * (size_t)n_in, hipMemcpyHostToDevice));
         uint32_t no = 0;
@@ -2305,7 +1035,6 @@ int csdr_chain_destroy(csdr_chain *h)
     if (h->agc_tail) agc_tail_destroy(h->agc_tail);
     h->timer.destroy();
     for (auto &sl : h->slot) {
-        if (sl.d_in) (void)hipFree(sl.d_in);
         if (sl.d_out) (void)hipFree(sl.d_out);
         if (sl.h_in) (void)hipHostFree(sl.h_in);
         if (sl.h_out) (void)hipHostFree(sl.h_out);

@@ -29,7 +29,7 @@ int  hip_fail(hipError_t e, const char *what, const char *file, int line);
         }                                                                       \
     } while (0)
 
-// ---- device buffers released together (fused plans, chain handles) ---------
+// ---- device buffers released together (fused plans, chain and block handles) ---------
 // alloc() records every buffer it makes; the destructor frees them all
 struct DeviceBuffers {
     DeviceBuffers() = default;
@@ -44,6 +44,7 @@ struct DeviceBuffers {
         *p = static_cast<T *>(q);
         return 0;
     }
+    template <class T> int alloc_n(T **p, size_t n) { return alloc(p, sizeof(T) * (n ? n : 1)); }   // n elements (at least one)
 private:
     std::vector<void *> owned;
 };

@@ -1,4 +1,4 @@
-// Interface between the C ABI (capi.hip) and the fused channelizer kernels
+// Interface between the chain handle of the C ABI (capi.hip) and the fused channelizer kernels
 // (kernels_fused.hip).  Product code.
 #pragma once
 #include "csdr_internal.h"

@@ -84,34 +84,62 @@ class _Handle:
             pass
 
 
+def _new_handle(block, *args, create="create"):
+    """csdr_<block>_<create>(*args, &h) -> the owner of the new handle"""
+    h = C.c_void_p()
+    check(getattr(lib(), f"csdr_{block}_{create}")(*args, C.byref(h)))
+    return _Handle(h, getattr(lib(), f"csdr_{block}_destroy"))
+
+
+def _handle_pipe(block, args, process):
+    """a function-style Pipe: `start` creates the csdr_<block> handle from `args`, `process(r, a)` uses r.h, `done` closes it"""
+    return Pipe(lambda: _new_handle(block, *args), process, lambda r: r.close())
+
+
+def _method_pipe(make, method="process"):
+    """a Pipe over an object's method: `start` makes the object, `process` calls the method, `done` closes the object"""
+    return Pipe(make, lambda r, a: getattr(r, method)(a), lambda r: r.close())
+
+
+class _Owner:
+    """Base of the classes that own one native csdr_<_block> handle in `_h`: `h` refuses a closed object, `close` is idempotent"""
+    _block = None
+
+    @property
+    def h(self):
+        if not self._h.h:
+            raise CsdrError(_lib.ERR_INVALID, f"{self._block} already destroyed")
+        return self._h.h
+
+    def close(self):
+        self._h.close()
+
+
+class _Resettable(_Owner):
+    """... whose C ABI has csdr_<_block>_reset"""
+
+    def reset(self):
+        check(getattr(lib(), f"csdr_{self._block}_reset")(self.h))
+
+
 def dcBlocker(alpha=0.0005, max_samples=1 << 20):
     """dcBlocker (Liquid.chs:575-589): iirfilt_crcf_create_dc_blocker(0.0005)."""
-    def start():
-        h = C.c_void_p()
-        check(lib().csdr_dcblock_create(alpha, max_samples, C.byref(h)))
-        return _Handle(h, lib().csdr_dcblock_destroy)
-
     def process(r, a):
         x = _c64(a)
         y = np.empty_like(x)
         check(lib().csdr_dcblock_process(r.h, _ptr(x), x.size, _ptr(y)))
         return y
-    return Pipe(start, process, lambda r: r.close())
+    return _handle_pipe("dcblock", (alpha, max_samples), process)
 
 
 def _mixer(f, up, max_samples):
-    def start():
-        h = C.c_void_p()
-        check(lib().csdr_nco_create(f, max_samples, C.byref(h)))
-        return _Handle(h, lib().csdr_nco_destroy)
-
     def process(r, a):
         x = _c64(a)
         y = np.empty_like(x)
         fn = lib().csdr_nco_mix_up if up else lib().csdr_nco_mix_down
         check(fn(r.h, _ptr(x), x.size, _ptr(y)))
         return y
-    return Pipe(start, process, lambda r: r.close())
+    return _handle_pipe("nco", (f, max_samples), process)
 
 
 def mixDown(f, max_samples=1 << 20):
@@ -127,66 +155,46 @@ def mixUp(f, max_samples=1 << 20):
 def automaticGainControl(tres, nchan=1, max_samples=4096):
     """automaticGainControl tres (Liquid.chs:727-728); nchan independent instances, input
     and output channel-major [nchan][n] (1-D arrays are treated as one channel)."""
-    def start():
-        h = C.c_void_p()
-        check(lib().csdr_agc_create(tres, nchan, max_samples, C.byref(h)))
-        return _Handle(h, lib().csdr_agc_destroy)
-
     def process(r, a):
         x = _c64(a)
         n = x.size // nchan
         y = np.empty_like(x)
         check(lib().csdr_agc_process(r.h, _ptr(x), n, _ptr(y)))
         return y
-    return Pipe(start, process, lambda r: r.close())
+    return _handle_pipe("agc", (tres, nchan, max_samples), process)
 
 
 def fmDemodulator(kf, nchan=1, max_samples=4096):
     """fmDemodulator kf (Liquid.chs:333-334)."""
-    def start():
-        h = C.c_void_p()
-        check(lib().csdr_freqdem_create(kf, nchan, max_samples, C.byref(h)))
-        return _Handle(h, lib().csdr_freqdem_destroy)
-
     def process(r, a):
         x = _c64(a)
         n = x.size // nchan
         m = np.empty(x.shape, dtype=np.float32)
         check(lib().csdr_freqdem_process(r.h, _ptr(x), n, _ptr(m)))
         return m
-    return Pipe(start, process, lambda r: r.close())
+    return _handle_pipe("freqdem", (kf, nchan, max_samples), process)
 
 
 def iirFilter(n, fc, f0=0.0, ap=10.0, as_db=10.0, nchan=1, max_samples=4096):
     """iirFilter n fc f0 ap as (Liquid.chs:629-638): real-valued Butterworth low-pass (order 2 is what the
     reference instantiates, as the WBFM de-emphasis)."""
-    def start():
-        h = C.c_void_p()
-        check(lib().csdr_iirfilt_create(n, fc, f0, ap, as_db, nchan, max_samples, C.byref(h)))
-        return _Handle(h, lib().csdr_iirfilt_destroy)
-
     def process(r, a):
         x = np.ascontiguousarray(a, dtype=np.float32)
         y = np.empty_like(x)
         check(lib().csdr_iirfilt_process(r.h, _ptr(x), x.size // nchan, _ptr(y)))
         return y
-    return Pipe(start, process, lambda r: r.close())
+    return _handle_pipe("iirfilt", (n, fc, f0, ap, as_db, nchan, max_samples), process)
 
 
 def firDecimator(m, nchan=1, max_samples=4096):
     """firDecimator m (Liquid.chs:500-501): Kaiser decimator (semi-length 10, 60 dB), n div m samples out."""
-    def start():
-        h = C.c_void_p()
-        check(lib().csdr_firdecim_create(m, nchan, max_samples, C.byref(h)))
-        return _Handle(h, lib().csdr_firdecim_destroy)
-
     def process(r, a):
         x = np.ascontiguousarray(a, dtype=np.float32)
         n = x.size // nchan
         y = np.empty(x.shape[:-1] + (n // m,) if x.ndim > 1 else (n // m,), dtype=np.float32)
         check(lib().csdr_firdecim_process(r.h, _ptr(x), n, _ptr(y)))
         return y
-    return Pipe(start, process, lambda r: r.close())
+    return _handle_pipe("firdecim", (m, nchan, max_samples), process)
 
 
 def wbFMDemodulator(quadRate, decim, max_samples=4096):
@@ -196,20 +204,13 @@ def wbFMDemodulator(quadRate, decim, max_samples=4096):
                            fmDemodulator(0.6, max_samples=max_samples)))
 
 
-class FmStereo:
+class FmStereo(_Resettable):
     """The `csdr_fmstereo_*` object: stereoFMDecoder quadRate decim on `nchan` independent F32 MPX streams (include/csdr.h)."""
+    _block = "fmstereo"
 
     def __init__(self, quadRate, decim, nchan=1, max_samples=1 << 16):
-        h = C.c_void_p()
-        check(lib().csdr_fmstereo_create(float(quadRate), int(decim), int(nchan), int(max_samples), C.byref(h)))
-        self._h = _Handle(h, lib().csdr_fmstereo_destroy)
+        self._h = _new_handle("fmstereo", float(quadRate), int(decim), int(nchan), int(max_samples))
         self.decim, self.nchan = int(decim), int(nchan)
-
-    @property
-    def h(self):
-        if not self._h.h:
-            raise CsdrError(_lib.ERR_INVALID, "fmstereo already destroyed")
-        return self._h.h
 
     @property
     def delay(self):
@@ -247,35 +248,21 @@ class FmStereo:
         check(lib().csdr_fmstereo_kernel_times(self.h, t))
         return list(t)
 
-    def reset(self):
-        check(lib().csdr_fmstereo_reset(self.h))
-
-    def close(self):
-        self._h.close()
-
 
 def stereoFMDecoder(quadRate, decim, nchan=1, max_samples=1 << 16):
     """stereoFMDecoder quadRate decim (Liquid.chs:1069-1078) as a Pipe from F32 MPX arrays ([nchan][n], or [n]) to interleaved
     stereo L, R, L, R ... ([nchan][2 (n div decim)]).  The wire delay is a constant d samples (deviation)."""
-    return Pipe(lambda: FmStereo(quadRate, decim, nchan, max_samples), lambda r, a: r.process(a), lambda r: r.close())
+    return _method_pipe(lambda: FmStereo(quadRate, decim, nchan, max_samples))
 
 
-class SymSync:
+class SymSync(_Resettable):
     """The `csdr_symsync_*` object: symSyncR k m beta npfb (set_lf_bw lf_bw, set_output_rate k_out) on `nchan` independent F32
     streams (include/csdr.h)."""
+    _block = "symsync"
 
     def __init__(self, k, m=4, beta=0.0, npfb=64, nchan=1, max_samples=1 << 16, lf_bw=0.05, k_out=2):
-        h = C.c_void_p()
-        check(lib().csdr_symsync_create(int(k), int(m), float(beta), int(npfb), float(lf_bw), int(k_out), int(nchan),
-                                        int(max_samples), C.byref(h)))
-        self._h = _Handle(h, lib().csdr_symsync_destroy)
+        self._h = _new_handle("symsync", int(k), int(m), float(beta), int(npfb), float(lf_bw), int(k_out), int(nchan), int(max_samples))
         self.k, self.npfb, self.nchan = int(k), int(npfb), int(nchan)
-
-    @property
-    def h(self):
-        if not self._h.h:
-            raise CsdrError(_lib.ERR_INVALID, "symsync already destroyed")
-        return self._h.h
 
     @property
     def taps_len(self):
@@ -315,17 +302,11 @@ class SymSync:
         check(lib().csdr_symsync_process_device(self.h, C.c_void_p(d_x_ptr), n, C.c_void_p(d_y_ptr), C.c_void_p(d_ny_ptr),
                                                 C.c_void_p(stream)))
 
-    def reset(self):
-        check(lib().csdr_symsync_reset(self.h))
-
-    def close(self):
-        self._h.close()
-
 
 def symSyncR(k, m=4, beta=0.0, M=64, nchan=1, max_samples=1 << 16):
     """symSyncR k m beta M (Liquid.chs:244-282: set_lf_bw 0.05, set_output_rate 2) as a Pipe from F32 arrays ([nchan][n], or
     [n]) to the synchronised samples: a list of per-stream arrays, or one array for [n]"""
-    return Pipe(lambda: SymSync(k, m, beta, M, nchan, max_samples), lambda r, a: r.process(a), lambda r: r.close())
+    return _method_pipe(lambda: SymSync(k, m, beta, M, nchan, max_samples))
 
 
 def fmDemWithSync(k, nchan=1, max_samples=1 << 16):
@@ -334,22 +315,15 @@ def fmDemWithSync(k, nchan=1, max_samples=1 << 16):
     return compose(symSyncR(k, 4, 0.0, 64, nchan, max_samples), fmDemodulator(kf, nchan, max_samples))
 
 
-class FirHilb:
+class FirHilb(_Resettable):
     """The `csdr_firhilb_*` object: firhilbf_create m As (firhilbCreate, Liquid.chs:520-525, fixes 5 and 60), a half-band Hilbert
     transform driven as a 2:1 real-to-complex decimator and a 1:2 complex-to-real interpolator on shared windows
     (include/csdr.h).  `max_samples` is the largest call in complex samples."""
+    _block = "firhilb"
 
     def __init__(self, m=5, as_db=60.0, max_samples=1 << 16):
-        h = C.c_void_p()
-        check(lib().csdr_firhilb_create(int(m), float(as_db), int(max_samples), C.byref(h)))
-        self._h = _Handle(h, lib().csdr_firhilb_destroy)
+        self._h = _new_handle("firhilb", int(m), float(as_db), int(max_samples))
         self.m = int(m)
-
-    @property
-    def h(self):
-        if not self._h.h:
-            raise CsdrError(_lib.ERR_INVALID, "firhilb already destroyed")
-        return self._h.h
 
     @property
     def taps_len(self):
@@ -384,39 +358,26 @@ class FirHilb:
         """Device-resident variant: n complex in, 2 n floats out"""
         check(lib().csdr_firhilb_interp_device(self.h, C.c_void_p(d_x_ptr), n, C.c_void_p(d_y_ptr), C.c_void_p(stream)))
 
-    def reset(self):
-        check(lib().csdr_firhilb_reset(self.h))
-
-    def close(self):
-        self._h.close()
-
 
 def realToComplex(m=5, as_db=60.0, max_samples=1 << 16):
     """realToComplex (Liquid.chs:536-537) as a Pipe from F32 arrays to CF32 arrays of half the length"""
-    return Pipe(lambda: FirHilb(m, as_db, max_samples), lambda r, a: r.decim(a), lambda r: r.close())
+    return _method_pipe(lambda: FirHilb(m, as_db, max_samples), "decim")
 
 
 def complexToReal(m=5, as_db=60.0, max_samples=1 << 16):
     """complexToReal (Liquid.chs:545-546) as a Pipe from CF32 arrays to F32 arrays of twice the length"""
-    return Pipe(lambda: FirHilb(m, as_db, max_samples), lambda r, a: r.interp(a), lambda r: r.close())
+    return _method_pipe(lambda: FirHilb(m, as_db, max_samples), "interp")
 
 
-class FskDem:
+class FskDem(_Owner):
     """The `csdr_fskdem_*` object: fskDemodulator m k bw (Liquid.chs:336-382) on `nchan` independent CF32 streams: M = 2^m
     tones, k samples per symbol (include/csdr.h, DESIGN.md 4.12).  A call of n samples per row yields n // k symbols per row
     and drops the last n % k samples; nothing is carried between calls."""
+    _block = "fskdem"
 
     def __init__(self, m, k, bw, nchan=1, max_samples=1 << 16):
-        h = C.c_void_p()
-        check(lib().csdr_fskdem_create(int(m), int(k), float(bw), int(nchan), int(max_samples), C.byref(h)))
-        self._h = _Handle(h, lib().csdr_fskdem_destroy)
+        self._h = _new_handle("fskdem", int(m), int(k), float(bw), int(nchan), int(max_samples))
         self.m, self.k, self.M, self.nchan = int(m), int(k), 1 << int(m), int(nchan)
-
-    @property
-    def h(self):
-        if not self._h.h:
-            raise CsdrError(_lib.ERR_INVALID, "fskdem already destroyed")
-        return self._h.h
 
     def design(self):
         """(K, demod_map): the transform size and the bin of each of the M tones"""
@@ -448,14 +409,11 @@ class FskDem:
         check(lib().csdr_fskdem_process_device(self.h, C.c_void_p(d_x_ptr), n, C.c_void_p(d_sym_ptr),
                                                C.c_void_p(d_energy_ptr) if d_energy_ptr else None, C.c_void_p(stream)))
 
-    def close(self):
-        self._h.close()
-
 
 def fskDemodulator(m, k, bw, nchan=1, max_samples=1 << 16):
     """fskDemodulator m k bw (Liquid.chs:378-382) as a Pipe from CF32 arrays ([nchan][n], or [n]) to uint32 symbols
     ([nchan][n div k], or [n div k]); the n mod k samples left over in a chunk are dropped, as there (Liquid.chs:367-376)"""
-    return Pipe(lambda: FskDem(m, k, bw, nchan, max_samples), lambda r, a: r.process(a), lambda r: r.close())
+    return _method_pipe(lambda: FskDem(m, k, bw, nchan, max_samples))
 
 
 def firdes_kaiser(n, fc, as_db=60.0):
@@ -473,22 +431,20 @@ def fir_groupdelay(h, fc):
     return gd.value
 
 
-class FirFilt:
+class FirFilt(_Resettable):
     """The `csdr_firfilt_*` object: firfilt_crcf (`is_complex`, CF32 rows) or firfilt_rrrf (F32 rows) with real taps on `nchan`
     independent rows: y[t] = scale * sum_i taps[i] x[t - i], the last len(taps) - 1 samples of a row carried from call to call
     (include/csdr.h).  `FirFilt.kaiser` is firfiltCreateCKaiser (Liquid.chs:889-895)."""
+    _block = "firfilt"
 
     def __init__(self, taps, scale=1.0, is_complex=True, nchan=1, max_samples=1 << 16, _kaiser=None):
-        h = C.c_void_p()
+        shape = (int(bool(is_complex)), int(nchan), int(max_samples))
         if _kaiser is not None:
             n, fc, as_db, mu = _kaiser
-            check(lib().csdr_firfilt_create_kaiser(int(n), float(fc), float(as_db), float(mu), int(bool(is_complex)), int(nchan),
-                                                   int(max_samples), C.byref(h)))
+            self._h = _new_handle("firfilt", int(n), float(fc), float(as_db), float(mu), *shape, create="create_kaiser")
         else:
             t = np.ascontiguousarray(taps, dtype=np.float32).reshape(-1)
-            check(lib().csdr_firfilt_create_taps(_ptr(t), t.size, float(scale), int(bool(is_complex)), int(nchan), int(max_samples),
-                                                 C.byref(h)))
-        self._h = _Handle(h, lib().csdr_firfilt_destroy)
+            self._h = _new_handle("firfilt", _ptr(t), t.size, float(scale), *shape, create="create_taps")
         self.is_complex, self.nchan = bool(is_complex), int(nchan)
         self.dtype = np.complex64 if self.is_complex else np.float32
 
@@ -496,12 +452,6 @@ class FirFilt:
     def kaiser(cls, n, fc, as_db=60.0, mu=0.0, is_complex=True, nchan=1, max_samples=1 << 16):
         """the taps of firdes_kaiser(n, fc, as_db) and the scale 2 fc"""
         return cls(None, is_complex=is_complex, nchan=nchan, max_samples=max_samples, _kaiser=(n, fc, as_db, mu))
-
-    @property
-    def h(self):
-        if not self._h.h:
-            raise CsdrError(_lib.ERR_INVALID, "firfilt already destroyed")
-        return self._h.h
 
     @property
     def taps_len(self):
@@ -525,27 +475,21 @@ class FirFilt:
         """Device-resident variant: raw device pointers (ints) for x and y, [nchan][n] each; enqueues on `stream`"""
         check(lib().csdr_firfilt_process_device(self.h, C.c_void_p(d_x_ptr), n, C.c_void_p(d_y_ptr), C.c_void_p(stream)))
 
-    def reset(self):
-        check(lib().csdr_firfilt_reset(self.h))
-
-    def close(self):
-        self._h.close()
-
 
 def firFilterCKaiser(n, fc, as_db=60.0, mu=0.0, nchan=1, max_samples=1 << 16):
     """firFilterCKaiser n fc as mu (Liquid.chs:897-916 over firfiltCreateCKaiser, :889-895) as a Pipe of CF32 arrays
     ([nchan][n], or [n])"""
-    return Pipe(lambda: FirFilt.kaiser(n, fc, as_db, mu, True, nchan, max_samples), lambda r, a: r.process(a), lambda r: r.close())
+    return _method_pipe(lambda: FirFilt.kaiser(n, fc, as_db, mu, True, nchan, max_samples))
 
 
 def firFilterC(taps, scale=1.0, nchan=1, max_samples=1 << 16):
     """firFilterC f (Liquid.chs:868-887): firfilt_crcf as a Pipe of CF32 arrays; the liquid object f is its taps and scale here"""
-    return Pipe(lambda: FirFilt(taps, scale, True, nchan, max_samples), lambda r, a: r.process(a), lambda r: r.close())
+    return _method_pipe(lambda: FirFilt(taps, scale, True, nchan, max_samples))
 
 
 def firFilterR(taps, scale=1.0, nchan=1, max_samples=1 << 16):
     """firFilterR f (Liquid.chs:955-957): firfilt_rrrf as a Pipe of F32 arrays; the liquid object f is its taps and scale here"""
-    return Pipe(lambda: FirFilt(taps, scale, False, nchan, max_samples), lambda r, a: r.process(a), lambda r: r.close())
+    return _method_pipe(lambda: FirFilt(taps, scale, False, nchan, max_samples))
 
 
 def _firdes_gmsk(fn, k, m, bt):
@@ -576,23 +520,16 @@ def firFilterRNyquist(k, m, beta, mu=0.0, nchan=1, max_samples=1 << 16):
     return firFilterR(firdes_gmskrx(k, m, beta), 1.0 / int(k), nchan, max_samples)
 
 
-class GmskDem:
+class GmskDem(_Resettable):
     """The `csdr_gmskdem_*` object: gmskdem_create(k, m, bt) (Liquid.chs:384-429; liquid's argument order) on `nchan`
     independent CF32 streams: k samples per symbol, a receive filter of 2 k m + 1 taps (firdes_gmskrx), one bit per symbol
     (include/csdr.h, DESIGN.md 4.15).  A call takes a multiple of k samples per row and yields n // k symbols per row; the last
     2 k m + 1 samples of a row are carried from call to call."""
+    _block = "gmskdem"
 
     def __init__(self, k, m, bt, nchan=1, max_samples=1 << 16):
-        h = C.c_void_p()
-        check(lib().csdr_gmskdem_create(int(k), int(m), float(bt), int(nchan), int(max_samples), C.byref(h)))
-        self._h = _Handle(h, lib().csdr_gmskdem_destroy)
+        self._h = _new_handle("gmskdem", int(k), int(m), float(bt), int(nchan), int(max_samples))
         self.k, self.m, self.nchan = int(k), int(m), int(nchan)
-
-    @property
-    def h(self):
-        if not self._h.h:
-            raise CsdrError(_lib.ERR_INVALID, "gmskdem already destroyed")
-        return self._h.h
 
     def design(self):
         """the receive filter's taps, F32 [2 k m + 1]"""
@@ -625,18 +562,12 @@ class GmskDem:
         check(lib().csdr_gmskdem_process_device(self.h, C.c_void_p(d_x_ptr), n, C.c_void_p(d_sym_ptr),
                                                 C.c_void_p(d_soft_ptr) if d_soft_ptr else None, C.c_void_p(stream)))
 
-    def reset(self):
-        check(lib().csdr_gmskdem_reset(self.h))
-
-    def close(self):
-        self._h.close()
-
 
 def gmskDemodulator(m, k, bw, nchan=1, max_samples=1 << 16):
     """gmskDemodulator m k bw (Liquid.chs:428-429; the reference's argument order, which hands `k m bw` on to gmskdem_create,
     :409) as a Pipe from CF32 arrays ([nchan][n], or [n]) to uint32 bits ([nchan][n div k], or [n div k]); n not a multiple
     of k is refused, as there (:421)"""
-    return Pipe(lambda: GmskDem(k, m, bw, nchan, max_samples), lambda r, a: r.process(a), lambda r: r.close())
+    return _method_pipe(lambda: GmskDem(k, m, bw, nchan, max_samples))
 
 
 def iirdes_butter_lowpass(n, fc):
@@ -649,26 +580,24 @@ def iirdes_butter_lowpass(n, fc):
     return b, a
 
 
-class IirSos:
+class IirSos(_Resettable):
     """The `csdr_iirsos_*` object: a cascade of 1 .. 8 second-order sections with real coefficients on `nchan` independent rows
     of CF32 (`is_complex`, iirfilt_crcf: re and im filtered alike) or F32 samples, every section's state carried from call to
     call (include/csdr.h, DESIGN.md 4.14).  `IirSos(b, a)` takes the caller's sections ([S][3] each, divided by their a0);
     `IirSos.prototype` is iirfilt_*_create_prototype(BUTTER, LOWPASS, SOS, n, fc, ..) (Liquid.chs:594-608)."""
+    _block = "iirsos"
 
     def __init__(self, b, a, is_complex=True, nchan=1, max_samples=1 << 16, _prototype=None):
-        h = C.c_void_p()
+        shape = (int(bool(is_complex)), int(nchan), int(max_samples))
         if _prototype is not None:
             n, fc, f0, ap, as_db = _prototype
-            check(lib().csdr_iirsos_create_prototype(int(n), float(fc), float(f0), float(ap), float(as_db), int(bool(is_complex)),
-                                                     int(nchan), int(max_samples), C.byref(h)))
+            self._h = _new_handle("iirsos", int(n), float(fc), float(f0), float(ap), float(as_db), *shape, create="create_prototype")
         else:
             b = np.ascontiguousarray(b, dtype=np.float32).reshape(-1)
             a = np.ascontiguousarray(a, dtype=np.float32).reshape(-1)
             if b.size != a.size or b.size % 3:
                 raise CsdrError(_lib.ERR_INVALID, "iirsos: b and a must be [S][3] each")
-            check(lib().csdr_iirsos_create_sos(_ptr(b), _ptr(a), b.size // 3, int(bool(is_complex)), int(nchan), int(max_samples),
-                                               C.byref(h)))
-        self._h = _Handle(h, lib().csdr_iirsos_destroy)
+            self._h = _new_handle("iirsos", _ptr(b), _ptr(a), b.size // 3, *shape, create="create_sos")
         self.is_complex, self.nchan = bool(is_complex), int(nchan)
         self.dtype = np.complex64 if self.is_complex else np.float32
 
@@ -676,12 +605,6 @@ class IirSos:
     def prototype(cls, n, fc, f0=0.0, ap=10.0, as_db=10.0, is_complex=True, nchan=1, max_samples=1 << 16):
         """the sections of iirdes_butter_lowpass(n, fc); f0, ap and as_db are accepted and ignored"""
         return cls(None, None, is_complex=is_complex, nchan=nchan, max_samples=max_samples, _prototype=(n, fc, f0, ap, as_db))
-
-    @property
-    def h(self):
-        if not self._h.h:
-            raise CsdrError(_lib.ERR_INVALID, "iirsos already destroyed")
-        return self._h.h
 
     @property
     def nsec(self):
@@ -706,61 +629,45 @@ class IirSos:
         enqueues on `stream`"""
         check(lib().csdr_iirsos_process_device(self.h, C.c_void_p(d_x_ptr), n, C.c_void_p(d_y_ptr), C.c_void_p(stream)))
 
-    def reset(self):
-        check(lib().csdr_iirsos_reset(self.h))
-
-    def close(self):
-        self._h.close()
-
 
 def iirCFilter(n, fc, f0=0.0, ap=10.0, as_db=10.0, nchan=1, max_samples=1 << 16):
     """iirCFilter n fc f0 ap as (Liquid.chs:600-608): order-n Butterworth low-pass (iirfilt_crcf) as a Pipe of CF32 arrays
     ([nchan][n], or [n])"""
-    return Pipe(lambda: IirSos.prototype(n, fc, f0, ap, as_db, True, nchan, max_samples), lambda r, a: r.process(a), lambda r: r.close())
+    return _method_pipe(lambda: IirSos.prototype(n, fc, f0, ap, as_db, True, nchan, max_samples))
 
 
 def iirFilterN(n, fc, f0=0.0, ap=10.0, as_db=10.0, nchan=1, max_samples=1 << 16):
     """iirCFilter's design on F32 arrays for any order 1 .. 16 (`iirFilter` itself stays the order-2 `csdr_iirfilt` object)"""
-    return Pipe(lambda: IirSos.prototype(n, fc, f0, ap, as_db, False, nchan, max_samples), lambda r, a: r.process(a), lambda r: r.close())
+    return _method_pipe(lambda: IirSos.prototype(n, fc, f0, ap, as_db, False, nchan, max_samples))
 
 
 def iirFilterSOS(b, a, complex=False, nchan=1, max_samples=1 << 16):
     """The caller's own second-order sections b, a ([S][3] each, S <= 8: a Chebyshev, elliptic or notch design brought from
     elsewhere) as a Pipe of F32 or (complex) CF32 arrays; a liquid iirfilt object is its sections here"""
-    return Pipe(lambda: IirSos(b, a, complex, nchan, max_samples), lambda r, a_: r.process(a_), lambda r: r.close())
+    return _method_pipe(lambda: IirSos(b, a, complex, nchan, max_samples))
 
 
 def resampler(r, as_db=60.0, max_samples=1 << 20):
     """resampler r as (Liquid.chs:115-117): Pipe IO (Array CF32) (Array CF32) with a variable-length output
     (`shrinkToFit` to the count msresamp_crcf_execute reports, :79-98).  r == 0 is the identity."""
-    def start():
-        h = C.c_void_p()
-        check(lib().csdr_resamp_create(r, as_db, max_samples, C.byref(h)))
-        return _Handle(h, lib().csdr_resamp_destroy)
-
     def process(rh, a):
         x = _c64(a)
         y = np.empty(int(lib().csdr_resamp_max_out(rh.h, x.size)), dtype=np.complex64)
         n = C.c_uint32()
         check(lib().csdr_resamp_process(rh.h, _ptr(x), x.size, _ptr(y), C.byref(n)))
         return y[:n.value].copy()
-    return Pipe(start, process, lambda rh: rh.close())
+    return _handle_pipe("resamp", (r, as_db, max_samples), process)
 
 
 def amDemodulator(nchan=1, max_samples=4096, mod_index=0.8):
     """amDemodulator (Liquid.chs:468-469): ampmodem_create 0.8 DSB, carrier present."""
-    def start():
-        h = C.c_void_p()
-        check(lib().csdr_ampdem_create(mod_index, nchan, max_samples, C.byref(h)))
-        return _Handle(h, lib().csdr_ampdem_destroy)
-
     def process(r, a):
         x = _c64(a)
         n = x.size // nchan
         m = np.empty(x.shape, dtype=np.float32)
         check(lib().csdr_ampdem_process(r.h, _ptr(x), n, _ptr(m)))
         return m
-    return Pipe(start, process, lambda r: r.close())
+    return _handle_pipe("ampdem", (mod_index, nchan, max_samples), process)
 
 
 @dataclass
@@ -786,8 +693,9 @@ class ChainConfig:
     dft_backward: bool = False  # CSDR_FLAG_DFT_BACKWARD: the analyzer's transform as e^{+j} (row k = forward row (M - k) mod M); include/csdr.h
 
 
-class Chain:
+class Chain(_Resettable):
     """The fused chain object behind `csdr_chain_*`."""
+    _block = "chain"
 
     def __init__(self, cfg: ChainConfig = None, **kw):
         cfg = cfg or ChainConfig(**kw)
@@ -804,20 +712,12 @@ class Chain:
         c.chan_stride = cfg.chan_stride
         c.device, c.max_frames, c.flags = cfg.device, cfg.max_frames, cfg.flags | (_lib.FLAG_TAIL_ONLY if cfg.tail_only else 0) | (_lib.FLAG_DFT_BACKWARD if cfg.dft_backward else 0)
         c.pfb_m, c.pfb_as = cfg.pfb_m, cfg.pfb_as
-        h = C.c_void_p()
-        check(lib().csdr_chain_create(C.byref(c), C.byref(h)))
-        self._h = _Handle(h, lib().csdr_chain_destroy)
+        self._h = _new_handle("chain", C.byref(c))
         self.M = cfg.channels
         self.C = cfg.channels // cfg.chan_stride if cfg.chan_stride > 1 else (cfg.chan_count or (cfg.channels - cfg.chan_first))
         self.mixed = bool(cfg.mix) and self.M > 1
         self.out_dtype = np.float32 if cfg.demod in ("fm", "am", "wbfm") else np.complex64
         self.decim = cfg.decim if cfg.demod == "wbfm" else 1
-
-    @property
-    def h(self):
-        if not self._h.h:
-            raise CsdrError(_lib.ERR_INVALID, "chain already destroyed")
-        return self._h.h
 
     @property
     def path(self):
@@ -913,7 +813,7 @@ class Chain:
         return lib().csdr_chain_debug_agc_tile_major_calls(self.h)
 
     def reset(self):
-        check(lib().csdr_chain_reset(self.h))
+        super().reset()
         self._pending = []                              # the native side abandons chunks still in flight
 
     def seek_frames(self, frames):
@@ -923,7 +823,7 @@ class Chain:
 
     def close(self):
         self._pending = []
-        self._h.close()
+        super().close()
 
 
 class host_array:

@@ -1,0 +1,132 @@
+"""The life-cycle the fifteen block handles of include/csdr.h share, on the GPU: two handles of one configuration are
+independent (the same input gives the same bits; destroying one leaves the other's state and buffers alone), close is
+idempotent, a closed object refuses work, and create / close cycles without a call in between are clean.
+
+One case per block kind (real and complex where a block has both) in the smallest configuration its own GPU test uses,
+nchan = 3 where the block takes nchan, calls of 3000 and 1000 samples per row (multiples of every k and decimation here)
+from a seeded generator.  Every comparison is of bits: the same calls on the same state give the same bits for every block.
+Every test runs under a time limit of its own: a watchdog thread ends the process if a GPU call does not come back."""
+import faulthandler
+
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+cs = pytest.importorskip("composable_sdr_amd")
+from composable_sdr_amd import _lib                           # noqa: E402
+
+f32, c64 = np.float32, np.complex64
+LIMIT_S = 120
+NCHAN, MAXN, N1, N2 = 3, 4096, 3000, 1000
+
+
+@pytest.fixture(autouse=True)
+def _time_limit(monkeypatch):
+    monkeypatch.setenv("CSDR_QUIET", "1")                     # the resampler prints its design otherwise
+    faulthandler.dump_traceback_later(LIMIT_S, exit=True)
+    yield
+    faulthandler.cancel_dump_traceback_later()
+
+
+class Case:
+    """make() -> resource; run(r, x) / lazy(r, x) -> tuple of arrays (lazy: the call that takes the lazily allocated buffer);
+    done(r); rows: nchan of the input, 0 for a block of one stream ([n] arrays); is_class: r is one of the handle-owning
+    classes (it has .h), not the resource of a function-style Pipe"""
+
+    def __init__(self, name, make, run, done, dtype, rows, lazy=None, is_class=False):
+        self.name, self.make, self.run, self.done, self.dtype, self.rows = name, make, run, done, dtype, rows
+        self.lazy, self.is_class = lazy or run, is_class
+
+
+def _pipe(name, pipe, dtype, rows):
+    return Case(name, pipe._start, lambda r, x: (pipe._process(r, x),), pipe._done, dtype, rows)
+
+
+def _obj(name, make, dtype, rows, run=None, lazy=None):
+    return Case(name, make, run or (lambda r, x: (r.process(x),)), lambda r: r.close(), dtype, rows, lazy, is_class=True)
+
+
+CASES = [
+    _pipe("dcblock", cs.dcBlocker(max_samples=MAXN), c64, 0),
+    _pipe("nco-down", cs.mixDown(0.1, max_samples=MAXN), c64, 0),
+    _pipe("nco-up", cs.mixUp(0.123, max_samples=MAXN), c64, 0),
+    _pipe("agc", cs.automaticGainControl(-35.0, nchan=NCHAN, max_samples=MAXN), c64, NCHAN),
+    _pipe("freqdem", cs.fmDemodulator(0.3, nchan=NCHAN, max_samples=MAXN), c64, NCHAN),
+    _pipe("iirfilt", cs.iirFilter(2, 0.025, nchan=NCHAN, max_samples=MAXN), f32, NCHAN),
+    _pipe("firdecim", cs.firDecimator(4, nchan=NCHAN, max_samples=MAXN), f32, NCHAN),
+    _pipe("resamp", cs.resampler(0.3, 60.0, max_samples=MAXN), c64, 0),
+    _pipe("ampdem", cs.amDemodulator(nchan=NCHAN, max_samples=MAXN), c64, NCHAN),
+    _obj("fmstereo", lambda: cs.FmStereo(192e3, 4, nchan=NCHAN, max_samples=MAXN), f32, NCHAN),
+    _obj("symsync", lambda: cs.SymSync(4, 4, 0.0, 64, nchan=NCHAN, max_samples=MAXN), f32, NCHAN, run=lambda r, x: tuple(r.process(x))),
+    _obj("firhilb-decim", lambda: cs.FirHilb(max_samples=MAXN), f32, 0, run=lambda r, x: (r.decim(x),)),
+    _obj("firhilb-interp", lambda: cs.FirHilb(max_samples=MAXN), c64, 0, run=lambda r, x: (r.interp(x),)),
+    _obj("fskdem", lambda: cs.FskDem(1, 8, 0.25, nchan=NCHAN, max_samples=MAXN), c64, NCHAN,
+         lazy=lambda r, x: r.process_rows(x, energy=True)),
+    _obj("firfilt-real", lambda: cs.FirFilt(np.ones(5, f32), 1.0, is_complex=False, nchan=NCHAN, max_samples=MAXN), f32, NCHAN),
+    _obj("firfilt-complex", lambda: cs.FirFilt.kaiser(21, 0.1, 60.0, is_complex=True, nchan=NCHAN, max_samples=MAXN), c64, NCHAN),
+    _obj("gmskdem", lambda: cs.GmskDem(4, 3, 0.3, nchan=NCHAN, max_samples=MAXN), c64, NCHAN,
+         lazy=lambda r, x: r.process_rows(x, soft=True)),
+    _obj("iirsos-real", lambda: cs.IirSos.prototype(3, 0.1, is_complex=False, nchan=NCHAN, max_samples=MAXN), f32, NCHAN),
+    _obj("iirsos-complex", lambda: cs.IirSos.prototype(3, 0.1, is_complex=True, nchan=NCHAN, max_samples=MAXN), c64, NCHAN),
+]
+
+
+def _input(case, n, seed):
+    shape = (case.rows, n) if case.rows else (n,)
+    rng = np.random.default_rng(seed)
+    x = rng.standard_normal(shape)
+    if case.dtype is c64:
+        x = x + 1j * rng.standard_normal(shape)
+    return (0.5 * x).astype(case.dtype)
+
+
+def _assert_same_bits(got, want, what):
+    assert len(got) == len(want) and len(got) >= 1, what
+    for g, w in zip(got, want):
+        g, w = np.ascontiguousarray(g), np.ascontiguousarray(w)
+        assert g.dtype == w.dtype and g.shape == w.shape and g.size > 0, (what, g.dtype, w.dtype, g.shape, w.shape)
+        assert g.tobytes() == w.tobytes(), what
+
+
+@pytest.mark.parametrize("case", CASES, ids=[c.name for c in CASES])
+def test_two_handles_are_independent_and_close_is_idempotent(case):
+    x, x2 = _input(case, N1, 1), _input(case, N2, 2)
+    a, b = case.make(), case.make()
+    _assert_same_bits(case.run(a, x), case.run(b, x), "two fresh handles, the same input")
+    case.done(b)
+    got = case.lazy(a, x2)                                    # the survivor goes on from its own state, in its own buffers
+    c = case.make()
+    case.run(c, x)
+    _assert_same_bits(got, case.lazy(c, x2), "the survivor of a destroy against a third fresh handle")
+    for r in (a, b, c):
+        case.done(r)
+        case.done(r)                                          # a second close (a second _done) is fine
+    if case.is_class:
+        for r in (a, b, c):
+            for use in (lambda: r.h, lambda: case.run(r, x)):
+                with pytest.raises(cs.CsdrError) as e:
+                    use()
+                assert e.value.code == _lib.ERR_INVALID and "already destroyed" in str(e.value)
+    else:
+        assert not a.h and not b.h and not c.h
+
+
+@pytest.mark.parametrize("case", CASES, ids=[c.name for c in CASES])
+def test_create_close_cycles_without_a_call(case):
+    for _ in range(3):
+        case.done(case.make())
+
+
+def test_resampler_rate_zero_owns_no_device_memory_and_still_lives_the_same_life():
+    pipe = cs.resampler(0.0, max_samples=MAXN)
+    x = _input(CASES[0], N1, 3)
+    a, b = pipe._start(), pipe._start()
+    assert np.array_equal(pipe._process(a, x), x) and np.array_equal(pipe._process(b, x), x)
+    pipe._done(b)
+    assert np.array_equal(pipe._process(a, x[:N2]), x[:N2])
+    pipe._done(a)
+    pipe._done(a)
+    pipe._done(b)
+    for _ in range(3):
+        pipe._done(pipe._start())
