@@ -9,6 +9,7 @@ from .pipes import (  # noqa: F401
     Pipe, compose, Chain, ChainConfig, dcBlocker, mixDown, mixUp, automaticGainControl,
     fmDemodulator, amDemodulator, resampler, iirFilter, firDecimator, wbFMDemodulator, firpfbchChannelizer,
     FmStereo, stereoFMDecoder, SymSync, symSyncR, fmDemWithSync, FirHilb, realToComplex, complexToReal,
+    symSyncC, firdes_rnyquist, CSDR_FIRFILT_ARKAISER, CSDR_FIRFILT_RRC,
     FskDem, fskDemodulator, FirFilt, firFilterCKaiser, firFilterC, firFilterR, firdes_kaiser, fir_groupdelay,
     IirSos, iirCFilter, iirFilterN, iirFilterSOS, iirdes_butter_lowpass,
     GmskDem, gmskDemodulator, firdes_gmsktx, firdes_gmskrx, firFilterRNyquist,

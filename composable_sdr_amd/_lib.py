@@ -89,6 +89,11 @@ SIGNATURES = {
     "csdr_symsync_get_taps_len": (_u32, [_vp]),
     "csdr_symsync_get_taps": (_i32, [_vp, _vp, _vp]),
     "csdr_symsync_destroy": (_i32, [_vp]),
+    "csdr_firdes_rnyquist": (_i32, [_i32, _u32, _u32, _f32, _f32, _vp]),
+    "csdr_symsync_set_taps": (_i32, [_vp, _vp, _u32]),
+    "csdr_symsync_set_rnyquist": (_i32, [_vp, _i32, _f32]),
+    "csdr_symsync_process_c": (_i32, [_vp, _vp, _u32, _vp, _pu32]),
+    "csdr_symsync_process_c_device": (_i32, [_vp, _vp, _u32, _vp, _vp, _vp]),
     "csdr_firhilb_create": (_i32, [_u32, _f32, _u32, _pp]),
     "csdr_firhilb_decim": (_i32, [_vp, _vp, _u32, _vp]),
     "csdr_firhilb_interp": (_i32, [_vp, _vp, _u32, _vp]),

@@ -482,14 +482,56 @@ struct csdr_symsync {
     int device; DeviceBuffers mem; uint32_t C, max_n; SymsyncDesign d;
     float *d_mf = nullptr, *d_dmf = nullptr, *d_hist = nullptr, *d_x = nullptr, *d_y = nullptr;
     SymsyncState *d_st = nullptr; uint32_t *d_ny = nullptr, *d_fault = nullptr;
+    // the sample type, fixed by the first process call after create, reset or a setter: 0 open, 1 F32 rows, 2 CF32 rows
+    int kind = 0;
+    float2 *d_histc = nullptr, *d_xc = nullptr, *d_yc = nullptr;    // the complex windows and staging: allocated by the first complex call
 };
 static int symsync_init_state(csdr_symsync *h)
 {
     CSDR_HIP(hipMemset(h->d_hist, 0, sizeof(float) * (size_t)h->C * (h->d.L - 1)));
+    if (h->d_histc) CSDR_HIP(hipMemset(h->d_histc, 0, sizeof(float2) * (size_t)h->C * (h->d.L - 1)));
+    h->kind = 0;
     std::vector<SymsyncState> st(h->C, h->d.init);
     CSDR_HIP(hipMemcpy(h->d_st, st.data(), sizeof(SymsyncState) * h->C, hipMemcpyHostToDevice));
     CSDR_HIP(hipMemset(h->d_fault, 0, sizeof(uint32_t)));
     return 0;
+}
+// the handle's sample type: the first process call fixes it, the other kind of call is refused with nothing touched
+static int symsync_take_kind(csdr_symsync *h, int kind)
+{
+    if (h->kind && h->kind != kind) {
+        set_error("symsync: the handle processes %s rows since its first call; reset, set_taps or set_rnyquist reopens the choice",
+                  h->kind == 1 ? "F32" : "CF32");
+        return CSDR_ERR_INVALID;
+    }
+    h->kind = kind;
+    return CSDR_OK;
+}
+// the checks in front of a complex call, and the complex windows the first one allocates (on the handle's device)
+static int symsync_complex_ready(csdr_symsync *h, uint32_t n, bool host)
+{
+    if (int r = block_check_n("symsync", n, h->max_n)) return r;
+    const size_t lds = symsyncc_lds_bytes(h->d.L, h->d.M);
+    if (lds > SYMSYNCC_MAX_LDS) {
+        set_error("symsync: complex rows need 8 (2 k m) npfb + 512 ((2 k m + 31) | 1) = %zu bytes of LDS, the limit is %zu", lds,
+                  SYMSYNCC_MAX_LDS);
+        return CSDR_ERR_INVALID;
+    }
+    int r = symsync_take_kind(h, 2); if (r) return r;
+    if (h->d_histc && (!host || h->d_xc)) return CSDR_OK;
+    DevGuard guard;
+    if ((r = block_select("symsync", guard, h->device))) return r;
+    const size_t C = h->C;
+    if (!h->d_histc && (r = block_zeros(h->mem, &h->d_histc, C * (h->d.L - 1)))) return r;
+    if (host && !h->d_xc && ((r = h->mem.alloc_n(&h->d_xc, C * h->max_n)) || (r = h->mem.alloc_n(&h->d_yc, C * h->max_n)))) return r;
+    return CSDR_OK;
+}
+static int symsync_launch_c(csdr_symsync *h, const void *d_x, uint32_t n, void *d_y, void *d_ny, void *stream)
+{
+    const SymsyncDesign &d = h->d;
+    SymsyncLaunch l{h->C, n, n, d.L, d.M, d.k_out, (float)d.k, d.b0, d.b1, d.b2, d.a1, d.a2, d.rate_adj};
+    return launch_symsyncc((const float2 *)d_x, (float2 *)d_y, (uint32_t *)d_ny, h->d_mf, h->d_dmf, h->d_histc, h->d_st, h->d_fault, l,
+                           (hipStream_t)stream);
 }
 extern "C" {
 int csdr_symsync_destroy(csdr_symsync *h) { return block_destroy(h); }
@@ -521,6 +563,7 @@ int csdr_symsync_process_device(csdr_symsync *h, const void *d_x, uint32_t n, vo
     if (!h || !d_ny) return block_null_arg("symsync");
     if (int r = block_check_n("symsync", n, h->max_n)) return r;
     if (n && (!d_x || !d_y)) { set_error("symsync: null buffer"); return CSDR_ERR_INVALID; }
+    if (int r = symsync_take_kind(h, 1)) return r;
     const SymsyncDesign &d = h->d;
     SymsyncLaunch l{h->C, n, n, d.L, d.M, d.k_out, (float)d.k, d.b0, d.b1, d.b2, d.a1, d.a2, d.rate_adj};
     return launch_symsync((const float *)d_x, (float *)d_y, (uint32_t *)d_ny, h->d_mf, h->d_dmf, h->d_hist, h->d_st, h->d_fault, l,
@@ -540,6 +583,58 @@ int csdr_symsync_process(csdr_symsync *h, const float *x, uint32_t n, float *y, 
     if (n) CSDR_HIP(hipMemcpy(y, h->d_y, sizeof(float) * (size_t)h->C * n, hipMemcpyDeviceToHost));
     if (fault) { set_error("symsync: a stream is faulted (del <= 0 or more than n outputs in a call); reset clears it"); return CSDR_ERR_SIZE; }
     return CSDR_OK;
+}
+int csdr_symsync_process_c_device(csdr_symsync *h, const void *d_x, uint32_t n, void *d_y, void *d_ny, void *stream)
+{
+    if (!h || !d_ny) return block_null_arg("symsync");
+    if (n && (!d_x || !d_y)) { set_error("symsync: null buffer"); return CSDR_ERR_INVALID; }
+    if (int r = symsync_complex_ready(h, n, false)) return r;
+    return symsync_launch_c(h, d_x, n, d_y, d_ny, stream);
+}
+int csdr_symsync_process_c(csdr_symsync *h, const float *x, uint32_t n, float *y, uint32_t *ny)
+{
+    if (!ny) return block_null_arg("symsync");
+    int r = block_check_call("symsync", h, x, n, y); if (r) return r;
+    DevGuard guard;
+    if ((r = block_select("symsync", guard, h->device))) return r;
+    if ((r = symsync_complex_ready(h, n, true))) return r;
+    if (n) CSDR_HIP(hipMemcpy(h->d_xc, x, sizeof(float2) * (size_t)h->C * n, hipMemcpyHostToDevice));
+    if ((r = symsync_launch_c(h, h->d_xc, n, h->d_yc, h->d_ny, nullptr))) return r;
+    uint32_t fault = 0;
+    CSDR_HIP(hipMemcpy(ny, h->d_ny, sizeof(uint32_t) * h->C, hipMemcpyDeviceToHost));
+    CSDR_HIP(hipMemcpy(&fault, h->d_fault, sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (n) CSDR_HIP(hipMemcpy(y, h->d_yc, sizeof(float2) * (size_t)h->C * n, hipMemcpyDeviceToHost));
+    if (fault) { set_error("symsync: a stream is faulted (del <= 0 or more than n outputs in a call); reset clears it"); return CSDR_ERR_SIZE; }
+    return CSDR_OK;
+}
+// symsync_create(k, M, H, H_len) behind create: new banks from the caller's prototype, then the state right after create
+int csdr_symsync_set_taps(csdr_symsync *h, const float *H, uint32_t H_len)
+{
+    if (!h || !H) return block_null_arg("symsync");
+    if (H_len != h->d.H_len) { set_error("symsync: %u prototype taps, the handle takes 2 npfb k m + 1 = %u", H_len, h->d.H_len); return CSDR_ERR_INVALID; }
+    bool ok = false;
+    for (uint32_t i = 0; i < H_len; i++) {
+        if (!std::isfinite(H[i])) { ok = false; break; }
+        if (H[i] != 0.f) ok = true;
+    }
+    if (!ok) { set_error("symsync: the prototype taps must be finite and not all zero"); return CSDR_ERR_INVALID; }
+    DevGuard guard;
+    int r = block_select("symsync", guard, h->device); if (r) return r;
+    CSDR_HIP(hipDeviceSynchronize());
+    h->d.H.assign(H, H + H_len);
+    symsync_set_prototype(h->d);
+    const size_t LM = h->d.mf.size();
+    CSDR_HIP(hipMemcpy(h->d_mf, h->d.mf.data(), sizeof(float) * LM, hipMemcpyHostToDevice));
+    CSDR_HIP(hipMemcpy(h->d_dmf, h->d.dmf.data(), sizeof(float) * LM, hipMemcpyHostToDevice));
+    return symsync_init_state(h);
+}
+// symsync_create_rnyquist(ftype, k, m, beta, npfb): the prototype at k npfb samples per symbol
+int csdr_symsync_set_rnyquist(csdr_symsync *h, int ftype, float beta)
+{
+    if (!h) return block_null_arg("symsync");
+    std::vector<float> H(h->d.H_len);
+    if (int r = csdr_firdes_rnyquist(ftype, h->d.k * h->d.M, h->d.m, beta, 0.f, H.data())) return r;
+    return csdr_symsync_set_taps(h, H.data(), h->d.H_len);
 }
 int csdr_symsync_reset(csdr_symsync *h)
 {
@@ -723,6 +818,23 @@ int csdr_firdes_kaiser(uint32_t n, float fc, float as_db, float mu, float *h)
     }
     const std::vector<float> t = design_firfilt_kaiser(n, fc, as_db);
     std::memcpy(h, t.data(), sizeof(float) * n);
+    return CSDR_OK;
+}
+int csdr_firdes_rnyquist(int ftype, uint32_t k, uint32_t m, float beta, float dt, float *h)
+{
+    const uint64_t n = 2ull * k * m + 1;
+    if (!h || (ftype != CSDR_FIRFILT_ARKAISER && ftype != CSDR_FIRFILT_RRC) || k < 2 || m < 1 || n > RNYQUIST_MAX_LEN ||
+        !(beta > 0.f && beta <= 1.f) || !(dt >= -1.f && dt <= 1.f)) {
+        set_error("firdes_rnyquist: bad arguments (ftype ARKAISER 7 or RRC 9, k >= 2, m >= 1, 2 k m + 1 <= %u, beta in (0, 1], dt in [-1, 1], h)",
+                  RNYQUIST_MAX_LEN);
+        return CSDR_ERR_INVALID;
+    }
+    const std::vector<float> t = design_rnyquist(ftype, k, m, beta, dt);
+    if (t.empty()) {
+        set_error("firdes_rnyquist: the ARKAISER bandwidth factor rho_hat of (m = %u, beta = %g) lies outside (0, 1)", m, (double)beta);
+        return CSDR_ERR_INVALID;
+    }
+    std::memcpy(h, t.data(), sizeof(float) * t.size());
     return CSDR_OK;
 }
 int csdr_fir_groupdelay(const float *h, uint32_t n, float fc, float *gd)

@@ -241,6 +241,8 @@ struct SymsyncDesign {
     SymsyncState init{};
 };
 SymsyncDesign design_symsync_kaiser(uint32_t k, uint32_t m, float beta, uint32_t M, float lf_bw, uint32_t k_out);
+// symsync_create(k, M, H, H_len) behind the prototype: from d.H (H_len taps) the derivative d.dH and both banks
+void symsync_set_prototype(SymsyncDesign &d);
 struct SymsyncLaunch {
     uint32_t C, n, cap, L, M, k_out;
     float kf, b0, b1, b2, a1, a2, rate_adj;
@@ -248,6 +250,18 @@ struct SymsyncLaunch {
 // x [C][n] -> y [C][cap] (row stride cap), ny [C]; hist [C][L - 1] and st [C] in place; *fault_any = 1 when a stream is faulted
 int launch_symsync(const float *x, float *y, uint32_t *ny, const float *mf, const float *dmf, float *hist, SymsyncState *st,
                    uint32_t *fault_any, const SymsyncLaunch &l, hipStream_t s);
+
+// ---- complex symbol synchroniser (kernels_symsyncc.hip; root-Nyquist designs in design.cpp) ----
+constexpr uint32_t RNYQUIST_MAX_LEN = 2 * 64 * 8 * 256 + 1;          // taps of a csdr_firdes_rnyquist prototype
+// liquid_firdes_prototype(CSDR_FIRFILT_ARKAISER | CSDR_FIRFILT_RRC, k, m, beta, dt): 2 k m + 1 taps, f64, rounded once; empty
+// when the ARKAISER bandwidth factor rho_hat falls outside (0, 1)
+std::vector<float> design_rnyquist(int ftype, uint32_t k, uint32_t m, float beta, float dt);
+// dynamic LDS of k_symsyncc in bytes: both banks and 64 complex windows; a handle is accepted up to SYMSYNCC_MAX_LDS
+constexpr size_t SYMSYNCC_MAX_LDS = 65536;
+size_t symsyncc_lds_bytes(uint32_t L, uint32_t M);
+// x [C][n] CF32 -> y [C][cap] CF32 (row stride cap), ny [C]; hist [C][L - 1] CF32 and st [C] in place, as launch_symsync
+int launch_symsyncc(const float2 *x, float2 *y, uint32_t *ny, const float *mf, const float *dmf, float2 *hist, SymsyncState *st,
+                    uint32_t *fault_any, const SymsyncLaunch &l, hipStream_t s);
 
 // ---- firhilbf: realToComplex / complexToReal (kernels_firhilb.hip; design in design.cpp) ----
 constexpr uint32_t FIRHILB_MAX_M = 16;               // filter semi-length m: 2 m quadrature taps, 2 m pairs of history

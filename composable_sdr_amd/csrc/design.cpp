@@ -3,6 +3,7 @@
 //   firpfbch_crcf_create_kaiser(0, M, 7, 80.0)            Liquid.chs:813
 //   nco_crcf_create(LIQUID_VCO) + set_frequency(offset)    Liquid.chs:816-818
 //   agc_crcf_squelch_set_threshold                         Liquid.chs:713
+#include "../../include/csdr.h"
 #include "csdr_internal.h"
 
 #include <cmath>
@@ -73,15 +74,15 @@ std::vector<float> design_pfb_taps(uint32_t M, uint32_t m, float As)
 }
 
 // liquid_firdes_kaiser(N, fc, As, 0): h[i] = sinc(2 fc t) w_kaiser(i), t = i - (N-1)/2 (f64).  The window's argument is
-// 2 t / wden, wden = N - 1 (what KAT1 pins) unless the caller passes another
-static std::vector<double> firdes_kaiser(uint32_t N, double fc, double As, double wden = 0.0)
+// 2 t / wden, wden = N - 1 (what KAT1 pins) unless the caller passes another; dt is liquid's fractional sample offset mu, added to t
+static std::vector<double> firdes_kaiser(uint32_t N, double fc, double As, double wden = 0.0, double dt = 0.0)
 {
     if (wden == 0.0) wden = (double)(N - 1);
     const double beta = kaiser_beta(As), ib = bessel_i0(beta);
     const double pi = 3.14159265358979323846;
     std::vector<double> h(N);
     for (uint32_t i = 0; i < N; i++) {
-        double t = (double)i - 0.5 * (double)(N - 1);
+        double t = (double)i - 0.5 * (double)(N - 1) + dt;
         double x = 2.0 * fc * t;
         double sinc = std::fabs(x) < 0.01
                           ? std::cos(pi * x / 2) * std::cos(pi * x / 4) * std::cos(pi * x / 8)
@@ -208,21 +209,12 @@ std::vector<float> design_firhilb(uint32_t m, float As)
     return hq;
 }
 
-// ---- symsync_rrrf_create_kaiser(k, m, beta, M) + set_lf_bw + set_output_rate (Liquid.chs:244-282), DESIGN.md 4.10 ----
-// liquid-dsp 1.3.2 as recalled (unpinned): H_len = 2 M k m + 1, Hf = liquid_firdes_kaiser(H_len, 0.75f / (k M), 40, 0) in f64,
-// H = Hf 2 0.75 rounded once to f32 (beta is ignored); the derivative, its scale and the loop filter in f32 as liquid does.
-SymsyncDesign design_symsync_kaiser(uint32_t k, uint32_t m, float beta, uint32_t M, float lf_bw, uint32_t k_out)
+// symsync_create(k, M, H, H_len)'s part behind the prototype d.H (H_len = 2 M k m + 1 taps, f32): the derivative with the
+// wrap-around ends, its 0.06 / max |H dH| scale and the two reversed tap-major banks, all in f32 as liquid does
+void symsync_set_prototype(SymsyncDesign &d)
 {
-    (void)beta;
-    SymsyncDesign d;
-    d.k = k; d.m = m; d.M = M; d.k_out = k_out;
-    d.H_len = 2 * M * k * m + 1;
-    d.L = d.H_len / M;                                                   // firpfb: integer division drops the last tap
-    const float fc = 0.75f / (float)(k * M);
-    std::vector<double> hd = firdes_kaiser(d.H_len, (double)fc, 40.0);
-    const uint32_t N = d.H_len;
-    d.H.resize(N); d.dH.resize(N);
-    for (uint32_t i = 0; i < N; i++) d.H[i] = (float)(hd[i] * 1.5);
+    const uint32_t N = d.H_len, M = d.M;
+    d.dH.resize(N);
     float hdh_max = 0.f;
     for (uint32_t i = 0; i < N; i++) {
         d.dH[i] = i == 0 ? d.H[1] - d.H[N - 1] : (i == N - 1 ? d.H[0] - d.H[i - 1] : d.H[i + 1] - d.H[i - 1]);
@@ -237,6 +229,24 @@ SymsyncDesign design_symsync_kaiser(uint32_t k, uint32_t m, float beta, uint32_t
             d.mf[(size_t)j * M + p] = d.H[p + (d.L - 1 - j) * M];          // loaded reversed: the newest sample meets H[p]
             d.dmf[(size_t)j * M + p] = d.dH[p + (d.L - 1 - j) * M];
         }
+}
+
+// ---- symsync_rrrf_create_kaiser(k, m, beta, M) + set_lf_bw + set_output_rate (Liquid.chs:244-282), DESIGN.md 4.10 ----
+// liquid-dsp 1.3.2 as recalled (unpinned): H_len = 2 M k m + 1, Hf = liquid_firdes_kaiser(H_len, 0.75f / (k M), 40, 0) in f64,
+// H = Hf 2 0.75 rounded once to f32 (beta is ignored); the derivative, its scale and the loop filter in f32 as liquid does.
+SymsyncDesign design_symsync_kaiser(uint32_t k, uint32_t m, float beta, uint32_t M, float lf_bw, uint32_t k_out)
+{
+    (void)beta;
+    SymsyncDesign d;
+    d.k = k; d.m = m; d.M = M; d.k_out = k_out;
+    d.H_len = 2 * M * k * m + 1;
+    d.L = d.H_len / M;                                                   // firpfb: integer division drops the last tap
+    const float fc = 0.75f / (float)(k * M);
+    std::vector<double> hd = firdes_kaiser(d.H_len, (double)fc, 40.0);
+    const uint32_t N = d.H_len;
+    d.H.resize(N);
+    for (uint32_t i = 0; i < N; i++) d.H[i] = (float)(hd[i] * 1.5);
+    symsync_set_prototype(d);
     // set_lf_bw(bt): B = {0.22 bt, 0, 0}, A = {1 - 0.5 (1 - bt), -0.495 (1 - bt), 0}; iirfiltsos divides both by A[0]
     const float alpha = 1.0f - lf_bw, lb = 0.22f * lf_bw, ha = 0.5f * alpha, hb = 0.495f * alpha;
     const float A0 = 1.0f - ha, A1 = -hb, A2 = 0.0f;
@@ -246,6 +256,47 @@ SymsyncDesign design_symsync_kaiser(uint32_t k, uint32_t m, float beta, uint32_t
     d.init.rate = (float)k / (float)k_out;                               // set_output_rate: rate = del = k / k_out
     d.init.del = d.init.rate;
     return d;
+}
+
+// ---- liquid_firdes_prototype(ARKAISER | RRC, k, m, beta, dt) (symSyncC, Liquid.chs:177-242), csdr_firdes_rnyquist; DESIGN.md 4.16 ----
+// n = 2 k m + 1 taps in f64.  RRC is liquid_firdes_rrcos' closed form.  ARKAISER is liquid_firdes_arkaiser as recalled: the
+// r-Kaiser filter with the approximation rho_hat of the bandwidth factor that minimises the inter-symbol interference of h * h
+// (the property tests/test_rnyquist_cpu.py pins); As comes from Kaiser's length formula, where liquid bisects an estimate
+// (deviation).  An empty vector: rho_hat outside (0, 1), where liquid switches to a second approximation not reproduced here.
+static std::vector<double> design_rnyquist_f64(int ftype, uint32_t k, uint32_t m, double beta, double dt)
+{
+    const double pi = 3.14159265358979323846;
+    const uint32_t n = 2 * k * m + 1;
+    std::vector<double> h(n);
+    if (ftype == CSDR_FIRFILT_RRC) {
+        for (uint32_t i = 0; i < n; i++) {
+            const double z = ((double)i + dt) / (double)k - (double)m;
+            const double g = 1.0 - 16.0 * beta * beta * z * z;
+            if (std::fabs(z) < 1e-12) h[i] = 1.0 - beta + 4.0 * beta / pi;
+            else if (std::fabs(g) < 1e-8)
+                h[i] = beta / std::sqrt(2.0) * ((1.0 + 2.0 / pi) * std::sin(pi / (4.0 * beta)) + (1.0 - 2.0 / pi) * std::cos(pi / (4.0 * beta)));
+            else h[i] = (std::sin(pi * z * (1.0 - beta)) + 4.0 * beta * z * std::cos(pi * z * (1.0 + beta))) / (pi * z * g);
+        }
+        return h;
+    }
+    const double lb = std::log(beta), lm = std::log((double)m);
+    const double c0 = 0.762886 + 0.067663 * lm, c1 = 0.065515, c2 = std::log(1.0 - 0.088 * std::pow((double)m, -1.6));
+    const double rho_hat = c0 + c1 * lb + c2 * lb * lb;
+    if (!(rho_hat > 0.0 && rho_hat < 1.0)) return {};
+    const double kf = 0.5 * (1.0 + beta * (1.0 - rho_hat)) / (double)k, del = beta * rho_hat / (double)k;
+    const double As = 14.26 * del * (double)n + 7.95;
+    h = firdes_kaiser(n, kf, As, 0.0, dt);
+    double e2 = 0.0;
+    for (double v : h) e2 += v * v;
+    const double g = std::sqrt((double)k / e2);
+    for (double &v : h) v *= g;
+    return h;
+}
+
+std::vector<float> design_rnyquist(int ftype, uint32_t k, uint32_t m, float beta, float dt)
+{
+    const std::vector<double> h = design_rnyquist_f64(ftype, k, m, (double)beta, (double)dt);
+    return std::vector<float>(h.begin(), h.end());
 }
 
 // ---- fskdem_create(m, k, bandwidth) (Liquid.chs:336-382), DESIGN.md 4.12 ----

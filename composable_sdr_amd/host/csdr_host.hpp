@@ -496,6 +496,35 @@ inline Pipe<std::vector<Array<float>>, std::vector<Array<float>>> symSyncR(uint3
     return p;
 }
 
+// ---- symSyncC m k (Liquid.chs:177-242; symsync_crcf_create_rnyquist(ARKAISER, k, m, 0.5, 32), lf_bw 0.01 and output rate 1 at
+// symsync_create's defaults) on the CF32 channel rows of one chunk, e.g. firpfbchChannelizer's: one csdr_symsync handle with one
+// stream per row for the whole run; row c of the output holds that stream's ny[c] symbols ----
+inline Pipe<std::vector<Array<cf32>>, std::vector<Array<cf32>>> symSyncC(uint32_t m, uint32_t k, uint32_t nchan, uint32_t max_in)
+{
+    Pipe<std::vector<Array<cf32>>, std::vector<Array<cf32>>> p;
+    p.start = [=]() {
+        csdr_symsync *h = nullptr;
+        check(csdr_symsync_create(k, m, 0.0f, 32, 0.01f, 1, nchan, max_in, &h));
+        std::shared_ptr<void> r(h, [](void *q) { csdr_symsync_destroy(static_cast<csdr_symsync *>(q)); });
+        check(csdr_symsync_set_rnyquist(h, CSDR_FIRFILT_ARKAISER, 0.5f));
+        return r;
+    };
+    p.process = [nchan](void *rr, const std::vector<Array<cf32>> &rows) {
+        if (rows.size() != nchan || rows[0].empty()) return std::vector<Array<cf32>>(rows.size());     // nx = 0 -> [empty]
+        const size_t n = rows[0].size();
+        Array<cf32> x(nchan * n), y(nchan * n);
+        for (uint32_t c = 0; c < nchan; c++) std::copy(rows[c].begin(), rows[c].end(), x.begin() + c * n);
+        std::vector<uint32_t> ny(nchan);
+        check(csdr_symsync_process_c(static_cast<csdr_symsync *>(rr), reinterpret_cast<const float *>(x.data()), (uint32_t)n,
+                                     reinterpret_cast<float *>(y.data()), ny.data()));
+        std::vector<Array<cf32>> out;
+        for (uint32_t c = 0; c < nchan; c++) out.emplace_back(y.begin() + c * n, y.begin() + c * n + ny[c]);
+        return out;
+    };
+    p.done = [](void *) {};
+    return p;
+}
+
 // ---- fskDemodulator m k bw (Liquid.chs:336-382) on the channel rows of one chunk: one csdr_fskdem handle with one stream
 // per row; row c of the output holds the n div k symbols of row c, the n mod k samples left over are dropped (:367-376) ----
 inline Pipe<std::vector<Array<cf32>>, std::vector<Array<uint32_t>>> FskDemodulator(uint32_t m, uint32_t k, float bw, uint32_t nchan,

@@ -255,9 +255,21 @@ def stereoFMDecoder(quadRate, decim, nchan=1, max_samples=1 << 16):
     return _method_pipe(lambda: FmStereo(quadRate, decim, nchan, max_samples))
 
 
+CSDR_FIRFILT_ARKAISER, CSDR_FIRFILT_RRC = 7, 9          # liquid's numbers, as Liquid.chs:225 and :160 pass them
+
+
+def firdes_rnyquist(ftype, k, m, beta, dt=0.0):
+    """liquid_firdes_prototype(ftype, k, m, beta, dt) for CSDR_FIRFILT_ARKAISER or CSDR_FIRFILT_RRC (`csdr_firdes_rnyquist`):
+    2 k m + 1 taps as F32, evaluated in f64 and rounded once.  No GPU needed"""
+    h = np.empty(2 * max(int(k), 0) * max(int(m), 0) + 1, dtype=np.float32)
+    check(lib().csdr_firdes_rnyquist(int(ftype), int(k), int(m), float(beta), float(dt), _ptr(h)))
+    return h
+
+
 class SymSync(_Resettable):
     """The `csdr_symsync_*` object: symSyncR k m beta npfb (set_lf_bw lf_bw, set_output_rate k_out) on `nchan` independent F32
-    streams (include/csdr.h)."""
+    streams (include/csdr.h), or, through `process_c`, symsync_crcf on CF32 streams.  The
+    first process call after create, reset or a setter fixes the sample type."""
     _block = "symsync"
 
     def __init__(self, k, m=4, beta=0.0, npfb=64, nchan=1, max_samples=1 << 16, lf_bw=0.05, k_out=2):
@@ -301,6 +313,54 @@ class SymSync(_Resettable):
         `stream`"""
         check(lib().csdr_symsync_process_device(self.h, C.c_void_p(d_x_ptr), n, C.c_void_p(d_y_ptr), C.c_void_p(d_ny_ptr),
                                                 C.c_void_p(stream)))
+
+
+    def set_taps(self, H):
+        """symsync_create(k, npfb, H, H_len): new banks from the prototype H (2 npfb k m + 1 taps); the state as after create"""
+        H = np.ascontiguousarray(H, dtype=np.float32).reshape(-1)
+        check(lib().csdr_symsync_set_taps(self.h, _ptr(H), H.size))
+
+    def set_rnyquist(self, ftype, beta):
+        """symsync_create_rnyquist(ftype, k, m, beta, npfb): firdes_rnyquist(ftype, k npfb, m, beta) as the prototype"""
+        check(lib().csdr_symsync_set_rnyquist(self.h, int(ftype), float(beta)))
+
+    def process_c(self, x):
+        """[nchan][n] (or [n]) complex64 -> (y complex64 [nchan][n], counts [nchan]): row c holds counts[c] outputs"""
+        x = _c64(x)
+        n = x.size // self.nchan
+        y = np.empty((self.nchan, n), dtype=np.complex64)
+        ny = np.zeros(self.nchan, dtype=np.uint32)
+        check(lib().csdr_symsync_process_c(self.h, _ptr(x), n, _ptr(y), ny.ctypes.data_as(C.POINTER(C.c_uint32))))
+        return y, ny
+
+    def process_c_device(self, d_x_ptr, n, d_y_ptr, d_ny_ptr, stream=0):
+        """Device-resident variant of process_c: raw device pointers (ints) for x, y [nchan][n] CF32 and counts [nchan];
+        enqueues on `stream`"""
+        check(lib().csdr_symsync_process_c_device(self.h, C.c_void_p(d_x_ptr), n, C.c_void_p(d_y_ptr), C.c_void_p(d_ny_ptr),
+                                                  C.c_void_p(stream)))
+
+
+def _symsyncc(m, k, nchan, max_samples):
+    s = SymSync(k, m, 0.0, 32, nchan, max_samples, lf_bw=0.01, k_out=1)
+    try:
+        s.set_rnyquist(CSDR_FIRFILT_ARKAISER, 0.5)
+    except Exception:
+        s.close()
+        raise
+    return s
+
+
+def _symsyncc_process(r, a):
+    y, ny = r.process_c(a)
+    out = [y[c, :ny[c]] for c in range(r.nchan)]
+    return out[0] if np.ndim(a) == 1 else out
+
+
+def symSyncC(m, k, nchan=1, max_samples=1 << 16):
+    """symSyncC m k (Liquid.chs:177-242: symsync_crcf_create_rnyquist(ARKAISER, k, m, 0.5, 32), lf_bw 0.01 and output rate 1
+    left at symsync_create's defaults) as a Pipe from complex64 arrays ([nchan][n], or [n]) to the synchronised symbols: a
+    list of per-stream arrays, or one array for [n].  It composes behind firpfbchChannelizer's rows"""
+    return Pipe(lambda: _symsyncc(m, k, nchan, max_samples), _symsyncc_process, lambda r: r.close())
 
 
 def symSyncR(k, m=4, beta=0.0, M=64, nchan=1, max_samples=1 << 16):

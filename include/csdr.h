@@ -277,6 +277,60 @@ int csdr_symsync_get_taps(const csdr_symsync *h, float *mf, float *dmf);
 int csdr_symsync_destroy(csdr_symsync *h);
 
 /* ------------------------------------------------------------------------ *
+ * symSyncC m k  (Liquid.chs:177-242), `nchan` independent CF32 streams: liquid's symsync_crcf, which is symsync_rrrf's
+ * macro on complex samples with the same real taps and the same loop.  The reference creates it with
+ * symsync_crcf_create_rnyquist(LIQUID_FIRFILT_ARKAISER, k, m, 0.5, 32) and leaves lf_bw (0.01) and the output rate (1) at
+ * symsync_create's defaults (Liquid.chs:223-232).  There is no new handle: a csdr_symsync handle learns new banks through
+ * two setters and complex rows through two process entry points.  liquid-dsp 1.3.2 as recalled: unpinned,
+ * except the two prototype designs.
+ *   csdr_firdes_rnyquist (no GPU needed): liquid_firdes_prototype(ftype, k, m, beta, dt), n = 2 k m + 1 taps, evaluated in
+ *     f64 and rounded once.
+ *     CSDR_FIRFILT_RRC: liquid_firdes_rrcos, the closed form (pinned by mathematics).  z = (i + dt) / k - m;
+ *       z = 0: 1 - beta + 4 beta / pi;  |z| = 1 / (4 beta) (taken as |1 - 16 beta^2 z^2| < 1e-8):
+ *       (beta / sqrt 2) [(1 + 2 / pi) sin(pi / (4 beta)) + (1 - 2 / pi) cos(pi / (4 beta))];  otherwise
+ *       [sin(pi z (1 - beta)) + 4 beta z cos(pi z (1 + beta))] / [pi z (1 - 16 beta^2 z^2)].  No further normalisation.
+ *     CSDR_FIRFILT_ARKAISER: liquid_firdes_arkaiser as recalled, the r-Kaiser filter with an approximated bandwidth factor:
+ *       rho_hat = c0 + c1 ln beta + c2 ln^2 beta, c0 = 0.762886 + 0.067663 ln m, c1 = 0.065515, c2 = ln(1 - 0.088 m^-1.6);
+ *       kf = 0.5 (1 + beta (1 - rho_hat)) / k, del = beta rho_hat / k; h = csdr_firdes_kaiser's function (n, kf, As) with t
+ *       shifted by dt, scaled to sum h^2 = k.  Pinned by the property it approximates: rho_hat lies within 0.02 of the rho
+ *       that minimises the inter-symbol interference of h * h, at no more than 3 times the least rms ISI
+ *       (tests/test_rnyquist_cpu.py).  DEVIATION: As = 14.26 del n + 7.95, Kaiser's length formula solved for As, where
+ *       liquid bisects an estimate.
+ *     CSDR_ERR_INVALID: another ftype, k < 2, m < 1, n > 2 64 8 256 + 1, beta outside (0, 1], dt outside [-1, 1], h NULL,
+ *       and an ARKAISER rho_hat outside (0, 1) (liquid switches to a second approximation there, not reproduced).
+ *   csdr_symsync_set_taps: liquid's symsync_create(k, npfb, H, H_len) behind create.  H_len must be the handle's
+ *     2 npfb k m + 1 (else CSDR_ERR_INVALID; so are NULL and taps that are not finite or all zero).  From H it builds what
+ *     create builds from its Kaiser prototype (dH with the wrap-around ends, the 0.06 / max |H dH| scale in f32, the two
+ *     reversed tap-major banks), uploads them and puts the handle back to its state right after create (synchronises).
+ *     csdr_symsync_get_taps reports the new banks.
+ *   csdr_symsync_set_rnyquist: symsync_create_rnyquist(ftype, k, m, beta, npfb) = csdr_firdes_rnyquist(ftype, k npfb, m,
+ *     beta, 0, H) + csdr_symsync_set_taps.  F32 and CF32 rows both run on whatever banks the handle holds.
+ *   Sample type: the first process call after create, reset, set_taps or set_rnyquist fixes whether the handle takes F32
+ *     rows (csdr_symsync_process*) or CF32 rows (csdr_symsync_process_c*); the other kind of call is CSDR_ERR_INVALID and
+ *     touches nothing.  The complex windows are allocated by the first complex call.
+ *   csdr_symsync_process_c*: x is [nchan][n] interleaved CF32, y is [nchan][n] CF32 (row stride n), row c holding ny[c]
+ *     outputs.  Per input sample as csdr_symsync above with MF_b and dMF_b complex: y = (MF.re / k, MF.im / k) and
+ *     q = clip(MF.re dMF.re + MF.im dMF.im, -1, 1) = Re(conj(MF) dMF).
+ *   Arithmetic: plain f32 without contraction; MF.re and MF.im (and dMF's) are independent sums, oldest sample first,
+ *     starting from the first product; q is two rounded products and one add; the rest as for F32 rows.  The output does
+ *     not depend on the chunking, on nchan or on host versus device entry, bit for bit.  The fault rule is the F32 rows'.
+ *   Limit of the complex calls (CSDR_ERR_INVALID otherwise; F32 rows are not affected): both banks and 64 complex windows
+ *     share 64 KiB of LDS, 8 (2 k m) npfb + 512 ((2 k m + 31) | 1) <= 65536 bytes.  Every handle with 2 k m <= 64 and
+ *     npfb <= 32 fits, and so does (k, m, npfb) = (4, 4, 64).
+ * ------------------------------------------------------------------------ */
+#define CSDR_FIRFILT_ARKAISER 7   /* liquid's numbers, as Liquid.chs:225 and :160 pass them */
+#define CSDR_FIRFILT_RRC      9
+int csdr_firdes_rnyquist(int ftype, uint32_t k, uint32_t m, float beta, float dt, float *h);   /* n = 2 k m + 1 taps */
+/* Liquid.chs:177-242: liquid's symsync_crcf_create(k, npfb, H, H_len) on an existing handle */
+int csdr_symsync_set_taps(csdr_symsync *h, const float *H, uint32_t H_len);
+/* Liquid.chs:177-242: symsync_crcf_create_rnyquist(ftype, k, m, beta, npfb) on an existing handle (:228) */
+int csdr_symsync_set_rnyquist(csdr_symsync *h, int ftype, float beta);
+/* Liquid.chs:177-242: symsync_crcf_execute (:188-191, :242); x, y interleaved CF32 [nchan][n] */
+int csdr_symsync_process_c(csdr_symsync *h, const float *x, uint32_t n, float *y, uint32_t *ny);
+/* Liquid.chs:177-242, device buffers: d_x, d_y [nchan][n] CF32, d_ny [nchan] uint32; enqueued on `stream`, no synchronisation */
+int csdr_symsync_process_c_device(csdr_symsync *h, const void *d_x, uint32_t n, void *d_y, void *d_ny, void *stream);
+
+/* ------------------------------------------------------------------------ *
  * realToComplex / complexToReal  (Liquid.chs:503-546; the audio-file source mixUp (2 pi 0.5) . realToComplex,
  * Source.chs:273-307).  Replaces firhilbf_create(m, As) (firhilbCreate passes 5, 60.0, Liquid.chs:520-525) with
  * firhilbf_decim_execute_block (Liquid.chs:530-534) and firhilbf_interp_execute_block (Liquid.chs:539-543).
