@@ -96,7 +96,7 @@ int  plan4096_create(const FusedConfig &cfg, ChainPlan **out);
 // second-generation run kernel of the M = 256 chain (kernels_fused_v2.hip): whole-band calls of >= run_min_tiles tiles.
 // run_args points at a RunArgs (fused_common.h) the plan fills.
 int  run256_v2_launch(const void *run_args, bool fm, unsigned G, unsigned nruns, hipStream_t s);
-int  run256_v2_blocks_per_cu(bool fm);
+int  run256_v2_blocks_per_cu(bool fm, unsigned G);
 // RunArgs::nowu launches: the near-DC channels of every run's first 112 frames get what the true DC state at the run's start adds (Rt: host table
 // [2 parities][DCFIX_F][4], fused_common.h)
 int  run256_dcfix_launch(const void *run_args, bool fm, unsigned nruns, const float2 *Rt, hipStream_t s);

@@ -542,7 +542,7 @@ int FusedPlan::init()
     for (int k = 0; k < 17; k++) A.b256[k] = (float)std::pow(beta, 256.0 * k);
     for (int k = 0; k < 16; k++) A.bj[k] = (float)std::pow(beta, (double)k);
     if (const char *e = diag_env("CSDR_CUS")) { if (atoi(e) > 0 && (uint32_t)atoi(e) < cus) cus = (uint32_t)atoi(e); }     // experiments: a plan sized for a CU-masked stream
-    resident_wgs_v2 = (uint32_t)(cus * run256_v2_blocks_per_cu(cfg.fm));
+    resident_wgs_v2 = (uint32_t)(cus * run256_v2_blocks_per_cu(cfg.fm, cfg.G));
     if (const char *e = diag_env("CSDR_RESIDENT_WGS")) resident_wgs_v2 = (uint32_t)atol(e);
 #ifdef CSDR_WITH_RUN256_V3          // variant build only (tools/variants/build_run256_v3.sh): round 4's one-workgroup-per-CU experiment
     if (const char *e = diag_env("CSDR_RUN_V3")) use_v3 = atoi(e) != 0;
@@ -621,7 +621,9 @@ int FusedPlan::run(const FusedCall &call, void *out, hipStream_t s, KernelTimer 
         // priority per tile instead was no better
         static const float v2_weight_cf[8] = {1.2f, 0.8f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f};
         static const float v2_weight_fm[8] = {1.24f, 0.76f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f};      // with whole-line stores the younger workgroup loses more (r03 trace: 4.8 vs 7.6 us per tile)
-        const float *v2_weight = c.fm ? v2_weight_fm : v2_weight_cf;
+        // whole-band FM (one tile buffer, three workgroups per CU): shares of the oldest, the middle and the youngest workgroup of a CU
+        static const float v2_weight_fm3[8] = {1.45f, 1.f, 0.55f, 1.f, 1.f, 1.f, 1.f, 1.f};   // measured: equal thirds 226 us, 1.3 : 1 : 0.7 217, 1.45 : 1 : 0.55 211
+        const float *v2_weight = c.fm ? ((cus && nruns == 3 * cus) ? v2_weight_fm3 : v2_weight_fm) : v2_weight_cf;
         static const float equal_weight[8] = {1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f};
         static const bool pd_equal = diag_env("CSDR_PD_EQUAL") != nullptr;
         RA.split = make_split(A.nb, nruns, cus, (call.indep && pd_equal) ? equal_weight : ((v2 && !diag_env("CSDR_RUN_WEIGHTS")) ? v2_weight : slot_weight));

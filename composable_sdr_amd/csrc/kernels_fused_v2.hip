@@ -16,6 +16,8 @@
 //     the previous frame of a channel is one DPP row shift away and a 16-lane row writes 64 (F32) / 128 (CF32)
 //     contiguous bytes of a channel row: no transpose of Y or of the demodulated samples through LDS at all.
 //   * two workgroups per CU (70 KiB of LDS each), up to 256 VGPRs: taps and pass-1 twiddles live in registers.
+//   * <FM, 1> (the headline) is the ONE-BUFFER form: one tile buffer + the taps as an LDS table (52 KiB), 167 VGPRs, three workgroups per CU.
+//     A tile's buffer is dead behind the Z reads of pass 2 (barrier B_g); the next tile's DMA goes into it while freqdem and the stores run.
 //
 // LDS map (float2 units): two tile buffers of 4096 (tile b lives in buffer b & 1 from its DMA to its last Z read, the
 // other buffer receives tile b + 1 meanwhile): raw image, 16-byte XOR swizzle (run-major b128 and column-major b64 both
@@ -51,6 +53,13 @@
                         // pass 1 touches (X reads, Z writes) and the 16 frames a b128 group of pass 2 reads land on different bank halves --
                         // tools/lds_conflicts_run256v2.py: 382 -> 286 LDS cycles per tile and wave, conflict-free.  0: round 4's dense image (A/B)
 #endif
+#ifndef V2_ONE_WGS
+#define V2_ONE_WGS 3    // workgroups per CU the one-buffer form <FM, 1> is compiled for (2: the one-buffer step alone, for A/B)
+#endif
+#ifndef V2_ONE_BURST
+#define V2_ONE_BURST 1  // one-buffer form: 1 = all eight DMA pieces of the next tile right behind B_g; 0 (A/B): two behind B_g, two behind each of the
+                        // freqdem quads 0..2 -- measured 1 % slower: the pieces need every cycle of the tail to land, not the address unit's 128
+#endif
 #ifndef V2_SNOP
 // Wait states in front of the asm stores would cover a scalar base that comes straight out of a spill lane (v_readlane ->
 // VMEM hazard, fused_v2_common.h); they cost 1 % of the launch, and this kernel has no SGPR spills (the bases are SALU
@@ -70,7 +79,11 @@ constexpr int V2_FS2 = (int)V2_FSB / 8;            // the same in float2
 constexpr int V2_BUF = 16 * V2_FS2;                // float2 per tile buffer (32 KiB + 2 KiB of padding)
 // two tile buffers, then: STASH 256, T 16, RED 16, pass-1 twiddles 256
 constexpr int V2_STASH = 2 * V2_BUF;
-constexpr int V2_F2 = V2_STASH + 256 + 32 + 256 + (V2_COLSCAN ? 512 : 0);   // 9248 float2 = 73 984 B: two workgroups per CU (dense image: 69 888 B)
+constexpr int V2_AUX2 = 256 + 32 + 256 + (V2_COLSCAN ? 512 : 0);
+constexpr int V2_F2 = V2_STASH + V2_AUX2;           // 9248 float2 = 73 984 B: two workgroups per CU (dense image: 69 888 B)
+// <FM, 1> (the one-buffer form, below): one tile buffer, the same tables, then the 14 x 256 FIR taps as an LDS table: 6688 float2 = 53 504 B,
+// three workgroups per CU
+constexpr int V2_F2_ONE = V2_BUF + V2_AUX2 + P * M256 / 2;
 #define V2_ZSW(f) (V2_PAD ? (((f) >> 1) & 7) : ((f) & 7))       // 16-byte slot swizzle of frame f's Z rows
 // 16-byte slot swizzle of run a (= 16 consecutive samples = 128 bytes) of a frame, raw image / y' / X.  The dense image used (a >> 1) & 7:
 // conflict-free for the b128 READS (lane groups {0-3,12-15,20-27}, {4-11,16-19,28-31}, ... over 64 banks: MI355X_MICROARCH.md, LDS) but
@@ -95,18 +108,24 @@ struct V2Args {
 // 256 threads: thread (q, f2), q = s NK1 + j1, takes row k1' = G j1 and the slice s of the 16 output slots, and the slice is
 // wave-uniform (G = 8: up to one lane bit), so that every wave runs a pass-2 butterfly pruned to its own quad of slots.
 template <bool FM, int G>
-__global__ __launch_bounds__(256, 2) void k_run256v2(V2Args VA)
+__global__ __launch_bounds__(256, (FM && G == 1) ? V2_ONE_WGS : 2) void k_run256v2(V2Args VA)
 {
     static_assert(G == 1 || G == 2 || G == 4 || G == 8, "interleaved shards: G = 2, 4, 8");
     constexpr int NK1 = 16 / G;                         // owned pass-1 rows per frame = output slots per slice
+    // ONE: the one-buffer form of the whole-band FM kernel.  Every tile lives in the same buffer: it is dead once every wave has read its Z rows
+    // in pass 2 (barrier B_g), and the next tile's DMA goes into it piece by piece while freqdem and the output stores run.  With the FIR taps in
+    // an LDS table the tile loop fits 168 VGPRs: three workgroups per CU (12 waves) instead of two.
+    constexpr bool ONE = FM && G == 1;
     const RunArgs &RA = VA.r;
     const TileArgs &A = RA.t;
-    __shared__ __attribute__((aligned(16))) float2 L[V2_F2];
-    float2 *R = L, *ST = L + V2_STASH, *Tt = ST + 256, *red = Tt + 16;
+    __shared__ __attribute__((aligned(16))) float2 L[(ONE && V2_ONE_WGS >= 3) ? V2_F2_ONE : V2_F2];     // (V2_ONE_WGS=2: the LDS of the two-buffer form keeps a third workgroup off the CU)
+    float2 *R = L, *ST = L + (ONE ? V2_BUF : V2_STASH), *Tt = ST + 256, *red = Tt + 16;
     float2 *tw_s = red + 16;
     float2 *TRc = tw_s + 256, *Ec = TRc + 256;          // V2_COLSCAN: run totals, run carries of the tile in work
     (void)TRc; (void)Ec;
-    float2 *H = L + V2_BUF;                             // run start only: the halo tile's image, then scratch of the one-frame DFT (buffer 1 is free until the first tile's B_a)
+    float *TP = reinterpret_cast<float *>(L + (ONE ? V2_BUF : V2_STASH) + V2_AUX2);     // ONE: taps table, TP[256 n + j] = tap n of branch j (thread j reads what it wrote)
+    float2 *H = ONE ? L : L + V2_BUF;                   // run start only: the halo tile's image (two buffers: buffer 1 is free until the first tile's B_a)
+    float2 *HS = ONE ? reinterpret_cast<float2 *>(TP) : H;     // run start only: scratch of the one-frame DFT (ONE: the taps table's place, filled behind it)
     float2 *E = ST;                                     // run start only: 256 run carries (the stash area, before the stash is initialised)
     const int tid = threadIdx.x, j = tid;
     const unsigned w = blockIdx.x;
@@ -142,8 +161,13 @@ __global__ __launch_bounds__(256, 2) void k_run256v2(V2Args VA)
     const bool cold = w > 0 || RA.indep;
     const int halo = (int)first - 1;
     auto tile_ptr = [&](int t) -> const float4 * { return t >= 0 ? x4 + (size_t)t * 2048 : RA.prev_tail + (size_t)(WU + 1 + t) * 2048; };
-    if (first < last) dma_tile<false, 2 * V2_FSB>(x4 + (size_t)first * 2048, goff, lds_wave);
-    if (cold) dma_tile<false, 2 * V2_FSB>(tile_ptr(halo), goff, lds_wave + (unsigned)(V2_BUF * 8));
+    if (ONE) {                                          // one buffer: the halo tile first; the first tile follows when the halo image has been read
+        if (cold) dma_tile<false, 2 * V2_FSB>(tile_ptr(halo), goff, lds_wave);
+        else if (first < last) dma_tile<false, 2 * V2_FSB>(x4 + (size_t)first * 2048, goff, lds_wave);
+    } else {
+        if (first < last) dma_tile<false, 2 * V2_FSB>(x4 + (size_t)first * 2048, goff, lds_wave);
+        if (cold) dma_tile<false, 2 * V2_FSB>(tile_ptr(halo), goff, lds_wave + (unsigned)(V2_BUF * 8));
+    }
     float h[P];
 #pragma unroll
     for (int n = 0; n < P; n++) h[n] = A.taps[(M256 - 1 - j) + n * M256];
@@ -202,7 +226,7 @@ __global__ __launch_bounds__(256, 2) void k_run256v2(V2Args VA)
         };
         const unsigned rot = RA.wu_rot ? w : 0u;
         unsigned i = 0;
-        if (nwu == 6 && RA.wu_batch6) {
+        if (!ONE && nwu == 6 && RA.wu_batch6) {          // (ONE: 168 VGPRs do not hold six tiles; the batches of three below)
             // the usual window: all six tiles requested before the first is folded (192 of the prologue's registers: nothing else is
             // live yet) -- one memory latency instead of two behind the DMA'd halo and first tile
             float4 rb[8], rc[8], rd[8], re[8], rf[8];
@@ -244,6 +268,7 @@ __global__ __launch_bounds__(256, 2) void k_run256v2(V2Args VA)
         E[tid] = cfma(cfma(ch, bf, vb), br, E[tid]);
         c = cfma(ch, A.b256[16], ve);
         __syncthreads();
+        if (ONE && first < last) dma_tile<false, 2 * V2_FSB>(x4 + (size_t)first * 2048, goff, lds_wave);     // every thread has read the halo image
 #pragma unroll
         for (int f = 3; f < NB; f++) wa[f] = cfma(E[16 * f + (j >> 4)], kj, wa[f]);
         w2 = cfma(E[16 * 2 + (j >> 4)], kj, w2);
@@ -270,22 +295,22 @@ __global__ __launch_bounds__(256, 2) void k_run256v2(V2Args VA)
             const float2 s2 = (n == P - 1) ? w2 : wa[NB - 1 - n];
             acc = __builtin_elementwise_fma((v2f){s2.x, s2.y}, (v2f){h[n], h[n]}, acc);
         }
-        H[j] = to_f2(acc);
+        HS[j] = to_f2(acc);
         __syncthreads();
         v2f vv[16];
         if (tid < 16) {
 #pragma unroll
-            for (int a = 0; a < 16; a++) vv[a] = to_v(H[16 * a + tid]);
+            for (int a = 0; a < 16; a++) vv[a] = to_v(HS[16 * a + tid]);
             fft16_v(vv);
 #pragma unroll
             for (int i = (G > 1 ? 0 : 1); i < 16; i++) vv[i] = cmul_v(vv[i], to_v(tw_s[16 * ((XIDX(i) + (G > 1 ? (int)A.c0 : 0)) & 15) + tid]));
 #pragma unroll
-            for (int i = 0; i < 16; i++) H[256 + 16 * XIDX(i) + tid] = to_f2(vv[i]);     // Z[k1'][b1], k1 = g + k1'
+            for (int i = 0; i < 16; i++) HS[256 + 16 * XIDX(i) + tid] = to_f2(vv[i]);     // Z[k1'][b1], k1 = g + k1'
         }
         __syncthreads();
         if (tid < 16) {                                 // thread row q = tid: pass-1 row k1' = G (q mod NK1); every slot is written, the row's own slice is read later
 #pragma unroll
-            for (int b = 0; b < 16; b++) vv[b] = to_v(H[256 + 16 * (G * (tid % NK1)) + b]);
+            for (int b = 0; b < 16; b++) vv[b] = to_v(HS[256 + 16 * (G * (tid % NK1)) + b]);
             fft16_v(vv);                                // vv[i] = Y[k1 + 16 XIDX(i)]
 #pragma unroll
             for (int i = 0; i < 16; i++) ST[tid * 16 + i] = to_f2(vv[i]);
@@ -297,6 +322,10 @@ __global__ __launch_bounds__(256, 2) void k_run256v2(V2Args VA)
         __syncthreads();
     }
 
+    if (ONE) {
+#pragma unroll
+        for (int n = 0; n < P; n++) TP[M256 * n + j] = h[n];
+    }
     // ------------------------------------------------------------------ per-thread constants of the tile loop
     const v2f Wav = to_v(Wa), Wbv = to_v(Wb);
     const float na = opaque_v(-A.alpha), be = opaque_v(A.beta);
@@ -307,12 +336,12 @@ __global__ __launch_bounds__(256, 2) void k_run256v2(V2Args VA)
                      opaque_v(1e-37f), opaque_v(A.fm_ref), opaque_v(RA.pk.hp), opaque_v(RA.pk.pi)};
     // LDS byte offsets inside a tile buffer that do not change from tile to tile
     const int q = tid, sw = V2_RSW(q & 15);
-    const unsigned raw_a = (unsigned)q * 128u + (unsigned)(q >> 4) * (V2_FSB - 2048u) + ((unsigned)sw << 4);   // slot i of my run: raw_a ^ (i << 4)
+    const unsigned raw_a_ = (unsigned)q * 128u + (unsigned)(q >> 4) * (V2_FSB - 2048u) + ((unsigned)sw << 4);   // slot i of my run: raw_a ^ (i << 4)
     const int f1 = tid >> 4, b1 = tid & 15;                                     // pass 1: frame, column digit
     const int k1 = tid >> 4, f2 = tid & 15;                                     // pass 2 / tail: channel digit, frame
-    const unsigned x_a = (unsigned)f1 * V2_FSB + (unsigned)b1 * 8u;             // X[f1][16 a + b1]: (x_a ^ (V2_RSW(a) << 4)) + 128 a
+    const unsigned x_a_ = (unsigned)f1 * V2_FSB + (unsigned)b1 * 8u;             // X[f1][16 a + b1]: (x_a ^ (V2_RSW(a) << 4)) + 128 a
     const unsigned zw_a = (unsigned)f1 * V2_FSB + (unsigned)((((b1 >> 1) ^ V2_ZSW(f1)) << 1) | (b1 & 1)) * 8u;   // Z[f1][k1][b1]: + 128 k1
-    const unsigned z_a = (unsigned)f2 * V2_FSB + (unsigned)k1 * 128u + ((unsigned)V2_ZSW(f2) << 4);             // pair i of Z[f2][k1][.]: z_a ^ (i << 4)
+    const unsigned z_a_ = (unsigned)f2 * V2_FSB + (unsigned)k1 * 128u + ((unsigned)V2_ZSW(f2) << 4);             // pair i of Z[f2][k1][.]: z_a ^ (i << 4)
     // interleaved shard: thread row q = k1 = s NK1 + j1; output row of channel (g + G j1) + 16 k2 in the shard's [M / G][nf] plane: j1 + NK1 k2
     const int j1 = k1 % NK1, hb = (G == 8) ? ((k1 >> 1) & 1) : 0;              // G = 8: lane bit of the slice (slots S0 + 2 hb, S0 + 2 hb + 1)
     const unsigned z_a_g = (unsigned)f2 * V2_FSB + (unsigned)(G * j1) * 128u + ((unsigned)V2_ZSW(f2) << 4);
@@ -332,13 +361,17 @@ __global__ __launch_bounds__(256, 2) void k_run256v2(V2Args VA)
     auto tile = [&](float2 (&old)[NB], float2 (&nw)[NB], unsigned b_, const int par) {
         unsigned b = (unsigned)__builtin_amdgcn_readfirstlane((int)b_);            // keep the tile index (store / DMA bases) in SGPRs
         asm volatile("" : "+s"(b));
-        char *B = reinterpret_cast<char *>(L) + par * (V2_BUF * 8);             // this tile's buffer
+        char *B = reinterpret_cast<char *>(L) + (ONE ? 0 : par) * (V2_BUF * 8);             // this tile's buffer
         float2 *Bf = reinterpret_cast<float2 *>(B);
         if (RA.prio_div) {
             // the CU issues oldest-wave-first: without this the older of a CU's two workgroups finishes its run ~35 % earlier
             // and the CU is half empty for the rest of the launch; alternating the priority per tile shares the issue slots
             if (((b_ - first) + w / RA.prio_div) & 1u) __builtin_amdgcn_s_setprio(1); else __builtin_amdgcn_s_setprio(0);
         }
+        // ONE: what follows from the thread index alone (LDS addresses, store offsets) is recomputed where it is used, from a copy of the index that
+        // hipcc cannot see through: as loop invariants these values are ~40 VGPRs that the 168 of three workgroups per CU do not have
+        int tid_t = tid;
+        if (ONE) asm volatile("" : "+v"(tid_t));
         V2STAMP(0);
         if (G == 1 && b + 1 == last && tid == 0) {      // the DC state in front of the next run's halo tile (launches without warm-up windows)
             if (kernarg_u32_s<offsetof(V2Args, r.nowu)>()) kernarg_ptr_s<offsetof(V2Args, r.cpre)>()[w + 1] = c;
@@ -354,8 +387,15 @@ __global__ __launch_bounds__(256, 2) void k_run256v2(V2Args VA)
             else dma_tile<false, 2 * V2_FSB>(x4 + (size_t)(b + 1) * 2048, goff, lds_wave + (unsigned)(par ^ 1) * (V2_BUF * 8u));
         }
 #else
-        if (!(V2_ABLATE & 1) && b + 1 < last) dma_tile<false, 2 * V2_FSB>(x4 + (size_t)(b + 1) * 2048, goff, lds_wave + (unsigned)(par ^ 1) * (V2_BUF * 8u));
+        if (!ONE && !(V2_ABLATE & 1) && b + 1 < last) dma_tile<false, 2 * V2_FSB>(x4 + (size_t)(b + 1) * 2048, goff, lds_wave + (unsigned)(par ^ 1) * (V2_BUF * 8u));
 #endif
+        // ONE: the next tile's image goes into this same buffer behind B_g, two of its eight pieces at a time
+        auto next_pieces = [&](const int it) {
+            if (ONE && !(V2_ABLATE & 1) && b + 1 < last) {
+                dma_piece<2 * V2_FSB>(x4 + (size_t)(b + 1) * 2048, goff, lds_wave, it);
+                dma_piece<2 * V2_FSB>(x4 + (size_t)(b + 1) * 2048, goff, lds_wave, it + 1);
+            }
+        };
 #if V2_COLSCAN
         // ---- DC blocker on the column-layout registers: thread j reads its raw column once; a run of 16 consecutive samples is one
         // 16-lane DPP row of one frame, so the zero-state scan inside a run is four v_fmac_dpp steps per component (col_run_scan);
@@ -387,6 +427,7 @@ __global__ __launch_bounds__(256, 2) void k_run256v2(V2Args VA)
         // missing: it is added in column layout below), then the blocker itself from that state
         v4f xr[8];
         float2 s = make_float2(0.f, 0.f);
+        const unsigned raw_a = ONE ? (unsigned)tid_t * 128u + (unsigned)(tid_t >> 4) * (V2_FSB - 2048u) + ((unsigned)V2_RSW(tid_t & 15) << 4) : raw_a_;
 #pragma unroll
         for (int i = 0; i < 8; i++) {
             xr[i] = *reinterpret_cast<const v4f *>(B + (raw_a ^ (unsigned)(i << 4)));
@@ -401,7 +442,7 @@ __global__ __launch_bounds__(256, 2) void k_run256v2(V2Args VA)
             t = dpp2<0x114>(s); s = cfma(t, A.b16[4], s);
             t = dpp2<0x118>(s); s = cfma(t, A.b16[8], s);
         }
-        if ((q & 15) == 15) Tt[q >> 4] = s;
+        if (((ONE ? tid_t : q) & 15) == 15) Tt[(ONE ? tid_t : q) >> 4] = s;
         s = dpp2<0x111>(s);
 #pragma unroll
         for (int i = 0; i < 8; i++) {
@@ -432,8 +473,9 @@ __global__ __launch_bounds__(256, 2) void k_run256v2(V2Args VA)
         }
 #endif
         if (b + 1 == A.nb) {                            // the stream's last 13 frames of y
+            float2 *yo = (ONE ? kernarg_ptr_s<offsetof(V2Args, r.t.yhist_out)>() : A.yhist_out) + (ONE ? tid_t : j);
 #pragma unroll
-            for (int f = 3; f < NB; f++) A.yhist_out[(f - 3) * M256 + j] = nw[f];
+            for (int f = 3; f < NB; f++) yo[(f - 3) * M256] = nw[f];
         }
 #pragma unroll
         for (int f = 0; f < NB; f += 2) {
@@ -444,6 +486,9 @@ __global__ __launch_bounds__(256, 2) void k_run256v2(V2Args VA)
         V2STAMP(4);
         // ---- polyphase FIR on the pre-mixed window, four frames at a time (independent accumulators); X goes where the
         // thread's column came from
+        float ht[P];                                    // ONE: the taps come out of the LDS table for the FIR only
+#pragma unroll
+        for (int n = 0; n < P; n++) ht[n] = ONE ? TP[M256 * n + j] : h[n];
 #pragma unroll
         for (int f0 = 0; f0 < NB; f0 += 4) {
             v2f acc[4] = {{0.f, 0.f}, {0.f, 0.f}, {0.f, 0.f}, {0.f, 0.f}};
@@ -453,7 +498,7 @@ __global__ __launch_bounds__(256, 2) void k_run256v2(V2Args VA)
                 for (int u = 0; u < 4; u++) {
                     const int i = f0 + u - n;
                     const float2 s2 = (i >= 0) ? nw[i] : old[NB + i];
-                    const v2f sv = {s2.x, s2.y}, hv = {h[n], h[n]};
+                    const v2f sv = {s2.x, s2.y}, hv = {ht[n], ht[n]};
                     acc[u] = __builtin_elementwise_fma(sv, hv, acc[u]);
                 }
             }
@@ -465,6 +510,7 @@ __global__ __launch_bounds__(256, 2) void k_run256v2(V2Args VA)
         V2STAMP(6);
         // ---- DFT pass 1: thread (f1, b1)
         v2f vv[16];
+        const unsigned x_a = ONE ? (unsigned)(tid_t >> 4) * V2_FSB + (unsigned)(tid_t & 15) * 8u : x_a_;
 #pragma unroll
         for (int a = 0; a < 16; a++) vv[a] = to_v(*reinterpret_cast<const float2 *>(B + (x_a ^ (unsigned)(V2_RSW(a) << 4)) + 128 * a));
         if (!(V2_ABLATE & 16)) fft16_v(vv);
@@ -568,24 +614,31 @@ __global__ __launch_bounds__(256, 2) void k_run256v2(V2Args VA)
             return;
         }
         // ---- DFT pass 2: thread (k1, f2) reads its 16 consecutive Z values as eight 16-byte pairs
+        const unsigned z_a = ONE ? (unsigned)(tid_t & 15) * V2_FSB + (unsigned)(tid_t >> 4) * 128u + ((unsigned)V2_ZSW(tid_t & 15) << 4) : z_a_;
 #pragma unroll
         for (int i = 0; i < 8; i++) {
             const v4f v = *reinterpret_cast<const v4f *>(B + (z_a ^ (unsigned)(i << 4)));
             vv[2 * i] = (v2f){v.x, v.y}; vv[2 * i + 1] = (v2f){v.z, v.w};
+        }
+        if (ONE) {
+            bar();                                      // B_g: every wave holds its Z rows: the buffer is free for the next tile
+            next_pieces(0);
+            if (V2_ONE_BURST) { next_pieces(2); next_pieces(4); next_pieces(6); }
         }
         if (!(V2_ABLATE & 16)) fft16_v(vv);             // vv[i] = Y[k1 + 16 XIDX(i)] of frame f2
         V2STAMP(11);
         if (G == 1 && cold && b - first < 7u && kernarg_u32_s<offsetof(V2Args, r.nowu)>()) {   // (uniform) the run's first seven tiles: Y of the channels around DC for k_run256_dcfix
             // (the kernel arguments are re-read here, behind an opaque copy of the pointer: as loop invariants they cost the tile loop SGPRs it
             // does not have -- the asm stores below rely on a kernel without SGPR spills)
-            float2 *sd = kernarg_ptr_s<offsetof(V2Args, r.side)>() + ((size_t)w * 4) * DCFIX_F + 1 + 16 * (size_t)(b - first) + f2;
-            if (k1 >= 14) sd[(k1 - 14) * DCFIX_F] = to_f2(vv[13]);
-            else if (k1 <= 1) sd[(2 + k1) * DCFIX_F] = to_f2(vv[2]);
+            const int k1s = ONE ? tid_t >> 4 : k1, f2s = ONE ? tid_t & 15 : f2;
+            float2 *sd = kernarg_ptr_s<offsetof(V2Args, r.side)>() + ((size_t)w * 4) * DCFIX_F + 1 + 16 * (size_t)(b - first) + f2s;
+            if (k1s >= 14) sd[(k1s - 14) * DCFIX_F] = to_f2(vv[13]);
+            else if (k1s <= 1) sd[(2 + k1s) * DCFIX_F] = to_f2(vv[2]);
         }
         // ---- tail
         char *obase = reinterpret_cast<char *>(A.out) + (size_t)b * RA.tile_step;
         if (FM) {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // next tile image (issued a tile ago): nothing else is outstanding
+            if (!ONE) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // next tile image (issued a tile ago): nothing else is outstanding
 #pragma unroll
             for (int i = 0; i < 16; i += 4) {
                 float2 rp[4], rr[4];
@@ -605,6 +658,7 @@ __global__ __launch_bounds__(256, 2) void k_run256v2(V2Args VA)
 #pragma unroll
                     for (int u = 0; u < 4; u++) mq[u] = fm_sample(rp[u], rr[u], k1s);
                 }
+                if (!V2_ONE_BURST && i < 12) next_pieces(2 + i / 2);                  // pieces 2 .. 7 between the quads 0 | 1 | 2 | 3
                 if (V2_PAIR && par == 0 && b + 1 < last) continue;   // (uniform) the odd tile of the pair stores these
 #pragma unroll
                 for (int u = 0; u < 4; u++) {                       // stores go out between the quads
@@ -619,6 +673,12 @@ __global__ __launch_bounds__(256, 2) void k_run256v2(V2Args VA)
             if (f2 == 15) {
 #pragma unroll
                 for (int i = 0; i < 16; i += 2) *reinterpret_cast<v4f *>(ST + k1 * 16 + i) = (v4f){vv[i].x, vv[i].y, vv[i + 1].x, vv[i + 1].y};
+            }
+            if (ONE && b + 1 < last) {
+                // the next tile's image must have landed before this wave reaches B_a.  Behind its last piece this wave has issued the stores of
+                // quads 2 and 3 (V2_ONE_BURST: of all four quads; an odd tile: 8 each; an even tile with a successor: none), which need not be waited for
+                if ((V2_PAIR && par == 0) || (V2_ABLATE & 2)) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                else asm volatile("s_waitcnt vmcnt(%0)" :: "n"((V2_ONE_BURST ? 4 : 2) * (V2_PAIR ? 8 : 4)) : "memory");
             }
             V2STAMP(12);
             V2STAMP(13);
@@ -734,10 +794,13 @@ int run256_v2_launch(const void *run_args, bool fm, unsigned G, unsigned nruns, 
     return 0;
 }
 
-int run256_v2_blocks_per_cu(bool fm)
+int run256_v2_blocks_per_cu(bool fm, unsigned G)
 {
     int occ = 0;
-    if (fm) (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (k_run256v2<true, 1>), 256, 0);
+    // (the shard variants all keep the two-buffer form of <.., 2>)
+    if (G != 1) { if (fm) (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (k_run256v2<true, 2>), 256, 0);
+                  else (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (k_run256v2<false, 2>), 256, 0); }
+    else if (fm) (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (k_run256v2<true, 1>), 256, 0);
     else (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (k_run256v2<false, 1>), 256, 0);
     return occ < 1 ? 1 : occ;
 }
