@@ -165,8 +165,9 @@ __device__ __forceinline__ float fast_atan2f(float y, float x)
 {
     const float ax = fabsf(x), ay = fabsf(y);
     const float mx = fmaxf(ax, ay), mn = fminf(ax, ay);
-    float a = mn * __builtin_amdgcn_rcpf(mx);
-    a = (mx == 0.0f) ? 0.0f : a;
+    // v_rcp_f32 reads a denormal as 0 (rcp = Inf, a = Inf or NaN): mx is clamped at 1e-37 like scaled_atan2f's, which also
+    // gives a = 0 for mx == 0.  Below the clamp the angle is finite and within +-pi, no more.
+    float a = mn * __builtin_amdgcn_rcpf(fmaxf(mx, 1e-37f));
     a = (mx == INFINITY) ? ((mn == INFINITY) ? 1.0f : 0.0f) : a;
     const float z = a * a;
     float p = 2.456645248e-03f;
