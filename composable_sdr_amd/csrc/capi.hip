@@ -1,5 +1,5 @@
-// C ABI of libcsdr_hip.so (see include/csdr.h): the route table and the chain handle (its device buffers, stream state and
-// per-chunk launch sequences).  The handles of the single blocks are in capi_blocks.hip.  Product code: no CPU fallback,
+// C ABI of libcsdr_hip.so (see include/csdr.h): the route table and the chain handle (the plan of its route, the tails behind
+// it, stream state and the per-chunk call sequence).  The handles of the single blocks are in capi_blocks.hip.  Product code: no CPU fallback,
 // nothing from oracle/.
 #include "../../include/csdr.h"
 #include "capi_internal.h"
@@ -22,22 +22,15 @@ struct csdr_chain {
     std::string path;
     // design
     std::vector<float> taps;
-    uint32_t theta = 0, d_theta = 0, tab_len = 0, tab_pos = 0;
+    uint32_t theta = 0, d_theta = 0;
     DcParams dc; AgcParams agc; float fm_ref = 0.f;
     // device memory (mem frees every buffer below with the handle)
     DeviceBuffers mem;
-    float *d_taps = nullptr;
-    float2 *d_tw = nullptr, *d_nco_tab = nullptr, *d_dcstate = nullptr, *d_scratch = nullptr;
-    uint32_t G = 1;                  // chan_stride: interleaved shard g = c0 of G (generic route, pruned DFT)
-    float2 *d_tw_g = nullptr, *d_fold_ph = nullptr, *d_fold = nullptr;   // (M/G)-point twiddles, fold phasors, folded frames
+    uint32_t G = 1;                  // chan_stride: interleaved shard g = c0 of G
     bool dft_backward = false;       // CSDR_FLAG_DFT_BACKWARD: rows leave through d_perm and a row permutation k -> (M - k) mod M
     void *d_perm = nullptr;
-    bool mix_identity = false;       // DeNo --mix over all channels: M * (branch-0 FIR) instead of bank + DFT + sum
-    bool mix_identity_shard = false; // the same for an interleaved shard g of G: (M / G) * sum of the G surviving branches' FIRs (round 6)
-    float2 *d_u0 = nullptr, *d_u0hist = nullptr;     // branch-0 samples of the call behind p - 1 of history; history between calls (two copies, ping-pong)
-    int u0_cur = 0;
-    float2 *d_u = nullptr, *d_hist_tmp = nullptr, *d_A = nullptr, *d_B = nullptr;
-    size_t a_guard = 0;              // fused M = 256 chain with the AGC tail: d_A has this many readable elements in front of and behind the plane (tile-major route)
+    float2 *d_A = nullptr, *d_B = nullptr;     // AGC on: Z, the channel-major CF32 plane between the plan and the tail; the tail's output in front of --mix
+    size_t a_guard = 0;              // fused chain with the AGC tail: d_A has this many readable elements in front of and behind the plane (tile-major route)
     AgcState *d_agc = nullptr;
     float2 *d_rp[2] = {nullptr, nullptr}; int rp_cur = 0;
     // host-API staging: CSDR_CHAIN_INFLIGHT slots (device in / out, page-locked host in / out), three streams
@@ -49,8 +42,7 @@ struct csdr_chain {
     HostSlot slot[CSDR_CHAIN_INFLIGHT];
     hipStream_t s_in = nullptr, s_k = nullptr, s_out = nullptr;
     uint32_t q_head = 0, q_count = 0;      // oldest pending slot, number of pending chunks
-    ChainPlan *plan = nullptr;       // the fused route's plan (fused.h); null: the any-M route (chain_generic)
-    DcTilePlan *dctile = nullptr;   // generic path with the DC blocker: single-pass scan kernel
+    ChainPlan *plan = nullptr;       // the route's plan (fused.h); null: CSDR_FLAG_TAIL_ONLY, the caller's rows are the front
     uint32_t n_cus = 256;            // compute units of the device (run counts of k_pfb1024 and of the plans: FusedConfig::cus)
     AgcTailPlan *agc_tail = nullptr; // AGC on: time-parallel verified tail (unless CSDR_FLAG_AGC_SEQUENTIAL)
     // DeAM: the chain runs as DeNo into d_amz, then the ampmodem peak detector (kernels_am.hip) [+ mix]
@@ -61,7 +53,6 @@ struct csdr_chain {
     float *d_wbf = nullptr, *d_wbo = nullptr, *d_wbh = nullptr, *d_wbhist[2] = {nullptr, nullptr}; float2 *d_wbst[2] = {nullptr, nullptr}; int wb_cur = 0;
     float2 *d_amz = nullptr; float *d_amf = nullptr; float *d_amq[2] = {nullptr, nullptr}; int amq_cur = 0;
     KernelTimer timer;
-    std::string timed_kernel;
     // pipelined device entry point (csdr_chain_submit_device): two handle-owned streams used alternately, so that consecutive
     // chunks' launches may overlap (the next launch's cold run starts fill the CUs the previous one has already left)
     hipStream_t s_pd[2] = {nullptr, nullptr};
@@ -107,8 +98,8 @@ struct RouteRow {
     uint32_t M;                 // channels the row is for; 0: any count
     uint32_t strides;           // bit g: chan_stride g accepted (bit 1: whole band or a contiguous shard)
     bool (*supported)(uint32_t M, uint32_t p);              // the plan takes M channels of p taps per branch
-    int (*create)(const FusedConfig &cfg, ChainPlan **out); // null: the any-M route (chain_generic)
-    const char *path_prefix;    // csdr_chain_path: prefix + the plan's kernel name [+interleaved-shard] [+agc]
+    int (*create)(const FusedConfig &cfg, ChainPlan **out);
+    const char *path_prefix;    // csdr_chain_path of a fused row: prefix + the plan's kernel name [+interleaved-shard] [+agc] (ChainPlan::route)
     // shortest window of the plan: WU = 6 read-only warm-up tiles of 4096 samples (k_run256v2, k_run64v2, k_run1024v3, k_run1024v2),
     // H_WU = 7 frames of 4096 samples in front of a k_front4096 run
     double dc_window;
@@ -132,7 +123,7 @@ const RouteRow ROUTES[] = {
      "-> k_back4096<CF32 | FM | FM,mix> (four 1024-point DFTs per frame, 16-frame blocks, whole 128-byte lines per row) [-> k_mix4096_finish]; whole band; "
      "DeNo --mix without the AGC keeps the any-M route's mix identity",
      "the same kernels (any call size; short calls use fewer runs)", "k_front4096 -> k_back4096<CF32> -> CF32 plane (tile-major: calls of whole 16-frame blocks, >= 4096 frames) -> k_agc_spec_tm | k_agc_spec -> k_agc_fix [-> k_mix]"},
-    {0, ST_ANY, nullptr, nullptr, nullptr, 0.0, "generic",
+    {0, ST_ANY, generic_supported, generic_create, nullptr, 0.0, "generic",
      "k_dc_tile -> k_pfb_fir (M = 1024, forced generic: k_pfb1024) -> k_fft_r16 | k_fft_pow2 | k_dft_direct [interleaved shard: k_fold + (M / G)-point DFT] "
      "-> k_transpose_fm | k_mix_frames | k_transpose;  DeNo --mix over all channels: k_dc_fold + k_mixid_finish (M % 4096 == 0) | k_dc_tile + k_branch0_fir "
      "(the sum of all bins of a frame is M x branch 0);  DeNo --mix of an interleaved shard (M % 4096 == 0, G = 2, 4, 8): k_dc_fold8 + k_mixid_shard_finish "
@@ -140,18 +131,18 @@ const RouteRow ROUTES[] = {
      "the same kernels (any call size)", "... -> k_transpose -> k_agc_spec -> k_agc_fix [-> k_fm] [-> k_mix]"},
 };
 // dc: the handle's DC blocker, null without one.  Every fused plan truncates the DC state somewhere (warm-up windows, look-back tiles,
-// dcfix); a handle whose alpha does not fit the plan's shortest window (dc_window_ok) takes the generic row.
+// dcfix); a handle whose alpha does not fit the plan's shortest window (dc_window_ok) takes the generic row.  The first row that takes
+// the configuration: the last one (M = 0) takes them all.
 const RouteRow *route_select(uint32_t M, uint32_t p, uint32_t G, uint32_t flags, const DcParams *dc)
 {
-    const RouteRow *generic = &ROUTES[sizeof(ROUTES) / sizeof(ROUTES[0]) - 1];
-    if (M <= 1 || (flags & CSDR_FLAG_FORCE_GENERIC)) return generic;
-    if (G > 1 && diag_env("CSDR_SHARD_GENERIC")) return generic;
-    for (const RouteRow &r : ROUTES) {
-        if (r.M != M || !(G < 32 && (r.strides >> G) & 1u)) continue;     // (the any-M row has M = 0)
-        if (dc && !dc_window_ok(*dc, r.dc_window)) continue;
-        if (r.supported(M, p)) return &r;
+    const bool fused = M > 1 && !(flags & CSDR_FLAG_FORCE_GENERIC) && !(G > 1 && diag_env("CSDR_SHARD_GENERIC"));
+    const RouteRow *r = ROUTES;
+    for (; r->M; r++) {
+        if (!fused || r->M != M || !(G < 32 && (r->strides >> G) & 1u)) continue;
+        if (dc && !dc_window_ok(*dc, r->dc_window)) continue;
+        if (r->supported(M, p)) break;
     }
-    return generic;
+    return r;
 }
 std::string route_table_text()
 {
@@ -199,10 +190,7 @@ void csdr_chain_cfg_default(csdr_chain_cfg *cfg, uint32_t channels)
 
 static int chain_init_state(csdr_chain *h, hipStream_t s)
 {
-    h->theta = 0; h->tab_pos = 0; h->rp_cur = 0;
-    CSDR_HIP(hipMemsetAsync(h->d_dcstate, 0, sizeof(float2), s));
-    if (h->d_u) CSDR_HIP(hipMemsetAsync(h->d_u, 0, sizeof(float2) * (size_t)(h->p - 1) * h->M, s));
-    if (h->d_u0hist) { CSDR_HIP(hipMemsetAsync(h->d_u0hist, 0, sizeof(float2) * 2 * (h->p - 1) * (h->mix_identity_shard ? h->G : 1u), s)); h->u0_cur = 0; }
+    h->theta = 0; h->rp_cur = 0;
     if (h->d_agc) { int r = launch_agc_init(h->d_agc, h->C, s); if (r) return r; }
     if (h->agc_tail) agc_tail_reset(h->agc_tail);
     if (h->d_rp[0]) {
@@ -221,9 +209,7 @@ static int chain_init_state(csdr_chain *h, hipStream_t s)
         CSDR_HIP(hipMemsetAsync(h->d_amq[0], 0, sizeof(float) * h->C, s));     // ampmodem_reset: q_hat = 0
         CSDR_HIP(hipMemsetAsync(h->d_amq[1], 0, sizeof(float) * h->C, s));
     }
-    if (h->plan) { int r = h->plan->reset(s); if (r) return r; }
-    if (h->dctile) { int r = dctile_reset(h->dctile, s); if (r) return r; }
-    return 0;
+    return h->plan ? h->plan->reset(s) : 0;
 }
 
 int csdr_chain_create(const csdr_chain_cfg *cfg_in, csdr_chain **out)
@@ -259,14 +245,12 @@ int csdr_chain_create(const csdr_chain_cfg *cfg_in, csdr_chain **out)
         h->agc = make_agc(cfg->agc_threshold_db);
         if (cfg->demod == CSDR_DEMOD_FM) h->fm_ref = fm_ref_of(cfg->kf);
         auto failt = [&](int code) { csdr_chain_destroy(h); return code; };
-        if ((r = chain_alloc(h, &h->d_dcstate, 1))) return failt(r);
         if ((r = chain_alloc(h, &h->d_agc, h->C))) return failt(r);
         if (cfg->demod == CSDR_DEMOD_FM && ((r = chain_alloc(h, &h->d_rp[0], h->C)) || (r = chain_alloc(h, &h->d_rp[1], h->C)))) return failt(r);
         if (cfg->mix && h->C > 1 && (r = chain_alloc(h, &h->d_B, (size_t)h->C * h->max_nf))) return failt(r);
         if (!(cfg->flags & CSDR_FLAG_AGC_SEQUENTIAL)) { if ((r = agc_tail_create(h->C, h->max_nf, &h->agc_tail))) return failt(r); }
         else if ((r = chain_alloc(h, &h->d_A, (size_t)h->C * h->max_nf))) return failt(r);        // the one-lane-per-channel kernel works in place
         h->path = std::string("tail-only+agc") + (h->agc_tail ? "-spec" : "");
-        h->timed_kernel = "k_agc_spec";
         if ((r = chain_init_state(h, nullptr))) return failt(r);
         CSDR_HIP_CLEAN(hipDeviceSynchronize(), csdr_chain_destroy(h));
         if (!(cfg->flags & CSDR_FLAG_QUIET)) {
@@ -311,105 +295,48 @@ int csdr_chain_create(const csdr_chain_cfg *cfg_in, csdr_chain **out)
     if (cfg->demod == CSDR_DEMOD_FM) h->fm_ref = fm_ref_of(cfg->kf);
 
     auto fail = [&](int code) { csdr_chain_destroy(h); return code; };
-    if ((r = chain_alloc(h, &h->d_dcstate, 1))) return fail(r);
-    if ((r = chain_alloc(h, &h->d_scratch, 2 * (size_t)(h->max_nx / DC_BLOCK + 2)))) return fail(r);
-
     if (M > 1) {
         h->taps = design_pfb_taps(M, m, As);
         h->d_theta = nco_freq_word(pfb_premix_freq(M));
-        h->tab_len = nco_period(h->d_theta, 1u << 17);
-        if ((r = chain_alloc(h, &h->d_taps, h->taps.size()))) return fail(r);
-        CSDR_HIP_CLEAN(hipMemcpy(h->d_taps, h->taps.data(), sizeof(float) * h->taps.size(), hipMemcpyHostToDevice), csdr_chain_destroy(h));
-        if (h->tab_len) {
-            std::vector<float2> tab(h->tab_len);
-            for (uint32_t i = 0; i < h->tab_len; i++) { float c, s; nco_phasor(i * h->d_theta, &c, &s); tab[i] = make_float2(c, s); }
-            if ((r = chain_alloc(h, &h->d_nco_tab, h->tab_len))) return fail(r);
-            CSDR_HIP_CLEAN(hipMemcpy(h->d_nco_tab, tab.data(), sizeof(float2) * h->tab_len, hipMemcpyHostToDevice), csdr_chain_destroy(h));
-        }
-        std::vector<float2> tw(M);
-        for (uint32_t i = 0; i < M; i++) {
-            double a = -2.0 * 3.14159265358979323846 * (double)i / (double)M;
-            tw[i] = make_float2((float)std::cos(a), (float)std::sin(a));
-        }
-        if ((r = chain_alloc(h, &h->d_tw, M))) return fail(r);
-        CSDR_HIP_CLEAN(hipMemcpy(h->d_tw, tw.data(), sizeof(float2) * M, hipMemcpyHostToDevice), csdr_chain_destroy(h));
     }
     if (cfg->agc_threshold_db != 0.0f && (r = chain_alloc(h, &h->d_agc, C))) return fail(r);
-    if (cfg->demod == CSDR_DEMOD_FM && ((r = chain_alloc(h, &h->d_rp[0], C)) || (r = chain_alloc(h, &h->d_rp[1], C)))) return fail(r);
+    // (without the AGC the plan does the freqdem and keeps its history)
+    if (cfg->agc_threshold_db != 0.0f && cfg->demod == CSDR_DEMOD_FM && ((r = chain_alloc(h, &h->d_rp[0], C)) || (r = chain_alloc(h, &h->d_rp[1], C)))) return fail(r);
 
-    // Path selection: the fused kernels cover M = 256 (DC blocker + pre-mix + PFB [+ freqdem]).
-    // With the AGC on, the fused kernel stops at the channel-major CF32 samples and the
-    // exactly-sequential per-channel AGC tail (one lane per channel) + freqdem + mix follow.
-    // interleaved shards: the fused M = 256 chain takes strides 2, 4, 8 (k_run256v2<.., G>); every other shape the any-M route with a pruned DFT
+    // Path selection.  With the AGC on, the plan stops at the channel-major CF32 samples and the per-channel AGC tail (time-parallel, or
+    // with CSDR_FLAG_AGC_SEQUENTIAL one lane per channel) + freqdem + mix follow.
+    // interleaved shards: the fused M = 256 and 1024 chains take strides 2, 4, 8; every other shape the any-M route with a pruned DFT
     const DcParams *dcp = cfg->dc_block ? &h->dc : nullptr;
     const RouteRow *route = route_select(M, h->p, G, cfg->flags, dcp);     // the one place a configuration is mapped to a plan (table above)
     if (route->M == 4096 && (C != M || (cfg->mix && cfg->demod == CSDR_DEMOD_NONE && cfg->agc_threshold_db == 0.0f && !am)))
         route = route_select(M, h->p, G, cfg->flags | CSDR_FLAG_FORCE_GENERIC, dcp);   // contiguous shards; DeNo --mix over all channels (= M x branch 0: nothing beats not computing
                                                                                    // the bank; CSDR_FLAG_NO_MIX_IDENTITY's full bank + DFT + sum stays on the any-M kernels too)
-    if (route->create) {
-        const bool agc_on = cfg->agc_threshold_db != 0.0f;
-        FusedConfig fc{};
-        fc.M = M; fc.p = h->p; fc.C = C; fc.c0 = c0; fc.max_nf = h->max_nf; fc.G = G;
-        fc.dc_block = cfg->dc_block != 0; fc.dc = h->dc;
-        fc.fm = cfg->demod == CSDR_DEMOD_FM && !agc_on; fc.fm_ref = h->fm_ref;
-        fc.mix = cfg->mix != 0 && !agc_on; fc.taps = h->taps.data(); fc.d_theta = h->d_theta; fc.cus = h->n_cus;
-        if ((r = route->create(fc, &h->plan))) return fail(r);
-        h->path = std::string(route->path_prefix) + h->plan->name() + (G > 1 ? "+interleaved-shard" : "") + (agc_on ? "+agc" : "");
-        h->timed_kernel = h->plan->name();
-        if (agc_on) {
-            // d_A: channel-major CF32 from the channelizer; d_B: per-channel tail output in front of --mix
-            // (the fused M = 256 plans may write it tile-major for k_agc_spec_tm, which reads up to a segment in front of / behind the plane)
-            // The guards (2 x 64 KiB per channel: 128 MiB at 1024 channels) exist only where a call can take that route: a time-parallel
-            // tail (not CSDR_FLAG_AGC_SEQUENTIAL), a channel count k_agc_spec_tm takes, calls of >= 4 W = 4096 frames
-            const bool tm_possible = !(cfg->flags & CSDR_FLAG_AGC_SEQUENTIAL) && h->max_nf >= 4096u &&
-                                     (C % 64u == 0 || (C < 64u && 64u % C == 0));
-            h->a_guard = tm_possible ? agc_tail_tm_guard(C) : 0;
-            if ((r = chain_alloc(h, &h->d_A, (size_t)C * h->max_nf + 2 * h->a_guard))) return fail(r);
-            if (h->a_guard) {
-                // only the guards need defined contents (the warm-ups of the first and last segments read them, masked by position)
-                CSDR_HIP_CLEAN(hipMemset(h->d_A, 0, sizeof(float2) * h->a_guard), csdr_chain_destroy(h));
-                CSDR_HIP_CLEAN(hipMemset(h->d_A + h->a_guard + (size_t)C * h->max_nf, 0, sizeof(float2) * h->a_guard), csdr_chain_destroy(h));
-            }
-            if (cfg->mix && (r = chain_alloc(h, &h->d_B, (size_t)C * h->max_nf))) return fail(r);
+    const bool agc_on = cfg->agc_threshold_db != 0.0f;
+    FusedConfig fc{};
+    fc.M = M; fc.p = h->p; fc.C = C; fc.c0 = c0; fc.max_nf = h->max_nf; fc.G = G;
+    fc.dc_block = cfg->dc_block != 0; fc.dc = h->dc;
+    fc.fm = cfg->demod == CSDR_DEMOD_FM && !agc_on; fc.fm_ref = h->fm_ref;
+    fc.mix = cfg->mix != 0 && !agc_on; fc.taps = h->taps.data(); fc.d_theta = h->d_theta; fc.cus = h->n_cus;
+    fc.no_mix_identity = (cfg->flags & CSDR_FLAG_NO_MIX_IDENTITY) != 0;
+    if ((r = route->create(fc, &h->plan))) return fail(r);
+    const std::string front = h->plan->route(route->path_prefix, agc_on);
+    h->path = front;
+    if (agc_on) {
+        // d_A: channel-major CF32 from the plan; d_B: per-channel tail output in front of --mix
+        // (the fused plans may write d_A tile-major for k_agc_spec_tm, which reads up to a segment in front of / behind the plane)
+        // The guards (2 x 64 KiB per channel: 128 MiB at 1024 channels) exist only where a call can take that route: a fused plan (the any-M
+        // plan never writes tile-major), a time-parallel tail (not CSDR_FLAG_AGC_SEQUENTIAL), a channel count k_agc_spec_tm takes, calls
+        // of >= 4 W = 4096 frames
+        const bool tm_possible = route->M && !(cfg->flags & CSDR_FLAG_AGC_SEQUENTIAL) && h->max_nf >= 4096u &&
+                                 (C % 64u == 0 || (C < 64u && 64u % C == 0));
+        h->a_guard = tm_possible ? agc_tail_tm_guard(C) : 0;
+        if ((r = chain_alloc(h, &h->d_A, (size_t)C * h->max_nf + 2 * h->a_guard))) return fail(r);
+        if (h->a_guard) {
+            // only the guards need defined contents (the warm-ups of the first and last segments read them, masked by position)
+            CSDR_HIP_CLEAN(hipMemset(h->d_A, 0, sizeof(float2) * h->a_guard), csdr_chain_destroy(h));
+            CSDR_HIP_CLEAN(hipMemset(h->d_A + h->a_guard + (size_t)C * h->max_nf, 0, sizeof(float2) * h->a_guard), csdr_chain_destroy(h));
         }
-    } else {
-        h->path = "generic";
-        const bool use1024 = G == 1 && pfb1024_supported(M, h->p) && !(cfg->mix && cfg->agc_threshold_db == 0.0f) && !diag_env("CSDR_NO_PFB1024");
-        h->timed_kernel = M > 1 ? (use1024 ? "k_pfb1024" : "k_pfb_fir") : "k_dc_apply";
-        if (use1024) h->path = "generic+pfb1024";
-        if (M > 1) {
-            if ((r = chain_alloc(h, &h->d_u, (size_t)(h->p - 1) * M + h->max_nx)) || (r = chain_alloc(h, &h->d_hist_tmp, (size_t)(h->p - 1) * M))) return fail(r);
-        }
-        if ((r = chain_alloc(h, &h->d_A, h->max_nx)) || (r = chain_alloc(h, &h->d_B, use1024 && h->max_nx < 2048 ? 2048 : h->max_nx))) return fail(r);   // k_pfb1024 keeps yfirst|ylast (2 x nruns x 1024) in d_B
-        if (M > 1 && cfg->dc_block && (r = dctile_create(h->dc, h->max_nx, &h->dctile))) return fail(r);
-        h->mix_identity = M > 1 && G == 1 && C == M && cfg->mix && cfg->demod == CSDR_DEMOD_NONE && cfg->agc_threshold_db == 0.0f &&
-                          h->dctile && !(cfg->flags & CSDR_FLAG_NO_MIX_IDENTITY) && !am;
-        if (h->mix_identity) {
-            if ((r = chain_alloc(h, &h->d_u0, (size_t)(h->p - 1) + h->max_nf)) || (r = chain_alloc(h, &h->d_u0hist, 2 * (h->p - 1)))) return fail(r);
-            h->path = "generic+mix-identity"; h->timed_kernel = (M % 4096u == 0) ? "k_dc_fold" : "k_dc_tile";   // refined per call
-        }
-        // interleaved shard, DeNo --mix, no AGC: only the G branches (M / G) n2 survive the shard's channel sum (kernels_dc_tile.hip, k_dc_fold8)
-        // (the conditions of dctile_mix_identity_shard_supported that do not depend on the call: every call of whole frames then takes it)
-        h->mix_identity_shard = M > 1 && (G == 2 || G == 4 || G == 8) && (uint64_t)C * G == M && cfg->mix && cfg->demod == CSDR_DEMOD_NONE && cfg->agc_threshold_db == 0.0f &&
-                                h->dctile && !(cfg->flags & CSDR_FLAG_NO_MIX_IDENTITY) && !am && M % 4096u == 0 && (M / G) % 512u == 0 &&
-                                h->p <= 33u && h->dc.beta > 0.f;
-        if (h->mix_identity_shard) {
-            if ((r = chain_alloc(h, &h->d_u0hist, 2 * (size_t)(h->p - 1) * G))) return fail(r);
-        }
-        if (G > 1) {
-            const uint32_t Mg = M / G;
-            std::vector<float2> twg(Mg), ph(G + Mg);
-            const double tp = -2.0 * 3.14159265358979323846;
-            for (uint32_t i = 0; i < Mg; i++) twg[i] = make_float2((float)std::cos(tp * i / Mg), (float)std::sin(tp * i / Mg));
-            for (uint32_t j2 = 0; j2 < G; j2++) ph[j2] = make_float2((float)std::cos(tp * ((uint64_t)j2 * c0 % G) / G), (float)std::sin(tp * ((uint64_t)j2 * c0 % G) / G));
-            for (uint32_t j1 = 0; j1 < Mg; j1++) ph[G + j1] = make_float2((float)std::cos(tp * ((uint64_t)j1 * c0 % M) / M), (float)std::sin(tp * ((uint64_t)j1 * c0 % M) / M));
-            if ((r = chain_alloc(h, &h->d_tw_g, Mg)) || (r = chain_alloc(h, &h->d_fold_ph, G + Mg)) || (r = chain_alloc(h, &h->d_fold, (size_t)Mg * h->max_nf))) return fail(r);
-            if (hipMemcpy(h->d_tw_g, twg.data(), sizeof(float2) * Mg, hipMemcpyHostToDevice) != hipSuccess ||
-                hipMemcpy(h->d_fold_ph, ph.data(), sizeof(float2) * (G + Mg), hipMemcpyHostToDevice) != hipSuccess) { set_error("chain: fold table upload failed"); return fail(CSDR_ERR_HIP); }
-            h->path = h->mix_identity_shard ? "generic+pruned-dft+shard-mix-identity" : "generic+pruned-dft";
-            if (h->mix_identity_shard) h->timed_kernel = "k_dc_fold8";
-        }
-        if (M > 1 && cfg->dc_block && !h->dctile) h->path += "+dc-scan";     // alpha outside the DC shortcuts (dc_window_ok): launch_dc_mix
+        if (cfg->mix && (r = chain_alloc(h, &h->d_B, (size_t)C * h->max_nf))) return fail(r);
     }
     if ((cfg_in->flags & CSDR_FLAG_DFT_BACKWARD) && M > 1 && !(cfg_in->mix != 0)) {
         if (C != M || G > 1) { set_error("chain: CSDR_FLAG_DFT_BACKWARD is built for whole-band handles (no channel shard)"); return fail(CSDR_ERR_INVALID); }
@@ -442,7 +369,7 @@ int csdr_chain_create(const csdr_chain_cfg *cfg_in, csdr_chain **out)
     }
     if (h->d_agc && !(cfg->flags & CSDR_FLAG_AGC_SEQUENTIAL)) {
         if ((r = agc_tail_create(C, h->max_nf, &h->agc_tail))) return fail(r);
-        h->path += h->plan ? "-spec" : "+agc-spec";
+        h->path += route->M ? "-spec" : "+agc-spec";      // (a fused row's text already says +agc)
     }
     if ((r = chain_init_state(h, nullptr))) return fail(r);
     CSDR_HIP_CLEAN(hipDeviceSynchronize(), csdr_chain_destroy(h));
@@ -454,7 +381,7 @@ int csdr_chain_create(const csdr_chain_cfg *cfg_in, csdr_chain **out)
                h->path.c_str(), dev, M, c0, c0 + C - 1, M > 1 ? M * h->p : 0, m, As, h->d_theta, cfg->dc_block,
                cfg->dc_alpha, cfg->agc_threshold_db, am ? "AM" : (wbfm ? "WBFM" : (cfg->demod == CSDR_DEMOD_FM ? "FM" : "none")), cfg->kf, cfg_in->mix);
         // per-channel outputs / AGC / demod tails beyond the fused kernels' channel counts run stage by stage through HBM
-        if (!h->plan && !h->mix_identity && M > 1024)
+        if (!route->M && M > 1024 && front != "generic+mix-identity")
             printf("csdr chain: note: %u channels with per-channel output run on the any-M route (DC blocker, FIR, DFT and tail as separate kernels, "
                    "~0.09 of the HBM roofline on MI355X); fused kernels exist for 64, 256 and 1024 channels, and for DeNo --mix over all channels of any count\n", M);
         fflush(stdout);
@@ -466,8 +393,8 @@ int csdr_chain_create(const csdr_chain_cfg *cfg_in, csdr_chain **out)
 uint32_t csdr_chain_out_elem_size(const csdr_chain *h) { return h && (h->cfg.demod == CSDR_DEMOD_FM || h->am || h->wbfm) ? 4u : 8u; }
 
 // Z[C][nf] (channel-major CF32) -> AGC + squelch [+ freqdem] [+ mix] -> d_out: the time-parallel tail (tm: Z tile-major), or with
-// CSDR_FLAG_AGC_SEQUENTIAL one lane per channel in place on Z; without the AGC (the any-M route) only freqdem / mix
-static int chain_tail(csdr_chain *h, float2 *Z, uint32_t nf, void *d_out, hipStream_t s, bool tm = false)
+// CSDR_FLAG_AGC_SEQUENTIAL one lane per channel in place on Z
+static int chain_tail(csdr_chain *h, float2 *Z, uint32_t nf, void *d_out, hipStream_t s, bool tm)
 {
     const bool fm = h->cfg.demod == CSDR_DEMOD_FM, mixo = h->cfg.mix && h->M > 1;
     int r;
@@ -479,7 +406,7 @@ static int chain_tail(csdr_chain *h, float2 *Z, uint32_t nf, void *d_out, hipStr
         if (mixo) return launch_mix((const float *)T, (float *)d_out, h->C, fm ? nf : 2 * nf, s);
         return 0;
     }
-    if (h->d_agc && (r = launch_agc(Z, h->C, nf, h->d_agc, h->agc, s))) return r;
+    if ((r = launch_agc(Z, h->C, nf, h->d_agc, h->agc, s))) return r;
     if (fm) {
         float *F = mixo ? (float *)h->d_B : (float *)d_out;
         if ((r = launch_fm(Z, F, h->C, nf, h->fm_ref, h->d_rp[h->rp_cur], h->d_rp[h->rp_cur ^ 1], s))) return r;
@@ -487,13 +414,6 @@ static int chain_tail(csdr_chain *h, float2 *Z, uint32_t nf, void *d_out, hipStr
         if (mixo) return launch_mix(F, (float *)d_out, h->C, nf, s);
     } else if (mixo) return launch_mix((const float *)Z, (float *)d_out, h->C, 2 * nf, s);
     return 0;
-}
-
-// the NCO phase behind a call of nx input samples (and the position in the pre-mix table)
-static void chain_advance_nco(csdr_chain *h, uint32_t nx)
-{
-    h->theta += nx * h->d_theta;
-    if (h->tab_len) h->tab_pos = (uint32_t)(((uint64_t)h->tab_pos + nx) % h->tab_len);
 }
 
 // The argument checks of every entry point that takes a chunk (texts and codes are part of the C ABI), then the handle's device
@@ -507,110 +427,72 @@ static int chain_check_chunk(const csdr_chain *h, const void *in, uint32_t n_in,
     return CSDR_OK;
 }
 
-static int chain_generic(csdr_chain *h, const float2 *d_in, uint32_t nx, void *d_out, hipStream_t s)
+// One call on stream: the plan (tail-only: the caller's rows), the AGC tail, the AM or the WBFM tail, the backward handle's row
+// reversal.  Every stage writes the next stage's input, the last one d_out.
+static int chain_call(csdr_chain *h, const void *d_in, uint32_t n_in, void *d_out, uint32_t *n_out, void *stream)
 {
-    const uint32_t M = h->M, nf = nx / M, C = h->C;
-    const bool fm = h->cfg.demod == CSDR_DEMOD_FM, mixo = h->cfg.mix && M > 1, agc = h->d_agc != nullptr;
-    int r;
-    // where the channel-major CF32 lands
-    float2 *Z = (!fm && !mixo && !(agc && h->agc_tail)) ? (float2 *)d_out : h->d_A;
-    NcoParams nco{};
-    if (M > 1) {
-        const size_t hist = (size_t)(h->p - 1) * M;
-        nco.theta0 = h->theta; nco.d_theta = h->d_theta; nco.tab_len = h->tab_len; nco.tab_pos = h->tab_pos; nco.up = 0;
-        if (h->mix_identity_shard) {
-            // the shard's channel sum = (M / G) x sum of the G surviving branches' FIRs.  The create-time predicate holds every condition
-            // that does not depend on the call, and calls are whole frames: a call it refuses is a bug, not a reason to switch routes (the
-            // pruned-DFT route keeps no branch histories of its own)
-            if (!dctile_mix_identity_shard_supported(h->dctile, M, nx, h->p, h->G)) { set_error("chain: shard mix identity refused a call of %u samples", nx); return CSDR_ERR_INVALID; }
-            const size_t hs = (size_t)(h->p - 1) * h->G;
-            float2 *hin = h->d_u0hist + (size_t)h->u0_cur * hs, *hout = h->d_u0hist + (size_t)(h->u0_cur ^ 1) * hs;
-            h->timed_kernel = "k_dc_fold8";
-            if ((r = h->timer.begin(s))) return r;
-            if ((r = dctile_mix_identity_shard(h->dctile, d_in, nx, nco, h->d_nco_tab, h->d_taps, M, h->p, h->G, h->c0, hin, hout, (float2 *)d_out, s))) return r;
-            if ((r = h->timer.end(s))) return r;
-            h->u0_cur ^= 1;
-            chain_advance_nco(h, nx);
-            return 0;
-        }
-        if (h->mix_identity) {
-            // sum over ALL channels of a frame = M * X_t[0]: DC blocker + pre-mix on the whole stream, every M-th sample kept,
-            // then the 2m-tap FIR of polyphase branch 0 (no bank, no DFT, no channel sum; 8 B read per input sample)
-            float2 *hin = h->d_u0hist + (size_t)h->u0_cur * (h->p - 1), *hout = h->d_u0hist + (size_t)(h->u0_cur ^ 1) * (h->p - 1);
-            if (dctile_mix_identity_supported(h->dctile, M, nx, h->p)) {
-                // k_dc_fold (one aggregate per tile: a plain streaming read) + k_mixid_finish (DC state, pick, pre-mix, FIR)
-                h->timed_kernel = "k_dc_fold";
-                if ((r = h->timer.begin(s))) return r;
-                if ((r = dctile_mix_identity(h->dctile, d_in, nx, nco, h->d_nco_tab, h->d_taps, M, h->p, hin, hout, (float2 *)d_out, s))) return r;
-                if ((r = h->timer.end(s))) return r;
-            } else {
-                h->timed_kernel = "k_dc_tile";
-                CSDR_HIP(hipMemcpyAsync(h->d_u0, hin, sizeof(float2) * (h->p - 1), hipMemcpyDeviceToDevice, s));
-                if ((r = h->timer.begin(s))) return r;
-                if ((r = dctile_process(h->dctile, d_in, h->d_u0 + (h->p - 1), nx, true, nco, h->d_nco_tab, s, M))) return r;
-                if ((r = h->timer.end(s))) return r;
-                if ((r = launch_branch0_fir(h->d_u0, h->d_taps, (float2 *)d_out, hout, M, h->p, nf, s))) return r;
-            }
-            h->u0_cur ^= 1;
-            chain_advance_nco(h, nx);
-            return 0;
-        }
-        float2 *u_new = h->d_u + hist;
-        if (h->dctile) r = dctile_process(h->dctile, d_in, u_new, nx, true, nco, h->d_nco_tab, s);
-        else r = launch_dc_mix(d_in, u_new, nx, h->cfg.dc_block != 0, h->dc, h->d_dcstate, h->d_scratch, true, nco, h->d_nco_tab, s);
-        if (r) return r;
-        // M = 1024: FIR + DFT + transpose [+ freqdem] in one kernel (no X / Y round trips through HBM); the frame-major
-        // mix tails without AGC still want Y in HBM and keep the three-kernel route
-        const bool fused1024 = h->G == 1 && pfb1024_supported(M, h->p) && !(mixo && !agc) && !diag_env("CSDR_NO_PFB1024");
-        if ((r = h->timer.begin(s))) return r;
-        if (fused1024) {
-            const bool fm_here = fm && !agc;                     // with the AGC on the tail does the freqdem
-            void *o = fm_here ? d_out : (void *)Z;
-            r = launch_pfb1024(u_new, h->d_taps, h->d_tw, o, fm_here, nf, h->c0, C, h->fm_ref, fm_here ? h->d_rp[h->rp_cur] : nullptr,
-                               fm_here ? h->d_rp[h->rp_cur ^ 1] : nullptr, h->d_B, h->n_cus, s);
-            if (!r && fm_here) h->rp_cur ^= 1;
-        } else r = launch_pfb_fir(u_new, h->d_taps, h->d_A, M, h->p, nf, s);
-        if (r) return r;
-        if ((r = h->timer.end(s))) return r;
-        // keep the last (p-1) frames of premixed input as the next call's history
-        CSDR_HIP(hipMemcpyAsync(h->d_hist_tmp, h->d_u + nx, sizeof(float2) * hist, hipMemcpyDeviceToDevice, s));
-        CSDR_HIP(hipMemcpyAsync(h->d_u, h->d_hist_tmp, sizeof(float2) * hist, hipMemcpyDeviceToDevice, s));
-        if (fused1024) {
-            chain_advance_nco(h, nx);
-            return agc ? chain_tail(h, Z, nf, d_out, s) : 0;      // (without the AGC: freqdem done in the kernel, no mix on this route)
-        }
-        // DeNo --mix over all channels: the frame sum happens inside the DFT kernel, Y never goes to HBM
-        const bool fused_mix = !agc && !fm && mixo && C == M && dft_mix_supported(M);
-        if (h->G > 1) {
-            // interleaved shard: fold the G sub-blocks of every frame, then an (M/G)-point DFT: d_B = Y[t][c0 + G m]
-            if ((r = launch_fold(h->d_A, h->d_fold, h->d_fold_ph, M, h->G, nf, s))) return r;
-            r = launch_dft(h->d_fold, h->d_B, h->d_tw_g, M / h->G, nf, s);
-        } else if (fused_mix) r = launch_dft_mix(h->d_A, (float2 *)d_out, h->d_tw, M, nf, s);
-        else r = launch_dft(h->d_A, h->d_B, h->d_tw, M, nf, s);
-        if (r) return r;
-        chain_advance_nco(h, nx);
-        if (fused_mix) return 0;
-        const uint32_t Mw = M / h->G, cw = h->G > 1 ? 0u : h->c0;     // width of a DFT output frame, first owned bin in it
-        if (!agc && (fm || mixo)) {
-            // frame-major tails: no transpose in front of freqdem / mix
-            if (mixo) r = launch_mix_frames(h->d_B, d_out, fm, Mw, nf, cw, C, h->fm_ref, h->d_rp[h->rp_cur], h->d_rp[h->rp_cur ^ 1], s);
-            else r = launch_transpose_fm(h->d_B, (float *)d_out, Mw, nf, cw, C, h->fm_ref, h->d_rp[h->rp_cur], h->d_rp[h->rp_cur ^ 1], s);
-            if (r) return r;
-            if (fm) h->rp_cur ^= 1;
-            return 0;
-        }
-        if ((r = launch_transpose(h->d_B, Z, Mw, nf, cw, C, s))) return r;
-    } else {
-        if ((r = h->timer.begin(s))) return r;
-        if ((r = launch_dc_mix(d_in, Z, nx, h->cfg.dc_block != 0, h->dc, h->d_dcstate, h->d_scratch, false, nco, nullptr, s))) return r;
-        if ((r = h->timer.end(s))) return r;
+    // 1. checks (texts, codes and their order are part of the C ABI)
+    if (!h) { set_error("chain: null handle"); return CSDR_ERR_INVALID; }
+    const bool backward = h->dft_backward && n_in && d_out;     // (with nothing to do or nowhere to put it a backward handle answers as a forward one)
+    if (n_out && !backward) *n_out = 0;                         // (a call a backward handle refuses has always left *n_out alone)
+    if (n_in == 0) return CSDR_OK;
+    if (!d_out) { set_error("chain: null buffer"); return CSDR_ERR_INVALID; }
+    if (h->wbfm && n_in % h->M == 0 && (n_in / h->M) % h->wb_decim) {
+        set_error("chain: %u frames per call are not a multiple of the WBFM decimation %u (firDecim's `div`, Liquid.chs:495-497)", n_in / h->M, h->wb_decim);
+        return CSDR_ERR_SIZE;
     }
-    return chain_tail(h, Z, nf, d_out, s);
+    DevGuard guard;
+    int r;
+    if ((r = chain_check_chunk(h, d_in, n_in, d_out, guard))) return r;
+    hipStream_t s = (hipStream_t)stream;
+    const uint32_t nf = n_in / h->M, C = h->C;
+    const bool agc_on = h->d_agc != nullptr, fm = h->cfg.demod == CSDR_DEMOD_FM, mixo = h->cfg.mix && h->M > 1;
+    void *const last = backward ? h->d_perm : d_out;                                      // output of stage 4
+    void *const chain_out = h->wbfm ? (void *)h->d_wbf : h->am ? (void *)h->d_amz : last;   // output of stages 2 + 3
+    uint32_t n = mixo ? nf : C * nf;                                                      // elements in it
+
+    // 2. front: the route's plan writes Z: chain_out, or with the AGC on the plane its tail reads (chain_out itself where the sequential
+    // AGC is the last step and works in place).  Tail-only: Z = the caller's rows (the sequential AGC works in place on a copy)
+    float2 *Z = (agc_on && (fm || mixo || h->agc_tail)) ? h->d_A + h->a_guard : (float2 *)chain_out;
+    bool tm = false;
+    if (h->plan) {
+        FusedCall fcall{};
+        // time-parallel AGC tail behind a fused plan, run-sized calls of whole tiles: the plane between the two kernels is tile-major
+        tm = h->agc_tail && h->a_guard && agc_tail_tm_supported(h->agc_tail, nf) && h->plan->tile_major_ok(nf);
+        fcall.tile_major = tm;
+        fcall.d_in = (const float2 *)d_in; fcall.d_out = Z; fcall.nf = nf; fcall.theta0 = h->theta;
+        fcall.indep = h->call_indep; fcall.ev_tail = h->call_ev_tail;
+        if ((r = h->plan->process(fcall, s, &h->timer))) return r;
+        h->theta += n_in * h->d_theta;     // the NCO phase behind the call
+    } else if (h->agc_tail) Z = (float2 *)d_in;
+    else { Z = h->d_A; CSDR_HIP(hipMemcpyAsync(Z, d_in, sizeof(float2) * (size_t)n_in, hipMemcpyDeviceToDevice, s)); }
+
+    // 3. AGC + squelch [+ freqdem] [+ mix]
+    if (agc_on && (r = chain_tail(h, Z, nf, chain_out, s, tm))) return r;
+    if (!h->plan && !h->agc_tail && !fm && !mixo) CSDR_HIP(hipMemcpyAsync(chain_out, Z, sizeof(float2) * (size_t)n_in, hipMemcpyDeviceToDevice, s));
+
+    // 4. DeWBFM: the chain ran as DeNBFM 0.6; de-emphasis + decimator [+ mix].  DeAM: it ran as DeNo; the ampmodem peak detector [+ mix]
+    if (h->wbfm) {
+        const uint32_t no = nf / h->wb_decim;
+        if ((r = launch_biquad(h->d_wbf, h->d_wbf, C, nf, h->wb_bq, h->d_wbst[h->wb_cur], h->d_wbst[h->wb_cur ^ 1], s))) return r;
+        float *O = h->wbfm_mix ? h->d_wbo : (float *)last;
+        if ((r = launch_firdecim(h->d_wbf, O, C, nf, h->wb_decim, h->d_wbh, h->wb_hlen, h->d_wbhist[h->wb_cur], h->d_wbhist[h->wb_cur ^ 1], s))) return r;
+        h->wb_cur ^= 1;
+        if (h->wbfm_mix && (r = launch_mix(O, (float *)last, C, no, s))) return r;
+        n = h->wbfm_mix ? no : C * no;
+    } else if (h->am) {
+        float *F = h->am_mix ? h->d_amf : (float *)last;
+        if ((r = launch_am(h->d_amz, F, C, nf, h->d_amq[h->amq_cur], h->d_amq[h->amq_cur ^ 1], 0.01f, s))) return r;
+        h->amq_cur ^= 1;
+        if (h->am_mix && (r = launch_mix(F, (float *)last, C, nf, s))) return r;
+        n = h->am_mix ? nf : C * nf;
+    }
+    if (n_out) *n_out = n;
+
+    // 5. CSDR_FLAG_DFT_BACKWARD: the chain as built (forward DFT) went into d_perm; row k of the output = its row (M - k) mod M
+    if (backward) return launch_rows_reversed(h->d_perm, d_out, C, (size_t)(n / C) * csdr_chain_out_elem_size(h), s);
+    return CSDR_OK;
 }
-
-static int chain_process_device_inner(csdr_chain *h, const void *d_in, uint32_t n_in, void *d_out, uint32_t *n_out, void *stream);
-
-static int chain_process_device_any(csdr_chain *h, const void *d_in, uint32_t n_in, void *d_out, uint32_t *n_out, void *stream);
 
 // A call on a caller's stream is remembered by an event behind its work, so that the host-buffer entry point (own stream s_k) can
 // order itself behind it without keeping the caller's stream handle
@@ -627,7 +509,7 @@ static int chain_mark_user_stream(csdr_chain *h, hipStream_t stream)
 
 int csdr_chain_process_device(csdr_chain *h, const void *d_in, uint32_t n_in, void *d_out, uint32_t *n_out, void *stream)
 {
-    if (!h || h->in_submit) return chain_process_device_any(h, d_in, n_in, d_out, n_out, stream);
+    if (!h || h->in_submit) return chain_call(h, d_in, n_in, d_out, n_out, stream);
     const bool own = h->s_k && (hipStream_t)stream == h->s_k;       // called by csdr_chain_submit / csdr_chain_process on the handle's stream
     DevGuard guard(h->device);
     if (!own && h->s_k && h->q_count) CSDR_HIP(hipStreamSynchronize(h->s_k));   // host-buffer chunks still in flight come first
@@ -635,7 +517,7 @@ int csdr_chain_process_device(csdr_chain *h, const void *d_in, uint32_t n_in, vo
         // the handle has pipelined chunks (csdr_chain_submit_device): this call follows them, and a later submit follows this call
         for (int i = 0; i < 2; i++) if (h->pd_used[i]) CSDR_HIP(hipStreamWaitEvent((hipStream_t)stream, h->e_pd_done[i], 0));
     }
-    int r = chain_process_device_any(h, d_in, n_in, d_out, n_out, stream);
+    int r = chain_call(h, d_in, n_in, d_out, n_out, stream);
     if (r) return r;
     if (h->s_pd[0]) {
         CSDR_HIP(hipEventRecord(h->e_serial, (hipStream_t)stream));
@@ -644,107 +526,15 @@ int csdr_chain_process_device(csdr_chain *h, const void *d_in, uint32_t n_in, vo
     return own ? CSDR_OK : chain_mark_user_stream(h, (hipStream_t)stream);
 }
 
-static int chain_process_device_any0(csdr_chain *h, const void *d_in, uint32_t n_in, void *d_out, uint32_t *n_out, void *stream);
-static int chain_process_device_any(csdr_chain *h, const void *d_in, uint32_t n_in, void *d_out, uint32_t *n_out, void *stream)
-{
-    if (!h || !h->dft_backward || n_in == 0 || !d_out) return chain_process_device_any0(h, d_in, n_in, d_out, n_out, stream);
-    // CSDR_FLAG_DFT_BACKWARD: the chain as built (forward DFT) into d_perm, then row k of the output = its row (M - k) mod M
-    uint32_t n = 0;
-    int r = chain_process_device_any0(h, d_in, n_in, h->d_perm, &n, stream);
-    if (r) return r;
-    if (n_out) *n_out = n;
-    DevGuard guard(h->device);
-    return launch_rows_reversed(h->d_perm, d_out, h->C, (size_t)(n / h->C) * csdr_chain_out_elem_size(h), (hipStream_t)stream);
-}
-
-static int chain_process_device_any0(csdr_chain *h, const void *d_in, uint32_t n_in, void *d_out, uint32_t *n_out, void *stream)
-{
-    if (h && h->wbfm) {
-        if (n_out) *n_out = 0;
-        if (n_in == 0) return CSDR_OK;
-        if (!d_out) { set_error("chain: null buffer"); return CSDR_ERR_INVALID; }
-        if (n_in % h->M == 0 && (n_in / h->M) % h->wb_decim) {
-            set_error("chain: %u frames per call are not a multiple of the WBFM decimation %u (firDecim's `div`, Liquid.chs:495-497)", n_in / h->M, h->wb_decim);
-            return CSDR_ERR_SIZE;
-        }
-        int r = chain_process_device_inner(h, d_in, n_in, h->d_wbf, nullptr, stream);
-        if (r) return r;
-        DevGuard guard(h->device);
-        hipStream_t s = (hipStream_t)stream;
-        const uint32_t nf = n_in / h->M, no = nf / h->wb_decim;
-        if ((r = launch_biquad(h->d_wbf, h->d_wbf, h->C, nf, h->wb_bq, h->d_wbst[h->wb_cur], h->d_wbst[h->wb_cur ^ 1], s))) return r;
-        float *O = h->wbfm_mix ? h->d_wbo : (float *)d_out;
-        if ((r = launch_firdecim(h->d_wbf, O, h->C, nf, h->wb_decim, h->d_wbh, h->wb_hlen, h->d_wbhist[h->wb_cur], h->d_wbhist[h->wb_cur ^ 1], s))) return r;
-        h->wb_cur ^= 1;
-        if (h->wbfm_mix && (r = launch_mix(O, (float *)d_out, h->C, no, s))) return r;
-        if (n_out) *n_out = h->wbfm_mix ? no : h->C * no;
-        return CSDR_OK;
-    }
-    if (!h || !h->am) return chain_process_device_inner(h, d_in, n_in, d_out, n_out, stream);
-    if (n_out) *n_out = 0;
-    if (n_in == 0) return CSDR_OK;
-    if (!d_out) { set_error("chain: null buffer"); return CSDR_ERR_INVALID; }
-    int r = chain_process_device_inner(h, d_in, n_in, h->d_amz, nullptr, stream);
-    if (r) return r;
-    DevGuard guard(h->device);
-    hipStream_t s = (hipStream_t)stream;
-    const uint32_t nf = n_in / h->M;
-    float *F = h->am_mix ? h->d_amf : (float *)d_out;
-    if ((r = launch_am(h->d_amz, F, h->C, nf, h->d_amq[h->amq_cur], h->d_amq[h->amq_cur ^ 1], 0.01f, s))) return r;
-    h->amq_cur ^= 1;
-    if (h->am_mix && (r = launch_mix(F, (float *)d_out, h->C, nf, s))) return r;
-    if (n_out) *n_out = h->am_mix ? nf : h->C * nf;
-    return CSDR_OK;
-}
-
-static int chain_process_device_inner(csdr_chain *h, const void *d_in, uint32_t n_in, void *d_out, uint32_t *n_out, void *stream)
-{
-    if (!h) { set_error("chain: null handle"); return CSDR_ERR_INVALID; }
-    if (n_out) *n_out = 0;
-    if (n_in == 0) return CSDR_OK;
-    DevGuard guard;
-    int r;
-    if ((r = chain_check_chunk(h, d_in, n_in, d_out, guard))) return r;
-    hipStream_t s = (hipStream_t)stream;
-    const uint32_t nf = n_in / h->M;
-    if (h->tail_only) {
-        // the time-parallel tail reads the rows where they are; the sequential AGC works in place on a copy
-        const bool fm = h->cfg.demod == CSDR_DEMOD_FM, mixo = h->cfg.mix && h->M > 1;
-        if (!h->agc_tail) CSDR_HIP(hipMemcpyAsync(h->d_A, d_in, sizeof(float2) * (size_t)n_in, hipMemcpyDeviceToDevice, s));
-        if ((r = chain_tail(h, h->agc_tail ? (float2 *)d_in : h->d_A, nf, d_out, s))) return r;
-        if (!h->agc_tail && !fm && !mixo) CSDR_HIP(hipMemcpyAsync(d_out, h->d_A, sizeof(float2) * (size_t)n_in, hipMemcpyDeviceToDevice, s));
-        if (n_out) *n_out = mixo ? nf : h->C * nf;
-        return CSDR_OK;
-    }
-    if (h->plan) {
-        const bool agc_on = h->d_agc != nullptr, fm = h->cfg.demod == CSDR_DEMOD_FM, mixo = h->cfg.mix != 0;
-        float2 *Z = (agc_on && (fm || mixo || h->agc_tail)) ? h->d_A + h->a_guard : (float2 *)d_out;
-        FusedCall fcall{};
-        // AGC tail behind a fused chain, run-sized calls of whole tiles: the plane between the two kernels is tile-major
-        const bool tm = agc_on && h->agc_tail && h->a_guard && Z != (float2 *)d_out && agc_tail_tm_supported(h->agc_tail, nf) && h->plan->tile_major_ok(nf);
-        fcall.tile_major = tm;
-        fcall.d_in = (const float2 *)d_in; fcall.d_out = agc_on ? (void *)Z : d_out; fcall.nf = nf; fcall.theta0 = h->theta;
-        fcall.indep = h->call_indep; fcall.ev_tail = h->call_ev_tail;
-        if ((r = h->plan->process(fcall, s, &h->timer))) return r;
-        chain_advance_nco(h, n_in);
-        if (agc_on && (r = chain_tail(h, Z, nf, d_out, s, tm))) return r;
-    } else {
-        if ((r = chain_generic(h, (const float2 *)d_in, n_in, d_out, s))) return r;
-    }
-    if (n_out) *n_out = (h->cfg.mix && h->M > 1) ? nf : h->C * nf;
-    return CSDR_OK;
-}
-
 // Device-side spin-wait time-outs (k_tile256 look-back / hand-off, k_dc_tile look-back) set a sticky status word and the
 // kernel carries on with garbage carries: report it as an error once, then clear it.  Synchronises the device.
 static int chain_device_status(csdr_chain *h)
 {
-    unsigned st = 0, st2 = 0;
+    unsigned st = 0;
     int r;
     if (h->plan && (r = h->plan->status(&st))) return r;
-    if (h->dctile && (r = dctile_status(h->dctile, &st2))) return r;
-    if (st || st2) {
-        set_error("chain: an inter-workgroup wait timed out on the device (fused status 0x%x, dc-tile status 0x%x): the output of the affected calls is invalid", st, st2);
+    if (st) {
+        set_error("chain: an inter-workgroup wait timed out on the device (plan status 0x%x): the output of the affected calls is invalid", st);
         return CSDR_ERR_HIP;
     }
     return CSDR_OK;
@@ -965,9 +755,7 @@ int csdr_chain_seek_frames(csdr_chain *h, uint64_t frames)
 {
     int r = csdr_chain_reset(h);
     if (r) return r;
-    const uint64_t n = frames * (uint64_t)h->M;
-    h->theta = (uint32_t)(n * (uint64_t)h->d_theta);
-    if (h->tab_len) h->tab_pos = (uint32_t)(n % h->tab_len);
+    h->theta = (uint32_t)(frames * (uint64_t)h->M * (uint64_t)h->d_theta);
     if (h->plan) h->plan->seek(frames);
     return CSDR_OK;
 }
@@ -1021,8 +809,7 @@ const char *csdr_chain_kernel_time(csdr_chain *h, double *total_ms, uint32_t *la
     if (total_ms) *total_ms = h->timer.acc_ms;
     if (launches) *launches = h->timer.launches;
     h->timer.acc_ms = 0.0; h->timer.launches = 0;
-    if (h->plan) h->timed_kernel = h->plan->name();      // the kernel the last call launched
-    return h->timed_kernel.c_str();
+    return h->plan ? h->plan->name() : "k_agc_spec";      // the kernel the last call timed (before the first call: the create-time choice)
 }
 
 int csdr_chain_destroy(csdr_chain *h)
@@ -1031,7 +818,6 @@ int csdr_chain_destroy(csdr_chain *h)
     DevGuard guard(h->device);
     (void)hipDeviceSynchronize();
     delete h->plan;
-    if (h->dctile) dctile_destroy(h->dctile);
     if (h->agc_tail) agc_tail_destroy(h->agc_tail);
     h->timer.destroy();
     for (auto &sl : h->slot) {

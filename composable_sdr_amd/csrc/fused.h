@@ -1,5 +1,5 @@
-// Interface between the chain handle of the C ABI (capi.hip) and the fused channelizer kernels
-// (kernels_fused.hip).  Product code.
+// Interface between the chain handle of the C ABI (capi.hip) and the plans of its routes: the four fused channelizers (M = 64, 256,
+// 1024, 4096) and the any-M route (plan_generic.hip).  Product code.
 #pragma once
 #include "csdr_internal.h"
 
@@ -14,6 +14,7 @@ struct FusedConfig {
     const float *taps;       // host, M*p
     uint32_t d_theta;
     uint32_t cus = 256;      // compute units of the device (the run counts of the launches)
+    bool no_mix_identity = false;    // CSDR_FLAG_NO_MIX_IDENTITY (any-M route: DeNo --mix through the full bank + DFT + sum)
 };
 
 struct FusedCall {
@@ -31,8 +32,9 @@ struct FusedCall {
     bool tile_major = false;
 };
 
-// The plan of one fused route (a RouteRow of capi.hip): M = 64 (kernels_fused_small.hip), 256 (kernels_fused.hip), 1024 (kernels_pfb1024.hip)
-// and 4096 (kernels_pfb4096.hip) derive from it.  The base owns what they share: the configuration, the CU count, the global frame counter,
+// The plan of one route (a RouteRow of capi.hip): M = 64 (kernels_fused_small.hip), 256 (kernels_fused.hip), 1024 (kernels_pfb1024.hip),
+// 4096 (kernels_pfb4096.hip) and any M (plan_generic.hip) derive from it.  With the AGC on (cfg.fm and cfg.mix are then false) a plan delivers
+// the channel-major CF32 plane the handle's tail reads; without it, the call's output.  The base owns what they share: the configuration, the CU count, the global frame counter,
 // the ping-pong index of the state buffers, the device buffers (mem: freed with the plan) and the mix ending of the 64, 256 and 1024 plans
 // (run() writes d_premix, process() sums its rows into the call's output).
 struct ChainPlan {
@@ -52,6 +54,11 @@ struct ChainPlan {
     void seek(uint64_t frames) { frames_done = frames; }     // after reset: global frame index of the next frame
     // the kernel the last call launched (before the first call: the one a call of max_nf frames takes)
     virtual const char *name() const = 0;
+    // csdr_chain_path in front of the handle's tails (+am, +wbfm, +dft-backward, -spec); prefix: the RouteRow's
+    virtual std::string route(const char *prefix, bool agc) const
+    {
+        return std::string(prefix) + name() + (cfg.G > 1 ? "+interleaved-shard" : "") + (agc ? "+agc" : "");
+    }
     virtual bool tile_major_ok(uint32_t nf) const = 0;     // FusedCall::tile_major for a call of nf frames
 
     // M = 256 only
@@ -92,6 +99,9 @@ int  plan1024_create(const FusedConfig &cfg, ChainPlan **out);
 // frame + tails); whole band
 bool plan4096_supported(uint32_t M, uint32_t p);      // (CSDR_NO_RUN4096: no)
 int  plan4096_create(const FusedConfig &cfg, ChainPlan **out);
+// any M, any shard, any alpha (plan_generic.hip): what no row above takes
+bool generic_supported(uint32_t M, uint32_t p);
+int  generic_create(const FusedConfig &cfg, ChainPlan **out);
 
 // second-generation run kernel of the M = 256 chain (kernels_fused_v2.hip): whole-band calls of >= run_min_tiles tiles.
 // run_args points at a RunArgs (fused_common.h) the plan fills.
