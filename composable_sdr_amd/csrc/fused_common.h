@@ -3,6 +3,7 @@
 // 256 samples (16 runs of 16), whatever the channel count.  Product code.
 #pragma once
 #include "fused.h"
+#include "run_split.h"
 
 #include <cmath>
 #include <cstdlib>
@@ -389,20 +390,7 @@ __device__ __forceinline__ float2 frame_carry_zero_state(const float2 *T, const 
 
 constexpr int WU = 6;
 
-// How a launch's tiles are split into runs.  Runs are grouped in "slots": slot s holds rps consecutive runs that
-// share tiles[s] tiles evenly, starting at tile base[s].  One slot with rps = nruns is the plain balanced
-// split; the run kernels use one slot per co-resident workgroup of a CU (blockIdx / #CUs) so that the share of
-// a run can follow the issue priority its workgroup gets (oldest first) and all runs end together.
-struct RunSplit {
-    uint32_t rps, nslots;
-    uint32_t base[8], tiles[8];
-};
-__host__ __device__ __forceinline__ void run_range(const RunSplit &sp, uint32_t w, uint32_t &first, uint32_t &last)
-{
-    const uint32_t s = w / sp.rps, i = w - s * sp.rps;
-    first = sp.base[s] + (uint32_t)((unsigned long long)i * sp.tiles[s] / sp.rps);
-    last = sp.base[s] + (uint32_t)((unsigned long long)(i + 1) * sp.tiles[s] / sp.rps);
-}
+// (RunSplit, run_range, make_split -- how a launch's tiles are split into runs: run_split.h)
 
 struct RunArgs {
     TileArgs t;

@@ -318,32 +318,7 @@ __global__ __launch_bounds__(256) void k_tile256(TileArgs A)
 
 }  // namespace
 
-// Split nb tiles into nruns runs.  With one run per resident workgroup slot (nruns = slots x cus) slot k's runs
-// get a share proportional to weight[k]; otherwise the split is uniform.  Every run keeps >= 8 tiles.
-static RunSplit make_split(uint32_t nb, uint32_t nruns, uint32_t cus, const float *weight)
-{
-    RunSplit sp{};
-    const uint32_t slots = (cus && nruns % cus == 0) ? nruns / cus : 0;
-    if (slots >= 2 && slots <= 8) {
-        double tot = 0;
-        for (uint32_t k = 0; k < slots; k++) tot += weight[k];
-        sp.rps = cus; sp.nslots = slots;
-        uint32_t base = 0;
-        bool ok = true;
-        for (uint32_t k = 0; k < slots; k++) {
-            double cum = 0;
-            for (uint32_t q = 0; q <= k; q++) cum += weight[q];
-            const uint32_t end = (k + 1 == slots) ? nb : (uint32_t)std::llround((double)nb * cum / tot);
-            sp.base[k] = base; sp.tiles[k] = end - base;
-            if (end < base || sp.tiles[k] < 8 * cus) ok = false;
-            base = end;
-        }
-        if (ok) return sp;
-    }
-    sp = RunSplit{};
-    sp.rps = nruns; sp.nslots = 1; sp.base[0] = 0; sp.tiles[0] = nb;
-    return sp;
-}
+// (make_split -- nb tiles into nruns runs, whole tile pairs with the same total on every CU: run_split.h)
 
 // The chunk's last WU + 1 raw tiles -> the plan's tail slot (a kernel on the launch's own stream rather than a D2D memcpy: no
 // copy engine, no blit-path synchronisation in front of the run kernel)
@@ -378,6 +353,8 @@ struct FusedPlan : ChainPlan {
     u64 *d_trace = nullptr;
     uint32_t run_min_tiles = 1024;   // chunks with at least this many tiles use the run kernel (measured crossover: FM ~900 tiles, CF32 ~700; profiles/r04_call_size_sweeps.txt)
     float slot_weight[8] = {1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f};   // tile share of the k-th co-resident run of a CU
+    uint32_t slot_pairs[8] = {0, 0, 0, 0, 0, 0, 0, 0};                 // CSDR_RUN_PAIRS: its tile pairs, given outright
+    bool have_pairs = false;
     uint32_t resident_wgs_v2 = 512;  // workgroups of k_run256v2 the device holds at once
     bool use_v3 = false;             // variant builds only (CSDR_WITH_RUN256_V3 + CSDR_RUN_V3=1): k_run256v3, round 4's one-workgroup-per-CU experiment (tools/variants/)
     // independent launches (csdr_chain_submit_device): the last WU + 1 raw tiles of the previous chunk, three slots (the launch
@@ -551,6 +528,11 @@ int FusedPlan::init()
         int k = 0;
         for (const char *q = e; *q && k < 8; k++) { slot_weight[k] = (float)atof(q); q = strchr(q, ','); if (!q) break; q++; }
     }
+    if (const char *e = diag_env("CSDR_RUN_PAIRS")) {    // tile pairs per run of each class, e.g. 15,11,6 (make_split ignores it unless it sums to the pairs of a CU)
+        int k = 0;
+        for (const char *q = e; *q && k < 8; k++) { slot_pairs[k] = (uint32_t)atol(q); q = strchr(q, ','); if (!q) break; q++; }
+        have_pairs = true;
+    }
     return 0;
 }
 
@@ -622,11 +604,14 @@ int FusedPlan::run(const FusedCall &call, void *out, hipStream_t s, KernelTimer 
         static const float v2_weight_cf[8] = {1.2f, 0.8f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f};
         static const float v2_weight_fm[8] = {1.24f, 0.76f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f};      // with whole-line stores the younger workgroup loses more (r03 trace: 4.8 vs 7.6 us per tile)
         // whole-band FM (one tile buffer, three workgroups per CU): shares of the oldest, the middle and the youngest workgroup of a CU
-        static const float v2_weight_fm3[8] = {1.45f, 1.f, 0.55f, 1.f, 1.f, 1.f, 1.f, 1.f};   // measured: equal thirds 226 us, 1.3 : 1 : 0.7 217, 1.45 : 1 : 0.55 211
+        // (make_split turns the shares into whole tile pairs per run, the same on every CU: 16 + 10 + 6 pairs at the bench size.  Measured on exact
+        // triples, profiles/r08_run_split_ab.txt: (16, 10, 6) ahead of (15, 10, 7), (17, 9, 6), (16, 9, 7), (15, 11, 6), (17, 10, 5), (16, 11, 5), (14, 11, 7), (14, 12, 6))
+        static const float v2_weight_fm3[8] = {1.6f, 1.f, 0.6f, 1.f, 1.f, 1.f, 1.f, 1.f};
         const float *v2_weight = c.fm ? ((cus && nruns == 3 * cus) ? v2_weight_fm3 : v2_weight_fm) : v2_weight_cf;
         static const float equal_weight[8] = {1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f};
         static const bool pd_equal = diag_env("CSDR_PD_EQUAL") != nullptr;
-        RA.split = make_split(A.nb, nruns, cus, (call.indep && pd_equal) ? equal_weight : ((v2 && !diag_env("CSDR_RUN_WEIGHTS")) ? v2_weight : slot_weight));
+        RA.split = make_split(A.nb, nruns, cus, (call.indep && pd_equal) ? equal_weight : ((v2 && !diag_env("CSDR_RUN_WEIGHTS")) ? v2_weight : slot_weight),
+                              have_pairs ? slot_pairs : nullptr);
         { const char *e = diag_env("CSDR_PRIO_ROT"); RA.prio_div = e ? (atoi(e) ? cus : 0u) : (v2 ? 0u : cus); }
         { const char *e = diag_env("CSDR_TRACE"); RA.trace_light = (e && atoi(e) == 2) ? 1u : 0u; }
         { const char *e = diag_env("CSDR_WU"); RA.wu = e ? (uint32_t)atoi(e) : (uint32_t)WU; }       // experiments: fewer tiles = wrong DC state at run starts

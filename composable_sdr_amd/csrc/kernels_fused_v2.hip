@@ -152,6 +152,12 @@ __global__ __launch_bounds__(256, (FM && G == 1) ? V2_ONE_WGS : 2) void k_run256
 #define V2LSTAMP(i) do { } while (0)
 #endif
     V2LSTAMP(0);
+#if V2_TRACE
+    // where the run landed, next to its stamps: XCC_ID (s_getreg_b32 hwreg 20) << 32 | HW_ID (hwreg 4: CU_ID 11:8, SH_ID 12, SE_ID 15:13);
+    // the split assumes that the blocks c, c + #CUs, c + 2 #CUs share a CU, oldest first (tools/trace_tiles.py tabulates it)
+    if (A.trace && RA.trace_light && tid == 0)
+        A.trace[(size_t)first * 16 + 5] = ((u64)__builtin_amdgcn_s_getreg(20 | (31 << 11)) << 32) | (u64)__builtin_amdgcn_s_getreg(4 | (31 << 11));
+#endif
     // Everything the run start waits for is requested up front, so that the prologue is one burst of memory traffic and not
     // a chain of round trips: the first tile (buffer 0) and the halo tile (buffer 1) by DMA, the table values as plain loads.
     // cold run start: DC state from a read-only warm-up window, FIR window and freqdem history from the halo tile.  Run 0

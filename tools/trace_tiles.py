@@ -62,6 +62,31 @@ if "v2" in kn and os.environ["CSDR_TRACE"] == "2":
     pair = np.array([endw[cu == c].max() - endw[cu == c].min() for c in range(256)]) if len(idx) >= 512 else np.zeros(1)
     print("  spread of run end inside a CU (max - min over its workgroups): median", round(float(np.median(pair)), 1), "max", round(float(pair.max()), 1),
           "; CU-level last end: quantiles", np.quantile(np.array([endw[cu == c].max() for c in range(256)]), q).round(1))
+    # (1) which physical CU held which runs: the split gives class k = w // 256 the share of a CU's k-th oldest workgroup and assumes
+    #     that the blocks c, c + 256, c + 512 meet on one CU.  Slot 5 of a run's row: XCC_ID << 32 | HW_ID (CU_ID 11:8, SH_ID 12, SE_ID 15:13)
+    hw = buf[idx, 5].astype(np.int64)
+    cls = wv // 256
+    if hw.any():
+        from collections import Counter
+        phys = (((hw >> 32) & 0xF) << 8) | ((hw >> 8) & 0xFF)
+        ent_w = buf[idx, 0].astype(np.int64)
+        held, ordered = Counter(), 0
+        for p in np.unique(phys):
+            m = phys == p
+            held[tuple(int((cls[m] == k).sum()) for k in range(nslot))] += 1
+            o = np.argsort(ent_w[m], kind="stable")
+            ordered += int(np.all(np.diff(cls[m][o]) >= 0))
+        ncu = sum(held.values())
+        print(f"  runs of each class (w // 256) held by a physical CU, {ncu} CUs seen (XCC, SE, SH, CU):")
+        for t, n in sorted(held.items(), key=lambda kv: -kv[1]):
+            print(f"    {t}: {n} CUs ({100.0 * n / ncu:.1f} %)")
+        print(f"    exactly one run of each class: {100.0 * held.get((1,) * nslot, 0) / ncu:.1f} % of the CUs; runs entered in class order (oldest first) on {100.0 * ordered / ncu:.1f} %;"
+              f" same CU for w, w + 256, ...: {100.0 * np.mean([len(set(phys[cu == c])) == 1 for c in range(256)]):.1f} % of the triples")
+    # (2) when the runs of each class end
+    print("  run end by class, us after the first entry (quantiles 0/10/50/90/100):")
+    for k in range(nslot):
+        print(f"    class {k}: {np.quantile(endw[cls == k], q).round(1)}  spread p90 - p10 {np.subtract(*np.quantile(endw[cls == k], [.9, .1])):.1f}")
+    print(f"    all runs: last end {endw.max():.1f}, mean end {endw.mean():.1f} ({100.0 * endw.mean() / endw.max():.1f} % of the last)")
     sys.exit(0)
 if "v2" in kn:
     t = buf[:got, :15].astype(np.int64)
