@@ -2,6 +2,8 @@
 // 1024, 4096) and the any-M route (plan_generic.hip).  Product code.
 #pragma once
 #include "csdr_internal.h"
+#include <type_traits>
+#include <utility>
 
 namespace csdr {
 
@@ -32,6 +34,57 @@ struct FusedCall {
     bool tile_major = false;
 };
 
+// What the plans share lives in chain_plan.cpp.
+// The stream state the 64-, 256- and 1024-channel plans carry between calls, as ping-pong pairs: a call reads the side [cur] and writes
+// [cur ^ 1].  hist: the 13 frames in front of the call (DC-blocked samples), vend: the DC blocker's v1, rp: freqdem's r' per channel.
+struct StreamState {
+    int alloc(DeviceBuffers &mem, size_t n_hist, size_t n_rp);
+    int reset(hipStream_t s) const;      // zero both sides
+    const float2 *hist_in(int cur) const { return hist[cur]; }      float2 *hist_out(int cur) const { return hist[cur ^ 1]; }
+    const float2 *vend_in(int cur) const { return vend[cur]; }      float2 *vend_out(int cur) const { return vend[cur ^ 1]; }
+    const float2 *rp_in(int cur) const { return rp[cur]; }          float2 *rp_out(int cur) const { return rp[cur ^ 1]; }
+private:
+    float2 *hist[2] = {nullptr, nullptr}, *vend[2] = {nullptr, nullptr}, *rp[2] = {nullptr, nullptr};
+    size_t n_hist = 0, n_rp = 0;
+};
+
+// The DC blocker's constants as the kernels take them (v[n] = x[n] + beta v[n-1], y = x - alpha v[n-1]): fixed when the plan is made.
+// Blocker off: beta = 0 (every power but the zeroth is 0) and l2beta = -1000.
+struct DcConsts {
+    float alpha, beta, l2beta;      // alpha = 1 - beta with beta = f32(1 - alpha of the handle); log2(beta)
+    float b16[16], b256[17], bj[16], wtile[12];      // beta^(16 i), beta^(256 i), beta^i, beta^(4096 i) (LOOKBACK + 2 tiles: fused_common.h)
+    DcConsts(bool dc_block, const DcParams &dc);
+    // into the members of a kernel's argument struct that carry them (every struct has alpha; the rest as declared)
+    template <class Args> void put(Args &A) const
+    {
+        A.alpha = alpha;
+        if constexpr (has_beta<Args>::value) A.beta = beta;
+        if constexpr (has_l2beta<Args>::value) A.l2beta = l2beta;
+        if constexpr (has_b16<Args>::value) { copy(A.b16, b16); copy(A.b256, b256); }
+        if constexpr (has_bj<Args>::value) { copy(A.bj, bj); copy(A.wtile, wtile); }
+    }
+private:
+#define CSDR_HAS_MEMBER(m)                                                                                                       \
+    template <class A, class = void> struct has_##m : std::false_type {};                                                        \
+    template <class A> struct has_##m<A, std::void_t<decltype(std::declval<A &>().m)>> : std::true_type {};
+    CSDR_HAS_MEMBER(beta) CSDR_HAS_MEMBER(l2beta) CSDR_HAS_MEMBER(b16) CSDR_HAS_MEMBER(bj)
+#undef CSDR_HAS_MEMBER
+    template <size_t N> static void copy(float (&dst)[N], const float (&src)[N]) { for (size_t i = 0; i < N; i++) dst[i] = src[i]; }
+};
+
+// Cold starts without warm-up windows: a run starts its halo tile from DC state 0 and a correction kernel behind the launch puts
+// back, at the four channels around DC, what the true state would have added.  cpre: the state hand-over between the runs; side: the
+// uncorrected samples of those channels; rt: [2 parities][nfr][4] the chain's response to a unit state (dc_state_response), null when the
+// handle keeps its warm-up windows (blocker off, an alpha the window does not fit: dc_window_ok, or CSDR_NOWU=0).
+struct ColdStart {
+    float2 *cpre = nullptr, *side = nullptr, *rt = nullptr;
+    // window: the samples behind a cold start after which the missing state is dropped.  cpre (n_cpre elements, zeroed) and side (n_side;
+    // 0: none) are made with rt, or whatever rt when state_always (kernels that write them on every launch).  rt: frames f0 .. f0 + nfr - 1
+    // behind the tile's start at the channels k0 .. k0 + 3 on the phasor table wpre (k0 < 0: all zero)
+    int init(DeviceBuffers &mem, const FusedConfig &cfg, double window, size_t n_cpre, size_t n_side, bool state_always,
+             uint32_t f0, uint32_t nfr, int k0, const float2 *wpre);
+};
+
 // The plan of one route (a RouteRow of capi.hip): M = 64 (kernels_fused_small.hip), 256 (kernels_fused.hip), 1024 (kernels_pfb1024.hip),
 // 4096 (kernels_pfb4096.hip) and any M (plan_generic.hip) derive from it.  With the AGC on (cfg.fm and cfg.mix are then false) a plan delivers
 // the channel-major CF32 plane the handle's tail reads; without it, the call's output.  The base owns what they share: the configuration, the CU count, the global frame counter,
@@ -44,8 +97,9 @@ struct ChainPlan {
     int cur = 0;                 // the next call reads the state buffers [cur] and writes [cur ^ 1]
     void *d_premix = nullptr;    // per-channel output in front of launch_mix (cfg.mix; the M = 4096 plan mixes in its back kernel)
     DeviceBuffers mem;
+    const DcConsts dcc;          // of cfg.dc_block and cfg.dc
 
-    explicit ChainPlan(const FusedConfig &c) : cfg(c), cus(c.cus) {}
+    explicit ChainPlan(const FusedConfig &c) : cfg(c), cus(c.cus), dcc(c.dc_block, c.dc) {}
     virtual ~ChainPlan() = default;
 
     // One call.  A tile-major or independent request the plan cannot run (tile_major_ok, can_overlap) is refused before anything is queued.
@@ -110,9 +164,6 @@ int  run256_v2_blocks_per_cu(bool fm, unsigned G);
 // RunArgs::nowu launches: the near-DC channels of every run's first 112 frames get what the true DC state at the run's start adds (Rt: host table
 // [2 parities][DCFIX_F][4], fused_common.h)
 int  run256_dcfix_launch(const void *run_args, bool fm, unsigned nruns, const float2 *Rt, hipStream_t s);
-// round 4's experiment (tools/variants/kernels_run256_v3.hip, NOT part of the product library: measured not faster: DESIGN.md 8.1):
-// one 512-thread workgroup per CU, front / back wave roles; linked only by tools/variants/build_run256_v3.sh (-DCSDR_WITH_RUN256_V3)
-int  run256_v3_launch(const void *run_args, bool fm, unsigned nruns, hipStream_t s);
 
 
 // k_run64v2 (kernels_run64_v2.hip): whole-band M = 64 calls with CF32 output and nf % 64 == 0; same state buffers as k_run64
@@ -126,11 +177,11 @@ struct Run64v2Host {
     uint32_t nf, nruns, parity0;
     uint32_t G = 1, g = 0;      // interleaved shard g of G (tables rotated by the plan)
     bool tile_major = false;    // CF32 plane of the AGC route: [block of 16 frames][64][128 B]
-    bool dc_block;
-    double beta;
+    const DcConsts *dc;         // the plan's
+    double weight = 1.1;        // tile share of the older workgroup of a CU (1 = even; 1.1 measured best: 243 vs 250 us; CSDR_RUN64_WEIGHT)
 };
 constexpr int RUN64_DCFIX_F = 448;                      // output frames of a run the state correction covers (7 tiles: 32 768 samples behind the halo tile's start)
-uint32_t run64_v2_runs(uint32_t nf, uint32_t cus);      // 0: not a call for the kernel
+uint32_t run64_v2_runs(uint32_t nf, uint32_t cus, bool all);      // 0: not a call for the kernel; all: no size threshold (CSDR_RUN64_V2_ALL)
 // Response of the chain (pre-mix table wpre [2][M], taps, forward DFT), at the channels k0 .. k0 + 3, to a DC-blocker state of 1 in
 // front of a tile: frames f0 .. f0 + nfr - 1 behind the tile's start, both parities of the tile's first frame; rt [2][nfr][4], f64 inside
 void dc_state_response(const FusedConfig &cfg, const float2 *wpre, uint32_t f0, uint32_t nfr, uint32_t k0, float2 *rt);
@@ -150,11 +201,17 @@ struct Run1024v2Host {
     // response to a unit state there; null: warm-up windows
     float2 *cpre = nullptr, *side = nullptr; const float2 *rt = nullptr;
     int mfix = -1;              // k_shard1024: the shard's row among the four channels around DC (side [nruns][RUN1024_DCFIX_F], rt channel 0), -1: none
-    bool dc_block;
-    double beta;
+    const DcConsts *dc;         // the plan's
     float fm_ref;
+    double weight = 1.2;        // k_run1024v2: tile share of the older workgroup of a CU (1 = even; CSDR_RUN1024_WEIGHT)
+    // debug builds of k_run1024v3 / k_shard1024: the plan's stamp buffer (RUN1024_V3_TRACE_N / SHARD1024_TRACE_N) and the file the
+    // launcher writes the last launch's stamps to (CSDR_RUN1024_V3_TRACE, CSDR_SHARD1024_TRACE); null: no trace
+    unsigned long long *trace = nullptr; const char *trace_file = nullptr;
 };
-uint32_t run1024_v2_runs(uint32_t nf, uint32_t cus);    // 0: call too short for the kernel
+constexpr size_t RUN1024_V3_TRACE_N = 1536, SHARD1024_TRACE_N = 768;
+// max_runs of the three *_runs below: 0, or an upper limit of the run count below the default (CSDR_RUN1024_RUNS, CSDR_RUN1024_V3_RUNS,
+// CSDR_SHARD1024_RUNS: experiments, and tests that force runs onto short inputs)
+uint32_t run1024_v2_runs(uint32_t nf, uint32_t cus, uint32_t max_runs);    // 0: call too short for the kernel
 int run1024_v2_launch(const Run1024v2Host &h, bool fm, hipStream_t s, KernelTimer *timer);
 // third-generation FM kernel (kernels_run1024_v3.hip): one 512-thread workgroup per CU, output lines staged in registers (no staging
 // block); whole band, calls of whole output lines (nf = 0 mod 32 frames F32 / 16 frames CF32)
@@ -164,9 +221,9 @@ int run1024_v2_launch(const Run1024v2Host &h, bool fm, hipStream_t s, KernelTime
 constexpr int RUN1024_DCFIX_F = 33;
 // interleaved-shard run kernel (kernels_shard1024.hip, round 6): chan_stride G = 4, 8, F32 or CF32 rows of the owned channels; the fold of the
 // aliasing branches behind the FIR + a (1024 / G)-point DFT across the lanes of a wave; same state arrays and tables as the plan's other kernels
-uint32_t shard1024_runs(uint32_t nf, bool fm, uint32_t G, uint32_t cus);    // 0: the call is not for this kernel
+uint32_t shard1024_runs(uint32_t nf, bool fm, uint32_t G, uint32_t cus, uint32_t max_runs);    // 0: the call is not for this kernel
 int shard1024_launch(const Run1024v2Host &h, bool fm, uint32_t nruns, hipStream_t s, KernelTimer *timer);
-uint32_t run1024_v3_runs(uint32_t nf, bool fm, uint32_t cus);    // 0: the call is not for this kernel
+uint32_t run1024_v3_runs(uint32_t nf, bool fm, uint32_t cus, uint32_t max_runs);    // 0: the call is not for this kernel
 int run1024_v3_launch(const Run1024v2Host &h, bool fm, uint32_t nruns, hipStream_t s, KernelTimer *timer);
 
 

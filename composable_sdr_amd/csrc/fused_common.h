@@ -200,6 +200,14 @@ __host__ __device__ __forceinline__ PhaseK phase_consts(float ref)
     k.hp = 1.57079632679489662f * ref; k.pi = 3.14159265358979324f * ref; k.ref = ref;
     return k;
 }
+// For the tails that scale a = min / max by ref before the last product (scaled_atan2f and its kin): the unscaled polynomial, with hp, pi
+// and ref scaled
+inline PhaseK phase_consts_scaled(float ref)
+{
+    PhaseK k = phase_consts(1.0f);
+    k.hp *= ref; k.pi *= ref; k.ref = ref;
+    return k;
+}
 // Selects with the condition in an SGPR pair: on gfx950 the VCC form of v_cndmask (what hipcc emits for `c ? a : b`) costs
 // 16 cycles per wave, the SGPR-mask form 4.6 (tools/probes/issue_probe2.hip).
 __device__ __forceinline__ float sel_abs_gt(float a, float b, float t, float f)        // |a| > |b| ? t : f
@@ -277,6 +285,7 @@ struct TileArgs {
     float b256[17];             // beta^(256 f)
     float bj[16];               // beta^i
 };
+static_assert(sizeof(TileArgs::wtile) == sizeof(DcConsts::wtile), "DcConsts::wtile holds LOOKBACK + 2 tile weights");
 
 // Raw tile -> registers: 8 x 16 bytes per thread, addressed so that the LDS image below is
 // XOR-swizzled at 16-byte granularity (both the run-major b128 accesses and the column-major
@@ -405,7 +414,7 @@ struct RunArgs {
     uint32_t pair_align;        // k_run256v2<FM>: run boundaries rounded down to even tiles (whole 128-byte output lines per tile pair)
     uint32_t wu_batch6;         // k_run256v2: the six warm-up tiles in one batch of loads (0: two batches of three)
     uint32_t wu, wu_rot;        // k_run256v2: read-only warm-up tiles in front of a run's halo tile (WU = 6); runs walk them in rotated order
-    uint32_t tile_step;         // k_run256v2 / v3: bytes between consecutive tiles in the output (16 frames x element size for row-major rows; C x 128 tile-major)
+    uint32_t tile_step;         // k_run256v2: bytes between consecutive tiles in the output (16 frames x element size for row-major rows; C x 128 tile-major)
     // round 5, whole-band k_run256v2: no read-only warm-up window at a run's start.  The run starts its halo tile from DC state 0; what
     // the true state would have added is, 16 frames later, confined to the four channels around DC (the step's edge excites every channel
     // for 13 frames -- the length of the FIR -- inside the halo tile, which has no output): k_run256_dcfix adds c_true x (the chain's

@@ -516,12 +516,7 @@ int dctile_create(const DcParams &dc, uint64_t max_samples, DcTilePlan **out)
     CSDR_HIP(hipMemset(p->d_vend[1], 0, sizeof(float2)));
     DcTileArgs &D = p->proto;
     D = DcTileArgs{};
-    const double beta = (double)dc.beta;
-    D.alpha = (float)(1.0 - beta); D.beta = (float)beta;
-    for (int k = 0; k < LOOKBACK + 2; k++) D.wtile[k] = (float)std::pow(beta, 4096.0 * k);
-    for (int k = 0; k < 16; k++) D.b16[k] = (float)std::pow(beta, 16.0 * k);
-    for (int k = 0; k < 17; k++) D.b256[k] = (float)std::pow(beta, 256.0 * k);
-    for (int k = 0; k < 16; k++) D.bj[k] = (float)std::pow(beta, (double)k);
+    DcConsts(true, dc).put(D);
     D.ticket = p->d_ticket; D.agg = p->d_agg; D.status = p->d_status;
     *out = p;
     return 0;

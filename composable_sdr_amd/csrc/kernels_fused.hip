@@ -337,33 +337,43 @@ __global__ __launch_bounds__(64) void k_shard_gather(const float *__restrict__ s
     for (uint32_t i = threadIdx.x; i < rem * w; i += 64) dst[((size_t)m * nf + t0) * w + i] = src[(size_t)(c0 + G * m) * rem * w + i];
 }
 
+// k_run256v2: the older of a CU's two workgroups wins the issue arbitration and runs ~1.4x faster than the younger one, so it gets the
+// larger share of the tiles (measured: both end together at about 1.2 : 0.8); rotating the priority per tile instead was no better
+constexpr float V2_WEIGHT_CF[8] = {1.2f, 0.8f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f};
+constexpr float V2_WEIGHT_FM[8] = {1.24f, 0.76f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f};      // with whole-line stores the younger workgroup loses more (r03 trace: 4.8 vs 7.6 us per tile)
+// whole-band FM (one tile buffer, three workgroups per CU): shares of the oldest, the middle and the youngest workgroup of a CU
+// (make_split turns the shares into whole tile pairs per run, the same on every CU: 16 + 10 + 6 pairs at the bench size.  Measured on exact
+// triples, profiles/r08_run_split_ab.txt: (16, 10, 6) ahead of (15, 10, 7), (17, 9, 6), (16, 9, 7), (15, 11, 6), (17, 10, 5), (16, 11, 5), (14, 11, 7), (14, 12, 6))
+constexpr float V2_WEIGHT_FM3[8] = {1.6f, 1.f, 0.6f, 1.f, 1.f, 1.f, 1.f, 1.f};
+constexpr float EQUAL_WEIGHT[8] = {1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f};
+
 struct FusedPlan : ChainPlan {
     using ChainPlan::ChainPlan;
     std::string kernel;
     uint32_t max_nb = 0, epoch = 0;
     float *d_taps = nullptr;
     float2 *d_tw = nullptr, *d_wpre = nullptr;
-    float2 *d_yhist[2] = {nullptr, nullptr}, *d_vend[2] = {nullptr, nullptr}, *d_rp[2] = {nullptr, nullptr};
+    StreamState st;
     unsigned *d_ticket = nullptr, *d_yflag = nullptr, *d_status = nullptr;
     u64 *d_agg = nullptr, *d_ylast = nullptr;
     // whole-band run-kernel launches without warm-up windows (RunArgs::nowu, round 5): DC state in front of every run's halo tile, the
     // uncorrected near-DC channels of every run's first tiles, the chain's response to a unit DC state (k_run256_dcfix)
-    float2 *d_cpre = nullptr, *d_side = nullptr, *d_rt = nullptr;
-    bool nowu = false;
+    ColdStart cold;
     u64 *d_trace = nullptr;
     uint32_t run_min_tiles = 1024;   // chunks with at least this many tiles use the run kernel (measured crossover: FM ~900 tiles, CF32 ~700; profiles/r04_call_size_sweeps.txt)
-    float slot_weight[8] = {1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f};   // tile share of the k-th co-resident run of a CU
+    float slot_weight[8] = {1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f};   // CSDR_RUN_WEIGHTS: tile share of the k-th co-resident run of a CU
     uint32_t slot_pairs[8] = {0, 0, 0, 0, 0, 0, 0, 0};                 // CSDR_RUN_PAIRS: its tile pairs, given outright
-    bool have_pairs = false;
+    bool have_weights = false, have_pairs = false;
+    bool pd_equal = false, pd_nocopy = false;     // CSDR_PD_EQUAL, CSDR_PD_NOCOPY: scheduling experiments of the independent launches (the second: wrong run-0 starts)
     uint32_t resident_wgs_v2 = 512;  // workgroups of k_run256v2 the device holds at once
-    bool use_v3 = false;             // variant builds only (CSDR_WITH_RUN256_V3 + CSDR_RUN_V3=1): k_run256v3, round 4's one-workgroup-per-CU experiment (tools/variants/)
     // independent launches (csdr_chain_submit_device): the last WU + 1 raw tiles of the previous chunk, three slots (the launch
     // two calls back may still be reading its slot when this call's copy is queued on the other stream)
     float *d_shard_tail = nullptr;   // interleaved shard: whole-band result of a call's ragged end, [256][< 16] CF32 at most
     float4 *d_tail[3] = {nullptr, nullptr, nullptr};
     int tail_w = 0;                  // slot that holds the tail of the most recent chunk
     bool tail_valid = false, save_tails = false;
-    TileArgs proto;
+    TileArgs proto;                  // what init() fixes of a k_tile256 launch
+    RunArgs run_proto;               // and of a k_run256v2 launch: the DC and phase constants, the cold-start arrays and the launch knobs
 
     int init();
     const char *name() const override { return kernel.c_str(); }
@@ -376,72 +386,20 @@ struct FusedPlan : ChainPlan {
     int reset_state(hipStream_t s) override;
     int run(const FusedCall &call, void *out, hipStream_t s, KernelTimer *timer) override;
     bool v2_call(uint32_t nf) const { return cfg.G == 1 && cfg.c0 == 0 && cfg.C == cfg.M && nf / NB >= run_min_tiles; }
+    void wire_state(TileArgs &A) const;
+    int run_kernel(const FusedCall &call, const TileArgs &A, hipStream_t s, KernelTimer *timer);
+    int tile_kernel(TileArgs &T, hipStream_t s, KernelTimer *timer);
+    int ragged_end(const FusedCall &call, void *out, uint32_t nb_full, uint32_t rem, hipStream_t s);
 };
-
-int ChainPlan::process(const FusedCall &call, hipStream_t s, KernelTimer *timer)
-{
-    if (!call.nf) return 0;
-    if ((call.tile_major && !tile_major_ok(call.nf)) || (call.indep && !can_overlap(call.nf))) {
-        set_error("fused: internal: tile-major output or an independent launch requested from a call that cannot run as one");
-        return -1;
-    }
-    int r = run(call, d_premix ? d_premix : call.d_out, s, timer);
-    if (r) return r;
-    cur ^= 1;
-    frames_done += call.nf;
-    if (d_premix) return launch_mix((const float *)d_premix, (float *)call.d_out, cfg.C, cfg.fm ? call.nf : 2 * call.nf, s);
-    return 0;
-}
-
-std::vector<float2> ChainPlan::premix_table() const
-{
-    std::vector<float2> wpre(2 * cfg.M);
-    for (uint32_t i = 0; i < 2 * cfg.M; i++) {
-        float c, s;
-        nco_phasor(i * cfg.d_theta, &c, &s);
-        wpre[i] = make_float2(c, -s);
-    }
-    return wpre;
-}
 
 bool plan256_supported(uint32_t M, uint32_t p) { return M == 256 && p == P; }
 int plan256_create(const FusedConfig &cfg, ChainPlan **out) { return make_plan<FusedPlan>(cfg, out); }
 
-void dc_state_response(const FusedConfig &cfg, const float2 *wpre, uint32_t f0, uint32_t nfr, uint32_t k0, float2 *rt)
+// a comma-separated knob into at most eight values
+template <class T, class Conv> static void parse_list(const char *e, T (&v)[8], Conv conv)
 {
-    // the blocker's output carries -alpha beta^n of the state at sample n behind the tile's start; that goes through the pre-mix, the
-    // polyphase FIR and the DFT like any input
-    const uint32_t M = cfg.M, T = f0 + nfr;
-    const double beta = (double)cfg.dc.beta, alpha = 1.0 - beta, tp = -2.0 * 3.14159265358979323846;
-    std::vector<double> ur((size_t)T * M), ui((size_t)T * M), xr(M), xi(M);
-    for (uint32_t par = 0; par < 2; par++) {
-        for (uint32_t f = 0; f < T; f++)
-            for (uint32_t j = 0; j < M; j++) {
-                const double e = -alpha * std::pow(beta, (double)f * M + j);
-                const float2 wv = wpre[((par + f) & 1u) * M + j];
-                ur[(size_t)f * M + j] = e * (double)wv.x; ui[(size_t)f * M + j] = e * (double)wv.y;
-            }
-        for (uint32_t t = 0; t < nfr; t++) {
-            const uint32_t f = f0 + t;
-            for (uint32_t j = 0; j < M; j++) {
-                double ar = 0.0, ai = 0.0;
-                for (uint32_t n = 0; n < cfg.p && n <= f; n++) {
-                    const double hh = (double)cfg.taps[(M - 1 - j) + n * M];
-                    ar += hh * ur[(size_t)(f - n) * M + j]; ai += hh * ui[(size_t)(f - n) * M + j];
-                }
-                xr[j] = ar; xi[j] = ai;
-            }
-            for (uint32_t ch = 0; ch < 4; ch++) {
-                const uint32_t k = k0 + ch;
-                double yr = 0.0, yi = 0.0;
-                for (uint32_t j = 0; j < M; j++) {
-                    const double a = tp * (double)((j * k) % M) / (double)M, cr = std::cos(a), ci = std::sin(a);
-                    yr += xr[j] * cr - xi[j] * ci; yi += xr[j] * ci + xi[j] * cr;
-                }
-                rt[((size_t)par * nfr + t) * 4 + ch] = make_float2((float)yr, (float)yi);
-            }
-        }
-    }
+    int k = 0;
+    for (const char *q = e; *q && k < 8; k++) { v[k] = (T)conv(q); q = strchr(q, ','); if (!q) break; q++; }
 }
 
 int FusedPlan::init()
@@ -452,11 +410,7 @@ int FusedPlan::init()
     if ((r = mem.alloc(&d_taps, sizeof(float) * cfg.M * cfg.p))) return r;
     if ((r = mem.alloc(&d_tw, sizeof(float2) * cfg.M))) return r;
     if ((r = mem.alloc(&d_wpre, sizeof(float2) * 2 * cfg.M))) return r;
-    for (int i = 0; i < 2; i++) {
-        if ((r = mem.alloc(&d_yhist[i], sizeof(float2) * 13 * cfg.M))) return r;
-        if ((r = mem.alloc(&d_vend[i], sizeof(float2)))) return r;
-        if ((r = mem.alloc(&d_rp[i], sizeof(float2) * (cfg.G > 1 ? cfg.M : cfg.C)))) return r;     // interleaved shard: full-band indices (fused_v2: rp_in / rp_out)
-    }
+    if ((r = st.alloc(mem, 13 * cfg.M, cfg.G > 1 ? cfg.M : cfg.C))) return r;     // interleaved shard: full-band indices (fused_v2: rp_in / rp_out)
     if (cfg.G > 1 && (r = mem.alloc(&d_shard_tail, sizeof(float2) * cfg.M * NB))) return r;
     for (int i = 0; i < 3; i++) {
         if ((r = mem.alloc(&d_tail[i], sizeof(float4) * 2048 * (WU + 1)))) return r;
@@ -470,17 +424,10 @@ int FusedPlan::init()
     if ((r = mem.alloc(&d_ylast, sizeof(u64) * (size_t)cfg.M * max_nb))) return r;
     if (const char *e = diag_env("CSDR_RUN_MIN_TILES")) run_min_tiles = (uint32_t)atol(e);
     if (cfg.mix && (r = mem.alloc(&d_premix, (size_t)cfg.C * cfg.max_nf * (cfg.fm ? 4 : 8)))) return r;
-    if (diag_env("CSDR_TRACE")) {
+    const char *trace_knob = diag_env("CSDR_TRACE");
+    if (trace_knob) {
         if ((r = mem.alloc(&d_trace, sizeof(u64) * 16 * max_nb))) return r;
         CSDR_HIP(hipMemset(d_trace, 0, sizeof(u64) * 16 * max_nb));
-    }
-    nowu = cfg.G == 1 && cfg.c0 == 0 && cfg.C == cfg.M && cfg.dc_block && dc_window_ok(cfg.dc, (DCFIX_F - 1) * 256.0) &&     // k_run256_dcfix: 112 frames
-           !(diag_env("CSDR_NOWU") && atoi(diag_env("CSDR_NOWU")) == 0);
-    if (nowu) {
-        if ((r = mem.alloc(&d_cpre, sizeof(float2) * 2050))) return r;
-        if ((r = mem.alloc(&d_side, sizeof(float2) * 2048 * 4 * DCFIX_F))) return r;
-        if ((r = mem.alloc(&d_rt, sizeof(float2) * 2 * DCFIX_F * 4))) return r;
-        CSDR_HIP(hipMemset(d_cpre, 0, sizeof(float2) * 2050));
     }
     CSDR_HIP(hipMemcpy(d_taps, cfg.taps, sizeof(float) * cfg.M * cfg.p, hipMemcpyHostToDevice));
     std::vector<float2> tw(cfg.M);
@@ -492,16 +439,11 @@ int FusedPlan::init()
     const std::vector<float2> wpre = premix_table();
     CSDR_HIP(hipMemcpy(d_tw, tw.data(), sizeof(float2) * cfg.M, hipMemcpyHostToDevice));
     CSDR_HIP(hipMemcpy(d_wpre, wpre.data(), sizeof(float2) * 2 * cfg.M, hipMemcpyHostToDevice));
-    if (nowu) {
-        // Response of the chain, at the channels 126..129, to a DC-blocker state of 1 in front of a tile: the blocker's output carries
-        // -alpha beta^n of it at sample n, which goes through the pre-mix (the table above), the polyphase FIR and the DFT like any
-        // input.  Frames 15 .. 127 behind the tile's start = frame -1 .. 111 of the run that started its halo tile without its state;
-        // by then the step's edge (13 frames of FIR, every channel) has left the filter and what remains sits around DC.  Both parities of
-        // the tile's first frame; f64 throughout.
-        std::vector<float2> rt((size_t)2 * DCFIX_F * 4);
-        dc_state_response(cfg, wpre.data(), 15u, (uint32_t)DCFIX_F, 126u, rt.data());
-        CSDR_HIP(hipMemcpy(d_rt, rt.data(), sizeof(float2) * rt.size(), hipMemcpyHostToDevice));
-    }
+    // Whole band: the response of the chain, at the channels 126..129, to a DC-blocker state of 1 in front of a tile.  Frames 15 .. 127
+    // behind the tile's start = frame -1 .. 111 of the run that started its halo tile without its state (k_run256_dcfix: 112 frames); by
+    // then the step's edge (13 frames of FIR, every channel) has left the filter and what remains sits around DC.
+    if (cfg.G == 1 && cfg.c0 == 0 && cfg.C == cfg.M &&
+        (r = cold.init(mem, cfg, (DCFIX_F - 1) * 256.0, 2050, (size_t)2048 * 4 * DCFIX_F, false, 15u, (uint32_t)DCFIX_F, 126, wpre.data()))) return r;
     CSDR_HIP(hipMemset(d_status, 0, sizeof(unsigned)));
     CSDR_HIP(hipMemset(d_yflag, 0, sizeof(unsigned) * max_nb));
     CSDR_HIP(hipMemset(d_agg, 0, sizeof(u64) * 2 * max_nb));
@@ -511,38 +453,33 @@ int FusedPlan::init()
     A.taps = d_taps; A.tw = d_tw; A.wpre = d_wpre;
     A.ticket = d_ticket; A.agg = d_agg; A.ylast = d_ylast; A.yflag = d_yflag; A.status = d_status;
     A.c0 = cfg.c0; A.C = cfg.C; A.fm_ref = cfg.fm_ref; A.trace = d_trace;
-    const double beta = cfg.dc_block ? (double)cfg.dc.beta : 0.0;
-    A.alpha = cfg.dc_block ? (float)(1.0 - beta) : 0.0f;    // alpha = 1 - beta with beta = f32(1 - 0.0005)
-    A.beta = (float)beta;
-    for (int k = 0; k < LOOKBACK + 2; k++) A.wtile[k] = (float)std::pow(beta, 4096.0 * k);
-    for (int k = 0; k < 16; k++) A.b16[k] = (float)std::pow(beta, 16.0 * k);
-    for (int k = 0; k < 17; k++) A.b256[k] = (float)std::pow(beta, 256.0 * k);
-    for (int k = 0; k < 16; k++) A.bj[k] = (float)std::pow(beta, (double)k);
+    dcc.put(A);
     if (const char *e = diag_env("CSDR_CUS")) { if (atoi(e) > 0 && (uint32_t)atoi(e) < cus) cus = (uint32_t)atoi(e); }     // experiments: a plan sized for a CU-masked stream
     resident_wgs_v2 = (uint32_t)(cus * run256_v2_blocks_per_cu(cfg.fm, cfg.G));
     if (const char *e = diag_env("CSDR_RESIDENT_WGS")) resident_wgs_v2 = (uint32_t)atol(e);
-#ifdef CSDR_WITH_RUN256_V3          // variant build only (tools/variants/build_run256_v3.sh): round 4's one-workgroup-per-CU experiment
-    if (const char *e = diag_env("CSDR_RUN_V3")) use_v3 = atoi(e) != 0;
-#endif
-    if (const char *e = diag_env("CSDR_RUN_WEIGHTS")) {
-        int k = 0;
-        for (const char *q = e; *q && k < 8; k++) { slot_weight[k] = (float)atof(q); q = strchr(q, ','); if (!q) break; q++; }
-    }
-    if (const char *e = diag_env("CSDR_RUN_PAIRS")) {    // tile pairs per run of each class, e.g. 15,11,6 (make_split ignores it unless it sums to the pairs of a CU)
-        int k = 0;
-        for (const char *q = e; *q && k < 8; k++) { slot_pairs[k] = (uint32_t)atol(q); q = strchr(q, ','); if (!q) break; q++; }
-        have_pairs = true;
-    }
+    if (const char *e = diag_env("CSDR_RUN_WEIGHTS")) { parse_list(e, slot_weight, atof); have_weights = true; }
+    // tile pairs per run of each class, e.g. 15,11,6 (make_split ignores it unless it sums to the pairs of a CU)
+    if (const char *e = diag_env("CSDR_RUN_PAIRS")) { parse_list(e, slot_pairs, atol); have_pairs = true; }
+    pd_equal = diag_env("CSDR_PD_EQUAL") != nullptr;
+    pd_nocopy = diag_env("CSDR_PD_NOCOPY") != nullptr;
+
+    RunArgs &RA = run_proto;
+    RA = RunArgs{};
+    RA.pk = phase_consts(cfg.fm_ref);
+    RA.l2beta = dcc.l2beta;
+    RA.cpre = cold.cpre; RA.side = cold.side;
+    { const char *e = diag_env("CSDR_PRIO_ROT"); RA.prio_div = (e && atoi(e)) ? cus : 0u; }
+    RA.trace_light = (trace_knob && atoi(trace_knob) == 2) ? 1u : 0u;
+    { const char *e = diag_env("CSDR_WU"); RA.wu = e ? (uint32_t)atoi(e) : (uint32_t)WU; }       // experiments: fewer tiles = wrong DC state at run starts
+    { const char *e = diag_env("CSDR_WU_ROT"); RA.wu_rot = e ? (uint32_t)atoi(e) : 0u; }      // measured: no effect on the run-start burst
+    RA.pair_align = (cfg.fm || diag_env("CSDR_PAIR_ALIGN_CF")) ? 1u : 0u;
+    { const char *e = diag_env("CSDR_WU_BATCH6"); RA.wu_batch6 = e ? (uint32_t)atoi(e) : 1u; }
     return 0;
 }
 
 int FusedPlan::reset_state(hipStream_t s)
 {
-    for (int i = 0; i < 2; i++) {
-        CSDR_HIP(hipMemsetAsync(d_yhist[i], 0, sizeof(float2) * 13 * cfg.M, s));
-        CSDR_HIP(hipMemsetAsync(d_vend[i], 0, sizeof(float2), s));
-        CSDR_HIP(hipMemsetAsync(d_rp[i], 0, sizeof(float2) * (cfg.G > 1 ? cfg.M : cfg.C), s));
-    }
+    if (int r = st.reset(s)) return r;
     CSDR_HIP(hipMemsetAsync(d_tail[0], 0, sizeof(float4) * 2048 * (WU + 1), s));
     tail_w = 0; tail_valid = true;
     return 0;
@@ -550,7 +487,7 @@ int FusedPlan::reset_state(hipStream_t s)
 
 bool FusedPlan::tile_major_ok(uint32_t nf) const
 {
-    // the calls that go to k_run256v2 / v3 as whole tiles: CF32 output below 4 GiB, no mix inside the plan
+    // the calls that go to k_run256v2 as whole tiles: CF32 output below 4 GiB, no mix inside the plan
     if (cfg.fm || cfg.mix || nf % NB || !nf) return false;
     if (cfg.G > 1) return (uint64_t)cfg.C * nf * 8u < (1ull << 32);
     return cfg.c0 == 0 && cfg.C == cfg.M && nf / NB >= run_min_tiles;
@@ -561,122 +498,117 @@ bool FusedPlan::can_overlap(uint32_t nf) const
     return save_tails && tail_valid && v2_call(nf) && nf % NB == 0 && !cfg.mix;
 }
 
+void FusedPlan::wire_state(TileArgs &A) const
+{
+    A.yhist_in = st.hist_in(cur); A.yhist_out = st.hist_out(cur);
+    A.vend_in = st.vend_in(cur);  A.vend_out = st.vend_out(cur);
+    A.rp_in = st.rp_in(cur);      A.rp_out = st.rp_out(cur);
+}
+
 int FusedPlan::run(const FusedCall &call, void *out, hipStream_t s, KernelTimer *timer)
 {
     const FusedConfig &c = cfg;
-    const uint32_t nf = call.nf;
+    const uint32_t nf = call.nf, nb_full = nf / NB, rem = nf - nb_full * NB;
+    const bool shard = c.G > 1;      // interleaved shard: every whole tile goes through k_run256v2<.., G> (the tile kernel only knows whole bands)
+    if (shard && (uint64_t)c.C * nf * (c.fm ? 4u : 8u) >= (1ull << 32)) { set_error("fused: interleaved shard output of %u frames exceeds 4 GiB", nf); return -1; }
     int r;
     TileArgs A = proto;
     A.x = call.d_in;
     A.out = out;
-    A.yhist_in = d_yhist[cur]; A.yhist_out = d_yhist[cur ^ 1];
-    A.vend_in = d_vend[cur];   A.vend_out = d_vend[cur ^ 1];
-    A.rp_in = d_rp[cur];       A.rp_out = d_rp[cur ^ 1];
-    A.out_stride = nf; A.out_t0 = 0;
-    if (call.tile_major) A.out_stride = NB;      // a row's 16 frames of a tile are one 128-byte line; rows follow each other inside the tile's block
+    wire_state(A);
+    A.out_stride = call.tile_major ? NB : nf;      // tile-major: a row's 16 frames of a tile are one 128-byte line; rows follow each other inside the tile's block
+    A.out_t0 = 0;
     A.parity0 = (uint32_t)(frames_done & 1);
-    const uint32_t nb_full = nf / NB;
-    const bool shard = c.G > 1;      // interleaved shard: every whole tile goes through k_run256v2<.., G> (the tile kernel only knows whole bands)
-    if (shard && (uint64_t)c.C * nf * (c.fm ? 4u : 8u) >= (1ull << 32)) { set_error("fused: interleaved shard output of %u frames exceeds 4 GiB", nf); return -1; }
-    const bool whole_band = c.G == 1 && c.c0 == 0 && c.C == c.M;      // (a contiguous channel shard takes the tile kernel, which masks its stores, at every size)
-    if ((nb_full >= run_min_tiles && whole_band) || shard) {
+    if (v2_call(nf) || shard) {      // (a contiguous channel shard takes the tile kernel, which masks its stores, at every size)
         // large chunk: dependency-free runs of full tiles (k_run256v2; its lane offsets are 32-bit over 16 rows and the row groups
         // go through a 64-bit base, so the output may exceed 4 GiB); a ragged tail (< 16 frames) follows as a second launch of the
         // tile kernel on the state the run kernel leaves behind
-        const bool v2 = true;
-        // third generation: one 512-thread workgroup per CU (half the cold starts), whole band
-        const bool v3 = !shard && use_v3;
-        kernel = v3 ? (c.fm ? "k_run256v3<FM>" : "k_run256v3<CF32>") : (c.fm ? "k_run256v2<FM>" : "k_run256v2<CF32>");
-        if (shard) kernel += "/G" + std::to_string(c.G);
-        RunArgs RA{};
         A.nf = nb_full * NB; A.nb = nb_full;
-        RA.t = A; RA.pk = phase_consts(c.fm_ref);
-        // one run per resident workgroup slot (a single round), runs balanced to within one tile,
-        // at least 8 tiles per run so that the warm-up reads stay below 7/8 of a run
-        uint32_t nruns = v3 ? cus : resident_wgs_v2;
-        if (v3) { if (const char *e = diag_env("CSDR_V3_RUNS")) nruns = (uint32_t)atol(e); }
-        if (nruns > A.nb / 8) nruns = A.nb / 8;
-        if (nruns < 1) nruns = 1;
-        RA.nruns = nruns;
-        // k_run256v2: the older of a CU's two workgroups wins the issue arbitration and runs ~1.4x faster than the younger
-        // one, so it gets the larger share of the tiles (measured: both end together at about 1.2 : 0.8); rotating the
-        // priority per tile instead was no better
-        static const float v2_weight_cf[8] = {1.2f, 0.8f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f};
-        static const float v2_weight_fm[8] = {1.24f, 0.76f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f};      // with whole-line stores the younger workgroup loses more (r03 trace: 4.8 vs 7.6 us per tile)
-        // whole-band FM (one tile buffer, three workgroups per CU): shares of the oldest, the middle and the youngest workgroup of a CU
-        // (make_split turns the shares into whole tile pairs per run, the same on every CU: 16 + 10 + 6 pairs at the bench size.  Measured on exact
-        // triples, profiles/r08_run_split_ab.txt: (16, 10, 6) ahead of (15, 10, 7), (17, 9, 6), (16, 9, 7), (15, 11, 6), (17, 10, 5), (16, 11, 5), (14, 11, 7), (14, 12, 6))
-        static const float v2_weight_fm3[8] = {1.6f, 1.f, 0.6f, 1.f, 1.f, 1.f, 1.f, 1.f};
-        const float *v2_weight = c.fm ? ((cus && nruns == 3 * cus) ? v2_weight_fm3 : v2_weight_fm) : v2_weight_cf;
-        static const float equal_weight[8] = {1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f};
-        static const bool pd_equal = diag_env("CSDR_PD_EQUAL") != nullptr;
-        RA.split = make_split(A.nb, nruns, cus, (call.indep && pd_equal) ? equal_weight : ((v2 && !diag_env("CSDR_RUN_WEIGHTS")) ? v2_weight : slot_weight),
-                              have_pairs ? slot_pairs : nullptr);
-        { const char *e = diag_env("CSDR_PRIO_ROT"); RA.prio_div = e ? (atoi(e) ? cus : 0u) : (v2 ? 0u : cus); }
-        { const char *e = diag_env("CSDR_TRACE"); RA.trace_light = (e && atoi(e) == 2) ? 1u : 0u; }
-        { const char *e = diag_env("CSDR_WU"); RA.wu = e ? (uint32_t)atoi(e) : (uint32_t)WU; }       // experiments: fewer tiles = wrong DC state at run starts
-        { const char *e = diag_env("CSDR_WU_ROT"); RA.wu_rot = e ? (uint32_t)atoi(e) : 0u; }      // measured: no effect on the run-start burst
-        RA.pair_align = (v2 && (c.fm || diag_env("CSDR_PAIR_ALIGN_CF"))) ? 1u : 0u;
-        { const char *e = diag_env("CSDR_WU_BATCH6"); RA.wu_batch6 = e ? (uint32_t)atoi(e) : 1u; }
-        RA.l2beta = c.dc_block ? (float)std::log2((double)c.dc.beta) : -1000.0f;
-        RA.tile_step = call.tile_major ? c.C * 128u : (uint32_t)NB * (c.fm ? 4u : 8u);
-        const bool whole = nf == nb_full * NB;
-        RA.indep = call.indep ? 1u : 0u;     // (process() has checked can_overlap)
-        // whole band, dependent launches: no warm-up windows (the DC state a run misses at its start is put back, where it still matters 16 frames
-        // later -- the four channels around DC -- by k_run256_dcfix behind the launch); runs of >= 8 tiles, <= 2048 of them
-        RA.nowu = (nowu && !shard && !v3 && !RA.indep && nruns >= 2 && nruns <= 2048) ? 1u : 0u;
-        RA.cpre = d_cpre; RA.side = d_side;
-        RA.prev_tail = d_tail[tail_w];
-        if (save_tails && !shard && v2 && whole && nb_full >= WU + 1) {
-            // this chunk's last WU + 1 tiles, for run 0 of the next call (queued in front of the launch: the copy only reads the input)
-            const int nxt = (tail_w + 1) % 3;
-            static const bool nocopy = diag_env("CSDR_PD_NOCOPY") != nullptr;      // scheduling experiments only (wrong run-0 starts)
-            if (!nocopy) hipLaunchKernelGGL(k_save_tail, dim3(2048 * (WU + 1) / 256), dim3(256), 0, s,
-                                            reinterpret_cast<const float4 *>(call.d_in + (size_t)(nb_full - (WU + 1)) * 4096), d_tail[nxt]);
-            if (call.ev_tail) CSDR_HIP(hipEventRecord(call.ev_tail, s));
-            tail_w = nxt; tail_valid = true;
-        } else tail_valid = false;
-        if (timer && (r = timer->begin(s))) return r;
-        if (nb_full == 0) { /* shard, fewer than 16 frames: the tile kernel below does the whole call */ }
-#ifdef CSDR_WITH_RUN256_V3
-        else if (v3) { if ((r = run256_v3_launch(&RA, c.fm, nruns, s))) return r; }
-#endif
-        else if ((r = run256_v2_launch(&RA, c.fm, c.G, nruns, s))) return r;
-        if (RA.nowu && nb_full && (r = run256_dcfix_launch(&RA, c.fm, nruns, d_rt, s))) return r;
-        if (timer && (r = timer->end(s))) return r;             // the bracket covers k_run256_dcfix: it is part of every no-warm-up step
-        const uint32_t rem = nf - nb_full * NB;
-        if (rem) {
-            if (nb_full) cur ^= 1;                            // the tail starts from the run kernel's state
-            TileArgs T = proto;
-            T.x = call.d_in + (size_t)nb_full * NB * c.M; T.out = A.out;
-            if (shard) { T.c0 = 0; T.C = c.M; T.out = d_shard_tail; }   // whole band into [256][rem], the owned rows are gathered below
-            T.yhist_in = d_yhist[cur]; T.yhist_out = d_yhist[cur ^ 1];
-            T.vend_in = d_vend[cur];   T.vend_out = d_vend[cur ^ 1];
-            T.rp_in = d_rp[cur];       T.rp_out = d_rp[cur ^ 1];
-            if (++epoch == 0) epoch = 1;
-            T.epoch = epoch; T.nf = rem; T.nb = 1; T.out_stride = nf; T.out_t0 = nb_full * NB;
-            if (shard) { T.out_stride = rem; T.out_t0 = 0; }
-            T.parity0 = (uint32_t)((frames_done + nb_full * NB) & 1);
-            CSDR_HIP(hipMemsetAsync(d_ticket, 0, sizeof(unsigned), s));
-            if (c.fm) hipLaunchKernelGGL(k_tile256<true>, dim3(1), dim3(256), 0, s, T);
-            else hipLaunchKernelGGL(k_tile256<false>, dim3(1), dim3(256), 0, s, T);
-            if (shard) hipLaunchKernelGGL(k_shard_gather, dim3(c.C), dim3(64), 0, s, (const float *)d_shard_tail, (float *)A.out, c.c0, c.G, rem,
-                                          nf, nb_full * NB, c.fm ? 1u : 2u);
-        }
+        if ((r = run_kernel(call, A, s, timer))) return r;
+        if (rem && (r = ragged_end(call, out, nb_full, rem, s))) return r;
     } else {
         kernel = c.fm ? "k_tile256<FM>" : "k_tile256<CF32>";
         tail_valid = false;
-        if (++epoch == 0) epoch = 1;
-        A.epoch = epoch; A.nf = nf; A.nb = (nf + NB - 1) / NB;
-        CSDR_HIP(hipMemsetAsync(d_ticket, 0, sizeof(unsigned), s));
-        if (timer && (r = timer->begin(s))) return r;
-        if (c.fm) hipLaunchKernelGGL(k_tile256<true>, dim3(A.nb), dim3(256), 0, s, A);
-        else hipLaunchKernelGGL(k_tile256<false>, dim3(A.nb), dim3(256), 0, s, A);
-        if (timer && (r = timer->end(s))) return r;
+        A.nf = nf; A.nb = (nf + NB - 1) / NB;
+        if ((r = tile_kernel(A, s, timer))) return r;
     }
     CSDR_HIP(hipGetLastError());
     return 0;
 }
+
+// The whole tiles of a call (A.nb of them; none: a shard's call of fewer than 16 frames, which ragged_end does alone) through k_run256v2
+int FusedPlan::run_kernel(const FusedCall &call, const TileArgs &A, hipStream_t s, KernelTimer *timer)
+{
+    const FusedConfig &c = cfg;
+    const bool shard = c.G > 1;
+    int r;
+    kernel = c.fm ? "k_run256v2<FM>" : "k_run256v2<CF32>";
+    if (shard) kernel += "/G" + std::to_string(c.G);
+    RunArgs RA = run_proto;
+    RA.t = A;
+    // one run per resident workgroup slot (a single round), runs balanced to within one tile,
+    // at least 8 tiles per run so that the warm-up reads stay below 7/8 of a run
+    uint32_t nruns = resident_wgs_v2;
+    if (nruns > A.nb / 8) nruns = A.nb / 8;
+    if (nruns < 1) nruns = 1;
+    RA.nruns = nruns;
+    const float *v2_weight = c.fm ? ((cus && nruns == 3 * cus) ? V2_WEIGHT_FM3 : V2_WEIGHT_FM) : V2_WEIGHT_CF;
+    RA.split = make_split(A.nb, nruns, cus, (call.indep && pd_equal) ? EQUAL_WEIGHT : (have_weights ? slot_weight : v2_weight),
+                          have_pairs ? slot_pairs : nullptr);
+    RA.tile_step = call.tile_major ? c.C * 128u : (uint32_t)NB * (c.fm ? 4u : 8u);
+    RA.indep = call.indep ? 1u : 0u;     // (process() has checked can_overlap)
+    // whole band, dependent launches: no warm-up windows (the DC state a run misses at its start is put back, where it still matters 16 frames
+    // later -- the four channels around DC -- by k_run256_dcfix behind the launch); runs of >= 8 tiles, <= 2048 of them
+    RA.nowu = (cold.rt && !shard && !RA.indep && nruns >= 2 && nruns <= 2048) ? 1u : 0u;
+    RA.prev_tail = d_tail[tail_w];
+    if (save_tails && !shard && call.nf == A.nb * NB && A.nb >= WU + 1) {
+        // this chunk's last WU + 1 tiles, for run 0 of the next call (queued in front of the launch: the copy only reads the input)
+        const int nxt = (tail_w + 1) % 3;
+        if (!pd_nocopy) hipLaunchKernelGGL(k_save_tail, dim3(2048 * (WU + 1) / 256), dim3(256), 0, s,
+                                           reinterpret_cast<const float4 *>(call.d_in + (size_t)(A.nb - (WU + 1)) * 4096), d_tail[nxt]);
+        if (call.ev_tail) CSDR_HIP(hipEventRecord(call.ev_tail, s));
+        tail_w = nxt; tail_valid = true;
+    } else tail_valid = false;
+    if (timer && (r = timer->begin(s))) return r;
+    if (A.nb && (r = run256_v2_launch(&RA, c.fm, c.G, nruns, s))) return r;
+    if (RA.nowu && A.nb && (r = run256_dcfix_launch(&RA, c.fm, nruns, cold.rt, s))) return r;
+    if (timer && (r = timer->end(s))) return r;             // the bracket covers k_run256_dcfix: it is part of every no-warm-up step
+    return 0;
+}
+
+// One k_tile256 launch of T.nb tiles: a new epoch for the look-back tags, the ticket counter back to zero
+int FusedPlan::tile_kernel(TileArgs &T, hipStream_t s, KernelTimer *timer)
+{
+    int r;
+    if (++epoch == 0) epoch = 1;
+    T.epoch = epoch;
+    CSDR_HIP(hipMemsetAsync(d_ticket, 0, sizeof(unsigned), s));
+    if (timer && (r = timer->begin(s))) return r;
+    if (cfg.fm) hipLaunchKernelGGL(k_tile256<true>, dim3(T.nb), dim3(256), 0, s, T);
+    else hipLaunchKernelGGL(k_tile256<false>, dim3(T.nb), dim3(256), 0, s, T);
+    if (timer && (r = timer->end(s))) return r;
+    return 0;
+}
+
+// The rem < 16 frames behind a run-kernel call's nb_full whole tiles: one tile of k_tile256 on the state the run kernel leaves behind
+int FusedPlan::ragged_end(const FusedCall &call, void *out, uint32_t nb_full, uint32_t rem, hipStream_t s)
+{
+    const FusedConfig &c = cfg;
+    const bool shard = c.G > 1;
+    int r;
+    if (nb_full) cur ^= 1;                            // the tail starts from the run kernel's state
+    TileArgs T = proto;
+    T.x = call.d_in + (size_t)nb_full * NB * c.M; T.out = out;
+    wire_state(T);
+    T.nf = rem; T.nb = 1; T.out_stride = call.nf; T.out_t0 = nb_full * NB;
+    if (shard) { T.c0 = 0; T.C = c.M; T.out = d_shard_tail; T.out_stride = rem; T.out_t0 = 0; }   // whole band into [256][rem], the owned rows are gathered below
+    T.parity0 = (uint32_t)((frames_done + nb_full * NB) & 1);
+    if ((r = tile_kernel(T, s, nullptr))) return r;
+    if (shard) hipLaunchKernelGGL(k_shard_gather, dim3(c.C), dim3(64), 0, s, (const float *)d_shard_tail, (float *)out, c.c0, c.G, rem,
+                                  call.nf, nb_full * NB, c.fm ? 1u : 2u);
+    return 0;
+}
+
 
 int FusedPlan::trace(unsigned long long *out, uint32_t ntiles)
 {

@@ -341,9 +341,11 @@ struct SmallPlan : ChainPlan {
     bool v2_ok = false, v2_last = false;     // k_run64v2 usable (CF32, whole band); used by the last call
     float *d_taps = nullptr;
     float2 *d_tw = nullptr, *d_wpre = nullptr;
-    float2 *d_yhist[2] = {nullptr, nullptr}, *d_vend[2] = {nullptr, nullptr}, *d_rp[2] = {nullptr, nullptr};
+    StreamState st;
     float2 *d_yfirst = nullptr, *d_ylast = nullptr;
-    float2 *d_cpre = nullptr, *d_rt = nullptr;      // k_run64v2 without warm-up windows (Run64v2Host::cpre / rt)
+    ColdStart cold;                          // k_run64v2 without warm-up windows (Run64v2Host::cpre / rt)
+    bool v2_all = false;                     // CSDR_RUN64_V2_ALL: k_run64v2 below its size threshold too
+    double v2_weight = 1.1;                  // CSDR_RUN64_WEIGHT (Run64v2Host::weight)
     TileArgs proto;
 
     int init();
@@ -351,9 +353,9 @@ struct SmallPlan : ChainPlan {
     // the call goes to k_run64v2 as whole 64-frame tiles, no mix inside the plan
     bool tile_major_ok(uint32_t nf) const override
     {
-        return v2_ok && !cfg.mix && !cfg.fm && (uint64_t)cfg.C * nf * 8u < (1ull << 32) && run64_v2_runs(nf, cus) != 0;
+        return v2_ok && !cfg.mix && !cfg.fm && (uint64_t)cfg.C * nf * 8u < (1ull << 32) && run64_v2_runs(nf, cus, v2_all) != 0;
     }
-    int reset_state(hipStream_t s) override;
+    int reset_state(hipStream_t s) override { return st.reset(s); }
     int run(const FusedCall &call, void *out, hipStream_t s, KernelTimer *timer) override;
 };
 
@@ -367,11 +369,7 @@ int SmallPlan::init()
     if ((r = mem.alloc(&d_taps, sizeof(float) * cfg.M * cfg.p))) return r;
     if ((r = mem.alloc(&d_tw, sizeof(float2) * 16 * R2))) return r;
     if ((r = mem.alloc(&d_wpre, sizeof(float2) * 2 * cfg.M))) return r;
-    for (int i = 0; i < 2; i++) {
-        if ((r = mem.alloc(&d_yhist[i], sizeof(float2) * 13 * cfg.M))) return r;
-        if ((r = mem.alloc(&d_vend[i], sizeof(float2)))) return r;
-        if ((r = mem.alloc(&d_rp[i], sizeof(float2) * cfg.C))) return r;
-    }
+    if ((r = st.alloc(mem, 13 * cfg.M, cfg.C))) return r;
     if ((r = mem.alloc(&d_yfirst, sizeof(float2) * (size_t)cfg.M * (max_nb + 2)))) return r;
     if ((r = mem.alloc(&d_ylast, sizeof(float2) * (size_t)cfg.M * (max_nb + 2)))) return r;
     if (cfg.mix && (r = mem.alloc(&d_premix, (size_t)cfg.C * cfg.max_nf * (cfg.fm ? 4 : 8)))) return r;
@@ -389,37 +387,18 @@ int SmallPlan::init()
     A = TileArgs{};
     A.taps = d_taps; A.tw = d_tw; A.wpre = d_wpre;
     A.c0 = cfg.c0; A.C = cfg.C; A.fm_ref = cfg.fm_ref;
-    const double beta = cfg.dc_block ? (double)cfg.dc.beta : 0.0;
-    A.alpha = cfg.dc_block ? (float)(1.0 - beta) : 0.0f;
-    A.beta = (float)beta;
-    for (int k = 0; k < 16; k++) A.b16[k] = (float)std::pow(beta, 16.0 * k);
-    for (int k = 0; k < 17; k++) A.b256[k] = (float)std::pow(beta, 256.0 * k);
-    for (int k = 0; k < 16; k++) A.bj[k] = (float)std::pow(beta, (double)k);
+    dcc.put(A);
     int occ = 3;
     if (cfg.fm) (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_run64<true>, 256, 0);
     else (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_run64<false>, 256, 0);
     if (occ < 1) occ = 1;
     resident_wgs = cus * (uint32_t)occ;
     v2_ok = !cfg.fm && cfg.c0 == 0 && cfg.C == (uint32_t)MS && !diag_env("CSDR_RUN64_V1");
-    if (v2_ok && cfg.dc_block && dc_window_ok(cfg.dc, RUN64_DCFIX_F * 64.0) && !(diag_env("CSDR_NOWU") && atoi(diag_env("CSDR_NOWU")) == 0)) {
-        // k_run64v2 without warm-up windows: the state hand-over array and the chain's response to a unit DC state at the channels 30..33,
-        // frames 64 .. 64 + RUN64_DCFIX_F - 1 behind a halo tile's start (= the run's first output frames)
-        if ((r = mem.alloc(&d_cpre, sizeof(float2) * 1026)) || (r = mem.alloc(&d_rt, sizeof(float2) * 2 * RUN64_DCFIX_F * 4))) return r;
-        CSDR_HIP(hipMemset(d_cpre, 0, sizeof(float2) * 1026));
-        std::vector<float2> rt((size_t)2 * RUN64_DCFIX_F * 4);
-        dc_state_response(cfg, wpre.data(), 64u, (uint32_t)RUN64_DCFIX_F, 30u, rt.data());
-        CSDR_HIP(hipMemcpy(d_rt, rt.data(), sizeof(float2) * rt.size(), hipMemcpyHostToDevice));
-    }
-    return 0;
-}
-
-int SmallPlan::reset_state(hipStream_t s)
-{
-    for (int i = 0; i < 2; i++) {
-        CSDR_HIP(hipMemsetAsync(d_yhist[i], 0, sizeof(float2) * 13 * cfg.M, s));
-        CSDR_HIP(hipMemsetAsync(d_vend[i], 0, sizeof(float2), s));
-        CSDR_HIP(hipMemsetAsync(d_rp[i], 0, sizeof(float2) * cfg.C, s));
-    }
+    v2_all = diag_env("CSDR_RUN64_V2_ALL") != nullptr;
+    if (const char *e = diag_env("CSDR_RUN64_WEIGHT")) v2_weight = atof(e);
+    // k_run64v2 without warm-up windows: the state hand-over array and the chain's response to a unit DC state at the channels 30..33,
+    // frames 64 .. 64 + RUN64_DCFIX_F - 1 behind a halo tile's start (= the run's first output frames)
+    if (v2_ok && (r = cold.init(mem, cfg, RUN64_DCFIX_F * 64.0, 1026, 0, false, 64u, (uint32_t)RUN64_DCFIX_F, 30, wpre.data()))) return r;
     return 0;
 }
 
@@ -428,18 +407,18 @@ int SmallPlan::run(const FusedCall &call, void *out, hipStream_t s, KernelTimer 
     const FusedConfig &c = cfg;
     const uint32_t nf = call.nf;
     int r;
-    const uint32_t v2runs = (v2_ok && (uint64_t)c.C * nf * 8u < (1ull << 32)) ? run64_v2_runs(nf, cus) : 0;
+    const uint32_t v2runs = (v2_ok && (uint64_t)c.C * nf * 8u < (1ull << 32)) ? run64_v2_runs(nf, cus, v2_all) : 0;
     v2_last = v2runs != 0;
     if (v2runs) {
         Run64v2Host H{};
         H.x = call.d_in; H.out = (float2 *)out;
         H.taps = d_taps; H.tw = d_tw; H.wpre = d_wpre;
-        H.uhist_in = d_yhist[cur]; H.uhist_out = d_yhist[cur ^ 1];
-        H.vend_in = d_vend[cur]; H.vend_out = d_vend[cur ^ 1];
+        H.uhist_in = st.hist_in(cur); H.uhist_out = st.hist_out(cur);
+        H.vend_in = st.vend_in(cur); H.vend_out = st.vend_out(cur);
         H.nf = nf; H.nruns = v2runs; H.parity0 = (uint32_t)(frames_done & 1);
         H.tile_major = call.tile_major;
-        H.cpre = v2runs <= 1024u ? d_cpre : nullptr; H.rt = d_rt;
-        H.dc_block = c.dc_block; H.beta = c.dc_block ? (double)c.dc.beta : 0.0;
+        H.cpre = v2runs <= 1024u ? cold.cpre : nullptr; H.rt = cold.rt;
+        H.dc = &dcc; H.weight = v2_weight;
         return run64_v2_launch(H, s, timer);
     }
     SmallArgs SA{};
@@ -447,9 +426,9 @@ int SmallPlan::run(const FusedCall &call, void *out, hipStream_t s, KernelTimer 
     A = proto;
     A.x = call.d_in;
     A.out = out;
-    A.yhist_in = d_yhist[cur]; A.yhist_out = d_yhist[cur ^ 1];
-    A.vend_in = d_vend[cur];   A.vend_out = d_vend[cur ^ 1];
-    A.rp_in = d_rp[cur];       A.rp_out = d_rp[cur ^ 1];
+    A.yhist_in = st.hist_in(cur); A.yhist_out = st.hist_out(cur);
+    A.vend_in = st.vend_in(cur);  A.vend_out = st.vend_out(cur);
+    A.rp_in = st.rp_in(cur);      A.rp_out = st.rp_out(cur);
     A.nf = nf; A.nb = (nf + TS - 1) / TS; A.out_stride = nf; A.out_t0 = 0;
     A.parity0 = (uint32_t)(frames_done & 1);
     SA.yfirst = d_yfirst; SA.ylast_run = d_ylast;
@@ -457,7 +436,7 @@ int SmallPlan::run(const FusedCall &call, void *out, hipStream_t s, KernelTimer 
     SA.S = (A.nb + resident_wgs - 1) / resident_wgs;
     if (SA.S < 8) SA.S = A.nb >= 8 * 64 ? 8 : (A.nb + 63) / 64;
     if (SA.S < 1) SA.S = 1;
-    SA.l2beta = c.dc_block ? (float)std::log2((double)c.dc.beta) : -1000.0f;
+    SA.l2beta = dcc.l2beta;
     const uint32_t nruns = (A.nb + SA.S - 1) / SA.S;
     if (timer && (r = timer->begin(s))) return r;
     if (c.fm) hipLaunchKernelGGL(k_run64<true>, dim3(nruns), dim3(256), 0, s, SA);

@@ -462,10 +462,14 @@ struct BigPlan : ChainPlan {
     bool s1_ok = false, s1_last = false;      // k_shard1024<.., G> usable (interleaved shard, G = 4, 8); used by the last call
     int s1_mfix = -1;                         // the shard's row among the four channels around DC (k_shard1024_dcfix), -1: none
     float2 *d_tw = nullptr, *d_wpre = nullptr;
-    float2 *d_uhist[2] = {nullptr, nullptr}, *d_vend[2] = {nullptr, nullptr}, *d_rp[2] = {nullptr, nullptr};
+    StreamState st;
     float2 *d_scratch = nullptr;     // yfirst | ylast
     void *d_full = nullptr;          // interleaved shard, calls k_run1024v2 does not take: whole-band result [1024][max_nf] (allocated on first use)
-    float2 *d_cpre = nullptr, *d_side = nullptr, *d_rt = nullptr;       // k_run1024v3 without warm-up windows (Run1024v2Host::cpre / side / rt)
+    ColdStart cold;                  // k_run1024v3 / k_shard1024 without warm-up windows (Run1024v2Host::cpre / side / rt)
+    uint32_t runs_v2 = 0, runs_v3 = 0, runs_s1 = 0;    // CSDR_RUN1024_RUNS, CSDR_RUN1024_V3_RUNS, CSDR_SHARD1024_RUNS (max_runs of the *_runs of fused.h)
+    double v2_weight = 1.2;          // CSDR_RUN1024_WEIGHT (Run1024v2Host::weight)
+    unsigned long long *d_trace = nullptr; std::string trace_file;      // CSDR_RUN1024_V3_TRACE / CSDR_SHARD1024_TRACE (Run1024v2Host::trace)
+    Pfb1024Args proto;               // what init() fixes of a k_pfb1024 launch
 
     int init();
     const char *name() const override
@@ -478,10 +482,10 @@ struct BigPlan : ChainPlan {
     // CF32 output through k_run1024v3<CF32> (whole band) or k_shard1024<CF32, G> (interleaved shard)
     bool tile_major_ok(uint32_t nf) const override
     {
-        if (s1_ok) return !cfg.fm && !cfg.mix && nf % 16u == 0 && shard1024_runs(nf, false, cfg.G, cus) != 0;
-        return v3_ok && !cfg.fm && !cfg.mix && nf % 16u == 0 && (uint64_t)nf * 8192u < (1ull << 31) && run1024_v3_runs(nf, false, cus) != 0;
+        if (s1_ok) return !cfg.fm && !cfg.mix && nf % 16u == 0 && shard1024_runs(nf, false, cfg.G, cus, runs_s1) != 0;
+        return v3_ok && !cfg.fm && !cfg.mix && nf % 16u == 0 && (uint64_t)nf * 8192u < (1ull << 31) && run1024_v3_runs(nf, false, cus, runs_v3) != 0;
     }
-    int reset_state(hipStream_t s) override;
+    int reset_state(hipStream_t s) override { return st.reset(s); }
     int run(const FusedCall &call, void *out, hipStream_t s, KernelTimer *timer) override;
 };
 
@@ -496,11 +500,7 @@ int BigPlan::init()
     if ((rc = mem.alloc(&d_taps_q, sizeof(float) * PM * 18))) return rc;
     if ((rc = mem.alloc(&d_tw, sizeof(float2) * PM))) return rc;
     if ((rc = mem.alloc(&d_wpre, sizeof(float2) * 2 * PM))) return rc;
-    for (int i = 0; i < 2; i++) {
-        if ((rc = mem.alloc(&d_uhist[i], sizeof(float2) * 13 * PM))) return rc;
-        if ((rc = mem.alloc(&d_vend[i], sizeof(float2)))) return rc;
-        if ((rc = mem.alloc(&d_rp[i], sizeof(float2) * (cfg.G > 1 ? (uint32_t)PM : cfg.C)))) return rc;     // interleaved shard: indexed by the primed channel k'
-    }
+    if ((rc = st.alloc(mem, 13 * PM, cfg.G > 1 ? (uint32_t)PM : cfg.C))) return rc;     // interleaved shard: rp indexed by the primed channel k'
     if ((rc = mem.alloc(&d_scratch, sizeof(float2) * 2 * (size_t)cus * PM))) return rc;
     if (cfg.mix && (rc = mem.alloc(&d_premix, (size_t)cfg.C * cfg.max_nf * (cfg.fm ? 4 : 8)))) return rc;
     CSDR_HIP(hipMemcpy(d_taps, cfg.taps, sizeof(float) * PM * PP, hipMemcpyHostToDevice));
@@ -540,58 +540,54 @@ int BigPlan::init()
             tq[(size_t)PM * 16 + 2 * (size_t)r] = wpre[PM + r].x; tq[(size_t)PM * 16 + 2 * (size_t)r + 1] = wpre[PM + r].y;
         }
         CSDR_HIP(hipMemcpy(d_taps_q, tq.data(), sizeof(float) * tq.size(), hipMemcpyHostToDevice));
-        // k_run1024v2: the interleaved shards only (FM output); its whole-band instantiations are no longer built -- k_run1024v3 takes every
-        // whole-band call of whole 4-frame tiles (a call that ends inside a 128-byte line stores the front part of it)
-        v2_ok = false;
-        // whole band, calls of whole 4-frame tiles: k_run1024v3 (CSDR_RUN1024_V3=0: k_run1024 for the comparison)
-        v3_ok = cfg.c0 == 0 && cfg.C == (uint32_t)PM && cfg.G == 1 && !diag_env("CSDR_RUN1024_V1") && !(diag_env("CSDR_RUN1024_V3") && atoi(diag_env("CSDR_RUN1024_V3")) == 0);
-        if (cfg.G > 1) v2_ok = cfg.fm && !diag_env("CSDR_RUN1024_V1");       // k_run1024v2<FM, G>; CF32 shards: whole band + row gather (below)
+        // whole band, calls of whole 4-frame tiles: k_run1024v3 (CSDR_RUN1024_V3=0: k_run1024 for the comparison); a call that ends inside
+        // a 128-byte line stores the front part of it
+        const bool v1 = diag_env("CSDR_RUN1024_V1") != nullptr;
+        const char *e3 = diag_env("CSDR_RUN1024_V3");
+        v3_ok = cfg.c0 == 0 && cfg.C == (uint32_t)PM && cfg.G == 1 && !v1 && !(e3 && atoi(e3) == 0);
+        // k_run1024v2: the interleaved shards only (FM output; its whole-band instantiations are no longer built); CF32 shards: whole band + row gather (below)
+        v2_ok = cfg.G > 1 && cfg.fm && !v1;
+        // k_shard1024<FM | CF32, G>: every run-sized call of whole tiles (CSDR_NO_SHARD1024: k_run1024v2<FM, G> or whole band + gather instead)
+        s1_ok = (cfg.G == 4 || cfg.G == 8) && !v1 && !diag_env("CSDR_NO_SHARD1024");
+        if (const char *e = diag_env("CSDR_RUN1024_RUNS")) runs_v2 = (uint32_t)atoi(e);
+        if (const char *e = diag_env("CSDR_RUN1024_V3_RUNS")) runs_v3 = (uint32_t)atoi(e);
+        if (const char *e = diag_env("CSDR_SHARD1024_RUNS")) runs_s1 = (uint32_t)atoi(e);
+        if (const char *e = diag_env("CSDR_RUN1024_WEIGHT")) v2_weight = atof(e);
         // until the first call: the kernel a call of max_nf frames would take (csdr_chain_path names it)
-        s1_ok = (cfg.G == 4 || cfg.G == 8) && !diag_env("CSDR_RUN1024_V1");      // k_shard1024<FM | CF32, G>: every run-sized call of whole tiles
-        s1_last = s1_ok && shard1024_runs(cfg.max_nf, cfg.fm, cfg.G, cus) != 0;
-        v2_last = !s1_last && v2_ok && (cfg.max_nf & 3u) == 0 && run1024_v2_runs(cfg.max_nf, cus) != 0;
-        v3_last = v3_ok && run1024_v3_runs(cfg.max_nf, cfg.fm, cus) != 0;
+        s1_last = s1_ok && shard1024_runs(cfg.max_nf, cfg.fm, cfg.G, cus, runs_s1) != 0;
+        v2_last = !s1_last && v2_ok && (cfg.max_nf & 3u) == 0 && run1024_v2_runs(cfg.max_nf, cus, runs_v2) != 0;
+        v3_last = v3_ok && run1024_v3_runs(cfg.max_nf, cfg.fm, cus, runs_v3) != 0;
         if (v3_last) v2_last = false;
+        // debug builds (-DB3_TRACE / -DS1_TRACE): the stamp buffer of the plan's run kernel and the file its launcher writes
+        if (const char *e = v3_ok ? diag_env("CSDR_RUN1024_V3_TRACE") : s1_ok ? diag_env("CSDR_SHARD1024_TRACE") : nullptr) {
+            trace_file = e;
+            if ((rc = mem.alloc_n(&d_trace, v3_ok ? RUN1024_V3_TRACE_N : SHARD1024_TRACE_N))) return rc;
+        }
     }
     if (s1_ok) {
         // k_shard1024 without warm-up windows (as k_run1024v3 below): the state hand-over between the runs, the side copies of the ONE owned channel
         // among the four around DC (510 .. 513; primed k' = k - g, row k' / G -- none for the shards 2 .. 5 of 8), and the chain's response to a
-        // unit DC state there (computed on the plan's phasor table, which carries the shard's shift: the primed spectrum)
+        // unit DC state there (computed on the plan's phasor table, which carries the shard's shift: the primed spectrum; channel 0 of the
+        // four is the owned one).  Window: error beta^(12 x 4096)
         s1_mfix = -1;
         uint32_t kp = 0;
         for (uint32_t k = 510; k <= 513; k++) if ((k + (uint32_t)PM - cfg.c0) % cfg.G == 0) { kp = (k + (uint32_t)PM - cfg.c0) % (uint32_t)PM; s1_mfix = (int)(kp / cfg.G); }
-        if ((rc = mem.alloc(&d_cpre, sizeof(float2) * (cus + 2))) || (rc = mem.alloc(&d_side, sizeof(float2) * (size_t)(cus + 1) * RUN1024_DCFIX_F))) return rc;
-        CSDR_HIP(hipMemset(d_cpre, 0, sizeof(float2) * (cus + 2)));
-        if (cfg.dc_block && dc_window_ok(cfg.dc, 12 * 4096.0) && !(diag_env("CSDR_NOWU") && atoi(diag_env("CSDR_NOWU")) == 0)) {   // error beta^(12 x 4096)
-            if ((rc = mem.alloc(&d_rt, sizeof(float2) * 2 * RUN1024_DCFIX_F * 4))) return rc;
-            std::vector<float2> rt((size_t)2 * RUN1024_DCFIX_F * 4, make_float2(0.f, 0.f));
-            if (s1_mfix >= 0) dc_state_response(cfg, wpre.data(), 15u, (uint32_t)RUN1024_DCFIX_F, kp, rt.data());      // (channel 0 of the four is the owned one)
-            CSDR_HIP(hipMemcpy(d_rt, rt.data(), sizeof(float2) * rt.size(), hipMemcpyHostToDevice));
-        }
+        if ((rc = cold.init(mem, cfg, 12 * 4096.0, cus + 2, (size_t)(cus + 1) * RUN1024_DCFIX_F, true, 15u, (uint32_t)RUN1024_DCFIX_F,
+                            s1_mfix >= 0 ? (int)kp : -1, wpre.data()))) return rc;
     }
-    if (v3_ok) {
-        // k_run1024v3's state hand-over and the side copies of the four channels around DC (510..513): the kernel always writes them (a few
-        // hundred bytes per run); launches without warm-up windows (dc_block, not CSDR_NOWU=0) also get the chain's response to a unit DC state
-        // at those channels, frames 15 .. 47 behind a cold start (= frame -1 .. 31 of the run)
-        if ((rc = mem.alloc(&d_cpre, sizeof(float2) * (cus + 2))) || (rc = mem.alloc(&d_side, sizeof(float2) * (size_t)(cus + 1) * 4 * RUN1024_DCFIX_F))) return rc;
-        CSDR_HIP(hipMemset(d_cpre, 0, sizeof(float2) * (cus + 2)));
-    }
-    if (v3_ok && cfg.dc_block && dc_window_ok(cfg.dc, 35 * 1024.0) && !(diag_env("CSDR_NOWU") && atoi(diag_env("CSDR_NOWU")) == 0)) {   // halo + 32-frame dcfix
-        if ((rc = mem.alloc(&d_rt, sizeof(float2) * 2 * RUN1024_DCFIX_F * 4))) return rc;
-        std::vector<float2> rt((size_t)2 * RUN1024_DCFIX_F * 4);
-        dc_state_response(cfg, wpre.data(), 15u, (uint32_t)RUN1024_DCFIX_F, 510u, rt.data());
-        CSDR_HIP(hipMemcpy(d_rt, rt.data(), sizeof(float2) * rt.size(), hipMemcpyHostToDevice));
-    }
-    return 0;
-}
-
-int BigPlan::reset_state(hipStream_t s)
-{
-    for (int i = 0; i < 2; i++) {
-        CSDR_HIP(hipMemsetAsync(d_uhist[i], 0, sizeof(float2) * 13 * PM, s));
-        CSDR_HIP(hipMemsetAsync(d_vend[i], 0, sizeof(float2), s));
-        CSDR_HIP(hipMemsetAsync(d_rp[i], 0, sizeof(float2) * (cfg.G > 1 ? (uint32_t)PM : cfg.C), s));
-    }
+    // k_run1024v3's state hand-over and the side copies of the four channels around DC (510..513): the kernel always writes them (a few
+    // hundred bytes per run); launches without warm-up windows (dc_block, not CSDR_NOWU=0) also get the chain's response to a unit DC state
+    // at those channels, frames 15 .. 47 behind a cold start (= frame -1 .. 31 of the run).  Window: halo + 32-frame dcfix
+    if (v3_ok && (rc = cold.init(mem, cfg, 35 * 1024.0, cus + 2, (size_t)(cus + 1) * 4 * RUN1024_DCFIX_F, true, 15u, (uint32_t)RUN1024_DCFIX_F,
+                                 510, wpre.data()))) return rc;
+    // k_run1024 (the calls no run kernel above takes)
+    proto = Pfb1024Args{};
+    proto.taps = d_taps; proto.taps_t = d_taps_t; proto.tw = d_tw; proto.wpre = d_wpre;
+    proto.ref = cfg.fm_ref; proto.pk = phase_consts(cfg.fm_ref);
+    dcc.put(proto);
+    const double beta = cfg.dc_block ? (double)cfg.dc.beta : 0.0;
+    for (int k = 0; k < 4; k++) { proto.bp[k] = (float)std::pow(beta, (double)(1 << k)); proto.dp[k] = (float)std::pow(beta, 16.0 * (1 << k)); }
+    proto.dm = (float)std::pow(beta, 1024.0);
     return 0;
 }
 
@@ -600,32 +596,32 @@ int BigPlan::run(const FusedCall &call, void *out, hipStream_t s, KernelTimer *t
     const FusedConfig &c = cfg;
     const uint32_t nf = call.nf;
     int r;
-    const uint32_t s1runs = s1_ok ? shard1024_runs(nf, c.fm, c.G, cus) : 0;
+    const uint32_t s1runs = s1_ok ? shard1024_runs(nf, c.fm, c.G, cus, runs_s1) : 0;
     s1_last = s1runs != 0;
-    const uint32_t v2runs = (!s1runs && v2_ok && (nf & 3u) == 0 && (uint64_t)nf * 8192u < (1ull << 31)) ? run1024_v2_runs(nf, cus) : 0;
+    const uint32_t v2runs = (!s1runs && v2_ok && (nf & 3u) == 0 && (uint64_t)nf * 8192u < (1ull << 31)) ? run1024_v2_runs(nf, cus, runs_v2) : 0;
     v2_last = v2runs != 0;
-    const uint32_t v3runs = (v3_ok && (uint64_t)nf * 8192u < (1ull << 31)) ? run1024_v3_runs(nf, c.fm, cus) : 0;
+    const uint32_t v3runs = (v3_ok && (uint64_t)nf * 8192u < (1ull << 31)) ? run1024_v3_runs(nf, c.fm, cus, runs_v3) : 0;
     v3_last = v3runs != 0;
     if (v3runs) v2_last = false;
     if (v2runs || v3runs || s1runs) {
         Run1024v2Host H{};
         H.x = call.d_in; H.out = out; H.taps_q = d_taps_q; H.tw = d_tw;
-        H.uhist_in = d_uhist[cur]; H.uhist_out = d_uhist[cur ^ 1];
-        H.vend_in = d_vend[cur]; H.vend_out = d_vend[cur ^ 1];
-        H.rp_in = d_rp[cur]; H.rp_out = d_rp[cur ^ 1];
+        H.uhist_in = st.hist_in(cur); H.uhist_out = st.hist_out(cur);
+        H.vend_in = st.vend_in(cur); H.vend_out = st.vend_out(cur);
+        H.rp_in = st.rp_in(cur); H.rp_out = st.rp_out(cur);
         H.nf = nf; H.nruns = v2runs; H.parity0 = (uint32_t)(frames_done & 1);
         H.G = c.G; H.g = c.G > 1 ? c.c0 : 0u;
         H.tile_major = call.tile_major && (v3runs || s1runs) && !c.fm;
-        H.dc_block = c.dc_block; H.beta = c.dc_block ? (double)c.dc.beta : 0.0; H.fm_ref = c.fm_ref;
-        if (v3runs) { H.cpre = d_cpre; H.side = d_side; H.rt = v3runs <= cus ? d_rt : nullptr; }
-        if (s1runs) { H.cpre = d_cpre; H.side = d_side; H.rt = d_rt; H.mfix = s1_mfix; }
+        H.dc = &dcc; H.fm_ref = c.fm_ref; H.weight = v2_weight;
+        if (d_trace) { H.trace = d_trace; H.trace_file = trace_file.c_str(); }
+        if (v3runs) { H.cpre = cold.cpre; H.side = cold.side; H.rt = v3runs <= cus ? cold.rt : nullptr; }
+        if (s1runs) { H.cpre = cold.cpre; H.side = cold.side; H.rt = cold.rt; H.mfix = s1_mfix; }
         if (s1runs) return shard1024_launch(H, c.fm, s1runs, s, timer);
         if (v3runs) return run1024_v3_launch(H, c.fm, v3runs, s, timer);
         return run1024_v2_launch(H, c.fm, s, timer);
     }
-    Pfb1024Args A{};
-    A.u = call.d_in; A.taps = d_taps; A.taps_t = d_taps_t; A.tw = d_tw; A.wpre = d_wpre;
-    A.out = out;
+    Pfb1024Args A = proto;
+    A.u = call.d_in; A.out = out;
     const bool shard = c.G > 1;
     if (shard) {
         // an interleaved shard's call that k_run1024v2<FM, G> does not take (CF32 output, ragged or short call): the whole primed
@@ -633,17 +629,11 @@ int BigPlan::run(const FusedCall &call, void *out, hipStream_t s, KernelTimer *t
         if (!d_full && (r = mem.alloc(&d_full, (size_t)PM * c.max_nf * (c.fm ? 4 : 8)))) return r;
         A.out = d_full;
     }
-    A.rp_in = d_rp[cur]; A.rp_out = d_rp[cur ^ 1];
-    A.vend_in = d_vend[cur]; A.vend_out = d_vend[cur ^ 1];
-    A.uhist_in = d_uhist[cur]; A.uhist_out = d_uhist[cur ^ 1];
-    A.nf = nf; A.nb = (nf + PT - 1) / PT; A.c0 = shard ? 0u : c.c0; A.C = shard ? (uint32_t)PM : c.C; A.ref = c.fm_ref;
+    A.rp_in = st.rp_in(cur); A.rp_out = st.rp_out(cur);
+    A.vend_in = st.vend_in(cur); A.vend_out = st.vend_out(cur);
+    A.uhist_in = st.hist_in(cur); A.uhist_out = st.hist_out(cur);
+    A.nf = nf; A.nb = (nf + PT - 1) / PT; A.c0 = shard ? 0u : c.c0; A.C = shard ? (uint32_t)PM : c.C;
     A.parity0 = (uint32_t)(frames_done & 1);
-    const double beta = c.dc_block ? (double)c.dc.beta : 0.0;
-    A.alpha = c.dc_block ? (float)(1.0 - beta) : 0.0f;
-    A.l2beta = c.dc_block ? (float)std::log2(beta) : -1000.0f;
-    for (int k = 0; k < 4; k++) { A.bp[k] = (float)std::pow(beta, (double)(1 << k)); A.dp[k] = (float)std::pow(beta, 16.0 * (1 << k)); }
-    A.dm = (float)std::pow(beta, 1024.0);
-    A.pk = phase_consts(c.fm_ref);
     // one run per CU, at least 8 tiles per run (a run >= 1 spends 3 read-only + 2 halo tiles on its start state)
     uint32_t nruns = cus;
     if (nruns > A.nb / 8) nruns = A.nb / 8;

@@ -415,6 +415,7 @@ struct HugePlan : ChainPlan {
     float2 *d_wpre = nullptr, *d_tw4 = nullptr, *d_tw = nullptr, *d_z = nullptr;
     float4 *d_tail[2] = {nullptr, nullptr};
     float *d_part = nullptr;
+    uint32_t runs_knob = 0;          // CSDR_RUN4096_RUNS: the run count before huge_runs shortens it (0: cus / 4)
     std::string kernel;
 
     int init();
@@ -454,15 +455,15 @@ int HugePlan::init()
     CSDR_HIP(hipMemcpy(d_tw4, tw4.data(), sizeof(float2) * tw4.size(), hipMemcpyHostToDevice));
     CSDR_HIP(hipMemcpy(d_tw, tw.data(), sizeof(float2) * tw.size(), hipMemcpyHostToDevice));
     CSDR_HIP(hipMemset(d_tail[0], 0, sizeof(float4) * 2048 * H_COLD));
+    if (const char *e = diag_env("CSDR_RUN4096_RUNS")) runs_knob = (uint32_t)atoi(e);
     kernel = cfg.mix ? "k_front4096+k_back4096<FM,mix>" : (cfg.fm ? "k_front4096+k_back4096<FM>" : "k_front4096+k_back4096<CF32>");
     return 0;
 }
 
 // frames per run: long enough that the 19 cold-start frames (about 8 frames' worth of work) stay below ~8 % of a run
-static uint32_t huge_runs(uint32_t nf, uint32_t cus)
+static uint32_t huge_runs(uint32_t nf, uint32_t cus, uint32_t runs_knob)
 {
-    uint32_t nruns = cus / 4;                           // 4 siblings per run, one 512-thread workgroup per CU
-    if (const char *e = diag_env("CSDR_RUN4096_RUNS")) { const uint32_t v = (uint32_t)atoi(e); if (v >= 1) nruns = v; }
+    uint32_t nruns = runs_knob >= 1 ? runs_knob : cus / 4;      // 4 siblings per run, one 512-thread workgroup per CU
     while (nruns > 1 && nf / nruns < 48) nruns >>= 1;    // (a run pays 20 cold-start frames: the reference chunk of 4096 frames is 64 runs of 64)
     if (nruns > 8) nruns &= ~7u;                        // the XCD-friendly workgroup -> (run, sibling) map wants a multiple of 8
     return nruns ? nruns : 1;
@@ -476,18 +477,15 @@ int HugePlan::run(const FusedCall &call, void *out, hipStream_t s, KernelTimer *
     Front4096Args A{};
     A.x = reinterpret_cast<const float4 *>(call.d_in); A.tail = d_tail[cur]; A.z = d_z;
     A.taps = d_taps; A.wpre = d_wpre; A.tw4 = d_tw4;
-    A.nf = nf; A.nruns = huge_runs(nf, cus); A.parity0 = (uint32_t)(frames_done & 1u);
-    const double beta = c.dc_block ? (double)c.dc.beta : 0.0;
-    A.alpha = c.dc_block ? (float)(1.0 - beta) : 0.0f; A.beta = (float)beta; A.l2beta = c.dc_block ? (float)std::log2(beta) : -1000.0f;
-    for (int i = 0; i < 16; i++) A.b16[i] = (float)std::pow(beta, 16.0 * i);
-    for (int i = 0; i < 17; i++) A.b256[i] = (float)std::pow(beta, 256.0 * i);
+    A.nf = nf; A.nruns = huge_runs(nf, cus, runs_knob); A.parity0 = (uint32_t)(frames_done & 1u);
+    dcc.put(A);
     int r;
     if (timer && (r = timer->begin(s))) return r;
     hipLaunchKernelGGL(k_front4096, dim3(4 * A.nruns), dim3(512), 0, s, A);
     Back4096Args Bk{};
     Bk.z = d_z; Bk.tw = d_tw; Bk.nf = nf; Bk.out_stride = nf;
     Bk.tile_major = call.tile_major ? 1u : 0u;
-    Bk.pk = phase_consts(1.0f); Bk.pk.hp *= c.fm_ref; Bk.pk.pi *= c.fm_ref; Bk.pk.ref = c.fm_ref;
+    Bk.pk = phase_consts_scaled(c.fm_ref);
     Bk.fm_ref = c.fm_ref; Bk.tiny = 1e-37f;
     const uint32_t nblk = (nf + 15) / 16;
     if (c.mix) {

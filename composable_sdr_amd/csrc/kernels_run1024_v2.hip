@@ -448,17 +448,11 @@ int run1024_v2_launch(const Run1024v2Host &h, bool fm, hipStream_t s, KernelTime
     A.uhist_in = h.uhist_in; A.uhist_out = h.uhist_out; A.vend_in = h.vend_in; A.vend_out = h.vend_out;
     A.rp_in = h.rp_in; A.rp_out = h.rp_out;
     A.nf = h.nf; A.nb = h.nf / B2_T4; A.nruns = h.nruns; A.parity0 = h.parity0; A.out_stride = h.nf;
-    {
-        static const double wt = diag_env("CSDR_RUN1024_WEIGHT") ? atof(diag_env("CSDR_RUN1024_WEIGHT")) : 1.2;   // share of the older workgroup of a CU (1 = even)
-        A.n0 = (h.nruns >= 2 && !(h.nruns & 1u) && wt > 1.0 && wt < 1.5) ? (uint32_t)std::llround(0.5 * wt * (double)A.nb) : 0u;
-    }
-    const double beta = h.dc_block ? h.beta : 0.0;
-    A.alpha = h.dc_block ? (float)(1.0 - beta) : 0.0f; A.beta = (float)beta; A.l2beta = h.dc_block ? (float)std::log2(beta) : -1000.0f;
-    for (int i = 0; i < 16; i++) A.b16[i] = (float)std::pow(beta, 16.0 * i);
-    for (int i = 0; i < 17; i++) A.b256[i] = (float)std::pow(beta, 256.0 * i);
+    const double wt = h.weight;
+    A.n0 = (h.nruns >= 2 && !(h.nruns & 1u) && wt > 1.0 && wt < 1.5) ? (uint32_t)std::llround(0.5 * wt * (double)A.nb) : 0u;
+    h.dc->put(A);
     A.fm_ref = h.fm_ref; A.tiny = 1e-37f;
-    A.pk = phase_consts(1.0f);                          // unscaled polynomial (fm_quad scales a = min / max by ref)
-    A.pk.hp *= h.fm_ref; A.pk.pi *= h.fm_ref; A.pk.ref = h.fm_ref;
+    A.pk = phase_consts_scaled(h.fm_ref);               // unscaled polynomial (fm_quad scales a = min / max by ref)
     int r;
     if (timer && (r = timer->begin(s))) return r;
     A.g = h.g;
@@ -473,13 +467,13 @@ int run1024_v2_launch(const Run1024v2Host &h, bool fm, hipStream_t s, KernelTime
     return 0;
 }
 
-uint32_t run1024_v2_runs(uint32_t nf, uint32_t cus)
+uint32_t run1024_v2_runs(uint32_t nf, uint32_t cus, uint32_t max_runs)
 {
     // two workgroups per CU; a run >= 1 spends 6 read-only + 4 halo tiles on its start state; the shorter (younger) runs get
     // up to 1/4 less than the average: at least 24 tiles per run on average (>= 16 for every one)
     const uint32_t nb = nf / B2_T4;
     uint32_t nruns = 2 * cus;
-    if (const char *e = diag_env("CSDR_RUN1024_RUNS")) { const uint32_t v = (uint32_t)atoi(e); if (v >= 1 && v < nruns) nruns = v; }   // experiments
+    if (max_runs >= 1 && max_runs < nruns) nruns = max_runs;
     if (nruns > nb / 24) nruns = nb / 24;
     if (nruns > 2) nruns &= ~1u;
     return nruns;                                       // 0: too short for this kernel

@@ -570,22 +570,15 @@ int run1024_v3_launch(const Run1024v2Host &h, bool fm, uint32_t nruns, hipStream
     A.uhist_in = h.uhist_in; A.uhist_out = h.uhist_out; A.vend_in = h.vend_in; A.vend_out = h.vend_out;
     A.rp_in = h.rp_in; A.rp_out = h.rp_out;
     A.nf = h.nf; A.nb = h.nf / B3_T4; A.nruns = nruns; A.parity0 = h.parity0; A.tile_major = (!fm && h.tile_major) ? 1u : 0u;
-    const double beta = h.dc_block ? h.beta : 0.0;
-    A.alpha = h.dc_block ? (float)(1.0 - beta) : 0.0f; A.beta = (float)beta; A.l2beta = h.dc_block ? (float)std::log2(beta) : -1000.0f;
-    for (int i = 0; i < 16; i++) A.b16[i] = (float)std::pow(beta, 16.0 * i);
-    for (int i = 0; i < 17; i++) A.b256[i] = (float)std::pow(beta, 256.0 * i);
+    h.dc->put(A);
     A.fm_ref = h.fm_ref; A.tiny = 1e-37f;
-    A.pk = phase_consts(1.0f);                          // unscaled polynomial (fm_quad scales a = min / max by ref)
-    A.pk.hp *= h.fm_ref; A.pk.pi *= h.fm_ref; A.pk.ref = h.fm_ref;
-    static const char *trace_file = diag_env("CSDR_RUN1024_V3_TRACE");
-    static unsigned long long *d_trace = nullptr;
-    if (trace_file && !d_trace) CSDR_HIP(hipMalloc(&d_trace, 1536 * sizeof(unsigned long long)));
-    if (trace_file) { CSDR_HIP(hipMemsetAsync(d_trace, 0, 1536 * sizeof(unsigned long long), s)); A.trace = d_trace; }
+    A.pk = phase_consts_scaled(h.fm_ref);               // unscaled polynomial (fm_quad scales a = min / max by ref)
+    if (h.trace) { CSDR_HIP(hipMemsetAsync(h.trace, 0, RUN1024_V3_TRACE_N * sizeof(unsigned long long), s)); A.trace = h.trace; }
     int r;
     if (timer && (r = timer->begin(s))) return r;
     // no warm-up windows: whole runs of >= 16 tiles (a cold start is 4 tiles deep and the correction covers 4 more), the state arrays there
     if (!h.cpre || !h.side) { set_error("run1024_v3_launch: internal: no state arrays"); return -1; }
-    A.nowu = (h.rt && h.dc_block && nruns >= 2 && A.nb / nruns >= 16u) ? 1u : 0u;
+    A.nowu = (h.rt && nruns >= 2 && A.nb / nruns >= 16u) ? 1u : 0u;      // (rt: the blocker is on)
     A.cpre = h.cpre; A.side = h.side;
     if (fm) hipLaunchKernelGGL((k_run1024v3<true>), dim3(nruns), dim3(512), 0, s, A);
     else hipLaunchKernelGGL((k_run1024v3<false>), dim3(nruns), dim3(512), 0, s, A);
@@ -595,16 +588,16 @@ int run1024_v3_launch(const Run1024v2Host &h, bool fm, uint32_t nruns, hipStream
     }
     if (timer && (r = timer->end(s))) return r;         // the bracket covers the correction kernel: it is part of every no-warm-up step
     CSDR_HIP(hipGetLastError());
-    if (trace_file) {                                   // debug: the last launch's stamps, raw uint64: front [128][8], back [128][4]
-        std::vector<unsigned long long> hbuf(1536);
+    if (h.trace) {                                      // debug: the last launch's stamps, raw uint64: front [128][8], back [128][4]
+        std::vector<unsigned long long> hbuf(RUN1024_V3_TRACE_N);
         CSDR_HIP(hipStreamSynchronize(s));
-        CSDR_HIP(hipMemcpy(hbuf.data(), d_trace, 1536 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-        if (FILE *f = fopen(trace_file, "wb")) { fwrite(hbuf.data(), sizeof(unsigned long long), 1536, f); fclose(f); }
+        CSDR_HIP(hipMemcpy(hbuf.data(), h.trace, hbuf.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+        if (FILE *f = fopen(h.trace_file, "wb")) { fwrite(hbuf.data(), sizeof(unsigned long long), hbuf.size(), f); fclose(f); }
     }
     return 0;
 }
 
-uint32_t run1024_v3_runs(uint32_t nf, bool fm, uint32_t cus)
+uint32_t run1024_v3_runs(uint32_t nf, bool fm, uint32_t cus, uint32_t max_runs)
 {
     const uint32_t B3_TB = fm ? B3_TBF : B3_TBC;
     // one workgroup per CU; runs are whole blocks of 8 (F32) / 4 (CF32) tiles (a row's 128-byte line), at least one (a run >= 1 walks 4
@@ -613,7 +606,7 @@ uint32_t run1024_v3_runs(uint32_t nf, bool fm, uint32_t cus)
     if (nf % B3_T4) return 0;
     const uint32_t nblk = (nf / B3_T4 + B3_TB - 1) / B3_TB;
     uint32_t nruns = cus;
-    if (const char *e = diag_env("CSDR_RUN1024_V3_RUNS")) { const uint32_t v = (uint32_t)atoi(e); if (v >= 1 && v < nruns) nruns = v; }   // experiments
+    if (max_runs >= 1 && max_runs < nruns) nruns = max_runs;
     if (nruns > nblk) nruns = nblk;
     return nruns;                                       // 0: a ragged call (not whole 4-frame tiles)
 }

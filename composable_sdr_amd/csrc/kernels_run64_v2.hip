@@ -339,14 +339,14 @@ __global__ __launch_bounds__(256) void k_run64_dcfix(Run64v2Args A, const float2
 
 }  // namespace
 
-uint32_t run64_v2_runs(uint32_t nf, uint32_t cus)
+uint32_t run64_v2_runs(uint32_t nf, uint32_t cus, bool all)
 {
     // two workgroups per CU; a run >= 1 reads 6 warm-up tiles and walks a halo tile: at least 16 tiles per run on average.  A call pays
     // those ~23 tile times (~60 us) whatever its size, so k_run64 keeps the calls below 3072 tiles (196 608 frames; measured by call size:
     // 4096 frames 17 us against 60 us, 131 072 frames 58 against 66, 262 144 frames 99 against 76)
     if (nf % 64u) return 0;
     const uint32_t nb = nf / 64u;
-    if (nb < 3072u && !diag_env("CSDR_RUN64_V2_ALL")) return 0;
+    if (nb < 3072u && !all) return 0;
     uint32_t nruns = 2 * cus;
     if (nruns > nb / 16) nruns = nb / 16;
     if (nruns > 2) nruns &= ~1u;
@@ -359,17 +359,12 @@ int run64_v2_launch(const Run64v2Host &h, hipStream_t s, KernelTimer *timer)
     A.x = h.x; A.out = h.out; A.taps = h.taps; A.tw = h.tw; A.wpre = h.wpre;
     A.uhist_in = h.uhist_in; A.uhist_out = h.uhist_out; A.vend_in = h.vend_in; A.vend_out = h.vend_out;
     A.nf = h.nf; A.nb = h.nf / 64u; A.nruns = h.nruns; A.parity0 = h.parity0; A.out_stride = h.nf; A.tile_major = h.tile_major ? 1u : 0u;
-    {
-        static const double wt = diag_env("CSDR_RUN64_WEIGHT") ? atof(diag_env("CSDR_RUN64_WEIGHT")) : 1.1;   // share of the older workgroup of a CU (1 = even; 1.1 measured best: 243 vs 250 us)
-        A.n0 = (h.nruns >= 2 && !(h.nruns & 1u) && wt > 1.0 && wt < 1.5) ? (uint32_t)std::llround(0.5 * wt * (double)A.nb) : 0u;
-    }
-    const double beta = h.dc_block ? h.beta : 0.0;
-    A.alpha = h.dc_block ? (float)(1.0 - beta) : 0.0f; A.beta = (float)beta; A.l2beta = h.dc_block ? (float)std::log2(beta) : -1000.0f;
-    for (int i = 0; i < 16; i++) A.b16[i] = (float)std::pow(beta, 16.0 * i);
-    for (int i = 0; i < 17; i++) A.b256[i] = (float)std::pow(beta, 256.0 * i);
+    const double wt = h.weight;
+    A.n0 = (h.nruns >= 2 && !(h.nruns & 1u) && wt > 1.0 && wt < 1.5) ? (uint32_t)std::llround(0.5 * wt * (double)A.nb) : 0u;
+    h.dc->put(A);
     int r;
     if (timer && (r = timer->begin(s))) return r;
-    A.nowu = (h.cpre && h.rt && h.dc_block && h.nruns >= 2 && A.nb / h.nruns >= 14u) ? 1u : 0u;
+    A.nowu = (h.cpre && h.rt && h.nruns >= 2 && A.nb / h.nruns >= 14u) ? 1u : 0u;      // (rt: the blocker is on)
     A.cpre = h.cpre;
     hipLaunchKernelGGL(k_run64v2, dim3(h.nruns), dim3(256), 0, s, A);
     if (A.nowu) hipLaunchKernelGGL(k_run64_dcfix, dim3(h.nruns - 1u, (4u * RUN64_DCFIX_F + 255u) / 256u), dim3(256), 0, s, A, h.rt);

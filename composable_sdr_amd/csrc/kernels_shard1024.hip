@@ -554,14 +554,13 @@ __global__ __launch_bounds__(64) void k_shard1024_dcfix(Shard1024Args A, const f
 }  // namespace
 
 // whole 4-frame tiles; at least two blocks (16 / 8 tiles) per run: a run >= 1 spends six read-only tiles and four halo tiles on its start
-uint32_t shard1024_runs(uint32_t nf, bool fm, uint32_t G, uint32_t cus)
+uint32_t shard1024_runs(uint32_t nf, bool fm, uint32_t G, uint32_t cus, uint32_t max_runs)
 {
     if ((G != 4 && G != 8) || (nf & 3u) || nf == 0) return 0;
-    if (diag_env("CSDR_NO_SHARD1024")) return 0;
     const uint32_t nb = nf / 4, TB = fm ? 8u : 4u, nblk = (nb + TB - 1) / TB;
     if ((uint64_t)(1024 / G) * nf * (fm ? 4u : 8u) >= (1ull << 31)) return 0;       // the row stores use 32-bit buffer offsets
     uint32_t nruns = cus;
-    if (const char *e = diag_env("CSDR_SHARD1024_RUNS")) { const uint32_t v = (uint32_t)atoi(e); if (v >= 1 && v < nruns) nruns = v; }   // tests: force runs onto short inputs
+    if (max_runs >= 1 && max_runs < nruns) nruns = max_runs;
     const uint32_t per = fm ? 2u : 4u;                  // >= 16 tiles per run
     if (nruns > nblk / per) nruns = nblk / per;
     return nruns;                                       // 0: too short for this kernel
@@ -575,19 +574,13 @@ int shard1024_launch(const Run1024v2Host &h, bool fm, uint32_t nruns, hipStream_
     A.rp_in = h.rp_in; A.rp_out = h.rp_out;
     A.nf = h.nf; A.nb = h.nf / 4; A.nruns = nruns; A.parity0 = h.parity0; A.tile_major = (!fm && h.tile_major) ? 1u : 0u;
     if (A.tile_major && (h.nf & 15u)) { set_error("k_shard1024: a tile-major plane takes whole 16-frame blocks"); return -1; }
-    const double beta = h.dc_block ? h.beta : 0.0;
-    A.alpha = h.dc_block ? (float)(1.0 - beta) : 0.0f; A.beta = (float)beta; A.l2beta = h.dc_block ? (float)std::log2(beta) : -1000.0f;
-    for (int i = 0; i < 16; i++) A.b16[i] = (float)std::pow(beta, 16.0 * i);
-    for (int i = 0; i < 17; i++) A.b256[i] = (float)std::pow(beta, 256.0 * i);
+    h.dc->put(A);
     A.fm_ref = h.fm_ref; A.tiny = 1e-37f;
-    A.pk = phase_consts(1.0f);                          // unscaled polynomial (fm_quad scales a = min / max by ref)
-    A.pk.hp *= h.fm_ref; A.pk.pi *= h.fm_ref; A.pk.ref = h.fm_ref;
-    static const char *trace_file = S1_TRACE ? diag_env("CSDR_SHARD1024_TRACE") : nullptr;
-    static unsigned long long *d_trace = nullptr;
-    if (trace_file && !d_trace) CSDR_HIP(hipMalloc(&d_trace, 768 * sizeof(unsigned long long)));
-    if (trace_file) { CSDR_HIP(hipMemsetAsync(d_trace, 0, 768 * sizeof(unsigned long long), s)); A.trace = d_trace; }
+    A.pk = phase_consts_scaled(h.fm_ref);               // unscaled polynomial (fm_quad scales a = min / max by ref)
+    unsigned long long *const trace = S1_TRACE ? h.trace : nullptr;
+    if (trace) { CSDR_HIP(hipMemsetAsync(trace, 0, SHARD1024_TRACE_N * sizeof(unsigned long long), s)); A.trace = trace; }
     // no warm-up windows: whole runs of >= 16 tiles (a cold start is 4 tiles deep and the correction covers 8 more), the state arrays there
-    A.nowu = (h.rt && h.cpre && h.side && h.dc_block && nruns >= 2) ? 1u : 0u;
+    A.nowu = (h.rt && h.cpre && h.side && nruns >= 2) ? 1u : 0u;      // (rt: the blocker is on)
     A.cpre = h.cpre; A.side = h.side; A.mfix = h.mfix;
     int r;
     if (timer && (r = timer->begin(s))) return r;
@@ -604,11 +597,11 @@ int shard1024_launch(const Run1024v2Host &h, bool fm, uint32_t nruns, hipStream_
     }
     if (timer && (r = timer->end(s))) return r;         // (the bracket covers the correction kernel)
     CSDR_HIP(hipGetLastError());
-    if (trace_file) {                                   // debug: the last launch's stamps, raw uint64 [role][96][4]
-        std::vector<unsigned long long> hbuf(768);
+    if (trace) {                                        // debug: the last launch's stamps, raw uint64 [role][96][4]
+        std::vector<unsigned long long> hbuf(SHARD1024_TRACE_N);
         CSDR_HIP(hipStreamSynchronize(s));
-        CSDR_HIP(hipMemcpy(hbuf.data(), d_trace, 768 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-        if (FILE *f = fopen(trace_file, "wb")) { fwrite(hbuf.data(), sizeof(unsigned long long), hbuf.size(), f); fclose(f); }
+        CSDR_HIP(hipMemcpy(hbuf.data(), trace, hbuf.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+        if (FILE *f = fopen(h.trace_file, "wb")) { fwrite(hbuf.data(), sizeof(unsigned long long), hbuf.size(), f); fclose(f); }
     }
     return 0;
 }

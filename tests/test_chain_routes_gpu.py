@@ -6,7 +6,9 @@ sizes with and without the AGC, a tail-only handle): Chain.path, the timed kerne
 csdr_last_error for calls a WBFM, an AM and a backward handle refuse or have nothing to do for.
 
 Both tables were recorded from the library as it stood before the any-M route became a ChainPlan (GenericPlan, plan_generic.hip), not
-from the code they test: the texts are read by tools and logs, and that change was to keep every one of them."""
+from the code they test: the texts are read by tools and logs, and that change was to keep every one of them.  The rows of the run-kernel
+cells (run*, shard*, fused*_fm_mix: knobs force the kernels onto small calls) were recorded the same way, from the library before the
+plans came to share their stream state, DC constants and cold-start setup."""
 import ctypes as C
 import os
 import sys
@@ -54,6 +56,17 @@ ROUTES = {
     'fused4096_fm': ('fused-4096|k_front4096+k_back4096<FM>', 'k_front4096+k_back4096<FM>', ['k_front4096+k_back4096<FM>', 'k_front4096+k_back4096<FM>']),
     'fused4096_fm_agc': ('fused-4096|k_front4096+k_back4096<CF32>+agc-spec', 'k_front4096+k_back4096<CF32>', ['k_front4096+k_back4096<CF32>', 'k_front4096+k_back4096<CF32>']),
     'tail_only_fm': ('tail-only+agc-spec', 'k_agc_spec', ['k_agc_spec', 'k_agc_spec']),
+    'run256v2_fm': ('fused-256|k_tile256<FM>', 'k_tile256<FM>', ['k_run256v2<FM>', 'k_run256v2<FM>']),
+    'run256v2_fm_wu': ('fused-256|k_tile256<FM>', 'k_tile256<FM>', ['k_run256v2<FM>', 'k_run256v2<FM>']),
+    'run256v2_cf32_agc': ('fused-256|k_tile256<CF32>+agc-spec', 'k_tile256<CF32>', ['k_run256v2<CF32>', 'k_run256v2<CF32>']),
+    'run256v2_fm_g8': ('fused-256|k_tile256<FM>+interleaved-shard', 'k_tile256<FM>', ['k_run256v2<FM>/G8', 'k_run256v2<FM>/G8']),
+    'run64v2_cf32': ('fused-k_run64<CF32>', 'k_run64<CF32>', ['k_run64v2', 'k_run64<CF32>', 'k_run64v2']),
+    'run1024v3_fm': ('fused-k_run1024v3<FM>', 'k_run1024v3<FM>', ['k_run1024v3<FM>', 'k_run1024<FM>', 'k_run1024v3<FM>']),
+    'run1024v3_cf32_agc': ('fused-k_run1024v3<CF32>+agc-spec', 'k_run1024v3<CF32>', ['k_run1024v3<CF32>', 'k_run1024<CF32>', 'k_run1024v3<CF32>']),
+    'shard1024_fm_g8': ('fused-k_shard1024<FM>/G8+interleaved-shard', 'k_shard1024<FM>/G8', ['k_shard1024<FM>/G8', 'k_run1024<FM>', 'k_shard1024<FM>/G8']),
+    'run1024v2_fm_g2': ('fused-k_run1024v2<FM>/G2+interleaved-shard', 'k_run1024v2<FM>/G2', ['k_run1024v2<FM>/G2', 'k_run1024<FM>', 'k_run1024v2<FM>/G2']),
+    'fused256_fm_mix': ('fused-256|k_tile256<FM>', 'k_tile256<FM>', ['k_tile256<FM>', 'k_tile256<FM>']),
+    'fused1024_fm_mix': ('fused-k_run1024v3<FM>', 'k_run1024v3<FM>', ['k_run1024v3<FM>', 'k_run1024<FM>']),
 }
 UNTOUCHED = 0xdeadbeef
 # handle: [(call, return code, *n_out, csdr_last_error()[:40] of a refused call)]

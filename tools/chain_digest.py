@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
 """One SHA-256 per chain route: does a build compute the same bits as another one?
 
-Every cell of CELLS is one chain configuration (the routes of csdr_route_table(), their tails and flags) run for two calls on the
-seeded synthetic signal (tests/synth.py); the digest covers the bytes of both outputs.  Only the public Python API is used, so
+Every cell of CELLS is one chain configuration (the routes of csdr_route_table(), their tails and flags) run for two or three calls on
+the seeded synthetic signal (tests/synth.py); the digest covers the bytes of all outputs.  A cell may carry diagnostics knobs (DESIGN.md
+6.1) that force a run kernel onto a small input: they are set, with CSDR_DIAG=1, around the cell's create and calls, and removed after.  Only the public Python API is used, so
 the file runs unchanged against any checkout, or against another build of the library (CSDR_LIB=/path/to/libcsdr_hip.so).
 
     python tools/chain_digest.py                       # id, digest, path, timed kernels
@@ -29,9 +30,10 @@ F = _lib
 SMALL, BIG, WB = [96, 75], [64, 43], [96, 76]       # frames of the two calls: the second one ragged (WBFM: whole decimations)
 
 
-def _cell(id, channels, frames=None, flags=0, **kw):
-    kw.update(channels=channels, max_frames=256, flags=F.FLAG_TIME_KERNELS | F.FLAG_QUIET | flags)
-    return id, kw, frames or (BIG if channels >= 4096 else SMALL)
+def _cell(id, channels, frames=None, flags=0, knobs=None, **kw):
+    frames = frames or (BIG if channels >= 4096 else SMALL)
+    kw.update(channels=channels, max_frames=max(frames), flags=F.FLAG_TIME_KERNELS | F.FLAG_QUIET | flags, knobs=knobs or {})
+    return id, kw, frames
 
 
 CELLS = [
@@ -60,21 +62,48 @@ CELLS = [
 for _m in (64, 256, 1024, 4096):
     CELLS += [_cell(f"fused{_m}_fm", _m, demod="fm"), _cell(f"fused{_m}_fm_agc", _m, demod="fm", agc=-10.0)]
 CELLS.append(_cell("tail_only_fm", 8, demod="fm", agc=-10.0, tail_only=True))
+# the run kernels, at the smallest shapes tests/test_chain_params_gpu.py forces them onto
+R256, RUN256 = [2048, 1029], {"CSDR_RUN_MIN_TILES": "1"}
+CELLS += [
+    _cell("run256v2_fm", 256, R256, knobs=RUN256, demod="fm"),
+    _cell("run256v2_fm_wu", 256, R256, knobs=dict(RUN256, CSDR_NOWU="0"), demod="fm"),
+    _cell("run256v2_cf32_agc", 256, R256, knobs=RUN256, agc=-10.0),
+    _cell("run256v2_fm_g8", 256, R256, knobs=RUN256, demod="fm", chan_stride=8, chan_first=6),      # channel 126: next to DC
+    _cell("run64v2_cf32", 64, [8192, 5, 6144], knobs={"CSDR_RUN64_V2_ALL": "1"}),
+    _cell("run1024v3_fm", 1024, [2048, 5, 1024], knobs={"CSDR_RUN1024_V3_RUNS": "8"}, demod="fm"),
+    _cell("run1024v3_cf32_agc", 1024, [2048, 5, 1024], knobs={"CSDR_RUN1024_V3_RUNS": "8"}, agc=-10.0),
+    _cell("shard1024_fm_g8", 1024, [1024, 5, 1024], knobs={"CSDR_SHARD1024_RUNS": "4"}, demod="fm", chan_stride=8),
+    _cell("run1024v2_fm_g2", 1024, [1024, 5, 1024], knobs={"CSDR_RUN1024_RUNS": "4"}, demod="fm", chan_stride=2),
+    _cell("fused256_fm_mix", 256, demod="fm", mix=True),
+    _cell("fused1024_fm_mix", 1024, demod="fm", mix=True),
+]
 
 
 def run_cell(kw, frames, x):
     """(path, timed kernel before the first call, [timed kernel after each call], [output of each call])"""
-    M = kw["channels"]
-    ch = Chain(**kw)
+    kw = dict(kw)
+    M, knobs = kw["channels"], dict(kw.pop("knobs", {}))
+    if knobs:
+        knobs["CSDR_DIAG"] = "1"
+    before = {k: os.environ.get(k) for k in knobs}
+    os.environ.update(knobs)
     try:
-        path, names, outs, pos = ch.path, [ch.kernel_time()[0]], [], 0
-        for nf in frames:
-            outs.append(ch.process(x[pos:pos + nf * M]))
-            names.append(ch.kernel_time()[0])
-            pos += nf * M
-        ch.status()
+        ch = Chain(**kw)
+        try:
+            path, names, outs, pos = ch.path, [ch.kernel_time()[0]], [], 0
+            for nf in frames:
+                outs.append(ch.process(x[pos:pos + nf * M]))
+                names.append(ch.kernel_time()[0])
+                pos += nf * M
+            ch.status()
+        finally:
+            ch.close()
     finally:
-        ch.close()
+        for k, v in before.items():
+            if v is None:
+                del os.environ[k]
+            else:
+                os.environ[k] = v
     return path, names[0], names[1:], outs
 
 
