@@ -71,11 +71,20 @@ def chain_truth(x, M, dc=True, alpha=0.0005, kf=0.3, m=7, As=80.0):
 
 
 # --------------------------------------------------------------------------- fixture
-def noise(M, nf, seed=None):
-    """complex white Gaussian noise, sigma = 0.5, zero mean: every channel equally strong, the phase advance uniform on (-pi, pi]"""
+def noise(M, nf, seed=None, offset=0.0):
+    """complex white Gaussian noise, sigma = 0.5, zero mean: every channel equally strong, the phase advance uniform on (-pi, pi].
+    offset: a constant added to every sample (in f64, rounded to f32 with the sum): the DC the blocker has to take out"""
     g = np.random.Generator(np.random.PCG64(7 + M if seed is None else seed))
     z = g.standard_normal((M * nf, 2)) * (0.5 / np.sqrt(2.0))
-    return (z[:, 0] + 1j * z[:, 1]).astype(np.complex64)
+    return (z[:, 0] + 1j * z[:, 1] + complex(offset)).astype(np.complex64)
+
+
+def dc_rows(M, m=7, As=80.0):
+    """the four channels a DC offset lands in (pre-mix by the PFB offset)"""
+    if M == 1:
+        return np.array([0])
+    y = O.Chain(M, dc_block=False, pfb_m=m, pfb_as=As).process(np.ones(M * (2 * m + 4), np.complex64))
+    return np.sort(np.argsort(np.abs(y[:, -1]))[-4:])
 
 
 def prev(a):
@@ -178,8 +187,9 @@ def phi17(kf=None):
 # --------------------------------------------------------------------------- shared references and the three FM assertions
 KF = 0.3
 ALPHA = 0.0005
-# every (M, frames) a case of test_fm_phase_routes_gpu.py runs on (it asserts membership)
-SHAPES = [(1, 42345), (7, 3333), (20, 533), (64, 3141), (256, 405), (1024, 2053), (1024, 3077), (4096, 49)]
+# every (M, frames) a case of test_fm_phase_routes_gpu.py or of fused_cases.py runs on (both assert membership); the noise stream of an
+# M is drawn once, at its largest frame count, and the shorter shapes are its prefixes
+SHAPES = [(1, 42345), (7, 3333), (20, 533), (64, 3141), (64, 14341), (256, 405), (256, 6277), (1024, 2053), (1024, 3077), (4096, 49)]
 _C = {}
 
 
@@ -191,13 +201,14 @@ def refs_of(x, M, dc, kf=KF, alpha=ALPHA):
                 orc_r=O.Chain(M, **kw).process(x), orc_fm=O.Chain(M, demod="fm", kf=kf, **kw).process(x))
 
 
-def refs(M, nf, dc, kf=KF, alpha=ALPHA):
-    """refs_of the noise stream's first nf frames, computed once (the cache holds one M at a time: the cases of a file come M by M)"""
-    key = (M, nf, dc, kf, alpha)
+def refs(M, nf, dc, kf=KF, alpha=ALPHA, offset=0.0):
+    """refs_of the noise stream's first nf frames (plus the constant `offset`), computed once (the cache holds one M at a time: the
+    cases of a file come M by M)"""
+    key = (M, nf, dc, kf, alpha, complex(offset))
     if key not in _C:
         if any(k[0] != M for k in _C):
             _C.clear()
-        _C[key] = refs_of(noise(M, max(n for m, n in SHAPES if m == M))[:M * nf], M, dc, kf, alpha)
+        _C[key] = refs_of(noise(M, max(n for m, n in SHAPES if m == M), offset=offset)[:M * nf], M, dc, kf, alpha)
     return _C[key]
 
 

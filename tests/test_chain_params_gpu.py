@@ -19,6 +19,7 @@ import numpy as np
 import pytest
 
 import oracle_lib as O
+from chain_truth import dc_rows as _dc_rows      # (shared with fused_cases.py, which has to import without the library)
 from util import knob, rel_rms, wrap_pm
 
 pytestmark = pytest.mark.gpu
@@ -53,14 +54,6 @@ def _input(M, nf, seed, dc=(0.3, 0.2)):
         _X.clear()
         _X[key] = x.cpu().numpy().view(np.complex64).reshape(-1)
     return _X[key]
-
-
-def _dc_rows(M, m=7, As=80.0):
-    """the four channels a DC offset lands in (pre-mix by the PFB offset)"""
-    if M == 1:
-        return np.array([0])
-    y = O.Chain(M, dc_block=False, pfb_m=m, pfb_as=As).process(np.ones(M * (2 * m + 4), np.complex64))
-    return np.sort(np.argsort(np.abs(y[:, -1]))[-4:])
 
 
 def _references(x, M, alpha, demod, mix=False, m=7, As=80.0):

@@ -14,8 +14,10 @@ truth modulo 1 / kf:
   (a) every counted sample (frames behind the window fill, r and r' != 0), unweighted:
           |d_t| <= ref (2 (E / |r_t| + E / |r_t-1|) + phi)
       E: the largest |got - truth| of the route's CF32 run on the same input (itself held to the standing rule of
-      test_chain_params_gpu._compare: rel-RMS <= 2 e_orc + 1e-6, per element <= 4 e_orc + 2e-5 max|truth|); where the route has no CF32
-      instantiation, the whole-band CF32 kernel of the same M.  phi: the phase function's own error, derived term by term in
+      test_chain_params_gpu._compare: rel-RMS <= 2 e_orc + 1e-6, per element <= 4 e_orc + 2e-5 max|truth|, and on the fused routes to
+      the per-element bound (b) of fused_cases.py, |got - truth| <= 4 max|oracle - truth| + 6 d U rms(truth) per row group, which is
+      what keeps a route with one channel off from buying itself a looser FM bound); where the route has no CF32 instantiation, the
+      whole-band CF32 kernel of the same M.  phi: the phase function's own error, derived term by term in
       chain_truth.phi15 / phi17 (7.6e-7 and 8.5e-7 rad; a route that uses two functions takes the larger).
   (b) per octant of the true angle, the mean signed error over the kept samples (min(|r|, |r'|) > 0.1 rms):
           |mean_o| <= 2 max_o |mean_o(oracle)| + ref 1.2e-7
@@ -44,6 +46,7 @@ import numpy as np
 import pytest
 
 import chain_truth as T
+import fused_cases as F
 from test_chain_params_gpu import ROUTES, TIMED, _dc_rows, _route_check
 from util import knob, rel_rms
 
@@ -160,14 +163,20 @@ def _sub(R, sl):
     return {k: (v[sl] if isinstance(v, np.ndarray) and v.ndim == 2 else v) for k, v in R.items()}
 
 
-def _cf32_E(tag, got, R):
-    """the standing rule of test_chain_params_gpu._compare on the CF32 partner's output; returns E = max |got - truth|"""
+def _cf32_E(tag, got, R, fused=None):
+    """the standing rule of test_chain_params_gpu._compare on the CF32 partner's output; returns E = max |got - truth|.
+    fused = (M, band rows of the output, d): a fused route, also held to (b) of fused_cases.py"""
     assert got.shape == R["r"].shape and np.isfinite(got.view(np.float32)).all(), tag
     eg, eo = np.abs(got.astype(np.complex128) - R["r"]), np.abs(R["orc_r"].astype(np.complex128) - R["r"])
     rg, ro = rel_rms(got, R["r"]), rel_rms(R["orc_r"], R["r"])
     print(f"{tag} CF32: rel-rms {rg:.3e} (oracle {ro:.3e}); max {eg.max():.3e} (oracle {eo.max():.3e})")
     assert rg <= 2 * ro + 1e-6, (tag, rg, ro)
     assert eg.max() <= 4 * eo.max() + 2e-5 * float(np.abs(R["r"]).max()), (tag, eg.max(), eo.max())
+    if fused is not None:
+        M, rows, d = fused
+        b = F.element_ratio(M, rows, got, R["r"], R["orc_r"], d)
+        print(f"{tag} CF32: worst ratio to the per-element bound (b) of fused_cases.py (d = {d:.2f}) {b:.3f}")
+        assert b <= 1.0, (tag, b)
     return float(eg.max())
 
 
@@ -187,7 +196,9 @@ def test_fm_of_every_route_in_all_octants(case, dc, monkeypatch):
         x = R["x"]
         fm, names, path = _run(case, x, frames, "fm", dc, ALPHA, kf, monkeypatch)
         cf, cnames, cpath = _run(case, x, frames, "none", dc, ALPHA, kf, monkeypatch)
-        E = _cf32_E(f"{tag} dc={dc} [{cpath}] {cnames}", cf, R)
+        g, G = _shard(case)
+        fused = (M, np.arange(g, M, G), F.d_for(M, G)) if cpath.startswith("fused") else None
+        E = _cf32_E(f"{tag} dc={dc} [{cpath}] {cnames}", cf, R, fused)
         worst, bias, bb = T.check_fm(f"{tag} dc={dc} kf={kf} [{path}] {names}", fm, R, E, _phi(case, kf), kf)
         assert worst <= 1.0, (tag, worst)
         assert np.abs(bias).max() <= bb, (tag, bias, bb)
