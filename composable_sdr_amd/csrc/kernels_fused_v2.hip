@@ -100,6 +100,14 @@ struct V2Args {
     RunArgs r;
 };
 
+// A store through a pointer that comes out of kernarg_ptr_s is a FLAT store to hipcc (a generic pointer), and FLAT counts on lgkmcnt too: the
+// waits of the tile loop are written by hand, so hipcc believes such a store in flight all around the loop and drains lgkmcnt(0) in front of
+// the first use of ANY LDS read.  Stored as global, the tile loop's LDS waits are counted (the reads return in the order of issue).
+__device__ __forceinline__ void store_global(float2 *p, float2 v)
+{
+    *(__attribute__((address_space(1))) v2f *)p = to_v(v);
+}
+
 // G > 1: INTERLEAVED CHANNEL SHARD g = A.c0 of G (rank g of G owns the channels g, g + G, ...; G | 16).  With
 // k = k1 + 16 k2 ownership only depends on k1, and W16^(a k1) = W16^(a g) W16^(a k1'), k1 = g + k1': the factor W16^(a g) is a
 // constant of polyphase branch j = 16 a + b1 and rides on its pre-mix phasor for free, after which the shard needs the pass-1
@@ -364,6 +372,11 @@ __global__ __launch_bounds__(256, (FM && G == 1) ? V2_ONE_WGS : 2) void k_run256
     // separately under the streaming reads: F32 output then costs as much HBM write energy as CF32 output of twice the size)
     float hold[16];
     v2f holdc[V2_PAIR_CF ? 16 : 1];
+    // ONE: the tile loop issues the reads of the FIR taps table and of a thread's run of the raw image ahead of the arithmetic that does
+    // not need them (hipcc otherwise puts a read group where the source has it, the wait right behind it).  V2_BEHIND(x) pins the order of
+    // issue and leaves the waits to hipcc: no LDS read crosses it, and what is computed from x stays behind it (x is in its registers at
+    // that point: the statement itself waits for nothing).
+#define V2_BEHIND(x) asm volatile("" : "+v"(x) :: "memory")
     auto tile = [&](float2 (&old)[NB], float2 (&nw)[NB], unsigned b_, const int par) {
         unsigned b = (unsigned)__builtin_amdgcn_readfirstlane((int)b_);            // keep the tile index (store / DMA bases) in SGPRs
         asm volatile("" : "+s"(b));
@@ -380,7 +393,10 @@ __global__ __launch_bounds__(256, (FM && G == 1) ? V2_ONE_WGS : 2) void k_run256
         if (ONE) asm volatile("" : "+v"(tid_t));
         V2STAMP(0);
         if (G == 1 && b + 1 == last && tid == 0) {      // the DC state in front of the next run's halo tile (launches without warm-up windows)
-            if (kernarg_u32_s<offsetof(V2Args, r.nowu)>()) kernarg_ptr_s<offsetof(V2Args, r.cpre)>()[w + 1] = c;
+            if (kernarg_u32_s<offsetof(V2Args, r.nowu)>()) {
+                if (ONE) store_global(kernarg_ptr_s<offsetof(V2Args, r.cpre)>() + (w + 1), c);
+                else kernarg_ptr_s<offsetof(V2Args, r.cpre)>()[w + 1] = c;
+            }
         }
         if (V2_TRACE && A.trace && !RA.trace_light && tid == 0) A.trace[(size_t)b_ * 16 + 15] = __builtin_amdgcn_s_memrealtime();
         bar();                                          // B_a: the tile image has landed (every wave waited for its own DMA); the other buffer is free
@@ -434,9 +450,14 @@ __global__ __launch_bounds__(256, (FM && G == 1) ? V2_ONE_WGS : 2) void k_run256
         v4f xr[8];
         float2 s = make_float2(0.f, 0.f);
         const unsigned raw_a = ONE ? (unsigned)tid_t * 128u + (unsigned)(tid_t >> 4) * (V2_FSB - 2048u) + ((unsigned)V2_RSW(tid_t & 15) << 4) : raw_a_;
+        if (ONE) {                                      // all eight reads of my run in front of the scan's first fmaf (counted waits, one per read)
+#pragma unroll
+            for (int i = 0; i < 8; i++) xr[i] = *reinterpret_cast<const v4f *>(B + (raw_a ^ (unsigned)(i << 4)));
+            V2_BEHIND(s.x); V2_BEHIND(s.y);
+        }
 #pragma unroll
         for (int i = 0; i < 8; i++) {
-            xr[i] = *reinterpret_cast<const v4f *>(B + (raw_a ^ (unsigned)(i << 4)));
+            if (!ONE) xr[i] = *reinterpret_cast<const v4f *>(B + (raw_a ^ (unsigned)(i << 4)));
             if (V2_ABLATE & 32) { s.x += xr[i].x; continue; }
             s = make_float2(fmaf(s.x, be, xr[i].x), fmaf(s.y, be, xr[i].y));
             s = make_float2(fmaf(s.x, be, xr[i].z), fmaf(s.y, be, xr[i].w));
@@ -481,20 +502,23 @@ __global__ __launch_bounds__(256, (FM && G == 1) ? V2_ONE_WGS : 2) void k_run256
         if (b + 1 == A.nb) {                            // the stream's last 13 frames of y
             float2 *yo = (ONE ? kernarg_ptr_s<offsetof(V2Args, r.t.yhist_out)>() : A.yhist_out) + (ONE ? tid_t : j);
 #pragma unroll
-            for (int f = 3; f < NB; f++) yo[(f - 3) * M256] = nw[f];
+            for (int f = 3; f < NB; f++) { if (ONE) store_global(yo + (f - 3) * M256, nw[f]); else yo[(f - 3) * M256] = nw[f]; }
         }
+        // ONE: the taps come out of the LDS table (written once, in front of the loop) for the pre-mix and the FIR only: read here, in front
+        // of the pre-mix, they arrive under its 16 complex products
+        float ht[P];
+#pragma unroll
+        for (int n = 0; n < P; n++) ht[n] = ONE ? TP[M256 * n + j] : h[n];
 #pragma unroll
         for (int f = 0; f < NB; f += 2) {
             v2f a0 = to_v(nw[f]), a1 = to_v(nw[f + 1]);
+            if (ONE) { V2_BEHIND(a0); V2_BEHIND(a1); }
             cmul2_v(a0, Wav, a1, Wbv);
             nw[f] = to_f2(a0); nw[f + 1] = to_f2(a1);
         }
         V2STAMP(4);
         // ---- polyphase FIR on the pre-mixed window, four frames at a time (independent accumulators); X goes where the
         // thread's column came from
-        float ht[P];                                    // ONE: the taps come out of the LDS table for the FIR only
-#pragma unroll
-        for (int n = 0; n < P; n++) ht[n] = ONE ? TP[M256 * n + j] : h[n];
 #pragma unroll
         for (int f0 = 0; f0 < NB; f0 += 4) {
             v2f acc[4] = {{0.f, 0.f}, {0.f, 0.f}, {0.f, 0.f}, {0.f, 0.f}};
@@ -638,8 +662,13 @@ __global__ __launch_bounds__(256, (FM && G == 1) ? V2_ONE_WGS : 2) void k_run256
             // does not have -- the asm stores below rely on a kernel without SGPR spills)
             const int k1s = ONE ? tid_t >> 4 : k1, f2s = ONE ? tid_t & 15 : f2;
             float2 *sd = kernarg_ptr_s<offsetof(V2Args, r.side)>() + ((size_t)w * 4) * DCFIX_F + 1 + 16 * (size_t)(b - first) + f2s;
-            if (k1s >= 14) sd[(k1s - 14) * DCFIX_F] = to_f2(vv[13]);
-            else if (k1s <= 1) sd[(2 + k1s) * DCFIX_F] = to_f2(vv[2]);
+            if (ONE) {
+                if (k1s >= 14) store_global(sd + (k1s - 14) * DCFIX_F, to_f2(vv[13]));
+                else if (k1s <= 1) store_global(sd + (2 + k1s) * DCFIX_F, to_f2(vv[2]));
+            } else {
+                if (k1s >= 14) sd[(k1s - 14) * DCFIX_F] = to_f2(vv[13]);
+                else if (k1s <= 1) sd[(2 + k1s) * DCFIX_F] = to_f2(vv[2]);
+            }
         }
         // ---- tail
         char *obase = reinterpret_cast<char *>(A.out) + (size_t)b * RA.tile_step;
