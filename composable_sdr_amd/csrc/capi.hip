@@ -1,13 +1,15 @@
 // C ABI of libcsdr_hip.so (see include/csdr.h): the route table and the chain handle (the plan of its route, the tails behind
-// it, stream state and the per-chunk call sequence).  The handles of the single blocks are in capi_blocks.hip.  Product code: no CPU fallback,
+// it (chain_tails.h), stream state and the per-chunk call sequence).  The handles of the single blocks are in capi_blocks.hip.  Product code: no CPU fallback,
 // nothing from oracle/.
 #include "../../include/csdr.h"
 #include "capi_internal.h"
+#include "chain_tails.h"
 #include "fused.h"
 
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <memory>
 #include <new>
 
 namespace csdr {
@@ -16,25 +18,36 @@ const char *last_error();
 using namespace csdr;
 
 struct csdr_chain {
+    // what mem and the members' own destructors do not release (block_destroy: the device is selected and idle)
+    ~csdr_chain()
+    {
+        delete plan;
+        timer.destroy();
+        for (hipStream_t st : {s_in, s_k, s_out}) if (st) (void)hipStreamDestroy(st);
+        if (e_user) (void)hipEventDestroy(e_user);
+    }
     csdr_chain_cfg cfg;
-    int device;
-    uint32_t M, p, C, c0, max_nf; uint64_t max_nx;
+    int device = -1;
+    uint32_t M = 0, p = 0, C = 0, c0 = 0, max_nf = 0; uint64_t max_nx = 0;
+    uint32_t G = 1;                  // chan_stride: interleaved shard g = c0 of G
     std::string path;
     // design
     std::vector<float> taps;
     uint32_t theta = 0, d_theta = 0;
-    DcParams dc; AgcParams agc; float fm_ref = 0.f;
-    // device memory (mem frees every buffer below with the handle)
-    DeviceBuffers mem;
-    uint32_t G = 1;                  // chan_stride: interleaved shard g = c0 of G
-    bool dft_backward = false;       // CSDR_FLAG_DFT_BACKWARD: rows leave through d_perm and a row permutation k -> (M - k) mod M
-    void *d_perm = nullptr;
-    float2 *d_A = nullptr, *d_B = nullptr;     // AGC on: Z, the channel-major CF32 plane between the plan and the tail; the tail's output in front of --mix
-    size_t a_guard = 0;              // fused chain with the AGC tail: d_A has this many readable elements in front of and behind the plane (tile-major route)
-    AgcState *d_agc = nullptr;
-    float2 *d_rp[2] = {nullptr, nullptr}; int rp_cur = 0;
+    DeviceBuffers mem;               // the handle's device memory, the tails' and the slots' included
+    ChainPlan *plan = nullptr;       // the route's plan (fused.h); null: CSDR_FLAG_TAIL_ONLY, the caller's rows are the front
+    std::unique_ptr<AgcTail> agc;    // AGC on
+    std::unique_ptr<AmTail> am;
+    std::unique_ptr<WbfmTail> wbfm;
+    std::unique_ptr<RowReversal> backward;
+    KernelTimer timer;
     // host-API staging: CSDR_CHAIN_INFLIGHT slots (device in / out, page-locked host in / out), three streams
     struct HostSlot {
+        ~HostSlot()
+        {
+            for (void *q : {h_in, h_out}) if (q) (void)hipHostFree(q);
+            for (hipEvent_t e : {e_in, e_k, e_out}) if (e) (void)hipEventDestroy(e);
+        }
         float2 *d_in = nullptr; void *d_out = nullptr; void *h_in = nullptr, *h_out = nullptr;
         hipEvent_t e_in = nullptr, e_k = nullptr, e_out = nullptr;
         void *user_out = nullptr; uint32_t n_out = 0; size_t out_bytes = 0; bool staged_out = false;
@@ -42,33 +55,39 @@ struct csdr_chain {
     HostSlot slot[CSDR_CHAIN_INFLIGHT];
     hipStream_t s_in = nullptr, s_k = nullptr, s_out = nullptr;
     uint32_t q_head = 0, q_count = 0;      // oldest pending slot, number of pending chunks
-    ChainPlan *plan = nullptr;       // the route's plan (fused.h); null: CSDR_FLAG_TAIL_ONLY, the caller's rows are the front
-    uint32_t n_cus = 256;            // compute units of the device (run counts of k_pfb1024 and of the plans: FusedConfig::cus)
-    AgcTailPlan *agc_tail = nullptr; // AGC on: time-parallel verified tail (unless CSDR_FLAG_AGC_SEQUENTIAL)
-    // DeAM: the chain runs as DeNo into d_amz, then the ampmodem peak detector (kernels_am.hip) [+ mix]
-    bool tail_only = false;          // CSDR_FLAG_TAIL_ONLY: AGC [+ freqdem] [+ mix] on a channel-major CF32 plane
-    bool am = false, am_mix = false;
-    // DeWBFM: the chain runs as DeNBFM 0.6 into d_wbf, then de-emphasis + decimator (kernels_wbfm.hip) [+ mix]
-    bool wbfm = false, wbfm_mix = false; uint32_t wb_decim = 4, wb_hlen = 0; BiquadParams wb_bq{};
-    float *d_wbf = nullptr, *d_wbo = nullptr, *d_wbh = nullptr, *d_wbhist[2] = {nullptr, nullptr}; float2 *d_wbst[2] = {nullptr, nullptr}; int wb_cur = 0;
-    float2 *d_amz = nullptr; float *d_amf = nullptr; float *d_amq[2] = {nullptr, nullptr}; int amq_cur = 0;
-    KernelTimer timer;
-    // pipelined device entry point (csdr_chain_submit_device): two handle-owned streams used alternately, so that consecutive
-    // chunks' launches may overlap (the next launch's cold run starts fill the CUs the previous one has already left)
-    hipStream_t s_pd[2] = {nullptr, nullptr};
-    hipEvent_t e_pd_done[2] = {nullptr, nullptr}, e_pd_tail[3] = {nullptr, nullptr, nullptr}, e_serial = nullptr;
-    bool pd_used[2] = {false, false}, pd_tail_rec = false, serial_pending = false, in_submit = false;
-    uint32_t pd_count = 0, pd_indep_calls = 0;
-    bool call_indep = false; hipEvent_t call_ev_tail = nullptr;     // handed to the plan by the call in progress
+    // pipelined device entry point (csdr_chain_submit_device; made by its first call): two handle-owned streams used alternately, so
+    // that consecutive chunks' launches may overlap (the next launch's cold run starts fill the CUs the previous one has already left)
+    struct Pipelined {
+        ~Pipelined()
+        {
+            for (hipStream_t q : s) if (q) (void)hipStreamDestroy(q);
+            for (hipEvent_t e : {e_done[0], e_done[1], e_tail[0], e_tail[1], e_tail[2], e_serial}) if (e) (void)hipEventDestroy(e);
+        }
+        int open()
+        {
+            bool ok = true;
+            for (hipStream_t &q : s) ok = ok && hipStreamCreateWithFlags(&q, hipStreamNonBlocking) == hipSuccess;
+            for (hipEvent_t *e : {&e_done[0], &e_done[1], &e_tail[0], &e_tail[1], &e_tail[2], &e_serial})
+                ok = ok && hipEventCreateWithFlags(e, hipEventDisableTiming) == hipSuccess;
+            if (ok) return CSDR_OK;
+            (void)hipGetLastError();
+            set_error("chain: cannot create the streams / events of the pipelined entry point");
+            return CSDR_ERR_HIP;
+        }
+        void reset() { used[0] = used[1] = tail_rec = serial_pending = last_indep = false; count = 0; }     // chunks in flight are abandoned
+        hipStream_t s[2] = {nullptr, nullptr};
+        hipEvent_t e_done[2] = {nullptr, nullptr}, e_tail[3] = {nullptr, nullptr, nullptr}, e_serial = nullptr;
+        bool used[2] = {false, false}, tail_rec = false, serial_pending = false;
+        bool last_indep = false;         // the previous csdr_chain_submit_device call ran as an independent launch
+        uint32_t count = 0, indep_calls = 0;
+    };
+    std::unique_ptr<Pipelined> pd;
     // entry points share the handle's state: a call on a caller's stream is remembered so that the host-buffer entry point
     // (own stream s_k) can order itself behind it, and the other way round
     // (a handle-owned event recorded on the caller's stream behind the call's work: the caller may destroy the stream afterwards)
     hipEvent_t e_user = nullptr; bool user_stream_dirty = false;
-    bool pd_last_indep = false;      // the previous csdr_chain_submit_device call ran as an independent launch
 };
-
-// a device buffer of the chain: n elements of T (at least one), freed with the handle
-template <class T> static int chain_alloc(csdr_chain *h, T **p, size_t n) { return h->mem.alloc_n(p, n); }
+using HostSlot = csdr_chain::HostSlot;
 
 extern "C" {
 
@@ -190,231 +209,137 @@ void csdr_chain_cfg_default(csdr_chain_cfg *cfg, uint32_t channels)
 
 static int chain_init_state(csdr_chain *h, hipStream_t s)
 {
-    h->theta = 0; h->rp_cur = 0;
-    if (h->d_agc) { int r = launch_agc_init(h->d_agc, h->C, s); if (r) return r; }
-    if (h->agc_tail) agc_tail_reset(h->agc_tail);
-    if (h->d_rp[0]) {
-        CSDR_HIP(hipMemsetAsync(h->d_rp[0], 0, sizeof(float2) * h->C, s));
-        CSDR_HIP(hipMemsetAsync(h->d_rp[1], 0, sizeof(float2) * h->C, s));
-    }
-    if (h->d_wbst[0]) {
-        h->wb_cur = 0;
-        for (int i = 0; i < 2; i++) {
-            CSDR_HIP(hipMemsetAsync(h->d_wbst[i], 0, sizeof(float2) * h->C, s));
-            CSDR_HIP(hipMemsetAsync(h->d_wbhist[i], 0, sizeof(float) * (size_t)h->C * (h->wb_hlen - 1), s));
-        }
-    }
-    if (h->d_amq[0]) {
-        h->amq_cur = 0;
-        CSDR_HIP(hipMemsetAsync(h->d_amq[0], 0, sizeof(float) * h->C, s));     // ampmodem_reset: q_hat = 0
-        CSDR_HIP(hipMemsetAsync(h->d_amq[1], 0, sizeof(float) * h->C, s));
-    }
+    h->theta = 0;
+    int r;
+    if (h->agc && (r = h->agc->reset(s))) return r;
+    if (h->am && (r = h->am->reset(s))) return r;
+    if (h->wbfm && (r = h->wbfm->reset(s))) return r;
     return h->plan ? h->plan->reset(s) : 0;
 }
 
+// argument checks -> device -> handle -> design -> front (the route's plan; CSDR_FLAG_TAIL_ONLY: none) -> tails -> state -> print
 int csdr_chain_create(const csdr_chain_cfg *cfg_in, csdr_chain **out)
 {
     if (!cfg_in || !out) { set_error("chain: null argument"); return CSDR_ERR_INVALID; }
     if (cfg_in->struct_size != sizeof(csdr_chain_cfg)) { set_error("chain: cfg.struct_size %u != %zu", cfg_in->struct_size, sizeof(csdr_chain_cfg)); return CSDR_ERR_INVALID; }
     if (cfg_in->demod > CSDR_DEMOD_WBFM) { set_error("chain: unknown demod %u", cfg_in->demod); return CSDR_ERR_INVALID; }
     // DeAM = amDemodulator . agc (SoapySDR.hs:265-272): everything up to the per-channel CF32 samples is the DeNo
-    // chain; the peak detector and the mix follow as a tail (see csdr_chain_process_device)
+    // chain; the peak detector and the mix follow as a tail (AmTail)
     csdr_chain_cfg eff = *cfg_in;
-    const bool am = cfg_in->demod == CSDR_DEMOD_AM, am_mix = am && cfg_in->mix != 0 && cfg_in->channels > 1;
+    const bool am = cfg_in->demod == CSDR_DEMOD_AM, wbfm = cfg_in->demod == CSDR_DEMOD_WBFM, tail_mix = cfg_in->mix != 0 && cfg_in->channels > 1;
     if (am) { eff.demod = CSDR_DEMOD_NONE; eff.mix = 0; }
     // DeWBFM decim = firDecimator decim . iirDeemph . fmDemodulator 0.6 . agc (SoapySDR.hs:252-259, Liquid.chs:653-656)
-    const bool wbfm = cfg_in->demod == CSDR_DEMOD_WBFM, wbfm_mix = wbfm && cfg_in->mix != 0 && cfg_in->channels > 1;
     if (wbfm) { eff.demod = CSDR_DEMOD_FM; eff.kf = 0.6f; eff.mix = 0; }
     const csdr_chain_cfg *cfg = &eff;
     if (cfg->channels < 1 || cfg->channels > (1u << 16)) { set_error("chain: channels %u out of range", cfg->channels); return CSDR_ERR_INVALID; }
-    if (cfg_in->flags & CSDR_FLAG_TAIL_ONLY) {
-        // the per-channel tail alone (hybrid multi-GPU partition): rows in, rows out; state = AGC {g, y2', mode, timer} + freqdem r' per row
-        if (cfg_in->agc_threshold_db == 0.0f || am || wbfm) { set_error("chain: CSDR_FLAG_TAIL_ONLY needs the AGC on (-a != 0) and demod none / FM (without the AGC a time stripe needs no tail shard)"); return CSDR_ERR_INVALID; }
-        if (cfg->demod == CSDR_DEMOD_FM && !(cfg->kf > 0.f)) { set_error("chain: FM needs kf > 0"); return CSDR_ERR_INVALID; }
-        int dev; int r = check_device(cfg->device, &dev); if (r) return r;
-        DevGuard guard(dev);
-        if (!guard.ok) { set_error("chain: cannot select device %d", dev); return CSDR_ERR_HIP; }
-        csdr_chain *h = new (std::nothrow) csdr_chain();
-        if (!h) return CSDR_ERR_NOMEM;
-        h->cfg = *cfg; h->cfg.chan_first = 0; h->cfg.chan_count = 0; h->cfg.chan_stride = 0; h->cfg.dc_block = 0;
-        h->device = dev; h->tail_only = true;
-        h->M = cfg->channels; h->C = cfg->channels; h->c0 = 0; h->G = 1; h->p = 0;
-        h->max_nf = cfg->max_frames ? cfg->max_frames : 4096;
-        h->max_nx = (uint64_t)h->max_nf * h->M;
-        if (h->max_nx > 0xffffffffull) { set_error("chain: max_frames*channels exceeds 2^32-1 samples"); delete h; return CSDR_ERR_INVALID; }
-        h->agc = make_agc(cfg->agc_threshold_db);
-        if (cfg->demod == CSDR_DEMOD_FM) h->fm_ref = fm_ref_of(cfg->kf);
-        auto failt = [&](int code) { csdr_chain_destroy(h); return code; };
-        if ((r = chain_alloc(h, &h->d_agc, h->C))) return failt(r);
-        if (cfg->demod == CSDR_DEMOD_FM && ((r = chain_alloc(h, &h->d_rp[0], h->C)) || (r = chain_alloc(h, &h->d_rp[1], h->C)))) return failt(r);
-        if (cfg->mix && h->C > 1 && (r = chain_alloc(h, &h->d_B, (size_t)h->C * h->max_nf))) return failt(r);
-        if (!(cfg->flags & CSDR_FLAG_AGC_SEQUENTIAL)) { if ((r = agc_tail_create(h->C, h->max_nf, &h->agc_tail))) return failt(r); }
-        else if ((r = chain_alloc(h, &h->d_A, (size_t)h->C * h->max_nf))) return failt(r);        // the one-lane-per-channel kernel works in place
-        h->path = std::string("tail-only+agc") + (h->agc_tail ? "-spec" : "");
-        if ((r = chain_init_state(h, nullptr))) return failt(r);
-        CSDR_HIP_CLEAN(hipDeviceSynchronize(), csdr_chain_destroy(h));
-        if (!(cfg->flags & CSDR_FLAG_QUIET)) {
-            printf("csdr chain [%s] on HIP device %d: %u channel rows, agc=%g dB demod=%s kf=%g mix=%u\n", h->path.c_str(), dev, h->C,
-                   cfg->agc_threshold_db, cfg->demod == CSDR_DEMOD_FM ? "FM" : "none", cfg->kf, cfg->mix);
-            fflush(stdout);
-        }
-        *out = h;
-        return CSDR_OK;
-    }
+    // CSDR_FLAG_TAIL_ONLY: the per-channel tail alone (hybrid multi-GPU partition): rows in, rows out, no plan
+    const bool tail_only = (cfg_in->flags & CSDR_FLAG_TAIL_ONLY) != 0, agc_on = cfg->agc_threshold_db != 0.0f;
+    if (tail_only && (!agc_on || am || wbfm)) { set_error("chain: CSDR_FLAG_TAIL_ONLY needs the AGC on (-a != 0) and demod none / FM (without the AGC a time stripe needs no tail shard)"); return CSDR_ERR_INVALID; }
     if (cfg->demod == CSDR_DEMOD_FM && !(cfg->kf > 0.f)) { set_error("chain: FM needs kf > 0"); return CSDR_ERR_INVALID; }
-    if (cfg->dc_block && !(cfg->dc_alpha > 0.f && cfg->dc_alpha < 1.f)) { set_error("chain: dc_alpha out of (0,1)"); return CSDR_ERR_INVALID; }
-    if (cfg->pfb_m > 32u) { set_error("chain: pfb_m %u out of 1..32 (0 = 7)", cfg->pfb_m); return CSDR_ERR_INVALID; }
-    const uint32_t M = cfg->channels;
-    uint32_t c0 = cfg->chan_first, C = cfg->chan_count ? cfg->chan_count : M - c0;
-    const uint32_t G = cfg->chan_stride > 1 ? cfg->chan_stride : 1;
-    if (G > 1) {
-        if (M % G || c0 >= G || (cfg->chan_count && cfg->chan_count != M / G)) {
-            set_error("chain: interleaved shard %u of %u needs chan_stride | channels (%u), chan_first < chan_stride, chan_count 0 or channels/chan_stride", c0, G, M);
-            return CSDR_ERR_INVALID;
-        }
-        C = M / G;
-    } else if (c0 >= M || C == 0 || c0 + C > M) { set_error("chain: channel shard [%u,+%u) outside 0..%u", c0, C, M); return CSDR_ERR_INVALID; }
-    int dev; int r = check_device(cfg->device, &dev); if (r) return r;
-    DevGuard guard(dev);
-    if (!guard.ok) { set_error("chain: cannot select device %d", dev); return CSDR_ERR_HIP; }
+    const uint32_t M = cfg->channels, G = !tail_only && cfg->chan_stride > 1 ? cfg->chan_stride : 1;
+    uint32_t c0 = 0, C = M;
+    if (tail_only) { eff.chan_first = 0; eff.chan_count = 0; eff.chan_stride = 0; eff.dc_block = 0; }
+    else {
+        if (cfg->dc_block && !(cfg->dc_alpha > 0.f && cfg->dc_alpha < 1.f)) { set_error("chain: dc_alpha out of (0,1)"); return CSDR_ERR_INVALID; }
+        if (cfg->pfb_m > 32u) { set_error("chain: pfb_m %u out of 1..32 (0 = 7)", cfg->pfb_m); return CSDR_ERR_INVALID; }
+        c0 = cfg->chan_first; C = cfg->chan_count ? cfg->chan_count : M - c0;
+        if (G > 1) {
+            if (M % G || c0 >= G || (cfg->chan_count && cfg->chan_count != M / G)) {
+                set_error("chain: interleaved shard %u of %u needs chan_stride | channels (%u), chan_first < chan_stride, chan_count 0 or channels/chan_stride", c0, G, M);
+                return CSDR_ERR_INVALID;
+            }
+            C = M / G;
+        } else if (c0 >= M || C == 0 || c0 + C > M) { set_error("chain: channel shard [%u,+%u) outside 0..%u", c0, C, M); return CSDR_ERR_INVALID; }
+    }
+    NewBlock<csdr_chain> nb;
+    int r = nb.open(cfg->device); if (r) return r;
+    csdr_chain *h = nb.get();
+    DevGuard guard(h->device);
+    if (!guard.ok) { set_error("chain: cannot select device %d", h->device); return CSDR_ERR_HIP; }
 
-    csdr_chain *h = new (std::nothrow) csdr_chain();
-    if (!h) return CSDR_ERR_NOMEM;
-    h->cfg = *cfg; h->device = dev; h->M = M; h->C = C; h->c0 = c0; h->G = G;
-    { int cus = 256; (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev); h->n_cus = (uint32_t)cus; }
     const uint32_t m = cfg->pfb_m ? cfg->pfb_m : 7;
     const float As = cfg->pfb_as > 0.f ? cfg->pfb_as : 80.0f;
-    h->p = 2 * m;
+    h->cfg = *cfg; h->M = M; h->C = C; h->c0 = c0; h->G = G; h->p = tail_only ? 0 : 2 * m;
     h->max_nf = cfg->max_frames ? cfg->max_frames : 4096;
     h->max_nx = (uint64_t)h->max_nf * M;
-    if (h->max_nx > 0xffffffffull) { set_error("chain: max_frames*channels exceeds 2^32-1 samples"); delete h; return CSDR_ERR_INVALID; }
-    h->timer.enabled = (cfg->flags & (CSDR_FLAG_TIME_KERNELS | CSDR_FLAG_TIME_REGION)) != 0;
-    h->timer.region = (cfg->flags & CSDR_FLAG_TIME_REGION) != 0;
-    if (cfg->dc_block) h->dc = make_dc(cfg->dc_alpha);
-    if (cfg->agc_threshold_db != 0.0f) h->agc = make_agc(cfg->agc_threshold_db);
-    if (cfg->demod == CSDR_DEMOD_FM) h->fm_ref = fm_ref_of(cfg->kf);
+    if (h->max_nx > 0xffffffffull) { set_error("chain: max_frames*channels exceeds 2^32-1 samples"); return CSDR_ERR_INVALID; }
 
-    auto fail = [&](int code) { csdr_chain_destroy(h); return code; };
-    if (M > 1) {
-        h->taps = design_pfb_taps(M, m, As);
-        h->d_theta = nco_freq_word(pfb_premix_freq(M));
-    }
-    if (cfg->agc_threshold_db != 0.0f && (r = chain_alloc(h, &h->d_agc, C))) return fail(r);
-    // (without the AGC the plan does the freqdem and keeps its history)
-    if (cfg->agc_threshold_db != 0.0f && cfg->demod == CSDR_DEMOD_FM && ((r = chain_alloc(h, &h->d_rp[0], C)) || (r = chain_alloc(h, &h->d_rp[1], C)))) return fail(r);
-
-    // Path selection.  With the AGC on, the plan stops at the channel-major CF32 samples and the per-channel AGC tail (time-parallel, or
+    // Front.  With the AGC on, the plan stops at the channel-major CF32 samples and the per-channel AGC tail (time-parallel, or
     // with CSDR_FLAG_AGC_SEQUENTIAL one lane per channel) + freqdem + mix follow.
-    // interleaved shards: the fused M = 256 and 1024 chains take strides 2, 4, 8; every other shape the any-M route with a pruned DFT
-    const DcParams *dcp = cfg->dc_block ? &h->dc : nullptr;
-    const RouteRow *route = route_select(M, h->p, G, cfg->flags, dcp);     // the one place a configuration is mapped to a plan (table above)
-    if (route->M == 4096 && (C != M || (cfg->mix && cfg->demod == CSDR_DEMOD_NONE && cfg->agc_threshold_db == 0.0f && !am)))
-        route = route_select(M, h->p, G, cfg->flags | CSDR_FLAG_FORCE_GENERIC, dcp);   // contiguous shards; DeNo --mix over all channels (= M x branch 0: nothing beats not computing
-                                                                                   // the bank; CSDR_FLAG_NO_MIX_IDENTITY's full bank + DFT + sum stays on the any-M kernels too)
-    const bool agc_on = cfg->agc_threshold_db != 0.0f;
-    FusedConfig fc{};
-    fc.M = M; fc.p = h->p; fc.C = C; fc.c0 = c0; fc.max_nf = h->max_nf; fc.G = G;
-    fc.dc_block = cfg->dc_block != 0; fc.dc = h->dc;
-    fc.fm = cfg->demod == CSDR_DEMOD_FM && !agc_on; fc.fm_ref = h->fm_ref;
-    fc.mix = cfg->mix != 0 && !agc_on; fc.taps = h->taps.data(); fc.d_theta = h->d_theta; fc.cus = h->n_cus;
-    fc.no_mix_identity = (cfg->flags & CSDR_FLAG_NO_MIX_IDENTITY) != 0;
-    if ((r = route->create(fc, &h->plan))) return fail(r);
-    const std::string front = h->plan->route(route->path_prefix, agc_on);
-    h->path = front;
-    if (agc_on) {
-        // d_A: channel-major CF32 from the plan; d_B: per-channel tail output in front of --mix
-        // (the fused plans may write d_A tile-major for k_agc_spec_tm, which reads up to a segment in front of / behind the plane)
-        // The guards (2 x 64 KiB per channel: 128 MiB at 1024 channels) exist only where a call can take that route: a fused plan (the any-M
-        // plan never writes tile-major), a time-parallel tail (not CSDR_FLAG_AGC_SEQUENTIAL), a channel count k_agc_spec_tm takes, calls
-        // of >= 4 W = 4096 frames
-        const bool tm_possible = route->M && !(cfg->flags & CSDR_FLAG_AGC_SEQUENTIAL) && h->max_nf >= 4096u &&
-                                 (C % 64u == 0 || (C < 64u && 64u % C == 0));
-        h->a_guard = tm_possible ? agc_tail_tm_guard(C) : 0;
-        if ((r = chain_alloc(h, &h->d_A, (size_t)C * h->max_nf + 2 * h->a_guard))) return fail(r);
-        if (h->a_guard) {
-            // only the guards need defined contents (the warm-ups of the first and last segments read them, masked by position)
-            CSDR_HIP_CLEAN(hipMemset(h->d_A, 0, sizeof(float2) * h->a_guard), csdr_chain_destroy(h));
-            CSDR_HIP_CLEAN(hipMemset(h->d_A + h->a_guard + (size_t)C * h->max_nf, 0, sizeof(float2) * h->a_guard), csdr_chain_destroy(h));
+    const RouteRow *route = nullptr;
+    std::string front = "tail-only+agc";
+    if (!tail_only) {
+        int cus = 256;               // compute units of the device (run counts of k_pfb1024 and of the plans: FusedConfig::cus)
+        (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device);
+        h->timer.enabled = (cfg->flags & (CSDR_FLAG_TIME_KERNELS | CSDR_FLAG_TIME_REGION)) != 0;
+        h->timer.region = (cfg->flags & CSDR_FLAG_TIME_REGION) != 0;
+        DcParams dc{};
+        if (cfg->dc_block) dc = make_dc(cfg->dc_alpha);
+        if (M > 1) {
+            h->taps = design_pfb_taps(M, m, As);
+            h->d_theta = nco_freq_word(pfb_premix_freq(M));
         }
-        if (cfg->mix && (r = chain_alloc(h, &h->d_B, (size_t)C * h->max_nf))) return fail(r);
+        // interleaved shards: the fused M = 256 and 1024 chains take strides 2, 4, 8; every other shape the any-M route with a pruned DFT
+        const DcParams *dcp = cfg->dc_block ? &dc : nullptr;
+        route = route_select(M, h->p, G, cfg->flags, dcp);     // the one place a configuration is mapped to a plan (table above)
+        if (route->M == 4096 && (C != M || (cfg->mix && cfg->demod == CSDR_DEMOD_NONE && !agc_on && !am)))
+            route = route_select(M, h->p, G, cfg->flags | CSDR_FLAG_FORCE_GENERIC, dcp);   // contiguous shards; DeNo --mix over all channels (= M x branch 0: nothing beats not computing
+                                                                                       // the bank; CSDR_FLAG_NO_MIX_IDENTITY's full bank + DFT + sum stays on the any-M kernels too)
+        FusedConfig fc{};
+        fc.M = M; fc.p = h->p; fc.C = C; fc.c0 = c0; fc.max_nf = h->max_nf; fc.G = G;
+        fc.dc_block = cfg->dc_block != 0; fc.dc = dc;
+        fc.fm = cfg->demod == CSDR_DEMOD_FM && !agc_on; fc.fm_ref = cfg->demod == CSDR_DEMOD_FM ? fm_ref_of(cfg->kf) : 0.f;     // (with the AGC on its tail does the freqdem)
+        fc.mix = cfg->mix != 0 && !agc_on; fc.taps = h->taps.data(); fc.d_theta = h->d_theta; fc.cus = (uint32_t)cus;
+        fc.no_mix_identity = (cfg->flags & CSDR_FLAG_NO_MIX_IDENTITY) != 0;
+        if ((r = route->create(fc, &h->plan))) return r;
+        front = h->plan->route(route->path_prefix, agc_on);
     }
-    if ((cfg_in->flags & CSDR_FLAG_DFT_BACKWARD) && M > 1 && !(cfg_in->mix != 0)) {
-        if (C != M || G > 1) { set_error("chain: CSDR_FLAG_DFT_BACKWARD is built for whole-band handles (no channel shard)"); return fail(CSDR_ERR_INVALID); }
-        h->dft_backward = true;
-        if ((r = h->mem.alloc(&h->d_perm, (size_t)C * h->max_nf * ((cfg_in->demod == CSDR_DEMOD_NONE) ? 8u : 4u)))) return fail(r);
-        h->path += "+dft-backward";
+    h->path = front;
+
+    // Tails (the order of their checks is part of the C ABI; the AGC tail's piece of the path comes last)
+    const bool fused = route && route->M;
+    if (agc_on) {
+        h->agc = std::make_unique<AgcTail>();
+        if ((r = h->agc->setup(h->mem, *cfg, C, h->max_nf, !tail_only, fused))) return r;
+    }
+    if (!tail_only && (cfg_in->flags & CSDR_FLAG_DFT_BACKWARD) && M > 1 && !(cfg_in->mix != 0)) {
+        if (C != M || G > 1) { set_error("chain: CSDR_FLAG_DFT_BACKWARD is built for whole-band handles (no channel shard)"); return CSDR_ERR_INVALID; }
+        h->backward = std::make_unique<RowReversal>();
+        if ((r = h->backward->setup(h->mem, C, h->max_nf, cfg_in->demod == CSDR_DEMOD_NONE ? 8u : 4u, h->path))) return r;
     }
     if (am) {
-        h->am = true; h->am_mix = am_mix;
-        if ((r = chain_alloc(h, &h->d_amz, (size_t)C * h->max_nf))) return fail(r);
-        if (am_mix && (r = chain_alloc(h, &h->d_amf, (size_t)C * h->max_nf))) return fail(r);
-        if ((r = chain_alloc(h, &h->d_amq[0], C)) || (r = chain_alloc(h, &h->d_amq[1], C))) return fail(r);
-        h->path += "+am";
+        h->am = std::make_unique<AmTail>();
+        if ((r = h->am->setup(h->mem, C, h->max_nf, tail_mix, h->path))) return r;
     }
     if (wbfm) {
-        h->wbfm = true; h->wbfm_mix = wbfm_mix;
-        h->wb_decim = cfg_in->wbfm_decim ? cfg_in->wbfm_decim : 4u;
-        const float fc = cfg_in->deemph_fc > 0.f ? cfg_in->deemph_fc : 0.025f;
-        if (!(fc < 0.5f)) { set_error("chain: deemph_fc %g out of (0, 0.5)", fc); return fail(CSDR_ERR_INVALID); }
-        h->wb_bq = design_butter2_lowpass(fc);
-        const std::vector<float> taps = design_firdecim_kaiser(h->wb_decim, 10, 60.0f);
-        h->wb_hlen = (uint32_t)taps.size();
-        const size_t rows = (size_t)C * h->max_nf, hist = (size_t)C * (h->wb_hlen - 1);
-        if (chain_alloc(h, &h->d_wbf, rows) || chain_alloc(h, &h->d_wbh, taps.size()) || chain_alloc(h, &h->d_wbhist[0], hist) || chain_alloc(h, &h->d_wbhist[1], hist) ||
-            chain_alloc(h, &h->d_wbst[0], C) || chain_alloc(h, &h->d_wbst[1], C) || (wbfm_mix && chain_alloc(h, &h->d_wbo, rows))) {
-            set_error("chain: WBFM tail allocation failed"); return fail(CSDR_ERR_HIP);
-        }
-        CSDR_HIP_CLEAN(hipMemcpy(h->d_wbh, taps.data(), sizeof(float) * taps.size(), hipMemcpyHostToDevice), csdr_chain_destroy(h));
-        h->path += "+wbfm";
+        h->wbfm = std::make_unique<WbfmTail>();
+        if ((r = h->wbfm->setup(h->mem, *cfg_in, C, h->max_nf, tail_mix, h->path))) return r;
     }
-    if (h->d_agc && !(cfg->flags & CSDR_FLAG_AGC_SEQUENTIAL)) {
-        if ((r = agc_tail_create(C, h->max_nf, &h->agc_tail))) return fail(r);
-        h->path += route->M ? "-spec" : "+agc-spec";      // (a fused row's text already says +agc)
-    }
-    if ((r = chain_init_state(h, nullptr))) return fail(r);
-    CSDR_HIP_CLEAN(hipDeviceSynchronize(), csdr_chain_destroy(h));
+    if (h->agc) h->path += h->agc->path_piece();
+    if ((r = chain_init_state(h, nullptr))) return r;
+    CSDR_HIP(hipDeviceSynchronize());
 
     if (!(cfg->flags & CSDR_FLAG_QUIET)) {
+        const char *demod = am ? "AM" : (wbfm ? "WBFM" : (cfg->demod == CSDR_DEMOD_FM ? "FM" : "none"));
         // what the reference prints at create (Liquid.chs:577-579, 814-820, 714-716, 319-321)
-        printf("csdr chain [%s] on HIP device %d: channels=%u (shard %u..%u) taps=%u (m=%u, As=%.1f) "
-               "nco.d_theta=0x%08x dc_block=%u(alpha=%g) agc=%g dB demod=%s kf=%g mix=%u\n",
-               h->path.c_str(), dev, M, c0, c0 + C - 1, M > 1 ? M * h->p : 0, m, As, h->d_theta, cfg->dc_block,
-               cfg->dc_alpha, cfg->agc_threshold_db, am ? "AM" : (wbfm ? "WBFM" : (cfg->demod == CSDR_DEMOD_FM ? "FM" : "none")), cfg->kf, cfg_in->mix);
+        if (tail_only)
+            printf("csdr chain [%s] on HIP device %d: %u channel rows, agc=%g dB demod=%s kf=%g mix=%u\n", h->path.c_str(), h->device, h->C,
+                   cfg->agc_threshold_db, demod, cfg->kf, cfg->mix);
+        else
+            printf("csdr chain [%s] on HIP device %d: channels=%u (shard %u..%u) taps=%u (m=%u, As=%.1f) "
+                   "nco.d_theta=0x%08x dc_block=%u(alpha=%g) agc=%g dB demod=%s kf=%g mix=%u\n",
+                   h->path.c_str(), h->device, M, c0, c0 + C - 1, M > 1 ? M * h->p : 0, m, As, h->d_theta, cfg->dc_block,
+                   cfg->dc_alpha, cfg->agc_threshold_db, demod, cfg->kf, cfg_in->mix);
         // per-channel outputs / AGC / demod tails beyond the fused kernels' channel counts run stage by stage through HBM
-        if (!route->M && M > 1024 && front != "generic+mix-identity")
+        if (route && !route->M && M > 1024 && front != "generic+mix-identity")
             printf("csdr chain: note: %u channels with per-channel output run on the any-M route (DC blocker, FIR, DFT and tail as separate kernels, "
                    "~0.09 of the HBM roofline on MI355X); fused kernels exist for 64, 256 and 1024 channels, and for DeNo --mix over all channels of any count\n", M);
         fflush(stdout);
     }
-    *out = h;
-    return CSDR_OK;
+    return nb.publish(out);
 }
 
 uint32_t csdr_chain_out_elem_size(const csdr_chain *h) { return h && (h->cfg.demod == CSDR_DEMOD_FM || h->am || h->wbfm) ? 4u : 8u; }
-
-// Z[C][nf] (channel-major CF32) -> AGC + squelch [+ freqdem] [+ mix] -> d_out: the time-parallel tail (tm: Z tile-major), or with
-// CSDR_FLAG_AGC_SEQUENTIAL one lane per channel in place on Z
-static int chain_tail(csdr_chain *h, float2 *Z, uint32_t nf, void *d_out, hipStream_t s, bool tm)
-{
-    const bool fm = h->cfg.demod == CSDR_DEMOD_FM, mixo = h->cfg.mix && h->M > 1;
-    int r;
-    if (h->agc_tail) {
-        void *T = mixo ? (void *)h->d_B : d_out;
-        if ((r = agc_tail_process(h->agc_tail, Z, T, fm, nf, h->d_agc, h->agc, h->fm_ref,
-                                  fm ? h->d_rp[h->rp_cur] : nullptr, fm ? h->d_rp[h->rp_cur ^ 1] : nullptr, s, tm))) return r;
-        if (fm) h->rp_cur ^= 1;
-        if (mixo) return launch_mix((const float *)T, (float *)d_out, h->C, fm ? nf : 2 * nf, s);
-        return 0;
-    }
-    if ((r = launch_agc(Z, h->C, nf, h->d_agc, h->agc, s))) return r;
-    if (fm) {
-        float *F = mixo ? (float *)h->d_B : (float *)d_out;
-        if ((r = launch_fm(Z, F, h->C, nf, h->fm_ref, h->d_rp[h->rp_cur], h->d_rp[h->rp_cur ^ 1], s))) return r;
-        h->rp_cur ^= 1;
-        if (mixo) return launch_mix(F, (float *)d_out, h->C, nf, s);
-    } else if (mixo) return launch_mix((const float *)Z, (float *)d_out, h->C, 2 * nf, s);
-    return 0;
-}
 
 // The argument checks of every entry point that takes a chunk (texts and codes are part of the C ABI), then the handle's device
 static int chain_check_chunk(const csdr_chain *h, const void *in, uint32_t n_in, const void *out, DevGuard &guard)
@@ -427,71 +352,57 @@ static int chain_check_chunk(const csdr_chain *h, const void *in, uint32_t n_in,
     return CSDR_OK;
 }
 
-// One call on stream: the plan (tail-only: the caller's rows), the AGC tail, the AM or the WBFM tail, the backward handle's row
-// reversal.  Every stage writes the next stage's input, the last one d_out.
-static int chain_call(csdr_chain *h, const void *d_in, uint32_t n_in, void *d_out, uint32_t *n_out, void *stream)
+// One call on s: the plan (tail-only: the caller's rows), the AGC tail, the AM or the WBFM tail, the backward handle's row
+// reversal.  Every stage writes the next stage's input, the last one d_out.  indep, ev_tail: csdr_chain_submit_device's, for the plan
+static int chain_call(csdr_chain *h, const void *d_in, uint32_t n_in, void *d_out, uint32_t *n_out, hipStream_t s, bool indep = false,
+                      hipEvent_t ev_tail = nullptr)
 {
     // 1. checks (texts, codes and their order are part of the C ABI)
-    if (!h) { set_error("chain: null handle"); return CSDR_ERR_INVALID; }
-    const bool backward = h->dft_backward && n_in && d_out;     // (with nothing to do or nowhere to put it a backward handle answers as a forward one)
+    const bool backward = h->backward && n_in && d_out;         // (with nothing to do or nowhere to put it a backward handle answers as a forward one)
     if (n_out && !backward) *n_out = 0;                         // (a call a backward handle refuses has always left *n_out alone)
     if (n_in == 0) return CSDR_OK;
     if (!d_out) { set_error("chain: null buffer"); return CSDR_ERR_INVALID; }
-    if (h->wbfm && n_in % h->M == 0 && (n_in / h->M) % h->wb_decim) {
-        set_error("chain: %u frames per call are not a multiple of the WBFM decimation %u (firDecim's `div`, Liquid.chs:495-497)", n_in / h->M, h->wb_decim);
+    if (h->wbfm && n_in % h->M == 0 && (n_in / h->M) % h->wbfm->decim()) {
+        set_error("chain: %u frames per call are not a multiple of the WBFM decimation %u (firDecim's `div`, Liquid.chs:495-497)", n_in / h->M, h->wbfm->decim());
         return CSDR_ERR_SIZE;
     }
     DevGuard guard;
     int r;
     if ((r = chain_check_chunk(h, d_in, n_in, d_out, guard))) return r;
-    hipStream_t s = (hipStream_t)stream;
     const uint32_t nf = n_in / h->M, C = h->C;
-    const bool agc_on = h->d_agc != nullptr, fm = h->cfg.demod == CSDR_DEMOD_FM, mixo = h->cfg.mix && h->M > 1;
-    void *const last = backward ? h->d_perm : d_out;                                      // output of stage 4
-    void *const chain_out = h->wbfm ? (void *)h->d_wbf : h->am ? (void *)h->d_amz : last;   // output of stages 2 + 3
-    uint32_t n = mixo ? nf : C * nf;                                                      // elements in it
+    const bool fm = h->cfg.demod == CSDR_DEMOD_FM, mixo = h->cfg.mix && h->M > 1;
+    void *const last = backward ? h->backward->input() : d_out;                                   // output of stage 4
+    void *const chain_out = h->wbfm ? h->wbfm->input() : h->am ? h->am->input() : last;           // output of stages 2 + 3
+    uint32_t n = mixo ? nf : C * nf;                                                              // elements in it
 
     // 2. front: the route's plan writes Z: chain_out, or with the AGC on the plane its tail reads (chain_out itself where the sequential
     // AGC is the last step and works in place).  Tail-only: Z = the caller's rows (the sequential AGC works in place on a copy)
-    float2 *Z = (agc_on && (fm || mixo || h->agc_tail)) ? h->d_A + h->a_guard : (float2 *)chain_out;
+    float2 *Z;
     bool tm = false;
     if (h->plan) {
         FusedCall fcall{};
+        Z = h->agc ? h->agc->plane(chain_out) : (float2 *)chain_out;
         // time-parallel AGC tail behind a fused plan, run-sized calls of whole tiles: the plane between the two kernels is tile-major
-        tm = h->agc_tail && h->a_guard && agc_tail_tm_supported(h->agc_tail, nf) && h->plan->tile_major_ok(nf);
+        tm = h->agc && h->agc->tile_major(nf) && h->plan->tile_major_ok(nf);
         fcall.tile_major = tm;
         fcall.d_in = (const float2 *)d_in; fcall.d_out = Z; fcall.nf = nf; fcall.theta0 = h->theta;
-        fcall.indep = h->call_indep; fcall.ev_tail = h->call_ev_tail;
+        fcall.indep = indep; fcall.ev_tail = ev_tail;
         if ((r = h->plan->process(fcall, s, &h->timer))) return r;
         h->theta += n_in * h->d_theta;     // the NCO phase behind the call
-    } else if (h->agc_tail) Z = (float2 *)d_in;
-    else { Z = h->d_A; CSDR_HIP(hipMemcpyAsync(Z, d_in, sizeof(float2) * (size_t)n_in, hipMemcpyDeviceToDevice, s)); }
+    } else if (h->agc->time_parallel()) Z = (float2 *)d_in;
+    else { Z = h->agc->plane(chain_out); CSDR_HIP(hipMemcpyAsync(Z, d_in, sizeof(float2) * (size_t)n_in, hipMemcpyDeviceToDevice, s)); }
 
     // 3. AGC + squelch [+ freqdem] [+ mix]
-    if (agc_on && (r = chain_tail(h, Z, nf, chain_out, s, tm))) return r;
-    if (!h->plan && !h->agc_tail && !fm && !mixo) CSDR_HIP(hipMemcpyAsync(chain_out, Z, sizeof(float2) * (size_t)n_in, hipMemcpyDeviceToDevice, s));
+    if (h->agc && (r = h->agc->run(Z, nf, chain_out, s, tm))) return r;
+    if (!h->plan && !h->agc->time_parallel() && !fm && !mixo) CSDR_HIP(hipMemcpyAsync(chain_out, Z, sizeof(float2) * (size_t)n_in, hipMemcpyDeviceToDevice, s));
 
     // 4. DeWBFM: the chain ran as DeNBFM 0.6; de-emphasis + decimator [+ mix].  DeAM: it ran as DeNo; the ampmodem peak detector [+ mix]
-    if (h->wbfm) {
-        const uint32_t no = nf / h->wb_decim;
-        if ((r = launch_biquad(h->d_wbf, h->d_wbf, C, nf, h->wb_bq, h->d_wbst[h->wb_cur], h->d_wbst[h->wb_cur ^ 1], s))) return r;
-        float *O = h->wbfm_mix ? h->d_wbo : (float *)last;
-        if ((r = launch_firdecim(h->d_wbf, O, C, nf, h->wb_decim, h->d_wbh, h->wb_hlen, h->d_wbhist[h->wb_cur], h->d_wbhist[h->wb_cur ^ 1], s))) return r;
-        h->wb_cur ^= 1;
-        if (h->wbfm_mix && (r = launch_mix(O, (float *)last, C, no, s))) return r;
-        n = h->wbfm_mix ? no : C * no;
-    } else if (h->am) {
-        float *F = h->am_mix ? h->d_amf : (float *)last;
-        if ((r = launch_am(h->d_amz, F, C, nf, h->d_amq[h->amq_cur], h->d_amq[h->amq_cur ^ 1], 0.01f, s))) return r;
-        h->amq_cur ^= 1;
-        if (h->am_mix && (r = launch_mix(F, (float *)last, C, nf, s))) return r;
-        n = h->am_mix ? nf : C * nf;
-    }
+    if (h->wbfm && (r = h->wbfm->run(nf, last, &n, s))) return r;
+    if (h->am && (r = h->am->run(nf, last, &n, s))) return r;
     if (n_out) *n_out = n;
 
-    // 5. CSDR_FLAG_DFT_BACKWARD: the chain as built (forward DFT) went into d_perm; row k of the output = its row (M - k) mod M
-    if (backward) return launch_rows_reversed(h->d_perm, d_out, C, (size_t)(n / C) * csdr_chain_out_elem_size(h), s);
-    return CSDR_OK;
+    // 5. CSDR_FLAG_DFT_BACKWARD: the chain as built (forward DFT) went into last; row k of the output = its row (M - k) mod M
+    return backward ? h->backward->run(n, d_out, s) : CSDR_OK;
 }
 
 // A call on a caller's stream is remembered by an event behind its work, so that the host-buffer entry point (own stream s_k) can
@@ -509,21 +420,22 @@ static int chain_mark_user_stream(csdr_chain *h, hipStream_t stream)
 
 int csdr_chain_process_device(csdr_chain *h, const void *d_in, uint32_t n_in, void *d_out, uint32_t *n_out, void *stream)
 {
-    if (!h || h->in_submit) return chain_call(h, d_in, n_in, d_out, n_out, stream);
-    const bool own = h->s_k && (hipStream_t)stream == h->s_k;       // called by csdr_chain_submit / csdr_chain_process on the handle's stream
+    if (!h) { set_error("chain: null handle"); return CSDR_ERR_INVALID; }
+    hipStream_t s = (hipStream_t)stream;
+    const bool own = h->s_k && s == h->s_k;             // called by csdr_chain_submit / csdr_chain_process on the handle's stream
     DevGuard guard(h->device);
     if (!own && h->s_k && h->q_count) CSDR_HIP(hipStreamSynchronize(h->s_k));   // host-buffer chunks still in flight come first
-    if (h->s_pd[0]) {
+    if (h->pd) {
         // the handle has pipelined chunks (csdr_chain_submit_device): this call follows them, and a later submit follows this call
-        for (int i = 0; i < 2; i++) if (h->pd_used[i]) CSDR_HIP(hipStreamWaitEvent((hipStream_t)stream, h->e_pd_done[i], 0));
+        for (int i = 0; i < 2; i++) if (h->pd->used[i]) CSDR_HIP(hipStreamWaitEvent(s, h->pd->e_done[i], 0));
     }
-    int r = chain_call(h, d_in, n_in, d_out, n_out, stream);
+    int r = chain_call(h, d_in, n_in, d_out, n_out, s);
     if (r) return r;
-    if (h->s_pd[0]) {
-        CSDR_HIP(hipEventRecord(h->e_serial, (hipStream_t)stream));
-        h->serial_pending = true;
+    if (h->pd) {
+        CSDR_HIP(hipEventRecord(h->pd->e_serial, s));
+        h->pd->serial_pending = true;
     }
-    return own ? CSDR_OK : chain_mark_user_stream(h, (hipStream_t)stream);
+    return own ? CSDR_OK : chain_mark_user_stream(h, s);
 }
 
 // Device-side spin-wait time-outs (k_tile256 look-back / hand-off, k_dc_tile look-back) set a sticky status word and the
@@ -554,63 +466,50 @@ int csdr_chain_submit_device(csdr_chain *h, const void *d_in, uint32_t n_in, voi
     if (n_in == 0) return CSDR_OK;
     DevGuard guard;
     if (int r = chain_check_chunk(h, d_in, n_in, d_out, guard)) return r;
-    if (!h->s_pd[0]) {
+    if (!h->pd) {
         CSDR_HIP(hipDeviceSynchronize());               // whatever the handle has queued on caller streams so far
-        // created into locals and published together: a partial failure leaves the handle as it was
-        hipStream_t st[2] = {nullptr, nullptr}; hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-        bool ok = true;
-        for (int i = 0; i < 2 && ok; i++) ok = hipStreamCreateWithFlags(&st[i], hipStreamNonBlocking) == hipSuccess;
-        for (int i = 0; i < 6 && ok; i++) ok = hipEventCreateWithFlags(&ev[i], hipEventDisableTiming) == hipSuccess;
-        if (!ok) {
-            for (hipStream_t q : st) if (q) (void)hipStreamDestroy(q);
-            for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
-            (void)hipGetLastError();
-            set_error("chain: cannot create the streams / events of the pipelined entry point");
-            return CSDR_ERR_HIP;
-        }
-        for (int i = 0; i < 2; i++) { h->s_pd[i] = st[i]; h->e_pd_done[i] = ev[i]; }
-        for (int i = 0; i < 3; i++) h->e_pd_tail[i] = ev[2 + i];
-        h->e_serial = ev[5];
+        // made apart and published whole: a partial failure leaves the handle as it was
+        auto pd = std::make_unique<csdr_chain::Pipelined>();
+        if (int r = pd->open()) return r;
+        h->pd = std::move(pd);
         if (h->plan) h->plan->keep_tail();
     }
+    csdr_chain::Pipelined &pd = *h->pd;
     if (h->s_k && h->q_count) CSDR_HIP(hipStreamSynchronize(h->s_k));       // host-buffer chunks still in flight come first
-    const uint32_t nf = n_in / h->M, k = h->pd_count;
+    const uint32_t nf = n_in / h->M, k = pd.count;
     const int si = (int)(k & 1);
-    hipStream_t s = h->s_pd[si];
+    hipStream_t s = pd.s[si];
     // An independent launch (fused M = 256 chain without AGC / AM / WBFM tails, run-kernel-sized whole-tile chunk, previous
     // chunk's tail on file) reads nothing an earlier launch writes: it only waits for the input and for the copy of the
     // previous chunk's tail.  Every other call is ordered behind everything the handle has in flight.
-    const bool overlap = h->plan && !h->d_agc && !h->am && !h->wbfm && h->plan->can_overlap(nf);
+    const bool overlap = h->plan && !h->agc && !h->am && !h->wbfm && h->plan->can_overlap(nf);
     if (ready_event) CSDR_HIP(hipStreamWaitEvent(s, (hipEvent_t)ready_event, 0));
-    if (h->serial_pending) { CSDR_HIP(hipStreamWaitEvent(s, h->e_serial, 0)); h->serial_pending = false; }
+    if (pd.serial_pending) { CSDR_HIP(hipStreamWaitEvent(s, pd.e_serial, 0)); pd.serial_pending = false; }
     if (overlap) {
-        if (h->pd_tail_rec) CSDR_HIP(hipStreamWaitEvent(s, h->e_pd_tail[(k + 2) % 3], 0));       // recorded by call k - 1
+        if (pd.tail_rec) CSDR_HIP(hipStreamWaitEvent(s, pd.e_tail[(k + 2) % 3], 0));       // recorded by call k - 1
         // a call k - 1 that was NOT independent reads the plan's ping-pong state (run 0) that this launch's last run overwrites:
         // then this launch follows all of it, not only its tail copy
-        if (!h->pd_last_indep && h->pd_used[si ^ 1]) CSDR_HIP(hipStreamWaitEvent(s, h->e_pd_done[si ^ 1], 0));
-    } else if (h->pd_used[si ^ 1]) CSDR_HIP(hipStreamWaitEvent(s, h->e_pd_done[si ^ 1], 0));
-    h->call_indep = overlap; h->call_ev_tail = h->e_pd_tail[k % 3]; h->in_submit = true;
-    const int r = csdr_chain_process_device(h, d_in, n_in, d_out, n_out, s);
-    h->call_indep = false; h->call_ev_tail = nullptr; h->in_submit = false;
-    if (r) return r;
-    h->pd_tail_rec = h->plan && h->plan->tail_recorded();
-    if (overlap) h->pd_indep_calls++;
-    h->pd_last_indep = overlap;
-    CSDR_HIP(hipEventRecord(h->e_pd_done[si], s));
-    h->pd_used[si] = true; h->pd_count = k + 1;
+        if (!pd.last_indep && pd.used[si ^ 1]) CSDR_HIP(hipStreamWaitEvent(s, pd.e_done[si ^ 1], 0));
+    } else if (pd.used[si ^ 1]) CSDR_HIP(hipStreamWaitEvent(s, pd.e_done[si ^ 1], 0));
+    if (int r = chain_call(h, d_in, n_in, d_out, n_out, s, overlap, pd.e_tail[k % 3])) return r;
+    pd.tail_rec = h->plan && h->plan->tail_recorded();
+    if (overlap) pd.indep_calls++;
+    pd.last_indep = overlap;
+    CSDR_HIP(hipEventRecord(pd.e_done[si], s));
+    pd.used[si] = true; pd.count = k + 1;
     return CSDR_OK;
 }
 
-uint32_t csdr_chain_debug_independent_launches(const csdr_chain *h) { return h ? h->pd_indep_calls : 0u; }
+uint32_t csdr_chain_debug_independent_launches(const csdr_chain *h) { return h && h->pd ? h->pd->indep_calls : 0u; }
 
 int csdr_chain_wait_device(csdr_chain *h, void *stream)
 {
     if (!h) { set_error("chain: null handle"); return CSDR_ERR_INVALID; }
     DevGuard guard(h->device);
-    for (int i = 0; i < 2; i++) {
-        if (!h->pd_used[i]) continue;
-        if (stream) CSDR_HIP(hipStreamWaitEvent((hipStream_t)stream, h->e_pd_done[i], 0));
-        else CSDR_HIP(hipEventSynchronize(h->e_pd_done[i]));
+    for (int i = 0; h->pd && i < 2; i++) {
+        if (!h->pd->used[i]) continue;
+        if (stream) CSDR_HIP(hipStreamWaitEvent((hipStream_t)stream, h->pd->e_done[i], 0));
+        else CSDR_HIP(hipEventSynchronize(h->pd->e_done[i]));
     }
     return CSDR_OK;
 }
@@ -645,6 +544,21 @@ static int chain_host_init(csdr_chain *h)
     return CSDR_OK;
 }
 
+// What a host-buffer call of n_in samples through slot sl needs first: the handle's streams and events, the calls on caller
+// streams behind it, the slot's device buffers
+static int chain_slot_setup(csdr_chain *h, HostSlot &sl, uint32_t n_in)
+{
+    int r;
+    if ((r = chain_host_init(h))) return r;
+    if (h->user_stream_dirty) {                         // csdr_chain_process_device calls on caller streams precede this chunk
+        CSDR_HIP(hipEventSynchronize(h->e_user));
+        h->user_stream_dirty = false;
+    }
+    if (n_in && !sl.d_in && (r = h->mem.alloc_n(&sl.d_in, h->max_nx))) return r;
+    if (n_in && !sl.d_out && (r = h->mem.alloc(&sl.d_out, (size_t)h->C * h->max_nf * 8))) return r;
+    return CSDR_OK;
+}
+
 int csdr_chain_submit(csdr_chain *h, const float *in, uint32_t n_in, void *out)
 {
     if (!h) { set_error("chain: null handle"); return CSDR_ERR_INVALID; }
@@ -652,17 +566,11 @@ int csdr_chain_submit(csdr_chain *h, const float *in, uint32_t n_in, void *out)
     int r;
     if ((r = chain_check_chunk(h, in, n_in, out, guard))) return r;
     if (h->q_count == CSDR_CHAIN_INFLIGHT) { set_error("chain: %d chunks already in flight (collect first)", CSDR_CHAIN_INFLIGHT); return CSDR_ERR_BUSY; }
-    if ((r = chain_host_init(h))) return r;
-    if (h->user_stream_dirty) {                         // csdr_chain_process_device calls on caller streams precede this chunk
-        CSDR_HIP(hipEventSynchronize(h->e_user));
-        h->user_stream_dirty = false;
-    }
-    csdr_chain::HostSlot &sl = h->slot[(h->q_head + h->q_count) % CSDR_CHAIN_INFLIGHT];
+    HostSlot &sl = h->slot[(h->q_head + h->q_count) % CSDR_CHAIN_INFLIGHT];
+    if ((r = chain_slot_setup(h, sl, n_in))) return r;
     sl.user_out = out; sl.n_out = 0; sl.out_bytes = 0; sl.staged_out = false;
     if (n_in) {
         const size_t in_bytes = sizeof(float2) * (size_t)n_in, out_max = (size_t)h->C * h->max_nf * 8;
-        if (!sl.d_in && ((r = chain_alloc(h, &sl.d_in, h->max_nx)))) return r;
-        if (!sl.d_out) { CSDR_HIP(hipMalloc(&sl.d_out, out_max)); }
         // every resource of the slot exists before the chain's state moves on: a failure below this point cannot skip a chunk's state
         const bool stage_out = !is_pinned(out);
         if (stage_out && !sl.h_out) { CSDR_HIP(hipHostMalloc(&sl.h_out, out_max, hipHostMallocDefault)); }
@@ -697,7 +605,7 @@ int csdr_chain_collect(csdr_chain *h, uint32_t *n_out)
     if (n_out) *n_out = 0;
     if (!h->q_count) { set_error("chain: nothing submitted"); return CSDR_ERR_INVALID; }
     DevGuard guard(h->device);
-    csdr_chain::HostSlot &sl = h->slot[h->q_head];
+    HostSlot &sl = h->slot[h->q_head];
     if (sl.out_bytes) {
         CSDR_HIP(hipEventSynchronize(sl.e_out));        // (a failed wait leaves the chunk queued)
         if (sl.staged_out) memcpy(sl.user_out, sl.h_out, sl.out_bytes);
@@ -721,11 +629,8 @@ int csdr_chain_process(csdr_chain *h, const float *in, uint32_t n_in, void *out,
         // pageable caller memory: the runtime's own staged hipMemcpy beats a hand-made copy into page-locked memory
         DevGuard guard;
         if ((r = chain_check_chunk(h, in, n_in, out, guard))) return r;
-        if ((r = chain_host_init(h))) return r;
-        if (h->user_stream_dirty) { CSDR_HIP(hipEventSynchronize(h->e_user)); h->user_stream_dirty = false; }
-        csdr_chain::HostSlot &sl = h->slot[0];
-        if (!sl.d_in && ((r = chain_alloc(h, &sl.d_in, h->max_nx)))) return r;
-        if (!sl.d_out) { CSDR_HIP(hipMalloc(&sl.d_out, (size_t)h->C * h->max_nf * 8)); }
+        HostSlot &sl = h->slot[0];
+        if ((r = chain_slot_setup(h, sl, n_in))) return r;
         CSDR_HIP(hipMemcpy(sl.d_in, in, sizeof(float2) * (size_t)n_in, hipMemcpyHostToDevice));
         uint32_t no = 0;
         if ((r = csdr_chain_process_device(h, sl.d_in, n_in, sl.d_out, &no, h->s_k))) return r;
@@ -743,8 +648,8 @@ int csdr_chain_reset(csdr_chain *h)
     DevGuard guard(h->device);
     CSDR_HIP(hipDeviceSynchronize());                  // chunks still in flight are abandoned
     h->q_head = 0; h->q_count = 0;
-    h->pd_used[0] = h->pd_used[1] = false; h->pd_tail_rec = false; h->serial_pending = false; h->pd_count = 0;
-    h->user_stream_dirty = false; h->pd_last_indep = false;
+    if (h->pd) h->pd->reset();
+    h->user_stream_dirty = false;
     int r = chain_init_state(h, nullptr);
     if (r) return r;
     CSDR_HIP(hipDeviceSynchronize());
@@ -784,12 +689,12 @@ int csdr_chain_debug_agc(csdr_chain *h, uint32_t *checked, uint32_t *redone)
     if (!h) return CSDR_ERR_INVALID;
     if (checked) *checked = 0;
     if (redone) *redone = 0;
-    if (!h->agc_tail) return 0;
+    if (!h->agc || !h->agc->time_parallel()) return 0;
     DevGuard guard(h->device);
     (void)hipDeviceSynchronize();
-    return agc_tail_stats(h->agc_tail, checked, redone);
+    return h->agc->stats(checked, redone);
 }
-uint32_t csdr_chain_debug_agc_tile_major_calls(const csdr_chain *h) { return h && h->agc_tail ? agc_tail_tm_calls(h->agc_tail) : 0u; }
+uint32_t csdr_chain_debug_agc_tile_major_calls(const csdr_chain *h) { return h && h->agc ? h->agc->tile_major_calls() : 0u; }
 const char *csdr_chain_path(const csdr_chain *h) { return h ? h->path.c_str() : ""; }
 int csdr_chain_get_cfg(const csdr_chain *h, csdr_chain_cfg *cfg_out)
 {
@@ -801,9 +706,9 @@ int csdr_chain_get_cfg(const csdr_chain *h, csdr_chain_cfg *cfg_out)
 const char *csdr_chain_kernel_time(csdr_chain *h, double *total_ms, uint32_t *launches)
 {
     if (!h) return "";
-    if (h->s_pd[0] && h->timer.region && h->timer.open && h->timer.last) {
+    if (h->pd && h->timer.region && h->timer.open && h->timer.last) {
         DevGuard guard(h->device);
-        for (int i = 0; i < 2; i++) if (h->pd_used[i]) (void)hipStreamWaitEvent(h->timer.last, h->e_pd_done[i], 0);
+        for (int i = 0; i < 2; i++) if (h->pd->used[i]) (void)hipStreamWaitEvent(h->timer.last, h->pd->e_done[i], 0);
     }
     (void)h->timer.drain();
     if (total_ms) *total_ms = h->timer.acc_ms;
@@ -812,24 +717,6 @@ const char *csdr_chain_kernel_time(csdr_chain *h, double *total_ms, uint32_t *la
     return h->plan ? h->plan->name() : "k_agc_spec";      // the kernel the last call timed (before the first call: the create-time choice)
 }
 
-int csdr_chain_destroy(csdr_chain *h)
-{
-    if (!h) return CSDR_OK;
-    DevGuard guard(h->device);
-    (void)hipDeviceSynchronize();
-    delete h->plan;
-    if (h->agc_tail) agc_tail_destroy(h->agc_tail);
-    h->timer.destroy();
-    for (auto &sl : h->slot) {
-        if (sl.d_out) (void)hipFree(sl.d_out);
-        if (sl.h_in) (void)hipHostFree(sl.h_in);
-        if (sl.h_out) (void)hipHostFree(sl.h_out);
-        for (hipEvent_t e : {sl.e_in, sl.e_k, sl.e_out}) if (e) (void)hipEventDestroy(e);
-    }
-    for (hipStream_t st : {h->s_in, h->s_k, h->s_out, h->s_pd[0], h->s_pd[1]}) if (st) (void)hipStreamDestroy(st);
-    for (hipEvent_t e : {h->e_pd_done[0], h->e_pd_done[1], h->e_pd_tail[0], h->e_pd_tail[1], h->e_pd_tail[2], h->e_serial, h->e_user}) if (e) (void)hipEventDestroy(e);
-    delete h;
-    return CSDR_OK;
-}
+int csdr_chain_destroy(csdr_chain *h) { return block_destroy(h); }
 
 }  // extern "C"

@@ -73,16 +73,17 @@ template <class H> int block_destroy(H *h)
     return CSDR_OK;
 }
 
-// A handle under construction: open() (behind the create's argument checks) finds the device and makes the handle, publish()
-// hands it to the caller.  Leaving the create on any other way, a CSDR_HIP included, destroys the handle and what it owns
+// A handle under construction: open() (behind the create's argument checks) finds the device (want, or -1: the current one) and
+// makes the handle, publish() hands it to the caller.  Leaving the create on any other way, a CSDR_HIP included, destroys the
+// handle and what it owns
 template <class H> struct NewBlock {
     NewBlock() = default;
     NewBlock(const NewBlock &) = delete;
     NewBlock &operator=(const NewBlock &) = delete;
     ~NewBlock() { (void)block_destroy(h); }
-    int open()
+    int open(int32_t want = -1)
     {
-        int dev; int r = check_device(-1, &dev); if (r) return r;
+        int dev; int r = check_device(want, &dev); if (r) return r;
         h = new (std::nothrow) H();
         if (!h) return CSDR_ERR_NOMEM;
         h->device = dev;
@@ -108,6 +109,28 @@ template <class T> int block_zeros(DeviceBuffers &mem, T **d, size_t n)
     if (n) CSDR_HIP(hipMemset(*d, 0, sizeof(T) * n));
     return CSDR_OK;
 }
+
+// State a kernel carries from one call to the next as two arrays of n elements owned by mem: a call reads in() and writes out(),
+// flip() behind the launch makes its output the next call's input
+template <class T> struct PingPong {
+    int alloc(DeviceBuffers &mem, size_t n_)
+    {
+        n = n_;
+        int r = mem.alloc_n(&side[0], n);
+        return r ? r : mem.alloc_n(&side[1], n);
+    }
+    int reset(hipStream_t s)             // zeros on both sides, back to side 0
+    {
+        cur = 0;
+        for (T *p : side) CSDR_HIP(hipMemsetAsync(p, 0, sizeof(T) * n, s));
+        return CSDR_OK;
+    }
+    const T *in() const { return side[cur]; }
+    T *out() const { return side[cur ^ 1]; }
+    void flip() { cur ^= 1; }
+private:
+    T *side[2] = {nullptr, nullptr}; size_t n = 0; int cur = 0;
+};
 
 inline int block_null_arg(const char *name) { set_error("%s: null argument", name); return CSDR_ERR_INVALID; }
 inline int block_check_n(const char *name, uint32_t n, uint32_t max_n)
