@@ -1,8 +1,10 @@
-// What the chain plans share (fused.h): the call sequence of ChainPlan, the carried stream state, the DC blocker's constants and the
-// set-up of cold starts without warm-up windows.  Host code only.  Product code.
+// What the chain plans share (fused.h): the call sequence of ChainPlan (one kernel choice per call), the carried stream state, the DC
+// blocker's constants, the set-up of cold starts without warm-up windows and the debug trace dump of the M = 1024 run kernels.  Host code
+// only.  Product code.
 #include "fused.h"
 
 #include <cmath>
+#include <cstdio>
 
 namespace csdr {
 
@@ -13,7 +15,8 @@ int ChainPlan::process(const FusedCall &call, hipStream_t s, KernelTimer *timer)
         set_error("fused: internal: tile-major output or an independent launch requested from a call that cannot run as one");
         return -1;
     }
-    int r = run(call, d_premix ? d_premix : call.d_out, s, timer);
+    last = choose(call.nf);
+    int r = run(call, last, d_premix ? d_premix : call.d_out, s, timer);
     if (r) return r;
     cur ^= 1;
     frames_done += call.nf;
@@ -48,6 +51,17 @@ int StreamState::reset(hipStream_t s) const
         CSDR_HIP(hipMemsetAsync(vend[i], 0, sizeof(float2), s));
         CSDR_HIP(hipMemsetAsync(rp[i], 0, sizeof(float2) * n_rp, s));
     }
+    return 0;
+}
+
+int Run1024Call::trace_dump(size_t n, bool before, hipStream_t s) const
+{
+    if (!trace) return 0;
+    if (before) { CSDR_HIP(hipMemsetAsync(trace, 0, n * sizeof(unsigned long long), s)); return 0; }
+    std::vector<unsigned long long> hbuf(n);
+    CSDR_HIP(hipStreamSynchronize(s));
+    CSDR_HIP(hipMemcpy(hbuf.data(), trace, n * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    if (FILE *f = fopen(trace_file, "wb")) { fwrite(hbuf.data(), sizeof(unsigned long long), n, f); fclose(f); }
     return 0;
 }
 

@@ -18,17 +18,6 @@ int  hip_fail(hipError_t e, const char *what, const char *file, int line);
         if (e__ != hipSuccess) return ::csdr::hip_fail(e__, #call, __FILE__, __LINE__); \
     } while (0)
 
-// same, for create functions: run `cleanup` (the object's destroy) before returning the error
-#define CSDR_HIP_CLEAN(call, cleanup)                                           \
-    do {                                                                        \
-        hipError_t e__ = (call);                                                \
-        if (e__ != hipSuccess) {                                                \
-            const int rc__ = ::csdr::hip_fail(e__, #call, __FILE__, __LINE__); \
-            cleanup;                                                            \
-            return rc__;                                                        \
-        }                                                                       \
-    } while (0)
-
 // ---- device buffers released together (fused plans, chain and block handles) ---------
 // alloc() records every buffer it makes; the destructor frees them all
 struct DeviceBuffers {

@@ -1,7 +1,15 @@
 // Interface between the chain handle of the C ABI (capi.hip) and the plans of its routes: the four fused channelizers (M = 64, 256,
-// 1024, 4096) and the any-M route (plan_generic.hip).  Product code.
+// 1024, 4096) and the any-M route.  Product code.
+//   chain_plan.cpp            what the plans share: ChainPlan::process, StreamState, DcConsts, ColdStart, dc_state_response
+//   kernel_choice.h           which kernel a call takes (KernelChoice, the run counts, the M = 64 and M = 1024 selection); no HIP
+//   kernels_fused_small.hip   M = 64: SmallPlan, k_run64; its run kernel k_run64v2 in kernels_run64_v2.hip
+//   kernels_fused.hip         M = 256: FusedPlan, k_tile256; its run kernel k_run256v2 in kernels_fused_v2.hip
+//   kernels_pfb1024.hip       M = 1024: BigPlan, k_run1024; its run kernels in kernels_run1024_v2.hip, kernels_run1024_v3.hip, kernels_shard1024.hip
+//   kernels_pfb4096.hip       M = 4096: HugePlan, k_front4096 + k_back4096
+//   plan_generic.hip          any M: GenericPlan over kernels_generic.hip, kernels_dc_tile.hip and k_pfb1024
 #pragma once
 #include "csdr_internal.h"
+#include "kernel_choice.h"
 #include <type_traits>
 #include <utility>
 
@@ -88,8 +96,10 @@ struct ColdStart {
 // The plan of one route (a RouteRow of capi.hip): M = 64 (kernels_fused_small.hip), 256 (kernels_fused.hip), 1024 (kernels_pfb1024.hip),
 // 4096 (kernels_pfb4096.hip) and any M (plan_generic.hip) derive from it.  With the AGC on (cfg.fm and cfg.mix are then false) a plan delivers
 // the channel-major CF32 plane the handle's tail reads; without it, the call's output.  The base owns what they share: the configuration, the CU count, the global frame counter,
-// the ping-pong index of the state buffers, the device buffers (mem: freed with the plan) and the mix ending of the 64, 256 and 1024 plans
-// (run() writes d_premix, process() sums its rows into the call's output).
+// the ping-pong index of the state buffers, the device buffers (mem: freed with the plan), the mix ending of the 64, 256 and 1024 plans
+// (run() writes d_premix, process() sums its rows into the call's output) and the kernel choice of the last call: a plan answers "which
+// kernel does a call of nf frames take, with how many runs" in choose() alone; process() asks once per call, hands the answer to run()
+// and keeps it for name() and route(); tile_major_ok() and can_overlap() are predicates on the same answer.
 struct ChainPlan {
     FusedConfig cfg;
     uint32_t cus;                // compute units the launches are sized for (cfg.cus; the M = 256 plan takes CSDR_CUS)
@@ -98,6 +108,7 @@ struct ChainPlan {
     void *d_premix = nullptr;    // per-channel output in front of launch_mix (cfg.mix; the M = 4096 plan mixes in its back kernel)
     DeviceBuffers mem;
     const DcConsts dcc;          // of cfg.dc_block and cfg.dc
+    KernelChoice last;           // of the last call (make_plan: first_choice() until then)
 
     explicit ChainPlan(const FusedConfig &c) : cfg(c), cus(c.cus), dcc(c.dc_block, c.dc) {}
     virtual ~ChainPlan() = default;
@@ -106,8 +117,10 @@ struct ChainPlan {
     int process(const FusedCall &call, hipStream_t s, KernelTimer *timer);
     int reset(hipStream_t s) { cur = 0; frames_done = 0; return reset_state(s); }
     void seek(uint64_t frames) { frames_done = frames; }     // after reset: global frame index of the next frame
-    // the kernel the last call launched (before the first call: the one a call of max_nf frames takes)
-    virtual const char *name() const = 0;
+    // The kernel a call of nf frames takes: a function of cfg, the knobs init() read, cus and nf, nothing else (no stream state)
+    virtual KernelChoice choose(uint32_t nf) const = 0;
+    // the kernel the last call launched (before the first call: first_choice())
+    const char *name() const { return kernel_name(last.id); }
     // csdr_chain_path in front of the handle's tails (+am, +wbfm, +dft-backward, -spec); prefix: the RouteRow's
     virtual std::string route(const char *prefix, bool agc) const
     {
@@ -129,8 +142,13 @@ protected:
     // (row 0: even frames, n = j; row 1: odd frames, n = M + j)
     std::vector<float2> premix_table() const;
     virtual int reset_state(hipStream_t s) = 0;      // zero the stream state the plan carries between calls
-    // the call's launches into out (d_premix when mixing); a launch sequence with two steps may flip cur between them, process() flips it behind the call
-    virtual int run(const FusedCall &call, void *out, hipStream_t s, KernelTimer *timer) = 0;
+    virtual const char *kernel_name(int id) const = 0;      // the plan's table: KernelChoice::id -> text
+    // what name() says before the first call: the kernel a call of max_nf frames takes (M = 64, 256: their first kernel, as their paths always read)
+    virtual KernelChoice first_choice() const { return choose(cfg.max_nf); }
+    // the call's launches, kernel k = choose(call.nf), into out (d_premix when mixing); a launch sequence with two steps may flip cur between them,
+    // process() flips it behind the call
+    virtual int run(const FusedCall &call, KernelChoice k, void *out, hipStream_t s, KernelTimer *timer) = 0;
+    template <class Plan> friend int make_plan(const FusedConfig &cfg, ChainPlan **out);
 };
 
 // the factories' common part: a plan of type Plan, set up by its init()
@@ -138,6 +156,7 @@ template <class Plan> int make_plan(const FusedConfig &cfg, ChainPlan **out)
 {
     Plan *p = new Plan(cfg);
     if (int r = p->init()) { delete p; return r; }
+    p->last = p->first_choice();
     *out = p;
     return 0;
 }
@@ -181,50 +200,48 @@ struct Run64v2Host {
     double weight = 1.1;        // tile share of the older workgroup of a CU (1 = even; 1.1 measured best: 243 vs 250 us; CSDR_RUN64_WEIGHT)
 };
 constexpr int RUN64_DCFIX_F = 448;                      // output frames of a run the state correction covers (7 tiles: 32 768 samples behind the halo tile's start)
-uint32_t run64_v2_runs(uint32_t nf, uint32_t cus, bool all);      // 0: not a call for the kernel; all: no size threshold (CSDR_RUN64_V2_ALL)
 // Response of the chain (pre-mix table wpre [2][M], taps, forward DFT), at the channels k0 .. k0 + 3, to a DC-blocker state of 1 in
 // front of a tile: frames f0 .. f0 + nfr - 1 behind the tile's start, both parities of the tile's first frame; rt [2][nfr][4], f64 inside
 void dc_state_response(const FusedConfig &cfg, const float2 *wpre, uint32_t f0, uint32_t nfr, uint32_t k0, float2 *rt);
 int run64_v2_launch(const Run64v2Host &h, hipStream_t s, KernelTimer *timer);
 
-// k_run1024v2 (kernels_run1024_v2.hip): whole-band M = 1024 calls with nf % 4 == 0; same state buffers as k_run1024
-struct Run1024v2Host {
+// One call of a run kernel of the M = 1024 plan: k_run1024v2<FM, G> (kernels_run1024_v2.hip: interleaved shards, nf % 4 == 0), k_run1024v3
+// (kernels_run1024_v3.hip: whole band, one 512-thread workgroup per CU, output lines staged in registers; calls of whole 4-frame tiles) or
+// k_shard1024<.., G> (kernels_shard1024.hip: chan_stride G = 4, 8, F32 or CF32 rows of the owned channels; the fold of the aliasing branches
+// behind the FIR + a (1024 / G)-point DFT across the lanes of a wave).  Same state buffers and tables as k_run1024.  Where no kernel is
+// named, all three launchers read the field (put_run1024, fused_common.h, copies those into the kernel's argument struct).
+struct Run1024Call {
     const float2 *x; void *out;
     const float4 *taps_q;       // [4][4][256] float4: taps of branch 256 q + j (14) + its even-frame pre-mix phasor
     const float2 *tw;
     const float2 *uhist_in; float2 *uhist_out; const float2 *vend_in; float2 *vend_out; const float2 *rp_in; float2 *rp_out;
-    uint32_t nf, nruns, parity0;
-    uint32_t G = 1, g = 0;      // interleaved shard g of G (tables rotated by the plan)
-    bool tile_major = false;    // k_run1024v3<CF32>: the lines of a 16-frame block back to back ([block][1024][128 B]) instead of row-major [1024][nf]
-    // k_run1024v3 without warm-up windows (round 5, as k_run256v2: DESIGN 4): cpre [nruns + 1] DC state four tiles in front of every run's
+    uint32_t nf, nruns, parity0;    // nruns: KernelChoice::runs
+    bool fm;                    // F32 freqdem output (k_run1024v2: always)
+    uint32_t G = 1, g = 0;      // k_run1024v2, k_shard1024: interleaved shard g of G (tables rotated by the plan)
+    bool tile_major = false;    // k_run1024v3<CF32>, k_shard1024<CF32>: the lines of a 16-frame block back to back ([block][rows][128 B]) instead of row-major [rows][nf]
+    // k_run1024v3, k_shard1024 without warm-up windows (as k_run256v2: DESIGN 4): cpre [nruns + 1] DC state four tiles in front of every run's
     // first tile, side [nruns][4][RUN1024_DCFIX_F] uncorrected Y of the channels 510..513 (FM), rt [2][RUN1024_DCFIX_F][4] the chain's
-    // response to a unit state there; null: warm-up windows
+    // response to a unit state there; rt null: warm-up windows
     float2 *cpre = nullptr, *side = nullptr; const float2 *rt = nullptr;
     int mfix = -1;              // k_shard1024: the shard's row among the four channels around DC (side [nruns][RUN1024_DCFIX_F], rt channel 0), -1: none
     const DcConsts *dc;         // the plan's
     float fm_ref;
     double weight = 1.2;        // k_run1024v2: tile share of the older workgroup of a CU (1 = even; CSDR_RUN1024_WEIGHT)
     // debug builds of k_run1024v3 / k_shard1024: the plan's stamp buffer (RUN1024_V3_TRACE_N / SHARD1024_TRACE_N) and the file the
-    // launcher writes the last launch's stamps to (CSDR_RUN1024_V3_TRACE, CSDR_SHARD1024_TRACE); null: no trace
+    // last launch's stamps go to (CSDR_RUN1024_V3_TRACE, CSDR_SHARD1024_TRACE); null: no trace
     unsigned long long *trace = nullptr; const char *trace_file = nullptr;
+    // the debug trace of a launch: before = zero the n stamps in front of it; else wait for it and write them, raw uint64, to trace_file
+    int trace_dump(size_t n, bool before, hipStream_t s) const;
 };
 constexpr size_t RUN1024_V3_TRACE_N = 1536, SHARD1024_TRACE_N = 768;
-// max_runs of the three *_runs below: 0, or an upper limit of the run count below the default (CSDR_RUN1024_RUNS, CSDR_RUN1024_V3_RUNS,
-// CSDR_SHARD1024_RUNS: experiments, and tests that force runs onto short inputs)
-uint32_t run1024_v2_runs(uint32_t nf, uint32_t cus, uint32_t max_runs);    // 0: call too short for the kernel
-int run1024_v2_launch(const Run1024v2Host &h, bool fm, hipStream_t s, KernelTimer *timer);
-// third-generation FM kernel (kernels_run1024_v3.hip): one 512-thread workgroup per CU, output lines staged in registers (no staging
-// block); whole band, calls of whole output lines (nf = 0 mod 32 frames F32 / 16 frames CF32)
-// frame -1 of a run (freqdem history) + its first eight tiles.  The first frame NOT corrected (32) has a window that reaches back to frame
-// 35 behind the cold start: alpha |c| beta^35840 = 1.6e-8 alpha |c| of the missing state is left in it (with four tiles it was 5.9e-5:
-// ~1e-5 of a unit signal at the strongest DC offset the tests use)
+// k_run1024v3's correction covers frame -1 of a run (freqdem history) + its first eight tiles.  The first frame NOT corrected (32) has a
+// window that reaches back to frame 35 behind the cold start: alpha |c| beta^35840 = 1.6e-8 alpha |c| of the missing state is left in it
+// (with four tiles it was 5.9e-5: ~1e-5 of a unit signal at the strongest DC offset the tests use)
 constexpr int RUN1024_DCFIX_F = 33;
-// interleaved-shard run kernel (kernels_shard1024.hip, round 6): chan_stride G = 4, 8, F32 or CF32 rows of the owned channels; the fold of the
-// aliasing branches behind the FIR + a (1024 / G)-point DFT across the lanes of a wave; same state arrays and tables as the plan's other kernels
-uint32_t shard1024_runs(uint32_t nf, bool fm, uint32_t G, uint32_t cus, uint32_t max_runs);    // 0: the call is not for this kernel
-int shard1024_launch(const Run1024v2Host &h, bool fm, uint32_t nruns, hipStream_t s, KernelTimer *timer);
-uint32_t run1024_v3_runs(uint32_t nf, bool fm, uint32_t cus, uint32_t max_runs);    // 0: the call is not for this kernel
-int run1024_v3_launch(const Run1024v2Host &h, bool fm, uint32_t nruns, hipStream_t s, KernelTimer *timer);
+// one launch per call (BigPlan::run, kernels_pfb1024.hip); no fix-up kernel: a run computes the frame in front of it itself
+int run1024_v2_launch(const Run1024Call &h, hipStream_t s, KernelTimer *timer);
+int run1024_v3_launch(const Run1024Call &h, hipStream_t s, KernelTimer *timer);
+int shard1024_launch(const Run1024Call &h, hipStream_t s, KernelTimer *timer);
 
 
 // single-pass DC blocker + NCO mix for whole chunks of the generic path (kernels_dc_tile.hip)

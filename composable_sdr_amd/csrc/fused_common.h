@@ -208,6 +208,18 @@ inline PhaseK phase_consts_scaled(float ref)
     k.hp *= ref; k.pi *= ref; k.ref = ref;
     return k;
 }
+// Run1024Call (fused.h) into the members Run1024v2Args, Run1024v3Args and Shard1024Args have in common (by name, as DcConsts::put; the
+// structs keep their own layouts: k_run1024v3 reads members at fixed kernarg offsets)
+template <class Args> inline void put_run1024(const Run1024Call &h, Args &A)
+{
+    A.x = h.x; A.out = h.out; A.taps_q = h.taps_q; A.tw = h.tw;
+    A.uhist_in = h.uhist_in; A.uhist_out = h.uhist_out; A.vend_in = h.vend_in; A.vend_out = h.vend_out;
+    A.rp_in = h.rp_in; A.rp_out = h.rp_out;
+    A.nf = h.nf; A.nb = h.nf / 4; A.nruns = h.nruns; A.parity0 = h.parity0;
+    h.dc->put(A);
+    A.fm_ref = h.fm_ref; A.tiny = 1e-37f;
+    A.pk = phase_consts_scaled(h.fm_ref);               // unscaled polynomial (fm_quad scales a = min / max by ref)
+}
 // Selects with the condition in an SGPR pair: on gfx950 the VCC form of v_cndmask (what hipcc emits for `c ? a : b`) costs
 // 16 cycles per wave, the SGPR-mask form 4.6 (tools/probes/issue_probe2.hip).
 __device__ __forceinline__ float sel_abs_gt(float a, float b, float t, float f)        // |a| > |b| ? t : f
@@ -301,6 +313,38 @@ __device__ __forceinline__ void tile_load(const float4 *__restrict__ src, int va
         raw[it] = (q < valid_runs) ? src[8 * q + i] : make_float4(0.f, 0.f, 0.f, 0.f);
     }
 }
+
+// Read-only DC warm-up of the run kernels: a run that starts inside a call takes the blocker's state from the raw tiles in front of it.
+// tile(): this lane's share of sum_n beta^(4095 - n) x[n] over one tile image of tile_load.  The weight of my piece `it` is
+// beta^(4095 - n), n = n0 + 512 it (the swizzle term of the slot does not depend on it): a running product, two registers and a uniform
+// ratio instead of sixteen.  wstep = beta^-512 (dc_block off, l2beta = -1000: no state to warm up, and no inf * 0).  Used by k_run64v2,
+// k_run1024v2, k_run1024v3 and k_shard1024; k_run256v2 (kernels_fused_v2.hip) keeps its own copy of the same lines: through the helper
+// hipcc schedules one instruction of its prologue elsewhere, and that kernel's instruction stream is not to move.
+struct DcWarmup {
+    float wt0, wt1, wstep;
+    __device__ __forceinline__ DcWarmup(int tid, float l2beta)
+    {
+        const int wave = tid >> 6, lane = tid & 63;
+        const int slot = 64 * wave + lane, q = slot >> 3;
+        const int i = (slot & 7) ^ ((q >> 1) & 7);
+        const int n = 16 * q + 2 * i;
+        wt0 = exp2f((float)(4095 - n) * l2beta);
+        wt1 = exp2f((float)(4094 - n) * l2beta);
+        wstep = l2beta < -100.0f ? 0.0f : exp2f(-512.0f * l2beta);
+    }
+    __device__ __forceinline__ float2 tile(const float4 (&r)[8]) const
+    {
+        float2 p = make_float2(0.f, 0.f);
+        float a0 = wt0, a1 = wt1;
+#pragma unroll
+        for (int it = 0; it < 8; it++) {
+            p = cfma(make_float2(r[it].x, r[it].y), a0, p);
+            p = cfma(make_float2(r[it].z, r[it].w), a1, p);
+            a0 *= wstep; a1 *= wstep;
+        }
+        return p;
+    }
+};
 
 __device__ __forceinline__ float2 scan_staged(float2 *R, float2 *E, float2 *T, const TileArgs &A, int tid);
 // Registers -> LDS, then the zero-state DC scan of the tile.  On return R holds

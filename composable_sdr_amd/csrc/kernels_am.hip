@@ -81,13 +81,13 @@ __global__ __launch_bounds__(AM_T) void k_am(const float2 *__restrict__ Z, float
     const float carry = fmaf(dl, carry_w, prev);                  // q_hat just before my first sample
     // the channel's state after the call is q_hat at the row's last sample: staged index `last`
     const int64_t last = (int64_t)nf - 1 - t0;
-    const bool owns_last = last >= AM_REAL && last < AM_TOT && (last >> 4) == tid;
+    const bool last_mine = last >= AM_REAL && last < AM_TOT && (last >> 4) == tid;
     float m = dec1;
 #pragma unroll
     for (int k = 0; k < AM_PER; k++) {
         const float qq = fmaf(m, carry, q[k]);
         ts[17 * tid + k] = 2.0f * (tv[k] - qq);
-        if (owns_last && k == (int)(last & 15)) q_out[c] = qq;
+        if (last_mine && k == (int)(last & 15)) q_out[c] = qq;
         m *= dec1;
     }
     __syncthreads();

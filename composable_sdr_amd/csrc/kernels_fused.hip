@@ -349,7 +349,7 @@ constexpr float EQUAL_WEIGHT[8] = {1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f};
 
 struct FusedPlan : ChainPlan {
     using ChainPlan::ChainPlan;
-    std::string kernel;
+    enum { K_TILE256 = 0, K_RUN256V2 };      // KernelChoice::id
     uint32_t max_nb = 0, epoch = 0;
     float *d_taps = nullptr;
     float2 *d_tw = nullptr, *d_wpre = nullptr;
@@ -376,7 +376,10 @@ struct FusedPlan : ChainPlan {
     RunArgs run_proto;               // and of a k_run256v2 launch: the DC and phase constants, the cold-start arrays and the launch knobs
 
     int init();
-    const char *name() const override { return kernel.c_str(); }
+    KernelChoice choose(uint32_t nf) const override;
+    const char *kernel_name(int id) const override;
+    // until the first call csdr_chain_path names the tile kernel, whatever a call of max_nf frames would take (the route strings are read by tools and logs)
+    KernelChoice first_choice() const override { return {K_TILE256, 0}; }
     bool tile_major_ok(uint32_t nf) const override;
     void keep_tail() override { save_tails = cfg.G == 1; }     // interleaved shards never run as independent launches
     bool can_overlap(uint32_t nf) const override;
@@ -384,10 +387,9 @@ struct FusedPlan : ChainPlan {
     int status(unsigned *st) override;
     int trace(unsigned long long *out, uint32_t ntiles) override;
     int reset_state(hipStream_t s) override;
-    int run(const FusedCall &call, void *out, hipStream_t s, KernelTimer *timer) override;
-    bool v2_call(uint32_t nf) const { return cfg.G == 1 && cfg.c0 == 0 && cfg.C == cfg.M && nf / NB >= run_min_tiles; }
+    int run(const FusedCall &call, KernelChoice k, void *out, hipStream_t s, KernelTimer *timer) override;
     void wire_state(TileArgs &A) const;
-    int run_kernel(const FusedCall &call, const TileArgs &A, hipStream_t s, KernelTimer *timer);
+    int run_kernel(const FusedCall &call, const TileArgs &A, uint32_t nruns, hipStream_t s, KernelTimer *timer);
     int tile_kernel(TileArgs &T, hipStream_t s, KernelTimer *timer);
     int ragged_end(const FusedCall &call, void *out, uint32_t nb_full, uint32_t rem, hipStream_t s);
 };
@@ -405,7 +407,6 @@ template <class T, class Conv> static void parse_list(const char *e, T (&v)[8], 
 int FusedPlan::init()
 {
     int r;
-    kernel = cfg.fm ? "k_tile256<FM>" : "k_tile256<CF32>";
     max_nb = (cfg.max_nf + NB - 1) / NB;
     if ((r = mem.alloc(&d_taps, sizeof(float) * cfg.M * cfg.p))) return r;
     if ((r = mem.alloc(&d_tw, sizeof(float2) * cfg.M))) return r;
@@ -485,17 +486,36 @@ int FusedPlan::reset_state(hipStream_t s)
     return 0;
 }
 
+// k_run256v2 takes the whole tiles of every call of an interleaved shard (the tile kernel only knows whole bands) and the whole-band calls of
+// >= run_min_tiles tiles; a contiguous channel shard takes the tile kernel, which masks its stores, at every size
+KernelChoice FusedPlan::choose(uint32_t nf) const
+{
+    const uint32_t nb = nf / NB;
+    if (cfg.G == 1 && !(cfg.c0 == 0 && cfg.C == cfg.M && nb >= run_min_tiles)) return {K_TILE256, 0};
+    // one run per resident workgroup slot (a single round), runs balanced to within one tile,
+    // at least 8 tiles per run so that the warm-up reads stay below 7/8 of a run
+    const uint32_t nruns = resident_wgs_v2 < nb / 8 ? resident_wgs_v2 : nb / 8;
+    return {K_RUN256V2, nruns ? nruns : 1};
+}
+
+const char *FusedPlan::kernel_name(int id) const
+{
+    static const char *const run[2][4] = {{"k_run256v2<CF32>", "k_run256v2<CF32>/G2", "k_run256v2<CF32>/G4", "k_run256v2<CF32>/G8"},
+                                          {"k_run256v2<FM>", "k_run256v2<FM>/G2", "k_run256v2<FM>/G4", "k_run256v2<FM>/G8"}};
+    if (id == K_RUN256V2) return run[cfg.fm][cfg.G == 8 ? 3 : cfg.G == 4 ? 2 : cfg.G == 2 ? 1 : 0];
+    return cfg.fm ? "k_tile256<FM>" : "k_tile256<CF32>";
+}
+
 bool FusedPlan::tile_major_ok(uint32_t nf) const
 {
     // the calls that go to k_run256v2 as whole tiles: CF32 output below 4 GiB, no mix inside the plan
-    if (cfg.fm || cfg.mix || nf % NB || !nf) return false;
-    if (cfg.G > 1) return (uint64_t)cfg.C * nf * 8u < (1ull << 32);
-    return cfg.c0 == 0 && cfg.C == cfg.M && nf / NB >= run_min_tiles;
+    if (cfg.fm || cfg.mix || nf % NB || !nf || (cfg.G > 1 && (uint64_t)cfg.C * nf * 8u >= (1ull << 32))) return false;
+    return choose(nf).id == K_RUN256V2;
 }
 
 bool FusedPlan::can_overlap(uint32_t nf) const
 {
-    return save_tails && tail_valid && v2_call(nf) && nf % NB == 0 && !cfg.mix;
+    return save_tails && tail_valid && nf % NB == 0 && !cfg.mix && choose(nf).id == K_RUN256V2;     // (save_tails: whole band)
 }
 
 void FusedPlan::wire_state(TileArgs &A) const
@@ -505,7 +525,7 @@ void FusedPlan::wire_state(TileArgs &A) const
     A.rp_in = st.rp_in(cur);      A.rp_out = st.rp_out(cur);
 }
 
-int FusedPlan::run(const FusedCall &call, void *out, hipStream_t s, KernelTimer *timer)
+int FusedPlan::run(const FusedCall &call, KernelChoice k, void *out, hipStream_t s, KernelTimer *timer)
 {
     const FusedConfig &c = cfg;
     const uint32_t nf = call.nf, nb_full = nf / NB, rem = nf - nb_full * NB;
@@ -519,15 +539,14 @@ int FusedPlan::run(const FusedCall &call, void *out, hipStream_t s, KernelTimer 
     A.out_stride = call.tile_major ? NB : nf;      // tile-major: a row's 16 frames of a tile are one 128-byte line; rows follow each other inside the tile's block
     A.out_t0 = 0;
     A.parity0 = (uint32_t)(frames_done & 1);
-    if (v2_call(nf) || shard) {      // (a contiguous channel shard takes the tile kernel, which masks its stores, at every size)
+    if (k.id == K_RUN256V2) {
         // large chunk: dependency-free runs of full tiles (k_run256v2; its lane offsets are 32-bit over 16 rows and the row groups
         // go through a 64-bit base, so the output may exceed 4 GiB); a ragged tail (< 16 frames) follows as a second launch of the
         // tile kernel on the state the run kernel leaves behind
         A.nf = nb_full * NB; A.nb = nb_full;
-        if ((r = run_kernel(call, A, s, timer))) return r;
+        if ((r = run_kernel(call, A, k.runs, s, timer))) return r;
         if (rem && (r = ragged_end(call, out, nb_full, rem, s))) return r;
     } else {
-        kernel = c.fm ? "k_tile256<FM>" : "k_tile256<CF32>";
         tail_valid = false;
         A.nf = nf; A.nb = (nf + NB - 1) / NB;
         if ((r = tile_kernel(A, s, timer))) return r;
@@ -537,20 +556,13 @@ int FusedPlan::run(const FusedCall &call, void *out, hipStream_t s, KernelTimer 
 }
 
 // The whole tiles of a call (A.nb of them; none: a shard's call of fewer than 16 frames, which ragged_end does alone) through k_run256v2
-int FusedPlan::run_kernel(const FusedCall &call, const TileArgs &A, hipStream_t s, KernelTimer *timer)
+int FusedPlan::run_kernel(const FusedCall &call, const TileArgs &A, uint32_t nruns, hipStream_t s, KernelTimer *timer)
 {
     const FusedConfig &c = cfg;
     const bool shard = c.G > 1;
     int r;
-    kernel = c.fm ? "k_run256v2<FM>" : "k_run256v2<CF32>";
-    if (shard) kernel += "/G" + std::to_string(c.G);
     RunArgs RA = run_proto;
     RA.t = A;
-    // one run per resident workgroup slot (a single round), runs balanced to within one tile,
-    // at least 8 tiles per run so that the warm-up reads stay below 7/8 of a run
-    uint32_t nruns = resident_wgs_v2;
-    if (nruns > A.nb / 8) nruns = A.nb / 8;
-    if (nruns < 1) nruns = 1;
     RA.nruns = nruns;
     const float *v2_weight = c.fm ? ((cus && nruns == 3 * cus) ? V2_WEIGHT_FM3 : V2_WEIGHT_FM) : V2_WEIGHT_CF;
     RA.split = make_split(A.nb, nruns, cus, (call.indep && pd_equal) ? EQUAL_WEIGHT : (have_weights ? slot_weight : v2_weight),

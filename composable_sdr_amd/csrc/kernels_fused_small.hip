@@ -338,25 +338,23 @@ __global__ __launch_bounds__(64) void k_run64_fixup(const float2 *__restrict__ y
 struct SmallPlan : ChainPlan {
     using ChainPlan::ChainPlan;
     uint32_t max_nb = 0, resident_wgs = 768;
-    bool v2_ok = false, v2_last = false;     // k_run64v2 usable (CF32, whole band); used by the last call
+    Choice64 pick{};                     // k_run64 or k_run64v2 (kernel_choice.h): cfg, cus and the knobs, fixed by init()
     float *d_taps = nullptr;
     float2 *d_tw = nullptr, *d_wpre = nullptr;
     StreamState st;
     float2 *d_yfirst = nullptr, *d_ylast = nullptr;
     ColdStart cold;                          // k_run64v2 without warm-up windows (Run64v2Host::cpre / rt)
-    bool v2_all = false;                     // CSDR_RUN64_V2_ALL: k_run64v2 below its size threshold too
     double v2_weight = 1.1;                  // CSDR_RUN64_WEIGHT (Run64v2Host::weight)
     TileArgs proto;
 
     int init();
-    const char *name() const override { return cfg.fm ? "k_run64<FM>" : (v2_last ? "k_run64v2" : "k_run64<CF32>"); }
-    // the call goes to k_run64v2 as whole 64-frame tiles, no mix inside the plan
-    bool tile_major_ok(uint32_t nf) const override
-    {
-        return v2_ok && !cfg.mix && !cfg.fm && (uint64_t)cfg.C * nf * 8u < (1ull << 32) && run64_v2_runs(nf, cus, v2_all) != 0;
-    }
+    KernelChoice choose(uint32_t nf) const override { return pick.choose(nf); }
+    // until the first call csdr_chain_path names k_run64, whatever a call of max_nf frames would take (the route strings are read by tools and logs)
+    KernelChoice first_choice() const override { return {K_RUN64, 0}; }
+    const char *kernel_name(int id) const override { return id == K_RUN64V2 ? "k_run64v2" : cfg.fm ? "k_run64<FM>" : "k_run64<CF32>"; }
+    bool tile_major_ok(uint32_t nf) const override { return pick.tile_major_ok(nf); }
     int reset_state(hipStream_t s) override { return st.reset(s); }
-    int run(const FusedCall &call, void *out, hipStream_t s, KernelTimer *timer) override;
+    int run(const FusedCall &call, KernelChoice k, void *out, hipStream_t s, KernelTimer *timer) override;
 };
 
 bool plan64_supported(uint32_t M, uint32_t p) { return M == (uint32_t)MS && p == (uint32_t)P; }
@@ -393,31 +391,30 @@ int SmallPlan::init()
     else (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_run64<false>, 256, 0);
     if (occ < 1) occ = 1;
     resident_wgs = cus * (uint32_t)occ;
-    v2_ok = !cfg.fm && cfg.c0 == 0 && cfg.C == (uint32_t)MS && !diag_env("CSDR_RUN64_V1");
-    v2_all = diag_env("CSDR_RUN64_V2_ALL") != nullptr;
+    pick.fm = cfg.fm; pick.mix = cfg.mix; pick.c0 = cfg.c0; pick.C = cfg.C; pick.cus = cus;
+    pick.v1 = diag_env("CSDR_RUN64_V1") != nullptr;
+    pick.v2_all = diag_env("CSDR_RUN64_V2_ALL") != nullptr;
     if (const char *e = diag_env("CSDR_RUN64_WEIGHT")) v2_weight = atof(e);
     // k_run64v2 without warm-up windows: the state hand-over array and the chain's response to a unit DC state at the channels 30..33,
     // frames 64 .. 64 + RUN64_DCFIX_F - 1 behind a halo tile's start (= the run's first output frames)
-    if (v2_ok && (r = cold.init(mem, cfg, RUN64_DCFIX_F * 64.0, 1026, 0, false, 64u, (uint32_t)RUN64_DCFIX_F, 30, wpre.data()))) return r;
+    if (pick.v2() && (r = cold.init(mem, cfg, RUN64_DCFIX_F * 64.0, 1026, 0, false, 64u, (uint32_t)RUN64_DCFIX_F, 30, wpre.data()))) return r;
     return 0;
 }
 
-int SmallPlan::run(const FusedCall &call, void *out, hipStream_t s, KernelTimer *timer)
+int SmallPlan::run(const FusedCall &call, KernelChoice k, void *out, hipStream_t s, KernelTimer *timer)
 {
     const FusedConfig &c = cfg;
     const uint32_t nf = call.nf;
     int r;
-    const uint32_t v2runs = (v2_ok && (uint64_t)c.C * nf * 8u < (1ull << 32)) ? run64_v2_runs(nf, cus, v2_all) : 0;
-    v2_last = v2runs != 0;
-    if (v2runs) {
+    if (k.id == K_RUN64V2) {
         Run64v2Host H{};
         H.x = call.d_in; H.out = (float2 *)out;
         H.taps = d_taps; H.tw = d_tw; H.wpre = d_wpre;
         H.uhist_in = st.hist_in(cur); H.uhist_out = st.hist_out(cur);
         H.vend_in = st.vend_in(cur); H.vend_out = st.vend_out(cur);
-        H.nf = nf; H.nruns = v2runs; H.parity0 = (uint32_t)(frames_done & 1);
+        H.nf = nf; H.nruns = k.runs; H.parity0 = (uint32_t)(frames_done & 1);
         H.tile_major = call.tile_major;
-        H.cpre = v2runs <= 1024u ? cold.cpre : nullptr; H.rt = cold.rt;
+        H.cpre = k.runs <= 1024u ? cold.cpre : nullptr; H.rt = cold.rt;
         H.dc = &dcc; H.weight = v2_weight;
         return run64_v2_launch(H, s, timer);
     }

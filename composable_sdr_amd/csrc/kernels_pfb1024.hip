@@ -457,36 +457,32 @@ struct BigPlan : ChainPlan {
     using ChainPlan::ChainPlan;
     float *d_taps = nullptr;
     float4 *d_taps_t = nullptr, *d_taps_q = nullptr;
-    bool v3_ok = false, v3_last = false;      // k_run1024v3 (FM, whole band) selected; used by the last call
-    bool v2_ok = false, v2_last = false;      // k_run1024v2 usable (whole band, not disabled); used by the last call
-    bool s1_ok = false, s1_last = false;      // k_shard1024<.., G> usable (interleaved shard, G = 4, 8); used by the last call
+    Choice1024 pick{};                        // which of the plan's four kernels a call takes (kernel_choice.h): cfg, cus and the knobs, fixed by init()
     int s1_mfix = -1;                         // the shard's row among the four channels around DC (k_shard1024_dcfix), -1: none
     float2 *d_tw = nullptr, *d_wpre = nullptr;
     StreamState st;
     float2 *d_scratch = nullptr;     // yfirst | ylast
     void *d_full = nullptr;          // interleaved shard, calls k_run1024v2 does not take: whole-band result [1024][max_nf] (allocated on first use)
-    ColdStart cold;                  // k_run1024v3 / k_shard1024 without warm-up windows (Run1024v2Host::cpre / side / rt)
-    uint32_t runs_v2 = 0, runs_v3 = 0, runs_s1 = 0;    // CSDR_RUN1024_RUNS, CSDR_RUN1024_V3_RUNS, CSDR_SHARD1024_RUNS (max_runs of the *_runs of fused.h)
-    double v2_weight = 1.2;          // CSDR_RUN1024_WEIGHT (Run1024v2Host::weight)
-    unsigned long long *d_trace = nullptr; std::string trace_file;      // CSDR_RUN1024_V3_TRACE / CSDR_SHARD1024_TRACE (Run1024v2Host::trace)
+    ColdStart cold;                  // k_run1024v3 / k_shard1024 without warm-up windows (Run1024Call::cpre / side / rt)
+    double v2_weight = 1.2;          // CSDR_RUN1024_WEIGHT (Run1024Call::weight)
+    unsigned long long *d_trace = nullptr; std::string trace_file;      // CSDR_RUN1024_V3_TRACE / CSDR_SHARD1024_TRACE (Run1024Call::trace)
     Pfb1024Args proto;               // what init() fixes of a k_pfb1024 launch
 
     int init();
-    const char *name() const override
+    KernelChoice choose(uint32_t nf) const override { return pick.choose(nf); }
+    const char *kernel_name(int id) const override
     {
-        if (v3_last) return cfg.fm ? "k_run1024v3<FM>" : "k_run1024v3<CF32>";
-        if (s1_last) return cfg.fm ? (cfg.G == 8 ? "k_shard1024<FM>/G8" : "k_shard1024<FM>/G4") : (cfg.G == 8 ? "k_shard1024<CF32>/G8" : "k_shard1024<CF32>/G4");
-        if (v2_last) return cfg.G == 8 ? "k_run1024v2<FM>/G8" : cfg.G == 4 ? "k_run1024v2<FM>/G4" : cfg.G == 2 ? "k_run1024v2<FM>/G2" : "k_run1024v2<FM>";
-        return cfg.fm ? "k_run1024<FM>" : "k_run1024<CF32>";
+        const bool g8 = cfg.G == 8;
+        switch (id) {
+        case K_RUN1024V3: return cfg.fm ? "k_run1024v3<FM>" : "k_run1024v3<CF32>";
+        case K_SHARD1024: return cfg.fm ? (g8 ? "k_shard1024<FM>/G8" : "k_shard1024<FM>/G4") : (g8 ? "k_shard1024<CF32>/G8" : "k_shard1024<CF32>/G4");
+        case K_RUN1024V2: return g8 ? "k_run1024v2<FM>/G8" : cfg.G == 4 ? "k_run1024v2<FM>/G4" : cfg.G == 2 ? "k_run1024v2<FM>/G2" : "k_run1024v2<FM>";
+        default: return cfg.fm ? "k_run1024<FM>" : "k_run1024<CF32>";
+        }
     }
-    // CF32 output through k_run1024v3<CF32> (whole band) or k_shard1024<CF32, G> (interleaved shard)
-    bool tile_major_ok(uint32_t nf) const override
-    {
-        if (s1_ok) return !cfg.fm && !cfg.mix && nf % 16u == 0 && shard1024_runs(nf, false, cfg.G, cus, runs_s1) != 0;
-        return v3_ok && !cfg.fm && !cfg.mix && nf % 16u == 0 && (uint64_t)nf * 8192u < (1ull << 31) && run1024_v3_runs(nf, false, cus, runs_v3) != 0;
-    }
+    bool tile_major_ok(uint32_t nf) const override { return pick.tile_major_ok(nf); }
     int reset_state(hipStream_t s) override { return st.reset(s); }
-    int run(const FusedCall &call, void *out, hipStream_t s, KernelTimer *timer) override;
+    int run(const FusedCall &call, KernelChoice k, void *out, hipStream_t s, KernelTimer *timer) override;
 };
 
 bool plan1024_supported(uint32_t M, uint32_t p) { return M == (uint32_t)PM && p == (uint32_t)PP && !diag_env("CSDR_NO_RUN1024"); }
@@ -540,31 +536,22 @@ int BigPlan::init()
             tq[(size_t)PM * 16 + 2 * (size_t)r] = wpre[PM + r].x; tq[(size_t)PM * 16 + 2 * (size_t)r + 1] = wpre[PM + r].y;
         }
         CSDR_HIP(hipMemcpy(d_taps_q, tq.data(), sizeof(float) * tq.size(), hipMemcpyHostToDevice));
-        // whole band, calls of whole 4-frame tiles: k_run1024v3 (CSDR_RUN1024_V3=0: k_run1024 for the comparison); a call that ends inside
-        // a 128-byte line stores the front part of it
-        const bool v1 = diag_env("CSDR_RUN1024_V1") != nullptr;
-        const char *e3 = diag_env("CSDR_RUN1024_V3");
-        v3_ok = cfg.c0 == 0 && cfg.C == (uint32_t)PM && cfg.G == 1 && !v1 && !(e3 && atoi(e3) == 0);
-        // k_run1024v2: the interleaved shards only (FM output; its whole-band instantiations are no longer built); CF32 shards: whole band + row gather (below)
-        v2_ok = cfg.G > 1 && cfg.fm && !v1;
-        // k_shard1024<FM | CF32, G>: every run-sized call of whole tiles (CSDR_NO_SHARD1024: k_run1024v2<FM, G> or whole band + gather instead)
-        s1_ok = (cfg.G == 4 || cfg.G == 8) && !v1 && !diag_env("CSDR_NO_SHARD1024");
-        if (const char *e = diag_env("CSDR_RUN1024_RUNS")) runs_v2 = (uint32_t)atoi(e);
-        if (const char *e = diag_env("CSDR_RUN1024_V3_RUNS")) runs_v3 = (uint32_t)atoi(e);
-        if (const char *e = diag_env("CSDR_SHARD1024_RUNS")) runs_s1 = (uint32_t)atoi(e);
+        // the inputs of the kernel choice (Choice1024, kernel_choice.h)
+        pick.fm = cfg.fm; pick.mix = cfg.mix; pick.c0 = cfg.c0; pick.C = cfg.C; pick.G = cfg.G; pick.cus = cus;
+        pick.v1 = diag_env("CSDR_RUN1024_V1") != nullptr;
+        { const char *e3 = diag_env("CSDR_RUN1024_V3"); pick.v3_off = e3 && atoi(e3) == 0; }
+        pick.no_shard = diag_env("CSDR_NO_SHARD1024") != nullptr;
+        if (const char *e = diag_env("CSDR_RUN1024_RUNS")) pick.runs_v2 = (uint32_t)atoi(e);
+        if (const char *e = diag_env("CSDR_RUN1024_V3_RUNS")) pick.runs_v3 = (uint32_t)atoi(e);
+        if (const char *e = diag_env("CSDR_SHARD1024_RUNS")) pick.runs_s1 = (uint32_t)atoi(e);
         if (const char *e = diag_env("CSDR_RUN1024_WEIGHT")) v2_weight = atof(e);
-        // until the first call: the kernel a call of max_nf frames would take (csdr_chain_path names it)
-        s1_last = s1_ok && shard1024_runs(cfg.max_nf, cfg.fm, cfg.G, cus, runs_s1) != 0;
-        v2_last = !s1_last && v2_ok && (cfg.max_nf & 3u) == 0 && run1024_v2_runs(cfg.max_nf, cus, runs_v2) != 0;
-        v3_last = v3_ok && run1024_v3_runs(cfg.max_nf, cfg.fm, cus, runs_v3) != 0;
-        if (v3_last) v2_last = false;
         // debug builds (-DB3_TRACE / -DS1_TRACE): the stamp buffer of the plan's run kernel and the file its launcher writes
-        if (const char *e = v3_ok ? diag_env("CSDR_RUN1024_V3_TRACE") : s1_ok ? diag_env("CSDR_SHARD1024_TRACE") : nullptr) {
+        if (const char *e = pick.v3() ? diag_env("CSDR_RUN1024_V3_TRACE") : pick.shard() ? diag_env("CSDR_SHARD1024_TRACE") : nullptr) {
             trace_file = e;
-            if ((rc = mem.alloc_n(&d_trace, v3_ok ? RUN1024_V3_TRACE_N : SHARD1024_TRACE_N))) return rc;
+            if ((rc = mem.alloc_n(&d_trace, pick.v3() ? RUN1024_V3_TRACE_N : SHARD1024_TRACE_N))) return rc;
         }
     }
-    if (s1_ok) {
+    if (pick.shard()) {
         // k_shard1024 without warm-up windows (as k_run1024v3 below): the state hand-over between the runs, the side copies of the ONE owned channel
         // among the four around DC (510 .. 513; primed k' = k - g, row k' / G -- none for the shards 2 .. 5 of 8), and the chain's response to a
         // unit DC state there (computed on the plan's phasor table, which carries the shard's shift: the primed spectrum; channel 0 of the
@@ -578,7 +565,7 @@ int BigPlan::init()
     // k_run1024v3's state hand-over and the side copies of the four channels around DC (510..513): the kernel always writes them (a few
     // hundred bytes per run); launches without warm-up windows (dc_block, not CSDR_NOWU=0) also get the chain's response to a unit DC state
     // at those channels, frames 15 .. 47 behind a cold start (= frame -1 .. 31 of the run).  Window: halo + 32-frame dcfix
-    if (v3_ok && (rc = cold.init(mem, cfg, 35 * 1024.0, cus + 2, (size_t)(cus + 1) * 4 * RUN1024_DCFIX_F, true, 15u, (uint32_t)RUN1024_DCFIX_F,
+    if (pick.v3() && (rc = cold.init(mem, cfg, 35 * 1024.0, cus + 2, (size_t)(cus + 1) * 4 * RUN1024_DCFIX_F, true, 15u, (uint32_t)RUN1024_DCFIX_F,
                                  510, wpre.data()))) return rc;
     // k_run1024 (the calls no run kernel above takes)
     proto = Pfb1024Args{};
@@ -591,35 +578,34 @@ int BigPlan::init()
     return 0;
 }
 
-int BigPlan::run(const FusedCall &call, void *out, hipStream_t s, KernelTimer *timer)
+int BigPlan::run(const FusedCall &call, KernelChoice k, void *out, hipStream_t s, KernelTimer *timer)
 {
     const FusedConfig &c = cfg;
     const uint32_t nf = call.nf;
     int r;
-    const uint32_t s1runs = s1_ok ? shard1024_runs(nf, c.fm, c.G, cus, runs_s1) : 0;
-    s1_last = s1runs != 0;
-    const uint32_t v2runs = (!s1runs && v2_ok && (nf & 3u) == 0 && (uint64_t)nf * 8192u < (1ull << 31)) ? run1024_v2_runs(nf, cus, runs_v2) : 0;
-    v2_last = v2runs != 0;
-    const uint32_t v3runs = (v3_ok && (uint64_t)nf * 8192u < (1ull << 31)) ? run1024_v3_runs(nf, c.fm, cus, runs_v3) : 0;
-    v3_last = v3runs != 0;
-    if (v3runs) v2_last = false;
-    if (v2runs || v3runs || s1runs) {
-        Run1024v2Host H{};
+    if (k.id != K_RUN1024) {
+        Run1024Call H{};
         H.x = call.d_in; H.out = out; H.taps_q = d_taps_q; H.tw = d_tw;
         H.uhist_in = st.hist_in(cur); H.uhist_out = st.hist_out(cur);
         H.vend_in = st.vend_in(cur); H.vend_out = st.vend_out(cur);
         H.rp_in = st.rp_in(cur); H.rp_out = st.rp_out(cur);
-        H.nf = nf; H.nruns = v2runs; H.parity0 = (uint32_t)(frames_done & 1);
-        H.G = c.G; H.g = c.G > 1 ? c.c0 : 0u;
-        H.tile_major = call.tile_major && (v3runs || s1runs) && !c.fm;
+        H.nf = nf; H.nruns = k.runs; H.parity0 = (uint32_t)(frames_done & 1);
+        H.fm = c.fm; H.G = c.G; H.g = c.G > 1 ? c.c0 : 0u;
+        H.tile_major = call.tile_major;      // (process() has checked tile_major_ok: CF32 through k_run1024v3 or k_shard1024)
         H.dc = &dcc; H.fm_ref = c.fm_ref; H.weight = v2_weight;
         if (d_trace) { H.trace = d_trace; H.trace_file = trace_file.c_str(); }
-        if (v3runs) { H.cpre = cold.cpre; H.side = cold.side; H.rt = v3runs <= cus ? cold.rt : nullptr; }
-        if (s1runs) { H.cpre = cold.cpre; H.side = cold.side; H.rt = cold.rt; H.mfix = s1_mfix; }
-        if (s1runs) return shard1024_launch(H, c.fm, s1runs, s, timer);
-        if (v3runs) return run1024_v3_launch(H, c.fm, v3runs, s, timer);
-        return run1024_v2_launch(H, c.fm, s, timer);
+        switch (k.id) {
+        case K_SHARD1024:
+            H.cpre = cold.cpre; H.side = cold.side; H.rt = cold.rt; H.mfix = s1_mfix;
+            return shard1024_launch(H, s, timer);
+        case K_RUN1024V3:
+            H.cpre = cold.cpre; H.side = cold.side; H.rt = k.runs <= cus ? cold.rt : nullptr;
+            return run1024_v3_launch(H, s, timer);
+        default:
+            return run1024_v2_launch(H, s, timer);
+        }
     }
+    // k_run1024: the calls no run kernel takes
     Pfb1024Args A = proto;
     A.u = call.d_in; A.out = out;
     const bool shard = c.G > 1;
@@ -634,10 +620,7 @@ int BigPlan::run(const FusedCall &call, void *out, hipStream_t s, KernelTimer *t
     A.uhist_in = st.hist_in(cur); A.uhist_out = st.hist_out(cur);
     A.nf = nf; A.nb = (nf + PT - 1) / PT; A.c0 = shard ? 0u : c.c0; A.C = shard ? (uint32_t)PM : c.C;
     A.parity0 = (uint32_t)(frames_done & 1);
-    // one run per CU, at least 8 tiles per run (a run >= 1 spends 3 read-only + 2 halo tiles on its start state)
-    uint32_t nruns = cus;
-    if (nruns > A.nb / 8) nruns = A.nb / 8;
-    if (nruns < 1) nruns = 1;
+    const uint32_t nruns = k.runs;
     A.nruns = nruns; A.yfirst = d_scratch; A.ylast = d_scratch + (size_t)nruns * PM;
     if (timer && (r = timer->begin(s))) return r;
     if (c.fm) hipLaunchKernelGGL((k_pfb1024<true, true>), dim3(nruns), dim3(1024), 0, s, A);

@@ -416,10 +416,14 @@ struct HugePlan : ChainPlan {
     float4 *d_tail[2] = {nullptr, nullptr};
     float *d_part = nullptr;
     uint32_t runs_knob = 0;          // CSDR_RUN4096_RUNS: the run count before huge_runs shortens it (0: cus / 4)
-    std::string kernel;
 
     int init();
-    const char *name() const override { return kernel.c_str(); }
+    // one kernel sequence: the choice is the front kernel's run count
+    KernelChoice choose(uint32_t nf) const override { return {0, huge_runs(nf, cus, runs_knob)}; }
+    const char *kernel_name(int) const override
+    {
+        return cfg.mix ? "k_front4096+k_back4096<FM,mix>" : (cfg.fm ? "k_front4096+k_back4096<FM>" : "k_front4096+k_back4096<CF32>");
+    }
     // CF32 output, whole 16-frame blocks, no mix inside the plan
     bool tile_major_ok(uint32_t nf) const override { return !cfg.fm && !cfg.mix && nf && (nf & 15u) == 0; }
     int reset_state(hipStream_t s) override
@@ -427,7 +431,7 @@ struct HugePlan : ChainPlan {
         CSDR_HIP(hipMemsetAsync(d_tail[0], 0, sizeof(float4) * 2048 * H_COLD, s));
         return 0;
     }
-    int run(const FusedCall &call, void *out, hipStream_t s, KernelTimer *timer) override;
+    int run(const FusedCall &call, KernelChoice k, void *out, hipStream_t s, KernelTimer *timer) override;
 };
 
 bool plan4096_supported(uint32_t M, uint32_t p) { return M == (uint32_t)H_M && p == (uint32_t)P && !diag_env("CSDR_NO_RUN4096"); }
@@ -456,20 +460,10 @@ int HugePlan::init()
     CSDR_HIP(hipMemcpy(d_tw, tw.data(), sizeof(float2) * tw.size(), hipMemcpyHostToDevice));
     CSDR_HIP(hipMemset(d_tail[0], 0, sizeof(float4) * 2048 * H_COLD));
     if (const char *e = diag_env("CSDR_RUN4096_RUNS")) runs_knob = (uint32_t)atoi(e);
-    kernel = cfg.mix ? "k_front4096+k_back4096<FM,mix>" : (cfg.fm ? "k_front4096+k_back4096<FM>" : "k_front4096+k_back4096<CF32>");
     return 0;
 }
 
-// frames per run: long enough that the 19 cold-start frames (about 8 frames' worth of work) stay below ~8 % of a run
-static uint32_t huge_runs(uint32_t nf, uint32_t cus, uint32_t runs_knob)
-{
-    uint32_t nruns = runs_knob >= 1 ? runs_knob : cus / 4;      // 4 siblings per run, one 512-thread workgroup per CU
-    while (nruns > 1 && nf / nruns < 48) nruns >>= 1;    // (a run pays 20 cold-start frames: the reference chunk of 4096 frames is 64 runs of 64)
-    if (nruns > 8) nruns &= ~7u;                        // the XCD-friendly workgroup -> (run, sibling) map wants a multiple of 8
-    return nruns ? nruns : 1;
-}
-
-int HugePlan::run(const FusedCall &call, void *out, hipStream_t s, KernelTimer *timer)
+int HugePlan::run(const FusedCall &call, KernelChoice k, void *out, hipStream_t s, KernelTimer *timer)
 {
     const FusedConfig &c = cfg;
     const uint32_t nf = call.nf;
@@ -477,7 +471,7 @@ int HugePlan::run(const FusedCall &call, void *out, hipStream_t s, KernelTimer *
     Front4096Args A{};
     A.x = reinterpret_cast<const float4 *>(call.d_in); A.tail = d_tail[cur]; A.z = d_z;
     A.taps = d_taps; A.wpre = d_wpre; A.tw4 = d_tw4;
-    A.nf = nf; A.nruns = huge_runs(nf, cus, runs_knob); A.parity0 = (uint32_t)(frames_done & 1u);
+    A.nf = nf; A.nruns = k.runs; A.parity0 = (uint32_t)(frames_done & 1u);
     dcc.put(A);
     int r;
     if (timer && (r = timer->begin(s))) return r;

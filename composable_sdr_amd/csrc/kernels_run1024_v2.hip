@@ -121,30 +121,10 @@ __global__ __launch_bounds__(256, 2) void k_run1024v2(Run1024v2Args A)
         const unsigned h0 = tile_begin - B2_WU;
         float2 acc = make_float2(0.f, 0.f);
         {
-            // round 3 (as k_run256v2): the six tiles in ONE batch of loads (the window's registers are not live yet), weights of my
-            // pieces as a running product: beta^(4095 - n), n = n0 + 512 it
+            // round 3 (as k_run256v2): the six tiles in ONE batch of loads (the window's registers are not live yet)
             float4 raw[8], rb[8], rc[8], rd[8], re[8], rf[8];
-            float wt0, wt1;
-            {
-                const int wave = tid >> 6, lane = tid & 63;
-                const int slot = 64 * wave + lane, q = slot >> 3;
-                const int i = (slot & 7) ^ ((q >> 1) & 7);
-                const int n = 16 * q + 2 * i;
-                wt0 = exp2f((float)(4095 - n) * A.l2beta);
-                wt1 = exp2f((float)(4094 - n) * A.l2beta);
-            }
-            const float wstep = A.l2beta < -100.0f ? 0.0f : exp2f(-512.0f * A.l2beta);
-            auto fold = [&](const float4 (&r)[8]) {
-                float2 p = make_float2(0.f, 0.f);
-                float a0 = wt0, a1 = wt1;
-#pragma unroll
-                for (int it = 0; it < 8; it++) {
-                    p = cfma(make_float2(r[it].x, r[it].y), a0, p);
-                    p = cfma(make_float2(r[it].z, r[it].w), a1, p);
-                    a0 *= wstep; a1 *= wstep;
-                }
-                acc = cfma(acc, A.b256[16], p);
-            };
+            const DcWarmup wu(tid, A.l2beta);
+            auto fold = [&](const float4 (&r)[8]) { acc = cfma(acc, A.b256[16], wu.tile(r)); };
             static_assert(B2_WU == 6, "one batch of six warm-up tiles");
             tile_load(x4 + (size_t)h0 * 2048, 256, raw, tid); tile_load(x4 + (size_t)(h0 + 1) * 2048, 256, rb, tid);
             tile_load(x4 + (size_t)(h0 + 2) * 2048, 256, rc, tid); tile_load(x4 + (size_t)(h0 + 3) * 2048, 256, rd, tid);
@@ -440,23 +420,17 @@ __global__ __launch_bounds__(256, 2) void k_run1024v2(Run1024v2Args A)
 
 }  // namespace
 
-// one launch per call (called by big_process, kernels_pfb1024.hip); no fix-up kernel: a run computes the frame in front of it itself
-int run1024_v2_launch(const Run1024v2Host &h, bool fm, hipStream_t s, KernelTimer *timer)
+int run1024_v2_launch(const Run1024Call &h, hipStream_t s, KernelTimer *timer)
 {
+    static_assert(B2_T4 == 4, "put_run1024: tiles of four frames");
     Run1024v2Args A{};
-    A.x = h.x; A.out = h.out; A.taps_q = h.taps_q; A.tw = h.tw;
-    A.uhist_in = h.uhist_in; A.uhist_out = h.uhist_out; A.vend_in = h.vend_in; A.vend_out = h.vend_out;
-    A.rp_in = h.rp_in; A.rp_out = h.rp_out;
-    A.nf = h.nf; A.nb = h.nf / B2_T4; A.nruns = h.nruns; A.parity0 = h.parity0; A.out_stride = h.nf;
+    put_run1024(h, A);
+    A.out_stride = h.nf; A.g = h.g;
     const double wt = h.weight;
     A.n0 = (h.nruns >= 2 && !(h.nruns & 1u) && wt > 1.0 && wt < 1.5) ? (uint32_t)std::llround(0.5 * wt * (double)A.nb) : 0u;
-    h.dc->put(A);
-    A.fm_ref = h.fm_ref; A.tiny = 1e-37f;
-    A.pk = phase_consts_scaled(h.fm_ref);               // unscaled polynomial (fm_quad scales a = min / max by ref)
     int r;
     if (timer && (r = timer->begin(s))) return r;
-    A.g = h.g;
-    if (h.G > 1 && !fm) { set_error("k_run1024v2: interleaved shards have F32 output only"); return -1; }
+    if (h.G > 1 && !h.fm) { set_error("k_run1024v2: interleaved shards have F32 output only"); return -1; }
     if (h.G == 2) hipLaunchKernelGGL((k_run1024v2<true, 2>), dim3(h.nruns), dim3(256), 0, s, A);
     else if (h.G == 4) hipLaunchKernelGGL((k_run1024v2<true, 4>), dim3(h.nruns), dim3(256), 0, s, A);
     else if (h.G == 8) hipLaunchKernelGGL((k_run1024v2<true, 8>), dim3(h.nruns), dim3(256), 0, s, A);
@@ -465,18 +439,6 @@ int run1024_v2_launch(const Run1024v2Host &h, bool fm, hipStream_t s, KernelTime
     if (timer && (r = timer->end(s))) return r;
     CSDR_HIP(hipGetLastError());
     return 0;
-}
-
-uint32_t run1024_v2_runs(uint32_t nf, uint32_t cus, uint32_t max_runs)
-{
-    // two workgroups per CU; a run >= 1 spends 6 read-only + 4 halo tiles on its start state; the shorter (younger) runs get
-    // up to 1/4 less than the average: at least 24 tiles per run on average (>= 16 for every one)
-    const uint32_t nb = nf / B2_T4;
-    uint32_t nruns = 2 * cus;
-    if (max_runs >= 1 && max_runs < nruns) nruns = max_runs;
-    if (nruns > nb / 24) nruns = nb / 24;
-    if (nruns > 2) nruns &= ~1u;
-    return nruns;                                       // 0: too short for this kernel
 }
 
 }  // namespace csdr

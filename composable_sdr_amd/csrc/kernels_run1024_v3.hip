@@ -127,27 +127,8 @@ __global__ __launch_bounds__(512) void k_run1024v3(Run1024v3Args A)
             // others -- and takes the rest from the stream's state below, which is then exact
             const int h0 = (int)tile_begin - B3_WU;
             float4 raw[8], rb[8], rc[8], rd[8], re[8], rf[8];
-            float wt0, wt1;
-            {
-                const int wave = lt >> 6, lane = lt & 63;
-                const int slot = 64 * wave + lane, q = slot >> 3;
-                const int i = (slot & 7) ^ ((q >> 1) & 7);
-                const int n = 16 * q + 2 * i;
-                wt0 = exp2f((float)(4095 - n) * A.l2beta);
-                wt1 = exp2f((float)(4094 - n) * A.l2beta);
-            }
-            const float wstep = A.l2beta < -100.0f ? 0.0f : exp2f(-512.0f * A.l2beta);
-            auto fold = [&](const float4 (&r)[8]) {
-                float2 p = make_float2(0.f, 0.f);
-                float a0 = wt0, a1 = wt1;
-#pragma unroll
-                for (int it = 0; it < 8; it++) {
-                    p = cfma(make_float2(r[it].x, r[it].y), a0, p);
-                    p = cfma(make_float2(r[it].z, r[it].w), a1, p);
-                    a0 *= wstep; a1 *= wstep;
-                }
-                acc = cfma(acc, A.b256[16], p);
-            };
+            const DcWarmup wu(lt, A.l2beta);
+            auto fold = [&](const float4 (&r)[8]) { acc = cfma(acc, A.b256[16], wu.tile(r)); };
             static_assert(B3_WU == 6, "one batch of six warm-up tiles");
             auto wload = [&](int t, float4 (&r)[8]) { tile_load(x4 + (size_t)(t > 0 ? t : 0) * 2048, t >= 0 ? 256 : 0, r, lt); };
             wload(h0, raw); wload(h0 + 1, rb); wload(h0 + 2, rc); wload(h0 + 3, rd); wload(h0 + 4, re); wload(h0 + 5, rf);
@@ -563,18 +544,17 @@ __global__ __launch_bounds__(128) void k_run1024_dcfix(Run1024v3Args A, const fl
 
 }  // namespace
 
-int run1024_v3_launch(const Run1024v2Host &h, bool fm, uint32_t nruns, hipStream_t s, KernelTimer *timer)
+int run1024_v3_launch(const Run1024Call &h, hipStream_t s, KernelTimer *timer)
 {
+    static_assert(B3_T4 == 4, "put_run1024: tiles of four frames");
+    const bool fm = h.fm;
+    const uint32_t nruns = h.nruns;
     Run1024v3Args A{};
-    A.x = h.x; A.out = h.out; A.taps_q = h.taps_q; A.tw = h.tw;
-    A.uhist_in = h.uhist_in; A.uhist_out = h.uhist_out; A.vend_in = h.vend_in; A.vend_out = h.vend_out;
-    A.rp_in = h.rp_in; A.rp_out = h.rp_out;
-    A.nf = h.nf; A.nb = h.nf / B3_T4; A.nruns = nruns; A.parity0 = h.parity0; A.tile_major = (!fm && h.tile_major) ? 1u : 0u;
-    h.dc->put(A);
-    A.fm_ref = h.fm_ref; A.tiny = 1e-37f;
-    A.pk = phase_consts_scaled(h.fm_ref);               // unscaled polynomial (fm_quad scales a = min / max by ref)
-    if (h.trace) { CSDR_HIP(hipMemsetAsync(h.trace, 0, RUN1024_V3_TRACE_N * sizeof(unsigned long long), s)); A.trace = h.trace; }
+    put_run1024(h, A);
+    A.tile_major = (!fm && h.tile_major) ? 1u : 0u;
+    A.trace = h.trace;
     int r;
+    if ((r = h.trace_dump(RUN1024_V3_TRACE_N, true, s))) return r;
     if (timer && (r = timer->begin(s))) return r;
     // no warm-up windows: whole runs of >= 16 tiles (a cold start is 4 tiles deep and the correction covers 4 more), the state arrays there
     if (!h.cpre || !h.side) { set_error("run1024_v3_launch: internal: no state arrays"); return -1; }
@@ -588,27 +568,8 @@ int run1024_v3_launch(const Run1024v2Host &h, bool fm, uint32_t nruns, hipStream
     }
     if (timer && (r = timer->end(s))) return r;         // the bracket covers the correction kernel: it is part of every no-warm-up step
     CSDR_HIP(hipGetLastError());
-    if (h.trace) {                                      // debug: the last launch's stamps, raw uint64: front [128][8], back [128][4]
-        std::vector<unsigned long long> hbuf(RUN1024_V3_TRACE_N);
-        CSDR_HIP(hipStreamSynchronize(s));
-        CSDR_HIP(hipMemcpy(hbuf.data(), h.trace, hbuf.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-        if (FILE *f = fopen(h.trace_file, "wb")) { fwrite(hbuf.data(), sizeof(unsigned long long), hbuf.size(), f); fclose(f); }
-    }
-    return 0;
+    return h.trace_dump(RUN1024_V3_TRACE_N, false, s);  // debug: front [128][8], back [128][4]
 }
-
-uint32_t run1024_v3_runs(uint32_t nf, bool fm, uint32_t cus, uint32_t max_runs)
-{
-    const uint32_t B3_TB = fm ? B3_TBF : B3_TBC;
-    // one workgroup per CU; runs are whole blocks of 8 (F32) / 4 (CF32) tiles (a row's 128-byte line), at least one (a run >= 1 walks 4
-    // halo tiles in front of its first tile and folds the up to 6 tiles in front of those: short calls get as many runs as they have
-    // blocks); the call's last block may be partial (nf = 0 mod 4: whole tiles)
-    if (nf % B3_T4) return 0;
-    const uint32_t nblk = (nf / B3_T4 + B3_TB - 1) / B3_TB;
-    uint32_t nruns = cus;
-    if (max_runs >= 1 && max_runs < nruns) nruns = max_runs;
-    if (nruns > nblk) nruns = nblk;
-    return nruns;                                       // 0: a ragged call (not whole 4-frame tiles)
-}
+static_assert(B3_TBF == 8 && B3_TBC == 4, "run1024_v3_runs (kernel_choice.h): runs of whole blocks of 8 (F32) / 4 (CF32) tiles");
 
 }  // namespace csdr

@@ -98,28 +98,8 @@ __global__ __launch_bounds__(256, 2) void k_run64v2(Run64v2Args A)
         float2 acc = make_float2(0.f, 0.f);
         {
             float4 raw[8];
-            // weight of my piece `it` of a tile: beta^(4095 - n), n = n0 + 512 it: a running product (two registers instead of sixteen)
-            float wt0, wt1;
-            {
-                const int wave = tid >> 6, lane = tid & 63;
-                const int slot = 64 * wave + lane, q = slot >> 3;
-                const int i = (slot & 7) ^ ((q >> 1) & 7);
-                const int n = 16 * q + 2 * i;
-                wt0 = exp2f((float)(4095 - n) * A.l2beta);
-                wt1 = exp2f((float)(4094 - n) * A.l2beta);
-            }
-            const float wstep = A.l2beta < -100.0f ? 0.0f : exp2f(-512.0f * A.l2beta);
-            auto fold = [&](const float4 (&r)[8]) {
-                float2 p = make_float2(0.f, 0.f);
-                float a0 = wt0, a1 = wt1;
-#pragma unroll
-                for (int it = 0; it < 8; it++) {
-                    p = cfma(make_float2(r[it].x, r[it].y), a0, p);
-                    p = cfma(make_float2(r[it].z, r[it].w), a1, p);
-                    a0 *= wstep; a1 *= wstep;
-                }
-                acc = cfma(acc, A.b256[16], p);
-            };
+            const DcWarmup wu(tid, A.l2beta);
+            auto fold = [&](const float4 (&r)[8]) { acc = cfma(acc, A.b256[16], wu.tile(r)); };
             unsigned t = h0;
             if (tile_begin - h0 == (unsigned)S2_WU) {   // the usual window: six tiles in one batch of loads (one memory latency, not six)
                 float4 rb[8], rc[8], rd[8], re[8], rf[8];
@@ -338,20 +318,6 @@ __global__ __launch_bounds__(256) void k_run64_dcfix(Run64v2Args A, const float2
 }
 
 }  // namespace
-
-uint32_t run64_v2_runs(uint32_t nf, uint32_t cus, bool all)
-{
-    // two workgroups per CU; a run >= 1 reads 6 warm-up tiles and walks a halo tile: at least 16 tiles per run on average.  A call pays
-    // those ~23 tile times (~60 us) whatever its size, so k_run64 keeps the calls below 3072 tiles (196 608 frames; measured by call size:
-    // 4096 frames 17 us against 60 us, 131 072 frames 58 against 66, 262 144 frames 99 against 76)
-    if (nf % 64u) return 0;
-    const uint32_t nb = nf / 64u;
-    if (nb < 3072u && !all) return 0;
-    uint32_t nruns = 2 * cus;
-    if (nruns > nb / 16) nruns = nb / 16;
-    if (nruns > 2) nruns &= ~1u;
-    return nruns;                                       // 0: not a call for this kernel
-}
 
 int run64_v2_launch(const Run64v2Host &h, hipStream_t s, KernelTimer *timer)
 {

@@ -161,27 +161,8 @@ __global__ __launch_bounds__(512) void k_shard1024(Shard1024Args A)
             // the stream's state below, which is then exact
             const int h0 = (int)tile_begin - S1_WU;
             float4 raw[8], rb[8], rc[8], rd[8], re[8], rf[8];
-            float wt0, wt1;
-            {
-                const int wave = lt >> 6, lane = lt & 63;
-                const int slot = 64 * wave + lane, q = slot >> 3;
-                const int i = (slot & 7) ^ ((q >> 1) & 7);
-                const int n = 16 * q + 2 * i;
-                wt0 = exp2f((float)(4095 - n) * A.l2beta);
-                wt1 = exp2f((float)(4094 - n) * A.l2beta);
-            }
-            const float wstep = A.l2beta < -100.0f ? 0.0f : exp2f(-512.0f * A.l2beta);
-            auto fold = [&](const float4 (&r)[8]) {
-                float2 p = make_float2(0.f, 0.f);
-                float a0 = wt0, a1 = wt1;
-#pragma unroll
-                for (int it = 0; it < 8; it++) {
-                    p = cfma(make_float2(r[it].x, r[it].y), a0, p);
-                    p = cfma(make_float2(r[it].z, r[it].w), a1, p);
-                    a0 *= wstep; a1 *= wstep;
-                }
-                acc = cfma(acc, A.b256[16], p);
-            };
+            const DcWarmup wu(lt, A.l2beta);
+            auto fold = [&](const float4 (&r)[8]) { acc = cfma(acc, A.b256[16], wu.tile(r)); };
             static_assert(S1_WU == 6, "one batch of six warm-up tiles");
             auto wload = [&](int t, float4 (&r)[8]) { tile_load(x4 + (size_t)(t > 0 ? t : 0) * 2048, t >= 0 ? 256 : 0, r, lt); };
             wload(h0, raw); wload(h0 + 1, rb); wload(h0 + 2, rc); wload(h0 + 3, rd); wload(h0 + 4, re); wload(h0 + 5, rf);
@@ -553,36 +534,20 @@ __global__ __launch_bounds__(64) void k_shard1024_dcfix(Shard1024Args A, const f
 
 }  // namespace
 
-// whole 4-frame tiles; at least two blocks (16 / 8 tiles) per run: a run >= 1 spends six read-only tiles and four halo tiles on its start
-uint32_t shard1024_runs(uint32_t nf, bool fm, uint32_t G, uint32_t cus, uint32_t max_runs)
+int shard1024_launch(const Run1024Call &h, hipStream_t s, KernelTimer *timer)
 {
-    if ((G != 4 && G != 8) || (nf & 3u) || nf == 0) return 0;
-    const uint32_t nb = nf / 4, TB = fm ? 8u : 4u, nblk = (nb + TB - 1) / TB;
-    if ((uint64_t)(1024 / G) * nf * (fm ? 4u : 8u) >= (1ull << 31)) return 0;       // the row stores use 32-bit buffer offsets
-    uint32_t nruns = cus;
-    if (max_runs >= 1 && max_runs < nruns) nruns = max_runs;
-    const uint32_t per = fm ? 2u : 4u;                  // >= 16 tiles per run
-    if (nruns > nblk / per) nruns = nblk / per;
-    return nruns;                                       // 0: too short for this kernel
-}
-
-int shard1024_launch(const Run1024v2Host &h, bool fm, uint32_t nruns, hipStream_t s, KernelTimer *timer)
-{
+    const bool fm = h.fm;
+    const uint32_t nruns = h.nruns;
     Shard1024Args A{};
-    A.x = h.x; A.out = h.out; A.taps_q = h.taps_q; A.tw = h.tw;
-    A.uhist_in = h.uhist_in; A.uhist_out = h.uhist_out; A.vend_in = h.vend_in; A.vend_out = h.vend_out;
-    A.rp_in = h.rp_in; A.rp_out = h.rp_out;
-    A.nf = h.nf; A.nb = h.nf / 4; A.nruns = nruns; A.parity0 = h.parity0; A.tile_major = (!fm && h.tile_major) ? 1u : 0u;
+    put_run1024(h, A);
+    A.tile_major = (!fm && h.tile_major) ? 1u : 0u;
     if (A.tile_major && (h.nf & 15u)) { set_error("k_shard1024: a tile-major plane takes whole 16-frame blocks"); return -1; }
-    h.dc->put(A);
-    A.fm_ref = h.fm_ref; A.tiny = 1e-37f;
-    A.pk = phase_consts_scaled(h.fm_ref);               // unscaled polynomial (fm_quad scales a = min / max by ref)
-    unsigned long long *const trace = S1_TRACE ? h.trace : nullptr;
-    if (trace) { CSDR_HIP(hipMemsetAsync(trace, 0, SHARD1024_TRACE_N * sizeof(unsigned long long), s)); A.trace = trace; }
+    A.trace = S1_TRACE ? h.trace : nullptr;             // (the stamps of a debug build only)
+    int r;
+    if (A.trace && (r = h.trace_dump(SHARD1024_TRACE_N, true, s))) return r;
     // no warm-up windows: whole runs of >= 16 tiles (a cold start is 4 tiles deep and the correction covers 8 more), the state arrays there
     A.nowu = (h.rt && h.cpre && h.side && nruns >= 2) ? 1u : 0u;      // (rt: the blocker is on)
     A.cpre = h.cpre; A.side = h.side; A.mfix = h.mfix;
-    int r;
     if (timer && (r = timer->begin(s))) return r;
     if (h.G == 8) {
         if (fm) hipLaunchKernelGGL((k_shard1024<true, 8>), dim3(nruns), dim3(512), 0, s, A);
@@ -597,13 +562,7 @@ int shard1024_launch(const Run1024v2Host &h, bool fm, uint32_t nruns, hipStream_
     }
     if (timer && (r = timer->end(s))) return r;         // (the bracket covers the correction kernel)
     CSDR_HIP(hipGetLastError());
-    if (trace) {                                        // debug: the last launch's stamps, raw uint64 [role][96][4]
-        std::vector<unsigned long long> hbuf(SHARD1024_TRACE_N);
-        CSDR_HIP(hipStreamSynchronize(s));
-        CSDR_HIP(hipMemcpy(hbuf.data(), trace, hbuf.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-        if (FILE *f = fopen(h.trace_file, "wb")) { fwrite(hbuf.data(), sizeof(unsigned long long), hbuf.size(), f); fclose(f); }
-    }
-    return 0;
+    return A.trace ? h.trace_dump(SHARD1024_TRACE_N, false, s) : 0;     // debug: [role][96][4]
 }
 
 }  // namespace csdr

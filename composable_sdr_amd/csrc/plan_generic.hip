@@ -27,12 +27,14 @@ struct GenericPlan : ChainPlan {
 
     ~GenericPlan() override { if (dctile) dctile_destroy(dctile); }
     int init();
-    const char *name() const override { return kernel.c_str(); }
+    // one kernel sequence per handle, no choice by call size; the name is what init() and run() noted in `kernel`
+    KernelChoice choose(uint32_t) const override { return {}; }
+    const char *kernel_name(int) const override { return kernel.c_str(); }
     std::string route(const char *, bool) const override;
     bool tile_major_ok(uint32_t) const override { return false; }
     int status(unsigned *st) override { *st = 0; return dctile ? dctile_status(dctile, st) : 0; }
     int reset_state(hipStream_t s) override;
-    int run(const FusedCall &call, void *out, hipStream_t s, KernelTimer *timer) override;
+    int run(const FusedCall &call, KernelChoice, void *out, hipStream_t s, KernelTimer *timer) override;
     int run_mix_identity(const FusedCall &call, const NcoParams &nco, hipStream_t s, KernelTimer *timer);
 };
 
@@ -146,7 +148,7 @@ int GenericPlan::run_mix_identity(const FusedCall &call, const NcoParams &nco, h
 }
 
 // With the AGC on (cfg.fm and cfg.mix are then false) out receives the channel-major CF32 plane the handle's tail reads
-int GenericPlan::run(const FusedCall &call, void *out, hipStream_t s, KernelTimer *timer)
+int GenericPlan::run(const FusedCall &call, KernelChoice, void *out, hipStream_t s, KernelTimer *timer)
 {
     const uint32_t M = cfg.M, C = cfg.C, G = cfg.G, nf = call.nf, nx = nf * M;
     const float2 *rp_in = d_rp[cur]; float2 *rp_out = d_rp[cur ^ 1];

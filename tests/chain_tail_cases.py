@@ -299,7 +299,7 @@ def timed_1024(kind, calls):
 
 
 def timed_shard1024(kind, calls, G=4):
-    """kernels_shard1024.hip shard1024_runs: k_shard1024 takes the calls of whole 4-frame tiles that hold a run of at least 16 tiles (four
+    """kernel_choice.h shard1024_runs: k_shard1024 takes the calls of whole 4-frame tiles that hold a run of at least 16 tiles (four
     blocks of 4 tiles CF32, two of 8 tiles FM), k_run1024 the others"""
     tb, per = (8, 2) if kind == "FM" else (4, 4)
     return [f"k_shard1024<{kind}>/G{G}" if f % 4 == 0 and -(-(f // 4) // tb) // per else f"k_run1024<{kind}>" for f in calls]

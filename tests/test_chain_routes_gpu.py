@@ -8,7 +8,8 @@ csdr_last_error for calls a WBFM, an AM and a backward handle refuse or have not
 Both tables were recorded from the library as it stood before the any-M route became a ChainPlan (GenericPlan, plan_generic.hip), not
 from the code they test: the texts are read by tools and logs, and that change was to keep every one of them.  The rows of the run-kernel
 cells (run*, shard*, fused*_fm_mix: knobs force the kernels onto small calls) were recorded the same way, from the library before the
-plans came to share their stream state, DC constants and cold-start setup."""
+plans came to share their stream state, DC constants and cold-start setup; the last three (run1024v2_fm_g4, shard1024_cf32_g8_agc,
+run64v2_cf32_agc) from the library before the plans' kernel choice moved into ChainPlan."""
 import ctypes as C
 import os
 import sys
@@ -67,6 +68,9 @@ ROUTES = {
     'run1024v2_fm_g2': ('fused-k_run1024v2<FM>/G2+interleaved-shard', 'k_run1024v2<FM>/G2', ['k_run1024v2<FM>/G2', 'k_run1024<FM>', 'k_run1024v2<FM>/G2']),
     'fused256_fm_mix': ('fused-256|k_tile256<FM>', 'k_tile256<FM>', ['k_tile256<FM>', 'k_tile256<FM>']),
     'fused1024_fm_mix': ('fused-k_run1024v3<FM>', 'k_run1024v3<FM>', ['k_run1024v3<FM>', 'k_run1024<FM>']),
+    'run1024v2_fm_g4': ('fused-k_run1024v2<FM>/G4+interleaved-shard', 'k_run1024v2<FM>/G4', ['k_run1024v2<FM>/G4', 'k_run1024<FM>', 'k_run1024v2<FM>/G4']),
+    'shard1024_cf32_g8_agc': ('fused-k_shard1024<CF32>/G8+interleaved-shard+agc-spec', 'k_shard1024<CF32>/G8', ['k_shard1024<CF32>/G8', 'k_run1024<CF32>', 'k_shard1024<CF32>/G8']),
+    'run64v2_cf32_agc': ('fused-k_run64<CF32>+agc-spec', 'k_run64<CF32>', ['k_run64v2', 'k_run64<CF32>', 'k_run64v2']),
 }
 UNTOUCHED = 0xdeadbeef
 # handle: [(call, return code, *n_out, csdr_last_error()[:40] of a refused call)]

@@ -76,6 +76,9 @@ CELLS += [
     _cell("run1024v2_fm_g2", 1024, [1024, 5, 1024], knobs={"CSDR_RUN1024_RUNS": "4"}, demod="fm", chan_stride=2),
     _cell("fused256_fm_mix", 256, demod="fm", mix=True),
     _cell("fused1024_fm_mix", 1024, demod="fm", mix=True),
+    _cell("run1024v2_fm_g4", 1024, [1024, 5, 1024], knobs={"CSDR_NO_SHARD1024": "1", "CSDR_RUN1024_RUNS": "4"}, demod="fm", chan_stride=4),
+    _cell("shard1024_cf32_g8_agc", 1024, [1024, 5, 1024], knobs={"CSDR_SHARD1024_RUNS": "4"}, agc=-10.0, chan_stride=8),      # tile-major plane
+    _cell("run64v2_cf32_agc", 64, [8192, 5, 6144], knobs={"CSDR_RUN64_V2_ALL": "1"}, agc=-10.0),                             # tile-major plane
 ]
 
 
