@@ -4,7 +4,9 @@
 //
 //   Pipe<A,B>      Types.hs:51-55     { start, process, done } around one native handle
 //   compose        Types.hs:93-99     process2 >=> process1, done2 before done1
-//   idPipe         Types.hs:101-102   Category id
+//   idPipe         Types.hs:101-102   Category id (purePipe id)
+//   handlePipe     every block's Pipe: create / destroy / process around one csdr_* handle
+//   rowPipe        handlePipe on the channel rows of one chunk (flattenRows, splitRows); rows of unequal length throw
 //   unPipe         Types.hs:109-115   create now; (per-array map, cleanup) for the stream side
 //   Fold<A>        streamly Fold      step / done
 //   addPipe        Types.hs:117-131   downstream start first, then create; done: destroy, then downstream
@@ -60,11 +62,30 @@ template <class A, class B, class C> Pipe<A, C> compose(Pipe<B, C> p1, Pipe<A, B
     return p;
 }
 
-template <class A> Pipe<A, A> idPipe()
+// a Pipe without a resource: process = f; idPipe is purePipe id
+template <class A, class B, class F> Pipe<A, B> purePipe(F f)
 {
-    Pipe<A, A> p;
+    Pipe<A, B> p;
     p.start = []() { return std::shared_ptr<void>(); };
-    p.process = [](void *, const A &a) { return a; };
+    p.process = [f](void *, const A &a) { return f(a); };
+    p.done = [](void *) {};
+    return p;
+}
+template <class A> Pipe<A, A> idPipe() { return purePipe<A, A>([](const A &a) { return a; }); }
+
+// handlePipe: the Pipe around one native handle H, and the only place that wraps a csdr_* handle.  start runs create(&h), which may
+// take more than one call (symSyncC); a throw from it destroys whatever handle it had made, once.  The handle then lives as long
+// as the last holder of the resource (unPipe's closures, AddPipe), not until done, which has nothing left to do.  process gets
+// the typed handle.
+template <class H, class A, class B, class Create, class Destroy, class Process> Pipe<A, B> handlePipe(Create create, Destroy destroy, Process process)
+{
+    Pipe<A, B> p;
+    p.start = [create, destroy]() {
+        H *h = nullptr;
+        try { create(&h); } catch (...) { if (h) destroy(h); throw; }
+        return std::shared_ptr<void>(h, [destroy](void *q) { destroy(static_cast<H *>(q)); });
+    };
+    p.process = [process](void *r, const A &a) { return process(static_cast<H *>(r), a); };
     p.done = [](void *) {};
     return p;
 }
@@ -202,40 +223,26 @@ struct AudioFileSink : Fold<Array<float>> {
 // ---- front-end Pipes: resampler r as (Liquid.chs:115-117), mixDown / mixUp f (Liquid.chs:805-809) ----
 inline Pipe<Array<cf32>, Array<cf32>> resampler(float r, float as_db, uint32_t max_in)
 {
-    Pipe<Array<cf32>, Array<cf32>> p;
-    p.start = [=]() {
-        csdr_resamp *h = nullptr;
-        check(csdr_resamp_create(r, as_db, max_in, &h));
-        return std::shared_ptr<void>(h, [](void *q) { csdr_resamp_destroy(static_cast<csdr_resamp *>(q)); });
-    };
-    p.process = [](void *rr, const Array<cf32> &a) {
-        auto *h = static_cast<csdr_resamp *>(rr);
-        Array<cf32> y(csdr_resamp_max_out(h, (uint32_t)a.size()));          // 2*ceil(r*nx), Liquid.chs:81
-        uint32_t n = 0;
-        check(csdr_resamp_process(h, reinterpret_cast<const float *>(a.data()), (uint32_t)a.size(), reinterpret_cast<float *>(y.data()), &n));
-        y.resize(n);                                                         // shrinkToFit, Liquid.chs:98
-        return y;
-    };
-    p.done = [](void *) {};
-    return p;
+    return handlePipe<csdr_resamp, Array<cf32>, Array<cf32>>(
+        [=](csdr_resamp **h) { check(csdr_resamp_create(r, as_db, max_in, h)); }, csdr_resamp_destroy,
+        [](csdr_resamp *h, const Array<cf32> &a) {
+            Array<cf32> y(csdr_resamp_max_out(h, (uint32_t)a.size()));          // 2*ceil(r*nx), Liquid.chs:81
+            uint32_t n = 0;
+            check(csdr_resamp_process(h, reinterpret_cast<const float *>(a.data()), (uint32_t)a.size(), reinterpret_cast<float *>(y.data()), &n));
+            y.resize(n);                                                         // shrinkToFit, Liquid.chs:98
+            return y;
+        });
 }
 inline Pipe<Array<cf32>, Array<cf32>> ncoMixer(float f, bool up, uint32_t max_in)
 {
-    Pipe<Array<cf32>, Array<cf32>> p;
-    p.start = [=]() {
-        csdr_nco *h = nullptr;
-        check(csdr_nco_create(f, max_in, &h));
-        return std::shared_ptr<void>(h, [](void *q) { csdr_nco_destroy(static_cast<csdr_nco *>(q)); });
-    };
-    p.process = [up](void *rr, const Array<cf32> &a) {
-        auto *h = static_cast<csdr_nco *>(rr);
-        Array<cf32> y(a.size());
-        if (!a.empty())
-            check((up ? csdr_nco_mix_up : csdr_nco_mix_down)(h, reinterpret_cast<const float *>(a.data()), (uint32_t)a.size(), reinterpret_cast<float *>(y.data())));
-        return y;
-    };
-    p.done = [](void *) {};
-    return p;
+    return handlePipe<csdr_nco, Array<cf32>, Array<cf32>>(
+        [=](csdr_nco **h) { check(csdr_nco_create(f, max_in, h)); }, csdr_nco_destroy,
+        [up](csdr_nco *h, const Array<cf32> &a) {
+            Array<cf32> y(a.size());
+            if (!a.empty())
+                check((up ? csdr_nco_mix_up : csdr_nco_mix_down)(h, reinterpret_cast<const float *>(a.data()), (uint32_t)a.size(), reinterpret_cast<float *>(y.data())));
+            return y;
+        });
 }
 inline Pipe<Array<cf32>, Array<cf32>> mixDown(float f, uint32_t max_in) { return ncoMixer(f, false, max_in); }
 inline Pipe<Array<cf32>, Array<cf32>> mixUp(float f, uint32_t max_in) { return ncoMixer(f, true, max_in); }
@@ -244,35 +251,23 @@ inline Pipe<Array<cf32>, Array<cf32>> mixUp(float f, uint32_t max_in) { return n
 // max_in in complex samples.  An odd-length float array loses its last float (firhilbDecim's `length div 2`) ----
 inline Pipe<Array<float>, Array<cf32>> realToComplex(uint32_t max_in, uint32_t m = 5, float as_db = 60.0f)
 {
-    Pipe<Array<float>, Array<cf32>> p;
-    p.start = [=]() {
-        csdr_firhilb *h = nullptr;
-        check(csdr_firhilb_create(m, as_db, max_in, &h));
-        return std::shared_ptr<void>(h, [](void *q) { csdr_firhilb_destroy(static_cast<csdr_firhilb *>(q)); });
-    };
-    p.process = [](void *rr, const Array<float> &a) {
-        Array<cf32> y(a.size() / 2);
-        check(csdr_firhilb_decim(static_cast<csdr_firhilb *>(rr), a.data(), (uint32_t)y.size(), reinterpret_cast<float *>(y.data())));
-        return y;
-    };
-    p.done = [](void *) {};
-    return p;
+    return handlePipe<csdr_firhilb, Array<float>, Array<cf32>>(
+        [=](csdr_firhilb **h) { check(csdr_firhilb_create(m, as_db, max_in, h)); }, csdr_firhilb_destroy,
+        [](csdr_firhilb *h, const Array<float> &a) {
+            Array<cf32> y(a.size() / 2);
+            check(csdr_firhilb_decim(h, a.data(), (uint32_t)y.size(), reinterpret_cast<float *>(y.data())));
+            return y;
+        });
 }
 inline Pipe<Array<cf32>, Array<float>> complexToReal(uint32_t max_in, uint32_t m = 5, float as_db = 60.0f)
 {
-    Pipe<Array<cf32>, Array<float>> p;
-    p.start = [=]() {
-        csdr_firhilb *h = nullptr;
-        check(csdr_firhilb_create(m, as_db, max_in, &h));
-        return std::shared_ptr<void>(h, [](void *q) { csdr_firhilb_destroy(static_cast<csdr_firhilb *>(q)); });
-    };
-    p.process = [](void *rr, const Array<cf32> &a) {
-        Array<float> y(2 * a.size());
-        check(csdr_firhilb_interp(static_cast<csdr_firhilb *>(rr), reinterpret_cast<const float *>(a.data()), (uint32_t)a.size(), y.data()));
-        return y;
-    };
-    p.done = [](void *) {};
-    return p;
+    return handlePipe<csdr_firhilb, Array<cf32>, Array<float>>(
+        [=](csdr_firhilb **h) { check(csdr_firhilb_create(m, as_db, max_in, h)); }, csdr_firhilb_destroy,
+        [](csdr_firhilb *h, const Array<cf32> &a) {
+            Array<float> y(2 * a.size());
+            check(csdr_firhilb_interp(h, reinterpret_cast<const float *>(a.data()), (uint32_t)a.size(), y.data()));
+            return y;
+        });
 }
 
 // ---- openAudioFile / readFromAudioFile (Source.chs:273-307) without libsndfile: a hand-written reader, as AudioFileSink is a
@@ -419,269 +414,198 @@ struct FileSource {
 // (Liquid.chs:333-334), stereoFMDecoder quadRate decim (Liquid.chs:1069-1078; interleaved L, R out) ----
 inline Pipe<Array<cf32>, Array<cf32>> agcPipe(float tres, uint32_t max_in)
 {
-    Pipe<Array<cf32>, Array<cf32>> p;
-    p.start = [=]() {
-        csdr_agc *h = nullptr;
-        check(csdr_agc_create(tres, 1, max_in, &h));
-        return std::shared_ptr<void>(h, [](void *q) { csdr_agc_destroy(static_cast<csdr_agc *>(q)); });
-    };
-    p.process = [](void *rr, const Array<cf32> &a) {
-        Array<cf32> y(a.size());
-        if (!a.empty())
-            check(csdr_agc_process(static_cast<csdr_agc *>(rr), reinterpret_cast<const float *>(a.data()), (uint32_t)a.size(), reinterpret_cast<float *>(y.data())));
-        return y;
-    };
-    p.done = [](void *) {};
-    return p;
+    return handlePipe<csdr_agc, Array<cf32>, Array<cf32>>(
+        [=](csdr_agc **h) { check(csdr_agc_create(tres, 1, max_in, h)); }, csdr_agc_destroy,
+        [](csdr_agc *h, const Array<cf32> &a) {
+            Array<cf32> y(a.size());
+            if (!a.empty())
+                check(csdr_agc_process(h, reinterpret_cast<const float *>(a.data()), (uint32_t)a.size(), reinterpret_cast<float *>(y.data())));
+            return y;
+        });
 }
 inline Pipe<Array<cf32>, Array<float>> freqdemPipe(float kf, uint32_t max_in)
 {
-    Pipe<Array<cf32>, Array<float>> p;
-    p.start = [=]() {
-        csdr_freqdem *h = nullptr;
-        check(csdr_freqdem_create(kf, 1, max_in, &h));
-        return std::shared_ptr<void>(h, [](void *q) { csdr_freqdem_destroy(static_cast<csdr_freqdem *>(q)); });
-    };
-    p.process = [](void *rr, const Array<cf32> &a) {
-        Array<float> m(a.size());
-        if (!a.empty())
-            check(csdr_freqdem_process(static_cast<csdr_freqdem *>(rr), reinterpret_cast<const float *>(a.data()), (uint32_t)a.size(), m.data()));
-        return m;
-    };
-    p.done = [](void *) {};
-    return p;
+    return handlePipe<csdr_freqdem, Array<cf32>, Array<float>>(
+        [=](csdr_freqdem **h) { check(csdr_freqdem_create(kf, 1, max_in, h)); }, csdr_freqdem_destroy,
+        [](csdr_freqdem *h, const Array<cf32> &a) {
+            Array<float> m(a.size());
+            if (!a.empty()) check(csdr_freqdem_process(h, reinterpret_cast<const float *>(a.data()), (uint32_t)a.size(), m.data()));
+            return m;
+        });
 }
 inline Pipe<Array<float>, Array<float>> fmStereoPipe(float quad_rate, uint32_t decim, uint32_t max_in)
 {
-    Pipe<Array<float>, Array<float>> p;
-    p.start = [=]() {
-        csdr_fmstereo *h = nullptr;
-        check(csdr_fmstereo_create(quad_rate, decim, 1, max_in, &h));
-        return std::shared_ptr<void>(h, [](void *q) { csdr_fmstereo_destroy(static_cast<csdr_fmstereo *>(q)); });
-    };
-    p.process = [decim](void *rr, const Array<float> &a) {
-        Array<float> y(2 * (a.size() / decim));
-        uint32_t n = 0;
-        if (!a.empty()) check(csdr_fmstereo_process(static_cast<csdr_fmstereo *>(rr), a.data(), (uint32_t)a.size(), y.data(), &n));
-        y.resize(n);
-        return y;
-    };
-    p.done = [](void *) {};
-    return p;
+    return handlePipe<csdr_fmstereo, Array<float>, Array<float>>(
+        [=](csdr_fmstereo **h) { check(csdr_fmstereo_create(quad_rate, decim, 1, max_in, h)); }, csdr_fmstereo_destroy,
+        [decim](csdr_fmstereo *h, const Array<float> &a) {
+            Array<float> y(2 * (a.size() / decim));
+            uint32_t n = 0;
+            if (!a.empty()) check(csdr_fmstereo_process(h, a.data(), (uint32_t)a.size(), y.data(), &n));
+            y.resize(n);
+            return y;
+        });
 }
 
-// ---- symSyncR k m beta M (Liquid.chs:244-282; set_lf_bw 0.05, set_output_rate 2) on the channel rows of one chunk: one
-// csdr_symsync handle with one stream per row for the whole run; row c of the output holds that stream's ny[c] samples ----
-inline Pipe<std::vector<Array<float>>, std::vector<Array<float>>> symSyncR(uint32_t k, uint32_t m, float beta, uint32_t M, uint32_t nchan,
-                                                                          uint32_t max_in)
+// ---- Pipes on the channel rows of one chunk: one handle with one stream (or filter state) per row for the whole run ----
+// The rows go to the C ABI as one flat [nchan][n] array and come back cut into rows.  The shape rule of every such Pipe: a
+// chunk whose row count is not nchan, or whose first row is empty (nx = 0 -> [empty]), passes through as rows.size() empty arrays
+// without a call.  Rows of unequal length throw a std::runtime_error that names the pipe, before anything is copied (the
+// copy used to be sized by rows[0] alone: a longer row wrote past the end of the heap buffer, a shorter one was zero-padded).
+template <class T> using Rows = std::vector<Array<T>>;
+
+// rows -> flat [nchan][n] with n = rows[0].size(); empty = "pass the chunk through" (the shape rule)
+template <class T> Array<T> flattenRows(const Rows<T> &rows, uint32_t nchan, const char *pipe)
 {
-    Pipe<std::vector<Array<float>>, std::vector<Array<float>>> p;
-    p.start = [=]() {
-        csdr_symsync *h = nullptr;
-        check(csdr_symsync_create(k, m, beta, M, 0.05f, 2, nchan, max_in, &h));
-        return std::shared_ptr<void>(h, [](void *q) { csdr_symsync_destroy(static_cast<csdr_symsync *>(q)); });
-    };
-    p.process = [nchan](void *rr, const std::vector<Array<float>> &rows) {
-        if (rows.size() != nchan || rows[0].empty()) return std::vector<Array<float>>(rows.size());   // nx = 0 -> [empty]
-        const size_t n = rows[0].size();
-        Array<float> x(nchan * n), y(nchan * n);
-        for (uint32_t c = 0; c < nchan; c++) std::copy(rows[c].begin(), rows[c].end(), x.begin() + c * n);
-        std::vector<uint32_t> ny(nchan);
-        check(csdr_symsync_process(static_cast<csdr_symsync *>(rr), x.data(), (uint32_t)n, y.data(), ny.data()));
-        std::vector<Array<float>> out;
-        for (uint32_t c = 0; c < nchan; c++) out.emplace_back(y.begin() + c * n, y.begin() + c * n + ny[c]);
-        return out;
-    };
-    p.done = [](void *) {};
-    return p;
+    if (rows.size() != nchan || rows.empty() || rows[0].empty()) return {};
+    const size_t n = rows[0].size();
+    for (const Array<T> &r : rows)
+        if (r.size() != n) throw std::runtime_error(std::string(pipe) + ": the rows of one chunk must have one length");
+    Array<T> flat(nchan * n);
+    for (uint32_t c = 0; c < nchan; c++) std::copy(rows[c].begin(), rows[c].end(), flat.begin() + c * n);
+    return flat;
+}
+// flat, rows `stride` apart -> row c = its first counts[c] elements; one count for every row is the special case
+template <class T> Rows<T> splitRows(const Array<T> &flat, uint32_t nchan, size_t stride, const std::vector<uint32_t> &counts)
+{
+    Rows<T> out;
+    for (uint32_t c = 0; c < nchan; c++) out.emplace_back(flat.begin() + c * stride, flat.begin() + c * stride + counts[c]);
+    return out;
+}
+template <class T> Rows<T> splitRows(const Array<T> &flat, uint32_t nchan, size_t stride, size_t count)
+{
+    return splitRows(flat, nchan, stride, std::vector<uint32_t>(nchan, (uint32_t)count));
+}
+// handlePipe on rows: call(h, flat, n) runs the ABI on the flat [nchan][n] input and returns the output rows
+template <class H, class A, class B, class Create, class Destroy, class Call>
+Pipe<Rows<A>, Rows<B>> rowPipe(const char *pipe, uint32_t nchan, Create create, Destroy destroy, Call call)
+{
+    return handlePipe<H, Rows<A>, Rows<B>>(create, destroy, [=](H *h, const Rows<A> &rows) {
+        const Array<A> x = flattenRows(rows, nchan, pipe);
+        return x.empty() ? Rows<B>(rows.size()) : call(h, x, (uint32_t)(x.size() / nchan));
+    });
+}
+
+// ---- symSyncR k m beta M (Liquid.chs:244-282; set_lf_bw 0.05, set_output_rate 2): row c of the output holds that stream's
+// ny[c] samples ----
+inline Pipe<Rows<float>, Rows<float>> symSyncR(uint32_t k, uint32_t m, float beta, uint32_t M, uint32_t nchan, uint32_t max_in)
+{
+    return rowPipe<csdr_symsync, float, float>(
+        "symSyncR", nchan, [=](csdr_symsync **h) { check(csdr_symsync_create(k, m, beta, M, 0.05f, 2, nchan, max_in, h)); }, csdr_symsync_destroy,
+        [nchan](csdr_symsync *h, const Array<float> &x, uint32_t n) {
+            Array<float> y(x.size());
+            std::vector<uint32_t> ny(nchan);
+            check(csdr_symsync_process(h, x.data(), n, y.data(), ny.data()));
+            return splitRows(y, nchan, n, ny);
+        });
 }
 
 // ---- symSyncC m k (Liquid.chs:177-242; symsync_crcf_create_rnyquist(ARKAISER, k, m, 0.5, 32), lf_bw 0.01 and output rate 1 at
-// symsync_create's defaults) on the CF32 channel rows of one chunk, e.g. firpfbchChannelizer's: one csdr_symsync handle with one
-// stream per row for the whole run; row c of the output holds that stream's ny[c] symbols ----
-inline Pipe<std::vector<Array<cf32>>, std::vector<Array<cf32>>> symSyncC(uint32_t m, uint32_t k, uint32_t nchan, uint32_t max_in)
+// symsync_create's defaults) on CF32 rows, e.g. firpfbchChannelizer's: row c of the output holds that stream's ny[c] symbols ----
+inline Pipe<Rows<cf32>, Rows<cf32>> symSyncC(uint32_t m, uint32_t k, uint32_t nchan, uint32_t max_in)
 {
-    Pipe<std::vector<Array<cf32>>, std::vector<Array<cf32>>> p;
-    p.start = [=]() {
-        csdr_symsync *h = nullptr;
-        check(csdr_symsync_create(k, m, 0.0f, 32, 0.01f, 1, nchan, max_in, &h));
-        std::shared_ptr<void> r(h, [](void *q) { csdr_symsync_destroy(static_cast<csdr_symsync *>(q)); });
-        check(csdr_symsync_set_rnyquist(h, CSDR_FIRFILT_ARKAISER, 0.5f));
-        return r;
-    };
-    p.process = [nchan](void *rr, const std::vector<Array<cf32>> &rows) {
-        if (rows.size() != nchan || rows[0].empty()) return std::vector<Array<cf32>>(rows.size());     // nx = 0 -> [empty]
-        const size_t n = rows[0].size();
-        Array<cf32> x(nchan * n), y(nchan * n);
-        for (uint32_t c = 0; c < nchan; c++) std::copy(rows[c].begin(), rows[c].end(), x.begin() + c * n);
-        std::vector<uint32_t> ny(nchan);
-        check(csdr_symsync_process_c(static_cast<csdr_symsync *>(rr), reinterpret_cast<const float *>(x.data()), (uint32_t)n,
-                                     reinterpret_cast<float *>(y.data()), ny.data()));
-        std::vector<Array<cf32>> out;
-        for (uint32_t c = 0; c < nchan; c++) out.emplace_back(y.begin() + c * n, y.begin() + c * n + ny[c]);
-        return out;
-    };
-    p.done = [](void *) {};
-    return p;
+    return rowPipe<csdr_symsync, cf32, cf32>(
+        "symSyncC", nchan,
+        [=](csdr_symsync **h) {
+            check(csdr_symsync_create(k, m, 0.0f, 32, 0.01f, 1, nchan, max_in, h));
+            check(csdr_symsync_set_rnyquist(*h, CSDR_FIRFILT_ARKAISER, 0.5f));
+        },
+        csdr_symsync_destroy,
+        [nchan](csdr_symsync *h, const Array<cf32> &x, uint32_t n) {
+            Array<cf32> y(x.size());
+            std::vector<uint32_t> ny(nchan);
+            check(csdr_symsync_process_c(h, reinterpret_cast<const float *>(x.data()), n, reinterpret_cast<float *>(y.data()), ny.data()));
+            return splitRows(y, nchan, n, ny);
+        });
 }
 
-// ---- fskDemodulator m k bw (Liquid.chs:336-382) on the channel rows of one chunk: one csdr_fskdem handle with one stream
-// per row; row c of the output holds the n div k symbols of row c, the n mod k samples left over are dropped (:367-376) ----
-inline Pipe<std::vector<Array<cf32>>, std::vector<Array<uint32_t>>> FskDemodulator(uint32_t m, uint32_t k, float bw, uint32_t nchan,
-                                                                                 uint32_t max_in)
+// ---- fskDemodulator m k bw (Liquid.chs:336-382): row c of the output holds the n div k symbols of row c, the n mod k samples
+// left over are dropped (:367-376).  gmskDemodulator m k bw (Liquid.chs:384-429; the reference's argument order, gmskdem_create
+// takes k m bw): the n / k bits of row c; a row length that is no multiple of k throws, as :421 does ----
+namespace detail {
+template <class H, class Create, class Destroy>
+Pipe<Rows<cf32>, Rows<uint32_t>> symbolRows(const char *pipe, uint32_t k, uint32_t nchan, Create create, Destroy destroy,
+                                            int (*process)(H *, const float *, uint32_t, uint32_t *, float *, uint32_t *))
 {
-    Pipe<std::vector<Array<cf32>>, std::vector<Array<uint32_t>>> p;
-    p.start = [=]() {
-        csdr_fskdem *h = nullptr;
-        check(csdr_fskdem_create(m, k, bw, nchan, max_in, &h));
-        return std::shared_ptr<void>(h, [](void *q) { csdr_fskdem_destroy(static_cast<csdr_fskdem *>(q)); });
-    };
-    p.process = [nchan, k](void *rr, const std::vector<Array<cf32>> &rows) {
-        if (rows.size() != nchan || rows[0].empty()) return std::vector<Array<uint32_t>>(rows.size());
-        const size_t n = rows[0].size(), ns = n / k;
-        Array<cf32> x(nchan * n);
-        for (uint32_t c = 0; c < nchan; c++) std::copy(rows[c].begin(), rows[c].end(), x.begin() + c * n);
+    return rowPipe<H, cf32, uint32_t>(pipe, nchan, create, destroy, [=](H *h, const Array<cf32> &x, uint32_t n) {
+        const size_t ns = n / k;
         Array<uint32_t> sym(nchan * ns);
         uint32_t n_out = 0;
-        check(csdr_fskdem_process(static_cast<csdr_fskdem *>(rr), reinterpret_cast<const float *>(x.data()), (uint32_t)n, sym.data(), nullptr, &n_out));
-        std::vector<Array<uint32_t>> out;
-        for (uint32_t c = 0; c < nchan; c++) out.emplace_back(sym.begin() + c * ns, sym.begin() + (c + 1) * ns);
-        return out;
-    };
-    p.done = [](void *) {};
-    return p;
-}
-
-// ---- firFilterCKaiser n fc as mu / firFilterC f / firFilterR f (Liquid.chs:868-916, 955-957) on the channel rows of one chunk:
-// one csdr_firfilt handle with one filter state per row; the liquid object f is its taps and scale here.  Rows of one chunk
-// have one length; an empty chunk passes through ----
-namespace detail {
-template <class T> Pipe<std::vector<Array<T>>, std::vector<Array<T>>> firFilterRows(std::function<csdr_firfilt *()> create, uint32_t nchan)
-{
-    Pipe<std::vector<Array<T>>, std::vector<Array<T>>> p;
-    p.start = [=]() { return std::shared_ptr<void>(create(), [](void *q) { csdr_firfilt_destroy(static_cast<csdr_firfilt *>(q)); }); };
-    p.process = [nchan](void *rr, const std::vector<Array<T>> &rows) {
-        if (rows.size() != nchan || rows[0].empty()) return std::vector<Array<T>>(rows.size());
-        const size_t n = rows[0].size();
-        Array<T> x(nchan * n), y(nchan * n);
-        for (uint32_t c = 0; c < nchan; c++) std::copy(rows[c].begin(), rows[c].end(), x.begin() + c * n);
-        check(csdr_firfilt_process(static_cast<csdr_firfilt *>(rr), reinterpret_cast<const float *>(x.data()), (uint32_t)n,
-                                   reinterpret_cast<float *>(y.data())));
-        std::vector<Array<T>> out;
-        for (uint32_t c = 0; c < nchan; c++) out.emplace_back(y.begin() + c * n, y.begin() + (c + 1) * n);
-        return out;
-    };
-    p.done = [](void *) {};
-    return p;
-}
-template <class T> Pipe<std::vector<Array<T>>, std::vector<Array<T>>> firFilterTaps(const Array<float> &taps, float scale, uint32_t nchan,
-                                                                                    uint32_t max_in)
-{
-    return firFilterRows<T>([=]() {
-        csdr_firfilt *h = nullptr;
-        check(csdr_firfilt_create_taps(taps.data(), (uint32_t)taps.size(), scale, std::is_same<T, cf32>::value, nchan, max_in, &h));
-        return h;
-    }, nchan);
+        check(process(h, reinterpret_cast<const float *>(x.data()), n, sym.data(), nullptr, &n_out));
+        return splitRows(sym, nchan, ns, ns);
+    });
 }
 }  // namespace detail
-inline Pipe<std::vector<Array<cf32>>, std::vector<Array<cf32>>> FirFilterC(const Array<float> &taps, float scale, uint32_t nchan, uint32_t max_in)
+inline Pipe<Rows<cf32>, Rows<uint32_t>> FskDemodulator(uint32_t m, uint32_t k, float bw, uint32_t nchan, uint32_t max_in)
 {
-    return detail::firFilterTaps<cf32>(taps, scale, nchan, max_in);
+    return detail::symbolRows<csdr_fskdem>(
+        "FskDemodulator", k, nchan, [=](csdr_fskdem **h) { check(csdr_fskdem_create(m, k, bw, nchan, max_in, h)); }, csdr_fskdem_destroy,
+        csdr_fskdem_process);
 }
-inline Pipe<std::vector<Array<float>>, std::vector<Array<float>>> FirFilterR(const Array<float> &taps, float scale, uint32_t nchan, uint32_t max_in)
+inline Pipe<Rows<cf32>, Rows<uint32_t>> GmskDemodulator(uint32_t m, uint32_t k, float bw, uint32_t nchan, uint32_t max_in)
 {
-    return detail::firFilterTaps<float>(taps, scale, nchan, max_in);
+    return detail::symbolRows<csdr_gmskdem>(
+        "GmskDemodulator", k, nchan, [=](csdr_gmskdem **h) { check(csdr_gmskdem_create(k, m, bw, nchan, max_in, h)); }, csdr_gmskdem_destroy,
+        csdr_gmskdem_process);
 }
-inline Pipe<std::vector<Array<cf32>>, std::vector<Array<cf32>>> FirFilterCKaiser(uint32_t n, float fc, float as_db, float mu, uint32_t nchan,
-                                                                                uint32_t max_in)
+
+// ---- firFilterCKaiser n fc as mu / firFilterC f / firFilterR f (Liquid.chs:868-916, 955-957): one csdr_firfilt handle with one
+// filter state per row; the liquid object f is its taps and scale here.  iirCFilter n fc f0 ap as (Liquid.chs:594-608) and the
+// caller's own second-order sections: one csdr_iirsos handle with one state per row and section; a liquid iirfilt object is its
+// sections here (b, a: [S][3] each, row-major).  Both give n samples out for n in ----
+namespace detail {
+template <class H, class T, class Create, class Destroy>
+Pipe<Rows<T>, Rows<T>> filterRows(const char *pipe, uint32_t nchan, Create create, Destroy destroy, int (*process)(H *, const float *, uint32_t, float *))
 {
-    return detail::firFilterRows<cf32>([=]() {
-        csdr_firfilt *h = nullptr;
-        check(csdr_firfilt_create_kaiser(n, fc, as_db, mu, 1, nchan, max_in, &h));
-        return h;
-    }, nchan);
+    return rowPipe<H, T, T>(pipe, nchan, create, destroy, [=](H *h, const Array<T> &x, uint32_t n) {
+        Array<T> y(x.size());
+        check(process(h, reinterpret_cast<const float *>(x.data()), n, reinterpret_cast<float *>(y.data())));
+        return splitRows(y, nchan, n, n);
+    });
+}
+template <class T> Pipe<Rows<T>, Rows<T>> firFilterTaps(const char *pipe, const Array<float> &taps, float scale, uint32_t nchan, uint32_t max_in)
+{
+    return filterRows<csdr_firfilt, T>(pipe, nchan, [=](csdr_firfilt **h) {
+        check(csdr_firfilt_create_taps(taps.data(), (uint32_t)taps.size(), scale, std::is_same<T, cf32>::value, nchan, max_in, h));
+    }, csdr_firfilt_destroy, csdr_firfilt_process);
+}
+}  // namespace detail
+inline Pipe<Rows<cf32>, Rows<cf32>> FirFilterC(const Array<float> &taps, float scale, uint32_t nchan, uint32_t max_in)
+{
+    return detail::firFilterTaps<cf32>("FirFilterC", taps, scale, nchan, max_in);
+}
+inline Pipe<Rows<float>, Rows<float>> FirFilterR(const Array<float> &taps, float scale, uint32_t nchan, uint32_t max_in)
+{
+    return detail::firFilterTaps<float>("FirFilterR", taps, scale, nchan, max_in);
+}
+inline Pipe<Rows<cf32>, Rows<cf32>> FirFilterCKaiser(uint32_t n, float fc, float as_db, float mu, uint32_t nchan, uint32_t max_in)
+{
+    return detail::filterRows<csdr_firfilt, cf32>("FirFilterCKaiser", nchan, [=](csdr_firfilt **h) {
+        check(csdr_firfilt_create_kaiser(n, fc, as_db, mu, 1, nchan, max_in, h));
+    }, csdr_firfilt_destroy, csdr_firfilt_process);
 }
 
 // ---- firFilterRNyquist k m beta mu (Liquid.chs:935-953: LIQUID_FIRFILT_GMSKRX and the scale 1 / k are hard-coded there):
 // FirFilterR on the taps of csdr_firdes_gmskrx(k, m, beta); mu != 0 is refused ----
-inline Pipe<std::vector<Array<float>>, std::vector<Array<float>>> FirFilterRNyquist(uint32_t k, uint32_t m, float beta, float mu, uint32_t nchan,
-                                                                                   uint32_t max_in)
+inline Pipe<Rows<float>, Rows<float>> FirFilterRNyquist(uint32_t k, uint32_t m, float beta, float mu, uint32_t nchan, uint32_t max_in)
 {
     if (mu != 0.f) throw std::runtime_error("FirFilterRNyquist: mu != 0 is not supported");
     Array<float> taps(2 * (size_t)k * m + 1);
     check(csdr_firdes_gmskrx(k, m, beta, taps.data()));
-    return FirFilterR(taps, 1.0f / (float)k, nchan, max_in);
+    return detail::firFilterTaps<float>("FirFilterRNyquist", taps, 1.0f / (float)k, nchan, max_in);
 }
 
-// ---- gmskDemodulator m k bw (Liquid.chs:384-429; the reference's argument order, gmskdem_create takes k m bw) on the channel
-// rows of one chunk: one csdr_gmskdem handle with one stream per row; row c of the output holds the n / k bits of row c; a row
-// length that is no multiple of k throws, as :421 does ----
-inline Pipe<std::vector<Array<cf32>>, std::vector<Array<uint32_t>>> GmskDemodulator(uint32_t m, uint32_t k, float bw, uint32_t nchan,
-                                                                                  uint32_t max_in)
+inline Pipe<Rows<cf32>, Rows<cf32>> IirCFilter(uint32_t n, float fc, float f0, float ap, float as_db, uint32_t nchan, uint32_t max_in)
 {
-    Pipe<std::vector<Array<cf32>>, std::vector<Array<uint32_t>>> p;
-    p.start = [=]() {
-        csdr_gmskdem *h = nullptr;
-        check(csdr_gmskdem_create(k, m, bw, nchan, max_in, &h));
-        return std::shared_ptr<void>(h, [](void *q) { csdr_gmskdem_destroy(static_cast<csdr_gmskdem *>(q)); });
-    };
-    p.process = [nchan, k](void *rr, const std::vector<Array<cf32>> &rows) {
-        if (rows.size() != nchan || rows[0].empty()) return std::vector<Array<uint32_t>>(rows.size());
-        const size_t n = rows[0].size(), ns = n / k;
-        Array<cf32> x(nchan * n);
-        for (uint32_t c = 0; c < nchan; c++) std::copy(rows[c].begin(), rows[c].end(), x.begin() + c * n);
-        Array<uint32_t> sym(nchan * ns);
-        uint32_t n_out = 0;
-        check(csdr_gmskdem_process(static_cast<csdr_gmskdem *>(rr), reinterpret_cast<const float *>(x.data()), (uint32_t)n, sym.data(), nullptr, &n_out));
-        std::vector<Array<uint32_t>> out;
-        for (uint32_t c = 0; c < nchan; c++) out.emplace_back(sym.begin() + c * ns, sym.begin() + (c + 1) * ns);
-        return out;
-    };
-    p.done = [](void *) {};
-    return p;
+    return detail::filterRows<csdr_iirsos, cf32>("IirCFilter", nchan, [=](csdr_iirsos **h) {
+        check(csdr_iirsos_create_prototype(n, fc, f0, ap, as_db, 1, nchan, max_in, h));
+    }, csdr_iirsos_destroy, csdr_iirsos_process);
 }
-
-// ---- iirCFilter n fc f0 ap as (Liquid.chs:594-608) and the caller's own second-order sections on the channel rows of one chunk:
-// one csdr_iirsos handle with one state per row and section; a liquid iirfilt object is its sections here (b, a: [S][3] each,
-// row-major).  Rows of one chunk have one length; an empty chunk passes through ----
-namespace detail {
-template <class T> Pipe<std::vector<Array<T>>, std::vector<Array<T>>> iirSosRows(std::function<csdr_iirsos *()> create, uint32_t nchan)
+template <class T> Pipe<Rows<T>, Rows<T>> IirFilterSOS(const Array<float> &b, const Array<float> &a, uint32_t nchan, uint32_t max_in)
 {
-    Pipe<std::vector<Array<T>>, std::vector<Array<T>>> p;
-    p.start = [=]() { return std::shared_ptr<void>(create(), [](void *q) { csdr_iirsos_destroy(static_cast<csdr_iirsos *>(q)); }); };
-    p.process = [nchan](void *rr, const std::vector<Array<T>> &rows) {
-        if (rows.size() != nchan || rows[0].empty()) return std::vector<Array<T>>(rows.size());
-        const size_t n = rows[0].size();
-        Array<T> x(nchan * n), y(nchan * n);
-        for (uint32_t c = 0; c < nchan; c++) std::copy(rows[c].begin(), rows[c].end(), x.begin() + c * n);
-        check(csdr_iirsos_process(static_cast<csdr_iirsos *>(rr), reinterpret_cast<const float *>(x.data()), (uint32_t)n,
-                                  reinterpret_cast<float *>(y.data())));
-        std::vector<Array<T>> out;
-        for (uint32_t c = 0; c < nchan; c++) out.emplace_back(y.begin() + c * n, y.begin() + (c + 1) * n);
-        return out;
-    };
-    p.done = [](void *) {};
-    return p;
-}
-}  // namespace detail
-inline Pipe<std::vector<Array<cf32>>, std::vector<Array<cf32>>> IirCFilter(uint32_t n, float fc, float f0, float ap, float as_db, uint32_t nchan,
-                                                                          uint32_t max_in)
-{
-    return detail::iirSosRows<cf32>([=]() {
-        csdr_iirsos *h = nullptr;
-        check(csdr_iirsos_create_prototype(n, fc, f0, ap, as_db, 1, nchan, max_in, &h));
-        return h;
-    }, nchan);
-}
-template <class T> Pipe<std::vector<Array<T>>, std::vector<Array<T>>> IirFilterSOS(const Array<float> &b, const Array<float> &a, uint32_t nchan,
-                                                                                   uint32_t max_in)
-{
-    return detail::iirSosRows<T>([=]() {
-        csdr_iirsos *h = nullptr;
+    return detail::filterRows<csdr_iirsos, T>("IirFilterSOS", nchan, [=](csdr_iirsos **h) {
         if (b.size() != a.size() || b.size() % 3) throw std::runtime_error("IirFilterSOS: b and a must hold 3 floats per section each");
-        check(csdr_iirsos_create_sos(b.data(), a.data(), (uint32_t)(b.size() / 3), std::is_same<T, cf32>::value, nchan, max_in, &h));
-        return h;
-    }, nchan);
+        check(csdr_iirsos_create_sos(b.data(), a.data(), (uint32_t)(b.size() / 3), std::is_same<T, cf32>::value, nchan, max_in, h));
+    }, csdr_iirsos_destroy, csdr_iirsos_process);
 }
 
 // ---- the fused chain as a Pipe (replaces mix . mux (replicate nch demod) . firpfbchChannelizer nc) ----
@@ -754,8 +678,7 @@ inline csdr_comm *commFromIdFile(const std::string &path, int rank, int world, i
 
 template <class Out> Pipe<Array<cf32>, std::vector<Array<Out>>> fusedChain(const ChainOpts &o)
 {
-    Pipe<Array<cf32>, std::vector<Array<Out>>> p;
-    p.start = [o]() {
+    return handlePipe<csdr_chain, Array<cf32>, std::vector<Array<Out>>>([o](csdr_chain **h) {
         csdr_chain_cfg cfg;
         csdr_chain_cfg_default(&cfg, o.channels);
         cfg.channels = o.channels; cfg.dc_block = o.dc_block; cfg.agc_threshold_db = o.agc;
@@ -765,12 +688,8 @@ template <class Out> Pipe<Array<cf32>, std::vector<Array<Out>>> fusedChain(const
             if (o.channels % o.world || o.rank >= o.world) throw std::runtime_error("channel shards: world must divide the channel count");
             cfg.chan_first = o.rank; cfg.chan_stride = o.world;
         }
-        csdr_chain *h = nullptr;
-        check(csdr_chain_create(&cfg, &h));
-        return std::shared_ptr<void>(h, [](void *q) { csdr_chain_destroy(static_cast<csdr_chain *>(q)); });
-    };
-    p.process = [o](void *r, const Array<cf32> &a) {
-        auto *h = static_cast<csdr_chain *>(r);
+        check(csdr_chain_create(&cfg, h));
+    }, csdr_chain_destroy, [o](csdr_chain *h, const Array<cf32> &a) {
         const uint32_t M = o.channels;
         if (a.empty()) return std::vector<Array<Out>>{Array<Out>{}};          // nx = 0 -> [empty] (Liquid.chs:856-862)
         uint32_t usable = (uint32_t)(a.size() / M * M), nf = usable / M;
@@ -789,9 +708,7 @@ template <class Out> Pipe<Array<cf32>, std::vector<Array<Out>>> fusedChain(const
         if (mixed || M == 1) { outs.push_back(std::move(flat)); return outs; }
         for (uint32_t k = 0; k < C; k++) outs.emplace_back(flat.begin() + (size_t)k * no, flat.begin() + (size_t)(k + 1) * no);
         return outs;
-    };
-    p.done = [](void *) {};
-    return p;
+    });
 }
 
 }  // namespace csdrhost

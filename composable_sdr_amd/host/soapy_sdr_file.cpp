@@ -22,6 +22,29 @@ using namespace csdrhost;
 struct FrontOpts { double samplerate = 2.56e6, bandwidth = 0.0, offset = 0.0; std::string audio; };
 static FrontOpts g_front;
 
+// prep = takeNArr ns . (resampler . offset)  (SoapySDR.hs:190-207) pushed into `fold`.  The caller has opened `src` before any sink
+// (a refused source leaves no output file) and built its sinks and fold before the front-end pipes start here
+static int pump(FileSource &src, size_t n, size_t chunk, Fold<Array<cf32>> &fold)
+{
+    using CPipe = Pipe<Array<cf32>, Array<cf32>>;
+    const float fo = (float)(2.0 * 3.14159265358979323846 * g_front.offset / g_front.samplerate);
+    CPipe offset = fo > 0 ? mixDown(fo, (uint32_t)chunk) : (fo < 0 ? mixUp(-fo, (uint32_t)chunk) : idPipe<Array<cf32>>());
+    CPipe resamp = g_front.bandwidth != 0.0 ? resampler((float)(g_front.bandwidth / g_front.samplerate), 60.0f, (uint32_t)chunk)
+                                            : idPipe<Array<cf32>>();
+    auto prep = unPipe(compose(resamp, offset));            // (process, cleanup) <- unPipe (resampler . offset)
+    TakeN take(n);
+    Array<cf32> a;
+    while (src.next(a)) {
+        Array<cf32> b = prep.process(a);
+        if (!take.feed(b)) break;
+        fold.step(b);
+    }
+    src.close();
+    fold.done();
+    prep.cleanup();
+    return 0;
+}
+
 template <class Out> static int run(const std::string &in, const ChainOpts &o, size_t n, const std::string &out, size_t chunk, const char *ext)
 {
     const uint32_t M = o.channels;
@@ -48,24 +71,7 @@ template <class Out> static int run(const std::string &in, const ChainOpts &o, s
     else for (uint32_t row = 0; row < o.owned(); row++) sinks.push_back(make(out + "_ch" + std::to_string(o.channel_of(row) + 1)));
     auto fold = compact<cf32>((size_t)4 * M * 1024, addPipe(fusedChain<Out>(o), std::static_pointer_cast<Fold<std::vector<Array<Out>>>>(
                                                                                     std::make_shared<Distribute<Out>>(sinks))));
-    // prep = takeNArr ns . (resampler . offset)  (SoapySDR.hs:190-207)
-    using CPipe = Pipe<Array<cf32>, Array<cf32>>;
-    const float fo = (float)(2.0 * 3.14159265358979323846 * g_front.offset / g_front.samplerate);
-    CPipe offset = fo > 0 ? mixDown(fo, (uint32_t)chunk) : (fo < 0 ? mixUp(-fo, (uint32_t)chunk) : idPipe<Array<cf32>>());
-    CPipe resamp = g_front.bandwidth != 0.0 ? resampler((float)(g_front.bandwidth / g_front.samplerate), 60.0f, (uint32_t)chunk)
-                                            : idPipe<Array<cf32>>();
-    auto prep = unPipe(compose(resamp, offset));            // (process, cleanup) <- unPipe (resampler . offset)
-    TakeN take(n);
-    Array<cf32> a;
-    while (src.next(a)) {
-        Array<cf32> b = prep.process(a);
-        if (!take.feed(b)) break;
-        fold->step(b);
-    }
-    src.close();
-    fold->done();
-    prep.cleanup();
-    return 0;
+    return pump(src, n, chunk, *fold);
 }
 
 // DeFMS decim fmt (SoapySDR.hs:261-264): prep src -> agc -> fmDemodulator 0.8 -> stereoFMDecoder outBW decim sink, one call per
@@ -82,23 +88,7 @@ static int run_fms(const std::string &in, const ChainOpts &o, size_t n, const st
     const uint32_t cap = (uint32_t)(4 * chunk + 16);                  // the resampler's largest output (rate <= 2)
     Pipe<Array<cf32>, Array<cf32>> agc = o.agc != 0.f ? agcPipe(o.agc, cap) : idPipe<Array<cf32>>();
     auto dem = addPipe(compose(fmStereoPipe((float)bw, o.decim, cap), compose(freqdemPipe(0.8f, cap), agc)), sink);
-    using CPipe = Pipe<Array<cf32>, Array<cf32>>;
-    const float fo = (float)(2.0 * 3.14159265358979323846 * g_front.offset / g_front.samplerate);
-    CPipe offset = fo > 0 ? mixDown(fo, (uint32_t)chunk) : (fo < 0 ? mixUp(-fo, (uint32_t)chunk) : idPipe<Array<cf32>>());
-    CPipe resamp = g_front.bandwidth != 0.0 ? resampler((float)(g_front.bandwidth / g_front.samplerate), 60.0f, (uint32_t)chunk)
-                                            : idPipe<Array<cf32>>();
-    auto prep = unPipe(compose(resamp, offset));
-    TakeN take(n);
-    Array<cf32> a;
-    while (src.next(a)) {
-        Array<cf32> b = prep.process(a);
-        if (!take.feed(b)) break;
-        dem->step(b);
-    }
-    src.close();
-    dem->done();
-    prep.cleanup();
-    return 0;
+    return pump(src, n, chunk, *dem);
 }
 
 // DeNBFMSync k (SoapySDR.hs:273-280): assembleFold with compact (4 k nch 1024) and, per channel, fmDemWithSync k . agc
@@ -115,31 +105,9 @@ static int run_sync(const std::string &in, ChainOpts o, uint32_t k, size_t n, co
     if (mixed || M == 1) sinks.push_back(std::make_shared<FileSink<float>>(out + ".f32"));
     else for (uint32_t c = 0; c < M; c++) sinks.push_back(std::make_shared<FileSink<float>>(out + "_ch" + std::to_string(c + 1) + ".f32"));
     std::shared_ptr<Fold<Rows>> tail = std::make_shared<Distribute<float>>(sinks);
-    if (mixed) {
-        Pipe<Rows, Rows> mixp;
-        mixp.start = []() { return std::shared_ptr<void>(); };
-        mixp.process = [](void *, const Rows &rows) { return Rows{mix(rows)}; };
-        mixp.done = [](void *) {};
-        tail = addPipe(mixp, tail);
-    }
+    if (mixed) tail = addPipe(purePipe<Rows, Rows>([](const Rows &rows) { return Rows{mix(rows)}; }), tail);
     auto fold = compact<cf32>((size_t)4 * k * M * 1024, addPipe(fusedChain<float>(o), addPipe(symSyncR(k, 4, 0.f, 64, M, 4 * k * 1024), tail)));
-    using CPipe = Pipe<Array<cf32>, Array<cf32>>;
-    const float fo = (float)(2.0 * 3.14159265358979323846 * g_front.offset / g_front.samplerate);
-    CPipe offset = fo > 0 ? mixDown(fo, (uint32_t)chunk) : (fo < 0 ? mixUp(-fo, (uint32_t)chunk) : idPipe<Array<cf32>>());
-    CPipe resamp = g_front.bandwidth != 0.0 ? resampler((float)(g_front.bandwidth / g_front.samplerate), 60.0f, (uint32_t)chunk)
-                                            : idPipe<Array<cf32>>();
-    auto prep = unPipe(compose(resamp, offset));
-    TakeN take(n);
-    Array<cf32> a;
-    while (src.next(a)) {
-        Array<cf32> b = prep.process(a);
-        if (!take.feed(b)) break;
-        fold->step(b);
-    }
-    src.close();
-    fold->done();
-    prep.cleanup();
-    return 0;
+    return pump(src, n, chunk, *fold);
 }
 
 int main(int argc, char **argv)

@@ -99,6 +99,59 @@ int main()
         d.done();
         assert(s0->items.size() == 2 && s1->items.size() == 1 && s0->finished && s1->finished);
     }
+    {   // handlePipe: one create per start, the typed handle in process, one destroy when the last holder goes (not at done)
+        struct Fake { int v; };
+        int made = 0, freed = 0;
+        auto destroy = [&](Fake *h) { freed++; delete h; };
+        auto twice = [](Fake *h, const int &a) { return h->v * a; };
+        auto p = handlePipe<Fake, int, int>([&](Fake **h) { *h = new Fake{2}; made++; }, destroy, twice);
+        {
+            auto r = p.start();
+            assert(made == 1 && freed == 0 && p.process(r.get(), 21) == 42);
+            auto keep = r;
+            p.done(r.get());
+            r.reset();
+            assert(freed == 0 && p.process(keep.get(), 4) == 8);       // done does not destroy: the resource has a holder left
+        }
+        assert(made == 1 && freed == 1);
+        auto u = unPipe(p);
+        assert(made == 2 && u.process(3) == 6);
+        u.cleanup();
+        assert(freed == 1 && u.process(5) == 10);
+        u = UnPiped<int, int>();
+        assert(freed == 2);
+        bool threw = false;                                             // a create that throws before it has a handle destroys nothing
+        try { handlePipe<Fake, int, int>([](Fake **) { throw std::runtime_error("no"); }, destroy, twice).start(); } catch (const std::runtime_error &) { threw = true; }
+        assert(threw && freed == 2);
+        threw = false;                                                  // a second step that throws (symSyncC's) destroys the handle once
+        try { handlePipe<Fake, int, int>([&](Fake **h) { *h = new Fake{1}; made++; throw std::runtime_error("no"); }, destroy, twice).start(); } catch (const std::runtime_error &) { threw = true; }
+        assert(threw && made == 3 && freed == 3);
+    }
+    {   // flattenRows / splitRows: the round trip, the shape rule, and rows of unequal length
+        const Rows<float> rows = {iota(0, 5), iota(10, 15), iota(20, 25)};
+        const Array<float> flat = flattenRows(rows, 3, "t");
+        assert(flat.size() == 15 && flat[5] == 10.f && flat[14] == 24.f);
+        assert(splitRows(flat, 3, 5, 5) == rows);
+        const Rows<float> cut = splitRows(flat, 3, 5, std::vector<uint32_t>{0, 2, 5});
+        assert(cut.size() == 3 && cut[0].empty() && cut[1] == iota(10, 12) && cut[2] == rows[2]);
+        int calls = 0;
+        struct Fake {} fake;
+        auto p = rowPipe<Fake, float, float>("echo", 3, [&](Fake **h) { *h = &fake; }, [](Fake *) {},
+                                             [&](Fake *, const Array<float> &x, uint32_t n) { calls++; return splitRows(x, 3, n, n); });
+        auto r = p.start();
+        assert(p.process(r.get(), rows) == rows && calls == 1);
+        assert(p.process(r.get(), Rows<float>{iota(0, 5), iota(0, 5)}) == Rows<float>(2));                   // wrong row count
+        assert(p.process(r.get(), Rows<float>{{}, iota(0, 5), iota(0, 5)}) == Rows<float>(3));               // empty first row
+        assert(p.process(r.get(), Rows<float>{}).empty() && calls == 1);                                     // zero rows
+        assert(flattenRows(Rows<float>{}, 0, "t").empty());                                                  // ... also of a pipe of none
+        for (const Rows<float> &bad : {Rows<float>{iota(0, 5), iota(0, 5), iota(0, 4)}, Rows<float>{iota(0, 2), iota(0, 5)}}) {
+            std::string what;
+            try { rowPipe<Fake, float, float>("echo", (uint32_t)bad.size(), [&](Fake **h) { *h = &fake; }, [](Fake *) {},
+                                              [&](Fake *, const Array<float> &, uint32_t) { calls++; return Rows<float>(); }).process(&fake, bad); }
+            catch (const std::runtime_error &e) { what = e.what(); }
+            assert(what.find("echo") == 0 && calls == 1);                                                    // names the pipe; nothing copied or called
+        }
+    }
     std::cout << "host combinators ok\n";
     return 0;
 }

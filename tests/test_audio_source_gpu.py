@@ -12,13 +12,13 @@ import numpy as np
 import pytest
 
 import helilink
+from host_exe import host_exe
 
 pytestmark = pytest.mark.gpu
 
 cs = pytest.importorskip("composable_sdr_amd")
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EXE = os.path.join(ROOT, "composable_sdr_amd", "host", "soapy_sdr_file")
 f32 = np.float32
 
 
@@ -50,9 +50,7 @@ def _by_hand(wav, chunksize, raw):
 
 
 def _cpp(args):
-    if not os.path.exists(EXE):
-        subprocess.check_call(["make", "-C", os.path.dirname(EXE), "-s"])
-    return subprocess.run([EXE] + [str(a) for a in args], capture_output=True, text=True, timeout=300, env=dict(os.environ, CSDR_QUIET="1"))
+    return subprocess.run([host_exe("soapy_sdr_file")] + [str(a) for a in args], capture_output=True, text=True, timeout=300, env=dict(os.environ, CSDR_QUIET="1"))
 
 
 def _real_band_signal(n, seed):

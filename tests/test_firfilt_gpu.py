@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import fir_restatement as R
+from host_exe import host_exe
 from synth import channel_centre
 
 pytestmark = pytest.mark.gpu
@@ -273,10 +274,7 @@ def test_cpp_pipes_write_the_same_bytes_as_the_python_pipes(tmp_path, kind):
     src, dst, tp = tmp_path / "in.raw", tmp_path / "out.raw", tmp_path / "taps.f32"
     x.tofile(src)
     taps.tofile(tp)
-    host = os.path.join(ROOT, "composable_sdr_amd", "host")
-    exe = os.path.join(host, "firfilt_host")
-    if not os.path.exists(exe):
-        subprocess.check_call(["make", "-C", host, "-s", "firfilt_host"])
+    exe = host_exe("firfilt_host")
     design = "65:0.05:60" if kind == "k" else f"{tp}:0.25"
     r = subprocess.run([exe, kind, design, str(C), ",".join(map(str, chunks)), str(src), str(dst)], capture_output=True, text=True,
                        timeout=120)

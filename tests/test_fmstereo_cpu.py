@@ -9,6 +9,7 @@ import pytest
 
 import fms_restatement as F
 import oracle_lib as O
+from host_exe import host_exe
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -105,9 +106,7 @@ def test_stereo_decoder_without_gpu_is_nodev():
 
 def test_cpp_host_parses_defms(tmp_path):
     """`--demod DeFMS 4` is an option of the C++ host (it used to stop with "unknown option 4")"""
-    exe = os.path.join(ROOT, "composable_sdr_amd", "host", "soapy_sdr_file")
-    if not os.path.exists(exe):
-        subprocess.check_call(["make", "-C", os.path.dirname(exe), "-s"])
+    exe = host_exe("soapy_sdr_file")
     r = subprocess.run([exe, "--filename", "/nonexistent.cf32", "-n", "16", "--demod", "DeFMS", "4", "--audio", "AU", "-o",
                         str(tmp_path / "fms")], capture_output=True, text=True, timeout=120, env=dict(os.environ, CSDR_QUIET="1"))
     assert "unknown option" not in r.stderr, r.stderr

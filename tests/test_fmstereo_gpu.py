@@ -14,6 +14,7 @@ import pytest
 
 import fms_restatement as F
 import oracle_lib as O
+from host_exe import host_exe
 from synth import synth_cf32
 
 pytestmark = pytest.mark.gpu
@@ -156,9 +157,7 @@ def test_sdr_process_fms_matches_replay_and_cpp_host(tmp_path, monkeypatch, band
     scale = np.abs(want).max()
     _report(f"sdr_process DeFMS 4 -b {bandwidth}", got, want)
     assert np.median(d) < 2e-5 * scale and np.quantile(d, 0.99) < 2e-3 * scale
-    exe = os.path.join(ROOT, "composable_sdr_amd", "host", "soapy_sdr_file")
-    if not os.path.exists(exe):
-        subprocess.check_call(["make", "-C", os.path.dirname(exe), "-s"])
+    exe = host_exe("soapy_sdr_file")
     args = [exe, "--filename", str(src), "-n", str(n), "-c", "1", "--demod", "DeFMS", "4", "-s", str(fs), "--audio", "AU",
             "-o", str(tmp_path / "cc")]
     if bandwidth:

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import fsk_restatement as F
+from host_exe import host_exe
 from synth import channel_centre
 
 pytestmark = pytest.mark.gpu
@@ -280,10 +281,7 @@ def test_cpp_pipe_writes_the_same_bytes_as_the_python_pipe(tmp_path):
     x = _noise((C, n), seed=21)
     src, dst = tmp_path / "in.cf32", tmp_path / "out.u32"
     x.tofile(src)
-    host = os.path.join(ROOT, "composable_sdr_amd", "host")
-    exe = os.path.join(host, "fskdem_host")
-    if not os.path.exists(exe):
-        subprocess.check_call(["make", "-C", host, "-s", "fskdem_host"])
+    exe = host_exe("fskdem_host")
     r = subprocess.run([exe, str(m), str(k), str(bw), str(C), str(chunk), str(src), str(dst)], capture_output=True, text=True,
                        timeout=120, env=dict(os.environ, CSDR_QUIET="1"))
     assert r.returncode == 0, r.stderr

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import gmsk_restatement as G
+from host_exe import host_exe
 from synth import channel_centre
 
 pytestmark = pytest.mark.gpu
@@ -301,10 +302,7 @@ def test_cpp_pipe_writes_the_same_bytes_as_the_python_pipe(tmp_path):
     x = _rows((k, m, bw), C, n // k)
     src, dst = tmp_path / "in.cf32", tmp_path / "out.u32"
     x.tofile(src)
-    host = os.path.join(ROOT, "composable_sdr_amd", "host")
-    exe = os.path.join(host, "gmskdem_host")
-    if not os.path.exists(exe):
-        subprocess.check_call(["make", "-C", host, "-s", "gmskdem_host"])
+    exe = host_exe("gmskdem_host")
     r = subprocess.run([exe, str(m), str(k), str(bw), str(C), str(chunk), str(src), str(dst)], capture_output=True, text=True,
                        timeout=120, env=dict(os.environ, CSDR_QUIET="1"))
     assert r.returncode == 0, r.stderr

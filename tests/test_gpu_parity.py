@@ -17,6 +17,7 @@ import numpy as np
 import pytest
 
 import oracle_lib as O
+from host_exe import host_exe
 from synth import synth_cf32
 from util import knob, max_abs_err, rel_rms, wrap_pm
 
@@ -1078,10 +1079,7 @@ def test_cpp_soapy_sdr_file_matches_python_replay(tmp_path):
     import os
     import subprocess
     from composable_sdr_amd.app import sdr_process
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    exe = os.path.join(root, "composable_sdr_amd", "host", "soapy_sdr_file")
-    if not os.path.exists(exe):
-        subprocess.check_call(["make", "-C", os.path.dirname(exe), "-s"])
+    exe = host_exe("soapy_sdr_file")
     M, n = 64, 64 * 4096 + 64 * 37
     x = synth_cf32(n + 100, M, seed=6)
     src = tmp_path / "in.cf32"
@@ -1103,9 +1101,7 @@ def test_cpp_soapy_sdr_file_channel_shards_and_mix_through_the_c_collectives(tmp
     (RCCL all-reduce under the C ABI) and leaves the unsharded run's bytes."""
     import os
     import subprocess
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    exe = os.path.join(root, "composable_sdr_amd", "host", "soapy_sdr_file")
-    subprocess.check_call(["make", "-C", os.path.dirname(exe), "-s"])
+    exe = host_exe("soapy_sdr_file")
     M, n, W = 64, 64 * 4096 * 2 + 64 * 37, 2
     x = synth_cf32(n + 100, M, seed=61)
     src = tmp_path / "in.cf32"
@@ -1869,10 +1865,7 @@ def test_cpp_soapy_sdr_file_front_end_matches_python_replay(tmp_path, monkeypatc
     import subprocess
     monkeypatch.setenv("CSDR_QUIET", "1")
     from composable_sdr_amd.app import sdr_process
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    exe = os.path.join(root, "composable_sdr_amd", "host", "soapy_sdr_file")
-    if not os.path.exists(exe):
-        subprocess.check_call(["make", "-C", os.path.dirname(exe), "-s"])
+    exe = host_exe("soapy_sdr_file")
     x = synth_cf32(400000, 1, seed=8)
     src = tmp_path / "in.cf32"
     x.tofile(src)
@@ -1959,10 +1952,7 @@ def test_cpp_soapy_sdr_file_wbfm_audio_matches_python_replay(tmp_path, monkeypat
     import subprocess
     monkeypatch.setenv("CSDR_QUIET", "1")
     from composable_sdr_amd.app import sdr_process
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    exe = os.path.join(root, "composable_sdr_amd", "host", "soapy_sdr_file")
-    if not os.path.exists(exe):
-        subprocess.check_call(["make", "-C", os.path.dirname(exe), "-s"])
+    exe = host_exe("soapy_sdr_file")
     x = synth_cf32(600000, 1, seed=18)
     src = tmp_path / "in.cf32"
     x.tofile(src)

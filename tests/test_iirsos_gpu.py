@@ -18,6 +18,7 @@ import numpy as np
 import pytest
 
 import iir_restatement as R
+from host_exe import host_exe
 from synth import channel_centre
 
 pytestmark = pytest.mark.gpu
@@ -311,10 +312,7 @@ def test_cpp_pipes_write_the_same_bytes_as_the_python_pipes(tmp_path, kind):
     src, dst, sp = tmp_path / "in.raw", tmp_path / "out.raw", tmp_path / "sos.f32"
     x.tofile(src)
     sos.tofile(sp)
-    host = os.path.join(ROOT, "composable_sdr_amd", "host")
-    exe = os.path.join(host, "iirsos_host")
-    if not os.path.exists(exe):
-        subprocess.check_call(["make", "-C", host, "-s", "iirsos_host"])
+    exe = host_exe("iirsos_host")
     design = "5:0.05" if kind == "p" else str(sp)
     r = subprocess.run([exe, kind, design, str(C), ",".join(map(str, chunks)), str(src), str(dst)], capture_output=True, text=True,
                        timeout=120)

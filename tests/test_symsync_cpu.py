@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import symsync_restatement as S
+from host_exe import host_exe
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 f32 = np.float32
@@ -124,9 +125,7 @@ def test_symsync_without_gpu_is_nodev():
 
 def test_cpp_host_parses_denbfmsync(tmp_path):
     """`--demod DeNBFMSync 4` is an option of the C++ host (it used to stop with "unknown option 4")"""
-    exe = os.path.join(ROOT, "composable_sdr_amd", "host", "soapy_sdr_file")
-    if not os.path.exists(exe):
-        subprocess.check_call(["make", "-C", os.path.dirname(exe), "-s"])
+    exe = host_exe("soapy_sdr_file")
     r = subprocess.run([exe, "--filename", "/nonexistent.cf32", "-n", "16", "--demod", "DeNBFMSync", "4", "-o",
                         str(tmp_path / "sync")], capture_output=True, text=True, timeout=120, env=dict(os.environ, CSDR_QUIET="1"))
     assert "unknown option" not in r.stderr, r.stderr

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import symsync_restatement as S
+from host_exe import host_exe
 from synth import synth_cf32
 
 pytestmark = pytest.mark.gpu
@@ -196,9 +197,7 @@ def test_sdr_process_nbfmsync_matches_replay_and_cpp_host(tmp_path, monkeypatch,
         got = np.fromfile(p, dtype=f32)
         assert got.size == w.size and got.size > 0, p
         assert np.array_equal(_bits(got), _bits(w)), p
-    exe = os.path.join(ROOT, "composable_sdr_amd", "host", "soapy_sdr_file")
-    if not os.path.exists(exe):
-        subprocess.check_call(["make", "-C", os.path.dirname(exe), "-s"])
+    exe = host_exe("soapy_sdr_file")
     args = [exe, "--filename", str(src), "-n", str(n), "-c", str(nch), "--demod", "DeNBFMSync", str(k), "-s", "2.56e6",
             "-o", str(tmp_path / "cc")] + (["-m"] if mixed else [])
     r = subprocess.run(args, capture_output=True, text=True, timeout=300, env=dict(os.environ, CSDR_QUIET="1"))

@@ -13,6 +13,7 @@ import pytest
 
 import symsync_restatement as S
 import symsyncc_restatement as R
+from host_exe import host_exe
 from synth import synth_cf32
 
 pytestmark = pytest.mark.gpu
@@ -272,9 +273,7 @@ def test_pipe_over_three_chunks_equals_the_object_and_the_cpp_host(tmp_path):
     obj.close()
     for c in range(C):
         assert np.array_equal(_bits(np.concatenate([ch[c] for ch in chunks])), _bits(got[c])), c
-    exe = os.path.join(ROOT, "composable_sdr_amd", "host", "symsyncc_host")
-    if not os.path.exists(exe):
-        subprocess.check_call(["make", "-C", os.path.dirname(exe), "-s"])
+    exe = host_exe("symsyncc_host")
     src, dst = tmp_path / "in.cf32", tmp_path / "out.cf32"
     X.astype(c64).tofile(src)
     p = subprocess.run([exe, "3", "2", str(C), "500", str(src), str(dst)], capture_output=True, text=True, timeout=120)
