@@ -268,9 +268,9 @@ int csdr_chain_create(const csdr_chain_cfg *cfg_in, csdr_chain **out)
     // with CSDR_FLAG_AGC_SEQUENTIAL one lane per channel) + freqdem + mix follow.
     const RouteRow *route = nullptr;
     std::string front = "tail-only+agc";
+    int cus = 256;                   // compute units of the device (run counts of k_pfb1024 and of the plans: FusedConfig::cus; the AGC tail's segments)
+    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device);
     if (!tail_only) {
-        int cus = 256;               // compute units of the device (run counts of k_pfb1024 and of the plans: FusedConfig::cus)
-        (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device);
         h->timer.enabled = (cfg->flags & (CSDR_FLAG_TIME_KERNELS | CSDR_FLAG_TIME_REGION)) != 0;
         h->timer.region = (cfg->flags & CSDR_FLAG_TIME_REGION) != 0;
         DcParams dc{};
@@ -300,7 +300,7 @@ int csdr_chain_create(const csdr_chain_cfg *cfg_in, csdr_chain **out)
     const bool fused = route && route->M;
     if (agc_on) {
         h->agc = std::make_unique<AgcTail>();
-        if ((r = h->agc->setup(h->mem, *cfg, C, h->max_nf, !tail_only, fused))) return r;
+        if ((r = h->agc->setup(h->mem, *cfg, C, h->max_nf, !tail_only, fused, (uint32_t)cus))) return r;
     }
     if (!tail_only && (cfg_in->flags & CSDR_FLAG_DFT_BACKWARD) && M > 1 && !(cfg_in->mix != 0)) {
         if (C != M || G > 1) { set_error("chain: CSDR_FLAG_DFT_BACKWARD is built for whole-band handles (no channel shard)"); return CSDR_ERR_INVALID; }

@@ -1,18 +1,20 @@
 // The tails behind the plan of a chain handle (capi.hip): the AGC tail, the AM and the WBFM tails, the backward handle's row
 // reversal.  Each one owns its buffers (out of the handle's mem) and its stream state, and has three operations: setup() from the
 // configuration (allocations, design, its piece of csdr_chain_path), reset() and run() for one call.  The handle has a tail or it
-// has not.  Local to the translation unit that includes it.
+// has not.  The launch shape of the time-parallel AGC tail is agc_tail_shape.h's.  Local to the translation unit that
+// includes it.
 #pragma once
 #include "capi_internal.h"
+#include <optional>
 
 namespace csdr {
 namespace {
 // Z[C][nf] (channel-major CF32) -> AGC + squelch [+ freqdem] [+ mix] -> out: the time-parallel verified tail (tm: Z tile-major), or
 // with CSDR_FLAG_AGC_SEQUENTIAL one lane per channel in place on Z.  State: AGC {g, y2', mode, timer} + freqdem r' per row
 struct AgcTail {
-    ~AgcTail() { if (spec) agc_tail_destroy(spec); }
-    // front: a plan writes Z (none: the caller's rows are Z); fused: that plan may write Z tile-major and its path says +agc
-    int setup(DeviceBuffers &mem, const csdr_chain_cfg &cfg, uint32_t C_, uint32_t max_nf, bool front, bool fused)
+    // front: a plan writes Z (none: the caller's rows are Z); fused: that plan may write Z tile-major and its path says +agc; cus: compute
+    // units of the handle's device
+    int setup(DeviceBuffers &mem, const csdr_chain_cfg &cfg, uint32_t C_, uint32_t max_nf, bool front, bool fused, uint32_t cus)
     {
         const bool sequential = (cfg.flags & CSDR_FLAG_AGC_SEQUENTIAL) != 0;
         C = C_; prm = make_agc(cfg.agc_threshold_db);
@@ -27,7 +29,7 @@ struct AgcTail {
             // The guards (2 x 64 KiB per channel: 128 MiB at 1024 channels) exist only where a call can take that route: a fused plan (the
             // any-M plan never writes tile-major), a time-parallel tail, a channel count k_agc_spec_tm takes, calls of >= 4 W = 4096 frames
             // 
-            if (fused && !sequential && max_nf >= 4096u && (C % 64u == 0 || (C < 64u && 64u % C == 0))) guard = agc_tail_tm_guard(C);
+            if (fused && !sequential && max_nf >= 4096u && agc_tail_tm_channels_ok(C)) guard = agc_tail_tm_guard(C);
             const size_t n = (size_t)C * max_nf;
             if ((r = mem.alloc_n(&d_A, n + 2 * guard))) return r;
             if (guard) {
@@ -37,7 +39,7 @@ struct AgcTail {
             }
         }
         if (mixo && (r = mem.alloc_n(&d_B, (size_t)C * max_nf))) return r;
-        if (!sequential && (r = agc_tail_create(C, max_nf, &spec))) return r;
+        if (!sequential && (r = spec.emplace().init(mem, C, max_nf, cus))) return r;
         piece = !spec ? "" : (fused || !front) ? "-spec" : "+agc-spec";
         return CSDR_OK;
     }
@@ -45,19 +47,19 @@ struct AgcTail {
     int reset(hipStream_t s)
     {
         int r = launch_agc_init(st, C, s); if (r) return r;
-        if (spec) agc_tail_reset(spec);
+        if (spec) spec->reset();
         return fm ? rp.reset(s) : CSDR_OK;
     }
-    bool time_parallel() const { return spec != nullptr; }         // (reads Z only)
+    bool time_parallel() const { return spec.has_value(); }         // (reads Z only)
     // where a front writes Z for run(..., out): the tail's plane, or out itself where the sequential AGC is the last step
     float2 *plane(void *out) const { return in_place ? (float2 *)out : d_A + guard; }
-    bool tile_major(uint32_t nf) const { return spec && guard && agc_tail_tm_supported(spec, nf); }    // the front may write plane() tile-major
+    bool tile_major(uint32_t nf) const { return spec && guard && spec->tm_supported(nf); }    // the front may write plane() tile-major
     int run(float2 *Z, uint32_t nf, void *out, hipStream_t s, bool tm)
     {
         int r;
         if (spec) {
             void *T = mixo ? (void *)d_B : out;
-            if ((r = agc_tail_process(spec, Z, T, fm, nf, st, prm, fm_ref, fm ? rp.in() : nullptr, fm ? rp.out() : nullptr, s, tm))) return r;
+            if ((r = spec->run(Z, T, fm, nf, st, prm, fm_ref, fm ? rp.in() : nullptr, fm ? rp.out() : nullptr, s, tm))) return r;
             if (fm) rp.flip();
             return mixo ? launch_mix((const float *)T, (float *)out, C, fm ? nf : 2 * nf, s) : CSDR_OK;
         }
@@ -70,8 +72,8 @@ struct AgcTail {
         } else if (mixo) return launch_mix((const float *)Z, (float *)out, C, 2 * nf, s);
         return CSDR_OK;
     }
-    int stats(uint32_t *checked, uint32_t *redone) { return spec ? agc_tail_stats(spec, checked, redone) : 0; }
-    uint32_t tile_major_calls() const { return spec ? agc_tail_tm_calls(spec) : 0u; }
+    int stats(uint32_t *checked, uint32_t *redone) { return spec ? spec->stats(checked, redone) : 0; }
+    uint32_t tile_major_calls() const { return spec ? spec->tm_calls : 0u; }
 private:
     uint32_t C = 0; AgcParams prm; float fm_ref = 0.f;
     bool fm = false, mixo = false, in_place = false;
@@ -79,7 +81,7 @@ private:
     AgcState *st = nullptr; PingPong<float2> rp;
     float2 *d_A = nullptr, *d_B = nullptr;    // Z, the plane between the front and the tail (guard readable elements on either side); the tail's output in front of --mix
     size_t guard = 0;
-    AgcTailPlan *spec = nullptr;              // the time-parallel tail (kernels_agc_tail.hip); null: CSDR_FLAG_AGC_SEQUENTIAL
+    std::optional<AgcTailPlan> spec;          // the time-parallel tail (kernels_agc_tail.hip); none: CSDR_FLAG_AGC_SEQUENTIAL
 };
 
 // DeAM = amDemodulator . agc: the chain runs as DeNo into input(), then the ampmodem peak detector (kernels_am.hip) [+ mix]

@@ -6,6 +6,7 @@
 #include <stdlib.h>
 #include <string>
 #include <vector>
+#include "agc_tail_shape.h"
 
 namespace csdr {
 
@@ -323,19 +324,31 @@ int launch_gmskdem(const float2 *x, uint32_t *sym, float *soft, const float *h, 
                    const GmskdemLaunch &l, hipStream_t s);
 
 // ---- time-parallel exact AGC [+ freqdem] tail (kernels_agc_tail.hip) ----
-struct AgcTailPlan;
-int agc_tail_create(uint32_t C, uint32_t max_nf, AgcTailPlan **out);
-void agc_tail_destroy(AgcTailPlan *p);
-// Z[C][nf] -> out[C][nf] (CF32, or F32 when fm); st (and rp_in -> rp_out when fm) carry the per-channel state
-// tm: Z is a TILE-MAJOR plane -- sample (c, t) at ((t >> 4) C + c) 16 + (t & 15), agc_tail_tm_guard(C) readable elements in front of
-// Z and behind the plane -- which the fused M = 256 run kernels write for calls agc_tail_tm_supported() accepts (k_agc_spec_tm)
-int agc_tail_process(AgcTailPlan *p, const float2 *Z, void *out, bool fm, uint32_t nf, AgcState *st, const AgcParams &prm,
-                     float fm_ref, const float2 *rp_in, float2 *rp_out, hipStream_t s, bool tm = false);
-bool agc_tail_tm_supported(const AgcTailPlan *p, uint32_t nf);
-size_t agc_tail_tm_guard(uint32_t C);
-uint32_t agc_tail_tm_calls(const AgcTailPlan *p);
-int agc_tail_stats(AgcTailPlan *p, unsigned *checked, unsigned *redone);
-void agc_tail_reset(AgcTailPlan *p);     // the AGC state was re-initialised: the next call pilots (kernels_agc_tail.hip)
+// The state of one tail (a member of AgcTail, chain_tails.h); which kernel a call takes, with which segments and grids: agc_tail_shape.h
+struct AgcTailPlan {
+    // calls of up to max_nf frames on C rows; the tables come out of mem; cus: compute units of the handle's device.  Reads CSDR_AGC_L,
+    // _L_TM, _W, _WGS, _TM and CSDR_CUS
+    int init(DeviceBuffers &mem, uint32_t C, uint32_t max_nf, uint32_t cus);
+    void reset() { fresh = true; seen = 0; }       // the AGC state was re-initialised: the next call pilots
+    int stats(unsigned *checked, unsigned *redone) const;
+    bool tm_supported(uint32_t nf) const { return agc_tail_tm_supported(knobs, C, nf); }
+    // Z[C][nf] -> out[C][nf] (CF32, or F32 when fm); st (and rp_in -> rp_out when fm) carry the per-channel state
+    // tm: Z is a TILE-MAJOR plane -- sample (c, t) at ((t >> 4) C + c) 16 + (t & 15), agc_tail_tm_guard(C) readable elements in front of
+    // Z and behind the plane -- which the fused run kernels write for calls tm_supported() accepts (k_agc_spec_tm)
+    int run(const float2 *Z, void *out, bool fm, uint32_t nf, AgcState *st, const AgcParams &prm, float fm_ref, const float2 *rp_in,
+            float2 *rp_out, hipStream_t s, bool tm);
+    uint32_t tm_calls = 0;           // calls that took k_agc_spec_tm since init
+private:
+    uint32_t C = 0;
+    AgcTailKnobs knobs;
+    AgcTailSizes sizes{};
+    void *d_start = nullptr, *d_end = nullptr, *d_ckpt = nullptr;    // AgcSeg records (kernels_agc_tail.hip): [C][max_seg] x 2, [ckpt_cap]
+    AgcState *d_st_tmp = nullptr;    // [C] settled state of the pilot (first call of a stream)
+    unsigned *d_stats = nullptr;
+    bool fresh = true;               // the AGC state is still inside its create-time transient: the next call runs the pilot
+    uint32_t pilot_n = 4096;
+    uint64_t seen = 0;               // samples per channel since init / reset
+};
 
 // ---- hipEvent bracket around the dominant kernel (CSDR_FLAG_TIME_KERNELS) ----
 struct KernelTimer {

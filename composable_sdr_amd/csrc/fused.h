@@ -2,6 +2,7 @@
 // 1024, 4096) and the any-M route.  Product code.
 //   chain_plan.cpp            what the plans share: ChainPlan::process, StreamState, DcConsts, ColdStart, dc_state_response
 //   kernel_choice.h           which kernel a call takes (KernelChoice, the run counts, the M = 64 and M = 1024 selection); no HIP
+//   agc_tail_shape.h          the launch shape of the AGC tail behind the plans (kernels_agc_tail.hip, chain_tails.h); no HIP
 //   kernels_fused_small.hip   M = 64: SmallPlan, k_run64; its run kernel k_run64v2 in kernels_run64_v2.hip
 //   kernels_fused.hip         M = 256: FusedPlan, k_tile256; its run kernel k_run256v2 in kernels_fused_v2.hip
 //   kernels_pfb1024.hip       M = 1024: BigPlan, k_run1024; its run kernels in kernels_run1024_v2.hip, kernels_run1024_v3.hip, kernels_shard1024.hip
@@ -244,25 +245,47 @@ int run1024_v3_launch(const Run1024Call &h, hipStream_t s, KernelTimer *timer);
 int shard1024_launch(const Run1024Call &h, hipStream_t s, KernelTimer *timer);
 
 
-// single-pass DC blocker + NCO mix for whole chunks of the generic path (kernels_dc_tile.hip)
-struct DcTilePlan;
-int  dctile_create(const DcParams &dc, uint64_t max_samples, DcTilePlan **out);
-int  dctile_reset(DcTilePlan *plan, hipStream_t s);
-// pick > 0: y receives only the samples whose index in this call is a multiple of `pick` (n / pick of them)
-int  dctile_process(DcTilePlan *plan, const float2 *x, float2 *y, uint32_t n, bool do_mix, const NcoParams &nco,
-                    const float2 *nco_tab, hipStream_t s, uint32_t pick = 0);
-// out[t] = M sum_n taps[(M-1) + n M] u0[(p-1) + t - n]; hist_out <- the last p - 1 samples of u0 (the next call's history)
-bool dctile_mix_identity_supported(const DcTilePlan *plan, uint32_t M, uint32_t n, uint32_t taps_p);
-int  dctile_mix_identity(DcTilePlan *plan, const float2 *x, uint32_t n, const NcoParams &nco, const float2 *nco_tab, const float *taps,
-                         uint32_t M, uint32_t taps_p, const float2 *hist_in, float2 *hist_out, float2 *out, hipStream_t s);
-// the mix identity of an interleaved channel shard g of G (G <= 8, (M / G) % 512 == 0): (M / G) sum_{n2 < G} W_G^(n2 g) x (FIR of branch
-// (M / G) n2); hist_in / hist_out: [G][p - 1]
-bool dctile_mix_identity_shard_supported(const DcTilePlan *plan, uint32_t M, uint32_t n, uint32_t taps_p, uint32_t G);
-int  dctile_mix_identity_shard(DcTilePlan *plan, const float2 *x, uint32_t n, const NcoParams &nco, const float2 *nco_tab, const float *taps,
-                               uint32_t M, uint32_t taps_p, uint32_t G, uint32_t g, const float2 *hist_in, float2 *hist_out, float2 *out, hipStream_t s);
+// Single-pass DC blocker + NCO mix for whole chunks of the any-M route (kernels_dc_tile.hip), a member of GenericPlan.
+// k_dc_tile looks back LOOKBACK tiles; k_dc_fold / k_dc_fold8 fold with beta^-512 ratios: a handle whose alpha does not fit them
+// (dc_window_ok) has no DcTilePlan and keeps the exact block scan
+bool dctile_supported(const DcParams &dc);
+struct DcTilePlan {
+    explicit DcTilePlan(const DcParams &dc) : dcc(true, dc) {}
+    // calls of up to max_samples samples; the arrays come out of mem; cus: compute units of the handle's device (the k_dc_fold grid);
+    // shard8: the handle takes mix_identity_shard (k_dc_fold8's scratch)
+    int init(DeviceBuffers &mem, uint64_t max_samples, uint32_t cus, bool shard8);
+    int reset(hipStream_t s);
+    // pick > 0: y receives only the samples whose index in this call is a multiple of `pick` (n / pick of them)
+    int process(const float2 *x, float2 *y, uint32_t n, bool do_mix, const NcoParams &nco, const float2 *nco_tab, hipStream_t s, uint32_t pick = 0);
+    // DeNo --mix over all M channels, M a multiple of 4096, n a multiple of M: out[n / M] = M x (branch-0 FIR of the DC-blocked,
+    // pre-mixed stream): out[t] = M sum_n taps[(M-1) + n M] u0[(p-1) + t - n]; hist_in / hist_out: the p - 1 picked samples before /
+    // after the call (different buffers)
+    bool mix_identity_supported(uint32_t M, uint32_t n, uint32_t taps_p) const
+    {
+        return M && M % 4096u == 0 && n && n % M == 0 && dcc.beta > 0.f && taps_p >= 1 && taps_p <= 33;
+    }
+    int mix_identity(const float2 *x, uint32_t n, const NcoParams &nco, const float2 *nco_tab, const float *taps, uint32_t M, uint32_t taps_p,
+                     const float2 *hist_in, float2 *hist_out, float2 *out, hipStream_t s);
+    // the same for the interleaved channel shard g of G: out[n / M] = (M / G) sum_{n2 < G} W_G^(n2 g) x (FIR of branch (M / G) n2); G <= 8,
+    // (M / G) % 512 == 0; hist_in / hist_out: [G][p - 1]
+    bool mix_identity_shard_supported(uint32_t M, uint32_t n, uint32_t taps_p, uint32_t G) const
+    {
+        return d_part8 && mix_identity_supported(M, n, taps_p) && (G == 2 || G == 4 || G == 8) && M % G == 0 && (M / G) % 512u == 0;
+    }
+    int mix_identity_shard(const float2 *x, uint32_t n, const NcoParams &nco, const float2 *nco_tab, const float *taps, uint32_t M, uint32_t taps_p,
+                           uint32_t G, uint32_t g, const float2 *hist_in, float2 *hist_out, float2 *out, hipStream_t s);
+    // sticky device-side error word (a look-back wait hit its spin limit); reads, then clears it; synchronises
+    int status(unsigned *status);
+
+    const DcConsts dcc;
+    uint32_t max_nb = 0, epoch = 0, cus = 256;
+    unsigned *d_ticket = nullptr, *d_status = nullptr;
+    unsigned long long *d_agg = nullptr;
+    float2 *d_part = nullptr;            // k_dc_fold: one aggregate and the first sample per tile
+    float2 *d_part8 = nullptr;           // k_dc_fold8 (shard8): 8 aggregates + 8 first samples per tile
+    float2 *d_vend[2] = {nullptr, nullptr};
+    int cur = 0;
+};
 int  launch_branch0_fir(const float2 *u0, const float *taps, float2 *out, float2 *hist_out, uint32_t M, uint32_t p, uint32_t nf, hipStream_t s);
-// sticky device-side error word (a look-back wait hit its spin limit); reads, then clears it; synchronises
-int  dctile_status(DcTilePlan *plan, unsigned *status);
-void dctile_destroy(DcTilePlan *plan);
 
 }  // namespace csdr

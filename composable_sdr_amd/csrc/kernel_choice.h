@@ -83,6 +83,13 @@ inline uint32_t huge_runs(uint32_t nf, uint32_t cus, uint32_t runs_knob)
     return nruns ? nruns : 1;
 }
 
+// k_dc_fold, k_dc_fold8 (kernels_dc_tile.hip).  Workgroups for nb tiles: four workgroups of four waves per CU, a tile per wave and round
+inline uint32_t dc_fold_grid(uint32_t nb, uint32_t cus)
+{
+    const uint32_t wgs = cus * 4u;
+    return wgs > (nb + 3) / 4 ? (nb + 3) / 4 : wgs;
+}
+
 // ---- M = 64 (kernels_fused_small.hip)
 enum Kernel64 { K_RUN64 = 0, K_RUN64V2 };
 struct Choice64 {

@@ -112,8 +112,7 @@ struct TailArgs {
     float ref;
     uint32_t tm;            // 1: Z is tile-major (what the fused run kernels write for k_agc_spec_tm)
 };
-constexpr uint32_t TM_CK = 256;         // samples between the checkpoints of a segment
-constexpr uint32_t TM_GUARD = 512;      // blocks of 16 samples: >= max(W, L) / 16 of the tile-major route (W, L <= 8192)
+// (TM_CK, the samples between the checkpoints of a segment, and TM_GUARD, the blocks in front of and behind a tile-major plane: agc_tail_shape.h)
 
 // index of sample (c, t) in the channelizer plane
 __device__ __forceinline__ size_t z_index(const TailArgs &A, uint32_t c, uint32_t t)
@@ -888,170 +887,72 @@ __global__ __launch_bounds__(256) void k_agc_fix(TailArgs A, AgcState *st_out, f
 
 }  // namespace
 
-struct AgcTailPlan {
-    uint32_t C = 0, max_nf = 0, L = 0, Lmin = 384, W = 1024, max_seg = 0;   // L > 0: fixed by CSDR_AGC_L
-    uint32_t L_tm = 0;               // tile-major route: fixed segment length (CSDR_AGC_L_TM), 0 = chosen per call
-    uint32_t tm_calls = 0;           // calls that took k_agc_spec_tm since create
-    AgcSeg *d_start = nullptr, *d_end = nullptr, *d_ckpt = nullptr;
-    size_t ckpt_cap = 0;
-    AgcState *d_st_tmp = nullptr;    // [C] settled state of the pilot (first call of a stream)
-    bool fresh = true;               // the AGC state is still inside its create-time transient: the next call runs the pilot
-    uint32_t pilot_n = 4096;
-    uint64_t seen = 0;               // samples per channel since create / reset
-    unsigned *d_stats = nullptr;
-    uint32_t wg_slots = 1024;            // workgroups the device holds at once
-};
-
-int agc_tail_create(uint32_t C, uint32_t max_nf, AgcTailPlan **out)
+int AgcTailPlan::init(DeviceBuffers &mem, uint32_t C_, uint32_t max_nf, uint32_t cus)
 {
-    AgcTailPlan *p = new AgcTailPlan();
-    p->C = C; p->max_nf = max_nf;
+    C = C_;
     if (TM_ABLATE) fprintf(stderr, "csdr: kernels_agc_tail.hip built with TM_ABLATE=%d: timing only, results are wrong\n", TM_ABLATE);
-    if (const char *e = diag_env("CSDR_AGC_L")) { p->L = (uint32_t)atol(e); p->L = (p->L + 15u) / 16u * 16u; if (p->L < 16) p->L = 16; }
-    if (const char *e = diag_env("CSDR_AGC_L_TM")) { p->L_tm = ((uint32_t)atol(e) + 15u) / 16u * 16u; if (p->L_tm < 16) p->L_tm = 16; if (p->L_tm > 8176u) p->L_tm = 8176u; }
-    if (const char *e = diag_env("CSDR_AGC_W")) p->W = (uint32_t)atol(e);
-    p->W = (p->W + 15u) / 16u * 16u;
-    {
-        int dev = 0, cus = 256;
-        (void)hipGetDevice(&dev);
-        (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-        if (const char *e = diag_env("CSDR_CUS")) { if (atoi(e) > 0 && atoi(e) < cus) cus = atoi(e); }      // experiments: a plan sized for a CU-masked stream
-        // k_agc_spec: two waves per workgroup at <= 256 VGPRs -> two waves per SIMD -> four workgroups per CU
-        p->wg_slots = (uint32_t)cus * 4u;
-        if (const char *e = diag_env("CSDR_AGC_WGS")) p->wg_slots = (uint32_t)cus * (uint32_t)(atol(e) > 0 ? atol(e) : 1);
-    }
-    p->max_seg = (max_nf + 15u) / 16u + 1;                      // L >= 16
-    const size_t n = (size_t)C * p->max_seg;
-    p->ckpt_cap = (size_t)C * ((size_t)max_nf / 128u + 64u);    // >= nseg x ceil(L / TM_CK) for every L >= 128 of the tile-major route
-    if (hipMalloc(&p->d_start, n * sizeof(AgcSeg)) != hipSuccess || hipMalloc(&p->d_end, n * sizeof(AgcSeg)) != hipSuccess ||
-        hipMalloc(&p->d_ckpt, p->ckpt_cap * sizeof(AgcSeg)) != hipSuccess ||
-        hipMalloc(&p->d_st_tmp, (size_t)C * sizeof(AgcState)) != hipSuccess || hipMalloc(&p->d_stats, 2 * sizeof(unsigned)) != hipSuccess) {
+    knobs = AgcTailKnobs::parse(cus, diag_env("CSDR_AGC_L"), diag_env("CSDR_AGC_L_TM"), diag_env("CSDR_AGC_W"), diag_env("CSDR_AGC_WGS"),
+                                diag_env("CSDR_CUS"), diag_env("CSDR_AGC_TM"));
+    sizes = agc_tail_sizes(C, max_nf);
+    const size_t n = (size_t)C * sizes.max_seg;
+    if (mem.alloc(&d_start, n * sizeof(AgcSeg)) || mem.alloc(&d_end, n * sizeof(AgcSeg)) || mem.alloc(&d_ckpt, sizes.ckpt_cap * sizeof(AgcSeg)) ||
+        mem.alloc_n(&d_st_tmp, C) || mem.alloc_n(&d_stats, 2)) {
         set_error("agc tail: device allocation failed");
-        agc_tail_destroy(p);
         return CSDR_ERR_HIP;
     }
-    CSDR_HIP(hipMemset(p->d_stats, 0, 2 * sizeof(unsigned)));
-    *out = p;
+    CSDR_HIP(hipMemset(d_stats, 0, 2 * sizeof(unsigned)));
     return 0;
 }
 
-void agc_tail_destroy(AgcTailPlan *p)
-{
-    if (!p) return;
-    void *ptrs[] = {p->d_start, p->d_end, p->d_ckpt, p->d_st_tmp, p->d_stats};
-    for (void *q : ptrs) if (q) (void)hipFree(q);
-    delete p;
-}
-
-void agc_tail_reset(AgcTailPlan *p) { if (p) { p->fresh = true; p->seen = 0; } }
-uint32_t agc_tail_tm_calls(const AgcTailPlan *p) { return p ? p->tm_calls : 0u; }
-
-int agc_tail_stats(AgcTailPlan *p, unsigned *checked, unsigned *redone)
+int AgcTailPlan::stats(unsigned *checked, unsigned *redone) const
 {
     unsigned h[2] = {0, 0};
-    CSDR_HIP(hipMemcpy(h, p->d_stats, sizeof(h), hipMemcpyDeviceToHost));
+    CSDR_HIP(hipMemcpy(h, d_stats, sizeof(h), hipMemcpyDeviceToHost));
     if (checked) *checked = h[0];
     if (redone) *redone = h[1];
     return 0;
 }
 
 // Z[C][nf] -> out[C][nf] (CF32, or F32 when fm); st and rp are updated in place.
-// the tile-major route (k_agc_spec_tm): whole 16-frame blocks, at least two segments, channel count a multiple or a divisor of 64
-bool agc_tail_tm_supported(const AgcTailPlan *p, uint32_t nf)
+int AgcTailPlan::run(const float2 *Z, void *out, bool fm, uint32_t nf, AgcState *st, const AgcParams &prm, float fm_ref, const float2 *rp_in,
+                     float2 *rp_out, hipStream_t s, bool tm)
 {
-    static const bool off = diag_env("CSDR_AGC_TM") && atoi(diag_env("CSDR_AGC_TM")) == 0;      // A/B: the row-major route for every call
-    if (off || !p || !nf || nf % 16u || p->W > 8192u || p->W % 16u) return false;
-    if (!(p->C % 64u == 0 || (p->C < 64u && 64u % p->C == 0))) return false;
-    if (nf < 4u * p->W) return false;                            // short calls: a handful of segments, the row-major kernel's ground
-    if (((uint64_t)nf / 16u + 2ull * TM_GUARD) * p->C * 128ull >= (1ull << 32)) return false;     // 32-bit byte offsets inside the plane
-    return true;
-}
-size_t agc_tail_tm_guard(uint32_t C) { return (size_t)TM_GUARD * 16u * C; }      // float2 elements in front of and behind a tile-major plane
-
-int agc_tail_process(AgcTailPlan *p, const float2 *Z, void *out, bool fm, uint32_t nf, AgcState *st, const AgcParams &prm,
-                     float fm_ref, const float2 *rp_in, float2 *rp_out, hipStream_t s, bool tm)
-{
-    if (!nf || !p->C) return 0;
-    if ((uint64_t)p->C * nf >= (1ull << 32)) { set_error("agc tail: C*nf = %llu samples exceeds 2^32", (unsigned long long)p->C * nf); return CSDR_ERR_SIZE; }
-    // Segment length: as many 64-segment groups per channel as the device holds workgroups at once (one round, every
-    // SIMD busy), not more -- shorter segments re-read more warm-up ((W + L) / L times the data) and a second round of
-    // workgroups costs more than it brings.  L / 16 is made odd: with a power-of-two L the 64 streams of a group and
-    // the groups of all channels hit the same few HBM channels at every step (L = 1024: 0.37 ms, 1040: 0.34 ms).
-    if (tm && !agc_tail_tm_supported(p, nf)) { set_error("agc tail: internal: tile-major plane for a call the tile-major kernel does not take"); return CSDR_ERR_INVALID; }
-    const uint32_t Cw = p->C < 64u ? p->C : 64u, nsub = 64u / Cw, ncg = p->C / Cw;     // tile-major: channels per workgroup, segments per workgroup, channel groups
-    uint32_t L = tm ? p->L_tm : p->L;
-    // tile-major route: the two-thirds rule below gives L >= 384 on its own once the plane passes ~128 MiB; below that the device is
-    // under-filled and the re-reads come out of the L2s / the MALL, so shorter segments pay (round 5, profiles/r05_call_size_sweeps.txt:
-    // 256 channels x 16 384 frames 153 -> 137 us, 1024 x 4096 151 -> 136 us with 128 against 384; nothing below 128)
-    const uint32_t lmin_tm = 128u;
-    if (!L && tm) {
-        // two thirds of the workgroups the device holds at once (ncg channel groups x nseg / nsub segment groups): measured optimum
-        // between the warm-up re-reads ((W + L) / L times the plane, shorter segments) and the blocks a workgroup walks (longer ones);
-        // profiles/r04_agc_tm_segment_sweep.txt
-        uint64_t nseg_t = (uint64_t)p->wg_slots * nsub * 2u / (3u * ncg);
-        if (nseg_t < 2) nseg_t = 2;
-        L = (uint32_t)((nf + nseg_t - 1) / nseg_t);
-        L = (L + 31u) / 32u * 32u;                               // F32 rows leave as whole 128-byte lines per block pair
-        if (L < lmin_tm) L = lmin_tm;
-        if (L > 8160u) L = 8160u;
-    }
-    if (tm && L < lmin_tm) L = lmin_tm;                          // (CSDR_AGC_L_TM below the plan's bounds: the checkpoint table is sized for L >= Lmin)
-    if (tm && (L % 32u)) L = (L + 31u) / 32u * 32u;
-    if (!L) {
-        // as many segments per row as the device has lanes for (the kernel packs the segments of several channels into a workgroup when
-        // a row has few)
-        const uint64_t nseg_t = 64ull * p->wg_slots / p->C ? 64ull * p->wg_slots / p->C : 1ull;
-        L = (uint32_t)((nf + nseg_t - 1) / nseg_t);
-        L = (L + 15u) / 16u * 16u;
-        // Lmin bounds the warm-up re-reads ((W + L) / L times the plane) of a bandwidth-bound call.  A call whose whole plane sits in the
-        // L2s (the reference's own 4096-frame chunk: 8 MiB at 256 channels) is bound by the walk instead -- (W + L) samples of a ~200-cycle
-        // recurrence per lane -- and 11 segments of 400 left 53 of a workgroup's 64 lanes idle: such calls take every segment the device
-        // has a lane for (round 5: 161 -> ~120 us per reference chunk)
-        const uint32_t lmin = ((uint64_t)p->C * nf * sizeof(float2) <= (24ull << 20)) ? 16u : p->Lmin;
-        if (L < lmin) L = lmin;
-        if (((L / 16u) & 1u) == 0) L += 16u;
-    }
-    const uint32_t nseg = (nf + L - 1) / L;
-    if (nseg > p->max_seg) { set_error("agc tail: internal segment bound"); return CSDR_ERR_INVALID; }
+    if (!nf || !C) return 0;
+    if ((uint64_t)C * nf >= (1ull << 32)) { set_error("agc tail: C*nf = %llu samples exceeds 2^32", (unsigned long long)C * nf); return CSDR_ERR_SIZE; }
+    if (tm && !tm_supported(nf)) { set_error("agc tail: internal: tile-major plane for a call the tile-major kernel does not take"); return CSDR_ERR_INVALID; }
+    const AgcTailShape h = agc_tail_shape(knobs, C, nf, tm);
+    if (h.nseg > sizes.max_seg) { set_error("agc tail: internal segment bound"); return CSDR_ERR_INVALID; }
+    if (tm && (size_t)C * h.nseg * h.nck > sizes.ckpt_cap) { set_error("agc tail: internal checkpoint bound"); return CSDR_ERR_INVALID; }
     TailArgs A{};
-    A.Z = Z; A.out = out; A.st_in = st; A.rp_in = rp_in; A.seg_start = p->d_start; A.seg_end = p->d_end;
-    A.C = p->C; A.nf = nf; A.L = L; A.W = p->W; A.nseg = nseg; A.p = prm; A.ref = fm_ref;
+    A.Z = Z; A.out = out; A.st_in = st; A.rp_in = rp_in; A.seg_start = (AgcSeg *)d_start; A.seg_end = (AgcSeg *)d_end;
+    A.C = C; A.nf = nf; A.L = h.L; A.W = knobs.W; A.nseg = h.nseg; A.p = prm; A.ref = fm_ref;
     A.st_spec = st; A.tm = tm ? 1u : 0u;
-    A.ckpt = p->d_ckpt; A.nck = (L + TM_CK - 1u) / TM_CK;
-    if (tm && (size_t)p->C * nseg * A.nck > p->ckpt_cap) { set_error("agc tail: internal checkpoint bound"); return CSDR_ERR_INVALID; }
-    if (p->fresh && nseg > 1) {
-        const uint32_t n = nf < p->pilot_n ? nf : p->pilot_n;
-        hipLaunchKernelGGL(k_agc_pilot, dim3((p->C + 63u) / 64u), dim3(64), 0, s, A, n, p->d_st_tmp);
-        A.st_spec = p->d_st_tmp;
+    A.ckpt = (AgcSeg *)d_ckpt; A.nck = h.nck;
+    if (fresh && h.nseg > 1) {
+        const uint32_t n = nf < pilot_n ? nf : pilot_n;
+        hipLaunchKernelGGL(k_agc_pilot, dim3((C + 63u) / 64u), dim3(64), 0, s, A, n, d_st_tmp);
+        A.st_spec = d_st_tmp;
     }
     // the create-time transient is over once the stream has seen pilot_n samples, however many calls that took (round 5: a stream of
     // 1024- or 2048-frame calls used to pilot for ever -- one serial lane per channel over the whole call, 180 / 267 us per call)
-    p->seen += nf;
-    if (p->seen >= p->pilot_n) p->fresh = false;
-    // PAIRS: nf even, so every row starts on a 16-byte boundary and ends on one (t is always even): a piece is one
-    // 16-byte load that never reaches past the buffer
-    const bool pairs = (nf & 1u) == 0 && (uint64_t)p->C * nf >= 2;
-    // row-major kernel: spw segments x cpw channels per workgroup (cpw > 1 needs whole-piece rows and 32-bit offsets inside its rows)
-    uint32_t ls = 6;
-    if (nseg <= 32u && pairs && (nf & 3u) == 0 && p->C >= 8u && (uint64_t)nf * 64ull < (1ull << 32)) { ls = 3; while ((1u << ls) < nseg) ls++; }
-    const uint32_t spw = 1u << ls, cpw = 64u >> ls;
-    const uint32_t groups = (nseg + spw - 1u) / spw;
-    const dim3 grid(((p->C + cpw - 1u) / cpw) * groups), block(128);
+    seen += nf;
+    if (seen >= pilot_n) fresh = false;
+    const dim3 grid(h.grid), block(128);
     if (tm) {
-        p->tm_calls++;
-        const dim3 gtm(ncg * ((nseg + nsub - 1) / nsub)), btm(128);
-        if (fm) hipLaunchKernelGGL((k_agc_spec_tm<true>), gtm, btm, 0, s, A, ncg, Cw, nsub);
-        else hipLaunchKernelGGL((k_agc_spec_tm<false>), gtm, btm, 0, s, A, ncg, Cw, nsub);
-    } else if (pairs) {
-        if (fm) hipLaunchKernelGGL((k_agc_spec<true, true>), grid, block, 0, s, A, groups, ls);
-        else hipLaunchKernelGGL((k_agc_spec<false, true>), grid, block, 0, s, A, groups, ls);
+        tm_calls++;
+        const dim3 gtm(h.grid_tm), btm(128);
+        if (fm) hipLaunchKernelGGL((k_agc_spec_tm<true>), gtm, btm, 0, s, A, h.ncg, h.Cw, h.nsub);
+        else hipLaunchKernelGGL((k_agc_spec_tm<false>), gtm, btm, 0, s, A, h.ncg, h.Cw, h.nsub);
+    } else if (h.pairs) {
+        if (fm) hipLaunchKernelGGL((k_agc_spec<true, true>), grid, block, 0, s, A, h.groups, h.ls);
+        else hipLaunchKernelGGL((k_agc_spec<false, true>), grid, block, 0, s, A, h.groups, h.ls);
     } else {
-        if (fm) hipLaunchKernelGGL((k_agc_spec<true, false>), grid, block, 0, s, A, groups, ls);
-        else hipLaunchKernelGGL((k_agc_spec<false, false>), grid, block, 0, s, A, groups, ls);
+        if (fm) hipLaunchKernelGGL((k_agc_spec<true, false>), grid, block, 0, s, A, h.groups, h.ls);
+        else hipLaunchKernelGGL((k_agc_spec<false, false>), grid, block, 0, s, A, h.groups, h.ls);
     }
     // the fix-up reads st_in through the segment records only, so st can be overwritten in place
-    if (fm) hipLaunchKernelGGL(k_agc_fix<true>, dim3(p->C), dim3(256), 0, s, A, st, rp_out, p->d_stats);
-    else hipLaunchKernelGGL(k_agc_fix<false>, dim3(p->C), dim3(256), 0, s, A, st, rp_out, p->d_stats);
+    if (fm) hipLaunchKernelGGL(k_agc_fix<true>, dim3(C), dim3(256), 0, s, A, st, rp_out, d_stats);
+    else hipLaunchKernelGGL(k_agc_fix<false>, dim3(C), dim3(256), 0, s, A, st, rp_out, d_stats);
     CSDR_HIP(hipGetLastError());
     return 0;
 }

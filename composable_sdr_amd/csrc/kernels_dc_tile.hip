@@ -467,113 +467,71 @@ int launch_branch0_fir(const float2 *u0, const float *taps, float2 *out, float2 
     return 0;
 }
 
-struct DcTilePlan {
-    uint32_t max_nb = 0, epoch = 0;
-    unsigned *d_ticket = nullptr, *d_status = nullptr;
-    u64 *d_agg = nullptr;
-    float2 *d_part = nullptr;            // k_dc_fold: one aggregate and the first sample per tile
-    float2 *d_part8 = nullptr;           // k_dc_fold8 (shard mix identity; allocated on first use): 8 aggregates + 8 first samples per tile
-    uint32_t cus = 256;
-    float2 *d_vend[2] = {nullptr, nullptr};
-    int cur = 0;
-    DcTileArgs proto;
-};
+bool dctile_supported(const DcParams &dc) { return dc_window_ok(dc, LOOKBACK * 4096.0); }
 
-int dctile_status(DcTilePlan *p, unsigned *status)
+int DcTilePlan::init(DeviceBuffers &mem, uint64_t max_samples, uint32_t cus_, bool shard8)
 {
-    CSDR_HIP(hipMemcpy(status, p->d_status, sizeof(unsigned), hipMemcpyDeviceToHost));
-    if (*status) CSDR_HIP(hipMemset(p->d_status, 0, sizeof(unsigned)));
+    max_nb = (uint32_t)((max_samples + 4095) / 4096); cus = cus_;
+    int r;
+    if ((r = mem.alloc_n(&d_ticket, 1)) || (r = mem.alloc_n(&d_status, 1)) || (r = mem.alloc_n(&d_agg, 2 * (size_t)max_nb)) ||
+        (r = mem.alloc_n(&d_part, 2 * (size_t)max_nb)) ||                 // [nb] tile aggregates | [nb] first samples of the tiles
+        (shard8 && (r = mem.alloc_n(&d_part8, 16 * (size_t)max_nb))) ||
+        (r = mem.alloc_n(&d_vend[0], 1)) || (r = mem.alloc_n(&d_vend[1], 1))) return r;
+    CSDR_HIP(hipMemset(d_status, 0, sizeof(unsigned)));
+    CSDR_HIP(hipMemset(d_agg, 0, sizeof(u64) * 2 * max_nb));
+    CSDR_HIP(hipMemset(d_vend[0], 0, sizeof(float2)));
+    CSDR_HIP(hipMemset(d_vend[1], 0, sizeof(float2)));
     return 0;
 }
 
-void dctile_destroy(DcTilePlan *p)
+int DcTilePlan::status(unsigned *status)
 {
-    if (!p) return;
-    void *ptrs[] = {p->d_ticket, p->d_status, p->d_agg, p->d_part, p->d_part8, p->d_vend[0], p->d_vend[1]};
-    for (void *q : ptrs) if (q) (void)hipFree(q);
-    delete p;
-}
-
-int dctile_create(const DcParams &dc, uint64_t max_samples, DcTilePlan **out)
-{
-    // k_dc_tile looks back LOOKBACK tiles; k_dc_fold / k_dc_fold8 fold with beta^-512 ratios: *out stays null when the handle's alpha
-    // does not fit them (dc_window_ok), and the caller keeps the exact block scan
-    *out = nullptr;
-    if (!dc_window_ok(dc, LOOKBACK * 4096.0)) return 0;
-    DcTilePlan *p = new DcTilePlan();
-    p->max_nb = (uint32_t)((max_samples + 4095) / 4096);
-    auto fail = [&](int r) { dctile_destroy(p); return r; };
-#define ALLOC(ptr, bytes) do { hipError_t e = hipMalloc((void **)&(ptr), (bytes) ? (bytes) : 1); if (e != hipSuccess) return fail(hip_fail(e, "hipMalloc", __FILE__, __LINE__)); } while (0)
-    ALLOC(p->d_ticket, sizeof(unsigned)); ALLOC(p->d_status, sizeof(unsigned));
-    ALLOC(p->d_agg, sizeof(u64) * 2 * p->max_nb);
-    ALLOC(p->d_part, sizeof(float2) * 2 * (size_t)p->max_nb);      // [nb] tile aggregates | [nb] first samples of the tiles
-    { int dev = 0, cus = 256; (void)hipGetDevice(&dev); (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev); p->cus = (uint32_t)cus; }
-    ALLOC(p->d_vend[0], sizeof(float2)); ALLOC(p->d_vend[1], sizeof(float2));
-#undef ALLOC
-    CSDR_HIP(hipMemset(p->d_status, 0, sizeof(unsigned)));
-    CSDR_HIP(hipMemset(p->d_agg, 0, sizeof(u64) * 2 * p->max_nb));
-    CSDR_HIP(hipMemset(p->d_vend[0], 0, sizeof(float2)));
-    CSDR_HIP(hipMemset(p->d_vend[1], 0, sizeof(float2)));
-    DcTileArgs &D = p->proto;
-    D = DcTileArgs{};
-    DcConsts(true, dc).put(D);
-    D.ticket = p->d_ticket; D.agg = p->d_agg; D.status = p->d_status;
-    *out = p;
+    CSDR_HIP(hipMemcpy(status, d_status, sizeof(unsigned), hipMemcpyDeviceToHost));
+    if (*status) CSDR_HIP(hipMemset(d_status, 0, sizeof(unsigned)));
     return 0;
 }
 
-int dctile_reset(DcTilePlan *p, hipStream_t s)
+int DcTilePlan::reset(hipStream_t s)
 {
-    p->cur = 0;
-    CSDR_HIP(hipMemsetAsync(p->d_vend[0], 0, sizeof(float2), s));
-    CSDR_HIP(hipMemsetAsync(p->d_vend[1], 0, sizeof(float2), s));
+    cur = 0;
+    CSDR_HIP(hipMemsetAsync(d_vend[0], 0, sizeof(float2), s));
+    CSDR_HIP(hipMemsetAsync(d_vend[1], 0, sizeof(float2), s));
     return 0;
 }
 
-// DeNo --mix over all M channels, M a multiple of 4096, n a multiple of M: out[n / M] = M x (branch-0 FIR of the DC-blocked,
-// pre-mixed stream); hist_in / hist_out: the p - 1 picked samples before / after the call (different buffers)
-bool dctile_mix_identity_supported(const DcTilePlan *p, uint32_t M, uint32_t n, uint32_t taps_p)
+// the arguments every call of the plan starts from: n samples of x, pre-mixed
+static DcTileArgs dctile_args(const DcTilePlan &p, const float2 *x, uint32_t n, const NcoParams &nco, const float2 *nco_tab, bool do_mix)
 {
-    return M && M % 4096u == 0 && n && n % M == 0 && p->proto.beta > 0.f && taps_p >= 1 && taps_p <= 33;
+    DcTileArgs D{};
+    p.dcc.put(D);
+    D.ticket = p.d_ticket; D.agg = p.d_agg; D.status = p.d_status;
+    D.x = x; D.n = n; D.nb = (n + 4095) / 4096;
+    D.vend_in = p.d_vend[p.cur]; D.vend_out = p.d_vend[p.cur ^ 1];
+    D.nco = nco; D.nco_tab = nco_tab; D.do_mix = do_mix ? 1 : 0;
+    return D;
 }
 
-int dctile_mix_identity(DcTilePlan *p, const float2 *x, uint32_t n, const NcoParams &nco, const float2 *nco_tab, const float *taps,
-                        uint32_t M, uint32_t taps_p, const float2 *hist_in, float2 *hist_out, float2 *out, hipStream_t s)
+int DcTilePlan::mix_identity(const float2 *x, uint32_t n, const NcoParams &nco, const float2 *nco_tab, const float *taps, uint32_t M, uint32_t taps_p,
+                             const float2 *hist_in, float2 *hist_out, float2 *out, hipStream_t s)
 {
-    DcTileArgs D = p->proto;
-    D.x = x; D.y = nullptr; D.n = n; D.nb = n / 4096u;
-    D.pick = M; D.ypick = nullptr;
-    D.vend_in = p->d_vend[p->cur]; D.vend_out = p->d_vend[p->cur ^ 1];
-    D.nco = nco; D.nco_tab = nco_tab; D.do_mix = 1;
+    DcTileArgs D = dctile_args(*this, x, n, nco, nco_tab, true);      // (n is a multiple of 4096: whole tiles)
+    D.pick = M;
     const float l2b = (float)std::log2((double)D.beta);
-    uint32_t wgs = p->cus * 4u;                                      // four workgroups of four waves per CU, a tile per wave and round
-    if (wgs > (D.nb + 3) / 4) wgs = (D.nb + 3) / 4;
-    float2 *d_first = p->d_part + (size_t)p->max_nb;
+    float2 *d_first = d_part + (size_t)max_nb;
     const uint32_t nf = n / M;
-    hipLaunchKernelGGL(k_dc_fold, dim3(wgs), dim3(256), 0, s, reinterpret_cast<const float4 *>(x), p->d_part, d_first, D.nb, l2b);
-    hipLaunchKernelGGL(k_mixid_finish, dim3((nf + 255) / 256), dim3(256), 0, s, D, (const float2 *)p->d_part, (const float2 *)d_first, taps,
+    hipLaunchKernelGGL(k_dc_fold, dim3(dc_fold_grid(D.nb, cus)), dim3(256), 0, s, reinterpret_cast<const float4 *>(x), d_part, d_first, D.nb, l2b);
+    hipLaunchKernelGGL(k_mixid_finish, dim3((nf + 255) / 256), dim3(256), 0, s, D, (const float2 *)d_part, (const float2 *)d_first, taps,
                        hist_in, hist_out, out, M, taps_p, nf);
     CSDR_HIP(hipGetLastError());
-    p->cur ^= 1;
+    cur ^= 1;
     return 0;
 }
 
-// the same for the interleaved channel shard g of G: out[n / M] = (M / G) sum_{n2 < G} W_G^(n2 g) x (FIR of branch (M / G) n2); G <= 8,
-// (M / G) % 512 == 0; hist_in / hist_out: [G][p - 1] picked samples before / after the call (different buffers)
-bool dctile_mix_identity_shard_supported(const DcTilePlan *p, uint32_t M, uint32_t n, uint32_t taps_p, uint32_t G)
+int DcTilePlan::mix_identity_shard(const float2 *x, uint32_t n, const NcoParams &nco, const float2 *nco_tab, const float *taps, uint32_t M,
+                                   uint32_t taps_p, uint32_t G, uint32_t g, const float2 *hist_in, float2 *hist_out, float2 *out, hipStream_t s)
 {
-    return dctile_mix_identity_supported(p, M, n, taps_p) && (G == 2 || G == 4 || G == 8) && M % G == 0 && (M / G) % 512u == 0;
-}
-
-int dctile_mix_identity_shard(DcTilePlan *p, const float2 *x, uint32_t n, const NcoParams &nco, const float2 *nco_tab, const float *taps,
-                              uint32_t M, uint32_t taps_p, uint32_t G, uint32_t g, const float2 *hist_in, float2 *hist_out, float2 *out, hipStream_t s)
-{
-    if (!p->d_part8) CSDR_HIP(hipMalloc((void **)&p->d_part8, sizeof(float2) * 16 * (size_t)p->max_nb));
-    DcTileArgs D = p->proto;
-    D.x = x; D.y = nullptr; D.n = n; D.nb = n / 4096u;
-    D.pick = M; D.ypick = nullptr;
-    D.vend_in = p->d_vend[p->cur]; D.vend_out = p->d_vend[p->cur ^ 1];
-    D.nco = nco; D.nco_tab = nco_tab; D.do_mix = 1;
+    DcTileArgs D = dctile_args(*this, x, n, nco, nco_tab, true);      // (n is a multiple of 4096: whole tiles)
+    D.pick = M;
     ShardMixArgs S{};
     S.G = G; S.Mg = M / G;
     for (uint32_t n2 = 0; n2 < G; n2++) {
@@ -581,33 +539,28 @@ int dctile_mix_identity_shard(DcTilePlan *p, const float2 *x, uint32_t n, const 
         S.ph[n2] = make_float2((float)std::cos(a), (float)std::sin(a));
     }
     const float l2b = (float)std::log2((double)D.beta);
-    uint32_t wgs = p->cus * 4u;                                      // four workgroups of four waves per CU, a tile per wave and round
-    if (wgs > (D.nb + 3) / 4) wgs = (D.nb + 3) / 4;
-    float2 *d_agg8 = p->d_part8, *d_first8 = p->d_part8 + (size_t)8 * p->max_nb;
+    float2 *d_agg8 = d_part8, *d_first8 = d_part8 + (size_t)8 * max_nb;
     const uint32_t nf = n / M;
-    hipLaunchKernelGGL(k_dc_fold8, dim3(wgs), dim3(256), 0, s, reinterpret_cast<const float4 *>(x), p->d_part, d_agg8, d_first8, D.nb, l2b);
+    hipLaunchKernelGGL(k_dc_fold8, dim3(dc_fold_grid(D.nb, cus)), dim3(256), 0, s, reinterpret_cast<const float4 *>(x), d_part, d_agg8, d_first8, D.nb, l2b);
     const uint32_t FW = 256u / G;                                    // frames per workgroup of the finish
-    hipLaunchKernelGGL(k_mixid_shard_finish, dim3((nf + FW - 1) / FW), dim3(256), 0, s, D, S, (const float2 *)p->d_part, (const float2 *)d_agg8,
+    hipLaunchKernelGGL(k_mixid_shard_finish, dim3((nf + FW - 1) / FW), dim3(256), 0, s, D, S, (const float2 *)d_part, (const float2 *)d_agg8,
                        (const float2 *)d_first8, taps, hist_in, hist_out, out, M, taps_p, nf);
     CSDR_HIP(hipGetLastError());
-    p->cur ^= 1;
+    cur ^= 1;
     return 0;
 }
 
-int dctile_process(DcTilePlan *p, const float2 *x, float2 *y, uint32_t n, bool do_mix, const NcoParams &nco,
-                   const float2 *nco_tab, hipStream_t s, uint32_t pick)
+int DcTilePlan::process(const float2 *x, float2 *y, uint32_t n, bool do_mix, const NcoParams &nco, const float2 *nco_tab, hipStream_t s, uint32_t pick)
 {
     if (!n) return 0;
-    DcTileArgs D = p->proto;
-    D.x = x; D.y = y; D.n = n; D.nb = (n + 4095) / 4096;
-    D.pick = pick; D.ypick = y;                          // pick > 0: y receives n / pick samples (calls start on a multiple of pick)
-    D.vend_in = p->d_vend[p->cur]; D.vend_out = p->d_vend[p->cur ^ 1];
-    if (++p->epoch == 0) p->epoch = 1;
-    D.epoch = p->epoch; D.nco = nco; D.nco_tab = nco_tab; D.do_mix = do_mix ? 1 : 0;
-    CSDR_HIP(hipMemsetAsync(p->d_ticket, 0, sizeof(unsigned), s));
+    DcTileArgs D = dctile_args(*this, x, n, nco, nco_tab, do_mix);
+    D.y = y; D.pick = pick; D.ypick = y;                 // pick > 0: y receives n / pick samples (calls start on a multiple of pick)
+    if (++epoch == 0) epoch = 1;
+    D.epoch = epoch;
+    CSDR_HIP(hipMemsetAsync(d_ticket, 0, sizeof(unsigned), s));
     hipLaunchKernelGGL(k_dc_tile, dim3(D.nb), dim3(256), 0, s, D);
     CSDR_HIP(hipGetLastError());
-    p->cur ^= 1;
+    cur ^= 1;
     return 0;
 }
 

@@ -5,6 +5,7 @@
 #include "fused.h"
 
 #include <cmath>
+#include <optional>
 
 namespace csdr {
 namespace {
@@ -16,7 +17,7 @@ struct GenericPlan : ChainPlan {
     float *d_taps = nullptr;
     float2 *d_tw = nullptr, *d_nco_tab = nullptr, *d_dcstate = nullptr, *d_scratch = nullptr;
     float2 *d_tw_g = nullptr, *d_fold_ph = nullptr, *d_fold = nullptr;   // interleaved shard (pruned DFT): (M/G)-point twiddles, fold phasors, folded frames
-    DcTilePlan *dctile = nullptr;    // DC blocker with an alpha the single-pass scan kernel takes; null: launch_dc_mix (+dc-scan)
+    std::optional<DcTilePlan> dctile;    // DC blocker with an alpha the single-pass scan kernel takes; none: launch_dc_mix (+dc-scan)
     bool use1024 = false;            // M = 1024: FIR + DFT + transpose [+ freqdem] in k_pfb1024
     bool mix_identity = false;       // DeNo --mix over all channels: M * (branch-0 FIR) instead of bank + DFT + sum
     bool mix_identity_shard = false; // the same for an interleaved shard g of G: (M / G) * sum of the G surviving branches' FIRs
@@ -25,14 +26,13 @@ struct GenericPlan : ChainPlan {
     float2 *d_A = nullptr, *d_B = nullptr;           // FIR plane X[nf][M] (M = 1 with freqdem: Z); DFT plane Y (k_pfb1024: yfirst | ylast)
     float2 *d_rp[2] = {nullptr, nullptr};            // cfg.fm: freqdem history r' per channel, ping-pong
 
-    ~GenericPlan() override { if (dctile) dctile_destroy(dctile); }
     int init();
     // one kernel sequence per handle, no choice by call size; the name is what init() and run() noted in `kernel`
     KernelChoice choose(uint32_t) const override { return {}; }
     const char *kernel_name(int) const override { return kernel.c_str(); }
     std::string route(const char *, bool) const override;
     bool tile_major_ok(uint32_t) const override { return false; }
-    int status(unsigned *st) override { *st = 0; return dctile ? dctile_status(dctile, st) : 0; }
+    int status(unsigned *st) override { *st = 0; return dctile ? dctile->status(st) : 0; }
     int reset_state(hipStream_t s) override;
     int run(const FusedCall &call, KernelChoice, void *out, hipStream_t s, KernelTimer *timer) override;
     int run_mix_identity(const FusedCall &call, const NcoParams &nco, hipStream_t s, KernelTimer *timer);
@@ -77,17 +77,18 @@ int GenericPlan::init()
     const size_t hist = (size_t)(p - 1) * M;
     if ((r = mem.alloc_n(&d_u, hist + max_nx)) || (r = mem.alloc_n(&d_hist_tmp, hist))) return r;
     if ((r = mem.alloc_n(&d_A, max_nx)) || (r = mem.alloc_n(&d_B, use1024 && max_nx < 2048 ? 2048 : max_nx))) return r;   // k_pfb1024 keeps yfirst|ylast (2 x nruns x 1024) in d_B
-    if (cfg.dc_block && (r = dctile_create(cfg.dc, max_nx, &dctile))) return r;
-    const bool deno_mix = cfg.mix && !cfg.fm && dctile && !cfg.no_mix_identity;     // (cfg.mix, cfg.fm: without the AGC)
+    const bool tile = cfg.dc_block && dctile_supported(cfg.dc);
+    const bool deno_mix = cfg.mix && !cfg.fm && tile && !cfg.no_mix_identity;       // (cfg.mix, cfg.fm: without the AGC)
     mix_identity = deno_mix && G == 1 && C == M;
     if (mix_identity) {
         if ((r = mem.alloc_n(&d_u0, (size_t)(p - 1) + cfg.max_nf)) || (r = mem.alloc_n(&d_u0hist, 2 * (p - 1)))) return r;
         kernel = (M % 4096u == 0) ? "k_dc_fold" : "k_dc_tile";   // refined per call
     }
     // interleaved shard, DeNo --mix, no AGC: only the G branches (M / G) n2 survive the shard's channel sum (kernels_dc_tile.hip, k_dc_fold8)
-    // (the conditions of dctile_mix_identity_shard_supported that do not depend on the call: every call of whole frames then takes it)
+    // (the conditions of DcTilePlan::mix_identity_shard_supported that do not depend on the call: every call of whole frames then takes it)
     mix_identity_shard = deno_mix && (G == 2 || G == 4 || G == 8) && (uint64_t)C * G == M && M % 4096u == 0 && (M / G) % 512u == 0 &&
                          p <= 33u && cfg.dc.beta > 0.f;
+    if (tile && (r = dctile.emplace(cfg.dc).init(mem, max_nx, cus, mix_identity_shard))) return r;
     if (mix_identity_shard && (r = mem.alloc_n(&d_u0hist, 2 * (size_t)(p - 1) * G))) return r;
     if (G > 1) {
         const uint32_t Mg = M / G, c0 = cfg.c0;
@@ -109,7 +110,7 @@ int GenericPlan::reset_state(hipStream_t s)
     if (d_u) CSDR_HIP(hipMemsetAsync(d_u, 0, sizeof(float2) * (size_t)(cfg.p - 1) * cfg.M, s));
     if (d_u0hist) CSDR_HIP(hipMemsetAsync(d_u0hist, 0, sizeof(float2) * 2 * (cfg.p - 1) * (mix_identity_shard ? cfg.G : 1u), s));
     for (float2 *rp : d_rp) if (rp) CSDR_HIP(hipMemsetAsync(rp, 0, sizeof(float2) * cfg.C, s));
-    return dctile ? dctile_reset(dctile, s) : 0;
+    return dctile ? dctile->reset(s) : 0;
 }
 
 // DeNo --mix without computing the bank: the channel sum of a frame from the surviving polyphase branches (histories: ping-pong by cur)
@@ -122,27 +123,27 @@ int GenericPlan::run_mix_identity(const FusedCall &call, const NcoParams &nco, h
         // the shard's channel sum = (M / G) x sum of the G surviving branches' FIRs.  The create-time predicate holds every condition
         // that does not depend on the call, and calls are whole frames: a call it refuses is a bug, not a reason to switch routes (the
         // pruned-DFT route keeps no branch histories of its own)
-        if (!dctile_mix_identity_shard_supported(dctile, M, nx, p, cfg.G)) { set_error("chain: shard mix identity refused a call of %u samples", nx); return CSDR_ERR_INVALID; }
+        if (!dctile->mix_identity_shard_supported(M, nx, p, cfg.G)) { set_error("chain: shard mix identity refused a call of %u samples", nx); return CSDR_ERR_INVALID; }
         const size_t hs = (size_t)(p - 1) * cfg.G;
         kernel = "k_dc_fold8";
         if (timer && (r = timer->begin(s))) return r;
-        if ((r = dctile_mix_identity_shard(dctile, call.d_in, nx, nco, d_nco_tab, d_taps, M, p, cfg.G, cfg.c0, d_u0hist + (size_t)cur * hs, d_u0hist + (size_t)(cur ^ 1) * hs, out, s))) return r;
+        if ((r = dctile->mix_identity_shard(call.d_in, nx, nco, d_nco_tab, d_taps, M, p, cfg.G, cfg.c0, d_u0hist + (size_t)cur * hs, d_u0hist + (size_t)(cur ^ 1) * hs, out, s))) return r;
         return timer ? timer->end(s) : 0;
     }
     // sum over ALL channels of a frame = M * X_t[0]: DC blocker + pre-mix on the whole stream, every M-th sample kept,
     // then the 2m-tap FIR of polyphase branch 0 (no bank, no DFT, no channel sum; 8 B read per input sample)
     float2 *hin = d_u0hist + (size_t)cur * (p - 1), *hout = d_u0hist + (size_t)(cur ^ 1) * (p - 1);
-    if (dctile_mix_identity_supported(dctile, M, nx, p)) {
+    if (dctile->mix_identity_supported(M, nx, p)) {
         // k_dc_fold (one aggregate per tile: a plain streaming read) + k_mixid_finish (DC state, pick, pre-mix, FIR)
         kernel = "k_dc_fold";
         if (timer && (r = timer->begin(s))) return r;
-        if ((r = dctile_mix_identity(dctile, call.d_in, nx, nco, d_nco_tab, d_taps, M, p, hin, hout, out, s))) return r;
+        if ((r = dctile->mix_identity(call.d_in, nx, nco, d_nco_tab, d_taps, M, p, hin, hout, out, s))) return r;
         return timer ? timer->end(s) : 0;
     }
     kernel = "k_dc_tile";
     CSDR_HIP(hipMemcpyAsync(d_u0, hin, sizeof(float2) * (p - 1), hipMemcpyDeviceToDevice, s));
     if (timer && (r = timer->begin(s))) return r;
-    if ((r = dctile_process(dctile, call.d_in, d_u0 + (p - 1), nx, true, nco, d_nco_tab, s, M))) return r;
+    if ((r = dctile->process(call.d_in, d_u0 + (p - 1), nx, true, nco, d_nco_tab, s, M))) return r;
     if (timer && (r = timer->end(s))) return r;
     return launch_branch0_fir(d_u0, d_taps, out, hout, M, p, nf, s);
 }
@@ -166,7 +167,7 @@ int GenericPlan::run(const FusedCall &call, KernelChoice, void *out, hipStream_t
     if (mix_identity || mix_identity_shard) return run_mix_identity(call, nco, s, timer);
     const size_t hist = (size_t)(cfg.p - 1) * M;
     float2 *u_new = d_u + hist;
-    if (dctile) r = dctile_process(dctile, call.d_in, u_new, nx, true, nco, d_nco_tab, s);
+    if (dctile) r = dctile->process(call.d_in, u_new, nx, true, nco, d_nco_tab, s);
     else r = launch_dc_mix(call.d_in, u_new, nx, cfg.dc_block, cfg.dc, d_dcstate, d_scratch, true, nco, d_nco_tab, s);
     if (r) return r;
     // M = 1024: FIR + DFT + transpose [+ freqdem] in one kernel (no X / Y round trips through HBM); the frame-major

@@ -1609,6 +1609,36 @@ def test_agc_tail_tile_major_route_at_64_channels_is_bit_identical_to_sequential
     a.close(); b.close()
 
 
+def test_agc_tile_major_knob_is_the_handles_own(monkeypatch):
+    """CSDR_AGC_TM=0 is read when a handle is created, with the tail's other knobs: a handle made while it is set keeps the row-major
+    route, a handle made after it is removed takes k_agc_spec_tm, whichever of them asked first -- and both routes give the same bits.
+    64 channels, DeNo, one call of TM_MIN = 2048 frames, the shortest the tile-major route takes under TM_KNOBS.  max_frames is 4096,
+    not the call's 2048: a handle has the guards a tile-major plane needs only from max_frames = 4096 on (AgcTail::setup), so a
+    2048-frame handle takes the row-major route whatever the knob says."""
+    import torch
+    from chain_tail_cases import TM_KNOBS, TM_MIN
+    from composable_sdr_amd import _lib
+    M, nf = 64, TM_MIN
+    for k, v in TM_KNOBS.items():
+        knob(monkeypatch, k, v)
+    dev = torch.device("cuda", 0)
+    xd = _bursty_torch(M, nf, 980, dev)
+    kw = dict(channels=M, demod="none", agc=8.0, max_frames=4096, flags=_lib.FLAG_QUIET)
+    knob(monkeypatch, "CSDR_AGC_TM", "0")
+    a = cs.Chain(**kw)
+    monkeypatch.delenv("CSDR_AGC_TM")
+    b = cs.Chain(**kw)
+    oa = torch.zeros(M * nf * 2, dtype=torch.float32, device=dev); ob = torch.zeros_like(oa)
+    a.process_device(xd.data_ptr(), M * nf, oa.data_ptr(), 0)
+    b.process_device(xd.data_ptr(), M * nf, ob.data_ptr(), 0)
+    torch.cuda.synchronize()
+    print(f"CSDR_AGC_TM=0 at create: {a.agc_tile_major_calls()} tile-major calls [{a.path}]; removed: {b.agc_tile_major_calls()} [{b.path}]")
+    assert a.agc_tile_major_calls() == 0 and b.agc_tile_major_calls() == 1
+    assert torch.equal(oa.view(torch.int32), ob.view(torch.int32)) and bool((oa != 0).any())
+    a.status(); b.status()
+    a.close(); b.close()
+
+
 def test_agc_tail_tile_major_route_at_4096_channels_is_bit_identical_to_sequential(monkeypatch):
     """The same at M = 4096 (round 6): k_back4096<CF32> stores its 16-frame blocks' lines back to back for k_agc_spec_tm (64 channel groups
     of 64); FM output against the one-lane-per-channel kernels behind the row-major plane, BIT FOR BIT, over a tile-major, a second
