@@ -13,5 +13,6 @@ from .pipes import (  # noqa: F401
     FskDem, fskDemodulator, FirFilt, firFilterCKaiser, firFilterC, firFilterR, firdes_kaiser, fir_groupdelay,
     IirSos, iirCFilter, iirFilterN, iirFilterSOS, iirdes_butter_lowpass,
     GmskDem, gmskDemodulator, firdes_gmsktx, firdes_gmskrx, firFilterRNyquist,
+    Firpfbch2, firpfbch2Channelizer, firdes_pfbch2,
 )
 from .trans import compact, takeNArr, mix, mux, distribute_, addPipe  # noqa: F401

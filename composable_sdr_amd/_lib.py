@@ -135,6 +135,15 @@ SIGNATURES = {
     "csdr_iirsos_get_nsec": (_u32, [_vp]),
     "csdr_iirsos_get_sos": (_i32, [_vp, _vp, _vp]),
     "csdr_iirsos_destroy": (_i32, [_vp]),
+    "csdr_pfbch2_design": (_i32, [_u32, _u32, _f32, _f32, _vp]),
+    "csdr_pfbch2_launch_shape": (_i32, [_u32, _u32, _u32, _u32, _pu32]),
+    "csdr_pfbch2_open_kaiser": (_i32, [_u32, _u32, _f32, _f32, _u32, _pp]),
+    "csdr_pfbch2_open_taps": (_i32, [_vp, _u32, _u32, _u32, _pp]),
+    "csdr_pfbch2_process": (_i32, [_vp, _vp, _u32, _vp, _pu32]),
+    "csdr_pfbch2_process_device": (_i32, [_vp, _vp, _u32, _vp, _vp]),
+    "csdr_pfbch2_rewind": (_i32, [_vp]),
+    "csdr_pfbch2_get_taps": (_i32, [_vp, _vp]),
+    "csdr_pfbch2_destroy": (_i32, [_vp]),
     "csdr_chain_cfg_default": (None, [C.POINTER(ChainCfg), _u32]),
     "csdr_chain_create": (_i32, [C.POINTER(ChainCfg), _pp]),
     "csdr_chain_process": (_i32, [_vp, _vp, _u32, _vp, _pu32]),

@@ -1112,4 +1112,113 @@ int csdr_iirsos_get_sos(const csdr_iirsos *h, float *b, float *a)
     return CSDR_OK;
 }
 
+// ---------------------------------------------------------------------------
+// firpfbch2Channelizer: liquid's firpfbch2_crcf analyzer, which the reference does not import.  The constructors
+// are `open` and the reset is `rewind`; the design and launch-shape functions need no GPU
+// ---------------------------------------------------------------------------
+static bool pfbch2_design_args_ok(uint32_t M, uint32_t m, float as_db, float fc)
+{
+    return pfb2_args_ok(M, m) && std::isfinite(as_db) && as_db > 0.f && std::isfinite(fc) && fc >= 0.f && fc < 0.5f;
+}
+static int pfbch2_bad_design()
+{
+    set_error("pfbch2: bad arguments (M a power of two in [%u, %u], m in [1, %u], As > 0, fc = 0 or in (0, 0.5), finite)", PFB2_MIN_M,
+              PFB2_MAX_M, PFB2_MAX_SEMI);
+    return CSDR_ERR_INVALID;
+}
+int csdr_pfbch2_design(uint32_t M, uint32_t m, float as_db, float fc, float *h)
+{
+    if (!h || !pfbch2_design_args_ok(M, m, as_db, fc)) return pfbch2_bad_design();
+    const std::vector<float> t = design_pfb2_taps(M, m, as_db, fc);
+    std::memcpy(h, t.data(), sizeof(float) * 2 * M * m);
+    return CSDR_OK;
+}
+int csdr_pfbch2_launch_shape(uint32_t M, uint32_t m, uint32_t frames, uint32_t cus, uint32_t *shape)
+{
+    if (!shape || !pfb2_args_ok(M, m) || !cus) { set_error("pfbch2_launch_shape: bad arguments (M, m as for the block, cus >= 1, shape)"); return CSDR_ERR_INVALID; }
+    const Pfb2Shape s = pfb2_shape(M, m, frames, cus);
+    const uint32_t v[6] = {s.F, s.tiles, s.tiles_per_run, s.runs, s.wgs_per_cu, (uint32_t)s.lds};
+    std::memcpy(shape, v, sizeof(v));
+    return CSDR_OK;
+}
+}  // extern "C"
+struct csdr_pfbch2 {
+    int device; DeviceBuffers mem; uint32_t M, m, max_n, max_frames, cus, parity = 0; std::vector<float> taps;    // max_n: samples per call
+    float *d_h = nullptr; float2 *d_tw = nullptr, *d_x = nullptr, *d_y = nullptr; PingPong<float2> hist;           // hist: [2 m M - M / 2]
+};
+extern "C" {
+int csdr_pfbch2_destroy(csdr_pfbch2 *h) { return block_destroy(h); }
+int csdr_pfbch2_open_taps(const float *taps, uint32_t M, uint32_t m, uint32_t max_frames, csdr_pfbch2 **out)
+{
+    bool ok = out && taps && pfb2_args_ok(M, m) && max_frames && (uint64_t)max_frames * M <= (1ull << 31);
+    for (uint32_t i = 0; ok && i < 2 * M * m; i++) ok = std::isfinite(taps[i]);
+    if (!ok) {
+        set_error("pfbch2: bad arguments (finite taps, M a power of two in [%u, %u], m in [1, %u], 1 <= max_frames <= 2^31 / M)", PFB2_MIN_M,
+                  PFB2_MAX_M, PFB2_MAX_SEMI);
+        return CSDR_ERR_INVALID;
+    }
+    NewBlock<csdr_pfbch2> h;
+    int r = h.open(); if (r) return r;
+    int cus = 256;
+    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device);
+    h->M = M; h->m = m; h->max_frames = max_frames; h->max_n = max_frames * (M / 2); h->cus = (uint32_t)cus;
+    h->taps.assign(taps, taps + 2 * M * m);
+    const std::vector<float2> tw = pfb2_twiddles(M);
+    if ((r = block_upload(h->mem, &h->d_h, taps, h->taps.size())) || (r = block_upload(h->mem, &h->d_tw, tw.data(), tw.size())) ||
+        (r = h->hist.alloc(h->mem, h->taps.size() - M / 2)) || (r = h->hist.reset(nullptr)) ||
+        (r = h->mem.alloc_n(&h->d_x, (size_t)h->max_n)) || (r = h->mem.alloc_n(&h->d_y, (size_t)max_frames * M))) return r;
+    CSDR_HIP(hipStreamSynchronize(nullptr));
+    return h.publish(out);
+}
+int csdr_pfbch2_open_kaiser(uint32_t M, uint32_t m, float as_db, float fc, uint32_t max_frames, csdr_pfbch2 **out)
+{
+    if (!pfbch2_design_args_ok(M, m, as_db, fc)) return pfbch2_bad_design();
+    const std::vector<float> t = design_pfb2_taps(M, m, as_db, fc);
+    return csdr_pfbch2_open_taps(t.data(), M, m, max_frames, out);
+}
+// n has to be a whole number of frames of M / 2 samples, at most max_frames of them; nothing is touched otherwise
+static int pfbch2_check_n(const csdr_pfbch2 *h, uint32_t n)
+{
+    if (n % (h->M / 2)) { set_error("pfbch2: %u samples are not a multiple of M / 2 = %u", n, h->M / 2); return CSDR_ERR_SIZE; }
+    return block_check_n("pfbch2", n, h->max_n);
+}
+int csdr_pfbch2_process_device(csdr_pfbch2 *h, const void *d_x, uint32_t n, void *d_y, void *stream)
+{
+    if (!h) return block_null_arg("pfbch2");
+    if (int r = pfbch2_check_n(h, n)) return r;
+    if (!n) return CSDR_OK;
+    if (!d_x || !d_y || d_x == d_y) { set_error("pfbch2: null or aliased buffer"); return CSDR_ERR_INVALID; }
+    const uint32_t frames = n / (h->M / 2);
+    const int r = launch_pfb2((const float2 *)d_x, (float2 *)d_y, h->d_h, h->d_tw, h->hist.in(), h->hist.out(), h->M, h->m, frames, h->parity,
+                              h->cus, (hipStream_t)stream);
+    if (!r) { h->hist.flip(); h->parity = (h->parity + frames) & 1u; }
+    return r;
+}
+int csdr_pfbch2_process(csdr_pfbch2 *h, const float *x, uint32_t n, float *y, uint32_t *frames)
+{
+    if (!frames) return block_null_arg("pfbch2");
+    if (int r = block_check_call("pfbch2", h, x, n, y)) return r;
+    if (int r = pfbch2_check_n(h, n)) return r;
+    *frames = n / (h->M / 2);
+    if (!n) return CSDR_OK;
+    return block_round_trip("pfbch2", h->device, h->d_x, x, sizeof(float2) * n, h->d_y, y, sizeof(float2) * *frames * h->M,
+                            [&] { return csdr_pfbch2_process_device(h, h->d_x, n, h->d_y, nullptr); });
+}
+int csdr_pfbch2_rewind(csdr_pfbch2 *h)
+{
+    if (!h) return CSDR_ERR_INVALID;
+    DevGuard guard(h->device);
+    CSDR_HIP(hipDeviceSynchronize());
+    if (int r = h->hist.reset(nullptr)) return r;
+    CSDR_HIP(hipStreamSynchronize(nullptr));
+    h->parity = 0;
+    return CSDR_OK;
+}
+int csdr_pfbch2_get_taps(const csdr_pfbch2 *h, float *taps)
+{
+    if (!h || !taps) return block_null_arg("pfbch2");
+    std::memcpy(taps, h->taps.data(), sizeof(float) * h->taps.size());
+    return CSDR_OK;
+}
+
 }  // extern "C"

@@ -7,6 +7,7 @@
 #include <string>
 #include <vector>
 #include "agc_tail_shape.h"
+#include "pfb2_shape.h"
 
 namespace csdr {
 
@@ -322,6 +323,17 @@ struct GmskdemLaunch { uint32_t C, n, k, m, L, kinv; };                  // n a 
 // [C][L]: the samples in front of the call and behind it (different arrays)
 int launch_gmskdem(const float2 *x, uint32_t *sym, float *soft, const float *h, const float2 *hist_in, float2 *hist_out,
                    const GmskdemLaunch &l, hipStream_t s);
+
+// ---- 2x-oversampled channelizer (kernels_pfb2.hip; launch shape in pfb2_shape.h; design in design.cpp) ----
+// Kaiser prototype of firpfbch2_crcf_create_kaiser(ANALYZER, M, m, As) as recalled (unpinned): 2 M m + 1 taps of cutoff fc
+// (0: the analyzer's rule, 1 / M), f64, scaled to sum M, rounded once; returns all 2 M m + 1, of which the bank uses the first 2 M m
+std::vector<float> design_pfb2_taps(uint32_t M, uint32_t m, float As, float fc);
+std::vector<float2> pfb2_twiddles(uint32_t M);                           // e^{+2 pi j k / M}, k < M / 4: f64, rounded once
+struct Pfb2Launch { uint32_t frames, par0, tiles, tiles_per_run; };
+// x [frames M / 2] CF32 -> y [M][frames] CF32; h [2 m M] and tw [M / 4] on the device; hist_in / hist_out [2 m M - M / 2]: the samples
+// in front of the call and behind it (different arrays); parity: frames since the start of the stream, mod 2; x and y must not overlap
+int launch_pfb2(const float2 *x, float2 *y, const float *h, const float2 *tw, const float2 *hist_in, float2 *hist_out, uint32_t M,
+                uint32_t m, uint32_t frames, uint32_t parity, uint32_t cus, hipStream_t s);
 
 // ---- time-parallel exact AGC [+ freqdem] tail (kernels_agc_tail.hip) ----
 // The state of one tail (a member of AgcTail, chain_tails.h); which kernel a call takes, with which segments and grids: agc_tail_shape.h

@@ -94,6 +94,20 @@ static std::vector<double> firdes_kaiser(uint32_t N, double fc, double As, doubl
     return h;
 }
 
+// ---- firpfbch2_crcf_create_kaiser(ANALYZER, M, m, As) as recalled (unpinned) ----
+// liquid_firdes_kaiser(2 M m + 1, fc, As, 0) with fc = 1 / M for an analyzer ("twice the synthesizer's bandwidth"), scaled so that
+// the taps sum to M; f64, rounded once
+std::vector<float> design_pfb2_taps(uint32_t M, uint32_t m, float As, float fc)
+{
+    const uint32_t N = 2 * M * m + 1;
+    const std::vector<double> hd = firdes_kaiser(N, fc == 0.f ? 1.0 / (double)M : (double)fc, (double)As);
+    double sum = 0.0;
+    for (double v : hd) sum += v;
+    std::vector<float> h(N);
+    for (uint32_t i = 0; i < N; i++) h[i] = (float)(hd[i] * (double)M / sum);
+    return h;
+}
+
 // ---- multi-stage resampler (msresamp_crcf's structure; "csdr msresamp v1" parameters) ----
 ResampDesign design_msresamp(float rate, float As)
 {

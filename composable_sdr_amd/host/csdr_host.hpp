@@ -676,6 +676,24 @@ inline csdr_comm *commFromIdFile(const std::string &path, int rank, int world, i
     return c;
 }
 
+// ---- the 2x-oversampled firpfbchChannelizer (liquid's firpfbch2_crcf analyzer, which the reference does not import): M rows at
+// 2 / M of the input rate, Kaiser prototype of semi-length m, attenuation as_db and cutoff fc (0: 1 / M); a chunk has to be a
+// whole number of frames of M / 2 samples; an empty chunk yields [empty], as firpfbchChannelizer's ----
+inline Pipe<Array<cf32>, std::vector<Array<cf32>>> Firpfbch2Channelizer(uint32_t M, uint32_t m, float as_db, float fc, uint32_t max_frames)
+{
+    return handlePipe<csdr_pfbch2, Array<cf32>, std::vector<Array<cf32>>>(
+        [=](csdr_pfbch2 **h) { check(csdr_pfbch2_open_kaiser(M, m, as_db, fc, max_frames, h)); }, csdr_pfbch2_destroy,
+        [M](csdr_pfbch2 *h, const Array<cf32> &a) {
+            if (a.empty()) return std::vector<Array<cf32>>{Array<cf32>{}};
+            Array<cf32> flat((size_t)2 * a.size());                          // [M][a.size() / (M / 2)]
+            uint32_t frames = 0;
+            check(csdr_pfbch2_process(h, reinterpret_cast<const float *>(a.data()), (uint32_t)a.size(), reinterpret_cast<float *>(flat.data()), &frames));
+            std::vector<Array<cf32>> outs;
+            for (uint32_t k = 0; k < M; k++) outs.emplace_back(flat.begin() + (size_t)k * frames, flat.begin() + (size_t)(k + 1) * frames);
+            return outs;
+        });
+}
+
 template <class Out> Pipe<Array<cf32>, std::vector<Array<Out>>> fusedChain(const ChainOpts &o)
 {
     return handlePipe<csdr_chain, Array<cf32>, std::vector<Array<Out>>>([o](csdr_chain **h) {

@@ -927,3 +927,69 @@ def firpfbchChannelizer(n, **kw):
         y = r.process(x)
         return [y[k] for k in range(y.shape[0])]
     return Pipe(start, process, lambda r: r.close())
+
+
+def firdes_pfbch2(M, m, as_db=80.0, fc=0.0):
+    """The prototype of the 2x-oversampled channelizer (`csdr_pfbch2_design`): the first 2 M m of the 2 M m + 1 Kaiser taps of
+    cutoff fc (0: the analyzer's rule 1 / M) that sum to M, evaluated in f64 and rounded once.  No GPU needed"""
+    M, m = int(M), int(m)
+    h = np.empty(2 * M * m if 0 < M <= 256 and 0 < m <= 8 else 1, dtype=np.float32)
+    check(lib().csdr_pfbch2_design(M, m, float(as_db), float(fc), _ptr(h)))
+    return h
+
+
+class Firpfbch2(_Owner):
+    """The `csdr_pfbch2_*` object: liquid's firpfbch2_crcf analyzer (which the reference does not import), M channels at twice
+    the critical rate: every M / 2 input samples give one frame, rows are channel-major and centred on 2 pi k / M
+    (include/csdr.h).  `Firpfbch2(taps, M, m)` takes a prototype of 2 M m taps, `Firpfbch2.kaiser` designs it."""
+    _block = "pfbch2"
+
+    def __init__(self, taps, M, m, max_frames=1 << 16, _kaiser=None):
+        self.M, self.m = int(M), int(m)
+        if _kaiser is not None:
+            as_db, fc = _kaiser
+            self._h = _new_handle("pfbch2", self.M, self.m, float(as_db), float(fc), int(max_frames), create="open_kaiser")
+        else:
+            t = np.ascontiguousarray(taps, dtype=np.float32).reshape(-1)
+            if t.size != 2 * self.M * self.m:
+                raise CsdrError(_lib.ERR_INVALID, f"pfbch2: {t.size} taps, not 2 M m = {2 * self.M * self.m}")
+            self._h = _new_handle("pfbch2", _ptr(t), self.M, self.m, int(max_frames), create="open_taps")
+
+    @classmethod
+    def kaiser(cls, M, m=7, as_db=80.0, fc=0.0, max_frames=1 << 16):
+        """the taps of firdes_pfbch2(M, m, as_db, fc)"""
+        return cls(None, M, m, max_frames, _kaiser=(as_db, fc))
+
+    def taps(self):
+        t = np.empty(2 * self.M * self.m, np.float32)
+        check(lib().csdr_pfbch2_get_taps(self.h, _ptr(t)))
+        return t
+
+    def rewind(self):
+        """back to the state right after the object was made (firpfbch2_crcf_reset)"""
+        check(lib().csdr_pfbch2_rewind(self.h))
+
+    def process(self, x):
+        """[n] CF32, n a multiple of M / 2 -> [M][n / (M / 2)] CF32"""
+        x = _c64(x).reshape(-1)
+        y = np.empty((self.M, x.size // (self.M // 2)), dtype=np.complex64)
+        frames = C.c_uint32()
+        check(lib().csdr_pfbch2_process(self.h, _ptr(x), x.size, _ptr(y), C.byref(frames)))
+        assert frames.value == y.shape[1], (frames.value, y.shape)
+        return y
+
+    def process_device(self, d_x_ptr, n, d_y_ptr, stream=0):
+        """Device-resident variant: raw device pointers (ints) for x [n] and y [M][n / (M / 2)]; enqueues on `stream`"""
+        check(lib().csdr_pfbch2_process_device(self.h, C.c_void_p(d_x_ptr), n, C.c_void_p(d_y_ptr), C.c_void_p(stream)))
+
+
+def firpfbch2Channelizer(M, m=7, as_db=80.0, fc=0.0, max_frames=1 << 16):
+    """The 2x-oversampled counterpart of firpfbchChannelizer: Pipe IO (Array CF32) [Array CF32], the list of M per-channel
+    arrays, each at 2 / M of the input rate; an empty input yields [empty], as there"""
+    def process(r, a):
+        x = _c64(a)
+        if x.size == 0:
+            return [np.empty(0, dtype=np.complex64)]
+        y = r.process(x)
+        return [y[k] for k in range(y.shape[0])]
+    return Pipe(lambda: Firpfbch2.kaiser(M, m, as_db, fc, max_frames), process, lambda r: r.close())

@@ -511,6 +511,44 @@ int csdr_iirsos_get_sos(const csdr_iirsos *h, float *b, float *a);   /* [3 nsec]
 int csdr_iirsos_destroy(csdr_iirsos *h);
 
 /* ------------------------------------------------------------------------ *
+ * firpfbch2Channelizer M m as: liquid's 2x-oversampled polyphase channelizer, firpfbch2_crcf, as an analyzer.  The reference
+ * itself does NOT import it (Liquid.chs binds only firpfbch_crcf, :813-866); the block stands for what a Haskell binding of
+ * firpfbch2_crcf_create_kaiser / _create / _execute (analyzer) / _reset / _destroy would call.  Recalled from liquid-dsp
+ * 1.3.2, unpinned.
+ *   M channels, a power of two in [4, 256]; prototype semi-length m in [1, 8]; a real prototype h[0 .. L - 1], L = 2 m M.
+ *   A call takes n samples, a multiple of M / 2, and yields frames = n / (M / 2) output frames, channel-major: y[k][t], M rows
+ *   of `frames` CF32 samples.  With t counting frames from the start of the stream and n_t = (t + 1) M / 2 - 1,
+ *     y_k[t] = (1 / M) sum_{i < L} h[i] x[n_t - i] e^{+j 2 pi k (i + t M / 2) / M},   x[s < 0] = 0:
+ *   row k is a phase-continuous down-conversion by 2 pi k / M rad/sample (no pre-shift), low-passed by h, decimated by M / 2.
+ *   The last L - M / 2 samples and the frame parity are carried from call to call.
+ *   Arithmetic: f32.  v[i] = sum_n h[i + n M] x[n_t - i - n M] by fmaf from +0, oldest sample first; the DFT input is rotated
+ *     by M / 2 on odd frames; an M-point backward radix-2 DFT (a complex product is one product and one fma per component)
+ *     whose operation order depends on M only; the scale 1 / M is exact.  The output is bit-identical for every chunking of
+ *     the stream and for host versus device entry.
+ *   csdr_pfbch2_design (no GPU needed): 2 M m + 1 taps of liquid_firdes_kaiser(., fc, as_db, 0) (csdr_firdes_kaiser's form),
+ *     fc = 0 meaning the recalled rule for an analyzer, fc = 1 / M; f64, scaled so that all 2 M m + 1 sum to M, rounded once;
+ *     the first 2 M m are returned and used, as firpfbch drops the last.
+ *   csdr_pfbch2_launch_shape (no GPU needed): how a call of `frames` frames runs on a device of `cus` compute units:
+ *     shape[6] = frames per tile, tiles, consecutive tiles per workgroup, workgroups, workgroups per CU, LDS bytes per workgroup.
+ *   open_kaiser = the design, then open_taps (firpfbch2_crcf_create_kaiser / _create); rewind is firpfbch2_crcf_reset: the
+ *     state right after open.  (`open` / `rewind`, not `create` / `reset`: the names of this block only.)
+ *   CSDR_ERR_INVALID: M not a power of two in [4, 256], m outside [1, 8], as_db <= 0 or not finite, fc < 0 or >= 0.5 or not
+ *     finite, max_frames = 0 or max_frames M > 2^31, NULL, a non-finite tap, x and y the same buffer.  CSDR_ERR_SIZE: n not a
+ *     multiple of M / 2, or more than max_frames frames; the state is untouched.  No GPU: CSDR_ERR_NODEV.
+ * ------------------------------------------------------------------------ */
+typedef struct csdr_pfbch2 csdr_pfbch2;
+int csdr_pfbch2_design(uint32_t M, uint32_t m, float as_db, float fc, float *h /* [2 M m] */);
+int csdr_pfbch2_launch_shape(uint32_t M, uint32_t m, uint32_t frames, uint32_t cus, uint32_t *shape /* [6] */);
+int csdr_pfbch2_open_kaiser(uint32_t M, uint32_t m, float as_db, float fc, uint32_t max_frames, csdr_pfbch2 **out);
+int csdr_pfbch2_open_taps(const float *h /* [2 M m] */, uint32_t M, uint32_t m, uint32_t max_frames, csdr_pfbch2 **out);
+int csdr_pfbch2_process(csdr_pfbch2 *h, const float *x_cf32, uint32_t n, float *y_cf32 /* [M][2 n / M] */, uint32_t *frames);
+/* device buffers as above; enqueued on `stream`, no synchronisation */
+int csdr_pfbch2_process_device(csdr_pfbch2 *h, const void *d_x, uint32_t n, void *d_y, void *stream);
+int csdr_pfbch2_rewind(csdr_pfbch2 *h);                           /* back to the state right after open               */
+int csdr_pfbch2_get_taps(const csdr_pfbch2 *h, float *taps /* [2 M m] */);
+int csdr_pfbch2_destroy(csdr_pfbch2 *h);
+
+/* ------------------------------------------------------------------------ *
  * The fused chain: everything assembleFold (apps/SoapySDR.hs:208-226) puts
  * behind `compact`:
  *     dcBlocker                                   (SoapySDR.hs:213-214)
