@@ -144,6 +144,16 @@ SIGNATURES = {
     "csdr_pfbch2_rewind": (_i32, [_vp]),
     "csdr_pfbch2_get_taps": (_i32, [_vp, _vp]),
     "csdr_pfbch2_destroy": (_i32, [_vp]),
+    "csdr_pfbsyn2_design": (_i32, [_u32, _u32, _f32, _f32, _vp]),
+    "csdr_pfbsyn2_launch_shape": (_i32, [_u32, _u32, _u32, _u32, _pu32]),
+    "csdr_pfbsyn2_open_kaiser": (_i32, [_u32, _u32, _f32, _f32, _u32, _pp]),
+    "csdr_pfbsyn2_open_taps": (_i32, [_vp, _u32, _u32, _u32, _pp]),
+    "csdr_pfbsyn2_process": (_i32, [_vp, _vp, _u32, _vp, _pu32]),
+    "csdr_pfbsyn2_process_device": (_i32, [_vp, _vp, _u32, _vp, _vp]),
+    "csdr_pfbsyn2_rewind": (_i32, [_vp]),
+    "csdr_pfbsyn2_get_taps": (_i32, [_vp, _vp]),
+    "csdr_pfbsyn2_delay": (_u32, [_vp]),
+    "csdr_pfbsyn2_destroy": (_i32, [_vp]),
     "csdr_chain_cfg_default": (None, [C.POINTER(ChainCfg), _u32]),
     "csdr_chain_create": (_i32, [C.POINTER(ChainCfg), _pp]),
     "csdr_chain_process": (_i32, [_vp, _vp, _u32, _vp, _pu32]),

@@ -1221,4 +1221,112 @@ int csdr_pfbch2_get_taps(const csdr_pfbch2 *h, float *taps)
     return CSDR_OK;
 }
 
+// ---------------------------------------------------------------------------
+// firpfbch2Synthesizer: the synthesizer side of liquid's firpfbch2_crcf, the way back from csdr_pfbch2's rows.
+// Names as csdr_pfbch2's: `open` and `rewind`; the design and launch-shape functions need no GPU
+// ---------------------------------------------------------------------------
+static int pfbsyn2_bad_design()
+{
+    set_error("pfbsyn2: bad arguments (M a power of two in [%u, %u], m in [1, %u], As > 0, fc = 0 or in (0, 0.5), finite)", PFB2_MIN_M,
+              PFB2_MAX_M, PFB2_MAX_SEMI);
+    return CSDR_ERR_INVALID;
+}
+// design_pfb2_taps with the synthesizer's rule for fc = 0: 0.5 / M, half the analyzer's cutoff
+static std::vector<float> pfbsyn2_taps(uint32_t M, uint32_t m, float as_db, float fc)
+{
+    return design_pfb2_taps(M, m, as_db, fc == 0.f ? 0.5f / (float)M : fc);
+}
+int csdr_pfbsyn2_design(uint32_t M, uint32_t m, float as_db, float fc, float *g)
+{
+    if (!g || !pfbch2_design_args_ok(M, m, as_db, fc)) return pfbsyn2_bad_design();
+    const std::vector<float> t = pfbsyn2_taps(M, m, as_db, fc);
+    std::memcpy(g, t.data(), sizeof(float) * 2 * M * m);
+    return CSDR_OK;
+}
+int csdr_pfbsyn2_launch_shape(uint32_t M, uint32_t m, uint32_t frames, uint32_t cus, uint32_t *shape)
+{
+    if (!shape || !pfb2_args_ok(M, m) || !cus) { set_error("pfbsyn2_launch_shape: bad arguments (M, m as for the block, cus >= 1, shape)"); return CSDR_ERR_INVALID; }
+    const Pfb2Shape s = pfb2s_shape(M, m, frames, cus);
+    const uint32_t v[6] = {s.F, s.tiles, s.tiles_per_run, s.runs, s.wgs_per_cu, (uint32_t)s.lds};
+    std::memcpy(shape, v, sizeof(v));
+    return CSDR_OK;
+}
+}  // extern "C"
+struct csdr_pfbsyn2 {
+    int device; DeviceBuffers mem; uint32_t M, m, max_n, cus, parity = 0, seen = 0; std::vector<float> taps;   // max_n: frames per call
+    float *d_g = nullptr; float2 *d_tw = nullptr, *d_y = nullptr, *d_x = nullptr; PingPong<float2> hist;         // hist: [M][4 m - 1]
+};
+extern "C" {
+int csdr_pfbsyn2_destroy(csdr_pfbsyn2 *h) { return block_destroy(h); }
+int csdr_pfbsyn2_open_taps(const float *taps, uint32_t M, uint32_t m, uint32_t max_frames, csdr_pfbsyn2 **out)
+{
+    bool ok = out && taps && pfb2_args_ok(M, m) && max_frames && (uint64_t)max_frames * M <= (1ull << 31);
+    for (uint32_t i = 0; ok && i < 2 * M * m; i++) ok = std::isfinite(taps[i]);
+    if (!ok) {
+        set_error("pfbsyn2: bad arguments (finite taps, M a power of two in [%u, %u], m in [1, %u], 1 <= max_frames <= 2^31 / M)", PFB2_MIN_M,
+                  PFB2_MAX_M, PFB2_MAX_SEMI);
+        return CSDR_ERR_INVALID;
+    }
+    NewBlock<csdr_pfbsyn2> h;
+    int r = h.open(); if (r) return r;
+    int cus = 256;
+    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device);
+    h->M = M; h->m = m; h->max_n = max_frames; h->cus = (uint32_t)cus;
+    h->taps.assign(taps, taps + 2 * M * m);
+    const std::vector<float2> tw = pfb2_twiddles(M);
+    if ((r = block_upload(h->mem, &h->d_g, taps, h->taps.size())) || (r = block_upload(h->mem, &h->d_tw, tw.data(), tw.size())) ||
+        (r = h->hist.alloc(h->mem, (size_t)M * pfb2s_halo_frames(m))) || (r = h->hist.reset(nullptr)) ||
+        (r = h->mem.alloc_n(&h->d_y, (size_t)max_frames * M)) || (r = h->mem.alloc_n(&h->d_x, (size_t)max_frames * (M / 2)))) return r;
+    CSDR_HIP(hipStreamSynchronize(nullptr));
+    return h.publish(out);
+}
+int csdr_pfbsyn2_open_kaiser(uint32_t M, uint32_t m, float as_db, float fc, uint32_t max_frames, csdr_pfbsyn2 **out)
+{
+    if (!pfbch2_design_args_ok(M, m, as_db, fc)) return pfbsyn2_bad_design();
+    const std::vector<float> t = pfbsyn2_taps(M, m, as_db, fc);
+    return csdr_pfbsyn2_open_taps(t.data(), M, m, max_frames, out);
+}
+int csdr_pfbsyn2_process_device(csdr_pfbsyn2 *h, const void *d_y, uint32_t frames, void *d_x, void *stream)
+{
+    if (!h) return block_null_arg("pfbsyn2");
+    if (int r = block_check_n("pfbsyn2", frames, h->max_n)) return r;
+    if (!frames) return CSDR_OK;
+    if (!d_y || !d_x || d_y == d_x) { set_error("pfbsyn2: null or aliased buffer"); return CSDR_ERR_INVALID; }
+    const int r = launch_pfb2s((const float2 *)d_y, (float2 *)d_x, h->d_g, h->d_tw, h->hist.in(), h->hist.out(), h->M, h->m, frames, h->parity,
+                               h->seen, h->cus, (hipStream_t)stream);
+    if (!r) {
+        h->hist.flip();
+        h->parity = (h->parity + frames) & 1u;
+        h->seen = (uint32_t)std::min<uint64_t>((uint64_t)h->seen + frames, pfb2s_halo_frames(h->m));
+    }
+    return r;
+}
+int csdr_pfbsyn2_process(csdr_pfbsyn2 *h, const float *y, uint32_t frames, float *x, uint32_t *n)
+{
+    if (!n) return block_null_arg("pfbsyn2");
+    if (int r = block_check_call("pfbsyn2", h, y, frames, x)) return r;
+    if (frames && (const void *)y == (const void *)x) { set_error("pfbsyn2: aliased buffer"); return CSDR_ERR_INVALID; }
+    *n = frames * (h->M / 2);
+    if (!frames) return CSDR_OK;
+    return block_round_trip("pfbsyn2", h->device, h->d_y, y, sizeof(float2) * frames * h->M, h->d_x, x, sizeof(float2) * *n,
+                            [&] { return csdr_pfbsyn2_process_device(h, h->d_y, frames, h->d_x, nullptr); });
+}
+int csdr_pfbsyn2_rewind(csdr_pfbsyn2 *h)
+{
+    if (!h) return CSDR_ERR_INVALID;
+    DevGuard guard(h->device);
+    CSDR_HIP(hipDeviceSynchronize());
+    if (int r = h->hist.reset(nullptr)) return r;
+    CSDR_HIP(hipStreamSynchronize(nullptr));
+    h->parity = 0; h->seen = 0;
+    return CSDR_OK;
+}
+int csdr_pfbsyn2_get_taps(const csdr_pfbsyn2 *h, float *taps)
+{
+    if (!h || !taps) return block_null_arg("pfbsyn2");
+    std::memcpy(taps, h->taps.data(), sizeof(float) * h->taps.size());
+    return CSDR_OK;
+}
+uint32_t csdr_pfbsyn2_delay(const csdr_pfbsyn2 *h) { return h ? 2 * h->M * h->m - h->M / 2 + 1 : 0; }
+
 }  // extern "C"

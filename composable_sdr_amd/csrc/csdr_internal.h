@@ -335,6 +335,15 @@ struct Pfb2Launch { uint32_t frames, par0, tiles, tiles_per_run; };
 int launch_pfb2(const float2 *x, float2 *y, const float *h, const float2 *tw, const float2 *hist_in, float2 *hist_out, uint32_t M,
                 uint32_t m, uint32_t frames, uint32_t parity, uint32_t cus, hipStream_t s);
 
+// ---- the synthesizer of the 2x-oversampled bank (kernels_pfb2s.hip; launch shape in pfb2_shape.h) ----
+// The prototype is design_pfb2_taps with the synthesizer's cutoff, 0.5 / M; the twiddles are pfb2_twiddles
+struct Pfb2sLaunch { uint32_t frames, par0, seen, tiles, tiles_per_run; };
+// y [M][frames] CF32 -> x [frames M / 2] CF32; g [2 m M] and tw [M / 4] on the device; hist_in / hist_out [M][4 m - 1]: the input frames
+// in front of the call and behind it (different arrays), of which the last `seen` belong to the stream; parity: frames since the
+// start of the stream, mod 2; x and y must not overlap
+int launch_pfb2s(const float2 *y, float2 *x, const float *g, const float2 *tw, const float2 *hist_in, float2 *hist_out, uint32_t M,
+                 uint32_t m, uint32_t frames, uint32_t parity, uint32_t seen, uint32_t cus, hipStream_t s);
+
 // ---- time-parallel exact AGC [+ freqdem] tail (kernels_agc_tail.hip) ----
 // The state of one tail (a member of AgcTail, chain_tails.h); which kernel a call takes, with which segments and grids: agc_tail_shape.h
 struct AgcTailPlan {

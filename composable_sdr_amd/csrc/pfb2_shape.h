@@ -1,6 +1,7 @@
-// The launch shape of k_pfb2 (kernels_pfb2.hip): frames per tile, the LDS of a workgroup, and how a call of
-// `frames` frames is cut into runs of consecutive tiles.  Pure functions of M, m, the frame count and the CU count; nothing here
-// needs the HIP headers, so a host-only program can include it (csdr_pfbch2_launch_shape hands it to tests/test_pfbch2_cpu.py).
+// The launch shape of k_pfb2 (kernels_pfb2.hip) and, at the end, of k_pfb2s (kernels_pfb2s.hip, 4.18): frames per
+// tile, the LDS of a workgroup, and how a call of `frames` frames is cut into runs of consecutive tiles.  Pure functions of M, m,
+// the frame count and the CU count; nothing here needs the HIP headers, so a host-only program can include it
+// (csdr_pfbch2_launch_shape and csdr_pfbsyn2_launch_shape hand it to tests/test_pfbch2_cpu.py and tests/test_pfbsyn2_cpu.py).
 #pragma once
 
 #include <cstddef>
@@ -53,6 +54,34 @@ inline Pfb2Shape pfb2_shape(uint32_t M, uint32_t m, uint32_t frames, uint32_t cu
     Pfb2Shape s{};
     s.F = pfb2_tile_frames(M);
     s.lds = pfb2_lds_bytes(M, m);
+    const size_t fit = PFB2_LDS_LIMIT / s.lds;
+    s.wgs_per_cu = (uint32_t)(fit < PFB2_MAX_WGS_PER_CU ? fit : PFB2_MAX_WGS_PER_CU);
+    s.tiles = (frames + s.F - 1) / s.F;
+    const uint32_t slots = (cus ? cus : 1u) * (s.wgs_per_cu ? s.wgs_per_cu : 1u);
+    s.tiles_per_run = s.tiles ? (s.tiles + slots - 1) / slots : 0;
+    s.runs = s.tiles ? (s.tiles + s.tiles_per_run - 1) / s.tiles_per_run : 0;
+    return s;
+}
+
+// ---- k_pfb2s, the synthesizer (kernels_pfb2s.hip): the same tiles, runs and row stride; only the LDS differs ----
+// float2 slots of the accumulator carry: the L - M/2 partial sums behind a tile.  The tile's own F M/2 sums are final when its FIR
+// ends and leave from registers, so they have no slot
+PFB2_HD constexpr uint32_t pfb2s_carry_slots(uint32_t M, uint32_t m) { return 2 * m * M - M / 2; }
+// frames in front of a run that reach into it (and that the handle carries from call to call): 4 m - 1
+PFB2_HD constexpr uint32_t pfb2s_halo_frames(uint32_t m) { return 4 * m - 1; }
+// bytes of LDS per workgroup: carry | V [F][row stride] | twiddles [M / 4], all float2, | the 2 m M taps, float
+PFB2_HD inline size_t pfb2s_lds_bytes(uint32_t M, uint32_t m)
+{
+    const size_t F = pfb2_tile_frames(M);
+    return 8 * ((size_t)pfb2s_carry_slots(M, m) + F * pfb2_row_stride(M) + M / 4) + 4 * (size_t)(2 * m * M);
+}
+// pfb2_shape's cut of a call into runs of tiles with the synthesizer's LDS.  A run's tiles are counted in output frames; the
+// kernel walks ceil((its frames + 4 m - 1) / F) tiles of input frames, the halo in front included
+inline Pfb2Shape pfb2s_shape(uint32_t M, uint32_t m, uint32_t frames, uint32_t cus)
+{
+    Pfb2Shape s{};
+    s.F = pfb2_tile_frames(M);
+    s.lds = pfb2s_lds_bytes(M, m);
     const size_t fit = PFB2_LDS_LIMIT / s.lds;
     s.wgs_per_cu = (uint32_t)(fit < PFB2_MAX_WGS_PER_CU ? fit : PFB2_MAX_WGS_PER_CU);
     s.tiles = (frames + s.F - 1) / s.F;

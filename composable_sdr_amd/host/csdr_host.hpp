@@ -694,6 +694,30 @@ inline Pipe<Array<cf32>, std::vector<Array<cf32>>> Firpfbch2Channelizer(uint32_t
         });
 }
 
+// ---- the way back from Firpfbch2Channelizer's rows to one stream (the synthesizer side of firpfbch2_crcf): M rows of `frames`
+// values give frames M / 2 samples; behind the channelizer the stream comes back 2 M m - M / 2 + 1 samples late.  Kaiser prototype
+// of cutoff fc (0: 0.5 / M, half the analyzer's); [empty], which the channelizer yields for an empty chunk, gives empty ----
+inline Pipe<std::vector<Array<cf32>>, Array<cf32>> Firpfbch2Synthesizer(uint32_t M, uint32_t m, float as_db, float fc, uint32_t max_frames)
+{
+    return handlePipe<csdr_pfbsyn2, std::vector<Array<cf32>>, Array<cf32>>(
+        [=](csdr_pfbsyn2 **h) { check(csdr_pfbsyn2_open_kaiser(M, m, as_db, fc, max_frames, h)); }, csdr_pfbsyn2_destroy,
+        [M](csdr_pfbsyn2 *h, const std::vector<Array<cf32>> &rows) {
+            const size_t frames = rows.empty() ? 0 : rows[0].size();
+            if (!frames) return Array<cf32>{};
+            if (rows.size() != M) throw std::runtime_error("Firpfbch2Synthesizer: not M rows");
+            Array<cf32> flat;                                                // [M][frames]
+            flat.reserve((size_t)M * frames);
+            for (const auto &r : rows) {
+                if (r.size() != frames) throw std::runtime_error("Firpfbch2Synthesizer: rows of unequal length");
+                flat.insert(flat.end(), r.begin(), r.end());
+            }
+            Array<cf32> x(frames * (M / 2));
+            uint32_t n = 0;
+            check(csdr_pfbsyn2_process(h, reinterpret_cast<const float *>(flat.data()), (uint32_t)frames, reinterpret_cast<float *>(x.data()), &n));
+            return x;
+        });
+}
+
 template <class Out> Pipe<Array<cf32>, std::vector<Array<Out>>> fusedChain(const ChainOpts &o)
 {
     return handlePipe<csdr_chain, Array<cf32>, std::vector<Array<Out>>>([o](csdr_chain **h) {

@@ -993,3 +993,74 @@ def firpfbch2Channelizer(M, m=7, as_db=80.0, fc=0.0, max_frames=1 << 16):
         y = r.process(x)
         return [y[k] for k in range(y.shape[0])]
     return Pipe(lambda: Firpfbch2.kaiser(M, m, as_db, fc, max_frames), process, lambda r: r.close())
+
+
+def firdes_pfbsyn2(M, m, as_db=80.0, fc=0.0):
+    """The prototype of the 2x-oversampled synthesizer (`csdr_pfbsyn2_design`): firdes_pfbch2's Kaiser design with fc = 0 meaning
+    the synthesizer's rule 0.5 / M, half the analyzer's cutoff.  No GPU needed"""
+    M, m = int(M), int(m)
+    g = np.empty(2 * M * m if 0 < M <= 256 and 0 < m <= 8 else 1, dtype=np.float32)
+    check(lib().csdr_pfbsyn2_design(M, m, float(as_db), float(fc), _ptr(g)))
+    return g
+
+
+class Firpfbch2Synth(_Owner):
+    """The `csdr_pfbsyn2_*` object: the synthesizer side of liquid's firpfbch2_crcf, the way back from Firpfbch2's rows to one
+    stream: every frame of M values gives M / 2 samples, and Firpfbch2.kaiser followed by Firpfbch2Synth.kaiser returns its
+    input `delay()` samples late (include/csdr.h).  `Firpfbch2Synth(taps, M, m)` takes a prototype of 2 M m taps,
+    `Firpfbch2Synth.kaiser` designs it."""
+    _block = "pfbsyn2"
+
+    def __init__(self, taps, M, m, max_frames=1 << 16, _kaiser=None):
+        self.M, self.m = int(M), int(m)
+        if _kaiser is not None:
+            as_db, fc = _kaiser
+            self._h = _new_handle("pfbsyn2", self.M, self.m, float(as_db), float(fc), int(max_frames), create="open_kaiser")
+        else:
+            t = np.ascontiguousarray(taps, dtype=np.float32).reshape(-1)
+            if t.size != 2 * self.M * self.m:
+                raise CsdrError(_lib.ERR_INVALID, f"pfbsyn2: {t.size} taps, not 2 M m = {2 * self.M * self.m}")
+            self._h = _new_handle("pfbsyn2", _ptr(t), self.M, self.m, int(max_frames), create="open_taps")
+
+    @classmethod
+    def kaiser(cls, M, m=7, as_db=80.0, fc=0.0, max_frames=1 << 16):
+        """the taps of firdes_pfbsyn2(M, m, as_db, fc)"""
+        return cls(None, M, m, max_frames, _kaiser=(as_db, fc))
+
+    def taps(self):
+        t = np.empty(2 * self.M * self.m, np.float32)
+        check(lib().csdr_pfbsyn2_get_taps(self.h, _ptr(t)))
+        return t
+
+    def delay(self):
+        """samples by which the analyzer followed by this synthesizer delays a stream: 2 M m - M / 2 + 1"""
+        return int(lib().csdr_pfbsyn2_delay(self.h))
+
+    def rewind(self):
+        """back to the state right after the object was made (firpfbch2_crcf_reset)"""
+        check(lib().csdr_pfbsyn2_rewind(self.h))
+
+    def process(self, y):
+        """[M][frames] CF32 -> [frames M / 2] CF32"""
+        y = _c64(y)
+        if y.ndim != 2 or y.shape[0] != self.M:
+            raise CsdrError(_lib.ERR_INVALID, f"pfbsyn2: a chunk of shape {y.shape}, not [{self.M}][frames]")
+        x = np.empty(y.shape[1] * (self.M // 2), dtype=np.complex64)
+        n = C.c_uint32()
+        check(lib().csdr_pfbsyn2_process(self.h, _ptr(y), y.shape[1], _ptr(x), C.byref(n)))
+        assert n.value == x.size, (n.value, x.shape)
+        return x
+
+    def process_device(self, d_y_ptr, frames, d_x_ptr, stream=0):
+        """Device-resident variant: raw device pointers (ints) for y [M][frames] and x [frames M / 2]; enqueues on `stream`"""
+        check(lib().csdr_pfbsyn2_process_device(self.h, C.c_void_p(d_y_ptr), frames, C.c_void_p(d_x_ptr), C.c_void_p(stream)))
+
+
+def firpfbch2Synthesizer(M, m=7, as_db=80.0, fc=0.0, max_frames=1 << 16):
+    """The way back from firpfbch2Channelizer: Pipe IO [Array CF32] (Array CF32), from the M per-channel arrays of a chunk (a list
+    or an [M][frames] array) to frames M / 2 samples; [empty], which the channelizer yields for an empty input, gives empty"""
+    def process(r, rows):
+        if sum(np.asarray(a).size for a in rows) == 0:
+            return np.empty(0, dtype=np.complex64)
+        return r.process(np.stack([_c64(a).reshape(-1) for a in rows]))
+    return Pipe(lambda: Firpfbch2Synth.kaiser(M, m, as_db, fc, max_frames), process, lambda r: r.close())

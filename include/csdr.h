@@ -549,6 +549,44 @@ int csdr_pfbch2_get_taps(const csdr_pfbch2 *h, float *taps /* [2 M m] */);
 int csdr_pfbch2_destroy(csdr_pfbch2 *h);
 
 /* ------------------------------------------------------------------------ *
+ * firpfbch2Synthesizer M m as: the synthesizer side of liquid's firpfbch2_crcf, the way back from csdr_pfbch2's rows to one
+ * stream (channelize, work on or drop rows, re-assemble).  Not imported by the reference either.
+ *   Recalled from liquid-dsp 1.3.2, unpinned by liquid: the structure (an M-point backward DFT per frame, M / 2 outputs per
+ *     frame from alternating halves of the last 4 m transforms) and the design rule, a cutoff of 0.5 / M, half the analyzer's.
+ *   This library's own: the scale.  liquid's is not recalled; the factor 1/2 below makes analysis followed by synthesis unit-gain.
+ *   What pins both halves without liquid: with the analyzer's prototype cut at 1 / M and this one's at 0.5 / M,
+ *     csdr_pfbch2 followed by csdr_pfbsyn2 returns its input delayed by D = 2 M m - M / 2 + 1 samples (liquid's figure): rel-RMS
+ *     4.3e-5 and gain 1.00002 at m = 7, 80 dB in f64; with equal cutoffs on both sides the rel-RMS is above 0.15.  The pair of
+ *     cutoffs is pinned, not which side has which: exchanged, they return the input as well.
+ *   M, m as csdr_pfbch2's; a real prototype g[0 .. L - 1], L = 2 m M; P = M / 2.  A call takes `frames` frames, channel-major as
+ *   csdr_pfbch2 writes them, Y[k][t] with the row stride `frames`, and yields frames P samples.  With t counting frames from
+ *   the start of the stream, w_t[q] = sum_{k < M} Y_k[t] e^{+j 2 pi k q / M} and r < P,
+ *     x[t P + r] = 1/2 sum_{n = 0 .. 4 m - 1, t - n >= 0} g[r + n P] w_{t-n}[(r + t P) mod M]
+ *   ( = 1/2 sum_t g[s - t P] sum_k Y_k[t] e^{+j 2 pi k s / M}).  The last 4 m - 1 input frames, how many of them belong to the
+ *   stream, and the frame parity are carried from call to call.
+ *   Arithmetic: f32.  The DFT is radix-2 (a complex product is one product and one fma per component) in an order that depends on
+ *     M only; the sum over n by fmaf from +0, oldest frame first, frames in front of the stream skipped; the factor 1/2 is exact.
+ *     The output is bit-identical for every chunking of the stream and for host versus device entry.
+ *   csdr_pfbsyn2_design (no GPU needed): csdr_pfbch2_design's Kaiser design with fc = 0 meaning 0.5 / M.
+ *   csdr_pfbsyn2_launch_shape (no GPU needed): as csdr_pfbch2_launch_shape, for this block's kernel.
+ *   open_kaiser / open_taps / rewind as csdr_pfbch2's.  csdr_pfbsyn2_delay: D above (0 for NULL).
+ *   CSDR_ERR_INVALID: as csdr_pfbch2's (bad M, m, as_db, fc, max_frames, NULL, a non-finite tap, y and x the same buffer).
+ *     CSDR_ERR_SIZE: more than max_frames frames; the state is untouched.  No GPU: CSDR_ERR_NODEV.  0 frames: a no-op.
+ * ------------------------------------------------------------------------ */
+typedef struct csdr_pfbsyn2 csdr_pfbsyn2;
+int csdr_pfbsyn2_design(uint32_t M, uint32_t m, float as_db, float fc, float *g /* [2 M m] */);
+int csdr_pfbsyn2_launch_shape(uint32_t M, uint32_t m, uint32_t frames, uint32_t cus, uint32_t *shape /* [6] */);
+int csdr_pfbsyn2_open_kaiser(uint32_t M, uint32_t m, float as_db, float fc, uint32_t max_frames, csdr_pfbsyn2 **out);
+int csdr_pfbsyn2_open_taps(const float *g /* [2 M m] */, uint32_t M, uint32_t m, uint32_t max_frames, csdr_pfbsyn2 **out);
+int csdr_pfbsyn2_process(csdr_pfbsyn2 *h, const float *y_cf32 /* [M][frames] */, uint32_t frames, float *x_cf32 /* [frames M / 2] */, uint32_t *n);
+/* device buffers as above; enqueued on `stream`, no synchronisation */
+int csdr_pfbsyn2_process_device(csdr_pfbsyn2 *h, const void *d_y, uint32_t frames, void *d_x, void *stream);
+int csdr_pfbsyn2_rewind(csdr_pfbsyn2 *h);                         /* back to the state right after open               */
+int csdr_pfbsyn2_get_taps(const csdr_pfbsyn2 *h, float *taps /* [2 M m] */);
+uint32_t csdr_pfbsyn2_delay(const csdr_pfbsyn2 *h);               /* 2 M m - M / 2 + 1 samples through both banks     */
+int csdr_pfbsyn2_destroy(csdr_pfbsyn2 *h);
+
+/* ------------------------------------------------------------------------ *
  * The fused chain: everything assembleFold (apps/SoapySDR.hs:208-226) puts
  * behind `compact`:
  *     dcBlocker                                   (SoapySDR.hs:213-214)
