@@ -15,5 +15,6 @@ from .pipes import (  # noqa: F401
     GmskDem, gmskDemodulator, firdes_gmsktx, firdes_gmskrx, firFilterRNyquist,
     Firpfbch2, firpfbch2Channelizer, firdes_pfbch2,
     Firpfbch2Synth, firpfbch2Synthesizer, firdes_pfbsyn2,
+    RowResamp, rowResampler, firdes_rowresamp,
 )
 from .trans import compact, takeNArr, mix, mux, distribute_, addPipe  # noqa: F401

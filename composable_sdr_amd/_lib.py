@@ -154,6 +154,17 @@ SIGNATURES = {
     "csdr_pfbsyn2_get_taps": (_i32, [_vp, _vp]),
     "csdr_pfbsyn2_delay": (_u32, [_vp]),
     "csdr_pfbsyn2_destroy": (_i32, [_vp]),
+    "csdr_rowresamp_design": (_i32, [C.c_double, _u32, _f32, _f32, _pu32, C.POINTER(C.c_uint64), _vp]),
+    "csdr_rowresamp_launch_shape": (_i32, [C.c_double, _u32, C.c_int32, _u32, _u32, _u32, C.c_uint64, _pu32]),
+    "csdr_rowresamp_open": (_i32, [C.c_double, _u32, _f32, _f32, C.c_int32, _u32, _u32, _pp]),
+    "csdr_rowresamp_max_out": (_u32, [_vp, _u32]),
+    "csdr_rowresamp_count": (_i32, [_vp, _u32, _pu32]),
+    "csdr_rowresamp_process": (_i32, [_vp, _vp, _u32, _vp, _pu32]),
+    "csdr_rowresamp_process_device": (_i32, [_vp, _vp, _u32, _vp, _pu32, _vp]),
+    "csdr_rowresamp_rewind": (_i32, [_vp]),
+    "csdr_rowresamp_get_design": (_i32, [_vp, _pu32, C.POINTER(C.c_uint64), _pu32, _vp]),
+    "csdr_rowresamp_get_time": (_i32, [_vp, C.POINTER(C.c_uint64)]),
+    "csdr_rowresamp_destroy": (_i32, [_vp]),
     "csdr_chain_cfg_default": (None, [C.POINTER(ChainCfg), _u32]),
     "csdr_chain_create": (_i32, [C.POINTER(ChainCfg), _pp]),
     "csdr_chain_process": (_i32, [_vp, _vp, _u32, _vp, _pu32]),

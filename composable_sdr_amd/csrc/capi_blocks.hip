@@ -1329,4 +1329,131 @@ int csdr_pfbsyn2_get_taps(const csdr_pfbsyn2 *h, float *taps)
 }
 uint32_t csdr_pfbsyn2_delay(const csdr_pfbsyn2 *h) { return h ? 2 * h->M * h->m - h->M / 2 + 1 : 0; }
 
+// ---------------------------------------------------------------------------
+// rowResampler: liquid's resamp_crcf / resamp_rrrf on nchan rows, which the reference does not import ("csdr rowresamp v1",
+// DESIGN.md 4.19).  Names as csdr_pfbch2's: `open` and `rewind`; the design and launch-shape functions need no GPU
+// ---------------------------------------------------------------------------
+static int rowresamp_bad_design()
+{
+    set_error("rowresamp: bad arguments (1/8 <= rate <= 8, m in [1, %u] with m D <= %u, 0 < as <= 120, fc = 0 or in (0, 0.5))", RRS_MAX_SEMI,
+              RRS_MAX_SEMI_D);
+    return CSDR_ERR_INVALID;
+}
+int csdr_rowresamp_design(double rate, uint32_t m, float as_db, float fc, uint32_t *taps_per_phase, uint64_t *delta, float *bank)
+{
+    if (!rowresamp_design_args_ok(rate, m, as_db, fc)) return rowresamp_bad_design();
+    const RowResampDesign d = design_rowresamp(rate, m, as_db, fc);
+    if (taps_per_phase) *taps_per_phase = d.P;
+    if (delta) *delta = d.delta;
+    if (bank) std::memcpy(bank, d.bank.data(), sizeof(float) * d.bank.size());
+    return CSDR_OK;
+}
+int csdr_rowresamp_launch_shape(double rate, uint32_t m, int32_t is_complex, uint32_t n_out, uint32_t nchan, uint32_t cus, uint64_t t_next,
+                                uint32_t *shape)
+{
+    if (!shape || !rowresamp_design_args_ok(rate, m, 60.f, 0.f) || !nchan || !cus) {
+        set_error("rowresamp_launch_shape: bad arguments (rate, m as for the block, nchan >= 1, cus >= 1, shape)");
+        return CSDR_ERR_INVALID;
+    }
+    const uint64_t delta = (uint64_t)std::llround(4294967296.0 / rate);
+    const RrsShape s = rrs_shape(delta, m, is_complex != 0, n_out, nchan, cus, t_next);
+    if (!s.ok) { set_error("rowresamp_launch_shape: %u rows of %u outputs are too many tiles", nchan, n_out); return CSDR_ERR_SIZE; }
+    const uint32_t v[8] = {s.P, s.TO, s.window, (uint32_t)s.lds, s.wgs_per_cu, s.tiles, s.items_per_run, s.runs};
+    std::memcpy(shape, v, sizeof(v));
+    return CSDR_OK;
+}
+}  // extern "C"
+struct csdr_rowresamp {
+    int device; DeviceBuffers mem; uint32_t m, nchan, max_n, cus; bool cplx; uint64_t delta, T = 0; RowResampDesign design;
+    float *d_bank = nullptr; float *d_x = nullptr, *d_y = nullptr; PingPong<float> hist;    // d_bank: [P][RRS_BANK_STRIDE]; hist: [nchan][P - 1] samples
+    size_t elem() const { return cplx ? 2 : 1; }                                             // floats per sample
+    uint32_t max_out(uint32_t n) const { return rrs_count(0, delta, n); }
+};
+extern "C" {
+int csdr_rowresamp_destroy(csdr_rowresamp *h) { return block_destroy(h); }
+int csdr_rowresamp_open(double rate, uint32_t m, float as_db, float fc, int32_t is_complex, uint32_t nchan, uint32_t max_samples,
+                        csdr_rowresamp **out)
+{
+    if (!rowresamp_design_args_ok(rate, m, as_db, fc)) return rowresamp_bad_design();
+    if (!out || !nchan || !max_samples || max_samples > (1u << 28)) {
+        set_error("rowresamp: bad arguments (nchan >= 1, 1 <= max_samples <= 2^28, out)");
+        return CSDR_ERR_INVALID;
+    }
+    NewBlock<csdr_rowresamp> h;
+    int r = h.open(); if (r) return r;
+    int cus = 256;
+    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device);
+    h->design = design_rowresamp(rate, m, as_db, fc);
+    h->m = m; h->nchan = nchan; h->max_n = max_samples; h->cus = (uint32_t)cus; h->cplx = is_complex != 0; h->delta = h->design.delta;
+    const uint32_t P = h->design.P;
+    std::vector<float> bank_t((size_t)RRS_BANK_STRIDE * P, 0.f);                             // the kernel's [j][column(b)] image
+    for (uint32_t b = 0; b <= RRS_NPFB; b++)
+        for (uint32_t j = 0; j < P; j++) bank_t[(size_t)j * RRS_BANK_STRIDE + rrs_bank_col(b)] = h->design.bank[(size_t)b * P + j];
+    if ((r = block_upload(h->mem, &h->d_bank, bank_t.data(), bank_t.size())) ||
+        (r = h->hist.alloc(h->mem, (size_t)nchan * (P - 1) * h->elem())) || (r = h->hist.reset(nullptr)) ||
+        (r = h->mem.alloc_n(&h->d_x, (size_t)nchan * max_samples * h->elem())) ||
+        (r = h->mem.alloc_n(&h->d_y, (size_t)nchan * h->max_out(max_samples) * h->elem()))) return r;
+    CSDR_HIP(hipStreamSynchronize(nullptr));
+    return h.publish(out);
+}
+uint32_t csdr_rowresamp_max_out(const csdr_rowresamp *h, uint32_t n) { return h && n <= h->max_n ? h->max_out(n) : 0; }
+int csdr_rowresamp_count(const csdr_rowresamp *h, uint32_t n, uint32_t *n_out)
+{
+    if (!h || !n_out) return block_null_arg("rowresamp");
+    if (int r = block_check_n("rowresamp", n, h->max_n)) return r;
+    *n_out = rrs_count(h->T, h->delta, n);
+    return CSDR_OK;
+}
+int csdr_rowresamp_process_device(csdr_rowresamp *h, const void *d_x, uint32_t n, void *d_y, uint32_t *n_out, void *stream)
+{
+    if (!h || !n_out) return block_null_arg("rowresamp");
+    if (int r = block_check_n("rowresamp", n, h->max_n)) return r;
+    if (!n) { *n_out = 0; return CSDR_OK; }
+    if (!d_x || !d_y || d_x == d_y) { set_error("rowresamp: null or aliased buffer"); return CSDR_ERR_INVALID; }
+    const uint32_t cnt = rrs_count(h->T, h->delta, n);
+    const int r = launch_rowresamp(d_x, d_y, h->d_bank, h->hist.in(), h->hist.out(), h->delta, h->m, h->cplx, h->nchan, n, cnt, h->T, h->cus,
+                                   (hipStream_t)stream);
+    if (r) return r;
+    h->hist.flip();
+    h->T = rrs_next_time(h->T, h->delta, n, cnt);
+    *n_out = cnt;
+    return CSDR_OK;
+}
+int csdr_rowresamp_process(csdr_rowresamp *h, const float *x, uint32_t n, float *y, uint32_t *n_out)
+{
+    if (!n_out) return block_null_arg("rowresamp");
+    if (int r = block_check_call("rowresamp", h, x, n, y)) return r;
+    if (n && (const void *)x == (const void *)y) { set_error("rowresamp: aliased buffer"); return CSDR_ERR_INVALID; }
+    if (!n) { *n_out = 0; return CSDR_OK; }
+    const size_t sample = sizeof(float) * h->elem();
+    const uint32_t cnt = rrs_count(h->T, h->delta, n);
+    return block_round_trip("rowresamp", h->device, h->d_x, x, sample * h->nchan * n, h->d_y, y, sample * h->nchan * cnt,
+                            [&] { return csdr_rowresamp_process_device(h, h->d_x, n, h->d_y, n_out, nullptr); });
+}
+int csdr_rowresamp_rewind(csdr_rowresamp *h)
+{
+    if (!h) return CSDR_ERR_INVALID;
+    DevGuard guard(h->device);
+    CSDR_HIP(hipDeviceSynchronize());
+    if (int r = h->hist.reset(nullptr)) return r;
+    CSDR_HIP(hipStreamSynchronize(nullptr));
+    h->T = 0;
+    return CSDR_OK;
+}
+int csdr_rowresamp_get_design(const csdr_rowresamp *h, uint32_t *taps_per_phase, uint64_t *delta, uint32_t *delay, float *bank)
+{
+    if (!h) return block_null_arg("rowresamp");
+    if (taps_per_phase) *taps_per_phase = h->design.P;
+    if (delta) *delta = h->delta;
+    if (delay) *delay = h->design.P / 2;
+    if (bank) std::memcpy(bank, h->design.bank.data(), sizeof(float) * h->design.bank.size());
+    return CSDR_OK;
+}
+int csdr_rowresamp_get_time(const csdr_rowresamp *h, uint64_t *t_next)
+{
+    if (!h || !t_next) return block_null_arg("rowresamp");
+    *t_next = h->T;
+    return CSDR_OK;
+}
+
 }  // extern "C"

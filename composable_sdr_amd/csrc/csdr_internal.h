@@ -8,6 +8,7 @@
 #include <vector>
 #include "agc_tail_shape.h"
 #include "pfb2_shape.h"
+#include "rowresamp_shape.h"
 
 namespace csdr {
 
@@ -343,6 +344,18 @@ struct Pfb2sLaunch { uint32_t frames, par0, seen, tiles, tiles_per_run; };
 // start of the stream, mod 2; x and y must not overlap
 int launch_pfb2s(const float2 *y, float2 *x, const float *g, const float2 *tw, const float2 *hist_in, float2 *hist_out, uint32_t M,
                  uint32_t m, uint32_t frames, uint32_t parity, uint32_t seen, uint32_t cus, hipStream_t s);
+
+// ---- rowResampler: the arbitrary-rate resampler on nchan rows (kernels_rowresamp.hip; launch shape in rowresamp_shape.h) ----
+// "csdr rowresamp v1": delta = llround(2^32 / rate), P = 2 m D taps per phase, fc = 0 meaning min(0.515 min(r, 1), 0.49), the bank
+// [257][P] = f32(2 fc g[b + 256 j]) of g = firdes_kaiser(256 P + 1, fc / 256, as)
+struct RowResampDesign { uint64_t delta = 0; uint32_t P = 0; float fc = 0.f; std::vector<float> bank; };
+bool rowresamp_design_args_ok(double rate, uint32_t m, float as_db, float fc);
+RowResampDesign design_rowresamp(double rate, uint32_t m, float as_db, float fc);
+struct RowResampLaunch { uint64_t delta, T; uint32_t m, n, n_out, tiles, items, items_per_run; };
+// x [nchan][n] -> y [nchan][n_out], CF32 (cplx) or F32, n_out = rrs_count(T, delta, n); bank_t: the bank as [P][RRS_BANK_STRIDE], phase b in column rrs_bank_col(b), on the device;
+// hist_in / hist_out [nchan][P - 1]: the samples in front of the call and behind it (different arrays); x and y must not overlap
+int launch_rowresamp(const void *x, void *y, const float *bank_t, const void *hist_in, void *hist_out, uint64_t delta, uint32_t m,
+                     bool cplx, uint32_t nchan, uint32_t n, uint32_t n_out, uint64_t T, uint32_t cus, hipStream_t s);
 
 // ---- time-parallel exact AGC [+ freqdem] tail (kernels_agc_tail.hip) ----
 // The state of one tail (a member of AgcTail, chain_tails.h); which kernel a call takes, with which segments and grids: agc_tail_shape.h

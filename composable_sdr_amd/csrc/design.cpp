@@ -138,6 +138,27 @@ ResampDesign design_msresamp(float rate, float As)
     return d;
 }
 
+// ---- rowResampler ("csdr rowresamp v1"): the arbitrary stage above on its own, with m and the stretch D free ----
+bool rowresamp_design_args_ok(double rate, uint32_t m, float as_db, float fc)
+{
+    if (!(rate >= 0.125 && rate <= 8.0) || !(as_db > 0.f && as_db <= 120.f) || !(fc >= 0.f && fc < 0.5f)) return false;
+    return rrs_args_ok((uint64_t)std::llround(4294967296.0 / rate), m);
+}
+RowResampDesign design_rowresamp(double rate, uint32_t m, float as_db, float fc_)
+{
+    RowResampDesign d;
+    d.delta = (uint64_t)std::llround(4294967296.0 / rate);
+    d.P = rrs_P(d.delta, m);
+    double fc = (double)fc_;
+    if (fc_ == 0.f) { fc = 0.515 * (rate < 1.0 ? rate : 1.0); if (fc > 0.49) fc = 0.49; }
+    d.fc = (float)fc;
+    const std::vector<double> g = firdes_kaiser(d.P * RRS_NPFB + 1, fc / (double)RRS_NPFB, (double)as_db);
+    d.bank.resize((size_t)(RRS_NPFB + 1) * d.P);
+    for (uint32_t b = 0; b <= RRS_NPFB; b++)
+        for (uint32_t j = 0; j < d.P; j++) d.bank[(size_t)b * d.P + j] = (float)(2.0 * fc * g[b + (size_t)j * RRS_NPFB]);
+    return d;
+}
+
 // 2nd-order Butterworth low-pass by the bilinear transform with pre-warping (liquid iirdes BUTTER/LOWPASS/SOS, order 2)
 BiquadParams design_butter2_lowpass(float fc)
 {

@@ -718,6 +718,24 @@ inline Pipe<std::vector<Array<cf32>>, Array<cf32>> Firpfbch2Synthesizer(uint32_t
         });
 }
 
+// ---- rowResampler rate m as fc: the arbitrary-rate resampler (liquid's resamp_crcf for T = cf32, resamp_rrrf for T = float; the
+// reference imports neither) on nchan rows that share one rate and one clock: every row of a chunk of n samples gives the same
+// number of outputs, which the handle knows before the call; what turns the channelizers' fs / M into the whole number of
+// samples per symbol the digital blocks take ----
+template <class T> Pipe<Rows<T>, Rows<T>> RowResampler(double rate, uint32_t m, float as_db, float fc, uint32_t nchan, uint32_t max_in)
+{
+    return rowPipe<csdr_rowresamp, T, T>(
+        "RowResampler", nchan,
+        [=](csdr_rowresamp **h) { check(csdr_rowresamp_open(rate, m, as_db, fc, std::is_same<T, cf32>::value, nchan, max_in, h)); },
+        csdr_rowresamp_destroy, [nchan](csdr_rowresamp *h, const Array<T> &x, uint32_t n) {
+            uint32_t n_out = 0;
+            check(csdr_rowresamp_count(h, n, &n_out));
+            Array<T> y((size_t)nchan * n_out + 1);                       // + 1: a call that yields nothing still has a buffer
+            check(csdr_rowresamp_process(h, reinterpret_cast<const float *>(x.data()), n, reinterpret_cast<float *>(y.data()), &n_out));
+            return splitRows(y, nchan, n_out, n_out);
+        });
+}
+
 template <class Out> Pipe<Array<cf32>, std::vector<Array<Out>>> fusedChain(const ChainOpts &o)
 {
     return handlePipe<csdr_chain, Array<cf32>, std::vector<Array<Out>>>([o](csdr_chain **h) {

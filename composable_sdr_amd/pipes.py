@@ -1064,3 +1064,87 @@ def firpfbch2Synthesizer(M, m=7, as_db=80.0, fc=0.0, max_frames=1 << 16):
             return np.empty(0, dtype=np.complex64)
         return r.process(np.stack([_c64(a).reshape(-1) for a in rows]))
     return Pipe(lambda: Firpfbch2Synth.kaiser(M, m, as_db, fc, max_frames), process, lambda r: r.close())
+
+
+def firdes_rowresamp(rate, m=7, as_db=60.0, fc=0.0):
+    """The design of the row resampler (`csdr_rowresamp_design`, "csdr rowresamp v1"): (bank F32 [257][P], delta),
+    delta = llround(2^32 / rate) Q32.32 input samples per output and P = 2 m D taps per phase.  No GPU needed"""
+    P, delta = C.c_uint32(), C.c_uint64()
+    check(lib().csdr_rowresamp_design(float(rate), int(m), float(as_db), float(fc), C.byref(P), C.byref(delta), None))
+    bank = np.empty((257, P.value), dtype=np.float32)
+    check(lib().csdr_rowresamp_design(float(rate), int(m), float(as_db), float(fc), None, None, _ptr(bank)))
+    return bank, int(delta.value)
+
+
+class RowResamp(_Owner):
+    """The `csdr_rowresamp_*` object: liquid's resamp_crcf (`complex`, CF32 rows) or resamp_rrrf (F32 rows) on `nchan` independent
+    rows that share one rate and one clock: [nchan][n] in, [nchan][n_out] out, n_out the same for every row and known before the
+    call (`count`).  The last P - 1 samples of a row and the time of the next output are carried from call to call, and the
+    output does not depend on how the stream is cut into calls (include/csdr.h)."""
+    _block = "rowresamp"
+
+    def __init__(self, rate, m=7, as_db=60.0, fc=0.0, complex=True, nchan=1, max_samples=1 << 16):
+        self._h = _new_handle("rowresamp", float(rate), int(m), float(as_db), float(fc), int(bool(complex)), int(nchan), int(max_samples),
+                              create="open")
+        self.is_complex, self.nchan = bool(complex), int(nchan)
+        self.dtype = np.complex64 if self.is_complex else np.float32
+
+    def design(self):
+        """(bank F32 [257][P], delta)"""
+        P, delta = C.c_uint32(), C.c_uint64()
+        check(lib().csdr_rowresamp_get_design(self.h, C.byref(P), C.byref(delta), None, None))
+        bank = np.empty((257, P.value), dtype=np.float32)
+        check(lib().csdr_rowresamp_get_design(self.h, None, None, None, _ptr(bank)))
+        return bank, int(delta.value)
+
+    def delay(self):
+        """the group delay in input samples: m D"""
+        d = C.c_uint32()
+        check(lib().csdr_rowresamp_get_design(self.h, None, None, C.byref(d), None))
+        return int(d.value)
+
+    def time(self):
+        """T: the Q32.32 time of the next output relative to the first sample of the next call"""
+        t = C.c_uint64()
+        check(lib().csdr_rowresamp_get_time(self.h, C.byref(t)))
+        return int(t.value)
+
+    def count(self, n):
+        """outputs per row that the next call of n samples per row yields"""
+        n_out = C.c_uint32()
+        check(lib().csdr_rowresamp_count(self.h, int(n), C.byref(n_out)))
+        return int(n_out.value)
+
+    def max_out(self, n):
+        """room per row that a call of n samples may need, whatever the time it starts at"""
+        return int(lib().csdr_rowresamp_max_out(self.h, int(n)))
+
+    def rewind(self):
+        """back to the state right after the object was made (resamp_crcf_reset)"""
+        check(lib().csdr_rowresamp_rewind(self.h))
+
+    def process(self, x):
+        """[nchan][n] -> [nchan][n_out]; [n] -> [n_out]"""
+        x = np.ascontiguousarray(x, dtype=self.dtype)
+        if x.size % self.nchan or (x.ndim == 2 and x.shape[0] != self.nchan) or x.ndim > 2:
+            raise CsdrError(_lib.ERR_INVALID, f"rowresamp: a chunk of shape {x.shape}, not [{self.nchan}][n]")
+        n = x.size // self.nchan
+        y = np.empty((self.nchan, self.count(n)), dtype=self.dtype)
+        n_out = C.c_uint32()
+        check(lib().csdr_rowresamp_process(self.h, _ptr(x), n, _ptr(y), C.byref(n_out)))
+        assert n_out.value == y.shape[1], (n_out.value, y.shape)
+        return y[0] if x.ndim == 1 else y
+
+    def process_device(self, d_x_ptr, n, d_y_ptr, stream=0):
+        """Device-resident variant: raw device pointers (ints) for x [nchan][n] and y [nchan][n_out]; enqueues on `stream` and
+        returns n_out without synchronising"""
+        n_out = C.c_uint32()
+        check(lib().csdr_rowresamp_process_device(self.h, C.c_void_p(d_x_ptr), int(n), C.c_void_p(d_y_ptr), C.byref(n_out), C.c_void_p(stream)))
+        return int(n_out.value)
+
+
+def rowResampler(rate, m=7, as_db=60.0, fc=0.0, complex=True, nchan=1, max_samples=1 << 16):
+    """The arbitrary-rate resampler on rows as a Pipe of [nchan][n] arrays (CF32, or F32 with complex=False; [n] for one row):
+    what turns the channelizers' fs / M into the whole number of samples per symbol that fskDemodulator, gmskDemodulator and the
+    symbol synchronisers take, or into an audio rate"""
+    return _method_pipe(lambda: RowResamp(rate, m, as_db, fc, complex, nchan, max_samples))

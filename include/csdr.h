@@ -587,6 +587,50 @@ uint32_t csdr_pfbsyn2_delay(const csdr_pfbsyn2 *h);               /* 2 M m - M /
 int csdr_pfbsyn2_destroy(csdr_pfbsyn2 *h);
 
 /* ------------------------------------------------------------------------ *
+ * rowResampler rate m as fc: liquid's resamp_crcf / resamp_rrrf (an arbitrary-rate polyphase resampler) on nchan rows at once,
+ * all CF32 or all F32, behind csdr_pfbch / csdr_pfbch2 and in front of the blocks that want a whole number of samples per
+ * symbol or a fixed audio rate.  The reference imports neither interface (its `resampler` is msresamp_crcf on one stream:
+ * csdr_resamp_* above, which stays as it is).
+ *   Own spec, "csdr rowresamp v1" (DESIGN.md 4.19), not liquid's bit for bit:
+ *   Timing: delta = llround(2^32 / rate) is Q32.32 input samples per output, so the rate that runs is 2^32 / delta.  Output k of
+ *     the stream sits at t_k = k delta: sample n_k = t_k >> 32, phase b = (t_k >> 24) & 255, mu = (t_k & 0xffffff) / 2^24.  The
+ *     handle carries T, the time of the next output relative to the first sample of the next call (0 at open).  A call of n
+ *     samples per row yields n_out = 0 if (T >> 32) >= n, else floor(((n << 32) - 1 - T) / delta) + 1 outputs per row, the same
+ *     for every row; then T <- T + n_out delta - (n << 32).  Output k belongs to the call that delivers sample n_k.
+ *   Filter: 256 phases, P = 2 m D taps per phase, D = 1 for delta <= 2^32, else ceil(delta / 2^32) ( = ceil(1 / r)); fc = 0 means
+ *     min(0.515 min(r, 1), 0.49); g = liquid_firdes_kaiser(256 P + 1, fc / 256, as); bank[b][j] = f32(2 fc g[b + 256 j]) for
+ *     b = 0 .. 256 (row 256 is row 0 one sample later).  s0 = sum_j bank[b][j] x[n_k - j], s1 the same with row b + 1,
+ *     y_k = fma(mu, s1, (1 - mu) s0), re and im apart; x[s < 0] = 0.  Group delay: m D input samples.
+ *   Arithmetic: f32; s0 and s1 by fmaf from +0 in the order j = 0 .. P - 1.  The output is bit-identical for every chunking of
+ *     the stream, for a row alone against the same row among others, for host versus device entry and after rewind.
+ *   Limits: 1/8 <= rate <= 8; 1 <= m <= 8 with m D <= 56; 0 < as_db <= 120; fc = 0 or 0 < fc < 0.5; nchan >= 1;
+ *     1 <= max_samples <= 2^28 (samples per row and call).  Anything else: CSDR_ERR_INVALID.
+ *   x is [nchan][n], y is [nchan][n_out], both dense; csdr_rowresamp_max_out(h, n) is the room per row a call of n may need
+ *     and csdr_rowresamp_count(h, n) what the next call of n yields.  The count comes from integers on the host:
+ *     process_device enqueues on `stream` and does not synchronise.
+ *   csdr_rowresamp_design, csdr_rowresamp_launch_shape: no GPU needed.  shape = {P, outputs per tile, window slots, LDS bytes,
+ *     workgroups per CU, tiles per row, items per run, runs}.
+ *   CSDR_ERR_SIZE: more than max_samples samples.  NULL, x and y the same buffer: CSDR_ERR_INVALID.  A refused call leaves the
+ *     stream untouched.  No GPU: CSDR_ERR_NODEV.  n = 0: yields nothing.  destroy(NULL) is 0.
+ * ------------------------------------------------------------------------ */
+typedef struct csdr_rowresamp csdr_rowresamp;
+int csdr_rowresamp_design(double rate, uint32_t m, float as_db, float fc, uint32_t *taps_per_phase, uint64_t *delta,
+                          float *bank /* [257][P] or NULL */);
+int csdr_rowresamp_launch_shape(double rate, uint32_t m, int32_t is_complex, uint32_t n_out, uint32_t nchan, uint32_t cus,
+                                uint64_t t_next, uint32_t *shape /* [8] */);
+int csdr_rowresamp_open(double rate, uint32_t m, float as_db, float fc, int32_t is_complex, uint32_t nchan, uint32_t max_samples,
+                        csdr_rowresamp **out);
+uint32_t csdr_rowresamp_max_out(const csdr_rowresamp *h, uint32_t n);            /* room a caller provides per row          */
+int csdr_rowresamp_count(const csdr_rowresamp *h, uint32_t n, uint32_t *n_out);  /* what the next call of n yields          */
+int csdr_rowresamp_process(csdr_rowresamp *h, const float *x, uint32_t n, float *y, uint32_t *n_out);
+int csdr_rowresamp_process_device(csdr_rowresamp *h, const void *d_x, uint32_t n, void *d_y, uint32_t *n_out, void *stream);
+int csdr_rowresamp_rewind(csdr_rowresamp *h);                                    /* back to the state right after open      */
+int csdr_rowresamp_get_design(const csdr_rowresamp *h, uint32_t *taps_per_phase, uint64_t *delta, uint32_t *delay,
+                              float *bank);                                      /* any pointer may be NULL                 */
+int csdr_rowresamp_get_time(const csdr_rowresamp *h, uint64_t *t_next);
+int csdr_rowresamp_destroy(csdr_rowresamp *h);
+
+/* ------------------------------------------------------------------------ *
  * The fused chain: everything assembleFold (apps/SoapySDR.hs:208-226) puts
  * behind `compact`:
  *     dcBlocker                                   (SoapySDR.hs:213-214)
