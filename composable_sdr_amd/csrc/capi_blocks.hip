@@ -1,6 +1,7 @@
 // C ABI of libcsdr_hip.so (see include/csdr.h): the handles of the single DSP blocks.  Product code: no CPU fallback,
 // nothing from oracle/.  Every handle owns its device memory through `mem` and lives the one life-cycle of capi_internal.h:
-// create = argument checks, NewBlock::open, fill, publish; destroy = block_destroy.
+// create (or open) = argument checks, NewBlock::open, fill, publish; reset (or rewind) = block_reset; a host call =
+// block_host_call around the device entry point; destroy = block_destroy.  State carried in two buffers is a PingPong.
 #include "capi_internal.h"
 
 #include <cstdio>
@@ -23,27 +24,25 @@ struct csdr_agc {
     int device; DeviceBuffers mem; uint32_t C, max_n; AgcParams p; AgcState *d_st = nullptr; float2 *d_z = nullptr;
 };
 struct csdr_iirfilt {
-    int device; DeviceBuffers mem; uint32_t C, max_n; BiquadParams p; float2 *d_st[2] = {nullptr, nullptr}; int cur = 0; float *d_x = nullptr;
+    int device; DeviceBuffers mem; uint32_t C, max_n; BiquadParams p; PingPong<float2> st; float *d_x = nullptr;
 };
 struct csdr_firdecim {
-    int device; DeviceBuffers mem; uint32_t C, max_n, M, h_len; float *d_h = nullptr, *d_hist[2] = {nullptr, nullptr}; int cur = 0;
+    int device; DeviceBuffers mem; uint32_t C, max_n, M, h_len; float *d_h = nullptr; PingPong<float> hist;
     float *d_x = nullptr, *d_y = nullptr;
 };
 struct csdr_resamp {
     int device; DeviceBuffers mem; uint32_t max_in; ResampDesign d;
-    // stage s (s < K: half-band decimators; s == K: the arbitrary stage): history-prefixed input buffer
+    // stage s (s < K: half-band decimators; s == K: the arbitrary stage): history-prefixed input buffer, its tail kept in place
     std::vector<float2 *> d_buf; std::vector<float *> d_h; std::vector<uint32_t> H; std::vector<uint64_t> n_seen;
     float *d_pfb = nullptr; float2 *d_out = nullptr;
     uint64_t t_next = 0;         // Q32.32 absolute time (arbitrary-stage input samples) of the next output
     bool passthrough = false;    // rate 0: the reference's "no resampler" (Liquid.chs:100-103); owns no device memory
 };
 struct csdr_ampdem {
-    int device; DeviceBuffers mem; uint32_t C, max_n; float *d_q[2] = {nullptr, nullptr}; int cur = 0;
-    float2 *d_z = nullptr; float *d_f = nullptr;
+    int device; DeviceBuffers mem; uint32_t C, max_n; PingPong<float> q; float2 *d_z = nullptr; float *d_f = nullptr;
 };
 struct csdr_freqdem {
-    int device; DeviceBuffers mem; uint32_t C, max_n; float ref; float2 *d_rp[2] = {nullptr, nullptr}; int cur = 0;
-    float2 *d_z = nullptr; float *d_f = nullptr;
+    int device; DeviceBuffers mem; uint32_t C, max_n; float ref; PingPong<float2> rp; float2 *d_z = nullptr; float *d_f = nullptr;
 };
 
 extern "C" {
@@ -56,7 +55,7 @@ int csdr_dcblock_create(float alpha, uint32_t max_samples, csdr_dcblock **out)
     if (!out || !(alpha > 0.f && alpha < 1.f)) { set_error("dcblock: bad arguments"); return CSDR_ERR_INVALID; }
     NewBlock<csdr_dcblock> h;
     int r = h.open(); if (r) return r;
-    h->max_n = max_samples ? max_samples : 1u << 20; h->dc = make_dc(alpha);
+    h->max_n = block_max_n(max_samples, 1u << 20); h->dc = make_dc(alpha);
     if ((r = block_zeros(h->mem, &h->d_state, 1)) || (r = h->mem.alloc_n(&h->d_scratch, 2 * (size_t)(h->max_n / DC_BLOCK + 2))) ||
         (r = h->mem.alloc_n(&h->d_x, h->max_n)) || (r = h->mem.alloc_n(&h->d_y, h->max_n))) return r;
     return h.publish(out);
@@ -89,7 +88,7 @@ int csdr_nco_create(float freq, uint32_t max_samples, csdr_nco **out)
     if (!out || !std::isfinite(freq)) { set_error("nco: bad arguments"); return CSDR_ERR_INVALID; }
     NewBlock<csdr_nco> h;
     int r = h.open(); if (r) return r;
-    h->max_n = max_samples ? max_samples : 1u << 20;
+    h->max_n = block_max_n(max_samples, 1u << 20);
     h->theta = 0; h->d_theta = nco_freq_word(freq);
     if ((r = h->mem.alloc_n(&h->d_x, h->max_n)) || (r = h->mem.alloc_n(&h->d_y, h->max_n))) return r;
     return h.publish(out);
@@ -126,7 +125,7 @@ int csdr_agc_create(float threshold_db, uint32_t nchan, uint32_t max_samples, cs
     if (!out || !nchan || !std::isfinite(threshold_db)) { set_error("agc: bad arguments"); return CSDR_ERR_INVALID; }
     NewBlock<csdr_agc> h;
     int r = h.open(); if (r) return r;
-    h->C = nchan; h->max_n = max_samples ? max_samples : 4096; h->p = make_agc(threshold_db);
+    h->C = nchan; h->max_n = block_max_n(max_samples); h->p = make_agc(threshold_db);
     if ((r = h->mem.alloc_n(&h->d_st, nchan)) || (r = h->mem.alloc_n(&h->d_z, (size_t)nchan * h->max_n))) return r;
     if ((r = launch_agc_init(h->d_st, nchan, nullptr))) return r;
     CSDR_HIP(hipDeviceSynchronize());
@@ -150,9 +149,9 @@ int csdr_freqdem_create(float kf, uint32_t nchan, uint32_t max_samples, csdr_fre
     if (!out || !nchan || !(kf > 0.f)) { set_error("freqdem: bad arguments (kf must be > 0)"); return CSDR_ERR_INVALID; }
     NewBlock<csdr_freqdem> h;
     int r = h.open(); if (r) return r;
-    h->C = nchan; h->max_n = max_samples ? max_samples : 4096; h->ref = fm_ref_of(kf);
-    if ((r = block_zeros(h->mem, &h->d_rp[0], nchan)) || (r = block_zeros(h->mem, &h->d_rp[1], nchan)) ||
-        (r = h->mem.alloc_n(&h->d_z, (size_t)nchan * h->max_n)) || (r = h->mem.alloc_n(&h->d_f, (size_t)nchan * h->max_n))) return r;
+    h->C = nchan; h->max_n = block_max_n(max_samples); h->ref = fm_ref_of(kf);
+    if ((r = h->rp.alloc_zeroed(h->mem, nchan)) || (r = h->mem.alloc_n(&h->d_z, (size_t)nchan * h->max_n)) ||
+        (r = h->mem.alloc_n(&h->d_f, (size_t)nchan * h->max_n))) return r;
     return h.publish(out);
 }
 int csdr_freqdem_process(csdr_freqdem *h, const float *x, uint32_t n, float *m)
@@ -161,9 +160,7 @@ int csdr_freqdem_process(csdr_freqdem *h, const float *x, uint32_t n, float *m)
     if (!n) return CSDR_OK;
     const size_t Cn = (size_t)h->C * n;
     return block_round_trip("freqdem", h->device, h->d_z, x, sizeof(float2) * Cn, h->d_f, m, sizeof(float) * Cn, [&] {
-        const int r = launch_fm(h->d_z, h->d_f, h->C, n, h->ref, h->d_rp[h->cur], h->d_rp[h->cur ^ 1], nullptr);
-        if (!r) h->cur ^= 1;
-        return r;
+        return h->rp.flip_behind(launch_fm(h->d_z, h->d_f, h->C, n, h->ref, h->rp.in(), h->rp.out(), nullptr));
     });
 }
 int csdr_freqdem_destroy(csdr_freqdem *h) { return block_destroy(h); }
@@ -178,9 +175,8 @@ int csdr_iirfilt_create(uint32_t order, float fc, float f0, float ap, float as_d
     if (order != 2) { set_error("iirfilt: only the reference's order-2 Butterworth low-pass is built (order %u)", order); return CSDR_ERR_INVALID; }
     NewBlock<csdr_iirfilt> h;
     int r = h.open(); if (r) return r;
-    h->C = nchan; h->max_n = max_samples ? max_samples : 4096; h->p = design_butter2_lowpass(fc);
-    if ((r = h->mem.alloc_n(&h->d_x, (size_t)nchan * h->max_n)) || (r = block_zeros(h->mem, &h->d_st[0], nchan)) ||
-        (r = block_zeros(h->mem, &h->d_st[1], nchan))) return r;
+    h->C = nchan; h->max_n = block_max_n(max_samples); h->p = design_butter2_lowpass(fc);
+    if ((r = h->mem.alloc_n(&h->d_x, (size_t)nchan * h->max_n)) || (r = h->st.alloc_zeroed(h->mem, nchan))) return r;
     return h.publish(out);
 }
 int csdr_iirfilt_process(csdr_iirfilt *h, const float *x, uint32_t n, float *y)
@@ -189,9 +185,7 @@ int csdr_iirfilt_process(csdr_iirfilt *h, const float *x, uint32_t n, float *y)
     if (!n) return CSDR_OK;
     const size_t bytes = sizeof(float) * (size_t)h->C * n;
     return block_round_trip("iirfilt", h->device, h->d_x, x, bytes, h->d_x, y, bytes, [&] {
-        const int r = launch_biquad(h->d_x, h->d_x, h->C, n, h->p, h->d_st[h->cur], h->d_st[h->cur ^ 1], nullptr);
-        if (!r) h->cur ^= 1;
-        return r;
+        return h->st.flip_behind(launch_biquad(h->d_x, h->d_x, h->C, n, h->p, h->st.in(), h->st.out(), nullptr));
     });
 }
 int csdr_iirfilt_destroy(csdr_iirfilt *h) { return block_destroy(h); }
@@ -202,11 +196,10 @@ int csdr_firdecim_create(uint32_t decim, uint32_t nchan, uint32_t max_samples, c
     NewBlock<csdr_firdecim> h;
     int r = h.open(); if (r) return r;
     const std::vector<float> taps = design_firdecim_kaiser(decim, 10, 60.0f);          // firdecimCreate, Liquid.chs:485-490
-    h->C = nchan; h->max_n = max_samples ? max_samples : 4096; h->M = decim; h->h_len = (uint32_t)taps.size();
+    h->C = nchan; h->max_n = block_max_n(max_samples); h->M = decim; h->h_len = (uint32_t)taps.size();
     const size_t hist = (size_t)nchan * (h->h_len - 1);
     if ((r = h->mem.alloc_n(&h->d_x, (size_t)nchan * h->max_n)) || (r = h->mem.alloc_n(&h->d_y, (size_t)nchan * (h->max_n / decim + 1))) ||
-        (r = block_upload(h->mem, &h->d_h, taps.data(), taps.size())) || (r = block_zeros(h->mem, &h->d_hist[0], hist)) ||
-        (r = block_zeros(h->mem, &h->d_hist[1], hist))) return r;
+        (r = block_upload(h->mem, &h->d_h, taps.data(), taps.size())) || (r = h->hist.alloc_zeroed(h->mem, hist))) return r;
     return h.publish(out);
 }
 int csdr_firdecim_process(csdr_firdecim *h, const float *x, uint32_t n, float *y)
@@ -216,9 +209,7 @@ int csdr_firdecim_process(csdr_firdecim *h, const float *x, uint32_t n, float *y
     if (!n) return CSDR_OK;
     const size_t C = h->C;
     return block_round_trip("firdecim", h->device, h->d_x, x, sizeof(float) * C * n, h->d_y, y, sizeof(float) * C * (n / h->M), [&] {
-        const int r = launch_firdecim(h->d_x, h->d_y, h->C, n, h->M, h->d_h, h->h_len, h->d_hist[h->cur], h->d_hist[h->cur ^ 1], nullptr);
-        if (!r) h->cur ^= 1;
-        return r;
+        return h->hist.flip_behind(launch_firdecim(h->d_x, h->d_y, h->C, n, h->M, h->d_h, h->h_len, h->hist.in(), h->hist.out(), nullptr));
     });
 }
 int csdr_firdecim_destroy(csdr_firdecim *h) { return block_destroy(h); }
@@ -232,7 +223,7 @@ int csdr_resamp_create(float rate, float As, uint32_t max_in, csdr_resamp **out)
     if (rate > 2.0f) { set_error("resamp: rate %g > 2 (interpolating half-band stages are not built)", rate); return CSDR_ERR_INVALID; }
     NewBlock<csdr_resamp> h;
     int r = h.open(); if (r) return r;
-    h->max_in = max_in ? max_in : 4096;
+    h->max_in = block_max_n(max_in);
     if (rate == 0.f) { h->passthrough = true; return h.publish(out); }
     h->d = design_msresamp(rate, As);
     const uint32_t K = h->d.K, P = 2 * h->d.m_arb;
@@ -344,9 +335,9 @@ int csdr_ampdem_create(float mod_index, uint32_t nchan, uint32_t max_samples, cs
     if (!out || !nchan || !(mod_index > 0.f)) { set_error("ampdem: bad arguments (mod_index must be > 0)"); return CSDR_ERR_INVALID; }
     NewBlock<csdr_ampdem> h;
     int r = h.open(); if (r) return r;
-    h->C = nchan; h->max_n = max_samples ? max_samples : 4096;
+    h->C = nchan; h->max_n = block_max_n(max_samples);
     if ((r = h->mem.alloc_n(&h->d_z, (size_t)nchan * h->max_n)) || (r = h->mem.alloc_n(&h->d_f, (size_t)nchan * h->max_n)) ||
-        (r = block_zeros(h->mem, &h->d_q[0], nchan)) || (r = block_zeros(h->mem, &h->d_q[1], nchan))) return r;
+        (r = h->q.alloc_zeroed(h->mem, nchan))) return r;
     return h.publish(out);
 }
 int csdr_ampdem_process(csdr_ampdem *h, const float *x, uint32_t n, float *m)
@@ -355,9 +346,7 @@ int csdr_ampdem_process(csdr_ampdem *h, const float *x, uint32_t n, float *m)
     if (!n) return CSDR_OK;
     const size_t Cn = (size_t)h->C * n;
     return block_round_trip("ampdem", h->device, h->d_z, x, sizeof(float2) * Cn, h->d_f, m, sizeof(float) * Cn, [&] {
-        const int r = launch_am(h->d_z, h->d_f, h->C, n, h->d_q[h->cur], h->d_q[h->cur ^ 1], 0.01f, nullptr);
-        if (!r) h->cur ^= 1;
-        return r;
+        return h->q.flip_behind(launch_am(h->d_z, h->d_f, h->C, n, h->q.in(), h->q.out(), 0.01f, nullptr));
     });
 }
 int csdr_ampdem_destroy(csdr_ampdem *h) { return block_destroy(h); }
@@ -367,6 +356,7 @@ int csdr_ampdem_destroy(csdr_ampdem *h) { return block_destroy(h); }
 // ---------------------------------------------------------------------------
 }  // extern "C"
 struct csdr_fmstereo {
+    // cur: the one index of the three pairs d_xh, d_ub, d_dh (no PingPong: FmsBufs / FmsLaunch take both sides and the index)
     int device; DeviceBuffers mem; uint32_t C, max_n, M; FmsDesign f; uint32_t theta = 0; int cur = 0;
     float *d_hp = nullptr, *d_ha = nullptr, *d_hdec = nullptr, *d_xh[2] = {nullptr, nullptr}, *d_ub[2] = {nullptr, nullptr};
     float2 *d_p = nullptr, *d_bq = nullptr; float *d_lpr = nullptr, *d_lr = nullptr, *d_dh[2] = {nullptr, nullptr}; uint2 *d_pll = nullptr;
@@ -400,7 +390,7 @@ int csdr_fmstereo_create(float quad_rate, uint32_t decim, uint32_t nchan, uint32
     }
     NewBlock<csdr_fmstereo> h;
     int r = h.open(); if (r) return r;
-    h->C = nchan; h->max_n = max_samples ? max_samples : 4096; h->M = decim;
+    h->C = nchan; h->max_n = block_max_n(max_samples); h->M = decim;
     h->f = design_fmstereo((double)quad_rate, decim);
     h->timed = diag_env("CSDR_FMS_TIME") != nullptr;           // hipEvents around the five kernels (tools/fms_time.py)
     const size_t C = nchan, N = h->f.N, Hd = h->f.h_dec.size() - 1, n = h->max_n;
@@ -445,13 +435,7 @@ int csdr_fmstereo_process(csdr_fmstereo *h, const float *mpx, uint32_t n, float 
     return block_round_trip("fmstereo", h->device, h->d_in, mpx, sizeof(float) * (size_t)h->C * n, h->d_out, lr, sizeof(float) * (size_t)*n_out,
                             [&] { return csdr_fmstereo_process_device(h, h->d_in, n, h->d_out, n_out, nullptr); });
 }
-int csdr_fmstereo_reset(csdr_fmstereo *h)
-{
-    if (!h) return CSDR_ERR_INVALID;
-    DevGuard guard(h->device);
-    CSDR_HIP(hipDeviceSynchronize());
-    return fms_init_state(h);
-}
+int csdr_fmstereo_reset(csdr_fmstereo *h) { return block_reset(h, [&] { return fms_init_state(h); }); }
 uint32_t csdr_fmstereo_get_delay(const csdr_fmstereo *h) { return h ? h->f.d : 0; }
 uint32_t csdr_fmstereo_get_taps_len(const csdr_fmstereo *h) { return h ? h->f.N : 0; }
 int csdr_fmstereo_get_pll(csdr_fmstereo *h, uint32_t chan, uint32_t *theta, uint32_t *d_theta)
@@ -481,7 +465,7 @@ int csdr_fmstereo_kernel_times(csdr_fmstereo *h, float *us5)
 struct csdr_symsync {
     int device; DeviceBuffers mem; uint32_t C, max_n; SymsyncDesign d;
     float *d_mf = nullptr, *d_dmf = nullptr, *d_hist = nullptr, *d_x = nullptr, *d_y = nullptr;
-    SymsyncState *d_st = nullptr; uint32_t *d_ny = nullptr, *d_fault = nullptr;
+    SymsyncState *d_st = nullptr; uint32_t *d_ny = nullptr, *d_fault = nullptr;    // state and windows are updated in place: no pair
     // the sample type, fixed by the first process call after create, reset or a setter: 0 open, 1 F32 rows, 2 CF32 rows
     int kind = 0;
     float2 *d_histc = nullptr, *d_xc = nullptr, *d_yc = nullptr;    // the complex windows and staging: allocated by the first complex call
@@ -533,6 +517,17 @@ static int symsync_launch_c(csdr_symsync *h, const void *d_x, uint32_t n, void *
     return launch_symsyncc((const float2 *)d_x, (float2 *)d_y, (uint32_t *)d_ny, h->d_mf, h->d_dmf, h->d_histc, h->d_st, h->d_fault, l,
                            (hipStream_t)stream);
 }
+// the host side of both calls: rows of row_bytes in (none for n = 0), run(), then the counts, the fault word and the rows out
+template <class Run>
+static int symsync_host_call(csdr_symsync *h, void *d_x, const float *x, size_t row_bytes, const void *d_y, float *y, uint32_t *ny, Run run)
+{
+    uint32_t fault = 0;
+    const int r = block_host_call("symsync", h->device, d_x, x, row_bytes, run,
+                                  {{ny, h->d_ny, sizeof(uint32_t) * h->C}, {&fault, h->d_fault, sizeof(uint32_t)}, {y, d_y, row_bytes}});
+    if (r) return r;
+    if (fault) { set_error("symsync: a stream is faulted (del <= 0 or more than n outputs in a call); reset clears it"); return CSDR_ERR_SIZE; }
+    return CSDR_OK;
+}
 extern "C" {
 int csdr_symsync_destroy(csdr_symsync *h) { return block_destroy(h); }
 int csdr_symsync_create(uint32_t k, uint32_t m, float beta, uint32_t npfb, float lf_bw, uint32_t k_out, uint32_t nchan,
@@ -547,7 +542,7 @@ int csdr_symsync_create(uint32_t k, uint32_t m, float beta, uint32_t npfb, float
     }
     NewBlock<csdr_symsync> h;
     int r = h.open(); if (r) return r;
-    h->C = nchan; h->max_n = max_samples ? max_samples : 4096;
+    h->C = nchan; h->max_n = block_max_n(max_samples);
     h->d = design_symsync_kaiser(k, m, beta, npfb, lf_bw, k_out);
     const size_t C = nchan, n = h->max_n, LM = h->d.mf.size();
     DeviceBuffers &mem = h->mem;
@@ -572,17 +567,9 @@ int csdr_symsync_process_device(csdr_symsync *h, const void *d_x, uint32_t n, vo
 int csdr_symsync_process(csdr_symsync *h, const float *x, uint32_t n, float *y, uint32_t *ny)
 {
     if (!ny) return block_null_arg("symsync");
-    int r = block_check_call("symsync", h, x, n, y); if (r) return r;
-    DevGuard guard;
-    if ((r = block_select("symsync", guard, h->device))) return r;
-    if (n) CSDR_HIP(hipMemcpy(h->d_x, x, sizeof(float) * (size_t)h->C * n, hipMemcpyHostToDevice));
-    if ((r = csdr_symsync_process_device(h, h->d_x, n, h->d_y, h->d_ny, nullptr))) return r;
-    uint32_t fault = 0;
-    CSDR_HIP(hipMemcpy(ny, h->d_ny, sizeof(uint32_t) * h->C, hipMemcpyDeviceToHost));
-    CSDR_HIP(hipMemcpy(&fault, h->d_fault, sizeof(uint32_t), hipMemcpyDeviceToHost));
-    if (n) CSDR_HIP(hipMemcpy(y, h->d_y, sizeof(float) * (size_t)h->C * n, hipMemcpyDeviceToHost));
-    if (fault) { set_error("symsync: a stream is faulted (del <= 0 or more than n outputs in a call); reset clears it"); return CSDR_ERR_SIZE; }
-    return CSDR_OK;
+    if (int r = block_check_call("symsync", h, x, n, y)) return r;
+    return symsync_host_call(h, h->d_x, x, sizeof(float) * (size_t)h->C * n, h->d_y, y, ny,
+                             [&] { return csdr_symsync_process_device(h, h->d_x, n, h->d_y, h->d_ny, nullptr); });
 }
 int csdr_symsync_process_c_device(csdr_symsync *h, const void *d_x, uint32_t n, void *d_y, void *d_ny, void *stream)
 {
@@ -595,17 +582,9 @@ int csdr_symsync_process_c(csdr_symsync *h, const float *x, uint32_t n, float *y
 {
     if (!ny) return block_null_arg("symsync");
     int r = block_check_call("symsync", h, x, n, y); if (r) return r;
-    DevGuard guard;
-    if ((r = block_select("symsync", guard, h->device))) return r;
     if ((r = symsync_complex_ready(h, n, true))) return r;
-    if (n) CSDR_HIP(hipMemcpy(h->d_xc, x, sizeof(float2) * (size_t)h->C * n, hipMemcpyHostToDevice));
-    if ((r = symsync_launch_c(h, h->d_xc, n, h->d_yc, h->d_ny, nullptr))) return r;
-    uint32_t fault = 0;
-    CSDR_HIP(hipMemcpy(ny, h->d_ny, sizeof(uint32_t) * h->C, hipMemcpyDeviceToHost));
-    CSDR_HIP(hipMemcpy(&fault, h->d_fault, sizeof(uint32_t), hipMemcpyDeviceToHost));
-    if (n) CSDR_HIP(hipMemcpy(y, h->d_yc, sizeof(float2) * (size_t)h->C * n, hipMemcpyDeviceToHost));
-    if (fault) { set_error("symsync: a stream is faulted (del <= 0 or more than n outputs in a call); reset clears it"); return CSDR_ERR_SIZE; }
-    return CSDR_OK;
+    return symsync_host_call(h, h->d_xc, x, sizeof(float2) * (size_t)h->C * n, h->d_yc, y, ny,
+                             [&] { return symsync_launch_c(h, h->d_xc, n, h->d_yc, h->d_ny, nullptr); });
 }
 // symsync_create(k, M, H, H_len) behind create: new banks from the caller's prototype, then the state right after create
 int csdr_symsync_set_taps(csdr_symsync *h, const float *H, uint32_t H_len)
@@ -619,14 +598,15 @@ int csdr_symsync_set_taps(csdr_symsync *h, const float *H, uint32_t H_len)
     }
     if (!ok) { set_error("symsync: the prototype taps must be finite and not all zero"); return CSDR_ERR_INVALID; }
     DevGuard guard;
-    int r = block_select("symsync", guard, h->device); if (r) return r;
-    CSDR_HIP(hipDeviceSynchronize());
-    h->d.H.assign(H, H + H_len);
-    symsync_set_prototype(h->d);
-    const size_t LM = h->d.mf.size();
-    CSDR_HIP(hipMemcpy(h->d_mf, h->d.mf.data(), sizeof(float) * LM, hipMemcpyHostToDevice));
-    CSDR_HIP(hipMemcpy(h->d_dmf, h->d.dmf.data(), sizeof(float) * LM, hipMemcpyHostToDevice));
-    return symsync_init_state(h);
+    if (int r = block_select("symsync", guard, h->device)) return r;
+    return block_idle_run([&] {
+        h->d.H.assign(H, H + H_len);
+        symsync_set_prototype(h->d);
+        const size_t LM = h->d.mf.size();
+        CSDR_HIP(hipMemcpy(h->d_mf, h->d.mf.data(), sizeof(float) * LM, hipMemcpyHostToDevice));
+        CSDR_HIP(hipMemcpy(h->d_dmf, h->d.dmf.data(), sizeof(float) * LM, hipMemcpyHostToDevice));
+        return symsync_init_state(h);
+    });
 }
 // symsync_create_rnyquist(ftype, k, m, beta, npfb): the prototype at k npfb samples per symbol
 int csdr_symsync_set_rnyquist(csdr_symsync *h, int ftype, float beta)
@@ -636,13 +616,7 @@ int csdr_symsync_set_rnyquist(csdr_symsync *h, int ftype, float beta)
     if (int r = csdr_firdes_rnyquist(ftype, h->d.k * h->d.M, h->d.m, beta, 0.f, H.data())) return r;
     return csdr_symsync_set_taps(h, H.data(), h->d.H_len);
 }
-int csdr_symsync_reset(csdr_symsync *h)
-{
-    if (!h) return CSDR_ERR_INVALID;
-    DevGuard guard(h->device);
-    CSDR_HIP(hipDeviceSynchronize());
-    return symsync_init_state(h);
-}
+int csdr_symsync_reset(csdr_symsync *h) { return block_reset(h, [&] { return symsync_init_state(h); }); }
 int csdr_symsync_get_state(csdr_symsync *h, uint32_t chan, float *tau, float *rate, float *del, float *q_hat)
 {
     if (!h || chan >= h->C) { set_error("symsync: bad channel"); return CSDR_ERR_INVALID; }
@@ -671,7 +645,7 @@ int csdr_symsync_get_taps(const csdr_symsync *h, float *mf, float *dmf)
 }  // extern "C"
 struct csdr_firhilb {
     int device; DeviceBuffers mem; uint32_t m, max_n; std::vector<float> hq;
-    float *d_hist[2] = {nullptr, nullptr}; int cur = 0;     // the windows, pair-interleaved (w1[j], w0[j]), ping-pong
+    PingPong<float> hist;                                   // the windows, pair-interleaved (w1[j], w0[j]): [4 m]
     float *d_x = nullptr, *d_y = nullptr;
 };
 static int firhilb_run(csdr_firhilb *h, bool interp, const void *d_x, uint32_t n, void *d_y, void *stream)
@@ -683,9 +657,7 @@ static int firhilb_run(csdr_firhilb *h, bool interp, const void *d_x, uint32_t n
     FirhilbLaunch l{};
     l.n = n; l.m = h->m;
     std::memcpy(l.hq, h->hq.data(), sizeof(float) * h->hq.size());
-    const int r = launch_firhilb(interp, (const float *)d_x, (float *)d_y, h->d_hist[h->cur], h->d_hist[h->cur ^ 1], l, (hipStream_t)stream);
-    if (!r) h->cur ^= 1;
-    return r;
+    return h->hist.flip_behind(launch_firhilb(interp, (const float *)d_x, (float *)d_y, h->hist.in(), h->hist.out(), l, (hipStream_t)stream));
 }
 static int firhilb_host(csdr_firhilb *h, bool interp, const float *x, uint32_t n, float *y)
 {
@@ -705,11 +677,10 @@ int csdr_firhilb_create(uint32_t m, float as_db, uint32_t max_samples, csdr_firh
     }
     NewBlock<csdr_firhilb> h;
     int r = h.open(); if (r) return r;
-    h->m = m; h->max_n = max_samples ? max_samples : 4096;
+    h->m = m; h->max_n = block_max_n(max_samples);
     h->hq = design_firhilb(m, as_db);
     const size_t n2 = 2 * (size_t)h->max_n;
-    if ((r = block_zeros(h->mem, &h->d_hist[0], 4 * m)) || (r = h->mem.alloc_n(&h->d_hist[1], 4 * m)) || (r = h->mem.alloc_n(&h->d_x, n2)) ||
-        (r = h->mem.alloc_n(&h->d_y, n2))) return r;
+    if ((r = h->hist.alloc_zeroed(h->mem, 4 * m)) || (r = h->mem.alloc_n(&h->d_x, n2)) || (r = h->mem.alloc_n(&h->d_y, n2))) return r;
     return h.publish(out);
 }
 int csdr_firhilb_decim_device(csdr_firhilb *h, const void *d_x, uint32_t n, void *d_y, void *stream)
@@ -722,14 +693,7 @@ int csdr_firhilb_interp_device(csdr_firhilb *h, const void *d_x, uint32_t n, voi
 }
 int csdr_firhilb_decim(csdr_firhilb *h, const float *x_f32, uint32_t n, float *y_cf32) { return firhilb_host(h, false, x_f32, n, y_cf32); }
 int csdr_firhilb_interp(csdr_firhilb *h, const float *x_cf32, uint32_t n, float *y_f32) { return firhilb_host(h, true, x_cf32, n, y_f32); }
-int csdr_firhilb_reset(csdr_firhilb *h)
-{
-    if (!h) return CSDR_ERR_INVALID;
-    DevGuard guard(h->device);
-    CSDR_HIP(hipDeviceSynchronize());
-    CSDR_HIP(hipMemset(h->d_hist[h->cur], 0, sizeof(float) * 4 * h->m));
-    return CSDR_OK;
-}
+int csdr_firhilb_reset(csdr_firhilb *h) { return block_reset(h, [&] { return h->hist.reset(nullptr); }); }
 uint32_t csdr_firhilb_get_taps_len(const csdr_firhilb *h) { return h ? 2 * h->m : 0; }
 int csdr_firhilb_get_taps(const csdr_firhilb *h, float *hq)
 {
@@ -757,7 +721,7 @@ int csdr_fskdem_create(uint32_t m, uint32_t k, float bandwidth, uint32_t nchan, 
     }
     NewBlock<csdr_fskdem> h;
     int r = h.open(); if (r) return r;
-    h->C = nchan; h->max_n = max_samples ? max_samples : 4096;
+    h->C = nchan; h->max_n = block_max_n(max_samples);
     h->d = design_fskdem(m, k, bandwidth);
     if (h->d.repeated && !getenv("CSDR_QUIET"))
         fprintf(stderr, "csdr_fskdem_create(%u, %u, %g): warning, the demodulation map is not unique (K = %u); consider a larger bandwidth or k\n",
@@ -785,14 +749,10 @@ int csdr_fskdem_process(csdr_fskdem *h, const float *x, uint32_t n, uint32_t *sy
     *n_out = (uint32_t)(C * ns);
     if (!ns) return CSDR_OK;
     if (!x || !sym) { set_error("fskdem: null buffer"); return CSDR_ERR_INVALID; }
-    DevGuard guard;
-    if ((r = block_select("fskdem", guard, h->device))) return r;
-    if (energy && !h->d_e && (r = h->mem.alloc_n(&h->d_e, C * (h->max_n / h->d.k) * h->d.M))) return r;
-    CSDR_HIP(hipMemcpy(h->d_x, x, sizeof(float2) * C * n, hipMemcpyHostToDevice));
-    if ((r = csdr_fskdem_process_device(h, h->d_x, n, h->d_sym, energy ? h->d_e : nullptr, nullptr))) return r;
-    CSDR_HIP(hipMemcpy(sym, h->d_sym, sizeof(uint32_t) * C * ns, hipMemcpyDeviceToHost));
-    if (energy) CSDR_HIP(hipMemcpy(energy, h->d_e, sizeof(float) * C * ns * h->d.M, hipMemcpyDeviceToHost));
-    return CSDR_OK;
+    if (energy && (r = block_lazy_alloc("fskdem", h->device, h->mem, &h->d_e, C * (h->max_n / h->d.k) * h->d.M))) return r;
+    return block_host_call("fskdem", h->device, h->d_x, x, sizeof(float2) * C * n,
+                           [&] { return csdr_fskdem_process_device(h, h->d_x, n, h->d_sym, energy ? h->d_e : nullptr, nullptr); },
+                           {{sym, h->d_sym, sizeof(uint32_t) * C * ns}, {energy, h->d_e, sizeof(float) * C * ns * h->d.M}});
 }
 int csdr_fskdem_get_design(const csdr_fskdem *h, uint32_t *K, uint32_t *demod_map)
 {
@@ -846,7 +806,7 @@ int csdr_fir_groupdelay(const float *h, uint32_t n, float fc, float *gd)
 }  // extern "C"
 struct csdr_firfilt {
     int device; DeviceBuffers mem; uint32_t C, max_n, el; bool cplx; std::vector<float> taps; float scale;   // el: bytes per sample
-    float *d_h = nullptr; char *d_hist[2] = {nullptr, nullptr}; int cur = 0;               // [C][L - 1] samples, ping-pong
+    float *d_h = nullptr; PingPong<char> hist;                                             // hist: [C][L - 1] samples, in bytes
     char *d_x = nullptr, *d_y = nullptr;
     size_t hist_bytes() const { return (size_t)C * (taps.size() - 1) * el; }
 };
@@ -861,13 +821,12 @@ int csdr_firfilt_create_taps(const float *taps, uint32_t n, float scale, int32_t
     }
     NewBlock<csdr_firfilt> h;
     int r = h.open(); if (r) return r;
-    h->C = nchan; h->max_n = max_samples ? max_samples : 4096; h->cplx = is_complex != 0;
+    h->C = nchan; h->max_n = block_max_n(max_samples); h->cplx = is_complex != 0;
     h->el = h->cplx ? sizeof(float2) : sizeof(float);
     h->taps.assign(taps, taps + n); h->scale = scale;
     const size_t plane = (size_t)nchan * h->max_n * h->el;
-    if ((r = block_upload(h->mem, &h->d_h, taps, n)) || (r = block_zeros(h->mem, &h->d_hist[0], h->hist_bytes())) ||
-        (r = h->mem.alloc_n(&h->d_hist[1], h->hist_bytes())) || (r = h->mem.alloc_n(&h->d_x, plane)) || (r = h->mem.alloc_n(&h->d_y, plane)))
-        return r;
+    if ((r = block_upload(h->mem, &h->d_h, taps, n)) || (r = h->hist.alloc_zeroed(h->mem, h->hist_bytes())) ||
+        (r = h->mem.alloc_n(&h->d_x, plane)) || (r = h->mem.alloc_n(&h->d_y, plane))) return r;
     return h.publish(out);
 }
 int csdr_firfilt_create_kaiser(uint32_t n, float fc, float as_db, float mu, int32_t is_complex, uint32_t nchan, uint32_t max_samples,
@@ -887,9 +846,7 @@ int csdr_firfilt_process_device(csdr_firfilt *h, const void *d_x, uint32_t n, vo
     if (!n) return CSDR_OK;
     if (!d_x || !d_y || d_x == d_y) { set_error("firfilt: null or aliased buffer"); return CSDR_ERR_INVALID; }
     const FirfiltLaunch l{h->C, n, (uint32_t)h->taps.size(), h->scale};
-    const int r = launch_firfilt(h->cplx, d_x, d_y, h->d_h, h->d_hist[h->cur], h->d_hist[h->cur ^ 1], l, (hipStream_t)stream);
-    if (!r) h->cur ^= 1;
-    return r;
+    return h->hist.flip_behind(launch_firfilt(h->cplx, d_x, d_y, h->d_h, h->hist.in(), h->hist.out(), l, (hipStream_t)stream));
 }
 int csdr_firfilt_process(csdr_firfilt *h, const float *x, uint32_t n, float *y)
 {
@@ -899,14 +856,7 @@ int csdr_firfilt_process(csdr_firfilt *h, const float *x, uint32_t n, float *y)
     return block_round_trip("firfilt", h->device, h->d_x, x, bytes, h->d_y, y, bytes,
                             [&] { return csdr_firfilt_process_device(h, h->d_x, n, h->d_y, nullptr); });
 }
-int csdr_firfilt_reset(csdr_firfilt *h)
-{
-    if (!h) return CSDR_ERR_INVALID;
-    DevGuard guard(h->device);
-    CSDR_HIP(hipDeviceSynchronize());
-    if (h->hist_bytes()) CSDR_HIP(hipMemset(h->d_hist[h->cur], 0, h->hist_bytes()));
-    return CSDR_OK;
-}
+int csdr_firfilt_reset(csdr_firfilt *h) { return block_reset(h, [&] { return h->hist.reset(nullptr); }); }
 uint32_t csdr_firfilt_get_taps_len(const csdr_firfilt *h) { return h ? (uint32_t)h->taps.size() : 0; }
 int csdr_firfilt_get_taps(const csdr_firfilt *h, float *taps, float *scale)
 {
@@ -935,10 +885,9 @@ int csdr_firdes_gmskrx(uint32_t k, uint32_t m, float bt, float *h) { return fird
 }  // extern "C"
 struct csdr_gmskdem {
     int device; DeviceBuffers mem; uint32_t C, max_n, k, m; std::vector<float> taps;
-    float *d_h = nullptr; float2 *d_hist[2] = {nullptr, nullptr}; int cur = 0;             // [C][L] samples, ping-pong
+    float *d_h = nullptr; PingPong<float2> hist;                                           // hist: [C][L] samples
     float2 *d_x = nullptr; uint32_t *d_sym = nullptr;
     float *d_soft = nullptr;                                // host-path soft values: allocated by the first call that asks for them
-    size_t hist_bytes() const { return sizeof(float2) * C * taps.size(); }
 };
 extern "C" {
 int csdr_gmskdem_destroy(csdr_gmskdem *h) { return block_destroy(h); }
@@ -951,12 +900,11 @@ int csdr_gmskdem_create(uint32_t k, uint32_t m, float bt, uint32_t nchan, uint32
     }
     NewBlock<csdr_gmskdem> h;
     int r = h.open(); if (r) return r;
-    h->C = nchan; h->max_n = max_samples ? max_samples : 4096; h->k = k; h->m = m;
+    h->C = nchan; h->max_n = block_max_n(max_samples); h->k = k; h->m = m;
     h->taps = design_gmskrx(k, m, bt);
     const size_t C = nchan, n = h->max_n, L = h->taps.size();
-    if ((r = block_upload(h->mem, &h->d_h, h->taps.data(), L)) || (r = block_zeros(h->mem, &h->d_hist[0], C * L)) ||
-        (r = h->mem.alloc_n(&h->d_hist[1], C * L)) || (r = h->mem.alloc_n(&h->d_x, C * n)) ||
-        (r = h->mem.alloc_n(&h->d_sym, C * (n / k) + 1))) return r;
+    if ((r = block_upload(h->mem, &h->d_h, h->taps.data(), L)) || (r = h->hist.alloc_zeroed(h->mem, C * L)) ||
+        (r = h->mem.alloc_n(&h->d_x, C * n)) || (r = h->mem.alloc_n(&h->d_sym, C * (n / k) + 1))) return r;
     return h.publish(out);
 }
 // n has to be a multiple of k (the reference throws, Liquid.chs:421) and at most max_samples; nothing is touched otherwise
@@ -972,10 +920,8 @@ int csdr_gmskdem_process_device(csdr_gmskdem *h, const void *d_x, uint32_t n, vo
     if (!n) return CSDR_OK;
     if (!d_x || !d_sym) { set_error("gmskdem: null buffer"); return CSDR_ERR_INVALID; }
     const GmskdemLaunch l{h->C, n, h->k, h->m, (uint32_t)h->taps.size(), (uint32_t)(0x100000000ull / h->k) + 1u};
-    r = launch_gmskdem((const float2 *)d_x, (uint32_t *)d_sym, (float *)d_soft, h->d_h, h->d_hist[h->cur], h->d_hist[h->cur ^ 1], l,
-                       (hipStream_t)stream);
-    if (!r) h->cur ^= 1;
-    return r;
+    return h->hist.flip_behind(launch_gmskdem((const float2 *)d_x, (uint32_t *)d_sym, (float *)d_soft, h->d_h, h->hist.in(), h->hist.out(), l,
+                                              (hipStream_t)stream));
 }
 int csdr_gmskdem_process(csdr_gmskdem *h, const float *x, uint32_t n, uint32_t *sym, float *soft, uint32_t *n_out)
 {
@@ -985,23 +931,12 @@ int csdr_gmskdem_process(csdr_gmskdem *h, const float *x, uint32_t n, uint32_t *
     *n_out = (uint32_t)(C * ns);
     if (!n) return CSDR_OK;
     if (!x || !sym) { set_error("gmskdem: null buffer"); return CSDR_ERR_INVALID; }
-    DevGuard guard;
-    if ((r = block_select("gmskdem", guard, h->device))) return r;
-    if (soft && !h->d_soft && (r = h->mem.alloc_n(&h->d_soft, C * (h->max_n / h->k) + 1))) return r;
-    CSDR_HIP(hipMemcpy(h->d_x, x, sizeof(float2) * C * n, hipMemcpyHostToDevice));
-    if ((r = csdr_gmskdem_process_device(h, h->d_x, n, h->d_sym, soft ? h->d_soft : nullptr, nullptr))) return r;
-    CSDR_HIP(hipMemcpy(sym, h->d_sym, sizeof(uint32_t) * C * ns, hipMemcpyDeviceToHost));
-    if (soft) CSDR_HIP(hipMemcpy(soft, h->d_soft, sizeof(float) * C * ns, hipMemcpyDeviceToHost));
-    return CSDR_OK;
+    if (soft && (r = block_lazy_alloc("gmskdem", h->device, h->mem, &h->d_soft, C * (h->max_n / h->k) + 1))) return r;
+    return block_host_call("gmskdem", h->device, h->d_x, x, sizeof(float2) * C * n,
+                           [&] { return csdr_gmskdem_process_device(h, h->d_x, n, h->d_sym, soft ? h->d_soft : nullptr, nullptr); },
+                           {{sym, h->d_sym, sizeof(uint32_t) * C * ns}, {soft, h->d_soft, sizeof(float) * C * ns}});
 }
-int csdr_gmskdem_reset(csdr_gmskdem *h)
-{
-    if (!h) return CSDR_ERR_INVALID;
-    DevGuard guard(h->device);
-    CSDR_HIP(hipDeviceSynchronize());
-    CSDR_HIP(hipMemset(h->d_hist[h->cur], 0, h->hist_bytes()));
-    return CSDR_OK;
-}
+int csdr_gmskdem_reset(csdr_gmskdem *h) { return block_reset(h, [&] { return h->hist.reset(nullptr); }); }
 int csdr_gmskdem_get_design(const csdr_gmskdem *h, uint32_t *taps_len, float *taps)
 {
     if (!h) return block_null_arg("gmskdem");
@@ -1027,7 +962,7 @@ int csdr_iirdes_butter_lowpass(uint32_t order, float fc, float *b, float *a)
 }  // extern "C"
 struct csdr_iirsos {
     int device; DeviceBuffers mem; uint32_t C, max_n, el; bool cplx; std::vector<float> b, a;   // el: bytes per sample; b, a [3 S], a0 = 1
-    IirSosSection *d_sec = nullptr; char *d_st = nullptr, *d_x = nullptr, *d_y = nullptr;  // d_st [C][S] states of 2 samples
+    IirSosSection *d_sec = nullptr; char *d_st = nullptr, *d_x = nullptr, *d_y = nullptr;  // d_st [C][S] states of 2 samples, in place
     uint32_t nsec() const { return (uint32_t)(b.size() / 3); }
     size_t st_bytes() const { return (size_t)C * nsec() * 2 * el; }
 };
@@ -1058,7 +993,7 @@ int csdr_iirsos_create_sos(const float *b, const float *a, uint32_t nsec, int32_
     }
     NewBlock<csdr_iirsos> h;
     int r = h.open(); if (r) return r;
-    h->C = nchan; h->max_n = max_samples ? max_samples : 4096; h->cplx = is_complex != 0;
+    h->C = nchan; h->max_n = block_max_n(max_samples); h->cplx = is_complex != 0;
     h->el = h->cplx ? sizeof(float2) : sizeof(float);
     h->b = bn; h->a = an;
     const size_t plane = (size_t)nchan * h->max_n * h->el;
@@ -1097,11 +1032,7 @@ int csdr_iirsos_process(csdr_iirsos *h, const float *x, uint32_t n, float *y)
 }
 int csdr_iirsos_reset(csdr_iirsos *h)
 {
-    if (!h) return CSDR_ERR_INVALID;
-    DevGuard guard(h->device);
-    CSDR_HIP(hipDeviceSynchronize());
-    CSDR_HIP(hipMemset(h->d_st, 0, h->st_bytes()));
-    return CSDR_OK;
+    return block_reset(h, [&] { CSDR_HIP(hipMemset(h->d_st, 0, h->st_bytes())); return (int)CSDR_OK; });
 }
 uint32_t csdr_iirsos_get_nsec(const csdr_iirsos *h) { return h ? h->nsec() : 0; }
 int csdr_iirsos_get_sos(const csdr_iirsos *h, float *b, float *a)
@@ -1116,30 +1047,54 @@ int csdr_iirsos_get_sos(const csdr_iirsos *h, float *b, float *a)
 // firpfbch2Channelizer: liquid's firpfbch2_crcf analyzer, which the reference does not import.  The constructors
 // are `open` and the reset is `rewind`; the design and launch-shape functions need no GPU
 // ---------------------------------------------------------------------------
+}  // extern "C"
 static bool pfbch2_design_args_ok(uint32_t M, uint32_t m, float as_db, float fc)
 {
     return pfb2_args_ok(M, m) && std::isfinite(as_db) && as_db > 0.f && std::isfinite(fc) && fc >= 0.f && fc < 0.5f;
 }
-static int pfbch2_bad_design()
+// what csdr_pfbch2 and csdr_pfbsyn2 (name) share: the refusal of a design, the argument check of open_taps, the six words of
+// launch_shape (shape_of: pfb2_shape or pfb2s_shape) and get_taps
+static int pfb2_bad_design(const char *name)
 {
-    set_error("pfbch2: bad arguments (M a power of two in [%u, %u], m in [1, %u], As > 0, fc = 0 or in (0, 0.5), finite)", PFB2_MIN_M,
+    set_error("%s: bad arguments (M a power of two in [%u, %u], m in [1, %u], As > 0, fc = 0 or in (0, 0.5), finite)", name, PFB2_MIN_M,
               PFB2_MAX_M, PFB2_MAX_SEMI);
     return CSDR_ERR_INVALID;
 }
+static int pfb2_check_open(const char *name, const void *out, const float *taps, uint32_t M, uint32_t m, uint32_t max_frames)
+{
+    bool ok = out && taps && pfb2_args_ok(M, m) && max_frames && (uint64_t)max_frames * M <= (1ull << 31);
+    for (uint32_t i = 0; ok && i < 2 * M * m; i++) ok = std::isfinite(taps[i]);
+    if (ok) return CSDR_OK;
+    set_error("%s: bad arguments (finite taps, M a power of two in [%u, %u], m in [1, %u], 1 <= max_frames <= 2^31 / M)", name, PFB2_MIN_M,
+              PFB2_MAX_M, PFB2_MAX_SEMI);
+    return CSDR_ERR_INVALID;
+}
+static int pfb2_launch_shape(const char *name, Pfb2Shape (*shape_of)(uint32_t, uint32_t, uint32_t, uint32_t), uint32_t M, uint32_t m,
+                             uint32_t frames, uint32_t cus, uint32_t *shape)
+{
+    if (!shape || !pfb2_args_ok(M, m) || !cus) { set_error("%s_launch_shape: bad arguments (M, m as for the block, cus >= 1, shape)", name); return CSDR_ERR_INVALID; }
+    const Pfb2Shape s = shape_of(M, m, frames, cus);
+    const uint32_t v[6] = {s.F, s.tiles, s.tiles_per_run, s.runs, s.wgs_per_cu, (uint32_t)s.lds};
+    std::memcpy(shape, v, sizeof(v));
+    return CSDR_OK;
+}
+template <class H> static int pfb2_get_taps(const char *name, const H *h, float *taps)
+{
+    if (!h || !taps) return block_null_arg(name);
+    std::memcpy(taps, h->taps.data(), sizeof(float) * h->taps.size());
+    return CSDR_OK;
+}
+extern "C" {
 int csdr_pfbch2_design(uint32_t M, uint32_t m, float as_db, float fc, float *h)
 {
-    if (!h || !pfbch2_design_args_ok(M, m, as_db, fc)) return pfbch2_bad_design();
+    if (!h || !pfbch2_design_args_ok(M, m, as_db, fc)) return pfb2_bad_design("pfbch2");
     const std::vector<float> t = design_pfb2_taps(M, m, as_db, fc);
     std::memcpy(h, t.data(), sizeof(float) * 2 * M * m);
     return CSDR_OK;
 }
 int csdr_pfbch2_launch_shape(uint32_t M, uint32_t m, uint32_t frames, uint32_t cus, uint32_t *shape)
 {
-    if (!shape || !pfb2_args_ok(M, m) || !cus) { set_error("pfbch2_launch_shape: bad arguments (M, m as for the block, cus >= 1, shape)"); return CSDR_ERR_INVALID; }
-    const Pfb2Shape s = pfb2_shape(M, m, frames, cus);
-    const uint32_t v[6] = {s.F, s.tiles, s.tiles_per_run, s.runs, s.wgs_per_cu, (uint32_t)s.lds};
-    std::memcpy(shape, v, sizeof(v));
-    return CSDR_OK;
+    return pfb2_launch_shape("pfbch2", pfb2_shape, M, m, frames, cus, shape);
 }
 }  // extern "C"
 struct csdr_pfbch2 {
@@ -1150,29 +1105,20 @@ extern "C" {
 int csdr_pfbch2_destroy(csdr_pfbch2 *h) { return block_destroy(h); }
 int csdr_pfbch2_open_taps(const float *taps, uint32_t M, uint32_t m, uint32_t max_frames, csdr_pfbch2 **out)
 {
-    bool ok = out && taps && pfb2_args_ok(M, m) && max_frames && (uint64_t)max_frames * M <= (1ull << 31);
-    for (uint32_t i = 0; ok && i < 2 * M * m; i++) ok = std::isfinite(taps[i]);
-    if (!ok) {
-        set_error("pfbch2: bad arguments (finite taps, M a power of two in [%u, %u], m in [1, %u], 1 <= max_frames <= 2^31 / M)", PFB2_MIN_M,
-                  PFB2_MAX_M, PFB2_MAX_SEMI);
-        return CSDR_ERR_INVALID;
-    }
+    int r = pfb2_check_open("pfbch2", out, taps, M, m, max_frames); if (r) return r;
     NewBlock<csdr_pfbch2> h;
-    int r = h.open(); if (r) return r;
-    int cus = 256;
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device);
-    h->M = M; h->m = m; h->max_frames = max_frames; h->max_n = max_frames * (M / 2); h->cus = (uint32_t)cus;
+    if ((r = h.open())) return r;
+    h->M = M; h->m = m; h->max_frames = max_frames; h->max_n = max_frames * (M / 2); h->cus = block_cu_count(h->device);
     h->taps.assign(taps, taps + 2 * M * m);
     const std::vector<float2> tw = pfb2_twiddles(M);
     if ((r = block_upload(h->mem, &h->d_h, taps, h->taps.size())) || (r = block_upload(h->mem, &h->d_tw, tw.data(), tw.size())) ||
-        (r = h->hist.alloc(h->mem, h->taps.size() - M / 2)) || (r = h->hist.reset(nullptr)) ||
-        (r = h->mem.alloc_n(&h->d_x, (size_t)h->max_n)) || (r = h->mem.alloc_n(&h->d_y, (size_t)max_frames * M))) return r;
-    CSDR_HIP(hipStreamSynchronize(nullptr));
+        (r = h->hist.alloc_zeroed(h->mem, h->taps.size() - M / 2)) || (r = h->mem.alloc_n(&h->d_x, (size_t)h->max_n)) ||
+        (r = h->mem.alloc_n(&h->d_y, (size_t)max_frames * M))) return r;
     return h.publish(out);
 }
 int csdr_pfbch2_open_kaiser(uint32_t M, uint32_t m, float as_db, float fc, uint32_t max_frames, csdr_pfbch2 **out)
 {
-    if (!pfbch2_design_args_ok(M, m, as_db, fc)) return pfbch2_bad_design();
+    if (!pfbch2_design_args_ok(M, m, as_db, fc)) return pfb2_bad_design("pfbch2");
     const std::vector<float> t = design_pfb2_taps(M, m, as_db, fc);
     return csdr_pfbch2_open_taps(t.data(), M, m, max_frames, out);
 }
@@ -1206,31 +1152,14 @@ int csdr_pfbch2_process(csdr_pfbch2 *h, const float *x, uint32_t n, float *y, ui
 }
 int csdr_pfbch2_rewind(csdr_pfbch2 *h)
 {
-    if (!h) return CSDR_ERR_INVALID;
-    DevGuard guard(h->device);
-    CSDR_HIP(hipDeviceSynchronize());
-    if (int r = h->hist.reset(nullptr)) return r;
-    CSDR_HIP(hipStreamSynchronize(nullptr));
-    h->parity = 0;
-    return CSDR_OK;
+    return block_reset(h, [&] { const int r = h->hist.reset(nullptr); if (!r) h->parity = 0; return r; });
 }
-int csdr_pfbch2_get_taps(const csdr_pfbch2 *h, float *taps)
-{
-    if (!h || !taps) return block_null_arg("pfbch2");
-    std::memcpy(taps, h->taps.data(), sizeof(float) * h->taps.size());
-    return CSDR_OK;
-}
+int csdr_pfbch2_get_taps(const csdr_pfbch2 *h, float *taps) { return pfb2_get_taps("pfbch2", h, taps); }
 
 // ---------------------------------------------------------------------------
 // firpfbch2Synthesizer: the synthesizer side of liquid's firpfbch2_crcf, the way back from csdr_pfbch2's rows.
 // Names as csdr_pfbch2's: `open` and `rewind`; the design and launch-shape functions need no GPU
 // ---------------------------------------------------------------------------
-static int pfbsyn2_bad_design()
-{
-    set_error("pfbsyn2: bad arguments (M a power of two in [%u, %u], m in [1, %u], As > 0, fc = 0 or in (0, 0.5), finite)", PFB2_MIN_M,
-              PFB2_MAX_M, PFB2_MAX_SEMI);
-    return CSDR_ERR_INVALID;
-}
 // design_pfb2_taps with the synthesizer's rule for fc = 0: 0.5 / M, half the analyzer's cutoff
 static std::vector<float> pfbsyn2_taps(uint32_t M, uint32_t m, float as_db, float fc)
 {
@@ -1238,18 +1167,14 @@ static std::vector<float> pfbsyn2_taps(uint32_t M, uint32_t m, float as_db, floa
 }
 int csdr_pfbsyn2_design(uint32_t M, uint32_t m, float as_db, float fc, float *g)
 {
-    if (!g || !pfbch2_design_args_ok(M, m, as_db, fc)) return pfbsyn2_bad_design();
+    if (!g || !pfbch2_design_args_ok(M, m, as_db, fc)) return pfb2_bad_design("pfbsyn2");
     const std::vector<float> t = pfbsyn2_taps(M, m, as_db, fc);
     std::memcpy(g, t.data(), sizeof(float) * 2 * M * m);
     return CSDR_OK;
 }
 int csdr_pfbsyn2_launch_shape(uint32_t M, uint32_t m, uint32_t frames, uint32_t cus, uint32_t *shape)
 {
-    if (!shape || !pfb2_args_ok(M, m) || !cus) { set_error("pfbsyn2_launch_shape: bad arguments (M, m as for the block, cus >= 1, shape)"); return CSDR_ERR_INVALID; }
-    const Pfb2Shape s = pfb2s_shape(M, m, frames, cus);
-    const uint32_t v[6] = {s.F, s.tiles, s.tiles_per_run, s.runs, s.wgs_per_cu, (uint32_t)s.lds};
-    std::memcpy(shape, v, sizeof(v));
-    return CSDR_OK;
+    return pfb2_launch_shape("pfbsyn2", pfb2s_shape, M, m, frames, cus, shape);
 }
 }  // extern "C"
 struct csdr_pfbsyn2 {
@@ -1260,29 +1185,20 @@ extern "C" {
 int csdr_pfbsyn2_destroy(csdr_pfbsyn2 *h) { return block_destroy(h); }
 int csdr_pfbsyn2_open_taps(const float *taps, uint32_t M, uint32_t m, uint32_t max_frames, csdr_pfbsyn2 **out)
 {
-    bool ok = out && taps && pfb2_args_ok(M, m) && max_frames && (uint64_t)max_frames * M <= (1ull << 31);
-    for (uint32_t i = 0; ok && i < 2 * M * m; i++) ok = std::isfinite(taps[i]);
-    if (!ok) {
-        set_error("pfbsyn2: bad arguments (finite taps, M a power of two in [%u, %u], m in [1, %u], 1 <= max_frames <= 2^31 / M)", PFB2_MIN_M,
-                  PFB2_MAX_M, PFB2_MAX_SEMI);
-        return CSDR_ERR_INVALID;
-    }
+    int r = pfb2_check_open("pfbsyn2", out, taps, M, m, max_frames); if (r) return r;
     NewBlock<csdr_pfbsyn2> h;
-    int r = h.open(); if (r) return r;
-    int cus = 256;
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device);
-    h->M = M; h->m = m; h->max_n = max_frames; h->cus = (uint32_t)cus;
+    if ((r = h.open())) return r;
+    h->M = M; h->m = m; h->max_n = max_frames; h->cus = block_cu_count(h->device);
     h->taps.assign(taps, taps + 2 * M * m);
     const std::vector<float2> tw = pfb2_twiddles(M);
     if ((r = block_upload(h->mem, &h->d_g, taps, h->taps.size())) || (r = block_upload(h->mem, &h->d_tw, tw.data(), tw.size())) ||
-        (r = h->hist.alloc(h->mem, (size_t)M * pfb2s_halo_frames(m))) || (r = h->hist.reset(nullptr)) ||
-        (r = h->mem.alloc_n(&h->d_y, (size_t)max_frames * M)) || (r = h->mem.alloc_n(&h->d_x, (size_t)max_frames * (M / 2)))) return r;
-    CSDR_HIP(hipStreamSynchronize(nullptr));
+        (r = h->hist.alloc_zeroed(h->mem, (size_t)M * pfb2s_halo_frames(m))) || (r = h->mem.alloc_n(&h->d_y, (size_t)max_frames * M)) ||
+        (r = h->mem.alloc_n(&h->d_x, (size_t)max_frames * (M / 2)))) return r;
     return h.publish(out);
 }
 int csdr_pfbsyn2_open_kaiser(uint32_t M, uint32_t m, float as_db, float fc, uint32_t max_frames, csdr_pfbsyn2 **out)
 {
-    if (!pfbch2_design_args_ok(M, m, as_db, fc)) return pfbsyn2_bad_design();
+    if (!pfbch2_design_args_ok(M, m, as_db, fc)) return pfb2_bad_design("pfbsyn2");
     const std::vector<float> t = pfbsyn2_taps(M, m, as_db, fc);
     return csdr_pfbsyn2_open_taps(t.data(), M, m, max_frames, out);
 }
@@ -1313,20 +1229,9 @@ int csdr_pfbsyn2_process(csdr_pfbsyn2 *h, const float *y, uint32_t frames, float
 }
 int csdr_pfbsyn2_rewind(csdr_pfbsyn2 *h)
 {
-    if (!h) return CSDR_ERR_INVALID;
-    DevGuard guard(h->device);
-    CSDR_HIP(hipDeviceSynchronize());
-    if (int r = h->hist.reset(nullptr)) return r;
-    CSDR_HIP(hipStreamSynchronize(nullptr));
-    h->parity = 0; h->seen = 0;
-    return CSDR_OK;
+    return block_reset(h, [&] { const int r = h->hist.reset(nullptr); if (!r) h->parity = h->seen = 0; return r; });
 }
-int csdr_pfbsyn2_get_taps(const csdr_pfbsyn2 *h, float *taps)
-{
-    if (!h || !taps) return block_null_arg("pfbsyn2");
-    std::memcpy(taps, h->taps.data(), sizeof(float) * h->taps.size());
-    return CSDR_OK;
-}
+int csdr_pfbsyn2_get_taps(const csdr_pfbsyn2 *h, float *taps) { return pfb2_get_taps("pfbsyn2", h, taps); }
 uint32_t csdr_pfbsyn2_delay(const csdr_pfbsyn2 *h) { return h ? 2 * h->M * h->m - h->M / 2 + 1 : 0; }
 
 // ---------------------------------------------------------------------------
@@ -1381,19 +1286,16 @@ int csdr_rowresamp_open(double rate, uint32_t m, float as_db, float fc, int32_t 
     }
     NewBlock<csdr_rowresamp> h;
     int r = h.open(); if (r) return r;
-    int cus = 256;
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device);
     h->design = design_rowresamp(rate, m, as_db, fc);
-    h->m = m; h->nchan = nchan; h->max_n = max_samples; h->cus = (uint32_t)cus; h->cplx = is_complex != 0; h->delta = h->design.delta;
+    h->m = m; h->nchan = nchan; h->max_n = max_samples; h->cus = block_cu_count(h->device); h->cplx = is_complex != 0; h->delta = h->design.delta;
     const uint32_t P = h->design.P;
     std::vector<float> bank_t((size_t)RRS_BANK_STRIDE * P, 0.f);                             // the kernel's [j][column(b)] image
     for (uint32_t b = 0; b <= RRS_NPFB; b++)
         for (uint32_t j = 0; j < P; j++) bank_t[(size_t)j * RRS_BANK_STRIDE + rrs_bank_col(b)] = h->design.bank[(size_t)b * P + j];
     if ((r = block_upload(h->mem, &h->d_bank, bank_t.data(), bank_t.size())) ||
-        (r = h->hist.alloc(h->mem, (size_t)nchan * (P - 1) * h->elem())) || (r = h->hist.reset(nullptr)) ||
+        (r = h->hist.alloc_zeroed(h->mem, (size_t)nchan * (P - 1) * h->elem())) ||
         (r = h->mem.alloc_n(&h->d_x, (size_t)nchan * max_samples * h->elem())) ||
         (r = h->mem.alloc_n(&h->d_y, (size_t)nchan * h->max_out(max_samples) * h->elem()))) return r;
-    CSDR_HIP(hipStreamSynchronize(nullptr));
     return h.publish(out);
 }
 uint32_t csdr_rowresamp_max_out(const csdr_rowresamp *h, uint32_t n) { return h && n <= h->max_n ? h->max_out(n) : 0; }
@@ -1432,13 +1334,7 @@ int csdr_rowresamp_process(csdr_rowresamp *h, const float *x, uint32_t n, float 
 }
 int csdr_rowresamp_rewind(csdr_rowresamp *h)
 {
-    if (!h) return CSDR_ERR_INVALID;
-    DevGuard guard(h->device);
-    CSDR_HIP(hipDeviceSynchronize());
-    if (int r = h->hist.reset(nullptr)) return r;
-    CSDR_HIP(hipStreamSynchronize(nullptr));
-    h->T = 0;
-    return CSDR_OK;
+    return block_reset(h, [&] { const int r = h->hist.reset(nullptr); if (!r) h->T = 0; return r; });
 }
 int csdr_rowresamp_get_design(const csdr_rowresamp *h, uint32_t *taps_per_phase, uint64_t *delta, uint32_t *delay, float *bank)
 {

@@ -5,6 +5,7 @@
 #include "csdr_internal.h"
 
 #include <cmath>
+#include <initializer_list>
 #include <new>
 
 namespace csdr {
@@ -73,6 +74,21 @@ template <class H> int block_destroy(H *h)
     return CSDR_OK;
 }
 
+// every csdr_<block>_reset / _rewind: NULL is refused, and the handle's device is selected while block_idle_run puts the state back
+template <class Body> int block_idle_run(Body body)
+{
+    CSDR_HIP(hipDeviceSynchronize());                     // nothing of the caller's is still running on the state
+    if (int r = body()) return r;
+    CSDR_HIP(hipStreamSynchronize(nullptr));              // what body() queued is done before a stream of the caller's goes on
+    return CSDR_OK;
+}
+template <class H, class Body> int block_reset(H *h, Body body)
+{
+    if (!h) return CSDR_ERR_INVALID;
+    DevGuard guard(h->device);
+    return block_idle_run(body);
+}
+
 // A handle under construction: open() (behind the create's argument checks) finds the device (want, or -1: the current one) and
 // makes the handle, publish() hands it to the caller.  Leaving the create on any other way, a CSDR_HIP included, destroys the
 // handle and what it owns
@@ -110,8 +126,8 @@ template <class T> int block_zeros(DeviceBuffers &mem, T **d, size_t n)
     return CSDR_OK;
 }
 
-// State a kernel carries from one call to the next as two arrays of n elements owned by mem: a call reads in() and writes out(),
-// flip() behind the launch makes its output the next call's input
+// State a kernel carries from one call to the next as two arrays of n elements owned by mem (n may be 0): a call reads in() and
+// writes the whole of out(), flip() behind the successful launch makes its output the next call's input
 template <class T> struct PingPong {
     int alloc(DeviceBuffers &mem, size_t n_)
     {
@@ -119,18 +135,37 @@ template <class T> struct PingPong {
         int r = mem.alloc_n(&side[0], n);
         return r ? r : mem.alloc_n(&side[1], n);
     }
+    int alloc_zeroed(DeviceBuffers &mem, size_t n_)      // a create's: the state of reset(), in place when the create returns
+    {
+        int r = alloc(mem, n_);
+        if (r || (r = reset(nullptr))) return r;
+        CSDR_HIP(hipStreamSynchronize(nullptr));
+        return CSDR_OK;
+    }
     int reset(hipStream_t s)             // zeros on both sides, back to side 0
     {
         cur = 0;
-        for (T *p : side) CSDR_HIP(hipMemsetAsync(p, 0, sizeof(T) * n, s));
+        for (T *p : side)
+            if (n) CSDR_HIP(hipMemsetAsync(p, 0, sizeof(T) * n, s));
         return CSDR_OK;
     }
     const T *in() const { return side[cur]; }
     T *out() const { return side[cur ^ 1]; }
     void flip() { cur ^= 1; }
+    int flip_behind(int r) { if (!r) flip(); return r; }        // r: what the launch returned; a refused one leaves the state alone
 private:
     T *side[2] = {nullptr, nullptr}; size_t n = 0; int cur = 0;
 };
+
+// the size of a call that a create takes for max_samples == 0
+inline uint32_t block_max_n(uint32_t max_samples, uint32_t dflt = 4096) { return max_samples ? max_samples : dflt; }
+// the CU count that a launch shape is sized by (256 where the device does not say)
+inline uint32_t block_cu_count(int device)
+{
+    int cus = 256;
+    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
+    return (uint32_t)cus;
+}
 
 inline int block_null_arg(const char *name) { set_error("%s: null argument", name); return CSDR_ERR_INVALID; }
 inline int block_check_n(const char *name, uint32_t n, uint32_t max_n)
@@ -151,17 +186,33 @@ inline int block_select(const char *name, DevGuard &guard, int device)
     if (!guard.ok) { set_error("%s: cannot select device %d", name, device); return CSDR_ERR_HIP; }
     return CSDR_OK;
 }
-// the host round trip on the handle's device: x -> d_in, run() (the device entry point or the launch), d_out -> y
+// a buffer that the first host call that wants it allocates, on the handle's device
+template <class T> int block_lazy_alloc(const char *name, int device, DeviceBuffers &mem, T **d, size_t n)
+{
+    if (*d) return CSDR_OK;
+    DevGuard guard;
+    int r = block_select(name, guard, device);
+    return r ? r : mem.alloc_n(d, n);
+}
+// the host call on the handle's device: x -> d_in, run() (the device entry point or the launch), then every out that has a
+// destination and bytes; block_round_trip is the call with one output
+struct BlockOut { void *dst; const void *src; size_t bytes; };
+template <class Run>
+int block_host_call(const char *name, int device, void *d_in, const void *x, size_t in_bytes, Run run, std::initializer_list<BlockOut> outs)
+{
+    DevGuard guard;
+    int r = block_select(name, guard, device); if (r) return r;
+    if (in_bytes) CSDR_HIP(hipMemcpy(d_in, x, in_bytes, hipMemcpyHostToDevice));
+    if ((r = run())) return r;
+    for (const BlockOut &o : outs)
+        if (o.dst && o.bytes) CSDR_HIP(hipMemcpy(o.dst, o.src, o.bytes, hipMemcpyDeviceToHost));
+    return CSDR_OK;
+}
 template <class Run>
 int block_round_trip(const char *name, int device, void *d_in, const void *x, size_t in_bytes, const void *d_out, void *y,
                      size_t out_bytes, Run run)
 {
-    DevGuard guard;
-    int r = block_select(name, guard, device); if (r) return r;
-    CSDR_HIP(hipMemcpy(d_in, x, in_bytes, hipMemcpyHostToDevice));
-    if ((r = run())) return r;
-    CSDR_HIP(hipMemcpy(y, d_out, out_bytes, hipMemcpyDeviceToHost));
-    return CSDR_OK;
+    return block_host_call(name, device, d_in, x, in_bytes, run, {{y, d_out, out_bytes}});
 }
 
 }  // namespace
