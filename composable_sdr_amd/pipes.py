@@ -6,6 +6,9 @@ array to one array, `done` destroys it -- exactly the life-cycle addPipe/unPipe 
 Names follow the reference: dcBlocker, mixDown, mixUp, automaticGainControl,
 fmDemodulator, firpfbchChannelizer.  `Chain` is the fused replacement for
 `mix . mux (replicate nch demod) . firpfbchChannelizer nc` (apps/SoapySDR.hs:218-225).
+
+Every block that works on `nchan` rows takes its arrays through `_rows`, the one place that says how a caller's array is read
+as [nchan][n] and how long the output rows are.  Device entry points take raw device pointers and streams as plain integers.
 """
 import ctypes as C
 from dataclasses import dataclass
@@ -101,15 +104,79 @@ def _method_pipe(make, method="process"):
     return Pipe(make, lambda r, a: getattr(r, method)(a), lambda r: r.close())
 
 
+def _rows(block, a, dtype, nchan, out_dtype=None, out_len=None, plane=False, strict=False):
+    """The one row marshaller: the caller's array `a` as contiguous `dtype` rows [nchan][n] -> (x, n, y), y the uninitialised
+    output of `out_dtype` (default: `dtype`) with `out_len(n)` (default: n) elements per row.  A flat array is rows of
+    size // nchan; a size that is no multiple of nchan is refused before anything is called (`strict`: so is an array that is
+    neither flat nor [nchan][n]).  y is [nchan][out_len(n)] for `plane`, else laid out as the caller laid out `a`"""
+    x = np.ascontiguousarray(a, dtype=dtype)
+    if x.size % nchan or (strict and (x.ndim > 2 or (x.ndim == 2 and x.shape[0] != nchan))):
+        raise CsdrError(_lib.ERR_INVALID, f"{block}: a chunk of shape {x.shape}, not [{nchan}][n]")
+    n = x.size // nchan
+    m = n if out_len is None else out_len(n)
+    if plane:
+        shape = (nchan, m)
+    elif out_len is None:
+        shape = x.shape
+    else:
+        shape = x.shape[:-1] + (m,) if x.ndim > 1 else (nchan * m,)
+    return x, n, np.empty(shape, dtype=out_dtype or dtype)
+
+
+def _row_pipe(block, args, dtype, out_dtype, nchan=1, out_len=None, entry="process"):
+    """a function-style Pipe over csdr_<block>_<entry>(h, x, n, y) on `nchan` rows: the first-generation blocks"""
+    def process(r, a):
+        x, n, y = _rows(block, a, dtype, nchan, out_dtype, out_len)
+        check(getattr(lib(), f"csdr_{block}_{entry}")(r.h, _ptr(x), n, _ptr(y)))
+        return y
+    return _handle_pipe(block, args, process)
+
+
+def _split_rows(y, counts, a):
+    """(y [nchan][n], counts [nchan]) -> the list of nchan arrays y[c, :counts[c]], or the one array when the caller's `a` is [n]"""
+    out = [y[c, :counts[c]] for c in range(len(counts))]
+    return out[0] if np.ndim(a) == 1 else out
+
+
+def _channel_list(process, a):
+    """what a channelizer Pipe yields for the chunk `a`: the rows of process(x) as a list; [empty] for an empty chunk"""
+    x = _c64(a)
+    return list(process(x)) if x.size else [np.empty(0, dtype=np.complex64)]
+
+
+def _sized(fn, args, sizes, alloc):
+    """A two-call getter: fn(*args, *&sizes, NULL) reports the sizes (None: not asked for), fn(*args, NULL .., buffer) fills the
+    buffer that `alloc` makes from them.  Returns the buffer"""
+    check(fn(*args, *[None if s is None else C.byref(s) for s in sizes], None))
+    buf = alloc(*[s.value for s in sizes if s is not None])
+    check(fn(*args, *[None] * len(sizes), _ptr(buf)))
+    return buf
+
+
 class _Owner:
     """Base of the classes that own one native csdr_<_block> handle in `_h`: `h` refuses a closed object, `close` is idempotent"""
     _block = None
+
+    @classmethod
+    def _adopt(cls, handle, *state):
+        """an object of this class around a handle that is already made (the alternate constructors); `state` goes to _state"""
+        self = cls.__new__(cls)
+        self._h = handle
+        self._state(*state)
+        return self
 
     @property
     def h(self):
         if not self._h.h:
             raise CsdrError(_lib.ERR_INVALID, f"{self._block} already destroyed")
         return self._h.h
+
+    def _get(self, entry, *args):
+        """csdr_<_block>_<entry>(h, *args)"""
+        return getattr(lib(), f"csdr_{self._block}_{entry}")(self.h, *args)
+
+    def _call(self, entry, *args):
+        check(self._get(entry, *args))
 
     def close(self):
         self._h.close()
@@ -119,82 +186,49 @@ class _Resettable(_Owner):
     """... whose C ABI has csdr_<_block>_reset"""
 
     def reset(self):
-        check(getattr(lib(), f"csdr_{self._block}_reset")(self.h))
+        self._call("reset")
 
 
 def dcBlocker(alpha=0.0005, max_samples=1 << 20):
     """dcBlocker (Liquid.chs:575-589): iirfilt_crcf_create_dc_blocker(0.0005)."""
-    def process(r, a):
-        x = _c64(a)
-        y = np.empty_like(x)
-        check(lib().csdr_dcblock_process(r.h, _ptr(x), x.size, _ptr(y)))
-        return y
-    return _handle_pipe("dcblock", (alpha, max_samples), process)
-
-
-def _mixer(f, up, max_samples):
-    def process(r, a):
-        x = _c64(a)
-        y = np.empty_like(x)
-        fn = lib().csdr_nco_mix_up if up else lib().csdr_nco_mix_down
-        check(fn(r.h, _ptr(x), x.size, _ptr(y)))
-        return y
-    return _handle_pipe("nco", (f, max_samples), process)
+    return _row_pipe("dcblock", (alpha, max_samples), np.complex64, np.complex64)
 
 
 def mixDown(f, max_samples=1 << 20):
     """mixDown f (Liquid.chs:798-799): y = x * conj(nco)."""
-    return _mixer(f, False, max_samples)
+    return _row_pipe("nco", (f, max_samples), np.complex64, np.complex64, entry="mix_down")
 
 
 def mixUp(f, max_samples=1 << 20):
     """mixUp f (Liquid.chs:808-809): y = x * nco."""
-    return _mixer(f, True, max_samples)
+    return _row_pipe("nco", (f, max_samples), np.complex64, np.complex64, entry="mix_up")
 
 
 def automaticGainControl(tres, nchan=1, max_samples=4096):
     """automaticGainControl tres (Liquid.chs:727-728); nchan independent instances, input
     and output channel-major [nchan][n] (1-D arrays are treated as one channel)."""
-    def process(r, a):
-        x = _c64(a)
-        n = x.size // nchan
-        y = np.empty_like(x)
-        check(lib().csdr_agc_process(r.h, _ptr(x), n, _ptr(y)))
-        return y
-    return _handle_pipe("agc", (tres, nchan, max_samples), process)
+    return _row_pipe("agc", (tres, nchan, max_samples), np.complex64, np.complex64, nchan)
 
 
 def fmDemodulator(kf, nchan=1, max_samples=4096):
     """fmDemodulator kf (Liquid.chs:333-334)."""
-    def process(r, a):
-        x = _c64(a)
-        n = x.size // nchan
-        m = np.empty(x.shape, dtype=np.float32)
-        check(lib().csdr_freqdem_process(r.h, _ptr(x), n, _ptr(m)))
-        return m
-    return _handle_pipe("freqdem", (kf, nchan, max_samples), process)
+    return _row_pipe("freqdem", (kf, nchan, max_samples), np.complex64, np.float32, nchan)
 
 
 def iirFilter(n, fc, f0=0.0, ap=10.0, as_db=10.0, nchan=1, max_samples=4096):
     """iirFilter n fc f0 ap as (Liquid.chs:629-638): real-valued Butterworth low-pass (order 2 is what the
     reference instantiates, as the WBFM de-emphasis)."""
-    def process(r, a):
-        x = np.ascontiguousarray(a, dtype=np.float32)
-        y = np.empty_like(x)
-        check(lib().csdr_iirfilt_process(r.h, _ptr(x), x.size // nchan, _ptr(y)))
-        return y
-    return _handle_pipe("iirfilt", (n, fc, f0, ap, as_db, nchan, max_samples), process)
+    return _row_pipe("iirfilt", (n, fc, f0, ap, as_db, nchan, max_samples), np.float32, np.float32, nchan)
 
 
 def firDecimator(m, nchan=1, max_samples=4096):
     """firDecimator m (Liquid.chs:500-501): Kaiser decimator (semi-length 10, 60 dB), n div m samples out."""
-    def process(r, a):
-        x = np.ascontiguousarray(a, dtype=np.float32)
-        n = x.size // nchan
-        y = np.empty(x.shape[:-1] + (n // m,) if x.ndim > 1 else (n // m,), dtype=np.float32)
-        check(lib().csdr_firdecim_process(r.h, _ptr(x), n, _ptr(y)))
-        return y
-    return _handle_pipe("firdecim", (m, nchan, max_samples), process)
+    return _row_pipe("firdecim", (m, nchan, max_samples), np.float32, np.float32, nchan, lambda n: n // m)
+
+
+def amDemodulator(nchan=1, max_samples=4096, mod_index=0.8):
+    """amDemodulator (Liquid.chs:468-469): ampmodem_create 0.8 DSB, carrier present."""
+    return _row_pipe("ampdem", (mod_index, nchan, max_samples), np.complex64, np.float32, nchan)
 
 
 def wbFMDemodulator(quadRate, decim, max_samples=4096):
@@ -202,6 +236,17 @@ def wbFMDemodulator(quadRate, decim, max_samples=4096):
     return compose(firDecimator(decim, max_samples=max_samples),
                    compose(iirFilter(2, 5000.0 / quadRate, 0.0, 10.0, 10.0, max_samples=max_samples),
                            fmDemodulator(0.6, max_samples=max_samples)))
+
+
+def resampler(r, as_db=60.0, max_samples=1 << 20):
+    """resampler r as (Liquid.chs:115-117): Pipe IO (Array CF32) (Array CF32) with a variable-length output
+    (`shrinkToFit` to the count msresamp_crcf_execute reports, :79-98).  r == 0 is the identity."""
+    def process(rh, a):
+        x, n, y = _rows("resamp", a, np.complex64, 1, out_len=lambda n: int(lib().csdr_resamp_max_out(rh.h, n)))
+        n_out = C.c_uint32()
+        check(lib().csdr_resamp_process(rh.h, _ptr(x), n, _ptr(y), C.byref(n_out)))
+        return y.reshape(-1)[:n_out.value].copy()
+    return _handle_pipe("resamp", (r, as_db, max_samples), process)
 
 
 class FmStereo(_Resettable):
@@ -214,38 +259,35 @@ class FmStereo(_Resettable):
 
     @property
     def delay(self):
-        return int(lib().csdr_fmstereo_get_delay(self.h))
+        return int(self._get("get_delay"))
 
     @property
     def taps_len(self):
-        return int(lib().csdr_fmstereo_get_taps_len(self.h))
+        return int(self._get("get_taps_len"))
 
     def pll(self, chan=0):
         th, d = C.c_uint32(), C.c_uint32()
-        check(lib().csdr_fmstereo_get_pll(self.h, chan, C.byref(th), C.byref(d)))
+        self._call("get_pll", chan, C.byref(th), C.byref(d))
         return th.value, d.value
 
     def process(self, mpx):
         """[nchan][n] (or [n] for one stream) F32 -> [nchan][2 (n // decim)] (or [2 (n // decim)]) interleaved L, R."""
-        x = np.ascontiguousarray(mpx, dtype=np.float32)
-        n = x.size // self.nchan
-        y = np.empty(x.shape[:-1] + (2 * (n // self.decim),), dtype=np.float32)
+        x, n, y = _rows("fmstereo", mpx, np.float32, self.nchan, out_len=lambda n: 2 * (n // self.decim))
         n_out = C.c_uint32()
-        check(lib().csdr_fmstereo_process(self.h, _ptr(x), n, _ptr(y), C.byref(n_out)))
+        self._call("process", _ptr(x), n, _ptr(y), C.byref(n_out))
         assert n_out.value == y.size, (n_out.value, y.size)
         return y
 
     def process_device(self, d_mpx_ptr, n, d_lr_ptr, stream=0):
         """Device-resident variant: raw device pointers (ints), enqueues on `stream`; returns the element count."""
         n_out = C.c_uint32()
-        check(lib().csdr_fmstereo_process_device(self.h, C.c_void_p(d_mpx_ptr), n, C.c_void_p(d_lr_ptr), C.byref(n_out),
-                                                 C.c_void_p(stream)))
+        self._call("process_device", d_mpx_ptr, n, d_lr_ptr, C.byref(n_out), stream)
         return n_out.value
 
     def kernel_times(self):
         """us of the last call's front, pll, back, deemph, decim kernels (needs CSDR_DIAG=1 CSDR_FMS_TIME=1 at create)"""
         t = (C.c_float * 5)()
-        check(lib().csdr_fmstereo_kernel_times(self.h, t))
+        self._call("kernel_times", t)
         return list(t)
 
 
@@ -278,66 +320,57 @@ class SymSync(_Resettable):
 
     @property
     def taps_len(self):
-        return int(lib().csdr_symsync_get_taps_len(self.h))
+        return int(self._get("get_taps_len"))
 
     def taps(self):
         """(mf, dmf), each [h_sub_len][npfb] as the kernel holds them"""
         L = self.taps_len
         mf, dmf = np.empty((L, self.npfb), np.float32), np.empty((L, self.npfb), np.float32)
-        check(lib().csdr_symsync_get_taps(self.h, _ptr(mf), _ptr(dmf)))
+        self._call("get_taps", _ptr(mf), _ptr(dmf))
         return mf, dmf
 
     def state(self, chan=0):
         """(tau, rate, del, q_hat) of stream `chan`; raises CsdrError (ERR_SIZE) when the stream is faulted"""
         v = [C.c_float() for _ in range(4)]
-        check(lib().csdr_symsync_get_state(self.h, chan, *[C.byref(a) for a in v]))
+        self._call("get_state", chan, *[C.byref(a) for a in v])
         return tuple(np.float32(a.value) for a in v)
+
+    def _sync(self, entry, x, dtype):
+        x, n, y = _rows("symsync", x, dtype, self.nchan, plane=True)
+        ny = np.zeros(self.nchan, dtype=np.uint32)
+        self._call(entry, _ptr(x), n, _ptr(y), ny.ctypes.data_as(C.POINTER(C.c_uint32)))
+        return y, ny
 
     def process_rows(self, x):
         """[nchan][n] (or [n]) F32 -> (y [nchan][n], counts [nchan]): row c holds counts[c] outputs"""
-        x = np.ascontiguousarray(x, dtype=np.float32)
-        n = x.size // self.nchan
-        y = np.empty((self.nchan, n), dtype=np.float32)
-        ny = np.zeros(self.nchan, dtype=np.uint32)
-        check(lib().csdr_symsync_process(self.h, _ptr(x), n, _ptr(y), ny.ctypes.data_as(C.POINTER(C.c_uint32))))
-        return y, ny
+        return self._sync("process", x, np.float32)
 
     def process(self, x):
         """[nchan][n] -> a list of nchan arrays (their lengths vary); [n] -> one array"""
-        y, ny = self.process_rows(x)
-        out = [y[c, :ny[c]] for c in range(self.nchan)]
-        return out[0] if np.ndim(x) == 1 else out
+        return _split_rows(*self.process_rows(x), x)
 
     def process_device(self, d_x_ptr, n, d_y_ptr, d_ny_ptr, stream=0):
         """Device-resident variant: raw device pointers (ints) for x [nchan][n], y [nchan][n], counts [nchan]; enqueues on
         `stream`"""
-        check(lib().csdr_symsync_process_device(self.h, C.c_void_p(d_x_ptr), n, C.c_void_p(d_y_ptr), C.c_void_p(d_ny_ptr),
-                                                C.c_void_p(stream)))
-
+        self._call("process_device", d_x_ptr, n, d_y_ptr, d_ny_ptr, stream)
 
     def set_taps(self, H):
         """symsync_create(k, npfb, H, H_len): new banks from the prototype H (2 npfb k m + 1 taps); the state as after create"""
         H = np.ascontiguousarray(H, dtype=np.float32).reshape(-1)
-        check(lib().csdr_symsync_set_taps(self.h, _ptr(H), H.size))
+        self._call("set_taps", _ptr(H), H.size)
 
     def set_rnyquist(self, ftype, beta):
         """symsync_create_rnyquist(ftype, k, m, beta, npfb): firdes_rnyquist(ftype, k npfb, m, beta) as the prototype"""
-        check(lib().csdr_symsync_set_rnyquist(self.h, int(ftype), float(beta)))
+        self._call("set_rnyquist", int(ftype), float(beta))
 
     def process_c(self, x):
         """[nchan][n] (or [n]) complex64 -> (y complex64 [nchan][n], counts [nchan]): row c holds counts[c] outputs"""
-        x = _c64(x)
-        n = x.size // self.nchan
-        y = np.empty((self.nchan, n), dtype=np.complex64)
-        ny = np.zeros(self.nchan, dtype=np.uint32)
-        check(lib().csdr_symsync_process_c(self.h, _ptr(x), n, _ptr(y), ny.ctypes.data_as(C.POINTER(C.c_uint32))))
-        return y, ny
+        return self._sync("process_c", x, np.complex64)
 
     def process_c_device(self, d_x_ptr, n, d_y_ptr, d_ny_ptr, stream=0):
         """Device-resident variant of process_c: raw device pointers (ints) for x, y [nchan][n] CF32 and counts [nchan];
         enqueues on `stream`"""
-        check(lib().csdr_symsync_process_c_device(self.h, C.c_void_p(d_x_ptr), n, C.c_void_p(d_y_ptr), C.c_void_p(d_ny_ptr),
-                                                  C.c_void_p(stream)))
+        self._call("process_c_device", d_x_ptr, n, d_y_ptr, d_ny_ptr, stream)
 
 
 def _symsyncc(m, k, nchan, max_samples):
@@ -350,17 +383,11 @@ def _symsyncc(m, k, nchan, max_samples):
     return s
 
 
-def _symsyncc_process(r, a):
-    y, ny = r.process_c(a)
-    out = [y[c, :ny[c]] for c in range(r.nchan)]
-    return out[0] if np.ndim(a) == 1 else out
-
-
 def symSyncC(m, k, nchan=1, max_samples=1 << 16):
     """symSyncC m k (Liquid.chs:177-242: symsync_crcf_create_rnyquist(ARKAISER, k, m, 0.5, 32), lf_bw 0.01 and output rate 1
     left at symsync_create's defaults) as a Pipe from complex64 arrays ([nchan][n], or [n]) to the synchronised symbols: a
     list of per-stream arrays, or one array for [n].  It composes behind firpfbchChannelizer's rows"""
-    return Pipe(lambda: _symsyncc(m, k, nchan, max_samples), _symsyncc_process, lambda r: r.close())
+    return Pipe(lambda: _symsyncc(m, k, nchan, max_samples), lambda r, a: _split_rows(*r.process_c(a), a), lambda r: r.close())
 
 
 def symSyncR(k, m=4, beta=0.0, M=64, nchan=1, max_samples=1 << 16):
@@ -370,7 +397,7 @@ def symSyncR(k, m=4, beta=0.0, M=64, nchan=1, max_samples=1 << 16):
 
 
 def fmDemWithSync(k, nchan=1, max_samples=1 << 16):
-    """fmDemWithSync k = symSyncR k 4 0 64 . fmDemodulator (0.02 * k) (Liquid.chs:431-437), the product taken in f32"""
+    """fmDemWithSync k = symSyncR k 4 0 64 . fmDemodulator (0.02 * k) (Liquid.chs:431-437), the product taken in np.float32"""
     kf = float(np.float32(0.02) * np.float32(k))
     return compose(symSyncR(k, 4, 0.0, 64, nchan, max_samples), fmDemodulator(kf, nchan, max_samples))
 
@@ -387,12 +414,12 @@ class FirHilb(_Resettable):
 
     @property
     def taps_len(self):
-        return int(lib().csdr_firhilb_get_taps_len(self.h))
+        return int(self._get("get_taps_len"))
 
     def taps(self):
         """the 2 m quadrature-branch taps hq, oldest sample first"""
         hq = np.empty(self.taps_len, np.float32)
-        check(lib().csdr_firhilb_get_taps(self.h, _ptr(hq)))
+        self._call("get_taps", _ptr(hq))
         return hq
 
     def decim(self, x):
@@ -400,23 +427,23 @@ class FirHilb(_Resettable):
         x = np.ascontiguousarray(x, dtype=np.float32).reshape(-1)
         n = x.size // 2
         y = np.empty(n, dtype=np.complex64)
-        check(lib().csdr_firhilb_decim(self.h, _ptr(x), n, _ptr(y)))
+        self._call("decim", _ptr(x), n, _ptr(y))
         return y
 
     def interp(self, x):
         """firhilbInterp (Liquid.chs:539-543): CF32 [n] -> F32 [2 n]"""
         x = _c64(x).reshape(-1)
         y = np.empty(2 * x.size, dtype=np.float32)
-        check(lib().csdr_firhilb_interp(self.h, _ptr(x), x.size, _ptr(y)))
+        self._call("interp", _ptr(x), x.size, _ptr(y))
         return y
 
     def decim_device(self, d_x_ptr, n, d_y_ptr, stream=0):
         """Device-resident variant: raw device pointers (ints) for 2 n floats in, n complex out; enqueues on `stream`"""
-        check(lib().csdr_firhilb_decim_device(self.h, C.c_void_p(d_x_ptr), n, C.c_void_p(d_y_ptr), C.c_void_p(stream)))
+        self._call("decim_device", d_x_ptr, n, d_y_ptr, stream)
 
     def interp_device(self, d_x_ptr, n, d_y_ptr, stream=0):
         """Device-resident variant: n complex in, 2 n floats out"""
-        check(lib().csdr_firhilb_interp_device(self.h, C.c_void_p(d_x_ptr), n, C.c_void_p(d_y_ptr), C.c_void_p(stream)))
+        self._call("interp_device", d_x_ptr, n, d_y_ptr, stream)
 
 
 def realToComplex(m=5, as_db=60.0, max_samples=1 << 16):
@@ -429,7 +456,28 @@ def complexToReal(m=5, as_db=60.0, max_samples=1 << 16):
     return _method_pipe(lambda: FirHilb(m, as_db, max_samples), "interp")
 
 
-class FskDem(_Owner):
+class _SymbolDem(_Owner):
+    """What FskDem and GmskDem share: `nchan` CF32 rows of n samples in, n // k uint32 symbols per row out, and on request a
+    second F32 output of `per` values per symbol (a NULL pointer: not wanted)"""
+
+    def _symbols(self, x, second, per=()):
+        x, n, sym = _rows(self._block, x, np.complex64, self.nchan, np.uint32, lambda n: n // self.k, plane=True)
+        e = np.empty(sym.shape + per, dtype=np.float32) if second else None
+        n_out = C.c_uint32()
+        self._call("process", _ptr(x), n, _ptr(sym), _ptr(e) if second else None, C.byref(n_out))
+        assert n_out.value == sym.size, (n_out.value, sym.size)
+        return (sym, e) if second else sym
+
+    def process(self, x):
+        """[nchan][n] -> symbols [nchan][n // k]; [n] -> [n // k]"""
+        sym = self.process_rows(x)
+        return sym[0] if np.ndim(x) == 1 else sym
+
+    def _device(self, d_x_ptr, n, d_sym_ptr, d_second_ptr, stream):
+        self._call("process_device", d_x_ptr, n, d_sym_ptr, d_second_ptr or None, stream)
+
+
+class FskDem(_SymbolDem):
     """The `csdr_fskdem_*` object: fskDemodulator m k bw (Liquid.chs:336-382) on `nchan` independent CF32 streams: M = 2^m
     tones, k samples per symbol (include/csdr.h, DESIGN.md 4.12).  A call of n samples per row yields n // k symbols per row
     and drops the last n % k samples; nothing is carried between calls."""
@@ -443,31 +491,17 @@ class FskDem(_Owner):
         """(K, demod_map): the transform size and the bin of each of the M tones"""
         K = C.c_uint32()
         dmap = np.empty(self.M, dtype=np.uint32)
-        check(lib().csdr_fskdem_get_design(self.h, C.byref(K), _ptr(dmap)))
+        self._call("get_design", C.byref(K), _ptr(dmap))
         return K.value, dmap
 
     def process_rows(self, x, energy=False):
         """[nchan][n] (or [n]) CF32 -> symbols [nchan][n // k] uint32, or with energy=True (symbols, E [nchan][n // k][M])"""
-        x = _c64(x)
-        n = x.size // self.nchan
-        ns = n // self.k
-        sym = np.empty((self.nchan, ns), dtype=np.uint32)
-        e = np.empty((self.nchan, ns, self.M), dtype=np.float32) if energy else None
-        n_out = C.c_uint32()
-        check(lib().csdr_fskdem_process(self.h, _ptr(x), n, _ptr(sym), _ptr(e) if energy else None, C.byref(n_out)))
-        assert n_out.value == sym.size, (n_out.value, sym.size)
-        return (sym, e) if energy else sym
-
-    def process(self, x):
-        """[nchan][n] -> symbols [nchan][n // k]; [n] -> [n // k]"""
-        sym = self.process_rows(x)
-        return sym[0] if np.ndim(x) == 1 else sym
+        return self._symbols(x, energy, (self.M,))
 
     def process_device(self, d_x_ptr, n, d_sym_ptr, d_energy_ptr=0, stream=0):
         """Device-resident variant: raw device pointers (ints) for x [nchan][n] CF32, symbols [nchan][n // k] uint32 and,
         unless 0, energies [nchan][n // k][M] F32; enqueues on `stream`"""
-        check(lib().csdr_fskdem_process_device(self.h, C.c_void_p(d_x_ptr), n, C.c_void_p(d_sym_ptr),
-                                               C.c_void_p(d_energy_ptr) if d_energy_ptr else None, C.c_void_p(stream)))
+        self._device(d_x_ptr, n, d_sym_ptr, d_energy_ptr, stream)
 
 
 def fskDemodulator(m, k, bw, nchan=1, max_samples=1 << 16):
@@ -491,49 +525,55 @@ def fir_groupdelay(h, fc):
     return gd.value
 
 
-class FirFilt(_Resettable):
+class _RowFilter(_Resettable):
+    """What FirFilt and IirSos share: `nchan` rows of CF32 (`is_complex`) or F32 samples, as many out as in"""
+
+    def _state(self, is_complex, nchan):
+        self.is_complex, self.nchan = bool(is_complex), int(nchan)
+        self.dtype = np.complex64 if self.is_complex else np.float32
+
+    def process(self, x):
+        """[nchan][n] -> [nchan][n]; [n] -> [n]"""
+        x, n, y = _rows(self._block, x, self.dtype, self.nchan)
+        self._call("process", _ptr(x), n, _ptr(y))
+        return y
+
+
+def _filter_shape(is_complex, nchan, max_samples):
+    return int(bool(is_complex)), int(nchan), int(max_samples)
+
+
+class FirFilt(_RowFilter):
     """The `csdr_firfilt_*` object: firfilt_crcf (`is_complex`, CF32 rows) or firfilt_rrrf (F32 rows) with real taps on `nchan`
     independent rows: y[t] = scale * sum_i taps[i] x[t - i], the last len(taps) - 1 samples of a row carried from call to call
     (include/csdr.h).  `FirFilt.kaiser` is firfiltCreateCKaiser (Liquid.chs:889-895)."""
     _block = "firfilt"
 
-    def __init__(self, taps, scale=1.0, is_complex=True, nchan=1, max_samples=1 << 16, _kaiser=None):
-        shape = (int(bool(is_complex)), int(nchan), int(max_samples))
-        if _kaiser is not None:
-            n, fc, as_db, mu = _kaiser
-            self._h = _new_handle("firfilt", int(n), float(fc), float(as_db), float(mu), *shape, create="create_kaiser")
-        else:
-            t = np.ascontiguousarray(taps, dtype=np.float32).reshape(-1)
-            self._h = _new_handle("firfilt", _ptr(t), t.size, float(scale), *shape, create="create_taps")
-        self.is_complex, self.nchan = bool(is_complex), int(nchan)
-        self.dtype = np.complex64 if self.is_complex else np.float32
+    def __init__(self, taps, scale=1.0, is_complex=True, nchan=1, max_samples=1 << 16):
+        t = np.ascontiguousarray(taps, dtype=np.float32).reshape(-1)
+        self._h = _new_handle("firfilt", _ptr(t), t.size, float(scale), *_filter_shape(is_complex, nchan, max_samples), create="create_taps")
+        self._state(is_complex, nchan)
 
     @classmethod
     def kaiser(cls, n, fc, as_db=60.0, mu=0.0, is_complex=True, nchan=1, max_samples=1 << 16):
         """the taps of firdes_kaiser(n, fc, as_db) and the scale 2 fc"""
-        return cls(None, is_complex=is_complex, nchan=nchan, max_samples=max_samples, _kaiser=(n, fc, as_db, mu))
+        return cls._adopt(_new_handle("firfilt", int(n), float(fc), float(as_db), float(mu), *_filter_shape(is_complex, nchan, max_samples),
+                                      create="create_kaiser"), is_complex, nchan)
 
     @property
     def taps_len(self):
-        return int(lib().csdr_firfilt_get_taps_len(self.h))
+        return int(self._get("get_taps_len"))
 
     def taps(self):
         """(taps F32 [L], scale)"""
         t = np.empty(self.taps_len, np.float32)
         s = C.c_float()
-        check(lib().csdr_firfilt_get_taps(self.h, _ptr(t), C.byref(s)))
+        self._call("get_taps", _ptr(t), C.byref(s))
         return t, np.float32(s.value)
-
-    def process(self, x):
-        """[nchan][n] -> [nchan][n]; [n] -> [n]"""
-        x = np.ascontiguousarray(x, dtype=self.dtype)
-        y = np.empty_like(x)
-        check(lib().csdr_firfilt_process(self.h, _ptr(x), x.size // self.nchan, _ptr(y)))
-        return y
 
     def process_device(self, d_x_ptr, n, d_y_ptr, stream=0):
         """Device-resident variant: raw device pointers (ints) for x and y, [nchan][n] each; enqueues on `stream`"""
-        check(lib().csdr_firfilt_process_device(self.h, C.c_void_p(d_x_ptr), n, C.c_void_p(d_y_ptr), C.c_void_p(stream)))
+        self._call("process_device", d_x_ptr, n, d_y_ptr, stream)
 
 
 def firFilterCKaiser(n, fc, as_db=60.0, mu=0.0, nchan=1, max_samples=1 << 16):
@@ -580,7 +620,7 @@ def firFilterRNyquist(k, m, beta, mu=0.0, nchan=1, max_samples=1 << 16):
     return firFilterR(firdes_gmskrx(k, m, beta), 1.0 / int(k), nchan, max_samples)
 
 
-class GmskDem(_Resettable):
+class GmskDem(_SymbolDem, _Resettable):
     """The `csdr_gmskdem_*` object: gmskdem_create(k, m, bt) (Liquid.chs:384-429; liquid's argument order) on `nchan`
     independent CF32 streams: k samples per symbol, a receive filter of 2 k m + 1 taps (firdes_gmskrx), one bit per symbol
     (include/csdr.h, DESIGN.md 4.15).  A call takes a multiple of k samples per row and yields n // k symbols per row; the last
@@ -593,34 +633,16 @@ class GmskDem(_Resettable):
 
     def design(self):
         """the receive filter's taps, F32 [2 k m + 1]"""
-        L = C.c_uint32()
-        check(lib().csdr_gmskdem_get_design(self.h, C.byref(L), None))
-        t = np.empty(L.value, dtype=np.float32)
-        check(lib().csdr_gmskdem_get_design(self.h, None, _ptr(t)))
-        return t
+        return _sized(lib().csdr_gmskdem_get_design, (self.h,), (C.c_uint32(),), lambda L: np.empty(L, dtype=np.float32))
 
     def process_rows(self, x, soft=False):
         """[nchan][n] (or [n]) CF32 -> symbols [nchan][n // k] uint32, or with soft=True (symbols, d [nchan][n // k] F32)"""
-        x = _c64(x)
-        n = x.size // self.nchan
-        ns = n // self.k
-        sym = np.empty((self.nchan, ns), dtype=np.uint32)
-        d = np.empty((self.nchan, ns), dtype=np.float32) if soft else None
-        n_out = C.c_uint32()
-        check(lib().csdr_gmskdem_process(self.h, _ptr(x), n, _ptr(sym), _ptr(d) if soft else None, C.byref(n_out)))
-        assert n_out.value == sym.size, (n_out.value, sym.size)
-        return (sym, d) if soft else sym
-
-    def process(self, x):
-        """[nchan][n] -> symbols [nchan][n // k]; [n] -> [n // k]"""
-        sym = self.process_rows(x)
-        return sym[0] if np.ndim(x) == 1 else sym
+        return self._symbols(x, soft)
 
     def process_device(self, d_x_ptr, n, d_sym_ptr, d_soft_ptr=0, stream=0):
         """Device-resident variant: raw device pointers (ints) for x [nchan][n] CF32, symbols [nchan][n // k] uint32 and,
         unless 0, soft values [nchan][n // k] F32; enqueues on `stream`"""
-        check(lib().csdr_gmskdem_process_device(self.h, C.c_void_p(d_x_ptr), n, C.c_void_p(d_sym_ptr),
-                                                C.c_void_p(d_soft_ptr) if d_soft_ptr else None, C.c_void_p(stream)))
+        self._device(d_x_ptr, n, d_sym_ptr, d_soft_ptr, stream)
 
 
 def gmskDemodulator(m, k, bw, nchan=1, max_samples=1 << 16):
@@ -640,54 +662,42 @@ def iirdes_butter_lowpass(n, fc):
     return b, a
 
 
-class IirSos(_Resettable):
+class IirSos(_RowFilter):
     """The `csdr_iirsos_*` object: a cascade of 1 .. 8 second-order sections with real coefficients on `nchan` independent rows
     of CF32 (`is_complex`, iirfilt_crcf: re and im filtered alike) or F32 samples, every section's state carried from call to
     call (include/csdr.h, DESIGN.md 4.14).  `IirSos(b, a)` takes the caller's sections ([S][3] each, divided by their a0);
     `IirSos.prototype` is iirfilt_*_create_prototype(BUTTER, LOWPASS, SOS, n, fc, ..) (Liquid.chs:594-608)."""
     _block = "iirsos"
 
-    def __init__(self, b, a, is_complex=True, nchan=1, max_samples=1 << 16, _prototype=None):
-        shape = (int(bool(is_complex)), int(nchan), int(max_samples))
-        if _prototype is not None:
-            n, fc, f0, ap, as_db = _prototype
-            self._h = _new_handle("iirsos", int(n), float(fc), float(f0), float(ap), float(as_db), *shape, create="create_prototype")
-        else:
-            b = np.ascontiguousarray(b, dtype=np.float32).reshape(-1)
-            a = np.ascontiguousarray(a, dtype=np.float32).reshape(-1)
-            if b.size != a.size or b.size % 3:
-                raise CsdrError(_lib.ERR_INVALID, "iirsos: b and a must be [S][3] each")
-            self._h = _new_handle("iirsos", _ptr(b), _ptr(a), b.size // 3, *shape, create="create_sos")
-        self.is_complex, self.nchan = bool(is_complex), int(nchan)
-        self.dtype = np.complex64 if self.is_complex else np.float32
+    def __init__(self, b, a, is_complex=True, nchan=1, max_samples=1 << 16):
+        b = np.ascontiguousarray(b, dtype=np.float32).reshape(-1)
+        a = np.ascontiguousarray(a, dtype=np.float32).reshape(-1)
+        if b.size != a.size or b.size % 3:
+            raise CsdrError(_lib.ERR_INVALID, "iirsos: b and a must be [S][3] each")
+        self._h = _new_handle("iirsos", _ptr(b), _ptr(a), b.size // 3, *_filter_shape(is_complex, nchan, max_samples), create="create_sos")
+        self._state(is_complex, nchan)
 
     @classmethod
     def prototype(cls, n, fc, f0=0.0, ap=10.0, as_db=10.0, is_complex=True, nchan=1, max_samples=1 << 16):
         """the sections of iirdes_butter_lowpass(n, fc); f0, ap and as_db are accepted and ignored"""
-        return cls(None, None, is_complex=is_complex, nchan=nchan, max_samples=max_samples, _prototype=(n, fc, f0, ap, as_db))
+        return cls._adopt(_new_handle("iirsos", int(n), float(fc), float(f0), float(ap), float(as_db),
+                                      *_filter_shape(is_complex, nchan, max_samples), create="create_prototype"), is_complex, nchan)
 
     @property
     def nsec(self):
-        return int(lib().csdr_iirsos_get_nsec(self.h))
+        return int(self._get("get_nsec"))
 
     def sos(self):
         """(b, a): F32 [S][3] each, as the handle runs them (a0 = 1)"""
         S = self.nsec
         b, a = np.empty((S, 3), np.float32), np.empty((S, 3), np.float32)
-        check(lib().csdr_iirsos_get_sos(self.h, _ptr(b), _ptr(a)))
+        self._call("get_sos", _ptr(b), _ptr(a))
         return b, a
-
-    def process(self, x):
-        """[nchan][n] -> [nchan][n]; [n] -> [n]"""
-        x = np.ascontiguousarray(x, dtype=self.dtype)
-        y = np.empty_like(x)
-        check(lib().csdr_iirsos_process(self.h, _ptr(x), x.size // self.nchan, _ptr(y)))
-        return y
 
     def process_device(self, d_x_ptr, n, d_y_ptr, stream=0):
         """Device-resident variant: raw device pointers (ints) for x and y, [nchan][n] each (the same buffer or disjoint ones);
         enqueues on `stream`"""
-        check(lib().csdr_iirsos_process_device(self.h, C.c_void_p(d_x_ptr), n, C.c_void_p(d_y_ptr), C.c_void_p(stream)))
+        self._call("process_device", d_x_ptr, n, d_y_ptr, stream)
 
 
 def iirCFilter(n, fc, f0=0.0, ap=10.0, as_db=10.0, nchan=1, max_samples=1 << 16):
@@ -705,29 +715,6 @@ def iirFilterSOS(b, a, complex=False, nchan=1, max_samples=1 << 16):
     """The caller's own second-order sections b, a ([S][3] each, S <= 8: a Chebyshev, elliptic or notch design brought from
     elsewhere) as a Pipe of F32 or (complex) CF32 arrays; a liquid iirfilt object is its sections here"""
     return _method_pipe(lambda: IirSos(b, a, complex, nchan, max_samples))
-
-
-def resampler(r, as_db=60.0, max_samples=1 << 20):
-    """resampler r as (Liquid.chs:115-117): Pipe IO (Array CF32) (Array CF32) with a variable-length output
-    (`shrinkToFit` to the count msresamp_crcf_execute reports, :79-98).  r == 0 is the identity."""
-    def process(rh, a):
-        x = _c64(a)
-        y = np.empty(int(lib().csdr_resamp_max_out(rh.h, x.size)), dtype=np.complex64)
-        n = C.c_uint32()
-        check(lib().csdr_resamp_process(rh.h, _ptr(x), x.size, _ptr(y), C.byref(n)))
-        return y[:n.value].copy()
-    return _handle_pipe("resamp", (r, as_db, max_samples), process)
-
-
-def amDemodulator(nchan=1, max_samples=4096, mod_index=0.8):
-    """amDemodulator (Liquid.chs:468-469): ampmodem_create 0.8 DSB, carrier present."""
-    def process(r, a):
-        x = _c64(a)
-        n = x.size // nchan
-        m = np.empty(x.shape, dtype=np.float32)
-        check(lib().csdr_ampdem_process(r.h, _ptr(x), n, _ptr(m)))
-        return m
-    return _handle_pipe("ampdem", (mod_index, nchan, max_samples), process)
 
 
 @dataclass
@@ -773,6 +760,7 @@ class Chain(_Resettable):
         c.device, c.max_frames, c.flags = cfg.device, cfg.max_frames, cfg.flags | (_lib.FLAG_TAIL_ONLY if cfg.tail_only else 0) | (_lib.FLAG_DFT_BACKWARD if cfg.dft_backward else 0)
         c.pfb_m, c.pfb_as = cfg.pfb_m, cfg.pfb_as
         self._h = _new_handle("chain", C.byref(c))
+        self._pending = []                              # (x, out) of the chunks between submit and collect
         self.M = cfg.channels
         self.C = cfg.channels // cfg.chan_stride if cfg.chan_stride > 1 else (cfg.chan_count or (cfg.channels - cfg.chan_first))
         self.mixed = bool(cfg.mix) and self.M > 1
@@ -781,19 +769,19 @@ class Chain(_Resettable):
 
     @property
     def path(self):
-        return lib().csdr_chain_path(self.h).decode()
+        return self._get("path").decode()
 
     @property
     def taps(self):
         n = self.M * 2 * self.cfg.pfb_m
         t = np.zeros(n, dtype=np.float32)
-        got = lib().csdr_chain_get_taps(self.h, _ptr(t), n)
+        got = self._get("get_taps", _ptr(t), n)
         return t[:max(got, 0)]
 
     @property
     def nco(self):
         th, d = C.c_uint32(), C.c_uint32()
-        check(lib().csdr_chain_get_nco(self.h, C.byref(th), C.byref(d)))
+        self._call("get_nco", C.byref(th), C.byref(d))
         return th.value, d.value
 
     def out_shape(self, n_in):
@@ -805,7 +793,7 @@ class Chain(_Resettable):
         x = _c64(x)
         out = np.empty(self.out_shape(x.size), dtype=self.out_dtype)
         n_out = C.c_uint32()
-        check(lib().csdr_chain_process(self.h, _ptr(x), x.size, _ptr(out), C.byref(n_out)))
+        self._call("process", _ptr(x), x.size, _ptr(out), C.byref(n_out))
         if x.size == 0:
             return out
         assert n_out.value == out.size, (n_out.value, out.size)
@@ -814,8 +802,7 @@ class Chain(_Resettable):
     def process_device(self, d_in_ptr, n_in, d_out_ptr, stream=0):
         """Device-resident variant: raw device pointers (ints), enqueues on `stream`."""
         n_out = C.c_uint32()
-        check(lib().csdr_chain_process_device(self.h, C.c_void_p(d_in_ptr), n_in, C.c_void_p(d_out_ptr),
-                                              C.byref(n_out), C.c_void_p(stream)))
+        check(lib().csdr_chain_process_device(self.h, d_in_ptr, n_in, d_out_ptr, C.byref(n_out), stream))
         return n_out.value
 
     # ---- pipelined device entry point (csdr_chain_submit_device / csdr_chain_wait_device)
@@ -823,15 +810,15 @@ class Chain(_Resettable):
         """Queue one HBM-resident chunk on the handle's own streams; consecutive chunks' launches may overlap (include/csdr.h).
         `d_in_ptr` must stay untouched and `d_out_ptr` unread until wait_device()."""
         n_out = C.c_uint32()
-        check(lib().csdr_chain_submit_device(self.h, C.c_void_p(d_in_ptr), n_in, C.c_void_p(d_out_ptr), C.byref(n_out), C.c_void_p(ready_event)))
+        check(lib().csdr_chain_submit_device(self.h, d_in_ptr, n_in, d_out_ptr, C.byref(n_out), ready_event))
         return n_out.value
 
     def independent_launches(self):
-        return lib().csdr_chain_debug_independent_launches(self.h)
+        return self._get("debug_independent_launches")
 
     def wait_device(self, stream=None):
         """Host (stream=None) or `stream` waits for every chunk queued with submit_device()."""
-        check(lib().csdr_chain_wait_device(self.h, C.c_void_p(stream) if stream is not None else None))
+        self._call("wait_device", stream)
 
     # ---- asynchronous host-buffer entry point (csdr_chain_submit / csdr_chain_collect)
     def submit(self, x, out=None):
@@ -840,37 +827,36 @@ class Chain(_Resettable):
         x = _c64(x)
         if out is None:
             out = np.empty(self.out_shape(x.size), dtype=self.out_dtype)
-        check(lib().csdr_chain_submit(self.h, _ptr(x), x.size, _ptr(out)))
-        self._pending = getattr(self, "_pending", [])
+        self._call("submit", _ptr(x), x.size, _ptr(out))
         self._pending.append((x, out))                   # keep the buffers alive until collect
         return out
 
     def collect(self):
         """Wait for the oldest submitted chunk; returns its output array."""
         n_out = C.c_uint32()
-        check(lib().csdr_chain_collect(self.h, C.byref(n_out)))
+        self._call("collect", C.byref(n_out))
         x, out = self._pending.pop(0)
         assert n_out.value == out.size or x.size == 0, (n_out.value, out.size)
         return out
 
     def status(self):
         """raises CsdrError if a device-side inter-workgroup wait timed out since the last check"""
-        check(lib().csdr_chain_status(self.h))
+        self._call("status")
 
     def kernel_time(self):
         ms, n = C.c_double(), C.c_uint32()
-        name = lib().csdr_chain_kernel_time(self.h, C.byref(ms), C.byref(n))
+        name = self._get("kernel_time", C.byref(ms), C.byref(n))
         return name.decode(), ms.value, n.value
 
     def agc_stats(self):
         """(segments checked, segments recomputed) of the time-parallel AGC tail since create"""
         a, b = C.c_uint32(), C.c_uint32()
-        check(lib().csdr_chain_debug_agc(self.h, C.byref(a), C.byref(b)))
+        self._call("debug_agc", C.byref(a), C.byref(b))
         return a.value, b.value
 
     def agc_tile_major_calls(self):
         """calls since create whose AGC tail ran on a tile-major plane (k_agc_spec_tm)"""
-        return lib().csdr_chain_debug_agc_tile_major_calls(self.h)
+        return self._get("debug_agc_tile_major_calls")
 
     def reset(self):
         super().reset()
@@ -878,7 +864,7 @@ class Chain(_Resettable):
 
     def seek_frames(self, frames):
         """reset, then continue as if `frames` frames of the stream had already gone by"""
-        check(lib().csdr_chain_seek_frames(self.h, int(frames)))
+        self._call("seek_frames", int(frames))
         self._pending = []
 
     def close(self):
@@ -917,128 +903,95 @@ def firpfbchChannelizer(n, **kw):
     """firpfbchChannelizer n (Liquid.chs:864-866): Pipe IO (Array CF32) [Array CF32].
     Output is the list of n per-channel arrays the reference produces by slicing one
     channel-major buffer (Liquid.chs:850-862); an empty input yields [empty]."""
-    def start():
-        return Chain(ChainConfig(channels=n, dc_block=False, **kw))
+    return Pipe(lambda: Chain(ChainConfig(channels=n, dc_block=False, **kw)), lambda r, a: _channel_list(r.process, a),
+                lambda r: r.close())
 
-    def process(r, a):
-        x = _c64(a)
-        if x.size == 0:
-            return [np.empty(0, dtype=np.complex64)]
-        y = r.process(x)
-        return [y[k] for k in range(y.shape[0])]
-    return Pipe(start, process, lambda r: r.close())
+
+def _firdes_bank2(fn, M, m, as_db, fc):
+    M, m = int(M), int(m)
+    h = np.empty(2 * M * m if 0 < M <= 256 and 0 < m <= 8 else 1, dtype=np.float32)
+    check(fn(M, m, float(as_db), float(fc), _ptr(h)))
+    return h
 
 
 def firdes_pfbch2(M, m, as_db=80.0, fc=0.0):
     """The prototype of the 2x-oversampled channelizer (`csdr_pfbch2_design`): the first 2 M m of the 2 M m + 1 Kaiser taps of
     cutoff fc (0: the analyzer's rule 1 / M) that sum to M, evaluated in f64 and rounded once.  No GPU needed"""
-    M, m = int(M), int(m)
-    h = np.empty(2 * M * m if 0 < M <= 256 and 0 < m <= 8 else 1, dtype=np.float32)
-    check(lib().csdr_pfbch2_design(M, m, float(as_db), float(fc), _ptr(h)))
-    return h
+    return _firdes_bank2(lib().csdr_pfbch2_design, M, m, as_db, fc)
 
 
-class Firpfbch2(_Owner):
-    """The `csdr_pfbch2_*` object: liquid's firpfbch2_crcf analyzer (which the reference does not import), M channels at twice
-    the critical rate: every M / 2 input samples give one frame, rows are channel-major and centred on 2 pi k / M
-    (include/csdr.h, DESIGN.md 4.17).  `Firpfbch2(taps, M, m)` takes a prototype of 2 M m taps, `Firpfbch2.kaiser` designs it."""
-    _block = "pfbch2"
+def firdes_pfbsyn2(M, m, as_db=80.0, fc=0.0):
+    """The prototype of the 2x-oversampled synthesizer (`csdr_pfbsyn2_design`): firdes_pfbch2's Kaiser design with fc = 0 meaning
+    the synthesizer's rule 0.5 / M, half the analyzer's cutoff (DESIGN.md 4.18).  No GPU needed"""
+    return _firdes_bank2(lib().csdr_pfbsyn2_design, M, m, as_db, fc)
 
-    def __init__(self, taps, M, m, max_frames=1 << 16, _kaiser=None):
+
+class _Bank2(_Owner):
+    """What the two 2x-oversampled bank objects share: M channels over a prototype of 2 M m taps, the caller's (`cls(taps, M, m)`)
+    or the block's own Kaiser design (`cls.kaiser`); `taps` reads it back, `rewind` is the reset"""
+
+    def __init__(self, taps, M, m, max_frames=1 << 16):
+        self._state(M, m)
+        t = np.ascontiguousarray(taps, dtype=np.float32).reshape(-1)
+        if t.size != 2 * self.M * self.m:
+            raise CsdrError(_lib.ERR_INVALID, f"{self._block}: {t.size} taps, not 2 M m = {2 * self.M * self.m}")
+        self._h = _new_handle(self._block, _ptr(t), self.M, self.m, int(max_frames), create="open_taps")
+
+    def _state(self, M, m):
         self.M, self.m = int(M), int(m)
-        if _kaiser is not None:
-            as_db, fc = _kaiser
-            self._h = _new_handle("pfbch2", self.M, self.m, float(as_db), float(fc), int(max_frames), create="open_kaiser")
-        else:
-            t = np.ascontiguousarray(taps, dtype=np.float32).reshape(-1)
-            if t.size != 2 * self.M * self.m:
-                raise CsdrError(_lib.ERR_INVALID, f"pfbch2: {t.size} taps, not 2 M m = {2 * self.M * self.m}")
-            self._h = _new_handle("pfbch2", _ptr(t), self.M, self.m, int(max_frames), create="open_taps")
 
     @classmethod
     def kaiser(cls, M, m=7, as_db=80.0, fc=0.0, max_frames=1 << 16):
-        """the taps of firdes_pfbch2(M, m, as_db, fc)"""
-        return cls(None, M, m, max_frames, _kaiser=(as_db, fc))
+        """the taps of the block's design function: firdes_pfbch2(M, m, as_db, fc) for Firpfbch2, firdes_pfbsyn2(M, m, as_db, fc)
+        for Firpfbch2Synth"""
+        return cls._adopt(_new_handle(cls._block, int(M), int(m), float(as_db), float(fc), int(max_frames), create="open_kaiser"), M, m)
 
     def taps(self):
         t = np.empty(2 * self.M * self.m, np.float32)
-        check(lib().csdr_pfbch2_get_taps(self.h, _ptr(t)))
+        self._call("get_taps", _ptr(t))
         return t
 
     def rewind(self):
         """back to the state right after the object was made (firpfbch2_crcf_reset)"""
-        check(lib().csdr_pfbch2_rewind(self.h))
+        self._call("rewind")
+
+
+class Firpfbch2(_Bank2):
+    """The `csdr_pfbch2_*` object: liquid's firpfbch2_crcf analyzer (which the reference does not import), M channels at twice
+    the critical rate: every M / 2 input samples give one frame, rows are channel-major and centred on 2 pi k / M
+    (include/csdr.h, DESIGN.md 4.17).  `Firpfbch2(taps, M, m)` takes a prototype of 2 M m taps, `Firpfbch2.kaiser` designs it."""
+    _block = "pfbch2"
 
     def process(self, x):
         """[n] CF32, n a multiple of M / 2 -> [M][n / (M / 2)] CF32"""
         x = _c64(x).reshape(-1)
         y = np.empty((self.M, x.size // (self.M // 2)), dtype=np.complex64)
         frames = C.c_uint32()
-        check(lib().csdr_pfbch2_process(self.h, _ptr(x), x.size, _ptr(y), C.byref(frames)))
+        self._call("process", _ptr(x), x.size, _ptr(y), C.byref(frames))
         assert frames.value == y.shape[1], (frames.value, y.shape)
         return y
 
     def process_device(self, d_x_ptr, n, d_y_ptr, stream=0):
         """Device-resident variant: raw device pointers (ints) for x [n] and y [M][n / (M / 2)]; enqueues on `stream`"""
-        check(lib().csdr_pfbch2_process_device(self.h, C.c_void_p(d_x_ptr), n, C.c_void_p(d_y_ptr), C.c_void_p(stream)))
+        self._call("process_device", d_x_ptr, n, d_y_ptr, stream)
 
 
 def firpfbch2Channelizer(M, m=7, as_db=80.0, fc=0.0, max_frames=1 << 16):
     """The 2x-oversampled counterpart of firpfbchChannelizer: Pipe IO (Array CF32) [Array CF32], the list of M per-channel
     arrays, each at 2 / M of the input rate; an empty input yields [empty], as there"""
-    def process(r, a):
-        x = _c64(a)
-        if x.size == 0:
-            return [np.empty(0, dtype=np.complex64)]
-        y = r.process(x)
-        return [y[k] for k in range(y.shape[0])]
-    return Pipe(lambda: Firpfbch2.kaiser(M, m, as_db, fc, max_frames), process, lambda r: r.close())
+    return Pipe(lambda: Firpfbch2.kaiser(M, m, as_db, fc, max_frames), lambda r, a: _channel_list(r.process, a), lambda r: r.close())
 
 
-def firdes_pfbsyn2(M, m, as_db=80.0, fc=0.0):
-    """The prototype of the 2x-oversampled synthesizer (`csdr_pfbsyn2_design`): firdes_pfbch2's Kaiser design with fc = 0 meaning
-    the synthesizer's rule 0.5 / M, half the analyzer's cutoff (DESIGN.md 4.18).  No GPU needed"""
-    M, m = int(M), int(m)
-    g = np.empty(2 * M * m if 0 < M <= 256 and 0 < m <= 8 else 1, dtype=np.float32)
-    check(lib().csdr_pfbsyn2_design(M, m, float(as_db), float(fc), _ptr(g)))
-    return g
-
-
-class Firpfbch2Synth(_Owner):
+class Firpfbch2Synth(_Bank2):
     """The `csdr_pfbsyn2_*` object: the synthesizer side of liquid's firpfbch2_crcf, the way back from Firpfbch2's rows to one
     stream: every frame of M values gives M / 2 samples, and Firpfbch2.kaiser followed by Firpfbch2Synth.kaiser returns its
     input `delay()` samples late (include/csdr.h).  `Firpfbch2Synth(taps, M, m)` takes a prototype of 2 M m taps,
     `Firpfbch2Synth.kaiser` designs it."""
     _block = "pfbsyn2"
 
-    def __init__(self, taps, M, m, max_frames=1 << 16, _kaiser=None):
-        self.M, self.m = int(M), int(m)
-        if _kaiser is not None:
-            as_db, fc = _kaiser
-            self._h = _new_handle("pfbsyn2", self.M, self.m, float(as_db), float(fc), int(max_frames), create="open_kaiser")
-        else:
-            t = np.ascontiguousarray(taps, dtype=np.float32).reshape(-1)
-            if t.size != 2 * self.M * self.m:
-                raise CsdrError(_lib.ERR_INVALID, f"pfbsyn2: {t.size} taps, not 2 M m = {2 * self.M * self.m}")
-            self._h = _new_handle("pfbsyn2", _ptr(t), self.M, self.m, int(max_frames), create="open_taps")
-
-    @classmethod
-    def kaiser(cls, M, m=7, as_db=80.0, fc=0.0, max_frames=1 << 16):
-        """the taps of firdes_pfbsyn2(M, m, as_db, fc)"""
-        return cls(None, M, m, max_frames, _kaiser=(as_db, fc))
-
-    def taps(self):
-        t = np.empty(2 * self.M * self.m, np.float32)
-        check(lib().csdr_pfbsyn2_get_taps(self.h, _ptr(t)))
-        return t
-
     def delay(self):
         """samples by which the analyzer followed by this synthesizer delays a stream: 2 M m - M / 2 + 1"""
-        return int(lib().csdr_pfbsyn2_delay(self.h))
-
-    def rewind(self):
-        """back to the state right after the object was made (firpfbch2_crcf_reset)"""
-        check(lib().csdr_pfbsyn2_rewind(self.h))
+        return int(self._get("delay"))
 
     def process(self, y):
         """[M][frames] CF32 -> [frames M / 2] CF32"""
@@ -1047,13 +1000,13 @@ class Firpfbch2Synth(_Owner):
             raise CsdrError(_lib.ERR_INVALID, f"pfbsyn2: a chunk of shape {y.shape}, not [{self.M}][frames]")
         x = np.empty(y.shape[1] * (self.M // 2), dtype=np.complex64)
         n = C.c_uint32()
-        check(lib().csdr_pfbsyn2_process(self.h, _ptr(y), y.shape[1], _ptr(x), C.byref(n)))
+        self._call("process", _ptr(y), y.shape[1], _ptr(x), C.byref(n))
         assert n.value == x.size, (n.value, x.shape)
         return x
 
     def process_device(self, d_y_ptr, frames, d_x_ptr, stream=0):
         """Device-resident variant: raw device pointers (ints) for y [M][frames] and x [frames M / 2]; enqueues on `stream`"""
-        check(lib().csdr_pfbsyn2_process_device(self.h, C.c_void_p(d_y_ptr), frames, C.c_void_p(d_x_ptr), C.c_void_p(stream)))
+        self._call("process_device", d_y_ptr, frames, d_x_ptr, stream)
 
 
 def firpfbch2Synthesizer(M, m=7, as_db=80.0, fc=0.0, max_frames=1 << 16):
@@ -1066,14 +1019,17 @@ def firpfbch2Synthesizer(M, m=7, as_db=80.0, fc=0.0, max_frames=1 << 16):
     return Pipe(lambda: Firpfbch2Synth.kaiser(M, m, as_db, fc, max_frames), process, lambda r: r.close())
 
 
+def _rowresamp_design(fn, args, delay=()):
+    """(bank F32 [257][P], delta) through the entry point fn(*args, &P, &delta, *delay, bank)"""
+    P, delta = C.c_uint32(), C.c_uint64()
+    bank = _sized(fn, args, (P, delta, *delay), lambda P, delta: np.empty((257, P), dtype=np.float32))
+    return bank, int(delta.value)
+
+
 def firdes_rowresamp(rate, m=7, as_db=60.0, fc=0.0):
     """The design of the row resampler (`csdr_rowresamp_design`, "csdr rowresamp v1"): (bank F32 [257][P], delta),
     delta = llround(2^32 / rate) Q32.32 input samples per output and P = 2 m D taps per phase.  No GPU needed"""
-    P, delta = C.c_uint32(), C.c_uint64()
-    check(lib().csdr_rowresamp_design(float(rate), int(m), float(as_db), float(fc), C.byref(P), C.byref(delta), None))
-    bank = np.empty((257, P.value), dtype=np.float32)
-    check(lib().csdr_rowresamp_design(float(rate), int(m), float(as_db), float(fc), None, None, _ptr(bank)))
-    return bank, int(delta.value)
+    return _rowresamp_design(lib().csdr_rowresamp_design, (float(rate), int(m), float(as_db), float(fc)))
 
 
 class RowResamp(_Owner):
@@ -1091,47 +1047,39 @@ class RowResamp(_Owner):
 
     def design(self):
         """(bank F32 [257][P], delta)"""
-        P, delta = C.c_uint32(), C.c_uint64()
-        check(lib().csdr_rowresamp_get_design(self.h, C.byref(P), C.byref(delta), None, None))
-        bank = np.empty((257, P.value), dtype=np.float32)
-        check(lib().csdr_rowresamp_get_design(self.h, None, None, None, _ptr(bank)))
-        return bank, int(delta.value)
+        return _rowresamp_design(lib().csdr_rowresamp_get_design, (self.h,), delay=(None,))
 
     def delay(self):
         """the group delay in input samples: m D"""
         d = C.c_uint32()
-        check(lib().csdr_rowresamp_get_design(self.h, None, None, C.byref(d), None))
+        self._call("get_design", None, None, C.byref(d), None)
         return int(d.value)
 
     def time(self):
         """T: the Q32.32 time of the next output relative to the first sample of the next call"""
         t = C.c_uint64()
-        check(lib().csdr_rowresamp_get_time(self.h, C.byref(t)))
+        self._call("get_time", C.byref(t))
         return int(t.value)
 
     def count(self, n):
         """outputs per row that the next call of n samples per row yields"""
         n_out = C.c_uint32()
-        check(lib().csdr_rowresamp_count(self.h, int(n), C.byref(n_out)))
+        self._call("count", int(n), C.byref(n_out))
         return int(n_out.value)
 
     def max_out(self, n):
         """room per row that a call of n samples may need, whatever the time it starts at"""
-        return int(lib().csdr_rowresamp_max_out(self.h, int(n)))
+        return int(self._get("max_out", int(n)))
 
     def rewind(self):
         """back to the state right after the object was made (resamp_crcf_reset)"""
-        check(lib().csdr_rowresamp_rewind(self.h))
+        self._call("rewind")
 
     def process(self, x):
         """[nchan][n] -> [nchan][n_out]; [n] -> [n_out]"""
-        x = np.ascontiguousarray(x, dtype=self.dtype)
-        if x.size % self.nchan or (x.ndim == 2 and x.shape[0] != self.nchan) or x.ndim > 2:
-            raise CsdrError(_lib.ERR_INVALID, f"rowresamp: a chunk of shape {x.shape}, not [{self.nchan}][n]")
-        n = x.size // self.nchan
-        y = np.empty((self.nchan, self.count(n)), dtype=self.dtype)
+        x, n, y = _rows("rowresamp", x, self.dtype, self.nchan, out_len=self.count, plane=True, strict=True)
         n_out = C.c_uint32()
-        check(lib().csdr_rowresamp_process(self.h, _ptr(x), n, _ptr(y), C.byref(n_out)))
+        self._call("process", _ptr(x), n, _ptr(y), C.byref(n_out))
         assert n_out.value == y.shape[1], (n_out.value, y.shape)
         return y[0] if x.ndim == 1 else y
 
@@ -1139,7 +1087,7 @@ class RowResamp(_Owner):
         """Device-resident variant: raw device pointers (ints) for x [nchan][n] and y [nchan][n_out]; enqueues on `stream` and
         returns n_out without synchronising"""
         n_out = C.c_uint32()
-        check(lib().csdr_rowresamp_process_device(self.h, C.c_void_p(d_x_ptr), int(n), C.c_void_p(d_y_ptr), C.byref(n_out), C.c_void_p(stream)))
+        self._call("process_device", d_x_ptr, int(n), d_y_ptr, C.byref(n_out), stream)
         return int(n_out.value)
 
 

@@ -40,7 +40,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import check, lib
-from .pipes import Chain, ChainConfig, _Handle
+from .pipes import Chain, ChainConfig, _Owner, _new_handle
 
 
 class _stdout_to_stderr:
@@ -65,19 +65,18 @@ class _stdout_to_stderr:
         return False
 
 
-class Comm:
+class Comm(_Owner):
     """`csdr_comm` (include/csdr.h): the collectives UNDER the C ABI -- RCCL over xGMI, one process per GPU.  What a non-Python host
     (the Haskell program, host/soapy_sdr_file.cpp) calls; ShardedChain uses it instead of torch.distributed whenever the ranks are
     on GPUs.  Bootstrapping: rank 0 makes `unique_id()`, every rank creates the communicator with those bytes (collective)."""
+    _block = "comm"
 
     def __init__(self, rank, world, unique_id, device=-1):
         if len(unique_id) != _lib.COMM_ID_BYTES:
             raise ValueError("unique_id: %d bytes" % _lib.COMM_ID_BYTES)
-        h = C.c_void_p()
         buf = (C.c_char * _lib.COMM_ID_BYTES).from_buffer_copy(bytes(unique_id))
         with _stdout_to_stderr():
-            check(lib().csdr_comm_create(rank, world, buf, device, C.byref(h)))
-        self._h = _Handle(h, lib().csdr_comm_destroy)
+            self._h = _new_handle("comm", rank, world, buf, device)
         self.rank, self.world = rank, world
 
     @staticmethod
@@ -94,22 +93,16 @@ class Comm:
         dist.broadcast_object_list(box, src=0, group=group)
         return cls(rank, world, box[0], device)
 
-    @property
-    def h(self):
-        return self._h.h
-
     def allreduce_f32(self, d_ptr, count, stream=0):
-        check(lib().csdr_comm_allreduce_f32(self.h, C.c_void_p(d_ptr), count, C.c_void_p(stream)))
+        self._call("allreduce_f32", d_ptr, count, stream)
 
     def broadcast(self, d_ptr, nbytes, root=0, stream=0):
-        check(lib().csdr_comm_broadcast(self.h, C.c_void_p(d_ptr), nbytes, root, C.c_void_p(stream)))
+        self._call("broadcast", d_ptr, nbytes, root, stream)
 
     def hybrid_exchange(self, d_plane, d_recv, chan_per_rank, stripe_frames, elem_bytes=8, stream=0):
         fr = (C.c_uint32 * len(stripe_frames))(*stripe_frames)
-        check(lib().csdr_hybrid_exchange(self.h, C.c_void_p(d_plane), C.c_void_p(d_recv), chan_per_rank, fr, elem_bytes, C.c_void_p(stream)))
+        check(lib().csdr_hybrid_exchange(self.h, d_plane, d_recv, chan_per_rank, fr, elem_bytes, stream))
 
-    def close(self):
-        self._h.close()
 
 WARMUP_SAMPLES = 32768     # DC blocker: (1 - 0.0005)^32768 = 7.6e-8 of the state is left
 
@@ -390,8 +383,8 @@ class ShardedChain:
         if self.comm is not None:
             # the C ABI's entry point: chain + ncclAllReduce on the caller's stream (what a non-Python host calls)
             n_out = C.c_uint32()
-            check(lib().csdr_chain_process_device_mix(self.chain.h, self.comm.h, C.c_void_p(x_dev.data_ptr()), x_dev.numel() // 2,
-                                                      C.c_void_p(out_dev.data_ptr()), C.byref(n_out), C.c_void_p(int(stream or 0))))
+            check(lib().csdr_chain_process_device_mix(self.chain.h, self.comm.h, x_dev.data_ptr(), x_dev.numel() // 2,
+                                                      out_dev.data_ptr(), C.byref(n_out), int(stream or 0)))
             return n_out.value
         n = self.chain.process_device(x_dev.data_ptr(), x_dev.numel() // 2, out_dev.data_ptr(), stream)
         if self.dist is not None and self.world > 1:

@@ -2,7 +2,8 @@
 independent (the same input gives the same bits; destroying one leaves the other's state and buffers alone), close is
 idempotent, a closed object refuses work, and create / close cycles without a call in between are clean.  For the ten blocks
 that carry their state in a ping-pong pair: a refused call leaves the state alone, and a reset (or rewind) gives the state
-of a fresh handle whichever side of the pair is current.
+of a fresh handle whichever side of the pair is current.  For the fifteen cases on nchan rows: a chunk that is no [rows][n] is
+refused by the Pipe layer and leaves the state alone.
 
 One case per block kind (real and complex where a block has both) in the smallest configuration its own GPU test uses,
 nchan = 3 where the block takes nchan, calls of 3000 and 1000 samples per row (multiples of every k and decimation here,
@@ -94,6 +95,7 @@ CASES = [
 ]
 PAIRS = [c for c in CASES if c.pair]                          # the ten blocks with a ping-pong pair: seven older ones, the three newest
 RESETS = [c for c in PAIRS if c.reset]
+ROWED = [c for c in CASES if c.rows > 1]                      # the fifteen cases whose chunks are [rows][n]
 
 
 def _input(case, n, seed):
@@ -171,6 +173,23 @@ def test_a_refused_call_leaves_the_state_alone(case):
             case.run(a, _input(case, n, 3))
         assert e.value.code == _lib.ERR_SIZE, (n, str(e.value))
     _assert_same_bits(case.run(a, xb), want[1], "call B behind the refused calls")
+    case.done(a)
+    case.done(b)
+
+
+@pytest.mark.parametrize("case", ROWED, ids=[c.name for c in ROWED])
+def test_a_ragged_chunk_is_refused_and_leaves_the_state_alone(case):
+    """a flat chunk of rows * 1000 + 1 elements is no [rows][n]: the Pipe layer refuses it (ERR_INVALID) before the library is
+    called, so the call behind it gives the bits of a handle that never saw it"""
+    x1, x2 = _input(case, N2, 1), _input(case, N2, 2)
+    a, b = case.make(), case.make()
+    _assert_same_bits(case.run(a, x1), case.run(b, x1), "the first call")
+    ragged = np.append(_input(case, N2, 3).reshape(-1), case.dtype(0.25))
+    assert ragged.shape == (case.rows * N2 + 1,) and ragged.dtype == case.dtype
+    with pytest.raises(cs.CsdrError) as e:
+        case.run(a, ragged)
+    assert e.value.code == _lib.ERR_INVALID, str(e.value)
+    _assert_same_bits(case.run(a, x2), case.run(b, x2), "the second call, behind the refused chunk on one of the two")
     case.done(a)
     case.done(b)
 
