@@ -1,6 +1,5 @@
 // What the chain plans share (fused.h): the call sequence of ChainPlan (one kernel choice per call), the carried stream state, the DC
-// blocker's constants, the set-up of cold starts without warm-up windows and the debug trace dump of the M = 1024 run kernels.  Host code
-// only.  Product code.
+// blocker's constants and the set-up of cold starts without warm-up windows.  Host code only.  Product code.
 #include "fused.h"
 
 #include <cmath>
@@ -54,17 +53,6 @@ int StreamState::reset(hipStream_t s) const
     return 0;
 }
 
-int Run1024Call::trace_dump(size_t n, bool before, hipStream_t s) const
-{
-    if (!trace) return 0;
-    if (before) { CSDR_HIP(hipMemsetAsync(trace, 0, n * sizeof(unsigned long long), s)); return 0; }
-    std::vector<unsigned long long> hbuf(n);
-    CSDR_HIP(hipStreamSynchronize(s));
-    CSDR_HIP(hipMemcpy(hbuf.data(), trace, n * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-    if (FILE *f = fopen(trace_file, "wb")) { fwrite(hbuf.data(), sizeof(unsigned long long), n, f); fclose(f); }
-    return 0;
-}
-
 DcConsts::DcConsts(bool dc_block, const DcParams &dc)
 {
     const double b = dc_block ? (double)dc.beta : 0.0;
@@ -77,10 +65,12 @@ DcConsts::DcConsts(bool dc_block, const DcParams &dc)
     for (int k = 0; k < 12; k++) wtile[k] = (float)std::pow(b, 4096.0 * k);
 }
 
-int ColdStart::init(DeviceBuffers &mem, const FusedConfig &cfg, double window, size_t n_cpre, size_t n_side, bool state_always,
+int ColdStart::init(DeviceBuffers &mem, const FusedConfig &cfg, double window, uint32_t max_runs, size_t side_per_run, bool state_always,
                     uint32_t f0, uint32_t nfr, int k0, const float2 *wpre)
 {
     int r;
+    runs = max_runs;
+    const size_t n_cpre = (size_t)max_runs + 2, n_side = ((size_t)max_runs + 1) * side_per_run;
     const char *e = diag_env("CSDR_NOWU");
     const bool on = cfg.dc_block && dc_window_ok(cfg.dc, window) && !(e && atoi(e) == 0);
     if (on || state_always) {

@@ -1,7 +1,9 @@
 // Interface between the chain handle of the C ABI (capi.hip) and the plans of its routes: the four fused channelizers (M = 64, 256,
 // 1024, 4096) and the any-M route.  Product code.
 //   chain_plan.cpp            what the plans share: ChainPlan::process, StreamState, DcConsts, ColdStart, dc_state_response
-//   kernel_choice.h           which kernel a call takes (KernelChoice, the run counts, the M = 64 and M = 1024 selection); no HIP
+//   kernel_choice.h           which kernel a call takes (KernelChoice, the run counts, the M = 64 and M = 1024 selection) and whether
+//                             its runs start cold (the run-length rules); no HIP
+//   run_split.h               the bounds of run w for every run kernel, and the constants they are judged against; no HIP
 //   agc_tail_shape.h          the launch shape of the AGC tail behind the plans (kernels_agc_tail.hip, chain_tails.h); no HIP
 //   kernels_fused_small.hip   M = 64: SmallPlan, k_run64; its run kernel k_run64v2 in kernels_run64_v2.hip
 //   kernels_fused.hip         M = 256: FusedPlan, k_tile256; its run kernel k_run256v2 in kernels_fused_v2.hip
@@ -87,11 +89,16 @@ private:
 // handle keeps its warm-up windows (blocker off, an alpha the window does not fit: dc_window_ok, or CSDR_NOWU=0).
 struct ColdStart {
     float2 *cpre = nullptr, *side = nullptr, *rt = nullptr;
-    // window: the samples behind a cold start after which the missing state is dropped.  cpre (n_cpre elements, zeroed) and side (n_side;
-    // 0: none) are made with rt, or whatever rt when state_always (kernels that write them on every launch).  rt: frames f0 .. f0 + nfr - 1
-    // behind the tile's start at the channels k0 .. k0 + 3 on the phasor table wpre (k0 < 0: all zero)
-    int init(DeviceBuffers &mem, const FusedConfig &cfg, double window, size_t n_cpre, size_t n_side, bool state_always,
+    uint32_t runs = 0;          // launches of up to this many runs fit the arrays
+    // window: the samples behind a cold start after which the missing state is dropped.  cpre (max_runs + 2 elements, zeroed) and side
+    // (max_runs + 1 runs of side_per_run elements; 0: none) are made with rt, or whatever rt when state_always (kernels that write them on
+    // every launch).  rt: frames f0 .. f0 + nfr - 1 behind the tile's start at the channels k0 .. k0 + 3 on the phasor table wpre (k0 < 0:
+    // all zero)
+    int init(DeviceBuffers &mem, const FusedConfig &cfg, double window, uint32_t max_runs, size_t side_per_run, bool state_always,
              uint32_t f0, uint32_t nfr, int k0, const float2 *wpre);
+    // the capacity half of a call's cold-start decision (the shape half: kernel_choice.h): the handle runs without warm-up windows and a
+    // launch of nruns runs fits the arrays
+    bool fits(uint32_t nruns) const { return rt && cold_fits(runs, nruns); }
 };
 
 // The plan of one route (a RouteRow of capi.hip): M = 64 (kernels_fused_small.hip), 256 (kernels_fused.hip), 1024 (kernels_pfb1024.hip),
@@ -192,57 +199,34 @@ struct Run64v2Host {
     const float *taps; const float2 *tw, *wpre;
     const float2 *uhist_in; float2 *uhist_out; const float2 *vend_in; float2 *vend_out;
     // runs without warm-up windows (round 5, as k_run256v2: DESIGN 4): cpre [nruns + 1] DC state in front of every run's halo tile,
-    // rt [2 parities][RUN64_DCFIX_F][4] the chain's response to a unit state at the channels 30..33; both null: warm-up windows
-    float2 *cpre = nullptr; const float2 *rt = nullptr;
+    // rt [2 parities][RUN64_DCFIX_F][4] the chain's response to a unit state at the channels 30..33; cold: this call's runs start that
+    // way (ColdStart::fits and run64_v2_cold, combined by the plan); else warm-up windows
+    float2 *cpre = nullptr; const float2 *rt = nullptr; bool cold = false;
     uint32_t nf, nruns, parity0;
     uint32_t G = 1, g = 0;      // interleaved shard g of G (tables rotated by the plan)
     bool tile_major = false;    // CF32 plane of the AGC route: [block of 16 frames][64][128 B]
     const DcConsts *dc;         // the plan's
     double weight = 1.1;        // tile share of the older workgroup of a CU (1 = even; 1.1 measured best: 243 vs 250 us; CSDR_RUN64_WEIGHT)
 };
-constexpr int RUN64_DCFIX_F = 448;                      // output frames of a run the state correction covers (7 tiles: 32 768 samples behind the halo tile's start)
 // Response of the chain (pre-mix table wpre [2][M], taps, forward DFT), at the channels k0 .. k0 + 3, to a DC-blocker state of 1 in
 // front of a tile: frames f0 .. f0 + nfr - 1 behind the tile's start, both parities of the tile's first frame; rt [2][nfr][4], f64 inside
 void dc_state_response(const FusedConfig &cfg, const float2 *wpre, uint32_t f0, uint32_t nfr, uint32_t k0, float2 *rt);
 int run64_v2_launch(const Run64v2Host &h, hipStream_t s, KernelTimer *timer);
 
-// One call of a run kernel of the M = 1024 plan: k_run1024v2<FM, G> (kernels_run1024_v2.hip: interleaved shards, nf % 4 == 0), k_run1024v3
-// (kernels_run1024_v3.hip: whole band, one 512-thread workgroup per CU, output lines staged in registers; calls of whole 4-frame tiles) or
-// k_shard1024<.., G> (kernels_shard1024.hip: chan_stride G = 4, 8, F32 or CF32 rows of the owned channels; the fold of the aliasing branches
-// behind the FIR + a (1024 / G)-point DFT across the lanes of a wave).  Same state buffers and tables as k_run1024.  Where no kernel is
-// named, all three launchers read the field (put_run1024, fused_common.h, copies those into the kernel's argument struct).
-struct Run1024Call {
-    const float2 *x; void *out;
-    const float4 *taps_q;       // [4][4][256] float4: taps of branch 256 q + j (14) + its even-frame pre-mix phasor
-    const float2 *tw;
-    const float2 *uhist_in; float2 *uhist_out; const float2 *vend_in; float2 *vend_out; const float2 *rp_in; float2 *rp_out;
-    uint32_t nf, nruns, parity0;    // nruns: KernelChoice::runs
-    bool fm;                    // F32 freqdem output (k_run1024v2: always)
-    uint32_t G = 1, g = 0;      // k_run1024v2, k_shard1024: interleaved shard g of G (tables rotated by the plan)
-    bool tile_major = false;    // k_run1024v3<CF32>, k_shard1024<CF32>: the lines of a 16-frame block back to back ([block][rows][128 B]) instead of row-major [rows][nf]
-    // k_run1024v3, k_shard1024 without warm-up windows (as k_run256v2: DESIGN 4): cpre [nruns + 1] DC state four tiles in front of every run's
-    // first tile, side [nruns][4][RUN1024_DCFIX_F] uncorrected Y of the channels 510..513 (FM), rt [2][RUN1024_DCFIX_F][4] the chain's
-    // response to a unit state there; rt null: warm-up windows
-    float2 *cpre = nullptr, *side = nullptr; const float2 *rt = nullptr;
-    int mfix = -1;              // k_shard1024: the shard's row among the four channels around DC (side [nruns][RUN1024_DCFIX_F], rt channel 0), -1: none
-    const DcConsts *dc;         // the plan's
-    float fm_ref;
-    double weight = 1.2;        // k_run1024v2: tile share of the older workgroup of a CU (1 = even; CSDR_RUN1024_WEIGHT)
-    // debug builds of k_run1024v3 / k_shard1024: the plan's stamp buffer (RUN1024_V3_TRACE_N / SHARD1024_TRACE_N) and the file the
-    // last launch's stamps go to (CSDR_RUN1024_V3_TRACE, CSDR_SHARD1024_TRACE); null: no trace
-    unsigned long long *trace = nullptr; const char *trace_file = nullptr;
-    // the debug trace of a launch: before = zero the n stamps in front of it; else wait for it and write them, raw uint64, to trace_file
-    int trace_dump(size_t n, bool before, hipStream_t s) const;
-};
+// One call of a run kernel of the M = 1024 plan (Run1024Call, fused_common.h: one argument struct for the three kernels plus what only
+// the host reads): k_run1024v2<FM, G> (kernels_run1024_v2.hip: interleaved shards, nf % 4 == 0), k_run1024v3 (kernels_run1024_v3.hip: whole
+// band, one 512-thread workgroup per CU, output lines staged in registers; calls of whole 4-frame tiles) or k_shard1024<.., G>
+// (kernels_shard1024.hip: chan_stride G = 4, 8, F32 or CF32 rows of the owned channels; the fold of the aliasing branches behind the FIR + a
+// (1024 / G)-point DFT across the lanes of a wave).  Same state buffers and tables as k_run1024.  One launcher (kernels_run1024_v3.hip), one
+// launch per call and, behind a cold one, k_run1024_dcfix; no fix-up kernel: a run computes the frame in front of it itself.
+struct Run1024Call;
+int run1024_launch(const Run1024Call &h, hipStream_t s, KernelTimer *timer);
+// The launcher's dispatch table is filled by the kernels' own files: the instantiation for (FM, G), its workgroup size and the stamps of
+// its debug trace (RUN1024_V3_TRACE_N / SHARD1024_TRACE_N; 0: not a trace build).  fn null: not built
+struct Run1024Kernel { const void *fn = nullptr; unsigned threads = 0; size_t trace_n = 0; };
+Run1024Kernel run1024_v2_kernel(bool fm, uint32_t G);
+Run1024Kernel shard1024_kernel(bool fm, uint32_t G);
 constexpr size_t RUN1024_V3_TRACE_N = 1536, SHARD1024_TRACE_N = 768;
-// k_run1024v3's correction covers frame -1 of a run (freqdem history) + its first eight tiles.  The first frame NOT corrected (32) has a
-// window that reaches back to frame 35 behind the cold start: alpha |c| beta^35840 = 1.6e-8 alpha |c| of the missing state is left in it
-// (with four tiles it was 5.9e-5: ~1e-5 of a unit signal at the strongest DC offset the tests use)
-constexpr int RUN1024_DCFIX_F = 33;
-// one launch per call (BigPlan::run, kernels_pfb1024.hip); no fix-up kernel: a run computes the frame in front of it itself
-int run1024_v2_launch(const Run1024Call &h, hipStream_t s, KernelTimer *timer);
-int run1024_v3_launch(const Run1024Call &h, hipStream_t s, KernelTimer *timer);
-int shard1024_launch(const Run1024Call &h, hipStream_t s, KernelTimer *timer);
 
 
 // Single-pass DC blocker + NCO mix for whole chunks of the any-M route (kernels_dc_tile.hip), a member of GenericPlan.

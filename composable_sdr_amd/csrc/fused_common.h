@@ -189,7 +189,9 @@ __device__ __forceinline__ float fast_atan2f(float y, float x)
 // ref * atan2f(y, x) for the run kernel's tail: degree-15 odd minimax polynomial (f32 evaluation error
 // <= 1.2e-7 rad), coefficients pre-scaled by ref; hp = ref*pi/2, pi = ref*pi.  Same signed-zero
 // behaviour as fast_atan2f; inputs are finite by construction (no Inf guard).
-struct PhaseK { float c[8]; float hp, pi, ref; };
+}  // namespace
+struct PhaseK { float c[8]; float hp, pi, ref; };      // (a member of Run1024Args below, which the plan and the launcher share by name)
+namespace {
 __host__ __device__ __forceinline__ PhaseK phase_consts(float ref)
 {
     PhaseK k;
@@ -208,18 +210,44 @@ inline PhaseK phase_consts_scaled(float ref)
     k.hp *= ref; k.pi *= ref; k.ref = ref;
     return k;
 }
-// Run1024Call (fused.h) into the members Run1024v2Args, Run1024v3Args and Shard1024Args have in common (by name, as DcConsts::put; the
-// structs keep their own layouts: k_run1024v3 reads members at fixed kernarg offsets)
-template <class Args> inline void put_run1024(const Run1024Call &h, Args &A)
-{
-    A.x = h.x; A.out = h.out; A.taps_q = h.taps_q; A.tw = h.tw;
-    A.uhist_in = h.uhist_in; A.uhist_out = h.uhist_out; A.vend_in = h.vend_in; A.vend_out = h.vend_out;
-    A.rp_in = h.rp_in; A.rp_out = h.rp_out;
-    A.nf = h.nf; A.nb = h.nf / 4; A.nruns = h.nruns; A.parity0 = h.parity0;
-    h.dc->put(A);
-    A.fm_ref = h.fm_ref; A.tiny = 1e-37f;
-    A.pk = phase_consts_scaled(h.fm_ref);               // unscaled polynomial (fm_quad scales a = min / max by ref)
-}
+}  // namespace
+// Kernel arguments of the M = 1024 run kernels k_run1024v2, k_run1024v3, k_shard1024 and of k_run1024_dcfix: one struct, filled by
+// BigPlan::run (a field no kernel is named for is read by all three)
+struct Run1024Args {
+    const float2 *x;            // raw input of this call
+    void *out;                  // [1024 / G][nf] F32 (FM) / CF32
+    const float4 *taps_q;       // [4 q][4 pieces][256 j]: the 14 taps h[(1023 - r) + 1024 n] of branch r = 256 q + j, then conj(nco phasor) of r at even frames; behind the 64 KiB: [4 q][256 j] float2, the phasor at odd frames
+    const float2 *tw;           // e^{-j 2 pi i / 1024}
+    const float2 *uhist_in; float2 *uhist_out;    // [13][1024] pre-mixed, DC-blocked window before / after the call
+    const float2 *vend_in; float2 *vend_out;      // DC blocker state v1
+    const float2 *rp_in; float2 *rp_out;          // [1024] freqdem r', indexed by the primed channel k' (interleaved shards: the plan's tables carry the shift by g channels)
+    uint32_t nf, nb, nruns, parity0;              // nb = nf / 4 tiles of four frames; nruns: KernelChoice::runs
+    uint32_t n0, out_stride;    // k_run1024v2: tiles of the first half of the runs (halves_n0; 0: even split), frames per output row
+    uint32_t tile_major;        // k_run1024v3<CF32>, k_shard1024<CF32>: the 128-byte lines of a 16-frame block back to back, [block][1024 / G][128 B] (the plane k_agc_spec_tm reads), instead of rows
+    unsigned long long *trace;  // debug builds (-DB3_TRACE / -DS1_TRACE): s_memtime stamps of run 1, RUN1024_V3_TRACE_N / SHARD1024_TRACE_N of them
+    float alpha, beta, l2beta, fm_ref, tiny;
+    float b16[16];              // beta^(16 r)
+    float b256[17];             // beta^(256 g)
+    PhaseK pk;                  // unscaled polynomial (fm_quad scales a = min / max by ref)
+    // k_run1024v3, k_shard1024 (as k_run256v2: DESIGN 4).  nowu = 1: a run starts cold from DC state 0 (no read-only warm-up tiles).  Always:
+    // a run leaves the state in front of tile last - 4 in cpre[w + 1] and (FM) the uncorrected Y of its frames -1 .. 31 in side, for
+    // k_run1024_dcfix: [w][4][RUN1024_DCFIX_F] of the channels 510..513 (k_run1024v3), [w][RUN1024_DCFIX_F] of row mfix (k_shard1024: the
+    // shard's owned channel among those four, -1: none)
+    uint32_t nowu;
+    int mfix;
+    float2 *cpre, *side;
+};
+// One call of those kernels (run1024_launch, fused.h): the arguments and what only the host reads
+struct Run1024Call {
+    Run1024Args a;
+    int id;                     // K_RUN1024V2, K_RUN1024V3 or K_SHARD1024 (kernel_choice.h)
+    bool fm;                    // F32 freqdem output (k_run1024v2: always)
+    uint32_t G = 1;             // k_run1024v2, k_shard1024: chan_stride of the interleaved shard
+    const float2 *rt = nullptr; // cold calls (a.nowu): [2][RUN1024_DCFIX_F][4] the chain's response to a unit DC state at the corrected channels
+    double weight = 1.2;        // k_run1024v2: tile share of the older workgroup of a CU (1 = even; CSDR_RUN1024_WEIGHT)
+    const char *trace_file = nullptr;   // a.trace: the file the last launch's stamps go to (CSDR_RUN1024_V3_TRACE, CSDR_SHARD1024_TRACE)
+};
+namespace {
 // Selects with the condition in an SGPR pair: on gfx950 the VCC form of v_cndmask (what hipcc emits for `c ? a : b`) costs
 // 16 cycles per wave, the SGPR-mask form 4.6 (tools/probes/issue_probe2.hip).
 __device__ __forceinline__ float sel_abs_gt(float a, float b, float t, float f)        // |a| > |b| ? t : f
@@ -443,7 +471,7 @@ __device__ __forceinline__ float2 frame_carry_zero_state(const float2 *T, const 
 
 constexpr int WU = 6;
 
-// (RunSplit, run_range, make_split -- how a launch's tiles are split into runs: run_split.h)
+// (how a launch's tiles are split into runs, and DCFIX_F: run_split.h)
 
 struct RunArgs {
     TileArgs t;
@@ -467,7 +495,6 @@ struct RunArgs {
     uint32_t nowu;
     float2 *cpre, *side;
 };
-constexpr int DCFIX_F = 113;    // frame -1 of a run (freqdem history) + its first seven tiles
 
 __device__ __forceinline__ float2 wg_sum(float2 v, float2 *red, int tid)
 {

@@ -1,9 +1,10 @@
-// Which kernel a chain call of nf frames takes, and with how many runs: KernelChoice, the run counts of the run kernels and the selection
-// of the M = 64 and M = 1024 plans.  Pure functions of the configuration, the knobs the plan read when it was made, the CU count and nf.
-// Included by the plans through fused.h and, on its own, by host-only programs (tests/test_kernel_choice.py): nothing here needs the
-// HIP headers.
+// Which kernel a chain call of nf frames takes, and with how many runs: KernelChoice, the run counts of the run kernels, whether their
+// runs start cold, and the selection of the M = 64 and M = 1024 plans.  Pure functions of the configuration, the knobs the plan read when
+// it was made, the CU count and nf.  Included by the plans through fused.h and, on its own, by host-only programs
+// (tests/test_kernel_choice.py, tests/test_run_bounds_cpu.py): nothing here needs the HIP headers.
 #pragma once
 
+#include "run_split.h"
 #include <cstdint>
 
 namespace csdr {
@@ -73,6 +74,19 @@ inline uint32_t shard1024_runs(uint32_t nf, bool fm, uint32_t G, uint32_t cus, u
     if (nruns > nblk / per) nruns = nblk / per;
     return nruns;
 }
+
+// ---- cold starts: whether the runs of a launch start from DC state 0, with the kernel's dcfix launch behind them.  The shape
+// half: there is a run >= 1, and every run is at least as long as what its dcfix kernel covers (run_split.h).  The capacity half is
+// ColdStart::fits (fused.h): the plan's arrays were made for at least this many runs.  A plan combines the two into one flag per call.
+constexpr uint32_t RUN64_COLD_TILES = 2 * (RUN64_DCFIX_F / 64);                                         // 14: the seven dcfix tiles, doubled
+constexpr uint32_t RUN1024_COLD_TILES = (RUN1024_HALO + (RUN1024_DCFIX_F - 1) / 4 + 7) / 8 * 8;         // 16: 4 halo + 8 dcfix tiles, in whole blocks of 8
+inline bool run64_v2_cold(uint32_t nb, uint32_t nruns) { return nruns >= 2 && nb / nruns >= RUN64_COLD_TILES; }
+inline bool run1024_v3_cold(uint32_t nb, uint32_t nruns) { return nruns >= 2 && nb / nruns >= RUN1024_COLD_TILES; }
+inline bool shard1024_cold(uint32_t nruns) { return nruns >= 2; }        // (shard1024_runs: at least 16 tiles per run)
+inline bool run256_v2_cold(uint32_t nruns) { return nruns >= 2; }        // (make_split: at least 8 tiles per run, the seven of its dcfix among them)
+// Runs the cold-start arrays are made for (ColdStart::init).  M = 1024: the plan's CU count, the most its run counts above return
+constexpr uint32_t RUN64_COLD_RUNS = 1024, RUN256_COLD_RUNS = 2048;
+inline bool cold_fits(uint32_t made_for, uint32_t nruns) { return nruns <= made_for; }
 
 // k_front4096.  Frames per run: long enough that the 19 cold-start frames (about 8 frames' worth of work) stay below ~8 % of a run
 inline uint32_t huge_runs(uint32_t nf, uint32_t cus, uint32_t runs_knob)

@@ -444,7 +444,7 @@ int FusedPlan::init()
     // behind the tile's start = frame -1 .. 111 of the run that started its halo tile without its state (k_run256_dcfix: 112 frames); by
     // then the step's edge (13 frames of FIR, every channel) has left the filter and what remains sits around DC.
     if (cfg.G == 1 && cfg.c0 == 0 && cfg.C == cfg.M &&
-        (r = cold.init(mem, cfg, (DCFIX_F - 1) * 256.0, 2050, (size_t)2048 * 4 * DCFIX_F, false, 15u, (uint32_t)DCFIX_F, 126, wpre.data()))) return r;
+        (r = cold.init(mem, cfg, (DCFIX_F - 1) * 256.0, RUN256_COLD_RUNS, (size_t)4 * DCFIX_F, false, 15u, (uint32_t)DCFIX_F, 126, wpre.data()))) return r;
     CSDR_HIP(hipMemset(d_status, 0, sizeof(unsigned)));
     CSDR_HIP(hipMemset(d_yflag, 0, sizeof(unsigned) * max_nb));
     CSDR_HIP(hipMemset(d_agg, 0, sizeof(u64) * 2 * max_nb));
@@ -570,8 +570,8 @@ int FusedPlan::run_kernel(const FusedCall &call, const TileArgs &A, uint32_t nru
     RA.tile_step = call.tile_major ? c.C * 128u : (uint32_t)NB * (c.fm ? 4u : 8u);
     RA.indep = call.indep ? 1u : 0u;     // (process() has checked can_overlap)
     // whole band, dependent launches: no warm-up windows (the DC state a run misses at its start is put back, where it still matters 16 frames
-    // later -- the four channels around DC -- by k_run256_dcfix behind the launch); runs of >= 8 tiles, <= 2048 of them
-    RA.nowu = (cold.rt && !shard && !RA.indep && nruns >= 2 && nruns <= 2048) ? 1u : 0u;
+    // later -- the four channels around DC -- by k_run256_dcfix behind the launch); runs of >= 8 tiles, as many as the arrays are made for
+    RA.nowu = (cold.fits(nruns) && run256_v2_cold(nruns) && !shard && !RA.indep) ? 1u : 0u;
     RA.prev_tail = d_tail[tail_w];
     if (save_tails && !shard && call.nf == A.nb * NB && A.nb >= WU + 1) {
         // this chunk's last WU + 1 tiles, for run 0 of the next call (queued in front of the launch: the copy only reads the input)

@@ -397,7 +397,7 @@ int SmallPlan::init()
     if (const char *e = diag_env("CSDR_RUN64_WEIGHT")) v2_weight = atof(e);
     // k_run64v2 without warm-up windows: the state hand-over array and the chain's response to a unit DC state at the channels 30..33,
     // frames 64 .. 64 + RUN64_DCFIX_F - 1 behind a halo tile's start (= the run's first output frames)
-    if (pick.v2() && (r = cold.init(mem, cfg, RUN64_DCFIX_F * 64.0, 1026, 0, false, 64u, (uint32_t)RUN64_DCFIX_F, 30, wpre.data()))) return r;
+    if (pick.v2() && (r = cold.init(mem, cfg, RUN64_DCFIX_F * 64.0, RUN64_COLD_RUNS, 0, false, 64u, (uint32_t)RUN64_DCFIX_F, 30, wpre.data()))) return r;
     return 0;
 }
 
@@ -414,7 +414,7 @@ int SmallPlan::run(const FusedCall &call, KernelChoice k, void *out, hipStream_t
         H.vend_in = st.vend_in(cur); H.vend_out = st.vend_out(cur);
         H.nf = nf; H.nruns = k.runs; H.parity0 = (uint32_t)(frames_done & 1);
         H.tile_major = call.tile_major;
-        H.cpre = k.runs <= 1024u ? cold.cpre : nullptr; H.rt = cold.rt;
+        H.cpre = cold.cpre; H.rt = cold.rt; H.cold = cold.fits(k.runs) && run64_v2_cold(nf / 64u, k.runs);
         H.dc = &dcc; H.weight = v2_weight;
         return run64_v2_launch(H, s, timer);
     }

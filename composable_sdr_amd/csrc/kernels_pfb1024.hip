@@ -88,7 +88,8 @@ __global__ __launch_bounds__(1024) void k_pfb1024(Pfb1024Args A)
     { const int k1 = tid >> 6, m = tid & 63; tw1[tid] = A.tw[(m * k1) & 1023]; }
     if (tid < 64) { const int k2 = tid >> 2, n3 = tid & 3; tw2[tid] = A.tw[(16 * n3 * k2) & 1023]; }
     const uint32_t w = blockIdx.x;
-    const uint32_t first = (uint32_t)((uint64_t)w * A.nb / A.nruns), last = (uint32_t)((uint64_t)(w + 1) * A.nb / A.nruns);
+    uint32_t first, last;
+    run_range_even(A.nb, A.nruns, w, first, last);
     if (first >= last) return;
 
     const bool owned = (uint32_t)tid >= A.c0 && (uint32_t)tid < A.c0 + A.C;
@@ -409,11 +410,12 @@ __global__ __launch_bounds__(1024) void k_pfb1024_fixup(Pfb1024Args A)
 {
     const uint32_t w = blockIdx.x + 1, k = threadIdx.x;
     if (k < A.c0 || k >= A.c0 + A.C) return;
-    const uint32_t first = (uint32_t)((uint64_t)w * A.nb / A.nruns), last = (uint32_t)((uint64_t)(w + 1) * A.nb / A.nruns);
+    uint32_t first, last, pf, pl;
+    run_range_even(A.nb, A.nruns, w, first, last);
     if (first >= last) return;
     // the run before w that is not empty
     uint32_t wp = w - 1;
-    while (wp > 0 && (uint32_t)((uint64_t)wp * A.nb / A.nruns) >= (uint32_t)((uint64_t)(wp + 1) * A.nb / A.nruns)) wp--;
+    while (wp > 0 && (run_range_even(A.nb, A.nruns, wp, pf, pl), pf >= pl)) wp--;
     ((float *)A.out)[(size_t)(k - A.c0) * A.nf + (size_t)first * PT] = fm_sample_rn(A.ylast[(size_t)wp * PM + k], A.yfirst[(size_t)w * PM + k], A.ref);
 }
 
@@ -458,14 +460,14 @@ struct BigPlan : ChainPlan {
     float *d_taps = nullptr;
     float4 *d_taps_t = nullptr, *d_taps_q = nullptr;
     Choice1024 pick{};                        // which of the plan's four kernels a call takes (kernel_choice.h): cfg, cus and the knobs, fixed by init()
-    int s1_mfix = -1;                         // the shard's row among the four channels around DC (k_shard1024_dcfix), -1: none
+    int s1_mfix = -1;                         // the shard's row among the four channels around DC (Run1024Args::mfix), -1: none
     float2 *d_tw = nullptr, *d_wpre = nullptr;
     StreamState st;
     float2 *d_scratch = nullptr;     // yfirst | ylast
     void *d_full = nullptr;          // interleaved shard, calls k_run1024v2 does not take: whole-band result [1024][max_nf] (allocated on first use)
-    ColdStart cold;                  // k_run1024v3 / k_shard1024 without warm-up windows (Run1024Call::cpre / side / rt)
+    ColdStart cold;                  // k_run1024v3 / k_shard1024 without warm-up windows (Run1024Args::cpre / side, Run1024Call::rt)
     double v2_weight = 1.2;          // CSDR_RUN1024_WEIGHT (Run1024Call::weight)
-    unsigned long long *d_trace = nullptr; std::string trace_file;      // CSDR_RUN1024_V3_TRACE / CSDR_SHARD1024_TRACE (Run1024Call::trace)
+    unsigned long long *d_trace = nullptr; std::string trace_file;      // CSDR_RUN1024_V3_TRACE / CSDR_SHARD1024_TRACE (Run1024Args::trace)
     Pfb1024Args proto;               // what init() fixes of a k_pfb1024 launch
 
     int init();
@@ -559,13 +561,13 @@ int BigPlan::init()
         s1_mfix = -1;
         uint32_t kp = 0;
         for (uint32_t k = 510; k <= 513; k++) if ((k + (uint32_t)PM - cfg.c0) % cfg.G == 0) { kp = (k + (uint32_t)PM - cfg.c0) % (uint32_t)PM; s1_mfix = (int)(kp / cfg.G); }
-        if ((rc = cold.init(mem, cfg, 12 * 4096.0, cus + 2, (size_t)(cus + 1) * RUN1024_DCFIX_F, true, 15u, (uint32_t)RUN1024_DCFIX_F,
+        if ((rc = cold.init(mem, cfg, 12 * 4096.0, cus, (size_t)RUN1024_DCFIX_F, true, 15u, (uint32_t)RUN1024_DCFIX_F,
                             s1_mfix >= 0 ? (int)kp : -1, wpre.data()))) return rc;
     }
     // k_run1024v3's state hand-over and the side copies of the four channels around DC (510..513): the kernel always writes them (a few
     // hundred bytes per run); launches without warm-up windows (dc_block, not CSDR_NOWU=0) also get the chain's response to a unit DC state
     // at those channels, frames 15 .. 47 behind a cold start (= frame -1 .. 31 of the run).  Window: halo + 32-frame dcfix
-    if (pick.v3() && (rc = cold.init(mem, cfg, 35 * 1024.0, cus + 2, (size_t)(cus + 1) * 4 * RUN1024_DCFIX_F, true, 15u, (uint32_t)RUN1024_DCFIX_F,
+    if (pick.v3() && (rc = cold.init(mem, cfg, 35 * 1024.0, cus, (size_t)4 * RUN1024_DCFIX_F, true, 15u, (uint32_t)RUN1024_DCFIX_F,
                                  510, wpre.data()))) return rc;
     // k_run1024 (the calls no run kernel above takes)
     proto = Pfb1024Args{};
@@ -585,25 +587,20 @@ int BigPlan::run(const FusedCall &call, KernelChoice k, void *out, hipStream_t s
     int r;
     if (k.id != K_RUN1024) {
         Run1024Call H{};
-        H.x = call.d_in; H.out = out; H.taps_q = d_taps_q; H.tw = d_tw;
-        H.uhist_in = st.hist_in(cur); H.uhist_out = st.hist_out(cur);
-        H.vend_in = st.vend_in(cur); H.vend_out = st.vend_out(cur);
-        H.rp_in = st.rp_in(cur); H.rp_out = st.rp_out(cur);
-        H.nf = nf; H.nruns = k.runs; H.parity0 = (uint32_t)(frames_done & 1);
-        H.fm = c.fm; H.G = c.G; H.g = c.G > 1 ? c.c0 : 0u;
-        H.tile_major = call.tile_major;      // (process() has checked tile_major_ok: CF32 through k_run1024v3 or k_shard1024)
-        H.dc = &dcc; H.fm_ref = c.fm_ref; H.weight = v2_weight;
-        if (d_trace) { H.trace = d_trace; H.trace_file = trace_file.c_str(); }
-        switch (k.id) {
-        case K_SHARD1024:
-            H.cpre = cold.cpre; H.side = cold.side; H.rt = cold.rt; H.mfix = s1_mfix;
-            return shard1024_launch(H, s, timer);
-        case K_RUN1024V3:
-            H.cpre = cold.cpre; H.side = cold.side; H.rt = k.runs <= cus ? cold.rt : nullptr;
-            return run1024_v3_launch(H, s, timer);
-        default:
-            return run1024_v2_launch(H, s, timer);
-        }
+        Run1024Args &A = H.a;
+        A.x = call.d_in; A.out = out; A.taps_q = d_taps_q; A.tw = d_tw;
+        A.uhist_in = st.hist_in(cur); A.uhist_out = st.hist_out(cur);
+        A.vend_in = st.vend_in(cur); A.vend_out = st.vend_out(cur);
+        A.rp_in = st.rp_in(cur); A.rp_out = st.rp_out(cur);
+        A.nf = nf; A.nb = nf / 4; A.nruns = k.runs; A.parity0 = (uint32_t)(frames_done & 1); A.out_stride = nf;
+        A.tile_major = (!c.fm && call.tile_major) ? 1u : 0u;     // (process() has checked tile_major_ok: CF32 through k_run1024v3 or k_shard1024)
+        dcc.put(A);
+        A.fm_ref = c.fm_ref; A.tiny = 1e-37f; A.pk = phase_consts_scaled(c.fm_ref);
+        A.trace = d_trace; A.cpre = cold.cpre; A.side = cold.side; A.mfix = k.id == K_SHARD1024 ? s1_mfix : -1;
+        // cold starts: the arrays fit the launch and its runs are long enough for the kernel's correction (k_run1024v2: always warm)
+        A.nowu = cold.fits(k.runs) && (k.id == K_SHARD1024 ? shard1024_cold(k.runs) : k.id == K_RUN1024V3 && run1024_v3_cold(A.nb, k.runs)) ? 1u : 0u;
+        H.id = k.id; H.fm = c.fm; H.G = c.G; H.rt = cold.rt; H.weight = v2_weight; H.trace_file = trace_file.c_str();
+        return run1024_launch(H, s, timer);
     }
     // k_run1024: the calls no run kernel takes
     Pfb1024Args A = proto;

@@ -73,7 +73,9 @@ __global__ __launch_bounds__(512, 1) void k_front4096(Front4096Args A)
     unsigned c, run;
     if ((A.nruns & 7u) == 0) { c = (w >> 3) & 3u; run = (w & 7u) + 8u * (w >> 5); }
     else { c = w & 3u; run = w >> 2; }
-    const int first = (int)((unsigned long long)run * A.nf / A.nruns), last = (int)((unsigned long long)(run + 1) * A.nf / A.nruns);
+    uint32_t first_u, last_u;
+    run_range_even(A.nf, A.nruns, run, first_u, last_u);    // (of frames)
+    const int first = (int)first_u, last = (int)last_u;
     if (first >= last) return;
     const int full_from = first - (run == 0 ? 1 : 0), t_begin = first - H_COLD, n = last - t_begin;
     auto tile_ptr = [&](int t) -> const float4 * { return t >= 0 ? A.x + (size_t)t * 2048 : A.tail + (size_t)(H_COLD + t) * 2048; };

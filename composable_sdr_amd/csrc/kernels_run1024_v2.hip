@@ -46,39 +46,11 @@ constexpr int B2_TW1 = 2 * B2_BUF;                 // twiddles W1024^(k1 b) at [
 constexpr int B2_ST = B2_TW1 + 960;                // FM: last Y frame of channel kk + 256 k3 at [kk][k3]: 1024 (the prologue's reduction scratch before that)
 constexpr int B2_TT = B2_ST + 1024;                // 16 group totals
 constexpr int B2_F2 = B2_TT + 16;                  // 10 192 float2 = 81 536 B: two workgroups per CU (81 920 each)
-constexpr int B2_WU = 6, B2_HALO = 4;              // read-only warm-up tiles (DC state), window refill tiles (13 frames of history)
+constexpr int B2_WU = RUN1024_WU, B2_HALO = RUN1024_HALO;     // read-only warm-up tiles (DC state), window refill tiles (13 frames of history): run_split.h
+static_assert(B2_T4 == 4, "Run1024Args::nb: tiles of four frames");
 
-struct Run1024v2Args {
-    const float2 *x;            // raw input of this call
-    void *out;                  // [1024][out_stride] F32 (FM) or CF32
-    const float4 *taps_q;       // [4 q][4 pieces][256 j]: the 14 taps h[(1023 - r) + 1024 n] of branch r = 256 q + j, then conj(nco phasor) of r at even frames; behind the 64 KiB: [4 q][256 j] float2, the phasor at odd frames
-    const float2 *tw;           // e^{-j 2 pi i / 1024}
-    const float2 *uhist_in; float2 *uhist_out;    // [13][1024] pre-mixed, DC-blocked window before / after the call
-    const float2 *vend_in; float2 *vend_out;      // DC blocker state v1
-    const float2 *rp_in; float2 *rp_out;          // [1024] freqdem r'
-    uint32_t nf, nb, nruns, n0, parity0, out_stride;   // n0: tiles of the first half of the runs (0: even split)
-    uint32_t g;                 // G > 1: shard index (informational: the tables carry the shift by g channels, see the kernel)
-    float alpha, beta, l2beta, fm_ref, tiny;
-    float b16[16];              // beta^(16 r)
-    float b256[17];             // beta^(256 g)
-    PhaseK pk;
-};
-
-// Run w of a launch.  nruns = two per CU: the first half (the workgroups dispatched first, the older ones of their CUs) win the
-// issue arbitration and get n0 of the nb tiles, the second half the rest (k_run256v2: both end together at about 1.2 : 0.8).
-// Output blocks are aligned to absolute tile indices, so a run may start and end inside a block (partial lines there).
-__host__ __device__ __forceinline__ void run_bounds(uint32_t nb, uint32_t nruns, uint32_t n0, unsigned w, unsigned &first, unsigned &last)
-{
-    if (n0 == 0 || (nruns & 1u)) {
-        first = (unsigned)((unsigned long long)w * nb / nruns);
-        last = (unsigned)((unsigned long long)(w + 1) * nb / nruns);
-        return;
-    }
-    const unsigned half = nruns / 2, s = w / half, i = w - s * half;
-    const unsigned base = s ? n0 : 0u, tiles = s ? nb - n0 : n0;
-    first = base + (unsigned)((unsigned long long)i * tiles / half);
-    last = base + (unsigned)((unsigned long long)(i + 1) * tiles / half);
-}
+// (Run1024Args: fused_common.h.  Run w of a launch: run_range_halves, run_split.h -- nruns = two per CU, the older half gets n0 of the nb
+// tiles.  Output blocks are aligned to absolute tile indices, so a run may start and end inside a block: partial lines there.)
 
 // G > 1: INTERLEAVED CHANNEL SHARD g of G (G = 2, 4, 8; FM output).  The host folds a shift of the spectrum by g channels,
 // W1024^(r g) on branch r, into the pre-mix phasors of the tap table (free: the FIR is linear), so that this kernel -- and the
@@ -90,7 +62,7 @@ __host__ __device__ __forceinline__ void run_bounds(uint32_t nb, uint32_t nruns,
 // directly: 512 workgroups x 1024/G rows keep 64/G MiB of lines open, which the L2s hold for G = 8 and mostly for G = 4 (the
 // staging block of the whole-band path exists because 64 MiB are not held).
 template <bool FM, int G>
-__global__ __launch_bounds__(256, 2) void k_run1024v2(Run1024v2Args A)
+__global__ __launch_bounds__(256, 2) void k_run1024v2(Run1024Args A)
 {
     static_assert(FM && (G == 2 || G == 4 || G == 8), "interleaved shards only: F32 output, G = 2, 4, 8");
     __shared__ __attribute__((aligned(16))) float2 L[B2_F2];
@@ -98,7 +70,7 @@ __global__ __launch_bounds__(256, 2) void k_run1024v2(Run1024v2Args A)
     const int tid = threadIdx.x, j = tid;
     const unsigned w = blockIdx.x;
     unsigned first, last;
-    run_bounds(A.nb, A.nruns, A.n0, w, first, last);
+    run_range_halves(A.nb, A.nruns, A.n0, w, first, last);
     const float4 *x4 = reinterpret_cast<const float4 *>(A.x);
     const int col_off = 16 * (j >> 4) + 2 * (((j & 15) >> 1) ^ (j >> 5)) + (j & 1);
 
@@ -420,25 +392,12 @@ __global__ __launch_bounds__(256, 2) void k_run1024v2(Run1024v2Args A)
 
 }  // namespace
 
-int run1024_v2_launch(const Run1024Call &h, hipStream_t s, KernelTimer *timer)
+// the launcher's table (run1024_launch): the instantiation for chan_stride G
+Run1024Kernel run1024_v2_kernel(bool fm, uint32_t G)
 {
-    static_assert(B2_T4 == 4, "put_run1024: tiles of four frames");
-    Run1024v2Args A{};
-    put_run1024(h, A);
-    A.out_stride = h.nf; A.g = h.g;
-    const double wt = h.weight;
-    A.n0 = (h.nruns >= 2 && !(h.nruns & 1u) && wt > 1.0 && wt < 1.5) ? (uint32_t)std::llround(0.5 * wt * (double)A.nb) : 0u;
-    int r;
-    if (timer && (r = timer->begin(s))) return r;
-    if (h.G > 1 && !h.fm) { set_error("k_run1024v2: interleaved shards have F32 output only"); return -1; }
-    if (h.G == 2) hipLaunchKernelGGL((k_run1024v2<true, 2>), dim3(h.nruns), dim3(256), 0, s, A);
-    else if (h.G == 4) hipLaunchKernelGGL((k_run1024v2<true, 4>), dim3(h.nruns), dim3(256), 0, s, A);
-    else if (h.G == 8) hipLaunchKernelGGL((k_run1024v2<true, 8>), dim3(h.nruns), dim3(256), 0, s, A);
-    else if (h.G > 1) { set_error("k_run1024v2: interleaved shards of stride %u are not built (2, 4, 8)", h.G); return -1; }
-    else { set_error("k_run1024v2: interleaved shards only (whole band: k_run1024v3 / k_run1024)"); return -1; }
-    if (timer && (r = timer->end(s))) return r;
-    CSDR_HIP(hipGetLastError());
-    return 0;
+    const void *fn = !fm ? nullptr : G == 2 ? (const void *)k_run1024v2<true, 2> : G == 4 ? (const void *)k_run1024v2<true, 4>
+                   : G == 8 ? (const void *)k_run1024v2<true, 8> : nullptr;
+    return {fn, 256u, 0};
 }
 
 }  // namespace csdr

@@ -33,10 +33,11 @@
 // What did not help: starting the runs of a CU group in different steps so that the blocks do not complete together (+3 %: the burst is
 // not an HBM problem), the tile DMA in the front waves' queue (in-order vmcnt: the first tap use then waits for the image).
 #include "fused_v2_common.h"
+#include <cstdio>
 #include <type_traits>
 
 #ifndef B3_TRACE
-#define B3_TRACE 0       // 1: s_memtime stamps of run 1's wave 0 / wave 4 per phase (12 KiB of LDS), written to Run1024v3Args::trace
+#define B3_TRACE 0       // 1: s_memtime stamps of run 1's wave 0 / wave 4 per phase (12 KiB of LDS), written to Run1024Args::trace
 #endif
 #ifndef B3_ABLATE
 #define B3_ABLATE 0      // timing experiments only (wrong results): 2 no output stores, 4 no freqdem, 8 row stores straight out of the registers (no LDS
@@ -54,38 +55,11 @@ constexpr int B3_ST = B3_TW1 + 960;                // last Y frame of channel kk
 constexpr int B3_TT = B3_ST + 1024;                // 16 group totals
 constexpr int B3_TW2 = B3_TT + 16;                 // pass-2 twiddles W64^(d k2) at [k2][d]: 64 (the three d of an instruction in three banks; tw1 has them 2 KiB apart)
 constexpr int B3_F2 = B3_TW2 + 64;                 // 18 448 float2 = 147 584 B: one workgroup per CU
-constexpr int B3_WU = 6, B3_HALO = 4;              // read-only warm-up tiles (DC state); 3 window-refill tiles + the muted tile in front of a run
-
-struct Run1024v3Args {
-    const float2 *x;            // raw input of this call
-    void *out;                  // [1024][nf] F32 (FM) / CF32
-    const float4 *taps_q;       // k_run1024v2's table: [4 q][4 pieces][256 j] taps + even-frame phasor; behind the 64 KiB: [4 q][256 j] odd-frame phasor
-    const float2 *tw;           // e^{-j 2 pi i / 1024}
-    const float2 *uhist_in; float2 *uhist_out;    // [13][1024] pre-mixed, DC-blocked window before / after the call
-    const float2 *vend_in; float2 *vend_out;      // DC blocker state v1
-    const float2 *rp_in; float2 *rp_out;          // [1024] freqdem r'
-    uint32_t nf, nb, nruns, parity0;
-    uint32_t tile_major;        // CF32: lines of a block back to back, [block][1024][128 B] (the plane k_agc_spec_tm reads), instead of rows [1024][nf]
-    unsigned long long *trace;  // debug (CSDR_RUN1024_V3_TRACE=file): s_memtime stamps of run 1's wave 0 (front) and wave 4 (back), [role][step][4]
-    float alpha, beta, l2beta, fm_ref, tiny;
-    float b16[16];              // beta^(16 r)
-    float b256[17];             // beta^(256 g)
-    PhaseK pk;
-    uint32_t nowu;              // 1: a run starts cold from DC state 0 (no read-only warm-up tiles), leaves the state in front of tile last - 4 in
-    float2 *cpre, *side;        //    cpre[w + 1] and (FM) the uncorrected Y of the channels 510..513 of its frames -1 .. 31 in side; k_run1024_dcfix
-};
-
-// run w: blocks of TB tiles, evenly; the call's last block may be a partial one (nb % TB tiles: its rows get the front part of a line)
-__host__ __device__ __forceinline__ void run3_bounds(uint32_t nb, uint32_t nruns, unsigned w, unsigned TB, unsigned &first, unsigned &last)
-{
-    const unsigned nblk = (nb + TB - 1) / TB;
-    first = TB * (unsigned)((unsigned long long)w * nblk / nruns);
-    last = TB * (unsigned)((unsigned long long)(w + 1) * nblk / nruns);
-    if (last > nb) last = nb;
-}
+constexpr int B3_WU = RUN1024_WU, B3_HALO = RUN1024_HALO;     // read-only warm-up tiles (DC state); 3 window-refill tiles + the muted tile in front of a run (run_split.h)
+static_assert(B3_T4 == 4, "Run1024Args::nb: tiles of four frames");
 
 template <bool FM>
-__global__ __launch_bounds__(512) void k_run1024v3(Run1024v3Args A)
+__global__ __launch_bounds__(512) void k_run1024v3(Run1024Args A)     // (run w: run_range_blocks, run_split.h)
 {
     constexpr unsigned B3_TB = FM ? B3_TBF : B3_TBC;
     __shared__ __attribute__((aligned(16))) float2 L[B3_F2];
@@ -97,7 +71,7 @@ __global__ __launch_bounds__(512) void k_run1024v3(Run1024v3Args A)
     const int lt = tid & 255, j = lt;                   // thread index inside the role; front: polyphase branches j + 256 q
     const unsigned w = blockIdx.x;
     unsigned first, last;
-    run3_bounds(A.nb, A.nruns, w, B3_TB, first, last);
+    run_range_blocks(A.nb, A.nruns, w, B3_TB, first, last);
     const float4 *x4 = reinterpret_cast<const float4 *>(A.x);
     const int col_off = 16 * (j >> 4) + 2 * (((j & 15) >> 1) ^ (j >> 5)) + (j & 1);
     const unsigned goff = dma_offset(lt);
@@ -408,7 +382,7 @@ __global__ __launch_bounds__(512) void k_run1024v3(Run1024v3Args A)
                 // 510, 511 = threads 254, 255 at k3 = 1; 512, 513 = threads 0, 1 at k3 = 2)
                 const int chs = lt >= 254 ? lt - 254 : (lt < 2 ? lt + 2 : -1);
                 if (chs >= 0) {
-                    float2 *sd = kernarg_ptr_s<offsetof(Run1024v3Args, side)>() + ((size_t)w * 4 + (unsigned)chs) * RUN1024_DCFIX_F;
+                    float2 *sd = kernarg_ptr_s<offsetof(Run1024Args, side)>() + ((size_t)w * 4 + (unsigned)chs) * RUN1024_DCFIX_F;
                     const int i0 = 4 * (int)(b + 1u - first) - 3;          // frame f of this tile -> slot i0 + f (slot 0 = frame -1)
 #pragma unroll
                     for (int f = 0; f < 4; f++)
@@ -511,30 +485,32 @@ __global__ __launch_bounds__(512) void k_run1024v3(Run1024v3Args A)
     }
 }
 
-// What the DC state a run started without contributes to the channels 510..513 over the run's first 32 frames: Y += cpre[w] x R (the chain
-// is linear up to Y).  CF32: in place on the rows (row-major or the tile-major plane); FM: freqdem of the corrected side copies.
+// What the DC state a run started without contributes, over the run's first 32 frames, to the nch channels k0 .. k0 + nch - 1 it is still
+// seen at: Y += cpre[w] x R (the chain is linear up to Y).  k_run1024v3: the four channels 510..513 of its 1024 rows; k_shard1024: the one
+// owned row mfix of its 1024 / G.  32 nch threads.  CF32: in place on the rows (row-major or the tile-major plane); FM: freqdem of the
+// corrected side copies.
 template <bool FM>
-__global__ __launch_bounds__(128) void k_run1024_dcfix(Run1024v3Args A, const float2 *__restrict__ rt)
+__global__ __launch_bounds__(128) void k_run1024_dcfix(Run1024Args A, const float2 *__restrict__ rt, unsigned nch, unsigned k0, unsigned rows)
 {
     constexpr unsigned B3_TB = FM ? B3_TBF : B3_TBC;
     const unsigned w = blockIdx.x + 1u, ch = threadIdx.x >> 5, fr = threadIdx.x & 31u;
     unsigned first, last;
-    run3_bounds(A.nb, A.nruns, w, B3_TB, first, last);
+    run_range_blocks(A.nb, A.nruns, w, B3_TB, first, last);
     const float2 c = A.cpre[w];
     const unsigned par = A.parity0 & 1u;                // a tile is 4 frames: every cold start begins on the call's parity
     const float2 *R = rt + (size_t)par * RUN1024_DCFIX_F * 4;
     auto corr = [&](unsigned i) { const float2 r = R[i * 4u + ch]; return make_float2(c.x * r.x - c.y * r.y, c.x * r.y + c.y * r.x); };
     const size_t t = (size_t)4 * first + fr;            // the frame in the call
     if (t >= A.nf) return;
-    const unsigned k = 510u + ch;
+    const unsigned k = k0 + ch;
     if (FM) {
-        const float2 *sd = A.side + ((size_t)w * 4 + ch) * RUN1024_DCFIX_F;
+        const float2 *sd = A.side + ((size_t)w * nch + ch) * RUN1024_DCFIX_F;
         const float2 p0 = sd[fr], p1 = sd[fr + 1u], d0 = corr(fr), d1 = corr(fr + 1u);
         const FmK fk = {A.tiny, A.fm_ref, A.pk.hp, A.pk.pi};
         reinterpret_cast<float *>(A.out)[(size_t)k * A.nf + t] =
             fm_sample(make_float2(p0.x + d0.x, p0.y + d0.y), make_float2(p1.x + d1.x, p1.y + d1.y), fk);
     } else {
-        float2 *o = reinterpret_cast<float2 *>(A.out) + (A.tile_major ? ((t >> 4) * 1024u + k) * 16u + (t & 15u) : (size_t)k * A.nf + t);
+        float2 *o = reinterpret_cast<float2 *>(A.out) + (A.tile_major ? ((t >> 4) * rows + k) * 16u + (t & 15u) : (size_t)k * A.nf + t);
         const float2 d1 = corr(fr + 1u);
         float2 y = *o;
         y.x += d1.x; y.y += d1.y;
@@ -542,33 +518,62 @@ __global__ __launch_bounds__(128) void k_run1024_dcfix(Run1024v3Args A, const fl
     }
 }
 
+// the debug trace of a launch: before = zero the n stamps in front of it; else wait for it and write them, raw uint64, to the file
+int trace_dump(const Run1024Call &h, size_t n, bool before, hipStream_t s)
+{
+    if (!h.a.trace || !n) return 0;
+    if (before) { CSDR_HIP(hipMemsetAsync(h.a.trace, 0, n * sizeof(unsigned long long), s)); return 0; }
+    std::vector<unsigned long long> hbuf(n);
+    CSDR_HIP(hipStreamSynchronize(s));
+    CSDR_HIP(hipMemcpy(hbuf.data(), h.a.trace, n * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    if (FILE *f = fopen(h.trace_file, "wb")) { fwrite(hbuf.data(), sizeof(unsigned long long), n, f); fclose(f); }
+    return 0;
+}
+
 }  // namespace
 
-int run1024_v3_launch(const Run1024Call &h, hipStream_t s, KernelTimer *timer)
+// One call of k_run1024v2, k_run1024v3 or k_shard1024: the kernel and, behind a cold call (a.nowu: BigPlan::run has decided), the correction
+// of the channels around DC.  The timer bracket covers the correction kernel: it is part of every no-warm-up step.
+int run1024_launch(const Run1024Call &h, hipStream_t s, KernelTimer *timer)
 {
-    static_assert(B3_T4 == 4, "put_run1024: tiles of four frames");
-    const bool fm = h.fm;
-    const uint32_t nruns = h.nruns;
-    Run1024v3Args A{};
-    put_run1024(h, A);
-    A.tile_major = (!fm && h.tile_major) ? 1u : 0u;
-    A.trace = h.trace;
-    int r;
-    if ((r = h.trace_dump(RUN1024_V3_TRACE_N, true, s))) return r;
-    if (timer && (r = timer->begin(s))) return r;
-    // no warm-up windows: whole runs of >= 16 tiles (a cold start is 4 tiles deep and the correction covers 4 more), the state arrays there
-    if (!h.cpre || !h.side) { set_error("run1024_v3_launch: internal: no state arrays"); return -1; }
-    A.nowu = (h.rt && nruns >= 2 && A.nb / nruns >= 16u) ? 1u : 0u;      // (rt: the blocker is on)
-    A.cpre = h.cpre; A.side = h.side;
-    if (fm) hipLaunchKernelGGL((k_run1024v3<true>), dim3(nruns), dim3(512), 0, s, A);
-    else hipLaunchKernelGGL((k_run1024v3<false>), dim3(nruns), dim3(512), 0, s, A);
-    if (A.nowu) {
-        if (fm) hipLaunchKernelGGL((k_run1024_dcfix<true>), dim3(nruns - 1u), dim3(128), 0, s, A, h.rt);
-        else hipLaunchKernelGGL((k_run1024_dcfix<false>), dim3(nruns - 1u), dim3(128), 0, s, A, h.rt);
+    Run1024Args A = h.a;
+    Run1024Kernel k;
+    unsigned nch = 0, k0 = 0;                           // k_run1024_dcfix: channels, the first of them
+    switch (h.id) {
+    case K_RUN1024V2:
+        if (h.G > 1 && !h.fm) { set_error("k_run1024v2: interleaved shards have F32 output only"); return -1; }
+        k = run1024_v2_kernel(h.fm, h.G);
+        if (!k.fn && h.G > 1) { set_error("k_run1024v2: interleaved shards of stride %u are not built (2, 4, 8)", h.G); return -1; }
+        if (!k.fn) { set_error("k_run1024v2: interleaved shards only (whole band: k_run1024v3 / k_run1024)"); return -1; }
+        A.n0 = halves_n0(A.nb, A.nruns, h.weight);
+        break;
+    case K_RUN1024V3:
+        // the state arrays are there whatever the start: the kernel always writes them
+        if (!A.cpre || !A.side) { set_error("run1024_launch: internal: no state arrays"); return -1; }
+        k = {h.fm ? (const void *)k_run1024v3<true> : (const void *)k_run1024v3<false>, 512u, RUN1024_V3_TRACE_N};     // debug: front [128][8], back [128][4]
+        nch = 4; k0 = 510;
+        break;
+    default:
+        if (A.tile_major && (A.nf & 15u)) { set_error("k_shard1024: a tile-major plane takes whole 16-frame blocks"); return -1; }
+        k = shard1024_kernel(h.fm, h.G);                // debug: [role][96][4]
+        if (!k.fn) { set_error("k_shard1024: chan_stride %u is not built (4, 8)", h.G); return -1; }
+        if (A.mfix >= 0) { nch = 1; k0 = (unsigned)A.mfix; }
+        break;
     }
-    if (timer && (r = timer->end(s))) return r;         // the bracket covers the correction kernel: it is part of every no-warm-up step
+    if (!k.trace_n) A.trace = nullptr;                  // (the stamps of a debug build only)
+    int r;
+    if ((r = trace_dump(h, k.trace_n, true, s))) return r;
+    if (timer && (r = timer->begin(s))) return r;
+    void *args[] = {&A};
+    CSDR_HIP(hipLaunchKernel(k.fn, dim3(A.nruns), dim3(k.threads), args, 0, s));
+    if (A.nowu && nch) {
+        const unsigned rows = 1024u / h.G;
+        if (h.fm) hipLaunchKernelGGL((k_run1024_dcfix<true>), dim3(A.nruns - 1u), dim3(32u * nch), 0, s, A, h.rt, nch, k0, rows);
+        else hipLaunchKernelGGL((k_run1024_dcfix<false>), dim3(A.nruns - 1u), dim3(32u * nch), 0, s, A, h.rt, nch, k0, rows);
+    }
+    if (timer && (r = timer->end(s))) return r;
     CSDR_HIP(hipGetLastError());
-    return h.trace_dump(RUN1024_V3_TRACE_N, false, s);  // debug: front [128][8], back [128][4]
+    return trace_dump(h, k.trace_n, false, s);
 }
 static_assert(B3_TBF == 8 && B3_TBC == 4, "run1024_v3_runs (kernel_choice.h): runs of whole blocks of 8 (F32) / 4 (CF32) tiles");
 

@@ -31,7 +31,8 @@ constexpr int S2_TW = S2_HIST + 13 * 64;            // 16 x 4 pass-1 twiddles W6
 constexpr int S2_TT = S2_TW + 64;                   // 16 group totals
 constexpr int S2_RED = S2_TT + 16;
 constexpr int S2_F2 = S2_RED + 16;                  // 9120 float2 = 72 960 B: two workgroups per CU
-constexpr int S2_WU = 6;                            // read-only warm-up tiles (DC state)
+constexpr int S2_WU = RUN64_WU;                     // read-only warm-up tiles (DC state); one halo tile behind them (run_split.h)
+static_assert(RUN64_HALO == 1, "a run >= 1 walks one halo tile");
 
 struct Run64v2Args {
     const float2 *x; float2 *out;
@@ -48,20 +49,6 @@ struct Run64v2Args {
     float2 *cpre;               //    k_run64_dcfix adds what the true state contributes to the channels 30..33 (as k_run256v2)
 };
 
-// first half of the runs (dispatched first: the older workgroups of their CUs) share n0 tiles, the second half the rest
-__device__ __forceinline__ void run64_bounds(const Run64v2Args &A, unsigned w, unsigned &first, unsigned &last)
-{
-    if (A.n0 == 0 || (A.nruns & 1u)) {
-        first = (unsigned)((unsigned long long)w * A.nb / A.nruns);
-        last = (unsigned)((unsigned long long)(w + 1) * A.nb / A.nruns);
-        return;
-    }
-    const unsigned half = A.nruns / 2, s = w / half, i = w - s * half;
-    const unsigned base = s ? A.n0 : 0u, tiles = s ? A.nb - A.n0 : A.n0;
-    first = base + (unsigned)((unsigned long long)i * tiles / half);
-    last = base + (unsigned)((unsigned long long)(i + 1) * tiles / half);
-}
-
 __global__ __launch_bounds__(256, 2) void k_run64v2(Run64v2Args A)
 {
     __shared__ __attribute__((aligned(16))) float2 L[S2_F2];
@@ -70,7 +57,7 @@ __global__ __launch_bounds__(256, 2) void k_run64v2(Run64v2Args A)
     const unsigned qw = (unsigned)__builtin_amdgcn_readfirstlane(tid >> 6);        // my wave = my block of 16 frames
     const unsigned w = blockIdx.x;
     unsigned first, last;
-    run64_bounds(A, w, first, last);
+    run_range_halves(A.nb, A.nruns, A.n0, w, first, last);
     const float4 *x4 = reinterpret_cast<const float4 *>(A.x);
 
     if (tid < 64) tw_s[tid] = A.tw[tid];
@@ -301,7 +288,7 @@ __global__ __launch_bounds__(256) void k_run64_dcfix(Run64v2Args A, const float2
 {
     const unsigned w = blockIdx.x + 1u;
     unsigned first, last;
-    run64_bounds(A, w, first, last);
+    run_range_halves(A.nb, A.nruns, A.n0, w, first, last);
     const float2 c = A.cpre[w];
     const unsigned par = A.parity0 & 1u;                // a tile is 64 frames: every halo tile starts on the call's parity
     // one element per thread (grid.y = 7 slices of 256): a loop of read-modify-writes ran one memory round trip after the other (8 us)
@@ -309,7 +296,7 @@ __global__ __launch_bounds__(256) void k_run64_dcfix(Run64v2Args A, const float2
     if (e >= 4u * RUN64_DCFIX_F) return;
     const unsigned ch = e / RUN64_DCFIX_F, t = e % RUN64_DCFIX_F;
     const size_t fr = (size_t)64 * first + t;
-    if (fr >= (size_t)64 * last) return;                // (runs are >= 14 tiles: never)
+    if (fr >= (size_t)64 * last) return;                // (never: run64_v2_cold, kernel_choice.h)
     float2 *o = A.out + (A.tile_major ? ((fr >> 4) * 64u + (30u + ch)) * 16u + (fr & 15u) : (size_t)(30u + ch) * A.out_stride + fr);
     const float2 r = rt[((size_t)par * RUN64_DCFIX_F + t) * 4u + ch];
     float2 y = *o;
@@ -325,12 +312,11 @@ int run64_v2_launch(const Run64v2Host &h, hipStream_t s, KernelTimer *timer)
     A.x = h.x; A.out = h.out; A.taps = h.taps; A.tw = h.tw; A.wpre = h.wpre;
     A.uhist_in = h.uhist_in; A.uhist_out = h.uhist_out; A.vend_in = h.vend_in; A.vend_out = h.vend_out;
     A.nf = h.nf; A.nb = h.nf / 64u; A.nruns = h.nruns; A.parity0 = h.parity0; A.out_stride = h.nf; A.tile_major = h.tile_major ? 1u : 0u;
-    const double wt = h.weight;
-    A.n0 = (h.nruns >= 2 && !(h.nruns & 1u) && wt > 1.0 && wt < 1.5) ? (uint32_t)std::llround(0.5 * wt * (double)A.nb) : 0u;
+    A.n0 = halves_n0(A.nb, h.nruns, h.weight);
     h.dc->put(A);
     int r;
     if (timer && (r = timer->begin(s))) return r;
-    A.nowu = (h.cpre && h.rt && h.nruns >= 2 && A.nb / h.nruns >= 14u) ? 1u : 0u;      // (rt: the blocker is on)
+    A.nowu = h.cold ? 1u : 0u;
     A.cpre = h.cpre;
     hipLaunchKernelGGL(k_run64v2, dim3(h.nruns), dim3(256), 0, s, A);
     if (A.nowu) hipLaunchKernelGGL(k_run64_dcfix, dim3(h.nruns - 1u, (4u * RUN64_DCFIX_F + 255u) / 256u), dim3(256), 0, s, A, h.rt);

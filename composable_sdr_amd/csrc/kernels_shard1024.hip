@@ -33,21 +33,21 @@
 // State arrays and tables are the plan's (kernels_pfb1024.hip): window uhist [13][1024] pre-mixed, DC state, freqdem history rp[] indexed by
 // the PRIMED channel k' = G m, tap table taps_q with the shard's phasors -- so ragged and short calls of the same handle can take the
 // whole-band kernel + row gather and carry the same state.
-// Run starts: cold, from DC state 0 (Shard1024Args::nowu; the six read-only warm-up tiles of the first version were 9 % of the reads): three
+// Run starts: cold, from DC state 0 (Run1024Args::nowu; the six read-only warm-up tiles of the first version were 9 % of the reads): three
 // window-refill tiles and (FM) the muted tile in front of the run for the freqdem history; what the missing state contributes to the ONE owned
-// channel among the four around DC (none for the shards 2 .. 5 of 8) is put back by k_shard1024_dcfix behind the launch, as k_run1024_dcfix does.
+// channel among the four around DC (none for the shards 2 .. 5 of 8) is put back by k_run1024_dcfix behind the launch (one channel: kernels_run1024_v3.hip).
 #include "fused_v2_common.h"
 #include <type_traits>
 
 #ifndef S1_TRACE
-#define S1_TRACE 0       // 1: s_memtime stamps of run 1's wave 0 (role 0) / wave 4 (role 1) per phase, written to Shard1024Args::trace (CSDR_SHARD1024_TRACE=file)
+#define S1_TRACE 0       // 1: s_memtime stamps of run 1's wave 0 (role 0) / wave 4 (role 1) per phase, written to Run1024Args::trace (CSDR_SHARD1024_TRACE=file)
 #endif
 
 namespace csdr {
 namespace {
 
 constexpr int S1_BUF = 4096;                       // float2 per tile buffer (32 KiB)
-constexpr int S1_WU = 6, S1_HALO = 4;
+constexpr int S1_WU = RUN1024_WU, S1_HALO = RUN1024_HALO;     // run_split.h
 
 template <int G> struct S1 {
     static constexpr int NP = 1024 / G;            // points of the pruned DFT = owned channels
@@ -65,26 +65,6 @@ template <int G> struct S1 {
     static constexpr int F2 = SG + NP * SGB / 8;
     static_assert(G == 4 || G == 8, "built for strides 4 and 8 (stride 2 keeps k_run1024v2<FM, 2>)");
     static_assert(F2 * 8 <= 160 * 1024, "one workgroup per CU");
-};
-
-struct Shard1024Args {
-    const float2 *x;            // raw input of this call
-    void *out;                  // [1024 / G][nf] F32 (FM) / CF32
-    const float4 *taps_q;       // the plan's table: [4 q][4 pieces][256 j] taps + even-frame phasor; behind the 64 KiB: [4 q][256 j] odd-frame phasor
-    const float2 *tw;           // e^{-j 2 pi i / 1024}
-    const float2 *uhist_in; float2 *uhist_out;    // [13][1024] pre-mixed, DC-blocked window before / after the call
-    const float2 *vend_in; float2 *vend_out;      // DC blocker state v1
-    const float2 *rp_in; float2 *rp_out;          // [1024] freqdem r', indexed by the primed channel k' = G m
-    uint32_t nf, nb, nruns, parity0;
-    uint32_t tile_major;        // CF32: the 128-byte lines of a 16-frame block back to back, [block][1024 / G][128 B] (the plane k_agc_spec_tm reads), instead of rows
-    float alpha, beta, l2beta, fm_ref, tiny;
-    float b16[16];              // beta^(16 r)
-    float b256[17];             // beta^(256 g)
-    PhaseK pk;
-    unsigned long long *trace;  // debug (S1_TRACE build): [role][step < 96][4] stamps
-    uint32_t nowu;              // 1: a run starts cold from DC state 0 (no read-only warm-up tiles), leaves the state in front of tile last - 4 in
-    int mfix;                   //    cpre[w + 1] and (FM) the uncorrected Y of row mfix (the owned channel among 510 .. 513; -1: none) for its frames
-    float2 *cpre, *side;        //    -1 .. 31 in side [w][RUN1024_DCFIX_F]: k_shard1024_dcfix
 };
 
 // value of lane l ^ D (upper: bit D of my lane index is set), without a trip through the LDS crossbar: DPP inside a row of 16 lanes,
@@ -110,17 +90,8 @@ template <int D> __device__ __forceinline__ float lane_xor(float x, bool upper)
     return __uint_as_float(upper ? r[0] : r[1]);
 }
 
-// run w: whole blocks of TB tiles (a row's 128-byte line), evenly; the call's last block may be a partial one
-__host__ __device__ __forceinline__ void shard_bounds(uint32_t nb, uint32_t nruns, unsigned w, unsigned TB, unsigned &first, unsigned &last)
-{
-    const unsigned nblk = (nb + TB - 1) / TB;
-    first = TB * (unsigned)((unsigned long long)w * nblk / nruns);
-    last = TB * (unsigned)((unsigned long long)(w + 1) * nblk / nruns);
-    if (last > nb) last = nb;
-}
-
 template <bool FM, int G>
-__global__ __launch_bounds__(512) void k_shard1024(Shard1024Args A)
+__global__ __launch_bounds__(512) void k_shard1024(Run1024Args A)   // (run w: run_range_blocks, run_split.h)
 {
     using K = S1<G>;
     constexpr int NP = K::NP, PPL = K::PPL, NBUF = K::NBUF, AHEAD = K::AHEAD;
@@ -133,7 +104,7 @@ __global__ __launch_bounds__(512) void k_shard1024(Shard1024Args A)
     const int lt = tid & 255, j = lt;
     const unsigned w = blockIdx.x;
     unsigned first, last;
-    shard_bounds(A.nb, A.nruns, w, TB, first, last);
+    run_range_blocks(A.nb, A.nruns, w, TB, first, last);
     const float4 *x4 = reinterpret_cast<const float4 *>(A.x);
     const int col_off = 16 * (j >> 4) + 2 * (((j & 15) >> 1) ^ (j >> 5)) + (j & 1);
     const int colb = col_off + 512 * rho;               // my first branch's group: 2 rho
@@ -306,7 +277,7 @@ __global__ __launch_bounds__(512) void k_shard1024(Shard1024Args A)
                     char *sg = reinterpret_cast<char *>(L + K::SG) + SGB * m;
                     const unsigned sw = (unsigned)m & (NSL - 1u);
                     if (FM && w > 0 && m == A.mfix && b + 1u >= first && b < first + 8u) {
-                        // the uncorrected Y of the owned channel next to DC, frames -1 .. 31 of the run, for k_shard1024_dcfix
+                        // the uncorrected Y of the owned channel next to DC, frames -1 .. 31 of the run, for k_run1024_dcfix
                         float2 *sd = A.side + (size_t)w * RUN1024_DCFIX_F;
                         const int i0 = 4 * (int)(b + 1u - first) - 3;          // frame f of this tile -> slot i0 + f (slot 0 = frame -1)
 #pragma unroll
@@ -501,68 +472,14 @@ __global__ __launch_bounds__(512) void k_shard1024(Shard1024Args A)
     }
 }
 
-// What the DC state a run started without contributes to the owned channel next to DC over the run's first 32 frames: Y += cpre[w] x R (the
-// chain is linear up to Y).  CF32: in place on the row (or the tile-major plane); FM: freqdem of the corrected side copies.
-template <bool FM>
-__global__ __launch_bounds__(64) void k_shard1024_dcfix(Shard1024Args A, const float2 *__restrict__ rt, unsigned NP)
-{
-    const unsigned TB = FM ? 8u : 4u;
-    const unsigned w = blockIdx.x + 1u, fr = threadIdx.x;
-    unsigned first, last;
-    shard_bounds(A.nb, A.nruns, w, TB, first, last);
-    if (fr >= 32u || A.mfix < 0) return;
-    const float2 c = A.cpre[w];
-    const float2 *R = rt + (size_t)(A.parity0 & 1u) * RUN1024_DCFIX_F * 4;      // a tile is 4 frames: every cold start begins on the call's parity
-    auto corr = [&](unsigned i) { const float2 r = R[i * 4u]; return make_float2(c.x * r.x - c.y * r.y, c.x * r.y + c.y * r.x); };
-    const size_t t = (size_t)4 * first + fr;            // the frame in the call
-    if (t >= A.nf) return;
-    const unsigned k = (unsigned)A.mfix;
-    if (FM) {
-        const float2 *sd = A.side + (size_t)w * RUN1024_DCFIX_F;
-        const float2 p0 = sd[fr], p1 = sd[fr + 1u], d0 = corr(fr), d1 = corr(fr + 1u);
-        const FmK fk = {A.tiny, A.fm_ref, A.pk.hp, A.pk.pi};
-        reinterpret_cast<float *>(A.out)[(size_t)k * A.nf + t] =
-            fm_sample(make_float2(p0.x + d0.x, p0.y + d0.y), make_float2(p1.x + d1.x, p1.y + d1.y), fk);
-    } else {
-        float2 *o = reinterpret_cast<float2 *>(A.out) + (A.tile_major ? ((t >> 4) * NP + k) * 16u + (t & 15u) : (size_t)k * A.nf + t);
-        const float2 d1 = corr(fr + 1u);
-        float2 y = *o;
-        y.x += d1.x; y.y += d1.y;
-        *o = y;
-    }
-}
-
 }  // namespace
 
-int shard1024_launch(const Run1024Call &h, hipStream_t s, KernelTimer *timer)
+// the launcher's table (run1024_launch): the instantiation for (FM, chan_stride G)
+Run1024Kernel shard1024_kernel(bool fm, uint32_t G)
 {
-    const bool fm = h.fm;
-    const uint32_t nruns = h.nruns;
-    Shard1024Args A{};
-    put_run1024(h, A);
-    A.tile_major = (!fm && h.tile_major) ? 1u : 0u;
-    if (A.tile_major && (h.nf & 15u)) { set_error("k_shard1024: a tile-major plane takes whole 16-frame blocks"); return -1; }
-    A.trace = S1_TRACE ? h.trace : nullptr;             // (the stamps of a debug build only)
-    int r;
-    if (A.trace && (r = h.trace_dump(SHARD1024_TRACE_N, true, s))) return r;
-    // no warm-up windows: whole runs of >= 16 tiles (a cold start is 4 tiles deep and the correction covers 8 more), the state arrays there
-    A.nowu = (h.rt && h.cpre && h.side && nruns >= 2) ? 1u : 0u;      // (rt: the blocker is on)
-    A.cpre = h.cpre; A.side = h.side; A.mfix = h.mfix;
-    if (timer && (r = timer->begin(s))) return r;
-    if (h.G == 8) {
-        if (fm) hipLaunchKernelGGL((k_shard1024<true, 8>), dim3(nruns), dim3(512), 0, s, A);
-        else hipLaunchKernelGGL((k_shard1024<false, 8>), dim3(nruns), dim3(512), 0, s, A);
-    } else if (h.G == 4) {
-        if (fm) hipLaunchKernelGGL((k_shard1024<true, 4>), dim3(nruns), dim3(512), 0, s, A);
-        else hipLaunchKernelGGL((k_shard1024<false, 4>), dim3(nruns), dim3(512), 0, s, A);
-    } else { set_error("k_shard1024: chan_stride %u is not built (4, 8)", h.G); return -1; }
-    if (A.nowu && A.mfix >= 0) {
-        if (fm) hipLaunchKernelGGL((k_shard1024_dcfix<true>), dim3(nruns - 1u), dim3(64), 0, s, A, h.rt, 1024u / h.G);
-        else hipLaunchKernelGGL((k_shard1024_dcfix<false>), dim3(nruns - 1u), dim3(64), 0, s, A, h.rt, 1024u / h.G);
-    }
-    if (timer && (r = timer->end(s))) return r;         // (the bracket covers the correction kernel)
-    CSDR_HIP(hipGetLastError());
-    return A.trace ? h.trace_dump(SHARD1024_TRACE_N, false, s) : 0;     // debug: [role][96][4]
+    const void *fn = G == 8 ? (fm ? (const void *)k_shard1024<true, 8> : (const void *)k_shard1024<false, 8>)
+                   : G == 4 ? (fm ? (const void *)k_shard1024<true, 4> : (const void *)k_shard1024<false, 4>) : nullptr;
+    return {fn, 512u, S1_TRACE ? SHARD1024_TRACE_N : 0};
 }
 
 }  // namespace csdr

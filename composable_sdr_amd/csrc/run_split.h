@@ -1,5 +1,8 @@
-// How a launch's tiles are split into runs: RunSplit, run_range (host and device) and make_split (host).  Included by the run kernels
-// through fused_common.h and, on its own, by host-only programs (tests/test_run_split.py): nothing here needs the HIP headers.
+// How a launch's tiles are split into runs, for every run kernel: the bounds of run w (host and device) -- run_range over a RunSplit
+// (k_run256v2), run_range_even (k_pfb1024, k_front4096), run_range_halves (k_run64v2, k_run1024v2), run_range_blocks (k_run1024v3,
+// k_shard1024) --, the host functions that size them (make_split, halves_n0) and the constants the bounds are judged against (tiles a run
+// reads in front of itself, frames its dcfix kernel covers).  Included by the run kernels through fused_common.h, by kernel_choice.h and,
+// on its own, by host-only programs (tests/test_run_split.py, tests/test_run_bounds_cpu.py): nothing here needs the HIP headers.
 #pragma once
 
 #include <cmath>
@@ -13,6 +16,51 @@
 
 namespace csdr {
 namespace {
+
+// Tiles (4096 samples) a run w >= 1 reads in front of its first tile: WU read-only warm-up tiles (DC state; none on a cold start) in front
+// of HALO tiles it walks without output (window refill).  k_run1024v2 reads all WU + HALO without a clamp; the others clamp the warm-up.
+constexpr int RUN64_WU = 6, RUN64_HALO = 1;             // k_run64v2
+constexpr int RUN1024_WU = 6, RUN1024_HALO = 4;         // k_run1024v2, k_run1024v3, k_shard1024
+// Output frames at a cold run's start that the dcfix kernel behind the launch corrects
+constexpr int DCFIX_F = 113;                            // k_run256_dcfix: frame -1 of a run (freqdem history) + its first seven tiles of 16 frames
+constexpr int RUN64_DCFIX_F = 448;                      // k_run64_dcfix: seven tiles of 64 frames (32 768 samples behind the halo tile's start)
+// k_run1024_dcfix: frame -1 of a run (freqdem history) + its first eight tiles of 4 frames.  The first frame NOT corrected (32) has a
+// window that reaches back to frame 35 behind the cold start: alpha |c| beta^35840 = 1.6e-8 alpha |c| of the missing state is left in it
+// (with four tiles it was 5.9e-5: ~1e-5 of a unit signal at the strongest DC offset the tests use)
+constexpr int RUN1024_DCFIX_F = 33;
+
+// The plain floor split: run w of nruns gets the tiles [w nb / nruns, (w + 1) nb / nruns)
+CSDR_SPLIT_HD void run_range_even(uint32_t nb, uint32_t nruns, uint32_t w, uint32_t &first, uint32_t &last)
+{
+    first = (uint32_t)((unsigned long long)w * nb / nruns);
+    last = (uint32_t)((unsigned long long)(w + 1) * nb / nruns);
+}
+
+// Two workgroups per CU: the first half of the runs (the workgroups dispatched first, the older ones of their CUs) win the issue
+// arbitration and share n0 of the nb tiles, the second half the rest (both halves then end together).  n0 = 0 or an odd nruns: even split
+CSDR_SPLIT_HD void run_range_halves(uint32_t nb, uint32_t nruns, uint32_t n0, uint32_t w, uint32_t &first, uint32_t &last)
+{
+    if (n0 == 0 || (nruns & 1u)) return run_range_even(nb, nruns, w, first, last);
+    const uint32_t half = nruns / 2, s = w / half, i = w - s * half;
+    const uint32_t base = s ? n0 : 0u, tiles = s ? nb - n0 : n0;
+    first = base + (uint32_t)((unsigned long long)i * tiles / half);
+    last = base + (uint32_t)((unsigned long long)(i + 1) * tiles / half);
+}
+// n0 of run_range_halves.  weight: tile share of the older workgroup of a CU (1 = even; read between 1 and 1.5)
+inline uint32_t halves_n0(uint32_t nb, uint32_t nruns, double weight)
+{
+    return (nruns >= 2 && !(nruns & 1u) && weight > 1.0 && weight < 1.5) ? (uint32_t)std::llround(0.5 * weight * (double)nb) : 0u;
+}
+
+// Whole blocks of TB tiles (a row's 128-byte output line), evenly; the call's last block may be a partial one (nb % TB tiles: its rows get
+// the front part of a line)
+CSDR_SPLIT_HD void run_range_blocks(uint32_t nb, uint32_t nruns, uint32_t w, uint32_t TB, uint32_t &first, uint32_t &last)
+{
+    const uint32_t nblk = (nb + TB - 1) / TB;
+    first = TB * (uint32_t)((unsigned long long)w * nblk / nruns);
+    last = TB * (uint32_t)((unsigned long long)(w + 1) * nblk / nruns);
+    if (last > nb) last = nb;
+}
 
 // Runs are grouped in "slots": slot s holds rps consecutive runs that share tiles[s] tiles evenly, starting at tile base[s].
 // One slot with rps = nruns is the plain balanced split; the run kernels use one slot per co-resident workgroup of a CU

@@ -1,4 +1,4 @@
-"""make_split / run_range (csrc/run_split.h): how a launch's tiles become the runs of k_run256v2 and k_run256_dcfix.  No GPU needed.
+"""make_split / run_range (csrc/run_split.h, which holds every run kernel's bounds: the others are in test_run_bounds_cpu.py): how a launch's tiles become the runs of k_run256v2 and k_run256_dcfix.  No GPU needed.
 
 A small stand-alone program includes the header, makes one split per command-line case and prints every run's range twice: as
 run_range gives it, and as the FM kernels use it (their pair_align rounding: starts and inner ends rounded down to even tiles).
