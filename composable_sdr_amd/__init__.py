@@ -16,5 +16,6 @@ from .pipes import (  # noqa: F401
     Firpfbch2, firpfbch2Channelizer, firdes_pfbch2,
     Firpfbch2Synth, firpfbch2Synthesizer, firdes_pfbsyn2,
     RowResamp, rowResampler, firdes_rowresamp,
+    PskTrack, pskTracker, SymTrack, symTracker, sincos_word, CSDR_PSKTRACK_EQ_DD, CSDR_PSKTRACK_EQ_CM,
 )
 from .trans import compact, takeNArr, mix, mux, distribute_, addPipe  # noqa: F401

@@ -165,6 +165,14 @@ SIGNATURES = {
     "csdr_rowresamp_get_design": (_i32, [_vp, _pu32, C.POINTER(C.c_uint64), _pu32, _vp]),
     "csdr_rowresamp_get_time": (_i32, [_vp, C.POINTER(C.c_uint64)]),
     "csdr_rowresamp_destroy": (_i32, [_vp]),
+    "csdr_sincos_word": (_i32, [_u32, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "csdr_psktrack_new": (_i32, [_u32, _u32, _u32, _u32, _f32, _u32, _u32, _f32, _f32, _u32, _u32, _pp]),
+    "csdr_psktrack_process": (_i32, [_vp, _vp, _u32, _vp, _vp, _vp, _vp]),
+    "csdr_psktrack_process_device": (_i32, [_vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp]),
+    "csdr_psktrack_restart": (_i32, [_vp]),
+    "csdr_psktrack_get_state": (_i32, [_vp, _u32, _pu32, _pu32, C.POINTER(C.c_float), _pu32, _vp]),
+    "csdr_psktrack_get_design": (_i32, [_vp, C.POINTER(C.c_float), C.POINTER(C.c_float), _pu32, _pu32]),
+    "csdr_psktrack_destroy": (_i32, [_vp]),
     "csdr_chain_cfg_default": (None, [C.POINTER(ChainCfg), _u32]),
     "csdr_chain_create": (_i32, [C.POINTER(ChainCfg), _pp]),
     "csdr_chain_process": (_i32, [_vp, _vp, _u32, _vp, _pu32]),

@@ -1352,4 +1352,104 @@ int csdr_rowresamp_get_time(const csdr_rowresamp *h, uint64_t *t_next)
     return CSDR_OK;
 }
 
+// ---------------------------------------------------------------------------
+// pskTracker (Liquid.chs:119-175 behind the symbol synchroniser): power normaliser, carrier PLL, T/2 equaliser and BPSK / QPSK
+// decisions on nchan independent CF32 rows; csdr_sincos_word needs no GPU
+// ---------------------------------------------------------------------------
+int csdr_sincos_word(uint32_t w, float *s, float *c)
+{
+    if (!s || !c) return block_null_arg("sincos_word");
+    psk_sincos_word(w, s, c);
+    return CSDR_OK;
+}
+}  // extern "C"
+struct csdr_psktrack {
+    int device; DeviceBuffers mem; uint32_t C, max_n; PskLaunch l;
+    PingPong<uint32_t> st;                                  // [C][psk_state_words(eq_len)]; all zeros is the state right after new
+    float2 *d_x = nullptr, *d_y = nullptr; uint32_t *d_sym = nullptr, *d_nx = nullptr, *d_ny = nullptr;   // the host path's
+};
+static int psktrack_launch(csdr_psktrack *h, const void *d_x, uint32_t n, const void *d_nx, void *d_y, void *d_sym, void *d_ny, void *stream)
+{
+    PskLaunch l = h->l;
+    l.n = n;
+    return h->st.flip_behind(launch_psktrack((const float2 *)d_x, (const uint32_t *)d_nx, (float2 *)d_y, (uint32_t *)d_sym, (uint32_t *)d_ny,
+                                             h->st.in(), h->st.out(), l, (hipStream_t)stream));
+}
+extern "C" {
+int csdr_psktrack_destroy(csdr_psktrack *h) { return block_destroy(h); }
+int csdr_psktrack_new(uint32_t bits, uint32_t sps, uint32_t phase, uint32_t eq_len, float eq_mu, uint32_t eq_mode, uint32_t eq_delay,
+                      float pll_bw, float agc_bw, uint32_t nchan, uint32_t max_samples, csdr_psktrack **out)
+{
+    const bool eq_ok = eq_len == 0 || (sps == 2 && (eq_len & 1u) && eq_len >= 3 && eq_len <= PSK_MAX_EQ);
+    if (!out || !nchan || bits < 1 || bits > 2 || sps < 1 || sps > 2 || phase > 1 || !eq_ok || !(eq_mu >= 0.f && eq_mu <= 1.f) ||
+        eq_mode > CSDR_PSKTRACK_EQ_CM || !(pll_bw >= 0.f && pll_bw <= 1.f) || !(agc_bw >= 0.f && agc_bw <= 1.f) || max_samples > (1u << 28)) {
+        set_error("psktrack: bad arguments (bits 1 or 2, sps 1 or 2, phase 0 or 1, eq_len 0 or odd in [3, %u] with sps 2, eq_mu, pll_bw and "
+                  "agc_bw in [0, 1], eq_mode 0 or 1, nchan >= 1, max_samples <= 2^28)", PSK_MAX_EQ);
+        return CSDR_ERR_INVALID;
+    }
+    NewBlock<csdr_psktrack> h;
+    int r = h.open(); if (r) return r;
+    h->C = nchan; h->max_n = block_max_n(max_samples);
+    h->l = PskLaunch{nchan, 0, bits, sps, phase, eq_len, eq_mode, eq_delay, eq_mu, agc_bw, pll_bw, std::sqrt(pll_bw)};
+    const size_t C = nchan, n = h->max_n;
+    DeviceBuffers &mem = h->mem;
+    if ((r = h->st.alloc_zeroed(mem, C * psk_state_words(eq_len))) || (r = mem.alloc_n(&h->d_x, C * n)) || (r = mem.alloc_n(&h->d_y, C * n)) ||
+        (r = mem.alloc_n(&h->d_sym, C * n)) || (r = mem.alloc_n(&h->d_nx, C)) || (r = mem.alloc_n(&h->d_ny, C)))
+        return r;
+    return h.publish(out);
+}
+int csdr_psktrack_process_device(csdr_psktrack *h, const void *d_x, uint32_t n, const void *d_nx, void *d_y, void *d_sym, void *d_ny,
+                                 void *stream)
+{
+    if (!h || !d_ny) return block_null_arg("psktrack");
+    if (int r = block_check_n("psktrack", n, h->max_n)) return r;
+    if (n && (!d_x || !d_y)) { set_error("psktrack: null buffer"); return CSDR_ERR_INVALID; }
+    return psktrack_launch(h, d_x, n, d_nx, d_y, d_sym, d_ny, stream);
+}
+int csdr_psktrack_process(csdr_psktrack *h, const float *x, uint32_t n, const uint32_t *nx, float *y, uint32_t *sym, uint32_t *ny)
+{
+    if (!ny) return block_null_arg("psktrack");
+    int r = block_check_call("psktrack", h, x, n, y); if (r) return r;
+    const size_t C = h->C;
+    if (nx)
+        for (size_t c = 0; c < C; c++)
+            if (nx[c] > n) { set_error("psktrack: row %zu holds %u samples > n = %u", c, nx[c], n); return CSDR_ERR_SIZE; }
+    return block_host_call("psktrack", h->device, h->d_x, x, sizeof(float2) * C * n,
+                           [&] {
+                               if (nx) CSDR_HIP(hipMemcpy(h->d_nx, nx, sizeof(uint32_t) * C, hipMemcpyHostToDevice));
+                               return psktrack_launch(h, h->d_x, n, nx ? h->d_nx : nullptr, h->d_y, sym ? h->d_sym : nullptr, h->d_ny, nullptr);
+                           },
+                           {{ny, h->d_ny, sizeof(uint32_t) * C}, {y, h->d_y, sizeof(float2) * C * n}, {sym, h->d_sym, sizeof(uint32_t) * C * n}});
+}
+int csdr_psktrack_restart(csdr_psktrack *h) { return block_reset(h, [&] { return h->st.reset(nullptr); }); }
+int csdr_psktrack_get_state(csdr_psktrack *h, uint32_t chan, uint32_t *theta, uint32_t *freq, float *p, uint32_t *nsym, float *w)
+{
+    if (!h || chan >= h->C) { set_error("psktrack: bad channel"); return CSDR_ERR_INVALID; }
+    DevGuard guard(h->device);
+    const uint32_t L = h->l.L;
+    std::vector<uint32_t> s(psk_state_words(L));
+    CSDR_HIP(hipDeviceSynchronize());
+    CSDR_HIP(hipMemcpy(s.data(), h->st.in() + (size_t)chan * s.size(), sizeof(uint32_t) * s.size(), hipMemcpyDeviceToHost));
+    const bool live = s[0] != 0u;
+    const float one = 1.f;
+    if (theta) *theta = live ? s[2] : 0u;
+    if (freq) *freq = live ? s[3] : 0u;
+    if (p) std::memcpy(p, live ? (const void *)&s[1] : (const void *)&one, sizeof(float));
+    if (nsym) *nsym = live ? s[5] : 0u;
+    if (w) {
+        if (live) std::memcpy(w, &s[PSK_HDR], sizeof(float) * 2 * L);
+        else for (uint32_t i = 0; i < 2 * L; i++) w[i] = i + 1 == L ? 1.f : 0.f;
+    }
+    return CSDR_OK;
+}
+int csdr_psktrack_get_design(const csdr_psktrack *h, float *alpha, float *beta, uint32_t *eq_len, uint32_t *lds_bytes)
+{
+    if (!h) return block_null_arg("psktrack");
+    if (alpha) *alpha = h->l.alpha;
+    if (beta) *beta = h->l.beta;
+    if (eq_len) *eq_len = h->l.L;
+    if (lds_bytes) *lds_bytes = (uint32_t)psk_lds_bytes(h->l.L);
+    return CSDR_OK;
+}
+
 }  // extern "C"

@@ -9,6 +9,7 @@
 #include "agc_tail_shape.h"
 #include "pfb2_shape.h"
 #include "rowresamp_shape.h"
+#include "psktrack_common.h"
 
 namespace csdr {
 
@@ -254,6 +255,16 @@ size_t symsyncc_lds_bytes(uint32_t L, uint32_t M);
 // x [C][n] CF32 -> y [C][cap] CF32 (row stride cap), ny [C]; hist [C][L - 1] CF32 and st [C] in place, as launch_symsync
 int launch_symsyncc(const float2 *x, float2 *y, uint32_t *ny, const float *mf, const float *dmf, float2 *hist, SymsyncState *st,
                     uint32_t *fault_any, const SymsyncLaunch &l, hipStream_t s);
+
+// ---- pskTracker: carrier PLL, T/2 equaliser and PSK decisions (kernels_psktrack.hip; shape and contract functions in
+// psktrack_common.h) ----
+struct PskLaunch {
+    uint32_t C, n, bits, sps, phase, L, mode, delay;     // L = eq_len (0: none); delay = eq_delay in symbols
+    float mu, agc_bw, alpha, beta;                       // alpha = pll_bw, beta = sqrtf(pll_bw)
+};
+// x [C][n] CF32, nx [C] or NULL -> y [C][n] CF32, sym [C][n] or NULL, ny [C]; st_in -> st_out: [C][psk_state_words(L)]
+int launch_psktrack(const float2 *x, const uint32_t *nx, float2 *y, uint32_t *sym, uint32_t *ny, const uint32_t *st_in,
+                    uint32_t *st_out, const PskLaunch &l, hipStream_t s);
 
 // ---- firhilbf: realToComplex / complexToReal (kernels_firhilb.hip; design in design.cpp) ----
 constexpr uint32_t FIRHILB_MAX_M = 16;               // filter semi-length m: 2 m quadrature taps, 2 m pairs of history

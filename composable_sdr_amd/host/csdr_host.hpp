@@ -518,6 +518,50 @@ inline Pipe<Rows<cf32>, Rows<cf32>> symSyncC(uint32_t m, uint32_t k, uint32_t nc
         });
 }
 
+// ---- pskTracker: power normaliser, carrier PLL, T/2 equaliser and BPSK / QPSK decisions on CF32 rows of their own
+// lengths, as symSyncC yields them (zero-padded to the longest, with the counts beside them); row c of the output holds that row's
+// soft symbols.  symTracker m k (Liquid.chs:119-175; symtrack_cccf_create(RRC, k, m, 0.25, BPSK)) is the composition: csdr_symsync
+// with npfb 16, lf_bw 0.01, output rate 2 and the RRC 0.25 banks, then PskTracker(bits 1, sps 2, phase 0, eq_len 9, constant modulus) ----
+inline Pipe<Rows<cf32>, Rows<cf32>> PskTracker(uint32_t bits, uint32_t sps, uint32_t phase, uint32_t eq_len, uint32_t eq_mode, uint32_t nchan,
+                                               uint32_t max_in)
+{
+    return handlePipe<csdr_psktrack, Rows<cf32>, Rows<cf32>>(
+        [=](csdr_psktrack **h) {
+            check(csdr_psktrack_new(bits, sps, phase, eq_len, CSDR_PSKTRACK_EQ_MU, eq_mode, CSDR_PSKTRACK_EQ_DELAY, CSDR_PSKTRACK_PLL_BW,
+                                    CSDR_PSKTRACK_AGC_BW, nchan, max_in, h));
+        },
+        csdr_psktrack_destroy,
+        [nchan](csdr_psktrack *h, const Rows<cf32> &rows) {
+            if (rows.size() != nchan) return Rows<cf32>(rows.size());
+            std::vector<uint32_t> nx(nchan), ny(nchan);
+            size_t n = 0;
+            for (uint32_t c = 0; c < nchan; c++) { nx[c] = (uint32_t)rows[c].size(); n = std::max(n, rows[c].size()); }
+            if (!n) return Rows<cf32>(rows.size());
+            Array<cf32> x(nchan * n), y(nchan * n);
+            for (uint32_t c = 0; c < nchan; c++) std::copy(rows[c].begin(), rows[c].end(), x.begin() + c * n);
+            check(csdr_psktrack_process(h, reinterpret_cast<const float *>(x.data()), (uint32_t)n, nx.data(), reinterpret_cast<float *>(y.data()),
+                                        nullptr, ny.data()));
+            return splitRows(y, nchan, n, ny);
+        });
+}
+inline Pipe<Rows<cf32>, Rows<cf32>> symTracker(uint32_t m, uint32_t k, uint32_t nchan, uint32_t max_in)
+{
+    auto sync = rowPipe<csdr_symsync, cf32, cf32>(
+        "symTracker", nchan,
+        [=](csdr_symsync **h) {
+            check(csdr_symsync_create(k, m, 0.0f, 16, 0.01f, 2, nchan, max_in, h));
+            check(csdr_symsync_set_rnyquist(*h, CSDR_FIRFILT_RRC, 0.25f));
+        },
+        csdr_symsync_destroy,
+        [nchan](csdr_symsync *h, const Array<cf32> &x, uint32_t n) {
+            Array<cf32> y(x.size());
+            std::vector<uint32_t> ny(nchan);
+            check(csdr_symsync_process_c(h, reinterpret_cast<const float *>(x.data()), n, reinterpret_cast<float *>(y.data()), ny.data()));
+            return splitRows(y, nchan, n, ny);
+        });
+    return compose(PskTracker(1, 2, 0, 9, CSDR_PSKTRACK_EQ_CM, nchan, max_in), sync);
+}
+
 // ---- fskDemodulator m k bw (Liquid.chs:336-382): row c of the output holds the n div k symbols of row c, the n mod k samples
 // left over are dropped (:367-376).  gmskDemodulator m k bw (Liquid.chs:384-429; the reference's argument order, gmskdem_create
 // takes k m bw): the n / k bits of row c; a row length that is no multiple of k throws, as :421 does ----

@@ -402,6 +402,139 @@ def fmDemWithSync(k, nchan=1, max_samples=1 << 16):
     return compose(symSyncR(k, 4, 0.0, 64, nchan, max_samples), fmDemodulator(kf, nchan, max_samples))
 
 
+CSDR_PSKTRACK_EQ_DD, CSDR_PSKTRACK_EQ_CM = 0, 1       # eq_mode: decision-directed, constant modulus
+
+
+def sincos_word(w):
+    """(sin, cos) of the uint32 phase word `w` (2^32 = one turn) as k_psktrack computes them (`csdr_sincos_word`, DESIGN.md
+    4.20), F32.  No GPU needed"""
+    s, c = C.c_float(), C.c_float()
+    check(lib().csdr_sincos_word(int(w) & 0xffffffff, C.byref(s), C.byref(c)))
+    return np.float32(s.value), np.float32(c.value)
+
+
+class PskTrack(_Owner):
+    """The `csdr_psktrack_*` object: power normaliser, carrier PLL, T/2 equaliser and BPSK / QPSK decisions on `nchan` independent
+    CF32 rows of their own lengths (include/csdr.h): the part of symTracker behind the symbol synchroniser."""
+    _block = "psktrack"
+
+    def __init__(self, bits, sps=1, phase=0, eq_len=0, eq_mu=0.05, eq_mode=CSDR_PSKTRACK_EQ_DD, eq_delay=200, pll_bw=9e-4,
+                 agc_bw=0.02, nchan=1, max_samples=1 << 16):
+        self._h = _new_handle("psktrack", int(bits), int(sps), int(phase), int(eq_len), float(eq_mu), int(eq_mode), int(eq_delay),
+                              float(pll_bw), float(agc_bw), int(nchan), int(max_samples), create="new")
+        self.bits, self.sps, self.eq_len, self.nchan = int(bits), int(sps), int(eq_len), int(nchan)
+
+    def restart(self):
+        """back to the state right after the constructor"""
+        self._call("restart")
+
+    def state(self, chan=0):
+        """(theta, freq, p, symbols so far, weights complex64 [eq_len]) of row `chan`; theta and freq are uint32 phase words"""
+        th, fr, n, p = C.c_uint32(), C.c_uint32(), C.c_uint32(), C.c_float()
+        w = np.zeros(self.eq_len, dtype=np.complex64)
+        self._call("get_state", chan, C.byref(th), C.byref(fr), C.byref(p), C.byref(n), _ptr(w))
+        return th.value, fr.value, np.float32(p.value), n.value, w
+
+    def design(self):
+        """(alpha, beta, eq_len, LDS bytes per workgroup)"""
+        a, b, L, lds = C.c_float(), C.c_float(), C.c_uint32(), C.c_uint32()
+        self._call("get_design", C.byref(a), C.byref(b), C.byref(L), C.byref(lds))
+        return np.float32(a.value), np.float32(b.value), L.value, lds.value
+
+    def _marshal(self, rows):
+        """a list of nchan rows of their own lengths -> (x [nchan][n] zero-padded, counts [nchan]); an array -> (it, None)"""
+        if not isinstance(rows, (list, tuple)):
+            return rows, None
+        if len(rows) != self.nchan:
+            raise CsdrError(_lib.ERR_INVALID, f"psktrack: a chunk of {len(rows)} rows, not {self.nchan}")
+        rows = [np.asarray(r, dtype=np.complex64).reshape(-1) for r in rows]
+        nx = np.array([r.size for r in rows], dtype=np.uint32)
+        x = np.zeros((self.nchan, int(nx.max())), dtype=np.complex64)
+        for c, r in enumerate(rows):
+            x[c, :r.size] = r
+        return x, nx
+
+    def process_rows(self, rows, symbols=False):
+        """a list of nchan CF32 rows (lengths may differ), or [nchan][n] (or [n]) -> (y complex64 [nchan][n], counts [nchan]), with
+        symbols=True (y, sym uint32 [nchan][n], counts): row c holds counts[c] outputs"""
+        a, nx = self._marshal(rows)
+        x, n, y = _rows("psktrack", a, np.complex64, self.nchan, plane=True, strict=True)
+        sym = np.empty((self.nchan, n), dtype=np.uint32) if symbols else None
+        ny = np.zeros(self.nchan, dtype=np.uint32)
+        self._call("process", _ptr(x), n, None if nx is None else _ptr(nx), _ptr(y), None if sym is None else _ptr(sym), _ptr(ny))
+        return (y, sym, ny) if symbols else (y, ny)
+
+    def process(self, rows):
+        """-> the list of nchan arrays of soft symbols d; one array for [n]"""
+        y, ny = self.process_rows(rows)
+        return _split_rows(y, ny, np.empty((0, 0)) if isinstance(rows, (list, tuple)) else rows)
+
+    def process_device(self, d_x_ptr, n, d_nx_ptr, d_y_ptr, d_sym_ptr, d_ny_ptr, stream=0):
+        """Device-resident variant: raw device pointers (ints) for x [nchan][n] CF32, the rows' sample counts [nchan] uint32 (0:
+        every row holds n), y [nchan][n] CF32, symbols [nchan][n] uint32 (0: not wanted) and counts [nchan]; enqueues on `stream`"""
+        self._call("process_device", d_x_ptr, n, d_nx_ptr or None, d_y_ptr, d_sym_ptr or None, d_ny_ptr, stream)
+
+
+def pskTracker(bits, sps=1, phase=0, eq_len=0, eq_mu=0.05, eq_mode=CSDR_PSKTRACK_EQ_DD, eq_delay=200, pll_bw=9e-4, agc_bw=0.02,
+               nchan=1, max_samples=1 << 16):
+    """pskTracker as a Pipe from a list of nchan CF32 rows of their own lengths, as symSyncC yields them (or one
+    array [nchan][n], or [n]), to the list of per-row soft symbols (or one array for [n])"""
+    return _method_pipe(lambda: PskTrack(bits, sps, phase, eq_len, eq_mu, eq_mode, eq_delay, pll_bw, agc_bw, nchan, max_samples))
+
+
+SYMTRACK_PHASE = 0          # the output parity of csdr_symsync at k_out = 2 that is the symbol instant (DESIGN.md 4.20)
+
+
+class SymTrack:
+    """symTracker m k (Liquid.chs:158-175: symtrack_cccf_create(RRC, k, m, 0.25, BPSK)) as the composition of two blocks on `nchan`
+    rows: SymSync(k, m, npfb 16, lf_bw, k_out 2) with the RRC 0.25 banks, then PskTrack(bits 1, sps 2, eq_len 9, constant
+    modulus).  The synchroniser's rows and counts stay on the device: the second block is enqueued behind the first on one
+    stream.  Deviations: no agc_crcf in front, so the input should be near unit rms, and lf_bw 0.01."""
+
+    def __init__(self, m, k, nchan=1, max_samples=1 << 16, lf_bw=0.01, bits=1, eq_len=9, eq_mode=CSDR_PSKTRACK_EQ_CM):
+        import torch
+        self._torch = torch
+        self.nchan, self.max_n = int(nchan), int(max_samples)
+        self.sync = SymSync(k, m, 0.0, 16, nchan, max_samples, lf_bw=lf_bw, k_out=2)
+        self.track = None
+        try:
+            self.sync.set_rnyquist(CSDR_FIRFILT_RRC, 0.25)
+            self.track = PskTrack(bits, 2, SYMTRACK_PHASE, eq_len, eq_mode=eq_mode, nchan=nchan, max_samples=max_samples)
+            dev = dict(device="cuda")
+            self._mid = torch.empty(2 * self.nchan * self.max_n, dtype=torch.float32, **dev)
+            self._y = torch.empty(2 * self.nchan * self.max_n, dtype=torch.float32, **dev)
+            self._cnt = torch.empty(2 * self.nchan, dtype=torch.int32, **dev)
+        except Exception:
+            self.close()
+            raise
+
+    def process(self, x):
+        """[nchan][n] (or [n]) complex64 -> the list of nchan arrays of soft symbols; one array for [n]"""
+        torch = self._torch
+        a, n, _ = _rows("symtrack", x, np.complex64, self.nchan, plane=True)
+        if n > self.max_n:
+            raise CsdrError(_lib.ERR_SIZE, f"symtrack: {n} samples > max {self.max_n}")
+        stream = torch.cuda.current_stream().cuda_stream
+        d_x = torch.from_numpy(a.view(np.float32).reshape(-1)).cuda()
+        d_mid_n, d_ny = self._cnt[:self.nchan], self._cnt[self.nchan:]
+        self.sync.process_c_device(d_x.data_ptr(), n, self._mid.data_ptr(), d_mid_n.data_ptr(), stream)
+        self.track.process_device(self._mid.data_ptr(), n, d_mid_n.data_ptr(), self._y.data_ptr(), 0, d_ny.data_ptr(), stream)
+        ny = d_ny.cpu().numpy().astype(np.uint32)
+        y = self._y[:2 * self.nchan * n].cpu().numpy().view(np.complex64).reshape(self.nchan, n)
+        return _split_rows(y, ny, x)
+
+    def close(self):
+        for o in (self.track, self.sync):
+            if o is not None:
+                o.close()
+
+
+def symTracker(m, k, nchan=1, max_samples=1 << 16, lf_bw=0.01):
+    """symTracker m k (Liquid.chs:173-175) as a Pipe from complex64 arrays ([nchan][n], or [n]) at k samples per symbol to the
+    tracked BPSK soft symbols: a list of per-row arrays, or one array for [n]"""
+    return _method_pipe(lambda: SymTrack(m, k, nchan, max_samples, lf_bw))
+
+
 class FirHilb(_Resettable):
     """The `csdr_firhilb_*` object: firhilbf_create m As (firhilbCreate, Liquid.chs:520-525, fixes 5 and 60), a half-band Hilbert
     transform driven as a 2:1 real-to-complex decimator and a 1:2 complex-to-real interpolator on shared windows

@@ -631,6 +631,64 @@ int csdr_rowresamp_get_time(const csdr_rowresamp *h, uint64_t *t_next);
 int csdr_rowresamp_destroy(csdr_rowresamp *h);
 
 /* ------------------------------------------------------------------------ *
+ * pskTracker bits sps ..: what liquid's symtrack_cccf (symTracker m k, Liquid.chs:119-175) does behind its symbol
+ * synchroniser, on `nchan` independent CF32 rows: power normaliser, carrier PLL, T/2-spaced equaliser, BPSK / QPSK decision.
+ * symTracker m k is then csdr_symsync (k_out = 2, RRC 0.25) followed by this block with bits 1, sps 2, eq_len 9, constant
+ * modulus.  Own spec, "csdr psktrack v1" (DESIGN.md 4.20), not liquid's bit for bit.  Per input sample v of a row, in this order:
+ *   1. p += agc_bw (|v|^2 - p), p = 1 at start and kept >= 2^-100; v /= sqrt(p).  Deviation: liquid's agc_crcf (an exp / log
+ *      recurrence that cannot be restated bit for bit) is replaced by this normaliser.
+ *   2. v *= conj(e^(j theta)); theta += freq.  theta and freq are uint32 phase words, 2^32 = one turn; sine and cosine of a word
+ *      are csdr_sincos_word below.
+ *   3. With an equaliser v enters a window of eq_len samples.  At sps 2 an output is due at every second sample: when the
+ *      sample under the window's centre tap (without an equaliser: v itself) is sample number `phase` modulo 2 of the row,
+ *      counted from the row's first sample after new / restart; the count carries across calls of any size.  At an output
+ *      d = sum_i conj(w[i]) buf[i], i = 0 (oldest) .. eq_len - 1, the weights starting as a unit centre tap; without an equaliser
+ *      d = v.
+ *   4. Decision.  BPSK: bit 0 = (d.re < 0), x_hat = +-1.  QPSK: bit 0 = (d.re < 0), bit 1 = (d.im < 0), x_hat = (+-1 +-j) / sqrt 2.
+ *      The symbol number is those bits, a Gray code: 0 (+, +), 1 (-, +), 3 (-, -), 2 (+, -) around the circle.
+ *   5. e = Im(d conj(x_hat)); freq += word(pll_bw e); theta += word(sqrt(pll_bw) e) (nco_pll_step with alpha = pll_bw,
+ *      beta = sqrt(pll_bw)).  word(r) = r * f32(2^31 / pi), NaN -> 0, clamped to +-2^30, rounded to nearest (ties to even),
+ *      added modulo 2^32.
+ *   6. From output number eq_delay on: w[i] += eq_mu conj(err) buf[i] / (sum |buf|^2 + 2^-20), err = x_hat - d (decision-
+ *      directed) or d / |d| - d (constant modulus; 0 when |d| = 0).
+ *   7. y gets d, sym (unless NULL) the symbol number.
+ *   Arithmetic: f32, nothing contracted, every sum in the order of kernels_psktrack.hip; / and sqrt correctly rounded.  The
+ *     output is bit-identical for every chunking (odd sizes at sps 2 included), row count, row position and host versus device
+ *     entry; tests/psktrack_restatement.py restates it.  The 180 / 90 degree ambiguity is the caller's to resolve.
+ *   Rows have their own lengths: x is [nchan][n], nx[c] <= n the samples of row c (NULL: every row holds n); y and sym are
+ *     [nchan][n] (row stride n), row c holding ny[c] outputs.  This is what csdr_symsync_process_c_device writes, so the two
+ *     device entries chain on one stream with no synchronisation between.  On the device path a count above n is clamped to n.
+ *   Limits: bits 1 | 2; sps 1 | 2; phase 0 | 1; eq_len 0, or odd in [3, 17] with sps 2; eq_mu, pll_bw, agc_bw in [0, 1];
+ *     nchan >= 1; max_samples <= 2^28.  Anything else: CSDR_ERR_INVALID, before a device is looked for.  No GPU: CSDR_ERR_NODEV.
+ *   CSDR_ERR_SIZE: n > max_samples, or (host path) nx[c] > n.  A refused call leaves the rows untouched.  destroy(NULL) is 0,
+ *     restart(NULL) CSDR_ERR_INVALID.
+ * ------------------------------------------------------------------------ */
+#define CSDR_PSKTRACK_EQ_DD 0u           /* eq_mode: decision-directed                                      */
+#define CSDR_PSKTRACK_EQ_CM 1u           /* eq_mode: constant modulus                                       */
+#define CSDR_PSKTRACK_EQ_MU 0.05f        /* the defaults that the Pipes pass                                */
+#define CSDR_PSKTRACK_EQ_DELAY 200u      /* liquid's symtrack                                               */
+#define CSDR_PSKTRACK_PLL_BW 9e-4f       /* liquid's symtrack default bandwidth 0.001 x 0.9, as recalled    */
+#define CSDR_PSKTRACK_AGC_BW 0.02f
+typedef struct csdr_psktrack csdr_psktrack;
+/* (sin, cos) of a phase word, as the kernel computes them: octant from the top 3 bits, the 29-bit remainder (reflected in odd
+ * octants) times f32(pi 2^-31), then sin a = ((((S3 z + S2) z + S1) z) a) + a and cos a = (1 - 0.5 z) + ((((C3 z + C2) z + C1) z) z)
+ * with z = a a, in f32, each operation rounded (coefficients: psktrack_common.h).  |error| <= 2^-21.  No GPU needed */
+int csdr_sincos_word(uint32_t w, float *s, float *c);
+int csdr_psktrack_new(uint32_t bits, uint32_t sps, uint32_t phase, uint32_t eq_len, float eq_mu, uint32_t eq_mode, uint32_t eq_delay,
+                      float pll_bw, float agc_bw, uint32_t nchan, uint32_t max_samples, csdr_psktrack **out);
+int csdr_psktrack_process(csdr_psktrack *h, const float *x /* CF32 [nchan][n] */, uint32_t n, const uint32_t *nx /* [nchan] or NULL */,
+                          float *y /* CF32 [nchan][n] */, uint32_t *sym /* [nchan][n] or NULL */, uint32_t *ny /* [nchan] */);
+/* device buffers as above (d_nx, d_sym may be NULL); enqueued on `stream`, no synchronisation */
+int csdr_psktrack_process_device(csdr_psktrack *h, const void *d_x, uint32_t n, const void *d_nx, void *d_y, void *d_sym, void *d_ny,
+                                 void *stream);
+int csdr_psktrack_restart(csdr_psktrack *h);                      /* back to the state right after new                */
+/* row chan: phase and frequency words, power estimate, outputs so far (saturating), weights [eq_len] CF32; any may be NULL */
+int csdr_psktrack_get_state(csdr_psktrack *h, uint32_t chan, uint32_t *theta, uint32_t *freq, float *p, uint32_t *nsym, float *w);
+/* alpha = pll_bw and beta = sqrt(pll_bw) as f32, eq_len, the kernel's LDS bytes per workgroup; any may be NULL */
+int csdr_psktrack_get_design(const csdr_psktrack *h, float *alpha, float *beta, uint32_t *eq_len, uint32_t *lds_bytes);
+int csdr_psktrack_destroy(csdr_psktrack *h);
+
+/* ------------------------------------------------------------------------ *
  * The fused chain: everything assembleFold (apps/SoapySDR.hs:208-226) puts
  * behind `compact`:
  *     dcBlocker                                   (SoapySDR.hs:213-214)
