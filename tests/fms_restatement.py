@@ -11,7 +11,9 @@ Per stream, on the F32 MPX x (the freqdem output):
 The FIR dot products are taken in f64 and rounded once (liquid's summation order is not reproducible anyway); the output scale
 2 fc is then applied in f32, as firfilt_crcf_set_scale does.  The PLL steps through every f32 operation of nco_crcf's VCO
 (oracle/csdr_oracle.c's constrain and float-phase phasor, restated here vectorised over streams and checked against the
-oracle's in tests/test_fmstereo_cpu.py) and GHC's class-default atan2.
+oracle's in tests/test_fmstereo_cpu.py) and GHC's class-default atan2.  `sums="f32"` is a second rounding of the same decoder
+(FIR sums accumulated in f32, the PLL's cos / sin from libm's cosf / sinf): tests/fms_cases.py takes the GPU tests' bounds
+from its distance to the default.
 """
 import ctypes as C
 import math
@@ -121,6 +123,15 @@ def _sin(ph):
     return np.sin(ph.astype(np.float64)).astype(np.float32)
 
 
+def _cosf(ph):
+    """libm's cosf, element by element (the rounding variant, sums="f32")"""
+    return np.array([_libm.cosf(float(v)) for v in np.ravel(ph)], dtype=np.float32).reshape(np.shape(ph))
+
+
+def _sinf(ph):
+    return np.array([_libm.sinf(float(v)) for v in np.ravel(ph)], dtype=np.float32).reshape(np.shape(ph))
+
+
 def hs_atan2(y, x):
     """GHC's class-default atan2 on Float, element-wise: atan (y / x) plus the quadrant fixes (not atan2f)"""
     y = np.asarray(y, dtype=np.float32).copy()
@@ -138,23 +149,39 @@ def hs_atan2(y, x):
 
 
 # ---- the decoder -------------------------------------------------------------------------------------------------------
-def _fir(h, x, scale):
-    y = np.convolve(x.astype(np.float64), h.astype(np.float64))[: x.size].astype(np.float32)
+def _check_sums(sums):
+    if sums not in ("f64", "f32"):
+        raise ValueError(f"sums: {sums!r} is neither 'f64' nor 'f32'")
+    return sums == "f32"
+
+
+def _fir(h, x, scale, sums="f64"):
+    """sums="f64": the dot products in f64, rounded once; "f32": accumulated in f32 tap by tap, every product and sum rounded"""
+    if _check_sums(sums):
+        h, x = np.asarray(h, np.float32), np.ascontiguousarray(x, dtype=np.float32)
+        xp = np.concatenate([np.zeros(h.size - 1, np.float32), x])
+        y = np.zeros(x.size, np.float32)
+        for k in range(h.size):
+            y = y + h[k] * xp[h.size - 1 - k: h.size - 1 - k + x.size]
+    else:
+        y = np.convolve(x.astype(np.float64), h.astype(np.float64))[: x.size].astype(np.float32)
     return y * scale
 
 
-def front(x, P):
+def front(x, P, sums="f64"):
     """x [n] F32 -> p [n] CF32 (pilot branch), s [n] (wire), lpr [n]"""
     x = np.asarray(x, dtype=np.float32)
     xm = O.Nco(P["ncoF"]).mix_down(x.astype(np.complex64))
-    z = (_fir(P["hp"], xm.real, P["sp"]) + 1j * _fir(P["hp"], xm.imag, P["sp"])).astype(np.complex64)
+    z = (_fir(P["hp"], xm.real, P["sp"], sums) + 1j * _fir(P["hp"], xm.imag, P["sp"], sums)).astype(np.complex64)
     p = O.Nco(P["ncoF"]).mix_up(z)
     s = np.concatenate([np.zeros(P["d"], np.float32), x])[: x.size]
-    return p, s, _fir(P["ha"], s, P["sa"])
+    return p, s, _fir(P["ha"], s, P["sa"], sums)
 
 
-def pll(p, s, P, theta=None, dtheta=None):
-    """pllStep over [R][n] (or [n]) streams -> u, and the end words (theta, d_theta) per stream"""
+def pll(p, s, P, theta=None, dtheta=None, sums="f64"):
+    """pllStep over [R][n] (or [n]) streams -> u, and the end words (theta, d_theta) per stream; sums="f32" takes every cos and
+    sin from libm's cosf / sinf instead of f64 rounded once"""
+    cos_, sin_ = (_cosf, _sinf) if _check_sums(sums) else (_cos, _sin)
     p, s = np.atleast_2d(p), np.atleast_2d(s).astype(np.float32)
     R, n = p.shape
     th = np.zeros(R, np.uint32) if theta is None else np.asarray(theta, np.uint32).copy()
@@ -165,7 +192,7 @@ def pll(p, s, P, theta=None, dtheta=None):
     for t in range(n):
         phi = phase(th)
         th_ss = constrain(f32(2) * phi)                       # ncoSS set_phase (2 phi)
-        cs, sn = _cos(phi), _sin(phi)                         # ncoPE cexpf
+        cs, sn = cos_(phi), sin_(phi)                         # ncoPE cexpf
         nsn = -sn
         re = pr[:, t] * cs - pi[:, t] * nsn                   # p * conjugate c  (Haskell's Complex (*))
         im = pr[:, t] * nsn + pi[:, t] * cs
@@ -173,12 +200,12 @@ def pll(p, s, P, theta=None, dtheta=None):
         dth = dth + constrain(e * alpha)                      # nco_crcf_pll_step: adjust_frequency, adjust_phase
         th = th + constrain(e * beta)
         th = th + dth                                         # nco_crcf_step
-        u[:, t] = s[:, t] * _cos(phase(th_ss))                # Re mix_block_down ncoSS (s + 0j)
+        u[:, t] = s[:, t] * cos_(phase(th_ss))                # Re mix_block_down ncoSS (s + 0j)
     return u, th, dth
 
 
-def back(u, lpr, P):
-    lmr = f32(2) * _fir(P["ha"], u, P["sa"])
+def back(u, lpr, P, sums="f64"):
+    lmr = f32(2) * _fir(P["ha"], u, P["sa"], sums)
     return lpr + lmr, lpr - lmr
 
 
@@ -193,38 +220,42 @@ def decimate_calls(y, calls, decim):
     return np.concatenate(out) if out else np.zeros(0, np.float32)
 
 
-def decode(x, q, decim=4, calls=None):
+def _tail(L, R, P, calls):
+    """L, R -> O.Butter2 -> the per-call decimator -> interleaved L, R, and the de-emphasised planes"""
+    L = O.Butter2(P["deemph_fc"]).execute_block(L)
+    R = O.Butter2(P["deemph_fc"]).execute_block(R)
+    Ld, Rd = decimate_calls(L, calls, P["decim"]), decimate_calls(R, calls, P["decim"])
+    lr = np.empty(2 * Ld.size, np.float32)
+    lr[0::2], lr[1::2] = Ld, Rd
+    return lr, L, R
+
+
+def decode(x, q, decim=4, calls=None, sums="f64"):
     """one stream: MPX x -> interleaved L, R as the library returns them over `calls` (sample counts per call; default one
-    call), plus the PLL end words and the intermediate planes"""
+    call), plus the PLL end words and the intermediate planes.  sums="f32" is the rounding variant: the FIR sums accumulated in
+    f32 and the PLL's cos / sin from libm's cosf / sinf.  It is no better a reference than the default; the distance between the
+    two measures how far the decoder's output moves under rounding alone (tests/fms_cases.py)"""
     P = design(q, decim)
     x = np.asarray(x, dtype=np.float32)
     calls = [x.size] if calls is None else list(calls)
     assert sum(calls) == x.size
-    p, s, lpr = front(x, P)
-    u, th, dth = pll(p, s, P)
-    L, R = back(u[0], lpr, P)
-    L = O.Butter2(P["deemph_fc"]).execute_block(L)
-    R = O.Butter2(P["deemph_fc"]).execute_block(R)
-    Ld, Rd = decimate_calls(L, calls, decim), decimate_calls(R, calls, decim)
-    lr = np.empty(2 * Ld.size, np.float32)
-    lr[0::2], lr[1::2] = Ld, Rd
+    p, s, lpr = front(x, P, sums)
+    u, th, dth = pll(p, s, P, sums=sums)
+    L, R = back(u[0], lpr, P, sums)
+    lr, L, R = _tail(L, R, P, calls)
     return lr, dict(theta=int(th[0]), dtheta=int(dth[0]), L=L, R=R, u=u[0], p=p, lpr=lpr, P=P)
 
 
-def decode_rows(X, q, decim=4):
-    """[R][n] streams in one call each (the PLL vectorised over the rows) -> [R][2 (n // decim)]"""
+def decode_rows(X, q, decim=4, calls=None, sums="f64"):
+    """[R][n] streams fed in `calls` (default one call; the PLL vectorised over the rows) -> [R][2 sum(c // decim for c in calls)],
+    and the PLL end words per row.  Each row is decode's of that row, bit for bit"""
     P = design(q, decim)
     X = np.asarray(X, dtype=np.float32)
-    fr = [front(x, P) for x in X]
-    u, th, dth = pll(np.stack([f[0] for f in fr]), np.stack([f[1] for f in fr]), P)
-    out = []
-    for r in range(X.shape[0]):
-        L, R = back(u[r], fr[r][2], P)
-        L = O.FirDecim(decim).execute_block(O.Butter2(P["deemph_fc"]).execute_block(L)[: X.shape[1] // decim * decim])
-        R = O.FirDecim(decim).execute_block(O.Butter2(P["deemph_fc"]).execute_block(R)[: X.shape[1] // decim * decim])
-        lr = np.empty(2 * L.size, np.float32)
-        lr[0::2], lr[1::2] = L, R
-        out.append(lr)
+    calls = [X.shape[1]] if calls is None else list(calls)
+    assert sum(calls) == X.shape[1]
+    fr = [front(x, P, sums) for x in X]
+    u, th, dth = pll(np.stack([f[0] for f in fr]), np.stack([f[1] for f in fr]), P, sums=sums)
+    out = [_tail(*back(u[r], fr[r][2], P, sums), P, calls)[0] for r in range(X.shape[0])]
     return np.stack(out), th, dth
 
 

@@ -7,6 +7,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import fms_cases as K
 import fms_restatement as F
 import oracle_lib as O
 from host_exe import host_exe
@@ -47,6 +48,98 @@ def test_taps_and_delay(q, N, d):
     assert (P["N"], P["d"]) == (N, d)
     assert abs(P["group_delay"] - (N - 1) / 2) < 1e-3
     assert P["d_nco"] == O.nco_constrain(np.float32(19000.0 * 2 * np.pi / q))
+
+
+@pytest.mark.parametrize("q", sorted(K.DESIGNS))
+def test_taps_and_delay_at_the_rates_of_the_shape_tests(q):
+    """odd N (176.4 and 250 kHz), the limits of quad_rate, and the even N whose x.5 group delay f32 rounding decides: 240 kHz lands
+    below 88.5, 256 kHz above 94.5.  tests/test_fmstereo_shapes_gpu.py holds the handle to the same literals"""
+    P = F.design(q)
+    print(f"{q:g} Hz: N {P['N']}, group delay {P['group_delay']:.6f} -> d {P['d']}")
+    assert (P["N"], P["d"]) == K.DESIGNS[q]
+    assert abs(P["group_delay"] - (P["N"] - 1) / 2) < 1e-3
+
+
+@pytest.mark.parametrize("sums", ["f64", "f32"])
+def test_decode_rows_over_calls_is_decode_of_each_row(sums):
+    """decode_rows(calls=...) decimates per call as decode(calls=...) does; each row bit for bit, the PLL words too"""
+    q, decim, calls = 40e3, 3, [7, 2, 0, 300, 1, 290]
+    X = np.stack([np.float32(0.3 + r) * F.stereo_mpx(sum(calls), q, fl=400.0 + 300 * r, seed=70 + r) for r in range(3)])
+    X[1] = np.float32(-0.0)
+    got, th, dth = F.decode_rows(X, q, decim, calls=calls, sums=sums)
+    assert got.shape == (3, 2 * sum(c // decim for c in calls))
+    for r in range(3):
+        want, st = F.decode(X[r], q, decim, calls=calls, sums=sums)
+        assert np.array_equal(got[r].view(np.uint32), want.view(np.uint32)), r
+        assert (int(th[r]), int(dth[r])) == (st["theta"], st["dtheta"]), r
+    one, _, _ = F.decode_rows(X, q, decim, sums=sums)          # the default is one call
+    assert one.shape == (3, 2 * (sum(calls) // decim))
+    assert np.array_equal(one[0], F.decode(X[0], q, decim, sums=sums)[0])
+
+
+def test_rounding_variant_of_the_restatement():
+    """sums="f32" (FIR sums accumulated in f32, cosf / sinf from libm) is another rounding of the same decoder: the default is
+    unchanged by the argument, the variant differs from it, by rounding noise only"""
+    q, n = 40e3, 2048
+    x = F.stereo_mpx(n, q, seed=5)
+    base, st = F.decode(x, q, 2)
+    same, _ = F.decode(x, q, 2, sums="f64")
+    alt, st_alt = F.decode(x, q, 2, sums="f32")
+    assert np.array_equal(base, same)
+    assert not np.array_equal(base, alt)
+    (l1, l2), (r1, r2) = K.stats(alt, base)
+    assert max(l1, r1) < 1e-5 and max(l2, r2) < 1e-4
+    assert abs(st["dtheta"] - st_alt["dtheta"]) / 2 ** 32 * q < 0.01
+    h, v = F.firdes_kaiser(30, 0.02), np.random.default_rng(0).standard_normal(100).astype(np.float32)
+    np.testing.assert_allclose(F._fir(h, v, np.float32(1), "f32"), F._fir(h, v, np.float32(1)), atol=1e-6)
+    with pytest.raises(ValueError):
+        F.decode(x, q, 2, sums="f16")
+
+
+def _assert_caps(tag, pair, bounds):
+    for ch, ((t1, t2), (b1, b2)) in enumerate(zip(pair, bounds)):
+        print(f"{tag} {'LR'[ch]}: pair T1 {t1:.2e} T2 {t2:.2e} -> bound1 {b1:.2e} bound2 {b2:.2e}")
+        assert K.MARGIN * t1 <= K.T1_CAP and K.MARGIN * t2 <= K.T2_CAP, (tag, t1, t2)
+        assert 1e-5 <= b1 <= K.T1_CAP and 4e-5 <= b2 <= K.T2_CAP
+
+
+@pytest.mark.parametrize("case", K.ONE_CALL, ids=[f"{q:g}-{decim}" for q, decim, _, _ in K.ONE_CALL])
+def test_reference_pair_is_within_the_caps_one_call(case):
+    """the bounds of tests/test_fmstereo_shapes_gpu.py come from the restatement's own rounding; for its inputs they stay
+    below 2e-4 (T1) and 2e-3 (T2), far below what one wrong sample does (tests/fms_cases.py)"""
+    x, ref = K.one_call(*case)
+    assert ref.want.size == 2 * (x.size // case[1]) and np.all(np.isfinite(ref.want))
+    _assert_caps(f"{case[0]:g} Hz decim {case[1]}", ref.pair, ref.bounds)
+
+
+def test_reference_pair_is_within_the_caps_seams():
+    x, calls, ref = K.seams()
+    need = {1, 4, 5, 6, 15, 16, 17, 87, 88, 89, 176, 177, 178, 255, 256, 257, 264, 265, 266, 0}
+    big = calls.index(max(calls))
+    assert sum(calls) == x.size and need <= set(calls[:big]) and need <= set(calls[big + 1:]) and 2500 <= calls[big] <= 3500
+    assert ref.want.size == 2 * sum(c // K.SEAM_DECIM for c in calls)
+    _assert_caps("240 kHz decim 5 seams", ref.pair, ref.bounds)
+
+
+def test_reference_pair_is_within_the_caps_67_rows():
+    X, calls, ref = K.rows()
+    assert X.shape == (K.ROWS_C, sum(calls)) and not np.any(X[1]) and not np.any(X[2])
+    assert not np.any(np.signbit(X[1])) and np.all(np.signbit(X[2]))
+    for r in range(K.ROWS_C):
+        if r in K.ROWS_SILENT:
+            assert not np.any(ref.want[r])                     # a silent row decodes to zeros (of either sign)
+        else:
+            _assert_caps(f"row {r}", ref.pair[r], ref.bounds[r])
+
+
+@pytest.mark.parametrize("q", [40e3, 250e3])
+def test_chunk_calls_hold_every_seam(q):
+    N, d = K.DESIGNS[q]
+    Hx = N - 1 + d
+    calls = K.chunk_calls(q)
+    need = {1, 2, 3, 15, 16, 17, d - 1, d, d + 1, N - 2, N - 1, N, Hx - 1, Hx, Hx + 1, 255, 256, 257, 0}
+    big = calls.index(max(calls))
+    assert sum(calls) == 8192 and need <= set(calls[:big]) and need <= set(calls[big + 1:]) and calls[big] > 3000
 
 
 @functools.lru_cache(maxsize=None)

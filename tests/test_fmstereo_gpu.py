@@ -114,8 +114,8 @@ def test_mono_broadcast_has_no_difference_signal():
     assert db <= -30
 
 
-def _replay(src, n, chunksize, samplerate, bandwidth):
-    """the restatement's DeFMS 4: per source chunk [-> O.MsResamp] (takeNArr n trims the prepared stream to n samples) ->
+def _replay(src, n, chunksize, samplerate, bandwidth, decim=4):
+    """the restatement's DeFMS decim: per source chunk [-> O.MsResamp] (takeNArr n trims the prepared stream to n samples) ->
     O.FreqDem(0.8), then the decoder over the calls' lengths"""
     x = np.fromfile(src, dtype=np.complex64)
     rs = O.MsResamp(np.float32(bandwidth / samplerate)) if bandwidth else None
@@ -132,33 +132,36 @@ def _replay(src, n, chunksize, samplerate, bandwidth):
         if seen == n:
             break
     q = bandwidth or samplerate
-    return F.decode(np.concatenate(mpx), q, 4, calls=calls)[0]
+    return F.decode(np.concatenate(mpx), q, decim, calls=calls)[0]
 
 
-@pytest.mark.parametrize("bandwidth", [0.0, 192e3])
-def test_sdr_process_fms_matches_replay_and_cpp_host(tmp_path, monkeypatch, bandwidth):
+@pytest.mark.parametrize("bandwidth,q,decim", [pytest.param(0.0, Q, 4, id="0.0"), pytest.param(192e3, Q, 4, id="192000.0"),
+                                               pytest.param(0.0, 240e3, 5, id="240k-decim5")])
+def test_sdr_process_fms_matches_replay_and_cpp_host(tmp_path, monkeypatch, bandwidth, q, decim):
+    """q: the decoder's rate, behind the resampler where there is one.  240 kHz with decim 5 (N = 178, d = 88): 1024-sample calls
+    are no multiple of 5, and the sink's rate is still 48 kHz"""
     monkeypatch.setenv("CSDR_QUIET", "1")
     from composable_sdr_amd.app import sdr_process
-    fs = 2 * Q if bandwidth else Q
+    fs = 2 * q if bandwidth else q
     n = 65536                                                  # samples after the resampler (takeNArr follows it)
     x, _ = F.stereo_broadcast((2 if bandwidth else 1) * n + 5000, fs, kf=0.8, seed=21)
     src = tmp_path / "in.cf32"
     x.tofile(src)
-    py = sdr_process(str(src), channels=1, demod="fms", decim=4, numsamples=n, outname=str(tmp_path / "py"), chunksize=1024,
+    py = sdr_process(str(src), channels=1, demod="fms", decim=decim, numsamples=n, outname=str(tmp_path / "py"), chunksize=1024,
                      samplerate=fs, bandwidth=bandwidth, audio="AU")
     a = open(py[0], "rb").read()
     hdr = struct.unpack(">4sIIIII", a[:24])
     got = np.frombuffer(a[24:], dtype=">f4").astype(np.float32)
     assert hdr == (b".snd", 24, 4 * got.size, 6, 48000, 2)
-    want = _replay(src, n, 1024, fs, bandwidth)
+    want = _replay(src, n, 1024, fs, bandwidth, decim)
     assert got.shape == want.shape
     # freqdem branch cuts land differently on the two sides (a flip is smeared over ~N samples by the FIRs): robust comparison
     d = np.abs(got.astype(np.float64) - want)
     scale = np.abs(want).max()
-    _report(f"sdr_process DeFMS 4 -b {bandwidth}", got, want)
+    _report(f"sdr_process DeFMS {decim} -s {fs:g} -b {bandwidth}", got, want)
     assert np.median(d) < 2e-5 * scale and np.quantile(d, 0.99) < 2e-3 * scale
     exe = host_exe("soapy_sdr_file")
-    args = [exe, "--filename", str(src), "-n", str(n), "-c", "1", "--demod", "DeFMS", "4", "-s", str(fs), "--audio", "AU",
+    args = [exe, "--filename", str(src), "-n", str(n), "-c", "1", "--demod", "DeFMS", str(decim), "-s", str(fs), "--audio", "AU",
             "-o", str(tmp_path / "cc")]
     if bandwidth:
         args += ["-b", str(bandwidth)]
